@@ -13,6 +13,10 @@ largest-degree vertex and 64 seeded non-isolated vertices.
   cpu_baseline = the oracle's serial deque BFS (port of the reference's SimpleReferenceBfs) on the host
                  cores of this box, on a bounded sample of the same graph
 
+A plain run sets up, warms up, times the K steps and prints the line (value, enact_mteps, ms_per_step, ...).  roofline,
+topdown, cpu_baseline, parity_vs_oracle and the 'secondary' legs take runs of their own and are filled in only with --full.
+--dump-outputs DIR writes what the last timed step computed (BFS: labels, label_counts) as DIR/<name>.npy.
+
 N > 1 (launched by torch.distributed.run): the same graph vertex-partitioned over the ranks
 (owner = v mod N), per-level halo exchange over RCCL (gunrockinst_amd/multi_gpu.py); "scaling": "strong".
 """
@@ -54,11 +58,20 @@ def parse():
                     help="rmat = mirrored R-MAT of --scale (default; for --primitive sssp the default is lj); lj = the DIRECTED R-MAT stand-in for soc-LiveJournal1 "
                          "(BASELINE.json config 3: the file is not available offline): 2^22 vertex ids, ~69 M directed edges, not mirrored")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="headline leg only: skip the compact legs for BASELINE.json configs 2, 3 (stand-in) and 4 that the default "
+                    help="headline leg only: skip the compact legs for BASELINE.json configs 2, 3 (stand-in) and 4 that the --full "
                          "N=1 run appends under 'secondary'")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: CPU baselines and oracle parity, the top-down "
+                         "leg, the instrumented roofline pass with the profile tables and the 'secondary' legs (each can still be "
+                         "dropped with its --no-* / --skip-* switch).  Off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64; arrays "
+                         "longer than %d elements as a fixed, seeded sample)" % DUMP_LIMIT)
     a = ap.parse_args()
     if a.graph is None:
         a.graph = "lj" if a.primitive == "sssp" else "rmat"
+    if not a.full:
+        a.no_cpu_baseline, a.skip_topdown_leg, a.no_secondary = True, True, True
     return a
 
 
@@ -67,6 +80,23 @@ def parse():
 # about the same number of directed edges.
 LJ_SCALE = 22
 LJ_PAIRS = 73_400_000
+
+# --dump-outputs: elements kept per array; a longer output is written at a fixed, seeded sample of its indices
+DUMP_LIMIT = 1 << 22
+DUMP_SEED = 0x6475
+
+
+def dump_outputs(dirpath, arrays):
+    """arrays: name -> torch tensor or numpy array.  Written as <dirpath>/<name>.npy: integers as float64 (exact), floats as
+    float32; an array longer than DUMP_LIMIT keeps the elements at DUMP_LIMIT sorted indices drawn with DUMP_SEED (the same
+    indices for every array of that length), so two runs with the same arguments compare element for element."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    for name, a in arrays.items():
+        a = (a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)).reshape(-1)
+        if a.size > DUMP_LIMIT:
+            a = a[np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, DUMP_LIMIT, replace=False))]
+        np.save(os.path.join(dirpath, name + ".npy"), a.astype(np.float32 if a.dtype.kind == "f" else np.float64))
 
 
 def make_graph(args, devgraph):
@@ -106,6 +136,8 @@ def main():
     torch.cuda.set_device(local_rank)
     # GUNROCK_FORCE_PARTITIONED=1: run the vertex-partitioned level loop even at world 1 (measures its per-level overhead)
     partitioned = world > 1 or os.environ.get("GUNROCK_FORCE_PARTITIONED") == "1"
+    if partitioned and args.dump_outputs:
+        raise SystemExit("--dump-outputs: not available for the vertex-partitioned loop (--gpus N > 1, GUNROCK_FORCE_PARTITIONED=1)")
     if partitioned:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("MASTER_PORT", "29533")
@@ -289,6 +321,8 @@ def bench_single(args, torch, ga, devgraph, device_index):
         enact_ms += per_step_ms[-1]
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
+    if args.dump_outputs:   # the last timed search's depth labels (-1 = unreached) and how many vertices hold each label
+        dump_outputs(args.dump_outputs, {"labels": labels_t, "label_counts": torch.bincount((labels_t + 1).long())})
 
     # per-source visited counts (untimed): rerun each distinct source used, read labels on the device
     used = [sources[k % len(sources)] for k in range(args.steps)]
@@ -316,101 +350,104 @@ def bench_single(args, torch, ga, devgraph, device_index):
         td_nodes += per_src[s_k][0] if s_k in per_src else 0
     topdown_mteps = td_edges / (td_ms * 1e3) if td_ms > 0 and td_edges else None
 
-    # instrumented pass (separate enactor instantiation): HIP events around every operator launch, on the launch stream
-    iprob = ga.BfsProblem(False, True, instrument=True, device=device_index)
-    iprob.init_device(n, m, ro.data_ptr(), ci.data_ptr())
-    if symmetric:
-        iprob.set_inverse_graph()
-    else:
-        iprob.auto_inverse()
-    iprob.set_tuning(args.alpha, args.beta, args.lite_factor, args.tail_edge_limit)
-    iprob.set_head_pass(args.head_pass_min, args.head_pass_max)
-    for kv in args.opt:
-        iprob.set_option(kv.split("=")[0], float(kv.split("=")[1]))
-    names = {6: "BottomUpKernel heads-only + count-only advance + FreshToBitmapKernel", 0: "advance::LoadBalancedKernel (top-down)", 1: "advance::BottomUpAutoKernel (chain of bottom-up sweeps, dense / compacting chosen on the device)",
-             2: "BitmapToQueueKernel + PersistentLevelsKernel (+ EmitLabelsKernel queued behind it)", 3: "advance::TailLevelsKernel",
-             4: "LoadBalancedKernel count-only + FreshToBitmapKernel", 5: "advance::PersistentLevelsKernel",
-             7: "BinnedExpandKernel + BinnedApplyKernel + FreshToBitmapKernel + BitmapToQueueKernel (binned top-down)",
-             8: "advance::TwcLevelsKernel", 9: "EmitLabelsKernel (when not already queued behind the closing launch)"}
-    by_kind = {}
-    kernel_ms, launches, balg = 0.0, 0, 0.0
-    for k in range(min(args.steps, len(sources))):
-        s = sources[k % len(sources)]
-        iprob.reset(s)
-        iprob.enact(s, traversal_mode=mode)
-        for rec in iprob.level_trace():
-            agg = by_kind.setdefault(rec["kind"], [0, 0.0])
-            agg[0] += 1
-            agg[1] += rec["ms"]
-            kernel_ms += rec["ms"]
-            launches += 1
-        if s in per_src:
-            nv, ev, _ = per_src[s]
+    # --full: the roofline figures from an instrumented pass (and the top-down leg's, when it ran)
+    roofline, topdown = None, None
+    if args.full:
+        # instrumented pass (separate enactor instantiation): HIP events around every operator launch, on the launch stream
+        iprob = ga.BfsProblem(False, True, instrument=True, device=device_index)
+        iprob.init_device(n, m, ro.data_ptr(), ci.data_ptr())
+        if symmetric:
+            iprob.set_inverse_graph()
         else:
-            il, _ = iprob.device_results()
-            vis = devgraph.as_tensor(il, n) > -1
-            nv, ev = int(vis.sum()), int(deg[vis].sum())
-        balg += 4.0 * ev + 20.0 * nv
-    dom = max(by_kind, key=lambda kd: by_kind[kd][1]) if by_kind else 0
-    n_inst = max(min(args.steps, len(sources)), 1)
-    # THE roofline figure (BASELINE.md section 4 / SURVEY 8(d)): algorithmic bytes of the searches / their Enact time
-    balg_timed = 4.0 * edges_total + 20.0 * nodes_total
-    achieved = balg_timed / (enact_ms * 1e-3) / 1e9 if enact_ms > 0 else 0.0
-    kernel_only = balg / (kernel_ms * 1e-3) / 1e9 if kernel_ms > 0 else 0.0   # same bytes / summed operator-kernel event time
-    whole_step = balg_timed / wall / 1e9
-    prof = profile_tables() if (mode == 2 and args.graph == "rmat" and args.scale == 24 and args.edge_factor == 8 and args.seed == 0x6772) else None
-    fresh = bool(prof) and not prof.get("stale")
-    kernel_s_per_search = (kernel_ms / n_inst) * 1e-3
-    phys = None
-    if fresh and kernel_s_per_search > 0:
-        phys = {"raw": round(prof["per_search"]["bytes"] / kernel_s_per_search / 8e12, 4),
-                "upper": round(prof["per_search"]["upper"] / kernel_s_per_search / 8e12, 4)}
-    roofline = {"bound": "hbm", "achieved": round(achieved, 2), "peak": 8000.0, "unit": "GB/s",
-                "frac": round(achieved / 8000.0, 5),
-                "definition": "algorithmic bytes (4*edges_visited + 20*nodes_visited) of the timed searches / their summed Enact "
-                              "time / 8 TB/s; a direction-optimizing search does not read most of those edges, so this is NOT "
-                              "the physical HBM rate (see hbm_frac_physical)",
-                "frac_kernel_only": round(kernel_only / 8000.0, 5),
-                "frac_whole_step": round(whole_step / 8000.0, 5),
-                "traffic": prof["per_search"]["bytes"] if fresh else None,
-                "traffic_detail": prof["per_search"] if fresh else (prof if prof else None),
-                "hbm_frac_physical": phys,
-                "kernel": names.get(dom, str(dom)),
-                "kernel_share_of_device_time": round(by_kind[dom][1] / kernel_ms, 4) if kernel_ms else None,
-                "kernel_launches": by_kind[dom][0] if by_kind else 0,
-                "kernel_avg_launch_ms": round(by_kind[dom][1] / max(by_kind[dom][0], 1), 5) if by_kind else None,
-                "all_launches": launches, "all_kernel_ms_per_bfs": round(kernel_ms / n_inst, 5),
-                "alg_bytes_per_bfs": round(balg / n_inst, 1),
-                "by_kernel_ms": {names.get(kd, str(kd)): round(v[1], 4) for kd, v in sorted(by_kind.items())},
-                "per_kernel": prof["per_kernel"] if fresh else None,
-                "profile_source": prof.get("source") if fresh else None}
-    # the top-down leg's own roofline object: same B_alg definition over its searches / their Enact time; dominant kernel and its
-    # average launch from an instrumented traversal_mode-0 pass over the same sources
-    topdown = None
-    if td_steps and td_ms > 0:
-        td_kind, td_kernel_ms = {}, 0.0
-        for k in range(td_steps):
-            s_k = sources[k % len(sources)]
-            iprob.reset(s_k)
-            iprob.enact(s_k, traversal_mode=0)
+            iprob.auto_inverse()
+        iprob.set_tuning(args.alpha, args.beta, args.lite_factor, args.tail_edge_limit)
+        iprob.set_head_pass(args.head_pass_min, args.head_pass_max)
+        for kv in args.opt:
+            iprob.set_option(kv.split("=")[0], float(kv.split("=")[1]))
+        names = {6: "BottomUpKernel heads-only + count-only advance + FreshToBitmapKernel", 0: "advance::LoadBalancedKernel (top-down)", 1: "advance::BottomUpAutoKernel (chain of bottom-up sweeps, dense / compacting chosen on the device)",
+                 2: "BitmapToQueueKernel + PersistentLevelsKernel (+ EmitLabelsKernel queued behind it)", 3: "advance::TailLevelsKernel",
+                 4: "LoadBalancedKernel count-only + FreshToBitmapKernel", 5: "advance::PersistentLevelsKernel",
+                 7: "BinnedExpandKernel + BinnedApplyKernel + FreshToBitmapKernel + BitmapToQueueKernel (binned top-down)",
+                 8: "advance::TwcLevelsKernel", 9: "EmitLabelsKernel (when not already queued behind the closing launch)"}
+        by_kind = {}
+        kernel_ms, launches, balg = 0.0, 0, 0.0
+        for k in range(min(args.steps, len(sources))):
+            s = sources[k % len(sources)]
+            iprob.reset(s)
+            iprob.enact(s, traversal_mode=mode)
             for rec in iprob.level_trace():
-                agg = td_kind.setdefault(rec["kind"], [0, 0.0])
+                agg = by_kind.setdefault(rec["kind"], [0, 0.0])
                 agg[0] += 1
                 agg[1] += rec["ms"]
-                td_kernel_ms += rec["ms"]
-        td_dom = max(td_kind, key=lambda kd: td_kind[kd][1]) if td_kind else 0
-        td_balg = 4.0 * td_edges + 20.0 * td_nodes
-        td_achieved = td_balg / (td_ms * 1e-3) / 1e9
-        topdown = {"workload": "the first %d sources, traversal_mode 0 (load-balanced top-down advance only; reference default mode)" % td_steps,
-                   "enact_ms_per_step": round(td_ms / td_steps, 4), "enact_mteps": round(topdown_mteps, 2),
-                   "bound": "hbm", "achieved": round(td_achieved, 2), "peak": 8000.0, "unit": "GB/s", "frac": round(td_achieved / 8000.0, 5),
-                   "kernel": names.get(td_dom, str(td_dom)),
-                   "kernel_share_of_device_time": round(td_kind[td_dom][1] / td_kernel_ms, 4) if td_kernel_ms else None,
-                   "kernel_launches": td_kind[td_dom][0] if td_kind else 0,
-                   "kernel_avg_launch_ms": round(td_kind[td_dom][1] / max(td_kind[td_dom][0], 1), 5) if td_kind else None,
-                   "all_kernel_ms_per_bfs": round(td_kernel_ms / td_steps, 5),
-                   "by_kernel_ms": {names.get(kd, str(kd)): round(v[1], 4) for kd, v in sorted(td_kind.items())}}
-    iprob.close()
+                kernel_ms += rec["ms"]
+                launches += 1
+            if s in per_src:
+                nv, ev, _ = per_src[s]
+            else:
+                il, _ = iprob.device_results()
+                vis = devgraph.as_tensor(il, n) > -1
+                nv, ev = int(vis.sum()), int(deg[vis].sum())
+            balg += 4.0 * ev + 20.0 * nv
+        dom = max(by_kind, key=lambda kd: by_kind[kd][1]) if by_kind else 0
+        n_inst = max(min(args.steps, len(sources)), 1)
+        # THE roofline figure (BASELINE.md section 4 / SURVEY 8(d)): algorithmic bytes of the searches / their Enact time
+        balg_timed = 4.0 * edges_total + 20.0 * nodes_total
+        achieved = balg_timed / (enact_ms * 1e-3) / 1e9 if enact_ms > 0 else 0.0
+        kernel_only = balg / (kernel_ms * 1e-3) / 1e9 if kernel_ms > 0 else 0.0   # same bytes / summed operator-kernel event time
+        whole_step = balg_timed / wall / 1e9
+        prof = profile_tables() if (mode == 2 and args.graph == "rmat" and args.scale == 24 and args.edge_factor == 8 and args.seed == 0x6772) else None
+        fresh = bool(prof) and not prof.get("stale")
+        kernel_s_per_search = (kernel_ms / n_inst) * 1e-3
+        phys = None
+        if fresh and kernel_s_per_search > 0:
+            phys = {"raw": round(prof["per_search"]["bytes"] / kernel_s_per_search / 8e12, 4),
+                    "upper": round(prof["per_search"]["upper"] / kernel_s_per_search / 8e12, 4)}
+        roofline = {"bound": "hbm", "achieved": round(achieved, 2), "peak": 8000.0, "unit": "GB/s",
+                    "frac": round(achieved / 8000.0, 5),
+                    "definition": "algorithmic bytes (4*edges_visited + 20*nodes_visited) of the timed searches / their summed Enact "
+                                  "time / 8 TB/s; a direction-optimizing search does not read most of those edges, so this is NOT "
+                                  "the physical HBM rate (see hbm_frac_physical)",
+                    "frac_kernel_only": round(kernel_only / 8000.0, 5),
+                    "frac_whole_step": round(whole_step / 8000.0, 5),
+                    "traffic": prof["per_search"]["bytes"] if fresh else None,
+                    "traffic_detail": prof["per_search"] if fresh else (prof if prof else None),
+                    "hbm_frac_physical": phys,
+                    "kernel": names.get(dom, str(dom)),
+                    "kernel_share_of_device_time": round(by_kind[dom][1] / kernel_ms, 4) if kernel_ms else None,
+                    "kernel_launches": by_kind[dom][0] if by_kind else 0,
+                    "kernel_avg_launch_ms": round(by_kind[dom][1] / max(by_kind[dom][0], 1), 5) if by_kind else None,
+                    "all_launches": launches, "all_kernel_ms_per_bfs": round(kernel_ms / n_inst, 5),
+                    "alg_bytes_per_bfs": round(balg / n_inst, 1),
+                    "by_kernel_ms": {names.get(kd, str(kd)): round(v[1], 4) for kd, v in sorted(by_kind.items())},
+                    "per_kernel": prof["per_kernel"] if fresh else None,
+                    "profile_source": prof.get("source") if fresh else None}
+        # the top-down leg's own roofline object: same B_alg definition over its searches / their Enact time; dominant kernel and its
+        # average launch from an instrumented traversal_mode-0 pass over the same sources
+        topdown = None
+        if td_steps and td_ms > 0:
+            td_kind, td_kernel_ms = {}, 0.0
+            for k in range(td_steps):
+                s_k = sources[k % len(sources)]
+                iprob.reset(s_k)
+                iprob.enact(s_k, traversal_mode=0)
+                for rec in iprob.level_trace():
+                    agg = td_kind.setdefault(rec["kind"], [0, 0.0])
+                    agg[0] += 1
+                    agg[1] += rec["ms"]
+                    td_kernel_ms += rec["ms"]
+            td_dom = max(td_kind, key=lambda kd: td_kind[kd][1]) if td_kind else 0
+            td_balg = 4.0 * td_edges + 20.0 * td_nodes
+            td_achieved = td_balg / (td_ms * 1e-3) / 1e9
+            topdown = {"workload": "the first %d sources, traversal_mode 0 (load-balanced top-down advance only; reference default mode)" % td_steps,
+                       "enact_ms_per_step": round(td_ms / td_steps, 4), "enact_mteps": round(topdown_mteps, 2),
+                       "bound": "hbm", "achieved": round(td_achieved, 2), "peak": 8000.0, "unit": "GB/s", "frac": round(td_achieved / 8000.0, 5),
+                       "kernel": names.get(td_dom, str(td_dom)),
+                       "kernel_share_of_device_time": round(td_kind[td_dom][1] / td_kernel_ms, 4) if td_kernel_ms else None,
+                       "kernel_launches": td_kind[td_dom][0] if td_kind else 0,
+                       "kernel_avg_launch_ms": round(td_kind[td_dom][1] / max(td_kind[td_dom][0], 1), 5) if td_kind else None,
+                       "all_kernel_ms_per_bfs": round(td_kernel_ms / td_steps, 5),
+                       "by_kernel_ms": {names.get(kd, str(kd)): round(v[1], 4) for kd, v in sorted(td_kind.items())}}
+        iprob.close()
 
     cpu = None
     cpu_parallel = None
@@ -531,6 +568,9 @@ def bench_bc(args, torch, ga, devgraph, device_index):
         run_ms += p.run(sources[k % len(sources)])
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
+    if args.dump_outputs:   # the last timed source's shortest-path counts and dependency values
+        sigma, bc = p.extract()
+        dump_outputs(args.dump_outputs, {"sigma": sigma, "bc": bc})
     # edges of the reached component, from a BFS of the same source (every reached vertex's edges are walked twice)
     bp = ga.BfsProblem(False, True, False, device_index).init_device(n, m, ro.data_ptr(), ci.data_ptr())
     edges_total, nodes_total = 0, 0
@@ -590,6 +630,9 @@ def bench_pr(args, torch, ga, devgraph, device_index):
         enact_ms += p.enact(iters)
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
+    if args.dump_outputs:   # the last timed run's ranking: vertex ids by descending rank, and their ranks
+        ids, ranks = p.extract()
+        dump_outputs(args.dump_outputs, {"ids": ids, "ranks": ranks})
     st = p.stats()
     done = max(st["iterations"], 1)
     cpu, parity = None, None
@@ -646,10 +689,13 @@ def bench_cc(args, torch, ga, devgraph, device_index):
     st = p.stats()
     ids = devgraph.as_tensor(p.device_results(), n)
     components = int((ids == torch.arange(n, device=ids.device, dtype=torch.int32)).sum())
-    ip = ga.CcProblem(instrument=True, device=device_index).init_device(n, m, ro.data_ptr(), ci.data_ptr())
-    ip.reset(); ip.enact()
-    ist = ip.stats()
-    ip.close()
+    if args.dump_outputs:   # the last timed run's component id of every vertex
+        dump_outputs(args.dump_outputs, {"component_ids": ids})
+    if args.full:           # instrumented pass: the roofline's kernel-only figures
+        ip = ga.CcProblem(instrument=True, device=device_index).init_device(n, m, ro.data_ptr(), ci.data_ptr())
+        ip.reset(); ip.enact()
+        ist = ip.stats()
+        ip.close()
     cpu, parity, ref_ih, ref_ij = None, None, None, None
     if not args.no_cpu_baseline:
         from oracle import gr_oracle as o
@@ -679,6 +725,7 @@ def bench_cc(args, torch, ga, devgraph, device_index):
             "config": {"workload": "CC hook/pointer-jump, %s; %d components; this run: %d edge sweeps, %d vertex sweeps"
                                    % (graph_desc, components, st["edge_sweeps"], st["vertex_sweeps"])},
             "enact_ms_per_step": round(enact_ms / steps, 4), "parity_vs_oracle": parity,
+            # --full only: it quotes the instrumented pass
             "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": 8000.0, "unit": "GB/s",
                          "frac": round(achieved / 8000.0, 5), "traffic": None, "kernel": "filter::ApplyKernel (hook / jump sweeps)",
                          "launches": ist["kernel_launches"], "kernel_ms": round(ist["kernel_ms"], 4),
@@ -697,7 +744,7 @@ def bench_cc(args, torch, ga, devgraph, device_index):
                                  "its opening move hooks every vertex under its SMALLEST lower neighbour, and after one neighbour round the sampled giant "
                                  "component sits out of the hooking sweeps, which run one lane per vertex over CSR rows (this_run counts them, the opening "
                                  "and the neighbour round with the vertex sweeps; DESIGN 3.4).  frac_own_sweeps prices this run's own sweeps (9 B per edge "
-                                 "of an edge-form sweep, 8 B per vertex of a vertex sweep): that is the bandwidth figure"},
+                                 "of an edge-form sweep, 8 B per vertex of a vertex sweep): that is the bandwidth figure"} if args.full else None,
             "cpu_baseline": cpu}
 
 
@@ -730,11 +777,14 @@ def bench_sssp(args, torch, ga, devgraph, device_index):
         relaxed += p.stats()["relaxed_edges"]
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
-    ip = ga.SsspProblem(False, True, device_index)
-    ip.init_device(n, m, ro.data_ptr(), ci.data_ptr(), w.data_ptr(), delta)
-    ip.reset(src0); ip.enact(src0)
-    ist = ip.stats()
-    ip.close()
+    if args.dump_outputs:   # the last timed source's distances (0xFFFFFFFF = unreached)
+        dump_outputs(args.dump_outputs, {"distances": p.extract()[0]})
+    if args.full:           # instrumented pass: the roofline's kernel-only figures
+        ip = ga.SsspProblem(False, True, device_index)
+        ip.init_device(n, m, ro.data_ptr(), ci.data_ptr(), w.data_ptr(), delta)
+        ip.reset(src0); ip.enact(src0)
+        ist = ip.stats()
+        ip.close()
     # reached vertices / their edges per timed source (on a directed graph they differ from source to source): from a BFS of the
     # same source -- the reachable set is the same
     bp = ga.BfsProblem(False, True, False, device_index).init_device(n, m, ro.data_ptr(), ci.data_ptr())
@@ -766,12 +816,14 @@ def bench_sssp(args, torch, ga, devgraph, device_index):
     p.close()
     achieved = balg / (enact_ms * 1e-3) / 1e9
     balg0 = 8.0 * reach[src0][1] + 20.0 * reach[src0][0]
-    roof = {"bound": "hbm", "achieved": round(achieved, 2), "peak": 8000.0, "unit": "GB/s", "frac": round(achieved / 8000.0, 5),
-            "traffic": None, "kernel": "advance::LoadBalancedKernel<SSSPFunctor> + priority_queue::BisectKernel",
-            "frac_kernel_only": round(balg0 / (ist["kernel_ms"] * 1e-3) / 8e12, 5) if ist["kernel_ms"] > 0 else None,
-            "launches_src0": ist["kernel_launches"], "kernel_ms_src0": round(ist["kernel_ms"], 4), "alg_bytes": balg,
-            "relaxed_edges_src0": ist["relaxed_edges"], "iterations_src0": ist["iterations"],
-            "note": "B_alg = 8*m_r + 20*n_r of the timed sources (reached vertices and their edges) / their summed Enact time"}
+    roof = None
+    if args.full:
+        roof = {"bound": "hbm", "achieved": round(achieved, 2), "peak": 8000.0, "unit": "GB/s", "frac": round(achieved / 8000.0, 5),
+                "traffic": None, "kernel": "advance::LoadBalancedKernel<SSSPFunctor> + priority_queue::BisectKernel",
+                "frac_kernel_only": round(balg0 / (ist["kernel_ms"] * 1e-3) / 8e12, 5) if ist["kernel_ms"] > 0 else None,
+                "launches_src0": ist["kernel_launches"], "kernel_ms_src0": round(ist["kernel_ms"], 4), "alg_bytes": balg,
+                "relaxed_edges_src0": ist["relaxed_edges"], "iterations_src0": ist["iterations"],
+                "note": "B_alg = 8*m_r + 20*n_r of the timed sources (reached vertices and their edges) / their summed Enact time"}
     return {"metric": ("SSSP R-MAT scale-%d" % args.scale if args.graph == "rmat" else "SSSP directed soc-LiveJournal1 stand-in") +
                       ", uniform weights [1,64]: MTEPS = edges of reached vertices / Enact time",
             "value": round(m_r / (enact_ms * 1e3), 2), "unit": "MTEPS", "n_gpus": 1,
