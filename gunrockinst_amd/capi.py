@@ -125,6 +125,17 @@ _SIGNATURES = {
     "grx_cc_extract": (C.c_int, [C.c_void_p, i32p, C.POINTER(C.c_uint)]),
     "grx_cc_device_results": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "grx_cc_destroy": (None, [C.c_void_p]),
+    "grx_mst_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int]),
+    "grx_mst_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p, i32p]),
+    "grx_mst_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "grx_mst_reset": (C.c_int, [C.c_void_p]),
+    "grx_mst_enact": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
+    "grx_mst_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
+                                C.POINTER(C.c_double)]),
+    "grx_mst_round_trace": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_double)]),
+    "grx_mst_extract": (C.c_int, [C.c_void_p, i32p, C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
+    "grx_mst_device_results": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "grx_mst_destroy": (None, [C.c_void_p]),
     "grx_sssp_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int]),
     "grx_sssp_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p, C.POINTER(C.c_uint32), C.c_int]),
     "grx_sssp_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float]),
@@ -532,6 +543,90 @@ def gunrock_cc(nodes, row_offsets, col_indices, device=0):
     dt = GunrockDataType(VTXID_INT, SIZET_INT, VALUE_INT)
     lib().gunrock_cc_func(C.byref(gout), C.byref(gin), cfg, dt)
     return _take_node_values(gout, nodes, np.int32)
+
+
+class MstProblem:
+    """MSTProblem + MSTEnactor behind the handle C ABI: the minimum spanning forest of the CSR read as an undirected multigraph,
+    unique under the order (weight as int32, then CSR index)."""
+
+    def __init__(self, instrument=False, device=0):
+        self._h = C.c_void_p()
+        _check(lib().grx_mst_create(C.byref(self._h), int(instrument), device), "grx_mst_create")
+        self.nodes = 0
+        self.edges = 0
+
+    def init(self, nodes, row_offsets, col_indices, edge_values):
+        ro = np.ascontiguousarray(row_offsets, dtype=np.int32)
+        ci = np.ascontiguousarray(col_indices, dtype=np.int32)
+        w = np.ascontiguousarray(edge_values, dtype=np.int32)
+        if w.shape[0] != ci.shape[0]:
+            raise ValueError("gunrockinst_amd: %d edge values for %d edges" % (w.shape[0], ci.shape[0]))
+        if ro.shape[0] != int(nodes) + 1:
+            raise ValueError("gunrockinst_amd: %d row offsets for %d nodes" % (ro.shape[0], int(nodes)))
+        self.nodes, self.edges = int(nodes), int(ci.shape[0])
+        _check(lib().grx_mst_init(self._h, self.nodes, self.edges, _p(ro), _p(ci), _p(w)), "MSTProblem::Init")
+        return self
+
+    def init_device(self, nodes, edges, d_row_offsets, d_col_indices, d_edge_values):
+        self.nodes, self.edges = int(nodes), int(edges)
+        _check(lib().grx_mst_init_device(self._h, self.nodes, self.edges, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices),
+                                         C.c_void_p(d_edge_values)), "MSTProblem::Init(device)")
+        return self
+
+    def reset(self):
+        _check(lib().grx_mst_reset(self._h), "MSTProblem::Reset")
+
+    def enact(self, max_grid_size=0):
+        ms = C.c_float()
+        _check(lib().grx_mst_enact(self._h, max_grid_size, C.byref(ms)), "MSTEnactor::Enact")
+        return float(ms.value)
+
+    def stats(self):
+        r, s, l = C.c_longlong(), C.c_longlong(), C.c_longlong()
+        k = C.c_double()
+        _check(lib().grx_mst_stats(self._h, C.byref(r), C.byref(s), C.byref(l), C.byref(k)), "grx_mst_stats")
+        return {"rounds": r.value, "edges_scanned": s.value, "kernel_launches": l.value, "kernel_ms": k.value}
+
+    def round_trace(self, max_rounds=1024):
+        entries = (C.c_longlong * max_rounds)()
+        ms = (C.c_double * max_rounds)()
+        n = lib().grx_mst_round_trace(self._h, max_rounds, entries, ms)
+        n = min(max(n, 0), max_rounds)
+        return [{"entries": entries[i], "ms": ms[i]} for i in range(n)]
+
+    def extract(self, selected=True):
+        """(selected 0/1 per CSR entry as int32, or None; total_weight; forest_edges)"""
+        sel = np.empty(max(self.edges, 1), dtype=np.int32) if selected else None
+        tw, fe = C.c_longlong(), C.c_int()
+        _check(lib().grx_mst_extract(self._h, None if sel is None else _p(sel), C.byref(tw), C.byref(fe)), "MSTProblem::Extract")
+        return (None if sel is None else sel[:self.edges]), int(tw.value), int(fe.value)
+
+    def device_results(self):
+        d = C.c_void_p()
+        _check(lib().grx_mst_device_results(self._h, C.byref(d)), "grx_mst_device_results")
+        return d.value
+
+    def close(self):
+        if self._h:
+            lib().grx_mst_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def gunrock_mst(nodes, row_offsets, col_indices, edge_values, device=0):
+    """One-shot minimum spanning forest: returns (selected, total_weight, forest_edges); components = nodes - forest_edges."""
+    p = MstProblem(device=device).init(nodes, row_offsets, col_indices, edge_values)
+    try:
+        p.reset()
+        p.enact()
+        return p.extract()
+    finally:
+        p.close()
 
 
 def gunrock_bc(nodes, row_offsets, col_indices, src=-1, queue_size=1.0, src_mode=SRC_MANUALLY, device=0):

@@ -201,6 +201,36 @@ int grx_cc_device_results(grx_cc *p, int **d_component_ids);
 void grx_cc_destroy(grx_cc *p);
 
 /* ------------------------------------------------------------------------------------------------
+ * MST: MSTProblem + MSTEnactor (reference gunrock/app/mst/mst_problem.cuh:44-520, mst_enactor.cuh:48-1260), a minimum
+ * spanning FOREST.  The CSR is read as an undirected multigraph: every entry e = (u, v, w), u != v, is one edge {u, v} of
+ * weight w (self-loops ignored; unsorted rows, duplicates, parallel edges and asymmetric input allowed).  Entries are ordered
+ * by (w as signed int32, then e); under that strict order the forest is unique and is what Kruskal over the sorted entries
+ * returns.  Any int32 weight is allowed.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct grx_mst grx_mst;
+
+int grx_mst_create(grx_mst **out, int instrument, int device);
+/* MSTProblem::Init(false, csr, 1) (reference mst_problem.cuh:252-495).  -1: nodes < 1, edges < 0 or a NULL array;
+ * -2: not a CSR of `nodes` vertices (offsets not from 0 to edges, decreasing, or a column outside [0, nodes)) */
+int grx_mst_init(grx_mst *p, int nodes, int edges, const int *row_offsets, const int *col_indices, const int *edge_values);
+/* the same for a CSR already in HBM (borrowed, not freed) */
+int grx_mst_init_device(grx_mst *p, int nodes, int edges, int *d_row_offsets, int *d_col_indices, int *d_edge_values);
+/* MSTProblem::Reset (reference mst_problem.cuh:501-520) */
+int grx_mst_reset(grx_mst *p);
+/* MSTEnactor::Enact(problem, max_grid_size) (reference mst_enactor.cuh:1198), HIP-event timed */
+int grx_mst_enact(grx_mst *p, int max_grid_size, float *elapsed_ms);
+/* Borůvka rounds of the last Enact, entries their minimum steps read, kernel launches and -- when instrumented -- the summed time
+ * of the rounds */
+int grx_mst_stats(grx_mst *p, long long *rounds, long long *edges_scanned, long long *kernel_launches, double *kernel_ms);
+/* per round of the last Enact: entries read by its minimum step and (instrumented) its time; returns the number of rounds */
+int grx_mst_round_trace(grx_mst *p, int max_rounds, long long *entries, double *ms);
+/* MSTProblem::Extract(h_mst_output) (reference mst_problem.cuh:218): h_selected[e] = 1 exactly on the forest's CSR entries;
+ * total_weight = sum of their weights, forest_edges = their number (components = nodes - forest_edges) */
+int grx_mst_extract(grx_mst *p, int *h_selected /* may be NULL */, long long *total_weight, int *forest_edges);
+int grx_mst_device_results(grx_mst *p, int **d_selected);
+void grx_mst_destroy(grx_mst *p);
+
+/* ------------------------------------------------------------------------------------------------
  * SSSP: SSSPProblem + SSSPEnactor (reference gunrock/app/sssp/sssp_problem.cuh:35-387, sssp_enactor.cuh:36-563)
  * ---------------------------------------------------------------------------------------------- */
 typedef struct grx_sssp grx_sssp;
