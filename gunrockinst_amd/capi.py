@@ -112,6 +112,9 @@ _SIGNATURES = {
                                       C.POINTER(C.c_double), i32p]),
     "grx_bfs_extract": (C.c_int, [C.c_void_p, i32p, i32p]),
     "grx_bfs_device_results": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "grx_bfs_mask_flushes": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
+    "grx_bfs_relabel_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_int),
+                                       C.POINTER(C.c_float), C.POINTER(C.c_longlong)]),
     "grx_bfs_destroy": (None, [C.c_void_p]),
     "grx_cc_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int]),
     "grx_cc_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p]),
@@ -421,6 +424,20 @@ class BfsProblem:
         dl, dp = C.c_void_p(), C.c_void_p()
         _check(lib().grx_bfs_device_results(self._h, C.byref(dl), C.byref(dp)), "grx_bfs_device_results")
         return dl.value, dp.value
+
+    def mask_flushes(self):
+        """kept level bitmaps flushed into the labels in the middle of a search, over the handle's life"""
+        v = C.c_longlong()
+        _check(lib().grx_bfs_mask_flushes(self._h, C.byref(v)), "grx_bfs_mask_flushes")
+        return v.value
+
+    def relabel_info(self):
+        """The relabelled copy of a symmetric problem: hub-tier size (-1 = no copy), vertices with edges, hub degree
+        threshold, build milliseconds, device bytes."""
+        h, we, t, ms, b = C.c_longlong(), C.c_longlong(), C.c_int(), C.c_float(), C.c_longlong()
+        _check(lib().grx_bfs_relabel_info(self._h, C.byref(h), C.byref(we), C.byref(t), C.byref(ms), C.byref(b)),
+               "grx_bfs_relabel_info")
+        return {"hubs": h.value, "with_edges": we.value, "threshold": t.value, "build_ms": ms.value, "bytes": b.value}
 
     def close(self):
         if self._h:

@@ -187,7 +187,7 @@ class BFSEnactor : public EnactorBase {
         GraphSlice<VertexId, SizeT, Value> *gs = problem->graph_slices[0];
         typename BFSProblem::DataSlice *ds = problem->data_slices[0];
         hipStream_t stream = gs->stream;
-        if (src < 0 || src >= problem->nodes) return problem->EmitLabels(stream);
+        if (src < 0 || src >= problem->nodes) return problem->FinishSearch(stream);
         // deferred labels (bfs_problem.hpp): vertex-ordered sweeps keep their output bitmap instead of storing labels
         const bool deferring = dobfs && problem->labels_deferred;
         ds->defer_labels = deferring ? 1 : 0;
@@ -772,9 +772,11 @@ class BFSEnactor : public EnactorBase {
         }
         enactor_stats.iteration = iteration;
         if (retval) return retval;
-        if (problem->labels_deferred) {  // every label of the search in one coalesced pass (bfs_problem.hpp EmitLabelsKernel)
+        // every label of the search in one coalesced pass (bfs_problem.hpp EmitLabelsKernel; TranslateLabelsKernel when the search
+        // ran on the relabelled copy)
+        if (problem->labels_deferred || problem->translate_pending) {
             if (INSTRUMENT && (retval = InstrumentBegin(stream))) return retval;
-            if ((retval = problem->EmitLabels(stream))) return retval;
+            if ((retval = problem->FinishSearch(stream))) return retval;
             if (INSTRUMENT) {
                 if ((retval = InstrumentEnd(stream))) return retval;
                 if ((retval = util::GRError(hipStreamSynchronize(stream), "BFSEnactor EmitLabels sync failed", __FILE__, __LINE__))) return retval;

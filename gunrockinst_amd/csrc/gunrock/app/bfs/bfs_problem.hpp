@@ -21,6 +21,7 @@
 
 #include <gunrock/app/problem_base.hpp>
 #include <gunrock/graphio/device_csr.hpp>
+#include <gunrock/graphio/relabel.hpp>
 #include <gunrock/oprtr/advance/binned.hpp>
 #include <gunrock/oprtr/advance/bottom_up.hpp>
 #include <gunrock/util/memset_kernel.hpp>
@@ -213,6 +214,188 @@ __global__ __launch_bounds__(256) void EmitLabelsKernel(LevelMaskList<VertexId> 
     }
 }
 
+// The closing label pass of a search on the relabelled copy (graphio/relabel.hpp): the level bitmaps, the visited bitmap and
+// the work labels / predecessors are in the copy's numbering, the output is in the caller's, four vertices (16 bytes) per lane.
+// The tier-0 (hub) vertices of a quad are consecutive new ids, and so are its tier-1 vertices: one window of each bitmap per tier
+// covers them, and every word of a window is loaded before the first is looked at (one round trip, as in EmitLabelsKernel).  A
+// vertex without edges is -1 without a lookup (the source: 0, predecessor -1).  Same gate and padding rules as
+// EmitLabelsKernel<FULL = true>.
+template <typename VertexId, int KMAX, bool PRED>
+__device__ __forceinline__ void TranslateTier(const LevelMaskList<VertexId> &levels, int valid, const unsigned long long *d_visited,
+                                              unsigned t4, long long x1, const VertexId *d_work_labels, const VertexId *d_work_preds,
+                                              const VertexId *d_old_of_new, int (&out)[4], int (&pout)[4])
+{
+    const long long xw = x1 >> 6;
+    const int xs = static_cast<int>(x1 & 63);
+    const bool cross = xs > 60;  // (the window of up to four bits reaches into the next word)
+    unsigned long long lo[KMAX > 0 ? KMAX : 1], hi[KMAX > 0 ? KMAX : 1];
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) lo[k] = levels.mask[k][xw];
+    const unsigned long long vlo = d_visited[xw];
+    unsigned long long vhi = 0ull;
+    if (cross) {
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k) hi[k] = levels.mask[k][xw + 1];
+        vhi = d_visited[xw + 1];
+    }
+    int lab[4] = {-1, -1, -1, -1};
+    unsigned covered = 0;
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+        const unsigned long long win = (lo[k] >> xs) | (cross ? hi[k] << (64 - xs) : 0ull);
+        const unsigned m = (k < valid) ? static_cast<unsigned>(win) & 0xFu : 0u;
+        covered |= m;
+        const VertexId l = levels.label[k];
+        if (m & 1u) lab[0] = l;
+        if (m & 2u) lab[1] = l;
+        if (m & 4u) lab[2] = l;
+        if (m & 8u) lab[3] = l;
+    }
+    const unsigned cnt = static_cast<unsigned>(__popc(t4));
+    const unsigned vis = static_cast<unsigned>((vlo >> xs) | (cross ? vhi << (64 - xs) : 0ull)) & ((1u << cnt) - 1u);
+    const unsigned keep = vis & ~covered;  // visited, in no kept bitmap: what a top-down kernel wrote at discovery
+    int j = 0;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        if (!((t4 >> b) & 1u)) continue;
+        int l = lab[0];
+        if (j == 1) l = lab[1];
+        if (j == 2) l = lab[2];
+        if (j == 3) l = lab[3];
+        if ((keep >> j) & 1u) l = d_work_labels[x1 + j];
+        out[b] = l;
+        if (PRED) {
+            const VertexId p = d_work_preds[x1 + j];
+            pout[b] = p >= 0 ? d_old_of_new[p] : p;
+        }
+        ++j;
+    }
+}
+
+template <typename VertexId, int KMAX, bool PRED>
+__global__ __launch_bounds__(256) void TranslateLabelsKernel(LevelMaskList<VertexId> levels, const unsigned long long *d_visited,
+                                                             graphio::RelabelView map, long long nodes, VertexId caller_src,
+                                                             const VertexId *d_work_labels, const VertexId *d_work_preds,
+                                                             const VertexId *d_old_of_new, VertexId *d_labels, VertexId *d_preds)
+{
+    typedef __attribute__((ext_vector_type(4))) int V4;
+    int valid = KMAX;
+    if (levels.d_gate) {  // (uniform)
+        if (levels.d_gate[0] == 0) return;
+        valid = levels.chain_first + levels.d_gate[1];
+    }
+    const bool hubs = map.hubs > 0;  // (uniform)
+    const long long quads = (nodes + 3) / 4;
+    const long long stride = static_cast<long long>(gridDim.x) * blockDim.x;
+    for (long long q = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; q < quads; q += stride) {
+        const long long v0 = q * 4;
+        const long long w = v0 >> 6;
+        const int sh = static_cast<int>(v0 & 63);
+        const unsigned long long edge = map.d_edge[w];
+        const unsigned long long hub = hubs ? map.d_hub[w] : 0ull;
+        const long long b1 = map.d_base1[w];
+        const long long b0 = hubs ? map.d_base0[w] : 0ll;
+        const unsigned long long low = (1ull << sh) - 1ull;
+        const unsigned h4 = static_cast<unsigned>(hub >> sh) & 0xFu, e4 = static_cast<unsigned>(edge >> sh) & 0xFu;
+        int out[4] = {-1, -1, -1, -1};
+        int pout[4] = {-2, -2, -2, -2};
+        if (e4)
+            TranslateTier<VertexId, KMAX, PRED>(levels, valid, d_visited, e4, map.hubs + b1 + __popcll(edge & low), d_work_labels, d_work_preds,
+                                                d_old_of_new, out, pout);
+        if (h4)
+            TranslateTier<VertexId, KMAX, PRED>(levels, valid, d_visited, h4, b0 + __popcll(hub & low), d_work_labels, d_work_preds,
+                                                d_old_of_new, out, pout);
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+            if (caller_src == v0 + b && !(((h4 | e4) >> b) & 1u)) {  // a source without edges
+                out[b] = 0;
+                pout[b] = -1;
+            }
+        if (v0 + 3 < nodes) {
+            *reinterpret_cast<V4 *>(d_labels + v0) = V4{out[0], out[1], out[2], out[3]};
+            if (PRED) *reinterpret_cast<V4 *>(d_preds + v0) = V4{pout[0], pout[1], pout[2], pout[3]};
+        } else {
+            for (int b = 0; b < 4 && v0 + b < nodes; ++b) {
+                d_labels[v0 + b] = out[b];
+                if (PRED) d_preds[v0 + b] = pout[b];
+            }
+        }
+    }
+}
+
+// Static per graph and numbering, what a direction-optimizing search reads besides the CSR: the never-discovered mask, the
+// compact heads index and the heads (bottom_up.hpp).  BFSProblem holds one for the caller's numbering and, when it has built
+// the relabelled copy, one for the copy; Reset points graph_slices[0] and the DataSlice at the active one.
+template <typename VertexId, typename SizeT>
+struct SearchGraph {
+    SizeT *d_row_offsets = nullptr;  // forward CSR (borrowed)
+    VertexId *d_column_indices = nullptr;
+    const SizeT *d_inv_row_offsets = nullptr;  // in-neighbour CSR (borrowed)
+    const VertexId *d_inv_column_indices = nullptr;
+    unsigned *d_never_mask = nullptr;  // bit v = v has no in-edge
+    unsigned *d_head_base = nullptr;   // vertices with in-edges before each 64-vertex word
+    int2 *d_inv_heads = nullptr;       // first two in-neighbours of every vertex with in-edges
+    long long with_in_edges = 0;
+
+    void Release()
+    {
+        if (d_never_mask) util::GRError(hipFree(d_never_mask), "SearchGraph hipFree d_never_mask failed", __FILE__, __LINE__);
+        if (d_head_base) util::GRError(hipFree(d_head_base), "SearchGraph hipFree d_head_base failed", __FILE__, __LINE__);
+        if (d_inv_heads) util::GRError(hipFree(d_inv_heads), "SearchGraph hipFree d_inv_heads failed", __FILE__, __LINE__);
+        d_never_mask = nullptr;
+        d_head_base = nullptr;
+        d_inv_heads = nullptr;
+    }
+
+    // fill the static state from the in-neighbour CSR (synchronous); mask_words: 32-bit words of a vertex bitmap
+    hipError_t Build(long long nodes, long long mask_words, hipStream_t stream)
+    {
+        hipError_t retval = hipSuccess;
+        // Bit v set when v has no in-edge.  Reset preloads the visited bitmap with it, so the bottom-up sweep skips those
+        // vertices (half of an R-MAT graph) without touching their row offsets, 64 at a time.
+        if (!d_never_mask)
+            GR_CHECK(hipMalloc(&d_never_mask, sizeof(unsigned) * static_cast<size_t>(mask_words + 2)), "SearchGraph hipMalloc d_never_mask failed");
+        if (!d_inv_heads)
+            GR_CHECK(hipMalloc(&d_inv_heads, sizeof(int2) * static_cast<size_t>(nodes > 0 ? nodes : 1)), "SearchGraph hipMalloc d_inv_heads failed");
+        const long long words64 = mask_words / 2 + 1;
+        long long grid = (words64 + 3) / 4;
+        if (grid > 2048) grid = 2048;
+        hipLaunchKernelGGL((NoInEdgeMaskKernel<SizeT>), dim3(static_cast<unsigned>(grid)), dim3(256), 0, stream, d_inv_row_offsets, nodes, words64,
+                           reinterpret_cast<unsigned long long *>(d_never_mask));
+        GR_CHECK(hipGetLastError(), "NoInEdgeMaskKernel launch failed");
+        // heads are stored only for vertices that have in-edges: d_head_base[w] = such vertices before word w
+        if (!d_head_base)
+            GR_CHECK(hipMalloc(&d_head_base, sizeof(unsigned) * static_cast<size_t>(words64 + 1)), "SearchGraph hipMalloc d_head_base failed");
+        unsigned *d_counts = nullptr;
+        unsigned long long *d_scan_sums = nullptr;
+        GR_CHECK(hipMalloc(&d_counts, sizeof(unsigned) * static_cast<size_t>(words64 + 1)), "SearchGraph hipMalloc failed");
+        GR_CHECK(hipMalloc(&d_scan_sums, sizeof(unsigned long long) * static_cast<size_t>(graphio::ScanScratchWords(words64))), "SearchGraph hipMalloc failed");
+        hipLaunchKernelGGL(WithInEdgesCountKernel, dim3(static_cast<unsigned>((words64 + 255) / 256)), dim3(256), 0, stream,
+                           reinterpret_cast<const unsigned long long *>(d_never_mask), nodes, words64, d_counts);
+        GR_CHECK(hipGetLastError(), "WithInEdgesCountKernel launch failed");
+        GR_CHECK(graphio::DeviceExclusiveScan<unsigned>(d_counts, d_head_base, words64, d_scan_sums, stream), "SearchGraph head-base scan failed");
+        GR_CHECK(hipStreamSynchronize(stream), "NoInEdgeMaskKernel failed");
+        {   // vertices that have in-edges = last base + last count (sizes the "nearly finished" test of the enactor)
+            unsigned last_base = 0, last_count = 0;
+            GR_CHECK(hipMemcpy(&last_base, d_head_base + (words64 - 1), sizeof(unsigned), hipMemcpyDeviceToHost), "SearchGraph read failed");
+            GR_CHECK(hipMemcpy(&last_count, d_counts + (words64 - 1), sizeof(unsigned), hipMemcpyDeviceToHost), "SearchGraph read failed");
+            with_in_edges = static_cast<long long>(last_base) + last_count;
+        }
+        GR_CHECK(hipFree(d_counts), "SearchGraph hipFree failed");
+        GR_CHECK(hipFree(d_scan_sums), "SearchGraph hipFree failed");
+        if (nodes > 0) {
+            long long hgrid = (nodes + 3) / 4;  // one wave per vertex
+            if (hgrid > 8192) hgrid = 8192;
+            hipLaunchKernelGGL((oprtr::advance::BuildHeadsKernel<VertexId, SizeT>), dim3(static_cast<unsigned>(hgrid)), dim3(256), 0, stream,
+                               d_inv_row_offsets, d_inv_column_indices, nodes, d_inv_heads, d_inv_row_offsets,
+                               reinterpret_cast<const unsigned long long *>(d_never_mask), d_head_base);
+            GR_CHECK(hipGetLastError(), "BuildHeadsKernel launch failed");
+            GR_CHECK(hipStreamSynchronize(stream), "BuildHeadsKernel failed");
+        }
+        return retval;
+    }
+};
+
 template <typename _VertexId, typename _SizeT, typename _Value, bool _MARK_PREDECESSORS,
           bool _ENABLE_IDEMPOTENCE, bool _USE_DOUBLE_BUFFER>
 struct BFSProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
@@ -296,29 +479,100 @@ struct BFSProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
 
     ~BFSProblem() override
     {
+        if (data_slices && active != 0) UseNumbering(0);  // (the graph slice frees the caller's CSR when it owns it)
         if (data_slices) {
             DataSlice *ds = data_slices[0];
             if (ds) {
-                if (ds->d_labels) util::GRError(hipFree(ds->d_labels), "BFSProblem hipFree d_labels failed", __FILE__, __LINE__);
-                if (ds->d_preds) util::GRError(hipFree(ds->d_preds), "BFSProblem hipFree d_preds failed", __FILE__, __LINE__);
+                if (d_out_labels) util::GRError(hipFree(d_out_labels), "BFSProblem hipFree d_labels failed", __FILE__, __LINE__);
+                if (d_out_preds) util::GRError(hipFree(d_out_preds), "BFSProblem hipFree d_preds failed", __FILE__, __LINE__);
+                if (d_work_labels) util::GRError(hipFree(d_work_labels), "BFSProblem hipFree work labels failed", __FILE__, __LINE__);
+                if (d_work_preds) util::GRError(hipFree(d_work_preds), "BFSProblem hipFree work preds failed", __FILE__, __LINE__);
                 if (ds->d_visited_mask) util::GRError(hipFree(ds->d_visited_mask), "BFSProblem hipFree d_visited_mask failed", __FILE__, __LINE__);
                 for (int i = 0; i < kLevelMasks; ++i)
                     if (ds->d_frontier_mask[i]) util::GRError(hipFree(ds->d_frontier_mask[i]), "BFSProblem hipFree d_frontier_mask failed", __FILE__, __LINE__);
                 if (ds->d_snapshot) util::GRError(hipFree(ds->d_snapshot), "BFSProblem hipFree d_snapshot failed", __FILE__, __LINE__);
-                if (ds->d_never_mask) util::GRError(hipFree(ds->d_never_mask), "BFSProblem hipFree d_never_mask failed", __FILE__, __LINE__);
                 if (ds->d_fresh) util::GRError(hipFree(ds->d_fresh), "BFSProblem hipFree d_fresh failed", __FILE__, __LINE__);
-                if (ds->d_head_base) util::GRError(hipFree(ds->d_head_base), "BFSProblem hipFree d_head_base failed", __FILE__, __LINE__);
-                if (ds->d_inv_heads) util::GRError(hipFree(ds->d_inv_heads), "BFSProblem hipFree d_inv_heads failed", __FILE__, __LINE__);
                 delete ds;
             }
             delete[] data_slices;
         }
+        for (int k = 0; k < 2; ++k) numbering[k].Release();
+        relabelled.Release();
         if (h_src_box) util::GRError(hipHostFree(h_src_box), "BFSProblem hipHostFree failed", __FILE__, __LINE__);
         bin_pool.Release();
     }
 
     // bitmaps are sized in whole 64-bit words: one wave owns one word in the bottom-up sweep
     SizeT MaskWords() const { return ((this->nodes + 63) / 64) * 2; }
+
+    // ---- two numberings of one graph (graphio/relabel.hpp, DESIGN §3.3 k) ----
+    // numbering[0]: the caller's; numbering[1]: the hub-first, edgeless-last copy a symmetric problem builds in InverseIsSelf.
+    // Kernels only ever see the active one: from Reset on, graph_slices[0] and the DataSlice point at it, labels and
+    // predecessors are worked in d_work_* in its numbering, and the closing label pass (TranslateLabelsKernel) writes the
+    // caller-order results into d_out_*, the arrays device_results() hands out.
+    SearchGraph<VertexId, SizeT> numbering[2];
+    graphio::RelabelledCsr relabelled;
+    int relabel = -1;                 // policy (effective at the next Reset): 1 search the relabelled copy, 0 the caller's numbering,
+                                      // -1 the copy on graphs of at least relabel_min_nodes vertices
+    long long relabel_min_nodes = 1ll << 23;  // (scale-22 R-MAT: the label pass costs more than the sweeps save, DESIGN §3.3 k)
+    long long relabel_hubs = 0;       // size limit of the hub tier (0: two tiers, with edges / without; DESIGN §3.3 k: hubs first measured no gain)
+    bool build_relabelled = false;    // policy: InverseIsSelf builds the copy (the one-shot entry point leaves it off)
+    int active = 0;                   // state: numbering of the running search
+    bool translate_pending = false;   // state: a non-deferred search on the copy still owes its caller-order pass
+    VertexId caller_source = -1;      // the source in the caller's numbering (`source` is in the active one)
+    VertexId *d_out_labels = nullptr, *d_out_preds = nullptr;    // results, caller order
+    VertexId *d_work_labels = nullptr, *d_work_preds = nullptr;  // the copy's numbering (allocated with the copy)
+
+    // (re)build the relabelled copy of a symmetric problem with at most `hubs` vertices in the hub tier
+    hipError_t BuildRelabelled(long long hubs)
+    {
+        hipError_t retval = hipSuccess;
+        hipStream_t stream = this->graph_slices[0]->stream;
+        if (!direction_optimizing || numbering[0].d_inv_row_offsets != numbering[0].d_row_offsets)
+            return util::GRError(hipErrorInvalidValue, "BFSProblem: the relabelled copy needs a symmetric graph (InverseIsSelf)", __FILE__, __LINE__);
+        GR_CHECK(hipStreamSynchronize(stream), "BFSProblem sync failed");
+        if (active == 1) UseNumbering(0);  // (the next Reset picks the new copy up)
+        numbering[1].Release();
+        GR_CHECK(relabelled.Build(this->nodes, this->edges, numbering[0].d_row_offsets, numbering[0].d_column_indices, hubs < 0 ? 0 : hubs,
+                                  MARK_PREDECESSORS, stream),
+                 "BFSProblem relabel build failed");
+        numbering[1].d_row_offsets = relabelled.d_row_offsets;
+        numbering[1].d_column_indices = relabelled.d_cols;
+        numbering[1].d_inv_row_offsets = relabelled.d_row_offsets;
+        numbering[1].d_inv_column_indices = relabelled.d_cols;
+        GR_CHECK(numbering[1].Build(this->nodes, MaskWords(), stream), "BFSProblem relabelled static state failed");
+        const size_t n = static_cast<size_t>(this->nodes > 0 ? this->nodes : 1);
+        if (!d_work_labels) GR_CHECK(hipMalloc(&d_work_labels, sizeof(VertexId) * n), "BFSProblem hipMalloc work labels failed");
+        if (MARK_PREDECESSORS && !d_work_preds) GR_CHECK(hipMalloc(&d_work_preds, sizeof(VertexId) * n), "BFSProblem hipMalloc work preds failed");
+        relabel_hubs = hubs;
+        return retval;
+    }
+    bool HasRelabelled() const { return relabelled.Ready() && numbering[1].d_never_mask != nullptr; }
+    bool RelabelActive() const
+    {
+        return HasRelabelled() && (relabel > 0 || (relabel < 0 && static_cast<long long>(this->nodes) >= relabel_min_nodes));
+    }
+    // id of caller vertex v in the numbering the kernels see
+    VertexId SearchId(VertexId v) const { return (active == 1 && v >= 0 && v < this->nodes) ? static_cast<VertexId>(relabelled.NewId(v)) : v; }
+
+    // point the kernels' view (graph slice, DataSlice, with_in_edges) at numbering k
+    void UseNumbering(int k)
+    {
+        DataSlice *ds = data_slices[0];
+        GraphSlice<VertexId, SizeT, Value> *gs = this->graph_slices[0];
+        active = k;
+        const SearchGraph<VertexId, SizeT> &g = numbering[k];
+        gs->d_row_offsets = g.d_row_offsets;
+        gs->d_column_indices = g.d_column_indices;
+        ds->d_inv_row_offsets = g.d_inv_row_offsets;
+        ds->d_inv_column_indices = g.d_inv_column_indices;
+        ds->d_never_mask = g.d_never_mask;
+        ds->d_head_base = g.d_head_base;
+        ds->d_inv_heads = g.d_inv_heads;
+        with_in_edges = g.with_in_edges;
+        ds->d_labels = k == 1 ? d_work_labels : d_out_labels;
+        ds->d_preds = k == 1 ? d_work_preds : d_out_preds;
+    }
 
     // Enable direction-optimizing traversal.  The in-neighbour CSR must stay valid while the problem lives;
     // for an undirected (symmetric) graph pass the problem's own device arrays (InverseIsSelf()).
@@ -327,70 +581,28 @@ struct BFSProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
     {
         hipError_t retval = hipSuccess;
         DataSlice *ds = data_slices[0];
-        ds->d_inv_row_offsets = d_inv_row_offsets;
-        ds->d_inv_column_indices = d_inv_column_indices;
+        if (active != 0) UseNumbering(0);  // (a new inverse: the caller's numbering again, the copy is dropped below)
+        relabelled.Release();
+        numbering[1].Release();
+        numbering[0].d_row_offsets = this->graph_slices[0]->d_row_offsets;
+        numbering[0].d_column_indices = this->graph_slices[0]->d_column_indices;
+        numbering[0].d_inv_row_offsets = d_inv_row_offsets;
+        numbering[0].d_inv_column_indices = d_inv_column_indices;
         for (int i = 0; i < kLevelMasks; ++i)
             if (!ds->d_frontier_mask[i])
                 GR_CHECK(hipMalloc(&ds->d_frontier_mask[i], sizeof(unsigned) * static_cast<size_t>(MaskWords() + 2)),
                          "BFSProblem hipMalloc d_frontier_mask failed");
         if (!ds->d_snapshot)
             GR_CHECK(hipMalloc(&ds->d_snapshot, sizeof(unsigned) * static_cast<size_t>(MaskWords() + 2)), "BFSProblem hipMalloc d_snapshot failed");
-        // Static per graph: bit v set when v has no in-edge.  Reset preloads the visited bitmap with it, so the bottom-up
-        // sweep skips those vertices (half of an R-MAT graph) without touching their row offsets, 64 at a time.
-        if (!ds->d_never_mask)
-            GR_CHECK(hipMalloc(&ds->d_never_mask, sizeof(unsigned) * static_cast<size_t>(MaskWords() + 2)),
-                     "BFSProblem hipMalloc d_never_mask failed");
         if (!ds->d_fresh) {
             const size_t bytes = (static_cast<size_t>(this->nodes) + 1023) / 1024 * 1024 + 1024;  // FreshToBitmapKernel reads 1 KiB steps
             GR_CHECK(hipMalloc(&ds->d_fresh, bytes), "BFSProblem hipMalloc d_fresh failed");
             GR_CHECK(hipMemset(ds->d_fresh, 0, bytes), "BFSProblem hipMemset d_fresh failed");  // levels leave it zero again
             GR_CHECK(hipDeviceSynchronize(), "BFSProblem sync failed");  // (null-stream memset: the problem's stream is not ordered behind it)
         }
-        if (!ds->d_inv_heads)
-            GR_CHECK(hipMalloc(&ds->d_inv_heads, sizeof(int2) * static_cast<size_t>(this->nodes > 0 ? this->nodes : 1)),
-                     "BFSProblem hipMalloc d_inv_heads failed");
-        {
-            const long long words64 = static_cast<long long>(MaskWords()) / 2 + 1;
-            long long grid = (words64 + 3) / 4;
-            if (grid > 2048) grid = 2048;
-            hipLaunchKernelGGL((NoInEdgeMaskKernel<SizeT>), dim3(static_cast<unsigned>(grid)), dim3(256), 0,
-                               this->graph_slices[0]->stream, d_inv_row_offsets, static_cast<long long>(this->nodes), words64,
-                               reinterpret_cast<unsigned long long *>(ds->d_never_mask));
-            GR_CHECK(hipGetLastError(), "NoInEdgeMaskKernel launch failed");
-            // heads are stored only for vertices that have in-edges: d_head_base[w] = such vertices before word w
-            if (!ds->d_head_base)
-                GR_CHECK(hipMalloc(&ds->d_head_base, sizeof(unsigned) * static_cast<size_t>(words64 + 1)), "BFSProblem hipMalloc d_head_base failed");
-            unsigned *d_counts = nullptr;
-            unsigned long long *d_scan_sums = nullptr;
-            GR_CHECK(hipMalloc(&d_counts, sizeof(unsigned) * static_cast<size_t>(words64 + 1)), "BFSProblem hipMalloc failed");
-            GR_CHECK(hipMalloc(&d_scan_sums, sizeof(unsigned long long) * static_cast<size_t>(graphio::ScanScratchWords(words64))),
-                     "BFSProblem hipMalloc failed");
-            hipLaunchKernelGGL(WithInEdgesCountKernel, dim3(static_cast<unsigned>((words64 + 255) / 256)), dim3(256), 0,
-                               this->graph_slices[0]->stream, reinterpret_cast<const unsigned long long *>(ds->d_never_mask),
-                               static_cast<long long>(this->nodes), words64, d_counts);
-            GR_CHECK(hipGetLastError(), "WithInEdgesCountKernel launch failed");
-            GR_CHECK(graphio::DeviceExclusiveScan<unsigned>(d_counts, ds->d_head_base, words64, d_scan_sums, this->graph_slices[0]->stream),
-                     "BFSProblem head-base scan failed");
-            GR_CHECK(hipStreamSynchronize(this->graph_slices[0]->stream), "NoInEdgeMaskKernel failed");
-            {   // vertices that have in-edges = last base + last count (sizes the "nearly finished" test of the enactor)
-                unsigned last_base = 0, last_count = 0;
-                GR_CHECK(hipMemcpy(&last_base, ds->d_head_base + (words64 - 1), sizeof(unsigned), hipMemcpyDeviceToHost), "BFSProblem read failed");
-                GR_CHECK(hipMemcpy(&last_count, d_counts + (words64 - 1), sizeof(unsigned), hipMemcpyDeviceToHost), "BFSProblem read failed");
-                with_in_edges = static_cast<long long>(last_base) + last_count;
-            }
-            GR_CHECK(hipFree(d_counts), "BFSProblem hipFree failed");
-            GR_CHECK(hipFree(d_scan_sums), "BFSProblem hipFree failed");
-        }
-        if (this->nodes > 0) {
-            long long grid = (static_cast<long long>(this->nodes) + 3) / 4;  // one wave per vertex
-            if (grid > 8192) grid = 8192;
-            hipLaunchKernelGGL((oprtr::advance::BuildHeadsKernel<VertexId, SizeT>), dim3(static_cast<unsigned>(grid)), dim3(256), 0,
-                               this->graph_slices[0]->stream, d_inv_row_offsets, d_inv_column_indices,
-                               static_cast<long long>(this->nodes), ds->d_inv_heads, d_inv_row_offsets,
-                               reinterpret_cast<const unsigned long long *>(ds->d_never_mask), ds->d_head_base);
-            GR_CHECK(hipGetLastError(), "BuildHeadsKernel launch failed");
-            GR_CHECK(hipStreamSynchronize(this->graph_slices[0]->stream), "BuildHeadsKernel failed");
-        }
+        GR_CHECK(numbering[0].Build(static_cast<long long>(this->nodes), MaskWords(), this->graph_slices[0]->stream),
+                 "BFSProblem static search state failed");
+        UseNumbering(0);
 
         if (alpha_ > 0) alpha = alpha_;
         if (beta_ > 0) beta = beta_;
@@ -418,9 +630,22 @@ struct BFSProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
         return retval;
     }
 
+    // The graph is its own inverse (symmetric).  With build_relabelled set, this also builds the relabelled copy that Reset
+    // searches while `relabel` is on.
     hipError_t InverseIsSelf(float alpha_ = 0.0f, float beta_ = 0.0f)
     {
-        return SetInverseGraph(this->graph_slices[0]->d_row_offsets, this->graph_slices[0]->d_column_indices, alpha_, beta_);
+        hipError_t retval = hipSuccess;
+        if (active != 0) UseNumbering(0);
+        GR_CHECK(SetInverseGraph(this->graph_slices[0]->d_row_offsets, this->graph_slices[0]->d_column_indices, alpha_, beta_),
+                 "BFSProblem SetInverseGraph failed");
+        // the copy is optional: when it cannot be built (device memory for the sort scratch), the searches keep the caller's numbering
+        if (build_relabelled && this->nodes > 0 && BuildRelabelled(relabel_hubs) != hipSuccess) {
+            hipGetLastError();  // (clear the report of the failed allocation)
+            relabelled.Release();
+            numbering[1].Release();
+            if (active != 0) UseNumbering(0);
+        }
+        return retval;
     }
 
     hipError_t AllocData()
@@ -433,6 +658,8 @@ struct BFSProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
         GR_CHECK(hipMalloc(&ds->d_labels, sizeof(VertexId) * n), "BFSProblem hipMalloc d_labels failed");
         if (MARK_PREDECESSORS)
             GR_CHECK(hipMalloc(&ds->d_preds, sizeof(VertexId) * n), "BFSProblem hipMalloc d_preds failed");
+        d_out_labels = ds->d_labels;
+        d_out_preds = ds->d_preds;
         GR_CHECK(hipMalloc(&ds->d_visited_mask, sizeof(unsigned) * static_cast<size_t>(MaskWords() + 2)),
                  "BFSProblem hipMalloc d_visited_mask failed");
         return retval;
@@ -465,6 +692,10 @@ struct BFSProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
             GR_CHECK(hipHostMalloc(reinterpret_cast<void **>(&h_src_box), sizeof(SourceBox), hipHostMallocMapped), "BFSProblem hipHostMalloc failed");
             h_src_box->seq = 0;
         }
+        // the numbering of this search: the relabelled copy while `relabel` is on and the copy exists
+        if (direction_optimizing) UseNumbering(RelabelActive() ? 1 : 0);
+        caller_source = src;
+        if (active == 1 && src >= 0 && src < this->nodes) src = static_cast<VertexId>(relabelled.NewId(src));  // (host copies of the masks)
         ds->iteration = 0;
         ds->defer_labels = 0;
         // direction-optimizing problems defer the labels of their vertex-ordered sweeps: no fill here, one pass at the end of Enact
@@ -493,6 +724,7 @@ struct BFSProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
         src_row[0] = src_row[1] = 0;
         src_row_pending = valid;
         source = src;
+        translate_pending = active == 1 && !labels_deferred;
         return retval;
     }
 
@@ -524,15 +756,14 @@ struct BFSProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
     hipError_t Extract(VertexId *h_labels, VertexId *h_preds)
     {
         hipError_t retval = hipSuccess;
-        DataSlice *ds = data_slices[0];
         hipStream_t stream = this->graph_slices[0]->stream;
-        GR_CHECK(EmitLabels(stream), "BFSProblem Extract: EmitLabels failed");  // (no-op after an Enact: it ends with this pass)
+        GR_CHECK(FinishSearch(stream), "BFSProblem Extract: label pass failed");  // (no-op after an Enact: it ends with this pass)
         GR_CHECK(hipStreamSynchronize(stream), "BFSProblem Extract sync failed");
         if (this->nodes > 0)
-            GR_CHECK(hipMemcpy(h_labels, ds->d_labels, sizeof(VertexId) * static_cast<size_t>(this->nodes), hipMemcpyDeviceToHost),
+            GR_CHECK(hipMemcpy(h_labels, d_out_labels, sizeof(VertexId) * static_cast<size_t>(this->nodes), hipMemcpyDeviceToHost),
                      "BFSProblem hipMemcpy d_labels failed");
         if (MARK_PREDECESSORS && h_preds && this->nodes > 0)
-            GR_CHECK(hipMemcpy(h_preds, ds->d_preds, sizeof(VertexId) * static_cast<size_t>(this->nodes), hipMemcpyDeviceToHost),
+            GR_CHECK(hipMemcpy(h_preds, d_out_preds, sizeof(VertexId) * static_cast<size_t>(this->nodes), hipMemcpyDeviceToHost),
                      "BFSProblem hipMemcpy d_preds failed");
         return retval;
     }
@@ -611,6 +842,23 @@ struct BFSProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
         const unsigned long long *nev = reinterpret_cast<const unsigned long long *>(ds->d_never_mask);
         const long long n = static_cast<long long>(this->nodes);
         const dim3 g(static_cast<unsigned>(grid)), b(256);
+        if (FULL && active == 1) {  // the search ran on the relabelled copy: the pass writes the caller's order
+            const graphio::RelabelView map = relabelled.View();
+            const VertexId csrc = (caller_source >= 0 && caller_source < this->nodes) ? caller_source : static_cast<VertexId>(-1);
+            const VertexId *o2n = relabelled.d_old_of_new;
+#define GRX_TRANSLATE_CASE(K) case K: hipLaunchKernelGGL((TranslateLabelsKernel<VertexId, K, MARK_PREDECESSORS>), g, b, 0, stream, list, vis, map, n, csrc, \
+                                                          d_work_labels, d_work_preds, o2n, d_out_labels, d_out_preds); break;
+            switch (kmax) {
+                GRX_TRANSLATE_CASE(0) GRX_TRANSLATE_CASE(1) GRX_TRANSLATE_CASE(2) GRX_TRANSLATE_CASE(3) GRX_TRANSLATE_CASE(4) GRX_TRANSLATE_CASE(5)
+                GRX_TRANSLATE_CASE(6) GRX_TRANSLATE_CASE(7) GRX_TRANSLATE_CASE(8)
+                default: hipLaunchKernelGGL((TranslateLabelsKernel<VertexId, kLevelMasks, MARK_PREDECESSORS>), g, b, 0, stream, list, vis, map, n, csrc,
+                                            d_work_labels, d_work_preds, o2n, d_out_labels, d_out_preds);
+            }
+#undef GRX_TRANSLATE_CASE
+            level_masks.count = 0;
+            translate_pending = false;
+            return util::GRError(hipGetLastError(), "TranslateLabelsKernel launch failed", __FILE__, __LINE__);
+        }
 #define GRX_EMIT_CASE(K) case K: hipLaunchKernelGGL((EmitLabelsKernel<VertexId, FULL, K>), g, b, 0, stream, list, vis, nev, n, src, ds->d_labels); break;
         switch (kmax) {
             GRX_EMIT_CASE(0) GRX_EMIT_CASE(1) GRX_EMIT_CASE(2) GRX_EMIT_CASE(3) GRX_EMIT_CASE(4) GRX_EMIT_CASE(5) GRX_EMIT_CASE(6) GRX_EMIT_CASE(7)
@@ -621,10 +869,21 @@ struct BFSProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
         level_masks.count = 0;
         return util::GRError(hipGetLastError(), "EmitLabelsKernel launch failed", __FILE__, __LINE__);
     }
+    long long mask_flushes = 0;  // kept bitmaps flushed in the middle of a search (counted over the problem's life)
     hipError_t FlushLevelMasks(hipStream_t stream)
     {
         if (level_masks.count == 0) return hipSuccess;
+        ++mask_flushes;
         return LaunchEmit<false>(stream, static_cast<VertexId>(-1));
+    }
+    // What every Enact ends with (and Extract, for a search that was reset but not run): the deferred label pass, or, for a
+    // search on the relabelled copy that labelled at discovery, the pass that brings its results into the caller's order.
+    hipError_t FinishSearch(hipStream_t stream)
+    {
+        if (labels_deferred) return EmitLabels(stream);
+        if (!translate_pending) return hipSuccess;
+        level_masks.count = 0;
+        return LaunchEmit<true>(stream, source);
     }
     // The closing pass of a search whose Reset left the labels unfilled.
     hipError_t EmitLabels(hipStream_t stream)

@@ -48,6 +48,9 @@ struct BfsRunner {
     virtual int Trace(int max_levels, long long *frontier, long long *edges, double *ms, int *kind) = 0;
     virtual hipError_t Extract(int *labels, int *preds) = 0;
     virtual void DeviceResults(int **labels, int **preds) = 0;
+    virtual void BuildRelabelled(bool on) = 0;
+    virtual long long MaskFlushes() = 0;
+    virtual void RelabelInfo(long long &hubs, long long &with_edges, int &threshold, float &build_ms, long long &bytes) = 0;
 };
 
 template <bool PRED, bool IDEMP, bool INSTR>
@@ -139,8 +142,32 @@ struct BfsRunnerT : BfsRunner {
         else if (key == "speculative_emit") problem.speculative_emit = value != 0.0;
         else if (key == "chain_sweeps") problem.chain_sweeps = static_cast<int>(value);
         else if (key == "chain_closing") problem.chain_closing = value != 0.0;
-        else return 1;
+        else if (key == "relabel") {  // from the next Reset: 1 the relabelled copy, 0 the caller's numbering, -1 by graph size
+            if (value > 0.0 && !problem.HasRelabelled()) return 2;
+            problem.relabel = value > 0.0 ? 1 : (value < 0.0 ? -1 : 0);
+        } else if (key == "relabel_min_nodes") {
+            if (value < 0.0) return 2;
+            problem.relabel_min_nodes = static_cast<long long>(value);
+        } else if (key == "relabel_hubs") {  // hub-tier size: rebuilds the copy when there is one
+            if (value < 0.0) return 2;
+            const long long hubs = static_cast<long long>(value);
+            if (!problem.HasRelabelled()) problem.relabel_hubs = hubs;
+            else if (hubs != problem.relabel_hubs && problem.BuildRelabelled(hubs) != hipSuccess) return 3;
+        } else return 1;
         return 0;
+    }
+    void BuildRelabelled(bool on) override { problem.build_relabelled = on; }
+    long long MaskFlushes() override { return problem.mask_flushes; }
+    void RelabelInfo(long long &hubs, long long &with_edges, int &threshold, float &build_ms, long long &bytes) override
+    {
+        const bool ready = problem.HasRelabelled();
+        hubs = ready ? problem.relabelled.hubs : -1;
+        with_edges = ready ? problem.relabelled.with_edges : -1;
+        threshold = ready ? problem.relabelled.threshold : 0;
+        build_ms = ready ? problem.relabelled.build_ms : 0.f;
+        // the copy's CSR and renumbering, its static search state (never mask, head base, heads) and the work arrays
+        const long long n = problem.nodes, words = (n + 63) / 64 + 2;
+        bytes = ready ? static_cast<long long>(problem.relabelled.bytes) + words * 8 + (words + 1) * 4 + n * 8 + n * 4 * (problem.MARK_PREDECESSORS ? 2 : 1) : 0;
     }
     void SetLabelDeferral(int enabled, int mask_limit) override
     {
@@ -196,8 +223,9 @@ struct BfsRunnerT : BfsRunner {
     hipError_t Extract(int *labels, int *preds) override { return problem.Extract(labels, preds); }
     void DeviceResults(int **labels, int **preds) override
     {
-        if (labels) *labels = problem.data_slices ? problem.data_slices[0]->d_labels : nullptr;
-        if (preds) *preds = problem.data_slices ? problem.data_slices[0]->d_preds : nullptr;
+        // (the caller-order arrays: the same pointers whichever numbering the searches run in)
+        if (labels) *labels = problem.data_slices ? problem.d_out_labels : nullptr;
+        if (preds) *preds = problem.data_slices ? problem.d_out_preds : nullptr;
     }
 };
 
@@ -253,6 +281,7 @@ int grx_bfs_create(grx_bfs **out, int mark_pred, int idempotence, int instrument
     if (!out) return -1;
     grx_bfs *h = new grx_bfs();
     h->runner = MakeRunner(mark_pred != 0, idempotence != 0, instrument != 0, device);
+    h->runner->BuildRelabelled(true);  // (a handle runs many searches: the relabelled copy pays back its build)
     *out = h;
     return 0;
 }
@@ -394,6 +423,28 @@ int grx_bfs_device_results(grx_bfs *p, int **d_labels, int **d_preds)
 {
     if (!p) return -1;
     p->runner->DeviceResults(d_labels, d_preds);
+    return 0;
+}
+
+int grx_bfs_mask_flushes(grx_bfs *p, long long *flushes)
+{
+    if (!p || !p->runner || !flushes) return -1;
+    *flushes = p->runner->MaskFlushes();
+    return 0;
+}
+
+int grx_bfs_relabel_info(grx_bfs *p, long long *hubs, long long *with_edges, int *threshold, float *build_ms, long long *bytes)
+{
+    if (!p || !p->runner) return -1;
+    long long h = -1, we = -1, b = 0;
+    int t = 0;
+    float ms = 0.f;
+    p->runner->RelabelInfo(h, we, t, ms, b);
+    if (hubs) *hubs = h;
+    if (with_edges) *with_edges = we;
+    if (threshold) *threshold = t;
+    if (build_ms) *build_ms = ms;
+    if (bytes) *bytes = b;
     return 0;
 }
 

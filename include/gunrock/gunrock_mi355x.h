@@ -131,8 +131,20 @@ int grx_bfs_set_label_deferral(grx_bfs *p, int enabled, int mask_limit);
 /* Enactor tuning by name (returns 1 for an unknown name): "emit_queue_factor" (a compacting bottom-up sweep also writes its
  * finds as the next top-down queue when its input frontier is within this factor of the switch-back threshold),
  * "sparse_sweep_div", "speculative_emit" (1/0: the label pass is queued behind the closing top-down launch without waiting
- * for its read-back), "chain_sweeps" (bottom-up sweeps queued per host round trip).  Results never depend on them. */
+ * for its read-back), "chain_sweeps" (bottom-up sweeps queued per host round trip).
+ * Relabelled copy (DESIGN.md 3.3 k): a symmetric problem (grx_bfs_set_inverse_graph without arrays, or grx_bfs_auto_inverse
+ * on a symmetric graph) also builds a copy of its CSR renumbered hub-first, edgeless-last, and searches it; labels and
+ * predecessors still come back in the caller's numbering.  "relabel" (1: search the copy; 0: the caller's numbering; -1, the
+ * default: the copy on graphs of at least "relabel_min_nodes" vertices, default 2^23; effective at the next grx_bfs_reset, both
+ * numberings are kept; returns 2 for 1 on a problem without a copy), "relabel_hubs" (most vertices in the hub tier, default 0;
+ * rebuilds the copy).  Results never depend on any of them. */
 int grx_bfs_set_option(grx_bfs *p, const char *name, double value);
+/* The relabelled copy: hub-tier size, vertices with edges, the hub degree threshold, build time (ms) and the device bytes it
+ * adds.  hubs = -1 when the problem has no copy. */
+/* Deferred labels: how many times a search of this handle ran out of frontier bitmaps and flushed its kept levels into the
+ * labels (summed over the handle's life; see grx_bfs_set_label_deferral's mask_limit). */
+int grx_bfs_mask_flushes(grx_bfs *p, long long *flushes);
+int grx_bfs_relabel_info(grx_bfs *p, long long *hubs, long long *with_edges, int *threshold, float *build_ms, long long *bytes);
 /* Direction-optimizing only: a level that would run count-only or bottom-up and has between `min_edges` and `max_edges`
  * frontier edges starts with a bottom-up pass that probes only the adjacency heads (the highest-degree in-neighbours); the
  * count-only top-down advance then handles what is left.  -1 = automatic bounds (edges/30 .. edges/7.8), min 0 = never,
