@@ -323,6 +323,224 @@ __global__ __launch_bounds__(256) void TranslateLabelsKernel(LevelMaskList<Verte
     }
 }
 
+// ---- the tiled closing label pass (label_pass = 1; both numberings) ----
+// The two kernels above derive the four labels of a quad per lane: the sixteen lanes of a 64-vertex word load and decode the same
+// words of every kept bitmap (EmitLabelsKernel), or a window of every bitmap at their own bit offset and, as soon as one
+// lane's window crosses a word, a second one (TranslateLabelsKernel: 14 wave-level loads per 1 KiB wave store at scale-24).
+// Here a workgroup owns a tile of kLabelTileWords consecutive 64-vertex words of the caller's numbering and loads every bitmap
+// word the tile needs ONCE, coalesced:
+//   phase 1: one lane per word of the search numbering folds that word of all kept bitmaps and of the visited bitmap into
+//            four code bit-planes in LDS.  The code of a vertex is 0 "no label" (-1), k + 1 "in kept bitmap k", or 13
+//            "visited, in no kept bitmap, not pre-marked" (the label a top-down kernel wrote at discovery: a gather).
+//            On the relabelled copy the tile's tier-1 vertices are one run of consecutive new ids (the renumbering is a
+//            stable partition), at most kLabelTileWords + 1 words, and so are its tier-0 vertices: one plane set per tier.
+//            The tier masks and bases of the tile go through LDS as well.
+//   phase 2: every lane takes the four code bits of its quads out of the planes, maps code -> label through a 16-entry
+//            table, gathers the rare code-13 label and stores 16 bytes.  The pass is bound by instruction issue once the
+//            loads are shared, so this phase works on 32-bit halves: the four planes of a half sit in one 16-byte LDS
+//            entry, an unaligned window is two such reads and one v_alignbit per plane, a 256-byte table spreads the window's
+//            bits over the quad's positions of the tier (so both tiers OR into one set of nibbles), and one 24-bit multiply
+//            per vertex gathers its four plane bits into the table offset.
+// All global loads of phase 1 are issued before the first is used; phase 2 has none but the gathers.  Gate, source and
+// edgeless-vertex rules are those of the kernels above.  List entries at or past `valid` do not count (the host pads
+// them with a loadable pointer).  Kept bitmaps are frontiers of different levels and never overlap; if two ever did, the
+// last listed one wins, as above.
+constexpr int kLabelTileWords = 64;                // 4096 vertices, 16 KiB of labels per 256-thread workgroup
+constexpr int kLabelSpan = kLabelTileWords + 2;    // plane words per tier: the run's kLabelTileWords + 1 and a window's upper word
+static_assert(kLabelSpan <= 128 && kLabelTileWords % 16 == 0, "phase 1 maps one tier to each half of the workgroup");
+constexpr unsigned kCodeWorkLabel = 13u;
+static_assert(kLevelMasks < kCodeWorkLabel && kCodeWorkLabel < 16u, "four code planes");
+
+typedef __attribute__((ext_vector_type(4))) unsigned LabelPlanes;  // the four code planes of one 32-bit half word
+
+// ORs into e[p] the window of plane p that starts at search-numbering id x, spread over the positions t4 of the quad
+__device__ __forceinline__ void TiledWindow(const LabelPlanes *planes, const unsigned char *spread, unsigned t4, unsigned x, unsigned first_half,
+                                            unsigned (&e)[4])
+{
+    const unsigned j = (x >> 5) - first_half;
+    const LabelPlanes lo = planes[j], hi = planes[j + 1];
+    const unsigned row = t4 << 4;
+#pragma unroll
+    for (int p = 0; p < 4; ++p)  // (v_alignbit shifts by x & 31; window bits past the tier's vertices of the quad are not looked at)
+        e[p] |= spread[row | (__builtin_amdgcn_alignbit(hi[p], lo[p], x) & 0xFu)];
+}
+
+// RELABEL: the search ran on the relabelled copy (bitmaps, d_work_* in its numbering; output in the caller's).  Otherwise
+// d_work_labels == d_labels, in place, and predecessors are not touched (they were written at discovery).
+template <typename VertexId, bool RELABEL, bool PRED>
+__global__ __launch_bounds__(256) void TiledLabelsKernel(LevelMaskList<VertexId> levels, const unsigned long long *d_visited,
+                                                         const unsigned long long *d_never, graphio::RelabelView map, long long nodes,
+                                                         VertexId src, const VertexId *d_work_labels, const VertexId *d_work_preds,
+                                                         const VertexId *d_old_of_new, VertexId *d_labels, VertexId *d_preds)
+{
+    typedef __attribute__((ext_vector_type(4))) int V4;
+    __shared__ LabelPlanes planes[2][2 * kLabelSpan];  // [0]: tier 1 (or the caller's numbering), [1]: tier 0; per 32-bit half
+    __shared__ uint2 s_tier[2][2 * kLabelTileWords];   // per half of a caller word: (tier mask, new id of its first tier vertex)
+    __shared__ int table[16];
+    __shared__ unsigned char spread[256];              // [t4 << 4 | c]: the low bits of c dealt to the set positions of t4
+    const int t = threadIdx.x;
+    const long long words = (nodes + 63) / 64;
+    const long long w0 = static_cast<long long>(blockIdx.x) * kLabelTileWords;
+    const bool hubs = RELABEL && map.hubs > 0;  // (uniform)
+    // first search-numbering word of the tile's tier-1 / tier-0 run (asked for before the gate words: one round trip)
+    long long xw1 = w0, xwh = 0;
+    if (RELABEL) {
+        xw1 = (map.hubs + map.d_base1[w0]) >> 6;
+        if (hubs) xwh = map.d_base0[w0] >> 6;
+    }
+    int valid = levels.count;
+    if (levels.d_gate) {  // (uniform)
+        const int go = levels.d_gate[0], filled = levels.d_gate[1];
+        if (go == 0) return;
+        valid = levels.chain_first + filled;
+    }
+    // phase 1
+    if (t < 16) table[t] = (t >= 1 && t <= kLevelMasks) ? levels.label[t - 1] : -1;
+    if (RELABEL) {
+        unsigned dealt = 0u;
+        for (int b = 0, r = 0; b < 4; ++b)
+            if ((t >> (4 + b)) & 1) {
+                dealt |= ((static_cast<unsigned>(t) >> r) & 1u) << b;
+                ++r;
+            }
+        spread[t] = static_cast<unsigned char>(dealt);
+    }
+    unsigned long long tile_edge = 0ull, tile_hub = 0ull;
+    unsigned tile_base1 = 0u, tile_base0 = 0u;
+    if (RELABEL && t < kLabelTileWords && w0 + t < words) {
+        tile_edge = map.d_edge[w0 + t];
+        tile_base1 = map.d_base1[w0 + t];
+        if (hubs) {
+            tile_hub = map.d_hub[w0 + t];
+            tile_base0 = map.d_base0[w0 + t];
+        }
+    }
+    const int tier = t >> 7, col = t & 127;
+    if (col < kLabelSpan && (tier == 0 || hubs)) {
+        const long long word = (tier ? xwh : xw1) + col;
+        const bool live = col < (RELABEL ? kLabelTileWords + 1 : kLabelTileWords) && word < words;
+        const long long at = live ? word : 0;
+        unsigned long long m[kLevelMasks];
+#pragma unroll
+        for (int k = 0; k < kLevelMasks; ++k) m[k] = levels.mask[k][at];
+        const unsigned long long vis = d_visited[at];
+        const unsigned long long nev = (!RELABEL && d_never) ? d_never[at] : 0ull;  // pre-marked "visited": never discovered
+        unsigned long long pl[4] = {0ull, 0ull, 0ull, 0ull}, later = 0ull;
+#pragma unroll
+        for (int k = kLevelMasks - 1; k >= 0; --k) {  // (last listed bitmap wins)
+            const unsigned long long own = (k < valid ? m[k] : 0ull) & ~later;
+            later |= own;
+#pragma unroll
+            for (int p = 0; p < 4; ++p)
+                if (((k + 1) >> p) & 1) pl[p] |= own;
+        }
+        const unsigned long long kept = vis & ~nev & ~later;
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            if ((kCodeWorkLabel >> p) & 1u) pl[p] |= kept;
+            if (!live) pl[p] = 0ull;
+        }
+        planes[tier][2 * col] = LabelPlanes{static_cast<unsigned>(pl[0]), static_cast<unsigned>(pl[1]), static_cast<unsigned>(pl[2]), static_cast<unsigned>(pl[3])};
+        planes[tier][2 * col + 1] = LabelPlanes{static_cast<unsigned>(pl[0] >> 32), static_cast<unsigned>(pl[1] >> 32), static_cast<unsigned>(pl[2] >> 32),
+                                                static_cast<unsigned>(pl[3] >> 32)};
+    }
+    if (RELABEL && t < kLabelTileWords) {
+        const unsigned e_lo = static_cast<unsigned>(tile_edge), h_lo = static_cast<unsigned>(tile_hub);
+        const unsigned x1 = static_cast<unsigned>(map.hubs) + tile_base1;
+        s_tier[0][2 * t] = make_uint2(e_lo, x1);
+        s_tier[0][2 * t + 1] = make_uint2(static_cast<unsigned>(tile_edge >> 32), x1 + __popc(e_lo));
+        s_tier[1][2 * t] = make_uint2(h_lo, tile_base0);
+        s_tier[1][2 * t + 1] = make_uint2(static_cast<unsigned>(tile_hub >> 32), tile_base0 + __popc(h_lo));
+    }
+    __syncthreads();
+    // phase 2: one quad (16-byte store) per lane and step, 1 KiB per wave store; the stores of a lane go out together at
+    // the end (a store between two steps makes the next step wait for it: its data registers are reused)
+    const int sh = (t & 15) * 4;
+    const int half = sh >> 5, s5 = sh & 31;
+    const unsigned below = (1u << s5) - 1u;
+    const unsigned first1 = static_cast<unsigned>(xw1) * 2u, firsth = static_cast<unsigned>(xwh) * 2u;
+    constexpr int kSteps = kLabelTileWords / 16;
+    int outs[kSteps][4], pouts[PRED ? kSteps : 1][4];
+#pragma unroll
+    for (int i = 0; i < kSteps; ++i) {
+        const int wi = i * 16 + (t >> 4);
+        const long long w = w0 + wi;
+        if (w >= words) continue;
+        const long long v0 = w * 64 + sh;
+        int(&out)[4] = outs[i];
+        unsigned e[4] = {0u, 0u, 0u, 0u};  // the quad's bits of the four planes, at the quad's positions
+        unsigned e4 = 0u, h4 = 0u, x1 = 0u, xh = 0u;
+        if (RELABEL) {
+            const uint2 m1 = s_tier[0][2 * wi + half];
+            e4 = (m1.x >> s5) & 0xFu;
+            x1 = m1.y + __popc(m1.x & below);
+            TiledWindow(planes[0], spread, e4, x1, first1, e);
+            if (hubs) {
+                const uint2 mh = s_tier[1][2 * wi + half];
+                h4 = (mh.x >> s5) & 0xFu;
+                xh = mh.y + __popc(mh.x & below);
+                TiledWindow(planes[1], spread, h4, xh, firsth, e);
+            }
+        } else {
+            const LabelPlanes c = planes[0][2 * wi + half];
+#pragma unroll
+            for (int p = 0; p < 4; ++p) e[p] = (c[p] >> s5) & 0xFu;
+        }
+        // plane p of vertex b at bit 6 p + b; times 0x8421 its four bits meet at bits 15 + b .. 18 + b (no two partial
+        // products share a bit, bits 13 + b and 14 + b stay clear): the byte offset into the label table
+        const unsigned packed = e[0] | (e[1] << 6) | (e[2] << 12) | (e[3] << 18);
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const unsigned at = (__umul24(packed & (0x041041u << b), 0x8421u) >> (13 + b)) & 0x3Cu;
+            out[b] = *reinterpret_cast<const int *>(reinterpret_cast<const char *>(table) + at);
+        }
+        int pout[4] = {-2, -2, -2, -2};
+        const unsigned work = e[0] & ~e[1] & e[2] & e[3];  // code 13
+        const bool src_here = static_cast<unsigned long long>(static_cast<long long>(src) - v0) < 4ull;
+        if (work || src_here || PRED) {  // (rare without predecessors)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                if (RELABEL) {
+                    const unsigned lower = (1u << b) - 1u;
+                    const bool in1 = (e4 >> b) & 1u, in0 = (h4 >> b) & 1u;
+                    const unsigned x = in1 ? x1 + __popc(e4 & lower) : xh + __popc(h4 & lower);
+                    if ((work >> b) & 1u) out[b] = d_work_labels[x];
+                    if (PRED && (in1 || in0)) {
+                        const VertexId p = d_work_preds[x];
+                        pout[b] = p >= 0 ? d_old_of_new[p] : p;
+                    }
+                    if (src == v0 + b && !in1 && !in0) {  // a source without edges
+                        out[b] = 0;
+                        pout[b] = -1;
+                    }
+                } else if ((((work >> b) & 1u) || src == v0 + b) && v0 + b < nodes) {
+                    out[b] = d_work_labels[v0 + b];  // (the source: Reset wrote its 0)
+                }
+            }
+        }
+        if (PRED)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) pouts[PRED ? i : 0][b] = pout[b];
+    }
+#pragma unroll
+    for (int i = 0; i < kSteps; ++i) {
+        const long long w = w0 + i * 16 + (t >> 4);
+        if (w >= words) continue;
+        const long long v0 = w * 64 + sh;
+        const int(&out)[4] = outs[i];
+        const int(&pout)[4] = pouts[PRED ? i : 0];
+        if (v0 + 3 < nodes) {
+            __builtin_nontemporal_store(V4{out[0], out[1], out[2], out[3]}, reinterpret_cast<V4 *>(d_labels + v0));
+            if (PRED) __builtin_nontemporal_store(V4{pout[0], pout[1], pout[2], pout[3]}, reinterpret_cast<V4 *>(d_preds + v0));
+        } else {
+            for (int b = 0; b < 4 && v0 + b < nodes; ++b) {
+                d_labels[v0 + b] = out[b];
+                if (PRED) d_preds[v0 + b] = pout[b];
+            }
+        }
+    }
+}
+
 // Static per graph and numbering, what a direction-optimizing search reads besides the CSR: the never-discovered mask, the
 // compact heads index and the heads (bottom_up.hpp).  BFSProblem holds one for the caller's numbering and, when it has built
 // the relabelled copy, one for the copy; Reset points graph_slices[0] and the DataSlice at the active one.
@@ -772,6 +990,7 @@ struct BFSProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
     bool defer_labels = true;       // policy (off: every kernel labels at discovery, Reset fills -1)
     bool emit_current = false;      // state: a speculative emit pass has run and no vertex has been discovered since
     bool labels_deferred = false;   // state: d_labels is incomplete until EmitLabels has run (set by Reset, cleared by EmitLabels)
+    int label_pass = 1;             // policy, read at every launch: 1 the tiled closing pass (TiledLabelsKernel), 0 the per-lane kernels
     int level_mask_limit = kLevelMasks;  // bitmaps of the pool a search may use (tests shrink it to force mid-search flushes)
     LevelMaskList<VertexId> level_masks; // (bitmap, label) of every kept level
     int mask_ring = 0;
@@ -842,6 +1061,26 @@ struct BFSProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
         const unsigned long long *nev = reinterpret_cast<const unsigned long long *>(ds->d_never_mask);
         const long long n = static_cast<long long>(this->nodes);
         const dim3 g(static_cast<unsigned>(grid)), b(256);
+        if (FULL && label_pass != 0) {  // the tiled pass: one kernel for every list length, either numbering
+            const bool copy = active == 1;
+            for (int k = list.count; k < kLevelMasks; ++k) {  // (entries past the count are loaded and not looked at)
+                list.mask[k] = list.count > 0 ? list.mask[0] : vis;
+                list.label[k] = -1;
+            }
+            const long long tiles = ((n + 63) / 64 + kLabelTileWords - 1) / kLabelTileWords;
+            const dim3 tg(static_cast<unsigned>(tiles > 0 ? tiles : 1));
+            if (copy) {
+                const VertexId csrc = (caller_source >= 0 && caller_source < this->nodes) ? caller_source : static_cast<VertexId>(-1);
+                hipLaunchKernelGGL((TiledLabelsKernel<VertexId, true, MARK_PREDECESSORS>), tg, b, 0, stream, list, vis, nev, relabelled.View(), n, csrc,
+                                   d_work_labels, d_work_preds, relabelled.d_old_of_new, d_out_labels, d_out_preds);
+                translate_pending = false;
+            } else {
+                hipLaunchKernelGGL((TiledLabelsKernel<VertexId, false, false>), tg, b, 0, stream, list, vis, nev, graphio::RelabelView(), n, src,
+                                   ds->d_labels, nullptr, nullptr, ds->d_labels, nullptr);
+            }
+            level_masks.count = 0;
+            return util::GRError(hipGetLastError(), "TiledLabelsKernel launch failed", __FILE__, __LINE__);
+        }
         if (FULL && active == 1) {  // the search ran on the relabelled copy: the pass writes the caller's order
             const graphio::RelabelView map = relabelled.View();
             const VertexId csrc = (caller_source >= 0 && caller_source < this->nodes) ? caller_source : static_cast<VertexId>(-1);

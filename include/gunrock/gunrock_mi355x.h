@@ -131,7 +131,9 @@ int grx_bfs_set_label_deferral(grx_bfs *p, int enabled, int mask_limit);
 /* Enactor tuning by name (returns 1 for an unknown name): "emit_queue_factor" (a compacting bottom-up sweep also writes its
  * finds as the next top-down queue when its input frontier is within this factor of the switch-back threshold),
  * "sparse_sweep_div", "speculative_emit" (1/0: the label pass is queued behind the closing top-down launch without waiting
- * for its read-back), "chain_sweeps" (bottom-up sweeps queued per host round trip).
+ * for its read-back), "chain_sweeps" (bottom-up sweeps queued per host round trip), "label_pass" (1, the default: the closing
+ * label pass loads every bitmap word once per workgroup tile; 0: the per-lane kernels it replaced; read at every launch of
+ * the pass, so it can be flipped between searches).
  * Relabelled copy (DESIGN.md 3.3 k): a symmetric problem (grx_bfs_set_inverse_graph without arrays, or grx_bfs_auto_inverse
  * on a symmetric graph) also builds a copy of its CSR renumbered hub-first, edgeless-last, and searches it; labels and
  * predecessors still come back in the caller's numbering.  "relabel" (1: search the copy; 0: the caller's numbering; -1, the
