@@ -1,4 +1,4 @@
-"""gunrockinst_amd -- MI355X-native frontier engine (BFS / CC / SSSP / BC / PageRank / TopK / MST) behind Gunrock's C ABI.
+"""gunrockinst_amd -- MI355X-native frontier engine (BFS / CC / SSSP / BC / PageRank / TopK / MST / MIS) behind Gunrock's C ABI.
 
 The product is the shared library ``gunrockinst_amd/lib/libgunrock.so`` (hand-written HIP for gfx950,
 built by ``gunrockinst_amd/csrc/Makefile``).  This package is only the host-side binding: ctypes
@@ -10,10 +10,12 @@ from .capi import (  # noqa: F401
     VTXID_INT, SIZET_INT, VALUE_INT, VALUE_UINT, VALUE_FLOAT, SRC_MANUALLY, SRC_RANDOMIZE, SRC_LARGEST_DEGREE,
     HostGraph, BfsProblem, CcProblem, SsspProblem, BcProblem, PrProblem, gunrock_bfs, gunrock_cc, gunrock_sssp, gunrock_bc,
     gunrock_pr, gunrock_topk, version, filter_queue, MstProblem, gunrock_mst,
+    MisProblem, gunrock_mis, gunrock_color, mis_priorities, MIS_SET, MIS_COLOR_ROUNDS, MIS_COLOR_FIRST_FIT,
 )
 
 __all__ = [
     "GunrockConfig", "GunrockDataType", "GunrockGraph", "LIB_PATH", "lib", "build_library",
     "HostGraph", "BfsProblem", "CcProblem", "SsspProblem", "BcProblem", "gunrock_bfs", "gunrock_cc", "gunrock_sssp",
     "gunrock_bc", "PrProblem", "gunrock_pr", "gunrock_topk", "version", "filter_queue", "MstProblem", "gunrock_mst",
+    "MisProblem", "gunrock_mis", "gunrock_color", "mis_priorities", "MIS_SET", "MIS_COLOR_ROUNDS", "MIS_COLOR_FIRST_FIT",
 ]

@@ -139,6 +139,18 @@ _SIGNATURES = {
     "grx_mst_extract": (C.c_int, [C.c_void_p, i32p, C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
     "grx_mst_device_results": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "grx_mst_destroy": (None, [C.c_void_p]),
+    "grx_mis_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int]),
+    "grx_mis_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p, i32p, C.c_uint]),
+    "grx_mis_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint]),
+    "grx_mis_set_tail": (C.c_int, [C.c_void_p, C.c_int]),
+    "grx_mis_reset": (C.c_int, [C.c_void_p]),
+    "grx_mis_enact": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "grx_mis_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
+                                C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_double)]),
+    "grx_mis_round_trace": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_double)]),
+    "grx_mis_extract": (C.c_int, [C.c_void_p, i32p, C.POINTER(C.c_longlong)]),
+    "grx_mis_device_results": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "grx_mis_destroy": (None, [C.c_void_p]),
     "grx_sssp_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int]),
     "grx_sssp_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p, C.POINTER(C.c_uint32), C.c_int]),
     "grx_sssp_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float]),
@@ -644,6 +656,123 @@ def gunrock_mst(nodes, row_offsets, col_indices, edge_values, device=0):
         return p.extract()
     finally:
         p.close()
+
+
+MIS_SET, MIS_COLOR_ROUNDS, MIS_COLOR_FIRST_FIT = 0, 1, 2  # enum GRX_MIS_* (gunrock_mi355x.h)
+
+
+def mis_priorities(nodes, seed=0):
+    """The hashed priorities grx_mis_* uses when none are passed: fmix32((uint32)v + seed * 0x9E3779B9) as uint32 (host helper:
+    the order is key(v) = (prio(v), v), prio compared as UNSIGNED here, as signed int32 for a caller's array)."""
+    h = (np.arange(int(nodes), dtype=np.uint64) + np.uint64((int(seed) * 0x9E3779B9) & 0xFFFFFFFF)) & np.uint64(0xFFFFFFFF)
+    h ^= h >> np.uint64(16)
+    h = (h * np.uint64(0x85EBCA6B)) & np.uint64(0xFFFFFFFF)
+    h ^= h >> np.uint64(13)
+    h = (h * np.uint64(0xC2B2AE35)) & np.uint64(0xFFFFFFFF)
+    h ^= h >> np.uint64(16)
+    return h.astype(np.uint32)
+
+
+class MisProblem:
+    """MISProblem + MISEnactor behind the handle C ABI: the lexicographically first maximal independent set and the two greedy
+    colourings of the CSR read as an undirected simple graph, unique under the order key(v) = (prio(v), v)."""
+
+    def __init__(self, instrument=False, device=0):
+        self._h = C.c_void_p()
+        _check(lib().grx_mis_create(C.byref(self._h), int(instrument), device), "grx_mis_create")
+        self.nodes = 0
+        self.edges = 0
+
+    def init(self, nodes, row_offsets, col_indices, priorities=None, seed=0):
+        ro = np.ascontiguousarray(row_offsets, dtype=np.int32)
+        ci = np.ascontiguousarray(col_indices, dtype=np.int32)
+        pr = None if priorities is None else np.ascontiguousarray(priorities, dtype=np.int32)
+        if pr is not None and pr.shape[0] != int(nodes):
+            raise ValueError("gunrockinst_amd: %d priorities for %d nodes" % (pr.shape[0], int(nodes)))
+        if ro.shape[0] != int(nodes) + 1:
+            raise ValueError("gunrockinst_amd: %d row offsets for %d nodes" % (ro.shape[0], int(nodes)))
+        self.nodes, self.edges = int(nodes), int(ci.shape[0])
+        _check(lib().grx_mis_init(self._h, self.nodes, self.edges, _p(ro), _p(ci), None if pr is None else _p(pr),
+                                  int(seed) & 0xFFFFFFFF), "MISProblem::Init")
+        return self
+
+    def init_device(self, nodes, edges, d_row_offsets, d_col_indices, d_priorities=None, seed=0):
+        self.nodes, self.edges = int(nodes), int(edges)
+        _check(lib().grx_mis_init_device(self._h, self.nodes, self.edges, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices),
+                                         C.c_void_p(d_priorities), int(seed) & 0xFFFFFFFF), "MISProblem::Init(device)")
+        return self
+
+    def set_tail(self, enable=True):
+        """False: one launch and one read-back per round to the end instead of the device-side tail loop (same result)"""
+        _check(lib().grx_mis_set_tail(self._h, int(bool(enable))), "grx_mis_set_tail")
+        return self
+
+    def reset(self):
+        _check(lib().grx_mis_reset(self._h), "MISProblem::Reset")
+
+    def enact(self, mode=MIS_SET, max_grid_size=0):
+        ms = C.c_float()
+        _check(lib().grx_mis_enact(self._h, int(mode), max_grid_size, C.byref(ms)), "MISEnactor::Enact")
+        return float(ms.value)
+
+    def stats(self):
+        r, t, e, q, l = C.c_longlong(), C.c_longlong(), C.c_longlong(), C.c_longlong(), C.c_longlong()
+        k = C.c_double()
+        _check(lib().grx_mis_stats(self._h, C.byref(r), C.byref(t), C.byref(e), C.byref(q), C.byref(l), C.byref(k)), "grx_mis_stats")
+        return {"rounds": r.value, "tail_sweeps": t.value, "entries_read": e.value, "polls": q.value, "kernel_launches": l.value,
+                "kernel_ms": k.value}
+
+    def round_trace(self, max_rounds=4096):
+        vertices = (C.c_longlong * max_rounds)()
+        ms = (C.c_double * max_rounds)()
+        n = lib().grx_mis_round_trace(self._h, max_rounds, vertices, ms)
+        n = min(max(n, 0), max_rounds)
+        return [{"vertices": vertices[i], "ms": ms[i]} for i in range(n)]
+
+    def extract(self, ids=True):
+        """(ids as int32 per vertex, or None; summary = the size of the set or the number of colours)"""
+        out = np.empty(max(self.nodes, 1), dtype=np.int32) if ids else None
+        summary = C.c_longlong()
+        _check(lib().grx_mis_extract(self._h, None if out is None else _p(out), C.byref(summary)), "MISProblem::Extract")
+        return (None if out is None else out[:self.nodes]), int(summary.value)
+
+    def device_results(self):
+        d = C.c_void_p()
+        _check(lib().grx_mis_device_results(self._h, C.byref(d)), "grx_mis_device_results")
+        return d.value
+
+    def close(self):
+        if self._h:
+            lib().grx_mis_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _mis_one_shot(mode, nodes, row_offsets, col_indices, priorities, seed, device):
+    p = MisProblem(device=device).init(nodes, row_offsets, col_indices, priorities, seed)
+    try:
+        p.reset()
+        p.enact(mode)
+        return p.extract()
+    finally:
+        p.close()
+
+
+def gunrock_mis(nodes, row_offsets, col_indices, priorities=None, seed=0, device=0):
+    """One-shot maximal independent set: returns (ids 0/1 per vertex, size of the set)."""
+    return _mis_one_shot(MIS_SET, nodes, row_offsets, col_indices, priorities, seed, device)
+
+
+def gunrock_color(nodes, row_offsets, col_indices, priorities=None, seed=0, first_fit=True, device=0):
+    """One-shot greedy colouring: returns (colour >= 1 per vertex, number of colours).  first_fit: Jones-Plassmann; else the
+    reference's independent-set rounds run to the end (colour = 1 + the largest colour among the larger-keyed neighbours)."""
+    return _mis_one_shot(MIS_COLOR_FIRST_FIT if first_fit else MIS_COLOR_ROUNDS, nodes, row_offsets, col_indices, priorities, seed,
+                         device)
 
 
 def gunrock_bc(nodes, row_offsets, col_indices, src=-1, queue_size=1.0, src_mode=SRC_MANUALLY, device=0):

@@ -245,6 +245,53 @@ int grx_mst_device_results(grx_mst *p, int **d_selected);
 void grx_mst_destroy(grx_mst *p);
 
 /* ------------------------------------------------------------------------------------------------
+ * MIS: MISProblem + MISEnactor (reference gunrock/app/mis/mis_problem.cuh:41-360, mis_enactor.cuh:40-440): a maximal
+ * independent set and two greedy colourings.  The CSR is read as an undirected simple graph: u and v are neighbours when v
+ * is in row u or u is in row v (self-loops ignored; unsorted rows, duplicates and asymmetric input allowed).  Vertices are
+ * ordered by key(v) = (prio(v), v), compared lexicographically: prio is the caller's array as signed int32, or -- priorities
+ * NULL -- fmix32((uint32)v + seed * 0x9E3779B9) as unsigned (fmix32 = MurmurHash3's 32-bit finaliser).  With H(v) = the
+ * neighbours of v with a larger key, each mode's result is the unique solution of its equation, which is what the sequential
+ * greedy pass over the vertices in descending key order writes:
+ *   GRX_MIS_SET              ids[v] = 1 iff no u in H(v) has ids[u] = 1, else 0 (the lexicographically first maximal set)
+ *   GRX_MIS_COLOR_ROUNDS     ids[v] = 1 + max(ids[u], u in H(v)), 1 when H(v) is empty: what the reference's schedule
+ *                            (mis_functor.cuh:84-89, mis_enactor.cuh:234-363) writes when run to the end with distinct labels
+ *   GRX_MIS_COLOR_FIRST_FIT  ids[v] = the smallest positive integer not among ids[u], u in H(v) (Jones-Plassmann)
+ * Unlike the reference: ties cannot occur (its `>=` lets two adjacent vertices with equal labels take one colour); there is
+ * no iteration cap (its driver stops after 20 and leaves -1), Enact runs to completion; the order is a seeded hash or the
+ * caller's, not std::random_shuffle.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct grx_mis grx_mis;
+enum { GRX_MIS_SET = 0, GRX_MIS_COLOR_ROUNDS = 1, GRX_MIS_COLOR_FIRST_FIT = 2 };
+
+int grx_mis_create(grx_mis **out, int instrument, int device);
+/* MISProblem::Init (reference mis_problem.cuh:145-310).  priorities: `nodes` values or NULL (hashed with `seed`).
+ * -1: nodes < 1, edges < 0 or a NULL array; -2: not a CSR of `nodes` vertices, as grx_mst_init; -3: the handle has been
+ * given a graph before (accepted or rejected): a handle takes one graph, create another */
+int grx_mis_init(grx_mis *p, int nodes, int edges, const int *row_offsets, const int *col_indices, const int *priorities,
+                 unsigned seed);
+/* the same for a CSR (and priorities, or NULL) already in HBM (borrowed, not freed) */
+int grx_mis_init_device(grx_mis *p, int nodes, int edges, int *d_row_offsets, int *d_col_indices, int *d_priorities, unsigned seed);
+/* enable = 0: one kernel launch and one read-back per round to the end, instead of finishing the long thin tail of the
+ * schedule in launches that loop on the device (the default).  The result is the same; for measurements. */
+int grx_mis_set_tail(grx_mis *p, int enable);
+/* MISProblem::Reset (reference mis_problem.cuh:320-346): every vertex undecided */
+int grx_mis_reset(grx_mis *p);
+/* MISEnactor::Enact(problem, max_grid_size) (reference mis_enactor.cuh:419) for one of the modes above, HIP-event timed */
+int grx_mis_enact(grx_mis *p, int mode, int max_grid_size, float *elapsed_ms);
+/* of the last Enact: host-visible sweeps (kernel launches with a read-back), sweeps made inside the device-side tail loop,
+ * row entries walked, polls (a blocked vertex asking its one blocking entry again), kernel launches (sweeps, tail windows and
+ * the two kernels around the tail's ordering; the radix sort's own kernels are not counted) and -- when instrumented -- the
+ * summed time of the rounds */
+int grx_mis_stats(grx_mis *p, long long *rounds, long long *tail_sweeps, long long *entries_read, long long *polls,
+                  long long *kernel_launches, double *kernel_ms);
+/* per host-visible round of the last Enact: undecided vertices it started with and (instrumented) its time; returns the rounds */
+int grx_mis_round_trace(grx_mis *p, int max_rounds, long long *vertices, double *ms);
+/* MISProblem::Extract(h_mis_ids) (reference mis_problem.cuh:106); summary = the size of the set, or the number of colours */
+int grx_mis_extract(grx_mis *p, int *h_ids /* may be NULL */, long long *summary);
+int grx_mis_device_results(grx_mis *p, int **d_ids);
+void grx_mis_destroy(grx_mis *p);
+
+/* ------------------------------------------------------------------------------------------------
  * SSSP: SSSPProblem + SSSPEnactor (reference gunrock/app/sssp/sssp_problem.cuh:35-387, sssp_enactor.cuh:36-563)
  * ---------------------------------------------------------------------------------------------- */
 typedef struct grx_sssp grx_sssp;
