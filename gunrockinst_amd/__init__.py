@@ -1,4 +1,4 @@
-"""gunrockinst_amd -- MI355X-native frontier engine (BFS / CC / SSSP / BC / PageRank / TopK / MST / MIS) behind Gunrock's C ABI.
+"""gunrockinst_amd -- MI355X-native frontier engine (BFS / CC / SSSP / BC / PageRank / TopK / MST / MIS / TC) behind Gunrock's C ABI.
 
 The product is the shared library ``gunrockinst_amd/lib/libgunrock.so`` (hand-written HIP for gfx950,
 built by ``gunrockinst_amd/csrc/Makefile``).  This package is only the host-side binding: ctypes
@@ -11,6 +11,7 @@ from .capi import (  # noqa: F401
     HostGraph, BfsProblem, CcProblem, SsspProblem, BcProblem, PrProblem, gunrock_bfs, gunrock_cc, gunrock_sssp, gunrock_bc,
     gunrock_pr, gunrock_topk, version, filter_queue, MstProblem, gunrock_mst,
     MisProblem, gunrock_mis, gunrock_color, mis_priorities, MIS_SET, MIS_COLOR_ROUNDS, MIS_COLOR_FIRST_FIT,
+    TcProblem, gunrock_tc, gunrock_clustering, TC_AUTO, TC_LANE, TC_LDS, TC_GLOBAL,
 )
 
 __all__ = [
@@ -18,4 +19,5 @@ __all__ = [
     "HostGraph", "BfsProblem", "CcProblem", "SsspProblem", "BcProblem", "gunrock_bfs", "gunrock_cc", "gunrock_sssp",
     "gunrock_bc", "PrProblem", "gunrock_pr", "gunrock_topk", "version", "filter_queue", "MstProblem", "gunrock_mst",
     "MisProblem", "gunrock_mis", "gunrock_color", "mis_priorities", "MIS_SET", "MIS_COLOR_ROUNDS", "MIS_COLOR_FIRST_FIT",
+    "TcProblem", "gunrock_tc", "gunrock_clustering", "TC_AUTO", "TC_LANE", "TC_LDS", "TC_GLOBAL",
 ]

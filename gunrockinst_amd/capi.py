@@ -151,6 +151,18 @@ _SIGNATURES = {
     "grx_mis_extract": (C.c_int, [C.c_void_p, i32p, C.POINTER(C.c_longlong)]),
     "grx_mis_device_results": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "grx_mis_destroy": (None, [C.c_void_p]),
+    "grx_tc_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int]),
+    "grx_tc_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p]),
+    "grx_tc_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "grx_tc_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
+    "grx_tc_reset": (C.c_int, [C.c_void_p]),
+    "grx_tc_enact": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
+    "grx_tc_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
+                               C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "grx_tc_extract": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "grx_tc_clustering": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "grx_tc_device_results": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "grx_tc_destroy": (None, [C.c_void_p]),
     "grx_sssp_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int]),
     "grx_sssp_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p, C.POINTER(C.c_uint32), C.c_int]),
     "grx_sssp_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float]),
@@ -773,6 +785,114 @@ def gunrock_color(nodes, row_offsets, col_indices, priorities=None, seed=0, firs
     reference's independent-set rounds run to the end (colour = 1 + the largest colour among the larger-keyed neighbours)."""
     return _mis_one_shot(MIS_COLOR_FIRST_FIT if first_fit else MIS_COLOR_ROUNDS, nodes, row_offsets, col_indices, priorities, seed,
                          device)
+
+
+TC_AUTO, TC_LANE, TC_LDS, TC_GLOBAL = 0, 1, 2, 3  # enum GRX_TC_* (gunrock_mi355x.h)
+
+
+class TcProblem:
+    """TCProblem + TCEnactor behind the handle C ABI: per-vertex triangle counts (int64), their total, clustering coefficients and
+    the transitivity of the CSR read as an undirected simple graph."""
+
+    def __init__(self, instrument=False, device=0):
+        self._h = C.c_void_p()
+        _check(lib().grx_tc_create(C.byref(self._h), int(instrument), device), "grx_tc_create")
+        self.nodes = 0
+        self.edges = 0
+
+    def init(self, nodes, row_offsets, col_indices):
+        ro = np.ascontiguousarray(row_offsets, dtype=np.int32)
+        ci = np.ascontiguousarray(col_indices, dtype=np.int32)
+        if ro.shape[0] != int(nodes) + 1:
+            raise ValueError("gunrockinst_amd: %d row offsets for %d nodes" % (ro.shape[0], int(nodes)))
+        self.nodes, self.edges = int(nodes), int(ci.shape[0])
+        _check(lib().grx_tc_init(self._h, self.nodes, self.edges, _p(ro), _p(ci)), "TCProblem::Init")
+        return self
+
+    def init_device(self, nodes, edges, d_row_offsets, d_col_indices):
+        self.nodes, self.edges = int(nodes), int(edges)
+        _check(lib().grx_tc_init_device(self._h, self.nodes, self.edges, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices)),
+               "TCProblem::Init(device)")
+        return self
+
+    def set_option(self, name, value):
+        """"strategy" (TC_AUTO / TC_LANE / TC_LDS / TC_GLOBAL), "lds_entries", "lane_max_row"; returns the library's code:
+        0 = set, 1 = unknown name (a value out of range raises)"""
+        rc = lib().grx_tc_set_option(self._h, name.encode(), float(value))
+        if rc not in (0, 1):
+            _check(rc, "grx_tc_set_option(%s)" % name)
+        return rc
+
+    def reset(self):
+        _check(lib().grx_tc_reset(self._h), "TCProblem::Reset")
+
+    def enact(self, max_grid_size=0):
+        ms = C.c_float()
+        _check(lib().grx_tc_enact(self._h, max_grid_size, C.byref(ms)), "TCEnactor::Enact")
+        return float(ms.value)
+
+    def stats(self):
+        o, r, e, l = C.c_longlong(), C.c_longlong(), C.c_longlong(), C.c_longlong()
+        rows = (C.c_longlong * 3)()
+        k, b = C.c_double(), C.c_double()
+        _check(lib().grx_tc_stats(self._h, C.byref(o), C.byref(r), C.byref(e), C.byref(l), rows, C.byref(k), C.byref(b)), "grx_tc_stats")
+        return {"oriented_edges": o.value, "max_out_row": r.value, "entries_probed": e.value, "kernel_launches": l.value,
+                "lane_rows": rows[0], "lds_rows": rows[1], "global_rows": rows[2], "kernel_ms": k.value, "build_ms": b.value}
+
+    def extract(self, triangles=True):
+        """(triangles as int64 per vertex, or None; the number of triangles of the graph)"""
+        out = np.empty(max(self.nodes, 1), dtype=np.int64) if triangles else None
+        total = C.c_longlong()
+        _check(lib().grx_tc_extract(self._h, None if out is None else out.ctypes.data_as(C.POINTER(C.c_longlong)), C.byref(total)),
+               "TCProblem::Extract")
+        return (None if out is None else out[:self.nodes]), int(total.value)
+
+    def clustering(self, coefficients=True):
+        """(clustering coefficient as float64 per vertex, or None; the transitivity of the graph)"""
+        out = np.empty(max(self.nodes, 1), dtype=np.float64) if coefficients else None
+        t = C.c_double()
+        _check(lib().grx_tc_clustering(self._h, None if out is None else out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(t)),
+               "TCProblem::Clustering")
+        return (None if out is None else out[:self.nodes]), float(t.value)
+
+    def device_results(self):
+        """(device pointer of the int64 counts, device pointer of the int32 degrees)"""
+        t, d = C.c_void_p(), C.c_void_p()
+        _check(lib().grx_tc_device_results(self._h, C.byref(t), C.byref(d)), "grx_tc_device_results")
+        return t.value, d.value
+
+    def close(self):
+        if self._h:
+            lib().grx_tc_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def gunrock_tc(nodes, row_offsets, col_indices, device=0):
+    """One-shot triangle counting: returns (triangles int64 per vertex, the number of triangles)."""
+    p = TcProblem(device=device).init(nodes, row_offsets, col_indices)
+    try:
+        p.reset()
+        p.enact()
+        return p.extract()
+    finally:
+        p.close()
+
+
+def gunrock_clustering(nodes, row_offsets, col_indices, device=0):
+    """One-shot clustering coefficients: returns (coefficient float64 per vertex, transitivity)."""
+    p = TcProblem(device=device).init(nodes, row_offsets, col_indices)
+    try:
+        p.reset()
+        p.enact()
+        return p.clustering()
+    finally:
+        p.close()
 
 
 def gunrock_bc(nodes, row_offsets, col_indices, src=-1, queue_size=1.0, src_mode=SRC_MANUALLY, device=0):

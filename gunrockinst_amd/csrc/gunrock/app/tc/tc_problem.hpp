@@ -1,0 +1,256 @@
+// app/tc/tc_problem.hpp -- device data for triangle counting and clustering coefficients.
+//
+// The reference snapshot has no app/tc; the shape is this tree's Problem (compare app/mis/mis_problem.hpp).  The input CSR is read
+// as MIS reads it: an undirected simple graph G in which u and v are neighbours when either row holds the other, self-loops
+// ignored, unsorted rows, duplicates and one-way edges allowed.  Init builds on the device, with the in-tree radix sort and scan:
+//   1. one key (min << cb | max) per CSR entry, self-loops as the sentinel; sorted; duplicates flagged off: the M edges of G
+//   2. d(v) by two atomic adds per edge
+//   3. every edge oriented from the endpoint with the smaller (d, id) to the larger, keyed (src << cb | dst) at its rank, sorted
+//      again: the oriented CSR with rows ascending by id; its offsets are the scanned out-degrees
+// Out-rows are short: v's out-neighbours all have d >= d+(v) (their (d, id) is larger and d+(v) <= d(v)), so the sum of degrees
+// 2M >= d+(v)^2, d+(v) <= floor(sqrt(2M)).
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <gunrock/app/problem_base.hpp>
+#include <gunrock/app/tc/tc_functor.hpp>
+#include <gunrock/graphio/device_sort.hpp>
+
+namespace gunrock {
+namespace app {
+namespace tc {
+
+template <bool _USE_DOUBLE_BUFFER>
+struct TCProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
+    typedef ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> Base;
+
+    struct DataSlice {
+        Count *d_triangles = nullptr;   // the result, one 64-bit count per vertex
+        unsigned *d_degrees = nullptr;  // d(v) in G
+        int *d_oro = nullptr;           // the oriented CSR
+        int *d_oci = nullptr;
+        int *d_osrc = nullptr;          // the row of every oriented entry
+        int *d_rows[2] = {nullptr, nullptr};  // the LDS and the global regime's row lists
+        int *d_words = nullptr;         // BinKernel's counters
+        Count *d_counters = nullptr;    // [0] triangles, [1] entries probed; [2] sum of C(d, 2), [3] the largest out-row
+        double *d_coeff = nullptr;      // clustering coefficients (allocated at the first request)
+    };
+
+    DataSlice **data_slices = nullptr;
+    int malformed = 0;            // Init found offsets or columns that are not a CSR of `nodes` vertices
+    long long oriented_edges = 0; // M
+    long long max_out_row = 0;
+    long long wedges = 0;         // sum over v of C(d(v), 2)
+    long long total = 0;          // of the last Extract
+    double build_ms = 0;          // HIP-event time of the oriented-graph build
+
+    ~TCProblem() override
+    {
+        if (data_slices) {
+            DataSlice *ds = data_slices[0];
+            if (ds) {
+                void *bufs[] = {ds->d_triangles, ds->d_degrees, ds->d_oro, ds->d_oci, ds->d_osrc, ds->d_rows[0], ds->d_rows[1], ds->d_words,
+                                ds->d_counters, ds->d_coeff};
+                for (void *b : bufs)
+                    if (b) util::GRError(hipFree(b), "TCProblem hipFree failed", __FILE__, __LINE__);
+                delete ds;
+            }
+            delete[] data_slices;
+        }
+    }
+
+    static int Grid(long long work)
+    {
+        long long blocks = (work + 255) / 256;
+        if (blocks < 1) blocks = 1;
+        if (blocks > 2048) blocks = 2048;  // 256 CUs x 8 workgroups, grid-stride the rest
+        return static_cast<int>(blocks);
+    }
+
+    Oriented DeviceGraph() const
+    {
+        const DataSlice *ds = data_slices[0];
+        return Oriented{ds->d_oro, ds->d_oci, ds->d_osrc};
+    }
+
+    hipError_t Build()
+    {
+        hipError_t retval = hipSuccess;
+        DataSlice *ds = data_slices[0];
+        GraphSlice<int, int, int> *gs = this->graph_slices[0];
+        hipStream_t stream = gs->stream;
+        const long long n = this->nodes, m = this->edges;
+        const size_t n1 = static_cast<size_t>(n > 0 ? n : 1);
+        GR_CHECK(hipMalloc(&ds->d_words, sizeof(int) * 4), "TCProblem hipMalloc failed");
+        GR_CHECK(hipMalloc(&ds->d_counters, sizeof(Count) * 4), "TCProblem hipMalloc failed");
+
+        // 1. the CSR must be one: the build indexes with what it reads
+        int bad = 0;
+        GR_CHECK(hipMemsetAsync(ds->d_words, 0, sizeof(int) * 4, stream), "TCProblem memset failed");
+        hipLaunchKernelGGL(ValidateCsrKernel, dim3(Grid((n > m ? n : m) + 1)), dim3(256), 0, stream, gs->d_row_offsets, gs->d_column_indices, n,
+                           m, ds->d_words);
+        GR_CHECK(hipGetLastError(), "ValidateCsrKernel launch failed");
+        GR_CHECK(hipMemcpyAsync(&bad, ds->d_words, sizeof(int), hipMemcpyDeviceToHost, stream), "TCProblem read-back failed");
+        GR_CHECK(hipStreamSynchronize(stream), "TCProblem read-back sync failed");
+        if (bad) {
+            malformed = 1;
+            return hipErrorInvalidValue;
+        }
+
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        GR_CHECK(hipEventCreate(&ev[0]), "TCProblem hipEventCreate failed");
+        GR_CHECK(hipEventCreate(&ev[1]), "TCProblem hipEventCreate failed");
+        GR_CHECK(hipEventRecord(ev[0], stream), "TCProblem hipEventRecord failed");
+
+        GR_CHECK(hipMalloc(&ds->d_triangles, sizeof(Count) * n1), "TCProblem hipMalloc d_triangles failed");
+        GR_CHECK(hipMalloc(&ds->d_degrees, sizeof(unsigned) * n1), "TCProblem hipMalloc d_degrees failed");
+        GR_CHECK(hipMalloc(&ds->d_oro, sizeof(int) * (n1 + 1)), "TCProblem hipMalloc d_oro failed");
+        GR_CHECK(hipMalloc(&ds->d_rows[0], sizeof(int) * n1), "TCProblem hipMalloc d_rows failed");
+        GR_CHECK(hipMalloc(&ds->d_rows[1], sizeof(int) * n1), "TCProblem hipMalloc d_rows failed");
+        GR_CHECK(hipMemsetAsync(ds->d_degrees, 0, sizeof(unsigned) * n1, stream), "TCProblem memset failed");
+        GR_CHECK(hipMemsetAsync(ds->d_oro, 0, sizeof(int) * (n1 + 1), stream), "TCProblem memset failed");
+        GR_CHECK(hipMemsetAsync(ds->d_counters, 0, sizeof(Count) * 4, stream), "TCProblem memset failed");
+
+        int col_bits = 1;
+        while ((1ll << col_bits) < n) ++col_bits;
+        const int key_bits = 2 * col_bits;  // <= 62
+        const unsigned long long sentinel = (1ull << key_bits) - 1ull;  // min = max = 2^cb - 1: never an edge
+        unsigned *d_keep = nullptr;  // the keep flags, then the out-degrees
+        unsigned long long *d_pos = nullptr, *d_sums = nullptr;
+        const long long flag_words = m > n + 1 ? m : n + 1;
+        graphio::DeviceKeySort edge_sort, oriented_sort;
+        oriented_edges = 0;
+        if (m > 0) {
+            GR_CHECK(hipMalloc(&d_keep, sizeof(unsigned) * static_cast<size_t>(flag_words)), "TCProblem hipMalloc failed");
+            GR_CHECK(hipMalloc(&d_pos, sizeof(unsigned long long) * static_cast<size_t>(m)), "TCProblem hipMalloc failed");
+            GR_CHECK(hipMalloc(&d_sums, sizeof(unsigned long long) * static_cast<size_t>(graphio::ScanScratchWords(flag_words))),
+                     "TCProblem hipMalloc failed");
+            GR_CHECK(edge_sort.Reserve(m), "TCProblem sort scratch failed");
+            hipLaunchKernelGGL(EdgeKeysKernel, dim3(Grid(m)), dim3(256), 0, stream, gs->d_row_offsets, gs->d_column_indices, static_cast<int>(n), m,
+                               col_bits, sentinel, edge_sort.Keys());
+            GR_CHECK(hipGetLastError(), "EdgeKeysKernel launch failed");
+            unsigned long long *d_sorted = nullptr;
+            GR_CHECK(edge_sort.Sort(m, key_bits, stream, &d_sorted), "TCProblem edge sort failed");
+            hipLaunchKernelGGL(graphio::FlagKernel, dim3(Grid(m)), dim3(256), 0, stream, d_sorted, m, sentinel, d_keep);
+            GR_CHECK(hipGetLastError(), "FlagKernel launch failed");
+            GR_CHECK(graphio::DeviceExclusiveScan<unsigned long long>(d_keep, d_pos, m, d_sums, stream), "TCProblem flag scan failed");
+            unsigned long long kept = 0;  // ScanSumsKernel leaves the total behind the tile offsets
+            const long long scan_tiles = (m + graphio::kScanTile - 1) / graphio::kScanTile;
+            GR_CHECK(hipMemcpyAsync(&kept, d_sums + scan_tiles, sizeof(kept), hipMemcpyDeviceToHost, stream), "TCProblem read-back failed");
+            GR_CHECK(hipStreamSynchronize(stream), "TCProblem read-back sync failed");
+            oriented_edges = static_cast<long long>(kept);
+
+            if (oriented_edges > 0) {
+                hipLaunchKernelGGL(DegreeKernel, dim3(Grid(m)), dim3(256), 0, stream, d_sorted, d_keep, m, col_bits, ds->d_degrees);
+                GR_CHECK(hipGetLastError(), "DegreeKernel launch failed");
+                GR_CHECK(oriented_sort.Reserve(oriented_edges), "TCProblem sort scratch failed");
+                unsigned *d_outdeg = nullptr;  // n + 1 words, the last one 0: its scan is the offsets
+                GR_CHECK(hipMalloc(&d_outdeg, sizeof(unsigned) * (n1 + 1)), "TCProblem hipMalloc failed");
+                GR_CHECK(hipMemsetAsync(d_outdeg, 0, sizeof(unsigned) * (n1 + 1), stream), "TCProblem memset failed");
+                hipLaunchKernelGGL(OrientKernel, dim3(Grid(m)), dim3(256), 0, stream, d_sorted, d_keep, d_pos, m, col_bits, ds->d_degrees,
+                                   oriented_sort.Keys(), d_outdeg);
+                GR_CHECK(hipGetLastError(), "OrientKernel launch failed");
+                GR_CHECK(graphio::DeviceExclusiveScan<int>(d_outdeg, ds->d_oro, n + 1, d_sums, stream), "TCProblem offset scan failed");
+                unsigned long long *d_osorted = nullptr;
+                GR_CHECK(oriented_sort.Sort(oriented_edges, key_bits, stream, &d_osorted), "TCProblem oriented sort failed");
+                GR_CHECK(hipMalloc(&ds->d_oci, sizeof(int) * static_cast<size_t>(oriented_edges)), "TCProblem hipMalloc d_oci failed");
+                GR_CHECK(hipMalloc(&ds->d_osrc, sizeof(int) * static_cast<size_t>(oriented_edges)), "TCProblem hipMalloc d_osrc failed");
+                hipLaunchKernelGGL(EmitOrientedKernel, dim3(Grid(oriented_edges)), dim3(256), 0, stream, d_osorted, oriented_edges, col_bits, ds->d_oci,
+                                   ds->d_osrc);
+                GR_CHECK(hipGetLastError(), "EmitOrientedKernel launch failed");
+                GR_CHECK(hipStreamSynchronize(stream), "TCProblem build sync failed");
+                GR_CHECK(hipFree(d_outdeg), "TCProblem hipFree failed");
+            }
+        }
+        hipLaunchKernelGGL(RowSummaryKernel, dim3(Grid(n)), dim3(256), 0, stream, ds->d_degrees, ds->d_oro, n, ds->d_counters + 2);
+        GR_CHECK(hipGetLastError(), "RowSummaryKernel launch failed");
+        Count summary[2] = {0, 0};
+        GR_CHECK(hipMemcpyAsync(summary, ds->d_counters + 2, sizeof(summary), hipMemcpyDeviceToHost, stream), "TCProblem read-back failed");
+        GR_CHECK(hipEventRecord(ev[1], stream), "TCProblem hipEventRecord failed");
+        GR_CHECK(hipStreamSynchronize(stream), "TCProblem build sync failed");
+        float ms = 0;
+        GR_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]), "TCProblem hipEventElapsedTime failed");
+        build_ms = ms;
+        hipEventDestroy(ev[0]);
+        hipEventDestroy(ev[1]);
+        wedges = static_cast<long long>(summary[0]);
+        max_out_row = static_cast<long long>(summary[1]);
+        if (d_keep) GR_CHECK(hipFree(d_keep), "TCProblem hipFree failed");
+        if (d_pos) GR_CHECK(hipFree(d_pos), "TCProblem hipFree failed");
+        if (d_sums) GR_CHECK(hipFree(d_sums), "TCProblem hipFree failed");
+        return retval;
+    }
+
+    // One Init per object (grx_tc_init refuses a second one)
+    hipError_t Init(bool stream_from_host, const Csr<int, int, int> &graph, int num_gpus = 1)
+    {
+        hipError_t retval = hipSuccess;
+        if ((retval = Base::Init(stream_from_host, graph, num_gpus, false))) return retval;
+        data_slices = new DataSlice *[1];
+        data_slices[0] = new DataSlice();
+        return Build();
+    }
+
+    hipError_t InitFromDevice(int nodes, int edges, int *d_row_offsets, int *d_column_indices)
+    {
+        hipError_t retval = hipSuccess;
+        if ((retval = Base::InitFromDevice(nodes, edges, d_row_offsets, d_column_indices))) return retval;
+        data_slices = new DataSlice *[1];
+        data_slices[0] = new DataSlice();
+        return Build();
+    }
+
+    // the counts to zero
+    hipError_t Reset(FrontierType /*frontier_type*/ = VERTEX_FRONTIERS)
+    {
+        hipError_t retval = hipSuccess;
+        DataSlice *ds = data_slices[0];
+        hipStream_t stream = this->graph_slices[0]->stream;
+        GR_CHECK(hipMemsetAsync(ds->d_triangles, 0, sizeof(Count) * static_cast<size_t>(this->nodes), stream), "TCProblem memset failed");
+        GR_CHECK(hipMemsetAsync(ds->d_counters, 0, sizeof(Count) * 2, stream), "TCProblem memset failed");
+        GR_CHECK(hipMemsetAsync(ds->d_words, 0, sizeof(int) * 4, stream), "TCProblem memset failed");
+        GR_CHECK(hipStreamSynchronize(stream), "TCProblem Reset sync failed");
+        total = 0;
+        return retval;
+    }
+
+    // h_triangles may be NULL: then only the total is read
+    hipError_t Extract(long long *h_triangles)
+    {
+        hipError_t retval = hipSuccess;
+        DataSlice *ds = data_slices[0];
+        hipStream_t stream = this->graph_slices[0]->stream;
+        Count t = 0;
+        GR_CHECK(hipMemcpyAsync(&t, ds->d_counters, sizeof(t), hipMemcpyDeviceToHost, stream), "TCProblem read total failed");
+        if (h_triangles)
+            GR_CHECK(hipMemcpyAsync(h_triangles, ds->d_triangles, sizeof(Count) * static_cast<size_t>(this->nodes), hipMemcpyDeviceToHost, stream),
+                     "TCProblem read d_triangles failed");
+        GR_CHECK(hipStreamSynchronize(stream), "TCProblem Extract sync failed");
+        total = static_cast<long long>(t);
+        return retval;
+    }
+
+    // h_coeff may be NULL: then only the transitivity 3 total / sum C(d, 2) is computed (one double division; 0 for no wedge)
+    hipError_t Clustering(double *h_coeff, double *transitivity)
+    {
+        hipError_t retval = hipSuccess;
+        DataSlice *ds = data_slices[0];
+        hipStream_t stream = this->graph_slices[0]->stream;
+        if ((retval = Extract(nullptr))) return retval;
+        if (transitivity) *transitivity = wedges > 0 ? static_cast<double>(3 * total) / static_cast<double>(wedges) : 0.0;
+        if (!h_coeff) return retval;
+        const size_t n = static_cast<size_t>(this->nodes);
+        if (!ds->d_coeff) GR_CHECK(hipMalloc(&ds->d_coeff, sizeof(double) * n), "TCProblem hipMalloc d_coeff failed");
+        hipLaunchKernelGGL(ClusteringKernel, dim3(Grid(this->nodes)), dim3(256), 0, stream, ds->d_triangles, ds->d_degrees,
+                           static_cast<long long>(this->nodes), ds->d_coeff);
+        GR_CHECK(hipGetLastError(), "ClusteringKernel launch failed");
+        GR_CHECK(hipMemcpyAsync(h_coeff, ds->d_coeff, sizeof(double) * n, hipMemcpyDeviceToHost, stream), "TCProblem read d_coeff failed");
+        GR_CHECK(hipStreamSynchronize(stream), "TCProblem Clustering sync failed");
+        return retval;
+    }
+};
+
+}  // namespace tc
+}  // namespace app
+}  // namespace gunrock

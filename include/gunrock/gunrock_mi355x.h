@@ -292,6 +292,50 @@ int grx_mis_device_results(grx_mis *p, int **d_ids);
 void grx_mis_destroy(grx_mis *p);
 
 /* ------------------------------------------------------------------------------------------------
+ * TC: TCProblem + TCEnactor: triangle counts and clustering coefficients (the reference snapshot has no app/tc; later Gunrock
+ * releases do).  The CSR is read as grx_mis_* reads it: the simple undirected graph G in which u and v are neighbours when v
+ * is in row u or u is in row v (self-loops ignored; unsorted rows, duplicates and one-way edges allowed), with M edges and
+ * degrees d(v).  Every result has exactly one value:
+ *   triangles[v]   the number of unordered pairs of neighbours of v that are neighbours (64-bit)
+ *   total          the number of triangles of G = sum(triangles) / 3 (64-bit)
+ *   clustering[v]  2 triangles[v] / (d(v) (d(v) - 1)) as one double division, 0.0 where d(v) < 2
+ *   transitivity   3 total / sum over v of C(d(v), 2) as one double division, 0.0 when there is no wedge
+ * Init orients every edge from the endpoint with the smaller (d, id) to the larger (no out-row exceeds floor(sqrt(2 M))) and
+ * Enact intersects the out-rows of the two ends of every oriented edge, in one of three regimes picked by the row's length.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct grx_tc grx_tc;
+enum { GRX_TC_AUTO = 0, GRX_TC_LANE = 1, GRX_TC_LDS = 2, GRX_TC_GLOBAL = 3 };
+
+int grx_tc_create(grx_tc **out, int instrument, int device);
+/* TCProblem::Init: validates the CSR and builds the oriented graph on the device.  -1: nodes < 1, edges < 0 or a NULL array;
+ * -2: not a CSR of `nodes` vertices, as grx_mis_init; -3: the handle has been given a graph before (accepted or rejected) */
+int grx_tc_init(grx_tc *p, int nodes, int edges, const int *row_offsets, const int *col_indices);
+/* the same for a CSR already in HBM (borrowed, not freed) */
+int grx_tc_init_device(grx_tc *p, int nodes, int edges, int *d_row_offsets, int *d_col_indices);
+/* named options, for the next Enact; 0: set, 1: unknown name, -1: a value out of range.
+ *   "strategy"      GRX_TC_AUTO (default): rows up to "lane_max_row" entries take one lane per oriented edge, rows up to
+ *                   "lds_entries" one workgroup with the row staged in LDS, longer rows one workgroup probing the row in global
+ *                   memory; GRX_TC_LANE / GRX_TC_LDS / GRX_TC_GLOBAL force that regime for every row (under GRX_TC_LDS a row
+ *                   beyond "lds_entries" still takes the global one).  The result does not depend on it.
+ *   "lds_entries"   the staging budget in row entries (default 4096, at most 8192: 8 bytes of LDS each)
+ *   "lane_max_row"  the longest row of the lane regime under GRX_TC_AUTO (default 32) */
+int grx_tc_set_option(grx_tc *p, const char *name, double value);
+/* TCProblem::Reset: the counts to zero */
+int grx_tc_reset(grx_tc *p);
+/* TCEnactor::Enact(problem, max_grid_size), HIP-event timed */
+int grx_tc_enact(grx_tc *p, int max_grid_size, float *elapsed_ms);
+/* oriented edges (M) and the largest out-row of the graph; of the last Enact: row entries streamed through an intersection,
+ * kernel launches, the non-empty rows the lane / LDS / global regimes took (regime_rows[3], may be NULL) and -- when
+ * instrumented -- the summed kernel time; build_ms: the HIP-event time of Init's oriented-graph build */
+int grx_tc_stats(grx_tc *p, long long *oriented_edges, long long *max_out_row, long long *entries_probed, long long *kernel_launches,
+                 long long *regime_rows, double *kernel_ms, double *build_ms);
+int grx_tc_extract(grx_tc *p, long long *h_triangles /* may be NULL */, long long *total);
+int grx_tc_clustering(grx_tc *p, double *h_coeff /* may be NULL */, double *transitivity);
+/* device arrays of the handle: 64-bit counts and 32-bit degrees d(v), `nodes` each */
+int grx_tc_device_results(grx_tc *p, long long **d_triangles, int **d_degrees);
+void grx_tc_destroy(grx_tc *p);
+
+/* ------------------------------------------------------------------------------------------------
  * SSSP: SSSPProblem + SSSPEnactor (reference gunrock/app/sssp/sssp_problem.cuh:35-387, sssp_enactor.cuh:36-563)
  * ---------------------------------------------------------------------------------------------- */
 typedef struct grx_sssp grx_sssp;
