@@ -1,4 +1,4 @@
-"""gunrockinst_amd -- MI355X-native frontier engine (BFS / CC / SSSP / BC / PageRank / TopK / MST / MIS / TC) behind Gunrock's C ABI.
+"""gunrockinst_amd -- MI355X-native frontier engine (BFS / CC / SSSP / BC / PageRank / TopK / MST / MIS / TC / k-core) behind Gunrock's C ABI.
 
 The product is the shared library ``gunrockinst_amd/lib/libgunrock.so`` (hand-written HIP for gfx950,
 built by ``gunrockinst_amd/csrc/Makefile``).  This package is only the host-side binding: ctypes
@@ -12,6 +12,7 @@ from .capi import (  # noqa: F401
     gunrock_pr, gunrock_topk, version, filter_queue, MstProblem, gunrock_mst,
     MisProblem, gunrock_mis, gunrock_color, mis_priorities, MIS_SET, MIS_COLOR_ROUNDS, MIS_COLOR_FIRST_FIT,
     TcProblem, gunrock_tc, gunrock_clustering, TC_AUTO, TC_LANE, TC_LDS, TC_GLOBAL,
+    KcoreProblem, gunrock_kcore, gunrock_kcore_members, KCORE_AUTO, KCORE_ROUNDS, KCORE_DEVICE_LOOP,
 )
 
 __all__ = [
@@ -20,4 +21,5 @@ __all__ = [
     "gunrock_bc", "PrProblem", "gunrock_pr", "gunrock_topk", "version", "filter_queue", "MstProblem", "gunrock_mst",
     "MisProblem", "gunrock_mis", "gunrock_color", "mis_priorities", "MIS_SET", "MIS_COLOR_ROUNDS", "MIS_COLOR_FIRST_FIT",
     "TcProblem", "gunrock_tc", "gunrock_clustering", "TC_AUTO", "TC_LANE", "TC_LDS", "TC_GLOBAL",
+    "KcoreProblem", "gunrock_kcore", "gunrock_kcore_members", "KCORE_AUTO", "KCORE_ROUNDS", "KCORE_DEVICE_LOOP",
 ]

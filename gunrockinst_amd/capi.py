@@ -163,6 +163,19 @@ _SIGNATURES = {
     "grx_tc_clustering": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "grx_tc_device_results": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "grx_tc_destroy": (None, [C.c_void_p]),
+    "grx_kcore_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int]),
+    "grx_kcore_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p]),
+    "grx_kcore_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "grx_kcore_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
+    "grx_kcore_reset": (C.c_int, [C.c_void_p]),
+    "grx_kcore_enact": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "grx_kcore_stats": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_longlong)] * 8 + [C.POINTER(C.c_double)] * 2),
+    "grx_kcore_level_trace": (C.c_int, [C.c_void_p, C.c_int, i32p, C.POINTER(C.c_longlong), C.POINTER(C.c_double)]),
+    "grx_kcore_extract": (C.c_int, [C.c_void_p, i32p, C.POINTER(C.c_int)]),
+    "grx_kcore_shells": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_longlong)]),
+    "grx_kcore_members": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_ubyte), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "grx_kcore_device_results": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "grx_kcore_destroy": (None, [C.c_void_p]),
     "grx_sssp_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int]),
     "grx_sssp_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p, C.POINTER(C.c_uint32), C.c_int]),
     "grx_sssp_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float]),
@@ -891,6 +904,138 @@ def gunrock_clustering(nodes, row_offsets, col_indices, device=0):
         p.reset()
         p.enact()
         return p.clustering()
+    finally:
+        p.close()
+
+
+KCORE_AUTO, KCORE_ROUNDS, KCORE_DEVICE_LOOP = 0, 1, 2  # enum GRX_KCORE_* (gunrock_mi355x.h)
+
+
+class KcoreProblem:
+    """KcoreProblem + KcoreEnactor behind the handle C ABI: the core number of every vertex (int32), the degeneracy, the shell
+    sizes and the k-cores of the CSR read as an undirected simple graph."""
+
+    _STATS = ("simple_edges", "max_degree", "levels", "rounds", "vertices_peeled", "entries_read", "compactions", "kernel_launches")
+
+    def __init__(self, instrument=False, device=0):
+        self._h = C.c_void_p()
+        _check(lib().grx_kcore_create(C.byref(self._h), int(instrument), device), "grx_kcore_create")
+        self.nodes = 0
+        self.edges = 0
+
+    def init(self, nodes, row_offsets, col_indices):
+        ro = np.ascontiguousarray(row_offsets, dtype=np.int32)
+        ci = np.ascontiguousarray(col_indices, dtype=np.int32)
+        if ro.shape[0] != int(nodes) + 1:
+            raise ValueError("gunrockinst_amd: %d row offsets for %d nodes" % (ro.shape[0], int(nodes)))
+        self.nodes, self.edges = int(nodes), int(ci.shape[0])
+        _check(lib().grx_kcore_init(self._h, self.nodes, self.edges, _p(ro), _p(ci)), "KcoreProblem::Init")
+        return self
+
+    def init_device(self, nodes, edges, d_row_offsets, d_col_indices):
+        self.nodes, self.edges = int(nodes), int(edges)
+        _check(lib().grx_kcore_init_device(self._h, self.nodes, self.edges, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices)),
+               "KcoreProblem::Init(device)")
+        return self
+
+    def set_option(self, name, value):
+        """"schedule" (KCORE_AUTO / KCORE_ROUNDS / KCORE_DEVICE_LOOP), "compact_below", "wave_min_row", "loop_max_list",
+        "loop_max_entries"; returns the library's code: 0 = set, 1 = unknown name (a value out of range raises)"""
+        rc = lib().grx_kcore_set_option(self._h, name.encode(), float(value))
+        if rc not in (0, 1):
+            _check(rc, "grx_kcore_set_option(%s)" % name)
+        return rc
+
+    def reset(self):
+        _check(lib().grx_kcore_reset(self._h), "KcoreProblem::Reset")
+
+    def enact(self, k_limit=-1, max_grid_size=0):
+        ms = C.c_float()
+        _check(lib().grx_kcore_enact(self._h, int(k_limit), max_grid_size, C.byref(ms)), "KcoreEnactor::Enact")
+        return float(ms.value)
+
+    def stats(self):
+        v = [C.c_longlong() for _ in self._STATS]
+        k, b = C.c_double(), C.c_double()
+        _check(lib().grx_kcore_stats(self._h, *([C.byref(x) for x in v] + [C.byref(k), C.byref(b)])), "grx_kcore_stats")
+        out = {name: x.value for name, x in zip(self._STATS, v)}
+        out["kernel_ms"], out["build_ms"] = k.value, b.value
+        return out
+
+    def level_trace(self):
+        """the non-empty levels of the last enact: (k as int32, vertices peeled at it as int64, milliseconds as float64)"""
+        count = lib().grx_kcore_level_trace(self._h, 0, None, None, None)
+        if count < 0:
+            _check(count, "grx_kcore_level_trace")
+        k = np.empty(max(count, 1), dtype=np.int32)
+        vertices = np.empty(max(count, 1), dtype=np.int64)
+        ms = np.empty(max(count, 1), dtype=np.float64)
+        lib().grx_kcore_level_trace(self._h, count, _p(k), vertices.ctypes.data_as(C.POINTER(C.c_longlong)),
+                                    ms.ctypes.data_as(C.POINTER(C.c_double)))
+        return k[:count], vertices[:count], ms[:count]
+
+    def extract(self, core=True):
+        """(core numbers as int32 per vertex, or None; the degeneracy)"""
+        out = np.empty(max(self.nodes, 1), dtype=np.int32) if core else None
+        d = C.c_int()
+        _check(lib().grx_kcore_extract(self._h, None if out is None else _p(out), C.byref(d)), "KcoreProblem::Extract")
+        return (None if out is None else out[:self.nodes]), int(d.value)
+
+    def shells(self):
+        """shell sizes as int64: entry k is the number of vertices with core number k, k = 0 .. degeneracy"""
+        count = lib().grx_kcore_shells(self._h, 0, None)
+        if count < 0:
+            _check(-count, "KcoreProblem::Shells")
+        out = np.empty(max(count, 1), dtype=np.int64)
+        rc = lib().grx_kcore_shells(self._h, count, out.ctypes.data_as(C.POINTER(C.c_longlong)))
+        if rc < 0:
+            _check(-rc, "KcoreProblem::Shells")
+        return out[:count]
+
+    def members(self, k, mask=True):
+        """the k-core: (mask core >= k as uint8 per vertex, or None; its vertices; the edges of the graph inside it)"""
+        out = np.empty(max(self.nodes, 1), dtype=np.uint8) if mask else None
+        v, e = C.c_longlong(), C.c_longlong()
+        _check(lib().grx_kcore_members(self._h, int(k), None if out is None else out.ctypes.data_as(C.POINTER(C.c_ubyte)), C.byref(v),
+                                       C.byref(e)), "KcoreProblem::Members")
+        return (None if out is None else out[:self.nodes]), int(v.value), int(e.value)
+
+    def device_results(self):
+        """(device pointer of the int32 core numbers, device pointer of the int32 degrees)"""
+        c, d = C.c_void_p(), C.c_void_p()
+        _check(lib().grx_kcore_device_results(self._h, C.byref(c), C.byref(d)), "grx_kcore_device_results")
+        return c.value, d.value
+
+    def close(self):
+        if self._h:
+            lib().grx_kcore_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def gunrock_kcore(nodes, row_offsets, col_indices, device=0):
+    """One-shot k-core decomposition: returns (core numbers int32 per vertex, the degeneracy)."""
+    p = KcoreProblem(device=device).init(nodes, row_offsets, col_indices)
+    try:
+        p.reset()
+        p.enact()
+        return p.extract()
+    finally:
+        p.close()
+
+
+def gunrock_kcore_members(nodes, row_offsets, col_indices, k, device=0):
+    """One-shot k-core extraction (peels the levels below k only): returns (mask uint8 per vertex, vertices, edges inside)."""
+    p = KcoreProblem(device=device).init(nodes, row_offsets, col_indices)
+    try:
+        p.reset()
+        p.enact(k_limit=k)
+        return p.members(k)
     finally:
         p.close()
 

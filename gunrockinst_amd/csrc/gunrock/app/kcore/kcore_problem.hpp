@@ -1,0 +1,305 @@
+// app/kcore/kcore_problem.hpp -- device data for the k-core decomposition.
+//
+// The reference snapshot has no app/kcore; the shape is this tree's Problem (compare app/tc/tc_problem.hpp).  The input CSR is read
+// as MIS and TC read it: an undirected simple graph G in which u and v are neighbours when either row holds the other, self-loops
+// ignored, unsorted rows, duplicates and one-way edges allowed.  Init builds on the device, with the in-tree radix sort and scan:
+//   1. one key (min << cb | max) per CSR entry, self-loops as the sentinel; sorted; duplicates flagged off: the M edges of G
+//      (TC's first step, with TC's kernels: tc_functor.hpp is included, not changed)
+//   2. d(v) by two atomic adds per edge; its exclusive scan is the offsets of the neighbour CSR, 2M entries
+//   3. both directions of every edge scattered through per-row cursors: the symmetric simple neighbour CSR (rows unordered)
+// core[] is the working array and the result (kcore_functor.hpp): Reset copies d(v) into it.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <gunrock/app/kcore/kcore_functor.hpp>
+#include <gunrock/app/problem_base.hpp>
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wunused-function"  // (only TC's build kernels are used here)
+#include <gunrock/app/tc/tc_functor.hpp>
+#pragma clang diagnostic pop
+#include <gunrock/graphio/device_sort.hpp>
+
+namespace gunrock {
+namespace app {
+namespace kcore {
+
+template <bool _USE_DOUBLE_BUFFER>
+struct KcoreProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
+    typedef ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> Base;
+
+    struct DataSlice {
+        int *d_core = nullptr;       // the working degrees, then the result
+        int *d_degrees = nullptr;    // d(v) in G (nodes + 1 words, the last 0: scanned into the offsets)
+        int *d_nro = nullptr;        // the neighbour CSR
+        int *d_nci = nullptr;
+        int *d_queue = nullptr;      // every vertex once, in peeling order
+        int *d_list[2] = {nullptr, nullptr};  // the live list, rebuilt from one into the other
+        unsigned *d_words = nullptr;          // W_* of kcore_functor.hpp
+        unsigned long long *d_counters = nullptr;  // [0] row entries walked; [1], [2] Members' counts; [3] the end of the trace's clock
+        int *d_trace_k = nullptr;    // one entry per level scan (max degree + 1: levels are distinct values)
+        int *d_trace_tail = nullptr;
+        unsigned long long *d_trace_clock = nullptr;
+        unsigned long long *d_shell = nullptr;  // allocated at the first request
+        unsigned char *d_mask = nullptr;        // allocated at the first request
+    };
+
+    DataSlice **data_slices = nullptr;
+    int malformed = 0;           // Init found offsets or columns that are not a CSR of `nodes` vertices
+    long long simple_edges = 0;  // M
+    long long max_degree = 0;
+    long long min_degree = 0;    // the smallest positive d(v)
+    long long zeros = 0;         // vertices with d(v) = 0
+    long long trace_capacity = 0;
+    long long shell_capacity = 0;
+    int degeneracy = 0;          // of the last Extract
+    bool fresh = false;          // Reset has run and Enact has not: core[] holds d(v) and the words are clear
+    double build_ms = 0;         // HIP-event time of the neighbour-CSR build
+
+    ~KcoreProblem() override
+    {
+        if (data_slices) {
+            DataSlice *ds = data_slices[0];
+            if (ds) {
+                void *bufs[] = {ds->d_core, ds->d_degrees, ds->d_nro, ds->d_nci, ds->d_queue, ds->d_list[0], ds->d_list[1], ds->d_words,
+                                ds->d_counters, ds->d_trace_k, ds->d_trace_tail, ds->d_trace_clock, ds->d_shell, ds->d_mask};
+                for (void *b : bufs)
+                    if (b) util::GRError(hipFree(b), "KcoreProblem hipFree failed", __FILE__, __LINE__);
+                delete ds;
+            }
+            delete[] data_slices;
+        }
+    }
+
+    static int Grid(long long work)
+    {
+        long long blocks = (work + 255) / 256;
+        if (blocks < 1) blocks = 1;
+        if (blocks > 2048) blocks = 2048;  // 256 CUs x 8 workgroups, grid-stride the rest
+        return static_cast<int>(blocks);
+    }
+
+    Graph DeviceGraph() const
+    {
+        const DataSlice *ds = data_slices[0];
+        return Graph{ds->d_nro, ds->d_nci};
+    }
+
+    // d_out[0..2] of SummaryKernel over d_values
+    hipError_t Summary(const int *d_values, unsigned *out)
+    {
+        hipError_t retval = hipSuccess;
+        DataSlice *ds = data_slices[0];
+        hipStream_t stream = this->graph_slices[0]->stream;
+        const unsigned init[3] = {0u, kNoLevel, 0u};
+        unsigned *d_out = ds->d_words + W_COUNT;  // (three words behind the shared ones)
+        GR_CHECK(hipMemcpyAsync(d_out, init, sizeof(init), hipMemcpyHostToDevice, stream), "KcoreProblem summary init failed");
+        hipLaunchKernelGGL(SummaryKernel, dim3(Grid(this->nodes)), dim3(256), 0, stream, d_values, static_cast<long long>(this->nodes), d_out);
+        GR_CHECK(hipGetLastError(), "SummaryKernel launch failed");
+        GR_CHECK(hipMemcpyAsync(out, d_out, sizeof(init), hipMemcpyDeviceToHost, stream), "KcoreProblem read-back failed");
+        GR_CHECK(hipStreamSynchronize(stream), "KcoreProblem read-back sync failed");
+        return retval;
+    }
+
+    hipError_t Build()
+    {
+        hipError_t retval = hipSuccess;
+        DataSlice *ds = data_slices[0];
+        GraphSlice<int, int, int> *gs = this->graph_slices[0];
+        hipStream_t stream = gs->stream;
+        const long long n = this->nodes, m = this->edges;
+        const size_t n1 = static_cast<size_t>(n > 0 ? n : 1);
+        GR_CHECK(hipMalloc(&ds->d_words, sizeof(unsigned) * (W_COUNT + 4)), "KcoreProblem hipMalloc failed");
+        GR_CHECK(hipMalloc(&ds->d_counters, sizeof(unsigned long long) * 4), "KcoreProblem hipMalloc failed");
+
+        // 1. the CSR must be one: the build indexes with what it reads
+        int bad = 0;
+        GR_CHECK(hipMemsetAsync(ds->d_words, 0, sizeof(unsigned) * (W_COUNT + 4), stream), "KcoreProblem memset failed");
+        hipLaunchKernelGGL(tc::ValidateCsrKernel, dim3(Grid((n > m ? n : m) + 1)), dim3(256), 0, stream, gs->d_row_offsets, gs->d_column_indices,
+                           n, m, reinterpret_cast<int *>(ds->d_words));
+        GR_CHECK(hipGetLastError(), "ValidateCsrKernel launch failed");
+        GR_CHECK(hipMemcpyAsync(&bad, ds->d_words, sizeof(int), hipMemcpyDeviceToHost, stream), "KcoreProblem read-back failed");
+        GR_CHECK(hipStreamSynchronize(stream), "KcoreProblem read-back sync failed");
+        if (bad) {
+            malformed = 1;
+            return hipErrorInvalidValue;
+        }
+
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        GR_CHECK(hipEventCreate(&ev[0]), "KcoreProblem hipEventCreate failed");
+        GR_CHECK(hipEventCreate(&ev[1]), "KcoreProblem hipEventCreate failed");
+        GR_CHECK(hipEventRecord(ev[0], stream), "KcoreProblem hipEventRecord failed");
+
+        GR_CHECK(hipMalloc(&ds->d_core, sizeof(int) * n1), "KcoreProblem hipMalloc d_core failed");
+        GR_CHECK(hipMalloc(&ds->d_degrees, sizeof(int) * (n1 + 1)), "KcoreProblem hipMalloc d_degrees failed");
+        GR_CHECK(hipMalloc(&ds->d_nro, sizeof(int) * (n1 + 1)), "KcoreProblem hipMalloc d_nro failed");
+        GR_CHECK(hipMalloc(&ds->d_queue, sizeof(int) * n1), "KcoreProblem hipMalloc d_queue failed");
+        GR_CHECK(hipMalloc(&ds->d_list[0], sizeof(int) * n1), "KcoreProblem hipMalloc d_list failed");
+        GR_CHECK(hipMalloc(&ds->d_list[1], sizeof(int) * n1), "KcoreProblem hipMalloc d_list failed");
+        GR_CHECK(hipMemsetAsync(ds->d_degrees, 0, sizeof(int) * (n1 + 1), stream), "KcoreProblem memset failed");
+        GR_CHECK(hipMemsetAsync(ds->d_nro, 0, sizeof(int) * (n1 + 1), stream), "KcoreProblem memset failed");
+
+        int col_bits = 1;
+        while ((1ll << col_bits) < n) ++col_bits;
+        const int key_bits = 2 * col_bits;  // <= 62
+        const unsigned long long sentinel = (1ull << key_bits) - 1ull;  // min = max = 2^cb - 1: never an edge
+        unsigned *d_keep = nullptr, *d_cursor = nullptr;
+        unsigned long long *d_sums = nullptr;
+        graphio::DeviceKeySort edge_sort;
+        simple_edges = 0;
+        if (m > 0) {
+            GR_CHECK(hipMalloc(&d_keep, sizeof(unsigned) * static_cast<size_t>(m)), "KcoreProblem hipMalloc failed");
+            GR_CHECK(hipMalloc(&d_cursor, sizeof(unsigned) * n1), "KcoreProblem hipMalloc failed");
+            GR_CHECK(hipMalloc(&d_sums, sizeof(unsigned long long) * static_cast<size_t>(graphio::ScanScratchWords(n + 1))),
+                     "KcoreProblem hipMalloc failed");
+            GR_CHECK(hipMemsetAsync(d_cursor, 0, sizeof(unsigned) * n1, stream), "KcoreProblem memset failed");
+            GR_CHECK(edge_sort.Reserve(m), "KcoreProblem sort scratch failed");
+            hipLaunchKernelGGL(tc::EdgeKeysKernel, dim3(Grid(m)), dim3(256), 0, stream, gs->d_row_offsets, gs->d_column_indices, static_cast<int>(n),
+                               m, col_bits, sentinel, edge_sort.Keys());
+            GR_CHECK(hipGetLastError(), "EdgeKeysKernel launch failed");
+            unsigned long long *d_sorted = nullptr;
+            GR_CHECK(edge_sort.Sort(m, key_bits, stream, &d_sorted), "KcoreProblem edge sort failed");
+            hipLaunchKernelGGL(graphio::FlagKernel, dim3(Grid(m)), dim3(256), 0, stream, d_sorted, m, sentinel, d_keep);
+            GR_CHECK(hipGetLastError(), "FlagKernel launch failed");
+            hipLaunchKernelGGL(tc::DegreeKernel, dim3(Grid(m)), dim3(256), 0, stream, d_sorted, d_keep, m, col_bits,
+                               reinterpret_cast<unsigned *>(ds->d_degrees));
+            GR_CHECK(hipGetLastError(), "DegreeKernel launch failed");
+            GR_CHECK(graphio::DeviceExclusiveScan<int>(reinterpret_cast<unsigned *>(ds->d_degrees), ds->d_nro, n + 1, d_sums, stream),
+                     "KcoreProblem offset scan failed");
+            int entries = 0;  // 2M <= 2 * edges; edges is an int, and so is every offset: refuse what does not fit
+            GR_CHECK(hipMemcpyAsync(&entries, ds->d_nro + n, sizeof(int), hipMemcpyDeviceToHost, stream), "KcoreProblem read-back failed");
+            GR_CHECK(hipStreamSynchronize(stream), "KcoreProblem read-back sync failed");
+            if (entries < 0) return hipErrorInvalidValue;
+            simple_edges = entries / 2;
+            if (entries > 0) {
+                GR_CHECK(hipMalloc(&ds->d_nci, sizeof(int) * static_cast<size_t>(entries)), "KcoreProblem hipMalloc d_nci failed");
+                hipLaunchKernelGGL(NeighbourScatterKernel, dim3(Grid(m)), dim3(256), 0, stream, d_sorted, d_keep, m, col_bits, ds->d_nro, d_cursor,
+                                   ds->d_nci);
+                GR_CHECK(hipGetLastError(), "NeighbourScatterKernel launch failed");
+            }
+        }
+        unsigned summary[3] = {0, 0, 0};
+        if ((retval = Summary(ds->d_degrees, summary))) return retval;
+        GR_CHECK(hipEventRecord(ev[1], stream), "KcoreProblem hipEventRecord failed");
+        GR_CHECK(hipStreamSynchronize(stream), "KcoreProblem build sync failed");
+        float ms = 0;
+        GR_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]), "KcoreProblem hipEventElapsedTime failed");
+        build_ms = ms;
+        hipEventDestroy(ev[0]);
+        hipEventDestroy(ev[1]);
+        max_degree = summary[0];
+        min_degree = summary[1] == kNoLevel ? 0 : summary[1];
+        zeros = summary[2];
+        trace_capacity = max_degree + 1;
+        GR_CHECK(hipMalloc(&ds->d_trace_k, sizeof(int) * static_cast<size_t>(trace_capacity)), "KcoreProblem hipMalloc failed");
+        GR_CHECK(hipMalloc(&ds->d_trace_tail, sizeof(int) * static_cast<size_t>(trace_capacity)), "KcoreProblem hipMalloc failed");
+        GR_CHECK(hipMalloc(&ds->d_trace_clock, sizeof(unsigned long long) * static_cast<size_t>(trace_capacity)), "KcoreProblem hipMalloc failed");
+        if (d_keep) GR_CHECK(hipFree(d_keep), "KcoreProblem hipFree failed");
+        if (d_cursor) GR_CHECK(hipFree(d_cursor), "KcoreProblem hipFree failed");
+        if (d_sums) GR_CHECK(hipFree(d_sums), "KcoreProblem hipFree failed");
+        return retval;
+    }
+
+    // One Init per object (grx_kcore_init refuses a second one)
+    hipError_t Init(bool stream_from_host, const Csr<int, int, int> &graph, int num_gpus = 1)
+    {
+        hipError_t retval = hipSuccess;
+        if ((retval = Base::Init(stream_from_host, graph, num_gpus, false))) return retval;
+        data_slices = new DataSlice *[1];
+        data_slices[0] = new DataSlice();
+        return Build();
+    }
+
+    hipError_t InitFromDevice(int nodes, int edges, int *d_row_offsets, int *d_column_indices)
+    {
+        hipError_t retval = hipSuccess;
+        if ((retval = Base::InitFromDevice(nodes, edges, d_row_offsets, d_column_indices))) return retval;
+        data_slices = new DataSlice *[1];
+        data_slices[0] = new DataSlice();
+        return Build();
+    }
+
+    // core[v] = d(v): every vertex with a neighbour is live
+    hipError_t Reset(FrontierType /*frontier_type*/ = VERTEX_FRONTIERS)
+    {
+        hipError_t retval = hipSuccess;
+        DataSlice *ds = data_slices[0];
+        hipStream_t stream = this->graph_slices[0]->stream;
+        GR_CHECK(hipMemcpyAsync(ds->d_core, ds->d_degrees, sizeof(int) * static_cast<size_t>(this->nodes), hipMemcpyDeviceToDevice, stream),
+                 "KcoreProblem Reset copy failed");
+        GR_CHECK(hipMemsetAsync(ds->d_words, 0, sizeof(unsigned) * W_COUNT, stream), "KcoreProblem memset failed");
+        GR_CHECK(hipMemsetAsync(ds->d_counters, 0, sizeof(unsigned long long) * 4, stream), "KcoreProblem memset failed");
+        GR_CHECK(hipStreamSynchronize(stream), "KcoreProblem Reset sync failed");
+        degeneracy = 0;
+        fresh = true;
+        return retval;
+    }
+
+    // h_core may be NULL: then only the degeneracy (the largest value) is read
+    hipError_t Extract(int *h_core)
+    {
+        hipError_t retval = hipSuccess;
+        DataSlice *ds = data_slices[0];
+        hipStream_t stream = this->graph_slices[0]->stream;
+        unsigned summary[3] = {0, 0, 0};
+        if ((retval = Summary(ds->d_core, summary))) return retval;
+        degeneracy = static_cast<int>(summary[0]);
+        if (h_core) {
+            GR_CHECK(hipMemcpyAsync(h_core, ds->d_core, sizeof(int) * static_cast<size_t>(this->nodes), hipMemcpyDeviceToHost, stream),
+                     "KcoreProblem read d_core failed");
+            GR_CHECK(hipStreamSynchronize(stream), "KcoreProblem Extract sync failed");
+        }
+        return retval;
+    }
+
+    // h_sizes[c] = the vertices with core c, c = 0 .. degeneracy, as far as max_entries reaches; *count = degeneracy + 1
+    hipError_t Shells(int max_entries, long long *h_sizes, int *count)
+    {
+        hipError_t retval = hipSuccess;
+        DataSlice *ds = data_slices[0];
+        hipStream_t stream = this->graph_slices[0]->stream;
+        if ((retval = Extract(nullptr))) return retval;
+        const long long shells = static_cast<long long>(degeneracy) + 1;
+        if (count) *count = static_cast<int>(shells);
+        if (!h_sizes || max_entries < 1) return retval;
+        if (shells > shell_capacity) {
+            if (ds->d_shell) GR_CHECK(hipFree(ds->d_shell), "KcoreProblem hipFree failed");
+            ds->d_shell = nullptr;
+            GR_CHECK(hipMalloc(&ds->d_shell, sizeof(unsigned long long) * static_cast<size_t>(shells)), "KcoreProblem hipMalloc d_shell failed");
+            shell_capacity = shells;
+        }
+        GR_CHECK(hipMemsetAsync(ds->d_shell, 0, sizeof(unsigned long long) * static_cast<size_t>(shells), stream), "KcoreProblem memset failed");
+        hipLaunchKernelGGL(ShellKernel, dim3(Grid(this->nodes)), dim3(256), 0, stream, ds->d_core, static_cast<long long>(this->nodes), ds->d_shell);
+        GR_CHECK(hipGetLastError(), "ShellKernel launch failed");
+        const long long take = shells < max_entries ? shells : max_entries;
+        GR_CHECK(hipMemcpyAsync(h_sizes, ds->d_shell, sizeof(long long) * static_cast<size_t>(take), hipMemcpyDeviceToHost, stream),
+                 "KcoreProblem read d_shell failed");
+        GR_CHECK(hipStreamSynchronize(stream), "KcoreProblem Shells sync failed");
+        return retval;
+    }
+
+    // the k-core: h_mask (may be NULL) = core >= k, its vertices and the edges of G inside it
+    hipError_t Members(int k, int wave_min_row, unsigned char *h_mask, long long *vertices, long long *edges)
+    {
+        hipError_t retval = hipSuccess;
+        DataSlice *ds = data_slices[0];
+        hipStream_t stream = this->graph_slices[0]->stream;
+        const size_t n = static_cast<size_t>(this->nodes);
+        if (!ds->d_mask) GR_CHECK(hipMalloc(&ds->d_mask, n), "KcoreProblem hipMalloc d_mask failed");
+        GR_CHECK(hipMemsetAsync(ds->d_counters + 1, 0, sizeof(unsigned long long) * 2, stream), "KcoreProblem memset failed");
+        hipLaunchKernelGGL(MembersKernel, dim3(Grid(this->nodes)), dim3(kKcoreThreads), 0, stream, DeviceGraph(), ds->d_core,
+                           static_cast<long long>(this->nodes), k, wave_min_row, ds->d_mask, ds->d_counters + 1);
+        GR_CHECK(hipGetLastError(), "MembersKernel launch failed");
+        unsigned long long out[2] = {0, 0};
+        GR_CHECK(hipMemcpyAsync(out, ds->d_counters + 1, sizeof(out), hipMemcpyDeviceToHost, stream), "KcoreProblem read-back failed");
+        if (h_mask) GR_CHECK(hipMemcpyAsync(h_mask, ds->d_mask, n, hipMemcpyDeviceToHost, stream), "KcoreProblem read d_mask failed");
+        GR_CHECK(hipStreamSynchronize(stream), "KcoreProblem Members sync failed");
+        if (vertices) *vertices = static_cast<long long>(out[0]);
+        if (edges) *edges = static_cast<long long>(out[1]);
+        return retval;
+    }
+};
+
+}  // namespace kcore
+}  // namespace app
+}  // namespace gunrock

@@ -336,6 +336,63 @@ int grx_tc_device_results(grx_tc *p, long long **d_triangles, int **d_degrees);
 void grx_tc_destroy(grx_tc *p);
 
 /* ------------------------------------------------------------------------------------------------
+ * KCORE: KcoreProblem + KcoreEnactor: the k-core decomposition (the reference snapshot has no app/kcore; later Gunrock releases
+ * do).  The CSR is read as grx_mis_* / grx_tc_* read it: the simple undirected graph G with M edges and degrees d(v).  The
+ * k-core is the largest subgraph in which every vertex has at least k neighbours inside the subgraph.  Every result has one value:
+ *   core[v]      the largest k whose k-core holds v (int32); 0 exactly where d(v) = 0, never more than d(v)
+ *   degeneracy   the largest core[v]
+ *   shell[k]     the number of vertices with core[v] = k, k = 0 .. degeneracy (64-bit)
+ *   members(k)   the mask core[v] >= k, the number of such vertices and the number of edges of G between them (64-bit)
+ * and a run limited to K gives min(core[v], K).  A degeneracy ordering is not offered: it is not unique.
+ * Init builds the symmetric simple neighbour CSR; Enact peels by levels (a vertex at the level takes one off every live
+ * neighbour with a returning atomic; the next level is the smallest value left), in wide launches or in a loop on the device.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct grx_kcore grx_kcore;
+enum { GRX_KCORE_AUTO = 0, GRX_KCORE_ROUNDS = 1, GRX_KCORE_DEVICE_LOOP = 2 };
+
+int grx_kcore_create(grx_kcore **out, int instrument, int device);
+/* KcoreProblem::Init: validates the CSR and builds the neighbour CSR and d(v) on the device.  -1: nodes < 1, edges < 0 or a
+ * NULL array; -2: not a CSR of `nodes` vertices, as grx_tc_init; -3: the handle has been given a graph before (accepted or
+ * rejected) */
+int grx_kcore_init(grx_kcore *p, int nodes, int edges, const int *row_offsets, const int *col_indices);
+/* the same for a CSR already in HBM (borrowed, not freed) */
+int grx_kcore_init_device(grx_kcore *p, int nodes, int edges, int *d_row_offsets, int *d_col_indices);
+/* named options, for the next Enact; 0: set, 1: unknown name, -1: a value out of range.  None changes a result.
+ *   "schedule"          GRX_KCORE_AUTO (default): a step (the scan that opens a level, a sub-round, a rebuild of the live list)
+ *                       is a launch of its own while it is wide, and everything else runs in a loop on the device, one launch
+ *                       and one read-back for a whole stretch of sub-rounds and levels; GRX_KCORE_ROUNDS: every step is a launch
+ *                       and a read-back (the plain form, for comparison); GRX_KCORE_DEVICE_LOOP: every step runs in the device loop
+ *   "compact_below"     in [0, 1]: the live list is rebuilt at a level's start when the live vertices are at most this share of
+ *                       its length (default 0.75; 0: never)
+ *   "wave_min_row"      >= 1: rows of at least this many entries are walked by the whole wave, shorter ones by a lane (default 16)
+ *   "loop_max_list"     under AUTO the device loop scans a live list of at most this length (default 32768)
+ *   "loop_max_entries"  under AUTO the device loop runs a sub-round whose rows hold at most this many entries (default 8192) */
+int grx_kcore_set_option(grx_kcore *p, const char *name, double value);
+/* KcoreProblem::Reset: core[v] = d(v), every vertex with a neighbour live */
+int grx_kcore_reset(grx_kcore *p);
+/* KcoreEnactor::Enact(problem, k_limit, max_grid_size), HIP-event timed.  k_limit >= 0: the levels below k_limit are peeled
+ * and the result is min(core[v], k_limit) */
+int grx_kcore_enact(grx_kcore *p, int k_limit /* < 0: to the end */, int max_grid_size, float *elapsed_ms);
+/* edges (M) and the largest d(v) of the graph; of the last Enact: the non-empty levels, the host-visible read-backs, the
+ * vertices given a core number by peeling (those with d(v) = 0 count: `nodes` after a full run), row entries walked, rebuilds
+ * of the live list, kernel launches and -- when instrumented -- the summed kernel time; build_ms: the HIP-event time of
+ * Init's neighbour-CSR build */
+int grx_kcore_stats(grx_kcore *p, long long *simple_edges, long long *max_degree, long long *levels, long long *rounds,
+                    long long *vertices_peeled, long long *entries_read, long long *compactions, long long *kernel_launches,
+                    double *kernel_ms, double *build_ms);
+/* the non-empty levels of the last Enact in ascending order, at most max_levels of them: the level, the vertices peeled at it
+ * and the time from its scan to the next level's by the device's constant-rate counter; returns the number of levels */
+int grx_kcore_level_trace(grx_kcore *p, int max_levels, int *k, long long *vertices, double *ms);
+int grx_kcore_extract(grx_kcore *p, int *h_core /* may be NULL */, int *degeneracy);
+/* h_sizes[k] = the vertices with core k, for k < max_entries; returns degeneracy + 1 (negative: an error) */
+int grx_kcore_shells(grx_kcore *p, int max_entries, long long *h_sizes);
+/* the k-core of the last Enact's result: the mask core[v] >= k (one byte per vertex), its vertices and the edges of G inside */
+int grx_kcore_members(grx_kcore *p, int k, unsigned char *h_mask /* may be NULL */, long long *vertices, long long *edges);
+/* device arrays of the handle: 32-bit core numbers and 32-bit degrees d(v), `nodes` each */
+int grx_kcore_device_results(grx_kcore *p, int **d_core, int **d_degrees);
+void grx_kcore_destroy(grx_kcore *p);
+
+/* ------------------------------------------------------------------------------------------------
  * SSSP: SSSPProblem + SSSPEnactor (reference gunrock/app/sssp/sssp_problem.cuh:35-387, sssp_enactor.cuh:36-563)
  * ---------------------------------------------------------------------------------------------- */
 typedef struct grx_sssp grx_sssp;
