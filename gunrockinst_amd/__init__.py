@@ -13,6 +13,7 @@ from .capi import (  # noqa: F401
     MisProblem, gunrock_mis, gunrock_color, mis_priorities, MIS_SET, MIS_COLOR_ROUNDS, MIS_COLOR_FIRST_FIT,
     TcProblem, gunrock_tc, gunrock_clustering, TC_AUTO, TC_LANE, TC_LDS, TC_GLOBAL,
     KcoreProblem, gunrock_kcore, gunrock_kcore_members, KCORE_AUTO, KCORE_ROUNDS, KCORE_DEVICE_LOOP,
+    TrussProblem, gunrock_truss, gunrock_edge_support, gunrock_ktruss, TRUSS_AUTO, TRUSS_ROUNDS,
 )
 
 __all__ = [
@@ -22,4 +23,5 @@ __all__ = [
     "MisProblem", "gunrock_mis", "gunrock_color", "mis_priorities", "MIS_SET", "MIS_COLOR_ROUNDS", "MIS_COLOR_FIRST_FIT",
     "TcProblem", "gunrock_tc", "gunrock_clustering", "TC_AUTO", "TC_LANE", "TC_LDS", "TC_GLOBAL",
     "KcoreProblem", "gunrock_kcore", "gunrock_kcore_members", "KCORE_AUTO", "KCORE_ROUNDS", "KCORE_DEVICE_LOOP",
+    "TrussProblem", "gunrock_truss", "gunrock_edge_support", "gunrock_ktruss", "TRUSS_AUTO", "TRUSS_ROUNDS",
 ]

@@ -176,6 +176,22 @@ _SIGNATURES = {
     "grx_kcore_members": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_ubyte), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "grx_kcore_device_results": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "grx_kcore_destroy": (None, [C.c_void_p]),
+    "grx_truss_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int]),
+    "grx_truss_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p]),
+    "grx_truss_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "grx_truss_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
+    "grx_truss_reset": (C.c_int, [C.c_void_p]),
+    "grx_truss_enact": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "grx_truss_stats": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_longlong)] * 10 + [C.POINTER(C.c_double)] * 3),
+    "grx_truss_level_trace": (C.c_int, [C.c_void_p, C.c_int, i32p, C.POINTER(C.c_longlong), C.POINTER(C.c_double)]),
+    "grx_truss_edges": (C.c_int, [C.c_void_p, i32p, i32p]),
+    "grx_truss_support": (C.c_int, [C.c_void_p, i32p, C.POINTER(C.c_longlong)]),
+    "grx_truss_extract": (C.c_int, [C.c_void_p, i32p, C.POINTER(C.c_int)]),
+    "grx_truss_classes": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_longlong)]),
+    "grx_truss_members": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_ubyte), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "grx_truss_vertex_truss": (C.c_int, [C.c_void_p, i32p]),
+    "grx_truss_device_results": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 4),
+    "grx_truss_destroy": (None, [C.c_void_p]),
     "grx_sssp_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int]),
     "grx_sssp_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p, C.POINTER(C.c_uint32), C.c_int]),
     "grx_sssp_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float]),
@@ -1036,6 +1052,185 @@ def gunrock_kcore_members(nodes, row_offsets, col_indices, k, device=0):
         p.reset()
         p.enact(k_limit=k)
         return p.members(k)
+    finally:
+        p.close()
+
+
+TRUSS_AUTO, TRUSS_ROUNDS = 0, 1  # enum GRX_TRUSS_* (gunrock_mi355x.h)
+
+
+class TrussProblem:
+    """TrussProblem + TrussEnactor behind the handle C ABI: the triangle support and the truss number of every edge (int32, in
+    the canonical edge order: (a, b) with a < b, sorted), the truss classes, the k-trusses and the per-vertex maximum, of the CSR
+    read as an undirected simple graph."""
+
+    _STATS = ("simple_edges", "triangles", "max_support", "levels", "rounds", "edges_peeled", "support_entries", "peel_entries",
+              "kernel_launches", "readbacks")
+
+    def __init__(self, instrument=False, device=0):
+        self._h = C.c_void_p()
+        _check(lib().grx_truss_create(C.byref(self._h), int(instrument), device), "grx_truss_create")
+        self.nodes = 0
+        self.entries = 0
+        self.simple_edges = 0
+
+    def _ready(self):
+        m = lib().grx_truss_edges(self._h, None, None)
+        if m < 0:
+            _check(-m, "TrussProblem::Edges")
+        self.simple_edges = int(m)
+
+    def init(self, nodes, row_offsets, col_indices):
+        ro = np.ascontiguousarray(row_offsets, dtype=np.int32)
+        ci = np.ascontiguousarray(col_indices, dtype=np.int32)
+        if ro.shape[0] != int(nodes) + 1:
+            raise ValueError("gunrockinst_amd: %d row offsets for %d nodes" % (ro.shape[0], int(nodes)))
+        self.nodes, self.entries = int(nodes), int(ci.shape[0])
+        _check(lib().grx_truss_init(self._h, self.nodes, self.entries, _p(ro), _p(ci)), "TrussProblem::Init")
+        self._ready()
+        return self
+
+    def init_device(self, nodes, edges, d_row_offsets, d_col_indices):
+        self.nodes, self.entries = int(nodes), int(edges)
+        _check(lib().grx_truss_init_device(self._h, self.nodes, self.entries, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices)),
+               "TrussProblem::Init(device)")
+        self._ready()
+        return self
+
+    def set_option(self, name, value):
+        """"schedule" (TRUSS_AUTO / TRUSS_ROUNDS), "wave_min_row", "loop_max_list", "loop_max_entries"; returns the library's
+        code: 0 = set, 1 = unknown name (a value out of range raises)"""
+        rc = lib().grx_truss_set_option(self._h, name.encode(), float(value))
+        if rc not in (0, 1):
+            _check(rc, "grx_truss_set_option(%s)" % name)
+        return rc
+
+    def reset(self):
+        _check(lib().grx_truss_reset(self._h), "TrussProblem::Reset")
+
+    def enact(self, k_limit=-1, max_grid_size=0):
+        ms = C.c_float()
+        _check(lib().grx_truss_enact(self._h, int(k_limit), max_grid_size, C.byref(ms)), "TrussEnactor::Enact")
+        return float(ms.value)
+
+    def stats(self):
+        v = [C.c_longlong() for _ in self._STATS]
+        d = [C.c_double() for _ in range(3)]
+        _check(lib().grx_truss_stats(self._h, *[C.byref(x) for x in v + d]), "grx_truss_stats")
+        out = {name: x.value for name, x in zip(self._STATS, v)}
+        out["kernel_ms"], out["build_ms"], out["support_ms"] = (x.value for x in d)
+        return out
+
+    def level_trace(self):
+        """the non-empty levels of the last enact: (k as int32, edges peeled at it as int64, milliseconds as float64)"""
+        count = lib().grx_truss_level_trace(self._h, 0, None, None, None)
+        if count < 0:
+            _check(count, "grx_truss_level_trace")
+        k = np.empty(max(count, 1), dtype=np.int32)
+        edges = np.empty(max(count, 1), dtype=np.int64)
+        ms = np.empty(max(count, 1), dtype=np.float64)
+        lib().grx_truss_level_trace(self._h, count, _p(k), edges.ctypes.data_as(C.POINTER(C.c_longlong)),
+                                    ms.ctypes.data_as(C.POINTER(C.c_double)))
+        return k[:count], edges[:count], ms[:count]
+
+    def _edge_array(self, dtype=np.int32):
+        return np.empty(max(self.simple_edges, 1), dtype=dtype)
+
+    def edges(self):
+        """the canonical edges (src, dst) as int32, src < dst, sorted by (src, dst)"""
+        src, dst = self._edge_array(), self._edge_array()
+        m = lib().grx_truss_edges(self._h, _p(src), _p(dst))
+        if m < 0:
+            _check(-m, "TrussProblem::Edges")
+        return src[:m], dst[:m]
+
+    def support(self):
+        """(triangles per edge as int32, the triangles of the graph); valid after init"""
+        out = self._edge_array()
+        total = C.c_longlong()
+        _check(lib().grx_truss_support(self._h, _p(out), C.byref(total)), "TrussProblem::Support")
+        return out[:self.simple_edges], int(total.value)
+
+    def extract(self, truss=True):
+        """(truss numbers as int32 per edge, or None; the largest)"""
+        out = self._edge_array() if truss else None
+        top = C.c_int()
+        _check(lib().grx_truss_extract(self._h, None if out is None else _p(out), C.byref(top)), "TrussProblem::Extract")
+        return (None if out is None else out[:self.simple_edges]), int(top.value)
+
+    def classes(self):
+        """class sizes as int64: entry k is the number of edges with truss number k, k = 0 .. max_truss"""
+        count = lib().grx_truss_classes(self._h, 0, None)
+        if count < 0:
+            _check(-count, "TrussProblem::Classes")
+        out = np.empty(max(count, 1), dtype=np.int64)
+        rc = lib().grx_truss_classes(self._h, count, out.ctypes.data_as(C.POINTER(C.c_longlong)))
+        if rc < 0:
+            _check(-rc, "TrussProblem::Classes")
+        return out[:count]
+
+    def members(self, k, mask=True):
+        """the k-truss: (mask truss >= k as uint8 per edge, or None; its edges; the vertices at one of them)"""
+        out = self._edge_array(np.uint8) if mask else None
+        e, v = C.c_longlong(), C.c_longlong()
+        _check(lib().grx_truss_members(self._h, int(k), None if out is None else out.ctypes.data_as(C.POINTER(C.c_ubyte)), C.byref(e),
+                                       C.byref(v)), "TrussProblem::Members")
+        return (None if out is None else out[:self.simple_edges]), int(e.value), int(v.value)
+
+    def vertex_truss(self):
+        """the largest truss number over the edges at every vertex, int32; 0 without a neighbour"""
+        out = np.empty(max(self.nodes, 1), dtype=np.int32)
+        _check(lib().grx_truss_vertex_truss(self._h, _p(out)), "TrussProblem::VertexTruss")
+        return out[:self.nodes]
+
+    def device_results(self):
+        """device pointers of the int32 arrays (truss, support, src, dst), simple_edges entries each"""
+        p = [C.c_void_p() for _ in range(4)]
+        _check(lib().grx_truss_device_results(self._h, *[C.byref(x) for x in p]), "grx_truss_device_results")
+        return tuple(x.value for x in p)
+
+    def close(self):
+        if self._h:
+            lib().grx_truss_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def gunrock_truss(nodes, row_offsets, col_indices, device=0):
+    """One-shot k-truss decomposition: returns (src, dst, truss numbers, the largest), int32 per canonical edge."""
+    p = TrussProblem(device=device).init(nodes, row_offsets, col_indices)
+    try:
+        p.reset()
+        p.enact()
+        src, dst = p.edges()
+        return (src, dst) + p.extract()
+    finally:
+        p.close()
+
+
+def gunrock_edge_support(nodes, row_offsets, col_indices, device=0):
+    """One-shot per-edge triangle support: returns (src, dst, support as int32 per canonical edge, the triangles of the graph)."""
+    p = TrussProblem(device=device).init(nodes, row_offsets, col_indices)
+    try:
+        src, dst = p.edges()
+        return (src, dst) + p.support()
+    finally:
+        p.close()
+
+
+def gunrock_ktruss(nodes, row_offsets, col_indices, k, device=0):
+    """One-shot k-truss extraction (peels the levels below k only): returns (src, dst, mask uint8 per edge, edges, vertices)."""
+    p = TrussProblem(device=device).init(nodes, row_offsets, col_indices)
+    try:
+        p.reset()
+        p.enact(k_limit=k)
+        src, dst = p.edges()
+        return (src, dst) + p.members(k)
     finally:
         p.close()
 

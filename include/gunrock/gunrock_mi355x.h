@@ -393,6 +393,72 @@ int grx_kcore_device_results(grx_kcore *p, int **d_core, int **d_degrees);
 void grx_kcore_destroy(grx_kcore *p);
 
 /* ------------------------------------------------------------------------------------------------
+ * TRUSS: TrussProblem + TrussEnactor: per-edge triangle support and the k-truss decomposition (the reference snapshot has no
+ * app/truss; later Gunrock releases and the GraphChallenge do).  The CSR is read as grx_mis_* / grx_tc_* / grx_kcore_* read it:
+ * the simple undirected graph G.  Its M edges (a, b), a < b, sorted by (a, b), are the canonical edge order; every per-edge array
+ * is indexed by that rank e.  The k-truss is the largest subgraph in which every edge is in at least k - 2 triangles of the
+ * subgraph.  Every result has one value:
+ *   support[e]       the triangles of G that hold e (int32); sum(support) = 3 * triangles
+ *   truss[e]         the largest k whose k-truss holds e (int32); 2 for an edge in no triangle, never more than support[e] + 2
+ *   max_truss        the largest truss[e]; 0 when M = 0
+ *   classes[k]       the number of edges with truss[e] = k, k = 0 .. max_truss (64-bit; entries 0 and 1 are 0)
+ *   members(k)       the mask truss[e] >= k, the number of such edges and of the vertices at one of them (64-bit)
+ *   vertex_truss[v]  the largest truss over the edges at v (int32); 0 for a vertex without a neighbour
+ * and a run limited to K gives min(truss[e], K).  A truss ordering is not offered: it is not unique.
+ * Init builds the canonical edges, the neighbour CSR with an edge id beside every entry and the supports; Enact peels by levels
+ * (an edge at the level takes one off the two other edges of every live triangle with a returning atomic; the next level is the
+ * smallest value left), in wide launches or in a loop on the device.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct grx_truss grx_truss;
+enum { GRX_TRUSS_AUTO = 0, GRX_TRUSS_ROUNDS = 1 };
+
+int grx_truss_create(grx_truss **out, int instrument, int device);
+/* TrussProblem::Init: validates the CSR, builds the edges, the neighbour CSR and support[] on the device.  -1: nodes < 1,
+ * edges < 0 or a NULL array; -2: not a CSR of `nodes` vertices, as grx_tc_init; -3: the handle has been given a graph before
+ * (accepted or rejected) */
+int grx_truss_init(grx_truss *p, int nodes, int edges, const int *row_offsets, const int *col_indices);
+/* the same for a CSR already in HBM (borrowed, not freed) */
+int grx_truss_init_device(grx_truss *p, int nodes, int edges, int *d_row_offsets, int *d_col_indices);
+/* named options; 0: set, 1: unknown name, -1: a value out of range.  None changes a result.
+ *   "schedule"          GRX_TRUSS_AUTO (default): a step (the scan that opens a level, a sub-round) is a launch of its own while
+ *                       it is wide, and everything else runs in a loop on the device, one launch and one read-back for a whole
+ *                       stretch of sub-rounds; GRX_TRUSS_ROUNDS: every step is a launch and a read-back (the plain form)
+ *   "wave_min_row"      >= 1: an intersection whose shorter row has at least this many entries is walked by the whole wave, a
+ *                       shorter one by a lane (default 32); set before Init it also holds for the support pass
+ *   "loop_max_list"     under AUTO the device loop scans the edges of a graph with at most this many (default 32768)
+ *   "loop_max_entries"  under AUTO the device loop runs a sub-round whose shorter rows hold at most this many entries
+ *                       (default 8192) */
+int grx_truss_set_option(grx_truss *p, const char *name, double value);
+/* TrussProblem::Reset: the working array = support[], every edge live */
+int grx_truss_reset(grx_truss *p);
+/* TrussEnactor::Enact(problem, k_limit, max_grid_size), HIP-event timed.  k_limit >= 0: the levels below k_limit are peeled
+ * and the result is min(truss[e], k_limit).  An Enact that does not follow a Reset makes its own */
+int grx_truss_enact(grx_truss *p, int k_limit /* < 0: to the end */, int max_grid_size, float *elapsed_ms);
+/* edges (M), triangles and the largest support[e] of the graph; of the last Enact: the non-empty levels, the sub-rounds (those of
+ * the synchronous peel under either schedule; the scans of levels nobody is at are not counted), the edges peeled (M after a
+ * full run), row entries walked by the support pass and by the peel, kernel launches, host-visible read-backs and -- when
+ * instrumented -- the summed kernel time; build_ms and support_ms: the HIP-event times of Init's build and of its support pass */
+int grx_truss_stats(grx_truss *p, long long *simple_edges, long long *triangles, long long *max_support, long long *levels,
+                    long long *rounds, long long *edges_peeled, long long *support_entries, long long *peel_entries,
+                    long long *kernel_launches, long long *readbacks, double *kernel_ms, double *build_ms, double *support_ms);
+/* the non-empty levels of the last Enact in ascending order, at most max_levels of them: k, the edges peeled at it and the
+ * time from its scan to the next level's by the device's constant-rate counter; returns the number of levels */
+int grx_truss_level_trace(grx_truss *p, int max_levels, int *k, long long *edges, double *ms);
+/* the canonical edges; returns M (negative: an error); either array may be NULL */
+int grx_truss_edges(grx_truss *p, int *h_src, int *h_dst);
+/* valid after Init, no Enact needed */
+int grx_truss_support(grx_truss *p, int *h_support /* may be NULL */, long long *total_triangles);
+int grx_truss_extract(grx_truss *p, int *h_truss /* may be NULL */, int *max_truss);
+/* h_sizes[k] = the edges with truss k, for k < max_entries; returns max_truss + 1 (negative: an error) */
+int grx_truss_classes(grx_truss *p, int max_entries, long long *h_sizes);
+/* the k-truss of the last Enact's result: the mask truss[e] >= k (one byte per edge), its edges and the vertices at them */
+int grx_truss_members(grx_truss *p, int k, unsigned char *h_mask /* may be NULL */, long long *edges, long long *vertices);
+int grx_truss_vertex_truss(grx_truss *p, int *h_vertex_truss);
+/* device arrays of the handle, M 32-bit entries each */
+int grx_truss_device_results(grx_truss *p, int **d_truss, int **d_support, int **d_src, int **d_dst);
+void grx_truss_destroy(grx_truss *p);
+
+/* ------------------------------------------------------------------------------------------------
  * SSSP: SSSPProblem + SSSPEnactor (reference gunrock/app/sssp/sssp_problem.cuh:35-387, sssp_enactor.cuh:36-563)
  * ---------------------------------------------------------------------------------------------- */
 typedef struct grx_sssp grx_sssp;
