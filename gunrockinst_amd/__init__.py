@@ -14,6 +14,7 @@ from .capi import (  # noqa: F401
     TcProblem, gunrock_tc, gunrock_clustering, TC_AUTO, TC_LANE, TC_LDS, TC_GLOBAL,
     KcoreProblem, gunrock_kcore, gunrock_kcore_members, KCORE_AUTO, KCORE_ROUNDS, KCORE_DEVICE_LOOP,
     TrussProblem, gunrock_truss, gunrock_edge_support, gunrock_ktruss, TRUSS_AUTO, TRUSS_ROUNDS,
+    advance_frontier, advance_queue, advance_reduce,
 )
 
 __all__ = [
@@ -24,4 +25,5 @@ __all__ = [
     "TcProblem", "gunrock_tc", "gunrock_clustering", "TC_AUTO", "TC_LANE", "TC_LDS", "TC_GLOBAL",
     "KcoreProblem", "gunrock_kcore", "gunrock_kcore_members", "KCORE_AUTO", "KCORE_ROUNDS", "KCORE_DEVICE_LOOP",
     "TrussProblem", "gunrock_truss", "gunrock_edge_support", "gunrock_ktruss", "TRUSS_AUTO", "TRUSS_ROUNDS",
+    "advance_frontier", "advance_queue", "advance_reduce",
 ]

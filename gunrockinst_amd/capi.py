@@ -199,6 +199,10 @@ _SIGNATURES = {
     "grx_sssp_pull_levels": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
     "grx_filter_queue": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int),
                                    C.POINTER(C.c_longlong), C.c_int]),
+    "grx_advance_queue": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.c_int]),
+    "grx_advance_reduce": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 7 + [C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_int]),
     "grx_sssp_reset": (C.c_int, [C.c_void_p, C.c_int, C.c_double]),
     "grx_sssp_enact": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]),
     "grx_sssp_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
@@ -1430,6 +1434,122 @@ def filter_queue(ids, row_offsets=None, capacity=None, max_grid_size=0):
                                   int(max_grid_size)), "filter::Kernel")
     k = out_len.value
     return d_v[:k].cpu().numpy(), d_rs[:k].cpu().numpy(), d_sc[:k].cpu().numpy(), int(out_edges.value)
+
+
+ADVANCE_MODES = {"ids": 0, "frontier": 1, "count": 2}
+ADVANCE_RULES = {"mask": 0, "claim": 1}
+ADVANCE_FUNCTORS = {"plain": 0, "hooked": 1}
+REDUCE_TYPES = {"vertex": 1, "edge": 2}
+REDUCE_OPS = {"plus": 1, "minus": 2, "multiplies": 3, "modulus": 4, "bit_or": 5, "bit_and": 6, "bit_xor": 7, "maximum": 8, "minimum": 9}
+REDUCE_VALUE_TYPES = {"int32": 0, "uint32": 1, "float32": 2, "int64": 3, "uint64": 4}
+
+
+def advance_frontier(row_offsets, vertices):
+    """The input frontier of an advance as the operator consumes it: (v, row_start, scan, in_edges), scan = the exclusive
+    prefix of the degrees in the given order.  A vertex without out-edges is outside the operator's contract: ValueError."""
+    ro = np.asarray(row_offsets, dtype=np.int64)
+    v = np.ascontiguousarray(vertices, dtype=np.int32).reshape(-1)
+    if v.size and (v.min() < 0 or v.max() >= ro.size - 1):
+        raise ValueError("advance_frontier: vertex id out of range")
+    deg = ro[v.astype(np.int64) + 1] - ro[v]
+    if (deg <= 0).any():
+        raise ValueError("advance_frontier: vertex %d has no out-edges; an advance frontier never holds one" % int(v[np.argmax(deg <= 0)]))
+    total = int(deg.sum())
+    if total >= 2 ** 31:
+        raise ValueError("advance_frontier: %d edge slots do not fit the operator's 32-bit SizeT" % total)
+    scan = np.zeros(v.size, dtype=np.int64)
+    np.cumsum(deg[:-1], out=scan[1:])
+    return v, ro[v].astype(np.int32), scan.astype(np.int32), total
+
+
+def _dev_i32(torch, a):
+    a = np.array(a, dtype=np.int32, order="C")            # (a copy: the caller's array may be read-only)
+    return torch.from_numpy(a).cuda() if a.size else torch.zeros(1, dtype=torch.int32, device="cuda")
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def advance_queue(row_offsets, col_indices, vertices, mode="ids", rule="mask", functor="plain", mask=None, labels=None, depth=0,
+                  record=True, capacity=None, max_grid_size=0):
+    """advance::LaunchKernel over the frontier `vertices` (grx_advance_queue), on the GPU.  Returns a dict: `out_len`,
+    `out_edges`, the output arrays `v` (+ `row_start`, `scan` in mode "frontier") cut to out_len, `buffers` = the whole output
+    allocations (pre-filled with -7), `edge_hits` / `edge_src` (record=True; edge_src starts as -1) and `labels` (rule
+    "claim").  Queue overflow raises RuntimeError."""
+    import torch
+    ro = np.ascontiguousarray(row_offsets, dtype=np.int32)
+    ci = np.ascontiguousarray(col_indices, dtype=np.int32)
+    v, rs, sc, in_edges = advance_frontier(ro, vertices)
+    cap = int(capacity if capacity is not None else max(in_edges, 1))
+    d_ro, d_ci, d_v, d_rs, d_sc = (_dev_i32(torch, a) for a in (ro, ci, v, rs, sc))
+    d_mask = _dev_i32(torch, mask) if mask is not None else None
+    d_labels = _dev_i32(torch, labels) if labels is not None else None
+    d_hits = torch.zeros(max(ci.size, 1), dtype=torch.int32, device="cuda") if record else None
+    d_src = torch.full((max(ci.size, 1),), -1, dtype=torch.int32, device="cuda") if record else None
+    outs = [torch.full((max(cap, 1),), -7, dtype=torch.int32, device="cuda") for _ in range(3 if mode == "frontier" else 1)]
+    out_len, out_edges = C.c_int(), C.c_longlong()
+    torch.cuda.synchronize()
+    _check(lib().grx_advance_queue(_ptr(d_ro), _ptr(d_ci), _ptr(d_v), _ptr(d_rs), _ptr(d_sc), int(v.size), in_edges, ADVANCE_MODES[mode],
+                                   ADVANCE_RULES[rule], ADVANCE_FUNCTORS[functor], _ptr(d_mask), _ptr(d_labels), int(depth),
+                                   _ptr(d_hits), _ptr(d_src), cap, _ptr(outs[0]), _ptr(outs[1]) if len(outs) > 1 else None,
+                                   _ptr(outs[2]) if len(outs) > 1 else None, C.byref(out_len), C.byref(out_edges),
+                                   int(max_grid_size)), "advance::LaunchKernel")
+    k = out_len.value
+    res = {"out_len": k, "out_edges": int(out_edges.value), "buffers": [t.cpu().numpy() for t in outs]}
+    if mode != "count":
+        for name, buf in zip(("v", "row_start", "scan"), res["buffers"]):
+            res[name] = buf[:k]
+    if record:
+        res["edge_hits"] = d_hits[:ci.size].cpu().numpy()
+        res["edge_src"] = d_src[:ci.size].cpu().numpy()
+    if labels is not None:
+        res["labels"] = d_labels.cpu().numpy()[:np.asarray(labels).size]
+    return res
+
+
+def advance_reduce(row_offsets, col_indices, vertices, values, r_type="vertex", op="plus", by_vertex=False, prefill=True, out=None,
+                   out_len=None, mask=None, functor="plain", record=False, max_grid_size=0):
+    """advance::LaunchReduce over the frontier `vertices` (grx_advance_reduce), on the GPU.  `values` (int32, uint32, float32,
+    int64 or uint64; per vertex for r_type "vertex", per edge for "edge") picks the value type.  `out` = initial contents of
+    the result array (default: zeros, one entry per vertex with by_vertex, else per frontier entry); `out_len` = entries the
+    operator pre-sets to the identity when prefill (default: all of them).  Returns a dict: `reduced` (+ `edge_hits`,
+    `edge_src` with record=True).  A combination the library does not instantiate raises RuntimeError."""
+    import torch
+    ro = np.ascontiguousarray(row_offsets, dtype=np.int32)
+    ci = np.ascontiguousarray(col_indices, dtype=np.int32)
+    v, rs, sc, in_edges = advance_frontier(ro, vertices)
+    values = np.ascontiguousarray(values)
+    vt = REDUCE_VALUE_TYPES[values.dtype.name]
+    carrier = np.int32 if values.dtype.itemsize == 4 else np.int64        # bit patterns travel as signed words
+    if values.size < (ci.size if r_type == "edge" else ro.size - 1):
+        raise ValueError("advance_reduce: too few values")
+    n_out = (ro.size - 1) if by_vertex else v.size
+    if out is None:
+        out = np.zeros(max(n_out, 1), dtype=values.dtype)
+    out = np.ascontiguousarray(out, dtype=values.dtype)
+    if out.size < n_out:
+        raise ValueError("advance_reduce: result array too short")
+    if out_len is None:
+        out_len = out.size
+    if out_len > out.size:
+        raise ValueError("advance_reduce: out_len beyond the result array")
+    d_ro, d_ci, d_v, d_rs, d_sc = (_dev_i32(torch, a) for a in (ro, ci, v, rs, sc))
+    d_val = torch.from_numpy(values.view(carrier).copy()).cuda() if values.size else torch.zeros(1, dtype=torch.int64, device="cuda")
+    d_out = torch.from_numpy(out.view(carrier).copy()).cuda() if out.size else torch.zeros(1, dtype=torch.int64, device="cuda")
+    d_mask = _dev_i32(torch, mask) if mask is not None else None
+    d_hits = torch.zeros(max(ci.size, 1), dtype=torch.int32, device="cuda") if record else None
+    d_src = torch.full((max(ci.size, 1),), -1, dtype=torch.int32, device="cuda") if record else None
+    torch.cuda.synchronize()
+    _check(lib().grx_advance_reduce(_ptr(d_ro), _ptr(d_ci), _ptr(d_v), _ptr(d_rs), _ptr(d_sc), int(v.size), in_edges, REDUCE_TYPES[r_type],
+                                    REDUCE_OPS[op], vt, int(bool(by_vertex)), int(bool(prefill)), int(out_len), _ptr(d_val), _ptr(d_out),
+                                    ADVANCE_FUNCTORS[functor], _ptr(d_mask), _ptr(d_hits), _ptr(d_src), int(max_grid_size)),
+           "advance::LaunchReduce")
+    res = {"reduced": d_out.cpu().numpy().view(values.dtype)[:out.size]}
+    if record:
+        res["edge_hits"] = d_hits[:ci.size].cpu().numpy()
+        res["edge_src"] = d_src[:ci.size].cpu().numpy()
+    return res
 
 
 class SsspProblem:

@@ -96,13 +96,16 @@ struct NoReduce {
 
 template <REDUCE_OP OP, typename T>
 struct ReduceOps {
+    // MINUS and MODULUS are names kept from the reference's enum; neither is associative, so no neighbour-list reduction is
+    // defined for them (they used to be summed silently)
+    static_assert(OP != NONE && OP != MINUS && OP != MODULUS, "no neighbour-list reduction is defined for this REDUCE_OP");
     static __device__ __forceinline__ T Identity()
     {
         if (OP == MULTIPLIES) return static_cast<T>(1);
         if (OP == MAXIMUM) return std::numeric_limits<T>::lowest();
         if (OP == MINIMUM) return std::numeric_limits<T>::max();
         if (OP == BIT_AND) return static_cast<T>(~0ull);
-        return static_cast<T>(0);  // PLUS, BIT_OR, BIT_XOR (and the operators without a reduction meaning)
+        return static_cast<T>(0);  // PLUS, BIT_OR, BIT_XOR
     }
     static __device__ __forceinline__ T Combine(T a, T b)
     {
@@ -119,11 +122,15 @@ struct ReduceOps {
     // combine `v` into *p (another workgroup or wave may hold the other part of the same neighbour list)
     static __device__ __forceinline__ void AtomicCombine(T *p, T v)
     {
-        if constexpr (OP == PLUS || OP == NONE || OP == MINUS || OP == MODULUS) {
+        if constexpr (OP == PLUS && std::is_integral<T>::value && sizeof(T) == 8) {
+            __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        } else if constexpr (OP == PLUS) {
             atomicAdd(p, v);
         } else if constexpr (std::is_integral<T>::value && sizeof(T) == 8 && (OP == MAXIMUM || OP == MINIMUM)) {
-            if constexpr (OP == MAXIMUM) atomicMax(reinterpret_cast<unsigned long long *>(p), static_cast<unsigned long long>(v));
-            else atomicMin(reinterpret_cast<unsigned long long *>(p), static_cast<unsigned long long>(v));
+            // typed builtins: a signed T is compared as signed (an unsigned compare would rank every negative value above
+            // every positive one, and MAXIMUM's identity lowest() would beat everything)
+            if constexpr (OP == MAXIMUM) __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         } else if constexpr (std::is_integral<T>::value && sizeof(T) == 4 && (OP == MAXIMUM || OP == MINIMUM || OP == BIT_OR || OP == BIT_AND || OP == BIT_XOR)) {
             if constexpr (OP == MAXIMUM) atomicMax(p, v);
             else if constexpr (OP == MINIMUM) atomicMin(p, v);
@@ -747,6 +754,7 @@ hipError_t LaunchReduce(AdvanceArgs<typename ProblemData::VertexId, typename Pro
                         int max_grid_size, hipStream_t stream, long long out_len = 0, bool prefill = true)
 {
     static_assert(R_TYPE != EMPTY && R_OP != NONE, "a reducing advance needs a reduction");
+    static_assert(R_OP != MINUS && R_OP != MODULUS, "MINUS and MODULUS are not associative: no neighbour-list reduction is defined for them");
     if (out_len <= 0) out_len = args.in_len;
     if (out_len <= 0) return hipSuccess;
     hipError_t rc = hipSuccess;

@@ -182,6 +182,46 @@ void grx_bfs_destroy(grx_bfs *p);
 int grx_filter_queue(int n, const int *d_in, const int *d_row_offsets, int capacity, int *d_out_v, int *d_out_row_start, int *d_out_scan,
                      int *out_len, long long *out_edges, int max_grid_size);
 
+/* The advance operator by itself (reference advance::LaunchKernel, gunrock/oprtr/advance/kernel.cuh:101-129), with the library's
+ * KernelPolicy<256, 4, 8, LB> and a small functor pair defined in lib/oprtr_app.hip.  All pointers are device pointers.
+ * Graph: d_row_offsets / d_col_indices.  Input frontier as the operator consumes it: in_len entries of (vertex, first edge,
+ * exclusive prefix of the degrees in queue order), in_edges = the sum of their degrees; every entry has at least one out-edge.
+ * max_grid_size: workgroups at most, 0 = one resident grid. */
+enum grx_advance_mode { GRX_ADVANCE_IDS = 0, GRX_ADVANCE_FRONTIER = 1, GRX_ADVANCE_COUNT_ONLY = 2 };
+enum grx_advance_rule { GRX_ADVANCE_RULE_MASK = 0, GRX_ADVANCE_RULE_CLAIM = 1 };
+/* PLAIN: CondEdge / ApplyEdge only; HOOKED: the same rule with ScreenEdge and IssueEdge / ResolveEdge (the operator's batch path) */
+enum grx_advance_functor { GRX_ADVANCE_FUNCTOR_PLAIN = 0, GRX_ADVANCE_FUNCTOR_HOOKED = 1 };
+/* values of advance::REDUCE_TYPE / advance::REDUCE_OP (reference advance/kernel_policy.cuh:58-79) */
+enum grx_reduce_type { GRX_REDUCE_VERTEX = 1, GRX_REDUCE_EDGE = 2 };
+enum grx_reduce_op {
+    GRX_REDUCE_PLUS = 1, GRX_REDUCE_MINUS = 2, GRX_REDUCE_MULTIPLIES = 3, GRX_REDUCE_MODULUS = 4, GRX_REDUCE_BIT_OR = 5,
+    GRX_REDUCE_BIT_AND = 6, GRX_REDUCE_BIT_XOR = 7, GRX_REDUCE_MAXIMUM = 8, GRX_REDUCE_MINIMUM = 9
+};
+enum grx_value_type { GRX_VALUE_INT = 0, GRX_VALUE_UINT = 1, GRX_VALUE_FLOAT = 2, GRX_VALUE_LONGLONG = 3, GRX_VALUE_ULONGLONG = 4 };
+/* Plain advance.  rule MASK: an edge is accepted iff d_mask[destination] != 0 (d_mask == NULL: every edge; a destination reached
+ * over several edges is enqueued once per edge); rule CLAIM: atomicCAS(&d_labels[destination], -1, depth) and the winner
+ * accepts.  Every accepted edge e adds 1 to d_edge_hits[e] and stores its source vertex in d_edge_src[e] (either may be NULL).
+ * mode IDS writes the accepted destinations to d_out_v; FRONTIER writes a complete frontier (as grx_filter_queue does,
+ * destinations without out-edges dropped); COUNT_ONLY writes no output array.  *out_len = entries accepted (written),
+ * *out_edges = the sum of their degrees (FRONTIER only, else 0); order unspecified.  Returns 0, a HIP error code ("Frontier
+ * queue overflow" when `capacity` entries do not hold the output), or -1 for an argument that makes no sense. */
+int grx_advance_queue(const int *d_row_offsets, const int *d_col_indices, const int *d_in_v, const int *d_in_row_start,
+                      const int *d_in_scan, int in_len, int in_edges, int mode, int rule, int functor, const int *d_mask, int *d_labels,
+                      int depth, int *d_edge_hits, int *d_edge_src, int capacity, int *d_out_v, int *d_out_row_start, int *d_out_scan,
+                      int *out_len, long long *out_edges, int max_grid_size);
+/* Reducing advance (advance::LaunchReduce) under rule MASK: d_reduced[i] = r_op over the accepted out-edges e = (v, u) of frontier
+ * entry i of d_values[u] (VERTEX) or d_values[e] (EDGE); the operator's identity when no edge is accepted.  by_vertex: results
+ * sit at d_reduced[v] and not at [i].  prefill: the first out_len entries of d_reduced (0 = in_len) are set to the identity
+ * first; without it the caller has done that for the entries of this frontier and the others are left alone.  value_type
+ * gives the element type of d_values and d_reduced.  Instantiated: PLUS, MULTIPLIES, MAXIMUM, MINIMUM for int, unsigned and
+ * float; BIT_OR, BIT_AND, BIT_XOR for int and unsigned; PLUS, MAXIMUM, MINIMUM for long long and unsigned long long; each for
+ * both reduce types and both by_vertex settings with the PLAIN functor (HOOKED: PLUS and MINIMUM of int and float, VERTEX by
+ * position and EDGE by vertex).  Any other combination returns -2. */
+int grx_advance_reduce(const int *d_row_offsets, const int *d_col_indices, const int *d_in_v, const int *d_in_row_start,
+                       const int *d_in_scan, int in_len, int in_edges, int r_type, int r_op, int value_type, int by_vertex, int prefill,
+                       long long out_len, const void *d_values, void *d_reduced, int functor, const int *d_mask, int *d_edge_hits,
+                       int *d_edge_src, int max_grid_size);
+
 /* DisplayStats' counters (reference tests/bfs/test_bfs.cu:184-196): visited vertices and the sum of their
  * out-degrees -- the numerator of MTEPS = edges_visited / (elapsed_ms * 1000) */
 void grx_bfs_count_visited(int nodes, const int *row_offsets, const int *labels,
