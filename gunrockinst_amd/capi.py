@@ -279,8 +279,64 @@ def _p(a):
     return a.ctypes.data_as(i32p)
 
 
-class HostGraph:
+def _i32(a):
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _check_offsets(row_offsets, nodes):
+    if row_offsets.shape[0] != int(nodes) + 1:
+        raise ValueError("gunrockinst_amd: %d row offsets for %d nodes" % (row_offsets.shape[0], int(nodes)))
+
+
+def _csr_arrays(row_offsets, col_indices, nodes=None):
+    """The two CSR arrays as contiguous int32; with `nodes`, the offsets must have nodes + 1 entries."""
+    ro, ci = _i32(row_offsets), _i32(col_indices)
+    if nodes is not None:
+        _check_offsets(ro, nodes)
+    return ro, ci
+
+
+class _Handle:
+    """Owner of one library handle `_h`; a subclass names the symbol that destroys it."""
+
+    _destroy = None
+
+    def _create(self, symbol, *args):
+        self._h = C.c_void_p()
+        _check(getattr(lib(), symbol)(C.byref(self._h), *args), symbol)
+
+    def _timed(self, fn, what, *args):
+        """a library call whose last argument receives the elapsed milliseconds"""
+        ms = C.c_float()
+        _check(fn(self._h, *args, C.byref(ms)), what)
+        return float(ms.value)
+
+    def close(self):
+        if self._h:
+            getattr(lib(), self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _one_shot(problem, *steps):
+    """Runs the steps on an initialised problem, closes it whatever happens and returns what the last step returned."""
+    try:
+        for step in steps[:-1]:
+            step(problem)
+        return steps[-1](problem)
+    finally:
+        problem.close()
+
+
+class HostGraph(_Handle):
     """gunrock::Csr<int,int,int> built by the library's own host graph code."""
+
+    _destroy = "grx_graph_free"
 
     def __init__(self, handle):
         self._h = C.c_void_p(handle)
@@ -319,9 +375,9 @@ class HostGraph:
 
     @classmethod
     def from_coo(cls, nodes, rows, cols, vals=None):
-        rows = np.ascontiguousarray(rows, dtype=np.int32)
-        cols = np.ascontiguousarray(cols, dtype=np.int32)
-        v = None if vals is None else np.ascontiguousarray(vals, dtype=np.int32)
+        rows = _i32(rows)
+        cols = _i32(cols)
+        v = None if vals is None else _i32(vals)
         h = C.c_void_p()
         _check(lib().grx_graph_from_coo(nodes, rows.shape[0], _p(rows), _p(cols), None if v is None else _p(v),
                                         C.byref(h)), "Csr::FromCoo")
@@ -329,9 +385,8 @@ class HostGraph:
 
     @classmethod
     def from_csr(cls, nodes, row_offsets, col_indices, edge_values=None):
-        ro = np.ascontiguousarray(row_offsets, dtype=np.int32)
-        ci = np.ascontiguousarray(col_indices, dtype=np.int32)
-        ev = None if edge_values is None else np.ascontiguousarray(edge_values, dtype=np.int32)
+        ro, ci = _csr_arrays(row_offsets, col_indices)
+        ev = None if edge_values is None else _i32(edge_values)
         h = C.c_void_p()
         _check(lib().grx_graph_from_csr(nodes, ci.shape[0], _p(ro), _p(ci), None if ev is None else _p(ev),
                                         C.byref(h)), "grx_graph_from_csr")
@@ -362,31 +417,19 @@ class HostGraph:
     def average_degree(self):
         return int(lib().grx_graph_average_degree(self._h))
 
-    def close(self):
-        if self._h:
-            lib().grx_graph_free(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class BfsProblem:
+class BfsProblem(_Handle):
     """BFSProblem + BFSEnactor behind the handle C ABI (Init once, Reset + Enact per run, Extract)."""
 
+    _destroy = "grx_bfs_destroy"
+
     def __init__(self, mark_pred=False, idempotence=False, instrument=False, device=0):
-        self._h = C.c_void_p()
         self.mark_pred = bool(mark_pred)
-        _check(lib().grx_bfs_create(C.byref(self._h), int(mark_pred), int(idempotence), int(instrument), device),
-               "grx_bfs_create")
+        self._create("grx_bfs_create", int(mark_pred), int(idempotence), int(instrument), device)
         self.nodes = 0
 
     def init(self, nodes, row_offsets, col_indices):
-        ro = np.ascontiguousarray(row_offsets, dtype=np.int32)
-        ci = np.ascontiguousarray(col_indices, dtype=np.int32)
+        ro, ci = _csr_arrays(row_offsets, col_indices)
         self.nodes = int(nodes)
         _check(lib().grx_bfs_init(self._h, nodes, ci.shape[0], _p(ro), _p(ci)), "BFSProblem::Init")
         return self
@@ -450,9 +493,7 @@ class BfsProblem:
         _check(lib().grx_bfs_reset(self._h, int(src), float(queue_sizing)), "BFSProblem::Reset")
 
     def enact(self, src, max_grid_size=0, traversal_mode=0):
-        ms = C.c_float()
-        _check(lib().grx_bfs_enact(self._h, int(src), max_grid_size, traversal_mode, C.byref(ms)), "BFSEnactor::Enact")
-        return float(ms.value)
+        return self._timed(lib().grx_bfs_enact, "BFSEnactor::Enact", int(src), max_grid_size, traversal_mode)
 
     def stats(self):
         q, d, l = C.c_longlong(), C.c_longlong(), C.c_longlong()
@@ -496,17 +537,6 @@ class BfsProblem:
                "grx_bfs_relabel_info")
         return {"hubs": h.value, "with_edges": we.value, "threshold": t.value, "build_ms": ms.value, "bytes": b.value}
 
-    def close(self):
-        if self._h:
-            lib().grx_bfs_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def _graph_struct(nodes, row_offsets, col_indices, edge_values=None):
     g = GunrockGraph()
@@ -531,8 +561,7 @@ def _take_node_values(gout, nodes, dtype):
 def gunrock_bfs(nodes, row_offsets, col_indices, src=0, mark_pred=False, idempotence=False, queue_size=1.0,
                 src_mode=SRC_MANUALLY, device=0):
     """Call gunrock_bfs_func exactly as reference shared_lib_tests/test_bfs.c does; returns the labels."""
-    ro = np.ascontiguousarray(row_offsets, dtype=np.int32)
-    ci = np.ascontiguousarray(col_indices, dtype=np.int32)
+    ro, ci = _csr_arrays(row_offsets, col_indices)
     gin = _graph_struct(nodes, ro, ci)
     gout = GunrockGraph()
     cfg = GunrockConfig()
@@ -543,17 +572,17 @@ def gunrock_bfs(nodes, row_offsets, col_indices, src=0, mark_pred=False, idempot
     return _take_node_values(gout, nodes, np.int32)
 
 
-class CcProblem:
+class CcProblem(_Handle):
     """CCProblem + CCEnactor behind the handle C ABI."""
 
+    _destroy = "grx_cc_destroy"
+
     def __init__(self, instrument=False, device=0):
-        self._h = C.c_void_p()
-        _check(lib().grx_cc_create(C.byref(self._h), int(instrument), device), "grx_cc_create")
+        self._create("grx_cc_create", int(instrument), device)
         self.nodes = 0
 
     def init(self, nodes, row_offsets, col_indices):
-        ro = np.ascontiguousarray(row_offsets, dtype=np.int32)
-        ci = np.ascontiguousarray(col_indices, dtype=np.int32)
+        ro, ci = _csr_arrays(row_offsets, col_indices)
         self.nodes = int(nodes)
         _check(lib().grx_cc_init(self._h, nodes, ci.shape[0], _p(ro), _p(ci)), "CCProblem::Init")
         return self
@@ -568,9 +597,7 @@ class CcProblem:
         _check(lib().grx_cc_reset(self._h), "CCProblem::Reset")
 
     def enact(self, max_grid_size=0):
-        ms = C.c_float()
-        _check(lib().grx_cc_enact(self._h, max_grid_size, C.byref(ms)), "CCEnactor::Enact")
-        return float(ms.value)
+        return self._timed(lib().grx_cc_enact, "CCEnactor::Enact", max_grid_size)
 
     def stats(self):
         es, vs, l = C.c_longlong(), C.c_longlong(), C.c_longlong()
@@ -594,22 +621,10 @@ class CcProblem:
         _check(lib().grx_cc_device_results(self._h, C.byref(d)), "grx_cc_device_results")
         return d.value
 
-    def close(self):
-        if self._h:
-            lib().grx_cc_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def gunrock_cc(nodes, row_offsets, col_indices, device=0):
     """Call gunrock_cc_func as reference shared_lib_tests/test_cc.c does; returns the component ids."""
-    ro = np.ascontiguousarray(row_offsets, dtype=np.int32)
-    ci = np.ascontiguousarray(col_indices, dtype=np.int32)
+    ro, ci = _csr_arrays(row_offsets, col_indices)
     gin = _graph_struct(nodes, ro, ci)
     gout = GunrockGraph()
     cfg = GunrockConfig()
@@ -619,24 +634,23 @@ def gunrock_cc(nodes, row_offsets, col_indices, device=0):
     return _take_node_values(gout, nodes, np.int32)
 
 
-class MstProblem:
+class MstProblem(_Handle):
     """MSTProblem + MSTEnactor behind the handle C ABI: the minimum spanning forest of the CSR read as an undirected multigraph,
     unique under the order (weight as int32, then CSR index)."""
 
+    _destroy = "grx_mst_destroy"
+
     def __init__(self, instrument=False, device=0):
-        self._h = C.c_void_p()
-        _check(lib().grx_mst_create(C.byref(self._h), int(instrument), device), "grx_mst_create")
+        self._create("grx_mst_create", int(instrument), device)
         self.nodes = 0
         self.edges = 0
 
     def init(self, nodes, row_offsets, col_indices, edge_values):
-        ro = np.ascontiguousarray(row_offsets, dtype=np.int32)
-        ci = np.ascontiguousarray(col_indices, dtype=np.int32)
-        w = np.ascontiguousarray(edge_values, dtype=np.int32)
+        ro, ci = _csr_arrays(row_offsets, col_indices)
+        w = _i32(edge_values)
         if w.shape[0] != ci.shape[0]:
             raise ValueError("gunrockinst_amd: %d edge values for %d edges" % (w.shape[0], ci.shape[0]))
-        if ro.shape[0] != int(nodes) + 1:
-            raise ValueError("gunrockinst_amd: %d row offsets for %d nodes" % (ro.shape[0], int(nodes)))
+        _check_offsets(ro, nodes)
         self.nodes, self.edges = int(nodes), int(ci.shape[0])
         _check(lib().grx_mst_init(self._h, self.nodes, self.edges, _p(ro), _p(ci), _p(w)), "MSTProblem::Init")
         return self
@@ -651,9 +665,7 @@ class MstProblem:
         _check(lib().grx_mst_reset(self._h), "MSTProblem::Reset")
 
     def enact(self, max_grid_size=0):
-        ms = C.c_float()
-        _check(lib().grx_mst_enact(self._h, max_grid_size, C.byref(ms)), "MSTEnactor::Enact")
-        return float(ms.value)
+        return self._timed(lib().grx_mst_enact, "MSTEnactor::Enact", max_grid_size)
 
     def stats(self):
         r, s, l = C.c_longlong(), C.c_longlong(), C.c_longlong()
@@ -680,27 +692,11 @@ class MstProblem:
         _check(lib().grx_mst_device_results(self._h, C.byref(d)), "grx_mst_device_results")
         return d.value
 
-    def close(self):
-        if self._h:
-            lib().grx_mst_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def gunrock_mst(nodes, row_offsets, col_indices, edge_values, device=0):
     """One-shot minimum spanning forest: returns (selected, total_weight, forest_edges); components = nodes - forest_edges."""
-    p = MstProblem(device=device).init(nodes, row_offsets, col_indices, edge_values)
-    try:
-        p.reset()
-        p.enact()
-        return p.extract()
-    finally:
-        p.close()
+    return _one_shot(MstProblem(device=device).init(nodes, row_offsets, col_indices, edge_values),
+                     MstProblem.reset, MstProblem.enact, MstProblem.extract)
 
 
 MIS_SET, MIS_COLOR_ROUNDS, MIS_COLOR_FIRST_FIT = 0, 1, 2  # enum GRX_MIS_* (gunrock_mi355x.h)
@@ -718,24 +714,23 @@ def mis_priorities(nodes, seed=0):
     return h.astype(np.uint32)
 
 
-class MisProblem:
+class MisProblem(_Handle):
     """MISProblem + MISEnactor behind the handle C ABI: the lexicographically first maximal independent set and the two greedy
     colourings of the CSR read as an undirected simple graph, unique under the order key(v) = (prio(v), v)."""
 
+    _destroy = "grx_mis_destroy"
+
     def __init__(self, instrument=False, device=0):
-        self._h = C.c_void_p()
-        _check(lib().grx_mis_create(C.byref(self._h), int(instrument), device), "grx_mis_create")
+        self._create("grx_mis_create", int(instrument), device)
         self.nodes = 0
         self.edges = 0
 
     def init(self, nodes, row_offsets, col_indices, priorities=None, seed=0):
-        ro = np.ascontiguousarray(row_offsets, dtype=np.int32)
-        ci = np.ascontiguousarray(col_indices, dtype=np.int32)
-        pr = None if priorities is None else np.ascontiguousarray(priorities, dtype=np.int32)
+        ro, ci = _csr_arrays(row_offsets, col_indices)
+        pr = None if priorities is None else _i32(priorities)
         if pr is not None and pr.shape[0] != int(nodes):
             raise ValueError("gunrockinst_amd: %d priorities for %d nodes" % (pr.shape[0], int(nodes)))
-        if ro.shape[0] != int(nodes) + 1:
-            raise ValueError("gunrockinst_amd: %d row offsets for %d nodes" % (ro.shape[0], int(nodes)))
+        _check_offsets(ro, nodes)
         self.nodes, self.edges = int(nodes), int(ci.shape[0])
         _check(lib().grx_mis_init(self._h, self.nodes, self.edges, _p(ro), _p(ci), None if pr is None else _p(pr),
                                   int(seed) & 0xFFFFFFFF), "MISProblem::Init")
@@ -756,9 +751,7 @@ class MisProblem:
         _check(lib().grx_mis_reset(self._h), "MISProblem::Reset")
 
     def enact(self, mode=MIS_SET, max_grid_size=0):
-        ms = C.c_float()
-        _check(lib().grx_mis_enact(self._h, int(mode), max_grid_size, C.byref(ms)), "MISEnactor::Enact")
-        return float(ms.value)
+        return self._timed(lib().grx_mis_enact, "MISEnactor::Enact", int(mode), max_grid_size)
 
     def stats(self):
         r, t, e, q, l = C.c_longlong(), C.c_longlong(), C.c_longlong(), C.c_longlong(), C.c_longlong()
@@ -786,26 +779,10 @@ class MisProblem:
         _check(lib().grx_mis_device_results(self._h, C.byref(d)), "grx_mis_device_results")
         return d.value
 
-    def close(self):
-        if self._h:
-            lib().grx_mis_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def _mis_one_shot(mode, nodes, row_offsets, col_indices, priorities, seed, device):
-    p = MisProblem(device=device).init(nodes, row_offsets, col_indices, priorities, seed)
-    try:
-        p.reset()
-        p.enact(mode)
-        return p.extract()
-    finally:
-        p.close()
+    return _one_shot(MisProblem(device=device).init(nodes, row_offsets, col_indices, priorities, seed),
+                     MisProblem.reset, lambda p: p.enact(mode), MisProblem.extract)
 
 
 def gunrock_mis(nodes, row_offsets, col_indices, priorities=None, seed=0, device=0):
@@ -823,21 +800,19 @@ def gunrock_color(nodes, row_offsets, col_indices, priorities=None, seed=0, firs
 TC_AUTO, TC_LANE, TC_LDS, TC_GLOBAL = 0, 1, 2, 3  # enum GRX_TC_* (gunrock_mi355x.h)
 
 
-class TcProblem:
+class TcProblem(_Handle):
     """TCProblem + TCEnactor behind the handle C ABI: per-vertex triangle counts (int64), their total, clustering coefficients and
     the transitivity of the CSR read as an undirected simple graph."""
 
+    _destroy = "grx_tc_destroy"
+
     def __init__(self, instrument=False, device=0):
-        self._h = C.c_void_p()
-        _check(lib().grx_tc_create(C.byref(self._h), int(instrument), device), "grx_tc_create")
+        self._create("grx_tc_create", int(instrument), device)
         self.nodes = 0
         self.edges = 0
 
     def init(self, nodes, row_offsets, col_indices):
-        ro = np.ascontiguousarray(row_offsets, dtype=np.int32)
-        ci = np.ascontiguousarray(col_indices, dtype=np.int32)
-        if ro.shape[0] != int(nodes) + 1:
-            raise ValueError("gunrockinst_amd: %d row offsets for %d nodes" % (ro.shape[0], int(nodes)))
+        ro, ci = _csr_arrays(row_offsets, col_indices, nodes)
         self.nodes, self.edges = int(nodes), int(ci.shape[0])
         _check(lib().grx_tc_init(self._h, self.nodes, self.edges, _p(ro), _p(ci)), "TCProblem::Init")
         return self
@@ -860,9 +835,7 @@ class TcProblem:
         _check(lib().grx_tc_reset(self._h), "TCProblem::Reset")
 
     def enact(self, max_grid_size=0):
-        ms = C.c_float()
-        _check(lib().grx_tc_enact(self._h, max_grid_size, C.byref(ms)), "TCEnactor::Enact")
-        return float(ms.value)
+        return self._timed(lib().grx_tc_enact, "TCEnactor::Enact", max_grid_size)
 
     def stats(self):
         o, r, e, l = C.c_longlong(), C.c_longlong(), C.c_longlong(), C.c_longlong()
@@ -894,60 +867,35 @@ class TcProblem:
         _check(lib().grx_tc_device_results(self._h, C.byref(t), C.byref(d)), "grx_tc_device_results")
         return t.value, d.value
 
-    def close(self):
-        if self._h:
-            lib().grx_tc_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def gunrock_tc(nodes, row_offsets, col_indices, device=0):
     """One-shot triangle counting: returns (triangles int64 per vertex, the number of triangles)."""
-    p = TcProblem(device=device).init(nodes, row_offsets, col_indices)
-    try:
-        p.reset()
-        p.enact()
-        return p.extract()
-    finally:
-        p.close()
+    return _one_shot(TcProblem(device=device).init(nodes, row_offsets, col_indices), TcProblem.reset, TcProblem.enact, TcProblem.extract)
 
 
 def gunrock_clustering(nodes, row_offsets, col_indices, device=0):
     """One-shot clustering coefficients: returns (coefficient float64 per vertex, transitivity)."""
-    p = TcProblem(device=device).init(nodes, row_offsets, col_indices)
-    try:
-        p.reset()
-        p.enact()
-        return p.clustering()
-    finally:
-        p.close()
+    return _one_shot(TcProblem(device=device).init(nodes, row_offsets, col_indices), TcProblem.reset, TcProblem.enact, TcProblem.clustering)
 
 
 KCORE_AUTO, KCORE_ROUNDS, KCORE_DEVICE_LOOP = 0, 1, 2  # enum GRX_KCORE_* (gunrock_mi355x.h)
 
 
-class KcoreProblem:
+class KcoreProblem(_Handle):
     """KcoreProblem + KcoreEnactor behind the handle C ABI: the core number of every vertex (int32), the degeneracy, the shell
     sizes and the k-cores of the CSR read as an undirected simple graph."""
+
+    _destroy = "grx_kcore_destroy"
 
     _STATS = ("simple_edges", "max_degree", "levels", "rounds", "vertices_peeled", "entries_read", "compactions", "kernel_launches")
 
     def __init__(self, instrument=False, device=0):
-        self._h = C.c_void_p()
-        _check(lib().grx_kcore_create(C.byref(self._h), int(instrument), device), "grx_kcore_create")
+        self._create("grx_kcore_create", int(instrument), device)
         self.nodes = 0
         self.edges = 0
 
     def init(self, nodes, row_offsets, col_indices):
-        ro = np.ascontiguousarray(row_offsets, dtype=np.int32)
-        ci = np.ascontiguousarray(col_indices, dtype=np.int32)
-        if ro.shape[0] != int(nodes) + 1:
-            raise ValueError("gunrockinst_amd: %d row offsets for %d nodes" % (ro.shape[0], int(nodes)))
+        ro, ci = _csr_arrays(row_offsets, col_indices, nodes)
         self.nodes, self.edges = int(nodes), int(ci.shape[0])
         _check(lib().grx_kcore_init(self._h, self.nodes, self.edges, _p(ro), _p(ci)), "KcoreProblem::Init")
         return self
@@ -970,9 +918,7 @@ class KcoreProblem:
         _check(lib().grx_kcore_reset(self._h), "KcoreProblem::Reset")
 
     def enact(self, k_limit=-1, max_grid_size=0):
-        ms = C.c_float()
-        _check(lib().grx_kcore_enact(self._h, int(k_limit), max_grid_size, C.byref(ms)), "KcoreEnactor::Enact")
-        return float(ms.value)
+        return self._timed(lib().grx_kcore_enact, "KcoreEnactor::Enact", int(k_limit), max_grid_size)
 
     def stats(self):
         v = [C.c_longlong() for _ in self._STATS]
@@ -1026,54 +972,34 @@ class KcoreProblem:
         _check(lib().grx_kcore_device_results(self._h, C.byref(c), C.byref(d)), "grx_kcore_device_results")
         return c.value, d.value
 
-    def close(self):
-        if self._h:
-            lib().grx_kcore_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def gunrock_kcore(nodes, row_offsets, col_indices, device=0):
     """One-shot k-core decomposition: returns (core numbers int32 per vertex, the degeneracy)."""
-    p = KcoreProblem(device=device).init(nodes, row_offsets, col_indices)
-    try:
-        p.reset()
-        p.enact()
-        return p.extract()
-    finally:
-        p.close()
+    return _one_shot(KcoreProblem(device=device).init(nodes, row_offsets, col_indices),
+                     KcoreProblem.reset, KcoreProblem.enact, KcoreProblem.extract)
 
 
 def gunrock_kcore_members(nodes, row_offsets, col_indices, k, device=0):
     """One-shot k-core extraction (peels the levels below k only): returns (mask uint8 per vertex, vertices, edges inside)."""
-    p = KcoreProblem(device=device).init(nodes, row_offsets, col_indices)
-    try:
-        p.reset()
-        p.enact(k_limit=k)
-        return p.members(k)
-    finally:
-        p.close()
+    return _one_shot(KcoreProblem(device=device).init(nodes, row_offsets, col_indices),
+                     KcoreProblem.reset, lambda p: p.enact(k_limit=k), lambda p: p.members(k))
 
 
 TRUSS_AUTO, TRUSS_ROUNDS = 0, 1  # enum GRX_TRUSS_* (gunrock_mi355x.h)
 
 
-class TrussProblem:
+class TrussProblem(_Handle):
     """TrussProblem + TrussEnactor behind the handle C ABI: the triangle support and the truss number of every edge (int32, in
     the canonical edge order: (a, b) with a < b, sorted), the truss classes, the k-trusses and the per-vertex maximum, of the CSR
     read as an undirected simple graph."""
+
+    _destroy = "grx_truss_destroy"
 
     _STATS = ("simple_edges", "triangles", "max_support", "levels", "rounds", "edges_peeled", "support_entries", "peel_entries",
               "kernel_launches", "readbacks")
 
     def __init__(self, instrument=False, device=0):
-        self._h = C.c_void_p()
-        _check(lib().grx_truss_create(C.byref(self._h), int(instrument), device), "grx_truss_create")
+        self._create("grx_truss_create", int(instrument), device)
         self.nodes = 0
         self.entries = 0
         self.simple_edges = 0
@@ -1085,10 +1011,7 @@ class TrussProblem:
         self.simple_edges = int(m)
 
     def init(self, nodes, row_offsets, col_indices):
-        ro = np.ascontiguousarray(row_offsets, dtype=np.int32)
-        ci = np.ascontiguousarray(col_indices, dtype=np.int32)
-        if ro.shape[0] != int(nodes) + 1:
-            raise ValueError("gunrockinst_amd: %d row offsets for %d nodes" % (ro.shape[0], int(nodes)))
+        ro, ci = _csr_arrays(row_offsets, col_indices, nodes)
         self.nodes, self.entries = int(nodes), int(ci.shape[0])
         _check(lib().grx_truss_init(self._h, self.nodes, self.entries, _p(ro), _p(ci)), "TrussProblem::Init")
         self._ready()
@@ -1113,9 +1036,7 @@ class TrussProblem:
         _check(lib().grx_truss_reset(self._h), "TrussProblem::Reset")
 
     def enact(self, k_limit=-1, max_grid_size=0):
-        ms = C.c_float()
-        _check(lib().grx_truss_enact(self._h, int(k_limit), max_grid_size, C.byref(ms)), "TrussEnactor::Enact")
-        return float(ms.value)
+        return self._timed(lib().grx_truss_enact, "TrussEnactor::Enact", int(k_limit), max_grid_size)
 
     def stats(self):
         v = [C.c_longlong() for _ in self._STATS]
@@ -1193,57 +1114,28 @@ class TrussProblem:
         _check(lib().grx_truss_device_results(self._h, *[C.byref(x) for x in p]), "grx_truss_device_results")
         return tuple(x.value for x in p)
 
-    def close(self):
-        if self._h:
-            lib().grx_truss_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def gunrock_truss(nodes, row_offsets, col_indices, device=0):
     """One-shot k-truss decomposition: returns (src, dst, truss numbers, the largest), int32 per canonical edge."""
-    p = TrussProblem(device=device).init(nodes, row_offsets, col_indices)
-    try:
-        p.reset()
-        p.enact()
-        src, dst = p.edges()
-        return (src, dst) + p.extract()
-    finally:
-        p.close()
+    return _one_shot(TrussProblem(device=device).init(nodes, row_offsets, col_indices),
+                     TrussProblem.reset, TrussProblem.enact, lambda p: p.edges() + p.extract())
 
 
 def gunrock_edge_support(nodes, row_offsets, col_indices, device=0):
     """One-shot per-edge triangle support: returns (src, dst, support as int32 per canonical edge, the triangles of the graph)."""
-    p = TrussProblem(device=device).init(nodes, row_offsets, col_indices)
-    try:
-        src, dst = p.edges()
-        return (src, dst) + p.support()
-    finally:
-        p.close()
+    return _one_shot(TrussProblem(device=device).init(nodes, row_offsets, col_indices), lambda p: p.edges() + p.support())
 
 
 def gunrock_ktruss(nodes, row_offsets, col_indices, k, device=0):
     """One-shot k-truss extraction (peels the levels below k only): returns (src, dst, mask uint8 per edge, edges, vertices)."""
-    p = TrussProblem(device=device).init(nodes, row_offsets, col_indices)
-    try:
-        p.reset()
-        p.enact(k_limit=k)
-        src, dst = p.edges()
-        return (src, dst) + p.members(k)
-    finally:
-        p.close()
+    return _one_shot(TrussProblem(device=device).init(nodes, row_offsets, col_indices),
+                     TrussProblem.reset, lambda p: p.enact(k_limit=k), lambda p: p.edges() + p.members(k))
 
 
 def gunrock_bc(nodes, row_offsets, col_indices, src=-1, queue_size=1.0, src_mode=SRC_MANUALLY, device=0):
     """Call gunrock_bc_func as reference shared_lib_tests/test_bc.c does (src -1 = every vertex in turn); returns
     (bc_values, ebc_values) as float32 arrays."""
-    ro = np.ascontiguousarray(row_offsets, dtype=np.int32)
-    ci = np.ascontiguousarray(col_indices, dtype=np.int32)
+    ro, ci = _csr_arrays(row_offsets, col_indices)
     gin = _graph_struct(nodes, ro, ci)
     gout = GunrockGraph()
     cfg = GunrockConfig()
@@ -1264,8 +1156,7 @@ def gunrock_pr(nodes, row_offsets, col_indices, src=-1, delta=0.85, error=0.01, 
                device=0):
     """Call gunrock_pr_func as reference shared_lib_tests/test_pr.c does; returns (node_ids, page_rank) in descending rank order
     (top_nodes entries, all of them when top_nodes <= 0)."""
-    ro = np.ascontiguousarray(row_offsets, dtype=np.int32)
-    ci = np.ascontiguousarray(col_indices, dtype=np.int32)
+    ro, ci = _csr_arrays(row_offsets, col_indices)
     gin = _graph_struct(nodes, ro, ci)
     gout = GunrockGraph()
     cfg = GunrockConfig()
@@ -1281,10 +1172,9 @@ def gunrock_pr(nodes, row_offsets, col_indices, src=-1, delta=0.85, error=0.01, 
 
 def gunrock_topk(nodes, row_offsets, col_indices, col_offsets, row_indices, top_nodes, device=0):
     """Call gunrock_topk_func as reference shared_lib_tests/test_topk.c does; returns (node_ids, in_degrees, out_degrees)."""
-    ro = np.ascontiguousarray(row_offsets, dtype=np.int32)
-    ci = np.ascontiguousarray(col_indices, dtype=np.int32)
-    co = np.ascontiguousarray(col_offsets, dtype=np.int32)
-    ri = np.ascontiguousarray(row_indices, dtype=np.int32)
+    ro, ci = _csr_arrays(row_offsets, col_indices)
+    co = _i32(col_offsets)
+    ri = _i32(row_indices)
     gin = _graph_struct(nodes, ro, ci)
     gin.col_offsets, gin.row_indices = co.ctypes.data, ri.ctypes.data
     gout = GunrockGraph()
@@ -1299,17 +1189,17 @@ def gunrock_topk(nodes, row_offsets, col_indices, col_offsets, row_indices, top_
     return ids[:k], ind[:k], outd[:k]
 
 
-class PrProblem:
+class PrProblem(_Handle):
     """PRProblem + PREnactor behind the handle ABI (grx_pr_*)."""
 
+    _destroy = "grx_pr_destroy"
+
     def __init__(self, device=0):
-        self._h = C.c_void_p()
-        _check(lib().grx_pr_create(C.byref(self._h), device), "grx_pr_create")
+        self._create("grx_pr_create", device)
         self.nodes = self.edges = 0
 
     def init(self, nodes, row_offsets, col_indices):
-        ro = np.ascontiguousarray(row_offsets, dtype=np.int32)
-        ci = np.ascontiguousarray(col_indices, dtype=np.int32)
+        ro, ci = _csr_arrays(row_offsets, col_indices)
         self.nodes, self.edges = int(nodes), int(ci.shape[0])
         _check(lib().grx_pr_init(self._h, self.nodes, self.edges, _p(ro), _p(ci)), "PRProblem::Init")
         return self
@@ -1331,9 +1221,7 @@ class PrProblem:
         return self
 
     def enact(self, max_iter=20, max_grid_size=0):
-        ms = C.c_float()
-        _check(lib().grx_pr_enact(self._h, int(max_iter), int(max_grid_size), C.byref(ms)), "PREnactor::Enact")
-        return float(ms.value)
+        return self._timed(lib().grx_pr_enact, "PREnactor::Enact", int(max_iter), int(max_grid_size))
 
     def stats(self):
         it, pr, sv = C.c_longlong(), C.c_longlong(), C.c_longlong()
@@ -1352,30 +1240,19 @@ class PrProblem:
         _check(lib().grx_pr_device_results(self._h, C.byref(r), C.byref(i)), "grx_pr_device_results")
         return r.value, i.value
 
-    def close(self):
-        if self._h:
-            lib().grx_pr_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class BcProblem:
+class BcProblem(_Handle):
     """BCProblem + BCEnactor behind the handle ABI (grx_bc_*)."""
 
+    _destroy = "grx_bc_destroy"
+
     def __init__(self, device=0):
-        self._h = C.c_void_p()
-        _check(lib().grx_bc_create(C.byref(self._h), device), "grx_bc_create")
+        self._create("grx_bc_create", device)
         self.nodes = self.edges = 0
         self._keep = None
 
     def init(self, nodes, row_offsets, col_indices):
-        ro = np.ascontiguousarray(row_offsets, dtype=np.int32)
-        ci = np.ascontiguousarray(col_indices, dtype=np.int32)
+        ro, ci = _csr_arrays(row_offsets, col_indices)
         self.nodes, self.edges = int(nodes), int(ci.shape[0])
         _check(lib().grx_bc_init(self._h, self.nodes, self.edges, ro.ctypes.data_as(C.c_void_p), ci.ctypes.data_as(C.c_void_p)),
                "BCProblem::Init")
@@ -1388,26 +1265,13 @@ class BcProblem:
         return self
 
     def run(self, src=-1, max_grid_size=0, queue_sizing=1.0):
-        ms = C.c_float()
-        _check(lib().grx_bc_run(self._h, int(src), max_grid_size, float(queue_sizing), C.byref(ms)), "BCEnactor::Enact")
-        return float(ms.value)
+        return self._timed(lib().grx_bc_run, "BCEnactor::Enact", int(src), max_grid_size, float(queue_sizing))
 
     def extract(self):
         sig = np.empty(max(self.nodes, 1), dtype=np.float32)
         bc = np.empty(max(self.nodes, 1), dtype=np.float32)
         _check(lib().grx_bc_extract(self._h, sig.ctypes.data_as(C.c_void_p), bc.ctypes.data_as(C.c_void_p), None), "BCProblem::Extract")
         return sig[:self.nodes], bc[:self.nodes]
-
-    def close(self):
-        if self._h:
-            lib().grx_bc_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def filter_queue(ids, row_offsets=None, capacity=None, max_grid_size=0):
@@ -1478,8 +1342,7 @@ def advance_queue(row_offsets, col_indices, vertices, mode="ids", rule="mask", f
     allocations (pre-filled with -7), `edge_hits` / `edge_src` (record=True; edge_src starts as -1) and `labels` (rule
     "claim").  Queue overflow raises RuntimeError."""
     import torch
-    ro = np.ascontiguousarray(row_offsets, dtype=np.int32)
-    ci = np.ascontiguousarray(col_indices, dtype=np.int32)
+    ro, ci = _csr_arrays(row_offsets, col_indices)
     v, rs, sc, in_edges = advance_frontier(ro, vertices)
     cap = int(capacity if capacity is not None else max(in_edges, 1))
     d_ro, d_ci, d_v, d_rs, d_sc = (_dev_i32(torch, a) for a in (ro, ci, v, rs, sc))
@@ -1516,8 +1379,7 @@ def advance_reduce(row_offsets, col_indices, vertices, values, r_type="vertex", 
     operator pre-sets to the identity when prefill (default: all of them).  Returns a dict: `reduced` (+ `edge_hits`,
     `edge_src` with record=True).  A combination the library does not instantiate raises RuntimeError."""
     import torch
-    ro = np.ascontiguousarray(row_offsets, dtype=np.int32)
-    ci = np.ascontiguousarray(col_indices, dtype=np.int32)
+    ro, ci = _csr_arrays(row_offsets, col_indices)
     v, rs, sc, in_edges = advance_frontier(ro, vertices)
     values = np.ascontiguousarray(values)
     vt = REDUCE_VALUE_TYPES[values.dtype.name]
@@ -1552,18 +1414,18 @@ def advance_reduce(row_offsets, col_indices, vertices, values, r_type="vertex", 
     return res
 
 
-class SsspProblem:
+class SsspProblem(_Handle):
     """SSSPProblem + SSSPEnactor behind the handle C ABI."""
 
+    _destroy = "grx_sssp_destroy"
+
     def __init__(self, mark_pred=False, instrument=False, device=0):
-        self._h = C.c_void_p()
         self.mark_pred = bool(mark_pred)
-        _check(lib().grx_sssp_create(C.byref(self._h), int(mark_pred), int(instrument), device), "grx_sssp_create")
+        self._create("grx_sssp_create", int(mark_pred), int(instrument), device)
         self.nodes = 0
 
     def init(self, nodes, row_offsets, col_indices, weights, delta_factor=16):
-        ro = np.ascontiguousarray(row_offsets, dtype=np.int32)
-        ci = np.ascontiguousarray(col_indices, dtype=np.int32)
+        ro, ci = _csr_arrays(row_offsets, col_indices)
         w = np.ascontiguousarray(weights, dtype=np.uint32)
         self.nodes = int(nodes)
         _check(lib().grx_sssp_init(self._h, nodes, ci.shape[0], _p(ro), _p(ci), w.ctypes.data_as(C.POINTER(C.c_uint32)),
@@ -1591,9 +1453,7 @@ class SsspProblem:
         _check(lib().grx_sssp_reset(self._h, int(src), float(queue_sizing)), "SSSPProblem::Reset")
 
     def enact(self, src, max_grid_size=0):
-        ms = C.c_float()
-        _check(lib().grx_sssp_enact(self._h, int(src), max_grid_size, C.byref(ms)), "SSSPEnactor::Enact")
-        return float(ms.value)
+        return self._timed(lib().grx_sssp_enact, "SSSPEnactor::Enact", int(src), max_grid_size)
 
     def stats(self):
         v, e, it, l = C.c_longlong(), C.c_longlong(), C.c_longlong(), C.c_longlong()
@@ -1610,23 +1470,11 @@ class SsspProblem:
                                       None if preds is None else _p(preds)), "SSSPProblem::Extract")
         return dist[:self.nodes], (None if preds is None else preds[:self.nodes])
 
-    def close(self):
-        if self._h:
-            lib().grx_sssp_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def gunrock_sssp(nodes, row_offsets, col_indices, weights, src=0, mark_pred=True, delta_factor=16, queue_size=1.0,
                  src_mode=SRC_MANUALLY, device=0):
     """Call gunrock_sssp_func as reference shared_lib_tests/test_sssp.c does; returns (distances, predecessors)."""
-    ro = np.ascontiguousarray(row_offsets, dtype=np.int32)
-    ci = np.ascontiguousarray(col_indices, dtype=np.int32)
+    ro, ci = _csr_arrays(row_offsets, col_indices)
     w = np.ascontiguousarray(weights, dtype=np.uint32)
     gin = _graph_struct(nodes, ro, ci, w)
     gout = GunrockGraph()

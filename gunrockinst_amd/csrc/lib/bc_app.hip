@@ -13,6 +13,7 @@
 
 #include <gunrock/app/bc/bc_enactor.hpp>
 #include <gunrock/app/bc/bc_problem.hpp>
+#include <gunrock/app/handle_runner.hpp>
 #include <gunrock/csr.hpp>
 #include <gunrock/graphio/utils.hpp>
 #include <gunrock/util/context.hpp>
@@ -29,24 +30,18 @@ struct grx_bc {
     util::DeviceContext context;
     Problem problem;
     BCEnactor<false> enactor;
-    hipEvent_t start = nullptr, stop = nullptr;
-    explicit grx_bc(int device) : context(device), enactor(false)
-    {
-        util::GRError(hipEventCreate(&start), "hipEventCreate failed", __FILE__, __LINE__);
-        util::GRError(hipEventCreate(&stop), "hipEventCreate failed", __FILE__, __LINE__);
-    }
-    ~grx_bc()
-    {
-        if (start) hipEventDestroy(start);
-        if (stop) hipEventDestroy(stop);
-    }
+    EventPair timer;
+    explicit grx_bc(int device) : context(device), enactor(false) { timer.Create(); }
     // one or all sources, then the reference's 0.5 scaling; elapsed = device time of the whole loop
     hipError_t Run(int src, int max_grid_size, double queue_sizing, float *ms)
     {
         hipError_t retval = hipSuccess;
-        hipStream_t stream = problem.graph_slices[0]->stream;
         GR_CHECK(problem.ClearBcValues(), "BC clear failed");
-        GR_CHECK(hipEventRecord(start, stream), "hipEventRecord failed");
+        return timer.Timed(problem.graph_slices[0]->stream, ms, [&]() { return RunSources(src, max_grid_size, queue_sizing); });
+    }
+    hipError_t RunSources(int src, int max_grid_size, double queue_sizing)
+    {
+        hipError_t retval = hipSuccess;
         const int first = (src == -1) ? 0 : src;
         const int last = (src == -1) ? problem.nodes : src + 1;
         for (int s = first; s < last; ++s) {
@@ -54,11 +49,6 @@ struct grx_bc {
             GR_CHECK(enactor.Enact<Problem>(context, &problem, s, max_grid_size), "BC Problem Enact Failed");
         }
         GR_CHECK(problem.ScaleBcValues(0.5f), "BC scale failed");
-        GR_CHECK(hipEventRecord(stop, stream), "hipEventRecord failed");
-        GR_CHECK(hipEventSynchronize(stop), "hipEventSynchronize failed");
-        float t = 0;
-        GR_CHECK(hipEventElapsedTime(&t, start, stop), "hipEventElapsedTime failed");
-        if (ms) *ms = t;
         return retval;
     }
 };
@@ -75,15 +65,8 @@ int grx_bc_create(grx_bc **out, int device)
 int grx_bc_init(grx_bc *p, int nodes, int edges, const int *row_offsets, const int *col_indices)
 {
     if (!p || !row_offsets || nodes < 0 || edges < 0) return -1;
-    Csr<int, float, int> wrap(false);
-    wrap.nodes = nodes;
-    wrap.edges = edges;
-    wrap.row_offsets = const_cast<int *>(row_offsets);
-    wrap.column_indices = const_cast<int *>(col_indices);
-    hipError_t rc = p->problem.Init(false, wrap, 1);
-    wrap.row_offsets = nullptr;
-    wrap.column_indices = nullptr;
-    return static_cast<int>(rc);
+    BorrowedCsr<float> wrap(nodes, edges, row_offsets, col_indices);
+    return static_cast<int>(p->problem.Init(false, wrap.graph, 1));
 }
 
 int grx_bc_init_device(grx_bc *p, int nodes, int edges, int *d_row_offsets, int *d_col_indices)
@@ -119,24 +102,18 @@ void gunrock_bc_func(struct GunrockGraph *graph_out, const struct GunrockGraph *
     }
     const int nodes = static_cast<int>(graph_in->num_nodes);
     const int edges = static_cast<int>(graph_in->num_edges);
-    Csr<int, float, int> view(false);
-    view.nodes = nodes;
-    view.edges = edges;
-    view.row_offsets = static_cast<int *>(graph_in->row_offsets);
-    view.column_indices = static_cast<int *>(graph_in->col_indices);
+    BorrowedCsr<float> view(nodes, edges, static_cast<int *>(graph_in->row_offsets), static_cast<int *>(graph_in->col_indices));
     int src = -1;
     switch (config.src_mode) {  // bc_app.cu:196-219
         case randomize: src = graphio::RandomNode(nodes); break;
         case largest_degree: {
             int max_deg = 0;
-            src = view.GetNodeWithHighestDegree(max_deg);
+            src = view.graph.GetNodeWithHighestDegree(max_deg);
             break;
         }
         case manually: src = config.src_node; break;
         default: src = -1; break;
     }
-    view.row_offsets = nullptr;
-    view.column_indices = nullptr;
     if (src < -1 || src >= nodes) {
         std::fprintf(stderr, "[gunrock] gunrock_bc_func: source %d outside the graph\n", src);
         return;

@@ -13,6 +13,7 @@
 
 #include <gunrock/app/bfs/bfs_enactor.hpp>
 #include <gunrock/app/bfs/bfs_problem.hpp>
+#include <gunrock/app/handle_runner.hpp>
 #include <gunrock/graphio/device_sort.hpp>
 #include <gunrock/graphio/symmetry.hpp>
 #include <gunrock/oprtr/filter/kernel.hpp>
@@ -59,19 +60,10 @@ struct BfsRunnerT : BfsRunner {
     util::DeviceContext context;
     Problem problem;
     BFSEnactor<INSTR> enactor;
-    hipEvent_t start = nullptr, stop = nullptr;
+    EventPair timer;
 
-    explicit BfsRunnerT(int device) : context(device), enactor(false)
-    {
-        util::GRError(hipEventCreate(&start), "hipEventCreate failed", __FILE__, __LINE__);
-        util::GRError(hipEventCreate(&stop), "hipEventCreate failed", __FILE__, __LINE__);
-    }
-    ~BfsRunnerT() override
-    {
-        if (start) hipEventDestroy(start);
-        if (stop) hipEventDestroy(stop);
-        FreeInverse();
-    }
+    explicit BfsRunnerT(int device) : context(device), enactor(false) { timer.Create(); }
+    ~BfsRunnerT() override { FreeInverse(); }
     hipError_t Init(const Csr<int, int, int> &g) override { return problem.Init(false, g, 1); }
     hipError_t InitDevice(int nodes, int edges, int *d_ro, int *d_ci) override
     {
@@ -106,7 +98,14 @@ struct BfsRunnerT : BfsRunner {
             return retval;
         }
         if (!build_if_directed) return retval;
-        GR_CHECK(hipEventRecord(start, gs->stream), "hipEventRecord failed");
+        if ((retval = timer.Timed(gs->stream, &build_ms, [&]() { return BuildInverse(gs); }))) return retval;
+        enabled = true;
+        built = true;
+        return retval;
+    }
+    hipError_t BuildInverse(GraphSlice<int, int, int> *gs)
+    {
+        hipError_t retval = hipSuccess;
         FreeInverse();
         GR_CHECK(hipMalloc(&d_inv_row_offsets, sizeof(int) * (static_cast<size_t>(problem.nodes) + 1)), "BFS hipMalloc inverse offsets failed");
         GR_CHECK(hipMalloc(&d_inv_column_indices, sizeof(int) * static_cast<size_t>(problem.edges)), "BFS hipMalloc inverse columns failed");
@@ -114,11 +113,6 @@ struct BfsRunnerT : BfsRunner {
                                              d_inv_column_indices, gs->stream),
                  "BFS transpose failed");
         GR_CHECK(problem.SetInverseGraph(d_inv_row_offsets, d_inv_column_indices), "BFS SetInverseGraph failed");
-        GR_CHECK(hipEventRecord(stop, gs->stream), "hipEventRecord failed");
-        GR_CHECK(hipEventSynchronize(stop), "hipEventSynchronize failed");
-        GR_CHECK(hipEventElapsedTime(&build_ms, start, stop), "hipEventElapsedTime failed");
-        enabled = true;
-        built = true;
         return retval;
     }
     void FreeInverse()
@@ -193,16 +187,7 @@ struct BfsRunnerT : BfsRunner {
     }
     hipError_t Enact(int src, int max_grid_size, int traversal_mode, float *ms) override
     {
-        hipStream_t stream = problem.graph_slices[0]->stream;
-        hipError_t retval = hipSuccess;
-        GR_CHECK(hipEventRecord(start, stream), "hipEventRecord failed");
-        hipError_t run = enactor.template Enact<Problem>(context, &problem, src, max_grid_size, traversal_mode);
-        GR_CHECK(hipEventRecord(stop, stream), "hipEventRecord failed");
-        GR_CHECK(hipEventSynchronize(stop), "hipEventSynchronize failed");
-        float t = 0;
-        GR_CHECK(hipEventElapsedTime(&t, start, stop), "hipEventElapsedTime failed");
-        if (ms) *ms = t;
-        return run;
+        return timer.Timed(problem.graph_slices[0]->stream, ms, [&]() { return enactor.template Enact<Problem>(context, &problem, src, max_grid_size, traversal_mode); });
     }
     void Stats(long long &queued, long long &depth, double &duty, long long &launches, double &kernel_ms) override
     {
@@ -212,14 +197,8 @@ struct BfsRunnerT : BfsRunner {
     int Trace(int max_levels, long long *frontier, long long *edges, double *ms, int *kind) override
     {
         const auto &t = enactor.GetLevelTrace();
-        int n = static_cast<int>(t.size()) < max_levels ? static_cast<int>(t.size()) : max_levels;
-        for (int i = 0; i < n; ++i) {
-            if (frontier) frontier[i] = t[i].frontier;
-            if (edges) edges[i] = t[i].edges;
-            if (ms) ms[i] = t[i].ms;
-            if (kind) kind[i] = t[i].kind;
-        }
-        return static_cast<int>(t.size());
+        return CopyTrace(t.size(), max_levels, Column(frontier, [&](int i) { return t[i].frontier; }), Column(edges, [&](int i) { return t[i].edges; }),
+                         Column(ms, [&](int i) { return t[i].ms; }), Column(kind, [&](int i) { return t[i].kind; }));
     }
     hipError_t Extract(int *labels, int *preds) override { return problem.Extract(labels, preds); }
     void DeviceResults(int **labels, int **preds) override
@@ -290,15 +269,8 @@ int grx_bfs_create(grx_bfs **out, int mark_pred, int idempotence, int instrument
 int grx_bfs_init(grx_bfs *p, int nodes, int edges, const int *row_offsets, const int *col_indices)
 {
     if (!p || !row_offsets || nodes < 0 || edges < 0) return -1;
-    Csr<int, int, int> wrap(false);  // borrow the caller's arrays (bfs_app.cu:256-260)
-    wrap.nodes = nodes;
-    wrap.edges = edges;
-    wrap.row_offsets = const_cast<int *>(row_offsets);
-    wrap.column_indices = const_cast<int *>(col_indices);
-    hipError_t rc = p->runner->Init(wrap);
-    wrap.row_offsets = nullptr;  // do not free what we do not own (bfs_app.cu:350-351)
-    wrap.column_indices = nullptr;
-    return static_cast<int>(rc);
+    BorrowedCsr<> wrap(nodes, edges, row_offsets, col_indices);
+    return static_cast<int>(p->runner->Init(wrap.graph));
 }
 
 int grx_bfs_init_device(grx_bfs *p, int nodes, int edges, int *d_row_offsets, int *d_col_indices)
@@ -514,11 +486,9 @@ void gunrock_bfs_func(struct GunrockGraph *graph_out, const struct GunrockGraph 
         std::printf("Not Yet Support This DataType Combination.\n");  // bfs_app.cu:354-365
         return;
     }
-    Csr<int, int, int> csr(false);
-    csr.nodes = static_cast<int>(graph_in->num_nodes);
-    csr.edges = static_cast<int>(graph_in->num_edges);
-    csr.row_offsets = static_cast<int *>(graph_in->row_offsets);
-    csr.column_indices = static_cast<int *>(graph_in->col_indices);
+    BorrowedCsr<> borrowed(static_cast<int>(graph_in->num_nodes), static_cast<int>(graph_in->num_edges), static_cast<int *>(graph_in->row_offsets),
+                           static_cast<int *>(graph_in->col_indices));
+    Csr<int, int, int> &csr = borrowed.graph;
 
     int src = 0;
     switch (configs.src_mode) {  // bfs_app.cu:271-294
@@ -555,8 +525,6 @@ void gunrock_bfs_func(struct GunrockGraph *graph_out, const struct GunrockGraph 
                     build_ms);
     if (!rc) DisplayStats("GPU Breadth-first search", src, h_labels, csr, elapsed, depth, queued, duty);
     delete runner;
-    csr.row_offsets = nullptr;
-    csr.column_indices = nullptr;
     util::GRError(hipDeviceSynchronize(), "hipDeviceSynchronize failed", __FILE__, __LINE__);
 }
 

@@ -12,6 +12,7 @@
 
 #include <gunrock/app/cc/cc_enactor.hpp>
 #include <gunrock/app/cc/cc_problem.hpp>
+#include <gunrock/app/handle_runner.hpp>
 #include <gunrock/csr.hpp>
 
 using namespace gunrock;
@@ -38,17 +39,11 @@ struct CcRunnerT : CcRunner {
     typedef CCProblem<int, int, int, true> Problem;
     Problem problem;
     CCEnactor<INSTR> enactor;
-    hipEvent_t start = nullptr, stop = nullptr;
+    EventPair timer;
     explicit CcRunnerT(int device) : enactor(false)
     {
         util::GRError(hipSetDevice(device), "hipSetDevice failed", __FILE__, __LINE__);
-        util::GRError(hipEventCreate(&start), "hipEventCreate failed", __FILE__, __LINE__);
-        util::GRError(hipEventCreate(&stop), "hipEventCreate failed", __FILE__, __LINE__);
-    }
-    ~CcRunnerT() override
-    {
-        if (start) hipEventDestroy(start);
-        if (stop) hipEventDestroy(stop);
+        timer.Create();
     }
     hipError_t Init(const Csr<int, int, int> &g) override { return problem.Init(false, g, 1); }
     hipError_t InitDevice(int nodes, int edges, int *d_ro, int *d_ci) override
@@ -58,16 +53,7 @@ struct CcRunnerT : CcRunner {
     hipError_t Reset() override { return problem.Reset(enactor.GetFrontierType()); }
     hipError_t Enact(int max_grid_size, float *ms) override
     {
-        hipStream_t stream = problem.graph_slices[0]->stream;
-        hipError_t retval = hipSuccess;
-        GR_CHECK(hipEventRecord(start, stream), "hipEventRecord failed");
-        hipError_t run = enactor.template Enact<Problem>(&problem, max_grid_size);
-        GR_CHECK(hipEventRecord(stop, stream), "hipEventRecord failed");
-        GR_CHECK(hipEventSynchronize(stop), "hipEventSynchronize failed");
-        float t = 0;
-        GR_CHECK(hipEventElapsedTime(&t, start, stop), "hipEventElapsedTime failed");
-        if (ms) *ms = t;
-        return run;
+        return timer.Timed(problem.graph_slices[0]->stream, ms, [&]() { return enactor.template Enact<Problem>(&problem, max_grid_size); });
     }
     void Stats(long long &es, long long &vs, long long &launches, double &kernel_ms) override
     {
@@ -89,7 +75,7 @@ struct CcRunnerT : CcRunner {
 }  // namespace
 
 struct grx_cc {
-    CcRunner *runner = nullptr;
+    std::unique_ptr<CcRunner> runner;
 };
 
 extern "C" {
@@ -97,24 +83,15 @@ extern "C" {
 int grx_cc_create(grx_cc **out, int instrument, int device)
 {
     if (!out) return -1;
-    grx_cc *h = new grx_cc();
-    h->runner = instrument ? static_cast<CcRunner *>(new CcRunnerT<true>(device)) : new CcRunnerT<false>(device);
-    *out = h;
+    *out = new grx_cc{MakeRunner<CcRunner, CcRunnerT>(instrument != 0, device)};
     return 0;
 }
 
 int grx_cc_init(grx_cc *p, int nodes, int edges, const int *row_offsets, const int *col_indices)
 {
     if (!p || !row_offsets || nodes < 0 || edges < 0) return -1;
-    Csr<int, int, int> wrap(false);
-    wrap.nodes = nodes;
-    wrap.edges = edges;
-    wrap.row_offsets = const_cast<int *>(row_offsets);
-    wrap.column_indices = const_cast<int *>(col_indices);
-    hipError_t rc = p->runner->Init(wrap);
-    wrap.row_offsets = nullptr;
-    wrap.column_indices = nullptr;
-    return static_cast<int>(rc);
+    BorrowedCsr<> wrap(nodes, edges, row_offsets, col_indices);
+    return static_cast<int>(p->runner->Init(wrap.graph));
 }
 
 int grx_cc_init_device(grx_cc *p, int nodes, int edges, int *d_row_offsets, int *d_col_indices)
@@ -170,12 +147,7 @@ int grx_cc_device_results(grx_cc *p, int **d_component_ids)
     return 0;
 }
 
-void grx_cc_destroy(grx_cc *p)
-{
-    if (!p) return;
-    delete p->runner;
-    delete p;
-}
+void grx_cc_destroy(grx_cc *p) { delete p; }
 
 void gunrock_cc_func(struct GunrockGraph *graph_out, const struct GunrockGraph *graph_in, struct GunrockConfig configs,
                      struct GunrockDataType data_type)
@@ -186,11 +158,9 @@ void gunrock_cc_func(struct GunrockGraph *graph_out, const struct GunrockGraph *
         std::printf("Not Yet Support This DataType Combination.\n");  // cc_app.cu:243-252
         return;
     }
-    Csr<int, int, int> csr(false);
-    csr.nodes = static_cast<int>(graph_in->num_nodes);
-    csr.edges = static_cast<int>(graph_in->num_edges);
-    csr.row_offsets = static_cast<int *>(graph_in->row_offsets);
-    csr.column_indices = static_cast<int *>(graph_in->col_indices);
+    BorrowedCsr<> borrowed(static_cast<int>(graph_in->num_nodes), static_cast<int>(graph_in->num_edges), static_cast<int *>(graph_in->row_offsets),
+                           static_cast<int *>(graph_in->col_indices));
+    Csr<int, int, int> &csr = borrowed.graph;
 
     int *h_ids = static_cast<int *>(std::malloc(sizeof(int) * static_cast<size_t>(csr.nodes > 0 ? csr.nodes : 1)));
     // the reference test leaves configs.device uninitialised only for fields it does not use; device IS set (test_cc.c:22)
@@ -208,8 +178,6 @@ void gunrock_cc_func(struct GunrockGraph *graph_out, const struct GunrockGraph *
     }
     graph_out->node_values = h_ids;  // caller frees (cc_app.cu:177)
     std::printf("GPU Connected Component finished in %lf msec.\n", elapsed);
-    csr.row_offsets = nullptr;
-    csr.column_indices = nullptr;
     util::GRError(hipDeviceSynchronize(), "hipDeviceSynchronize failed", __FILE__, __LINE__);
 }
 

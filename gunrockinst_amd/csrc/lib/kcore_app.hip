@@ -7,6 +7,7 @@
 
 #include <gunrock/app/kcore/kcore_enactor.hpp>
 #include <gunrock/app/kcore/kcore_problem.hpp>
+#include <gunrock/app/handle_runner.hpp>
 #include <gunrock/csr.hpp>
 
 using namespace gunrock;
@@ -19,11 +20,10 @@ static_assert(GRX_KCORE_AUTO == KCORE_AUTO && GRX_KCORE_ROUNDS == KCORE_ROUNDS &
 namespace {
 
 struct KcoreRunner {
+    InitState state;
     virtual ~KcoreRunner() {}
-    virtual hipError_t Init(const Csr<int, int, int> &g) = 0;
-    virtual hipError_t InitDevice(int nodes, int edges, int *d_ro, int *d_ci) = 0;
-    virtual bool Malformed() = 0;
-    virtual bool Used() = 0;
+    virtual int Init(const Csr<int, int, int> &g) = 0;
+    virtual int InitDevice(int nodes, int edges, int *d_ro, int *d_ci) = 0;
     virtual int SetOption(const char *name, double value) = 0;
     virtual hipError_t Reset() = 0;
     virtual hipError_t Enact(int k_limit, int max_grid_size, float *ms) = 0;
@@ -40,36 +40,22 @@ struct KcoreRunnerT : KcoreRunner {
     typedef KcoreProblem<false> Problem;
     Problem problem;
     KcoreEnactor<INSTR> enactor;
-    hipEvent_t start = nullptr, stop = nullptr;
-    bool ready = false;  // Init succeeded: the other phases may run
-    bool used = false;   // Init was called: a handle takes one graph
+    EventPair timer;
     explicit KcoreRunnerT(int device) : enactor(false)
     {
         util::GRError(hipSetDevice(device), "hipSetDevice failed", __FILE__, __LINE__);
-        util::GRError(hipEventCreate(&start), "hipEventCreate failed", __FILE__, __LINE__);
-        util::GRError(hipEventCreate(&stop), "hipEventCreate failed", __FILE__, __LINE__);
+        timer.Create();
     }
-    ~KcoreRunnerT() override
+    int Init(const Csr<int, int, int> &g) override
     {
-        if (start) hipEventDestroy(start);
-        if (stop) hipEventDestroy(stop);
-    }
-    hipError_t Init(const Csr<int, int, int> &g) override
-    {
-        used = true;
         const hipError_t rc = problem.Init(false, g, 1);
-        ready = rc == hipSuccess;
-        return rc;
+        return state.AdmitCode(rc, problem.malformed != 0);
     }
-    hipError_t InitDevice(int nodes, int edges, int *d_ro, int *d_ci) override
+    int InitDevice(int nodes, int edges, int *d_ro, int *d_ci) override
     {
-        used = true;
         const hipError_t rc = problem.InitFromDevice(nodes, edges, d_ro, d_ci);
-        ready = rc == hipSuccess;
-        return rc;
+        return state.AdmitCode(rc, problem.malformed != 0);
     }
-    bool Malformed() override { return problem.malformed != 0; }
-    bool Used() override { return used; }
     int SetOption(const char *name, double value) override
     {
         const long long v = static_cast<long long>(value);
@@ -93,20 +79,11 @@ struct KcoreRunnerT : KcoreRunner {
         }
         return 0;
     }
-    hipError_t Reset() override { return ready ? problem.Reset() : hipErrorNotReady; }
+    hipError_t Reset() override { return state.ready ? problem.Reset() : hipErrorNotReady; }
     hipError_t Enact(int k_limit, int max_grid_size, float *ms) override
     {
-        if (!ready) return hipErrorNotReady;
-        hipStream_t stream = problem.graph_slices[0]->stream;
-        hipError_t retval = hipSuccess;
-        GR_CHECK(hipEventRecord(start, stream), "hipEventRecord failed");
-        hipError_t run = enactor.template Enact<Problem>(&problem, k_limit, max_grid_size);
-        GR_CHECK(hipEventRecord(stop, stream), "hipEventRecord failed");
-        GR_CHECK(hipEventSynchronize(stop), "hipEventSynchronize failed");
-        float t = 0;
-        GR_CHECK(hipEventElapsedTime(&t, start, stop), "hipEventElapsedTime failed");
-        if (ms) *ms = t;
-        return run;
+        if (!state.ready) return hipErrorNotReady;
+        return timer.Timed(problem.graph_slices[0]->stream, ms, [&]() { return enactor.template Enact<Problem>(&problem, k_limit, max_grid_size); });
     }
     void Stats(long long *out, double &kernel_ms, double &build_ms) override
     {
@@ -123,42 +100,37 @@ struct KcoreRunnerT : KcoreRunner {
     }
     int LevelTrace(int max_levels, int *k, long long *vertices, double *ms) override
     {
-        const int count = static_cast<int>(enactor.trace_k.size());
-        for (int i = 0; i < count && i < max_levels; ++i) {
-            if (k) k[i] = enactor.trace_k[i];
-            if (vertices) vertices[i] = enactor.trace_vertices[i];
-            if (ms) ms[i] = enactor.trace_ms[i];
-        }
-        return count;
+        return CopyTrace(enactor.trace_k.size(), max_levels, Column(k, [&](int i) { return enactor.trace_k[i]; }),
+                         Column(vertices, [&](int i) { return enactor.trace_vertices[i]; }), Column(ms, [&](int i) { return enactor.trace_ms[i]; }));
     }
     hipError_t Extract(int *core, int *degeneracy) override
     {
-        if (!ready) return hipErrorNotReady;
+        if (!state.ready) return hipErrorNotReady;
         const hipError_t rc = problem.Extract(core);
         if (degeneracy) *degeneracy = problem.degeneracy;
         return rc;
     }
     hipError_t Shells(int max_entries, long long *sizes, int *count) override
     {
-        if (!ready) return hipErrorNotReady;
+        if (!state.ready) return hipErrorNotReady;
         return problem.Shells(max_entries, sizes, count);
     }
     hipError_t Members(int k, unsigned char *mask, long long *vertices, long long *edges) override
     {
-        if (!ready) return hipErrorNotReady;
+        if (!state.ready) return hipErrorNotReady;
         return problem.Members(k, enactor.wave_min_row, mask, vertices, edges);
     }
     void DeviceResults(int **d_core, int **d_degrees) override
     {
-        if (d_core) *d_core = ready ? problem.data_slices[0]->d_core : nullptr;
-        if (d_degrees) *d_degrees = ready ? problem.data_slices[0]->d_degrees : nullptr;
+        if (d_core) *d_core = state.ready ? problem.data_slices[0]->d_core : nullptr;
+        if (d_degrees) *d_degrees = state.ready ? problem.data_slices[0]->d_degrees : nullptr;
     }
 };
 
 }  // namespace
 
 struct grx_kcore {
-    KcoreRunner *runner = nullptr;
+    std::unique_ptr<KcoreRunner> runner;
 };
 
 extern "C" {
@@ -166,9 +138,7 @@ extern "C" {
 int grx_kcore_create(grx_kcore **out, int instrument, int device)
 {
     if (!out) return -1;
-    grx_kcore *h = new grx_kcore();
-    h->runner = instrument ? static_cast<KcoreRunner *>(new KcoreRunnerT<true>(device)) : new KcoreRunnerT<false>(device);
-    *out = h;
+    *out = new grx_kcore{MakeRunner<KcoreRunner, KcoreRunnerT>(instrument != 0, device)};
     return 0;
 }
 
@@ -176,27 +146,17 @@ int grx_kcore_init(grx_kcore *p, int nodes, int edges, const int *row_offsets, c
 {
     if (!p || !row_offsets || nodes < 1 || edges < 0) return -1;
     if (edges > 0 && !col_indices) return -1;
-    if (p->runner->Used()) return -3;
-    Csr<int, int, int> wrap(false);
-    wrap.nodes = nodes;
-    wrap.edges = edges;
-    wrap.row_offsets = const_cast<int *>(row_offsets);
-    wrap.column_indices = const_cast<int *>(col_indices);
-    hipError_t rc = p->runner->Init(wrap);
-    wrap.row_offsets = nullptr;
-    wrap.column_indices = nullptr;
-    if (rc && p->runner->Malformed()) return -2;
-    return static_cast<int>(rc);
+    if (int taken = p->runner->state.Taken()) return taken;
+    BorrowedCsr<> wrap(nodes, edges, row_offsets, col_indices);
+    return p->runner->Init(wrap.graph);
 }
 
 int grx_kcore_init_device(grx_kcore *p, int nodes, int edges, int *d_row_offsets, int *d_col_indices)
 {
     if (!p || !d_row_offsets || nodes < 1 || edges < 0) return -1;
     if (edges > 0 && !d_col_indices) return -1;
-    if (p->runner->Used()) return -3;
-    const hipError_t rc = p->runner->InitDevice(nodes, edges, d_row_offsets, d_col_indices);
-    if (rc && p->runner->Malformed()) return -2;
-    return static_cast<int>(rc);
+    if (int taken = p->runner->state.Taken()) return taken;
+    return p->runner->InitDevice(nodes, edges, d_row_offsets, d_col_indices);
 }
 
 int grx_kcore_set_option(grx_kcore *p, const char *name, double value)
@@ -262,11 +222,6 @@ int grx_kcore_device_results(grx_kcore *p, int **d_core, int **d_degrees)
     return 0;
 }
 
-void grx_kcore_destroy(grx_kcore *p)
-{
-    if (!p) return;
-    delete p->runner;
-    delete p;
-}
+void grx_kcore_destroy(grx_kcore *p) { delete p; }
 
 }  // extern "C"

@@ -7,6 +7,7 @@
 
 #include <gunrock/app/mis/mis_enactor.hpp>
 #include <gunrock/app/mis/mis_problem.hpp>
+#include <gunrock/app/handle_runner.hpp>
 #include <gunrock/csr.hpp>
 
 using namespace gunrock;
@@ -19,11 +20,10 @@ static_assert(GRX_MIS_SET == MIS_SET && GRX_MIS_COLOR_ROUNDS == MIS_COLOR_ROUNDS
 namespace {
 
 struct MisRunner {
+    InitState state;
     virtual ~MisRunner() {}
-    virtual hipError_t Init(const Csr<int, int, int> &g, const int *priorities, unsigned seed) = 0;
-    virtual hipError_t InitDevice(int nodes, int edges, int *d_ro, int *d_ci, int *d_prio, unsigned seed) = 0;
-    virtual bool Malformed() = 0;
-    virtual bool Used() = 0;
+    virtual int Init(const Csr<int, int, int> &g, const int *priorities, unsigned seed) = 0;
+    virtual int InitDevice(int nodes, int edges, int *d_ro, int *d_ci, int *d_prio, unsigned seed) = 0;
     virtual void SetTail(bool on) = 0;
     virtual hipError_t Reset() = 0;
     virtual hipError_t Enact(int mode, int max_grid_size, float *ms) = 0;
@@ -38,51 +38,28 @@ struct MisRunnerT : MisRunner {
     typedef MISProblem<false> Problem;
     Problem problem;
     MISEnactor<INSTR> enactor;
-    hipEvent_t start = nullptr, stop = nullptr;
-    bool ready = false;  // Init succeeded: the other phases may run
-    bool used = false;   // Init was called: a handle takes one graph
+    EventPair timer;
     explicit MisRunnerT(int device) : enactor(false)
     {
         util::GRError(hipSetDevice(device), "hipSetDevice failed", __FILE__, __LINE__);
-        util::GRError(hipEventCreate(&start), "hipEventCreate failed", __FILE__, __LINE__);
-        util::GRError(hipEventCreate(&stop), "hipEventCreate failed", __FILE__, __LINE__);
+        timer.Create();
     }
-    ~MisRunnerT() override
+    int Init(const Csr<int, int, int> &g, const int *priorities, unsigned seed) override
     {
-        if (start) hipEventDestroy(start);
-        if (stop) hipEventDestroy(stop);
-    }
-    hipError_t Init(const Csr<int, int, int> &g, const int *priorities, unsigned seed) override
-    {
-        used = true;
         const hipError_t rc = problem.Init(false, g, priorities, seed, 1);
-        ready = rc == hipSuccess;
-        return rc;
+        return state.AdmitCode(rc, problem.malformed != 0);
     }
-    hipError_t InitDevice(int nodes, int edges, int *d_ro, int *d_ci, int *d_prio, unsigned seed) override
+    int InitDevice(int nodes, int edges, int *d_ro, int *d_ci, int *d_prio, unsigned seed) override
     {
-        used = true;
         const hipError_t rc = problem.InitFromDevice(nodes, edges, d_ro, d_ci, d_prio, seed);
-        ready = rc == hipSuccess;
-        return rc;
+        return state.AdmitCode(rc, problem.malformed != 0);
     }
-    bool Malformed() override { return problem.malformed != 0; }
-    bool Used() override { return used; }
     void SetTail(bool on) override { enactor.use_tail = on; }
-    hipError_t Reset() override { return ready ? problem.Reset() : hipErrorNotReady; }
+    hipError_t Reset() override { return state.ready ? problem.Reset() : hipErrorNotReady; }
     hipError_t Enact(int mode, int max_grid_size, float *ms) override
     {
-        if (!ready) return hipErrorNotReady;
-        hipStream_t stream = problem.graph_slices[0]->stream;
-        hipError_t retval = hipSuccess;
-        GR_CHECK(hipEventRecord(start, stream), "hipEventRecord failed");
-        hipError_t run = enactor.template Enact<Problem>(&problem, mode, max_grid_size);
-        GR_CHECK(hipEventRecord(stop, stream), "hipEventRecord failed");
-        GR_CHECK(hipEventSynchronize(stop), "hipEventSynchronize failed");
-        float t = 0;
-        GR_CHECK(hipEventElapsedTime(&t, start, stop), "hipEventElapsedTime failed");
-        if (ms) *ms = t;
-        return run;
+        if (!state.ready) return hipErrorNotReady;
+        return timer.Timed(problem.graph_slices[0]->stream, ms, [&]() { return enactor.template Enact<Problem>(&problem, mode, max_grid_size); });
     }
     void Stats(long long &rounds, long long &tail_sweeps, long long &entries, long long &polls, long long &launches, double &kernel_ms) override
     {
@@ -95,27 +72,23 @@ struct MisRunnerT : MisRunner {
     }
     int Trace(int max_rounds, long long *entries, double *ms) override
     {
-        const int n = static_cast<int>(enactor.trace.size());
-        for (int i = 0; i < n && i < max_rounds; ++i) {
-            if (entries) entries[i] = enactor.trace[i].entries;
-            if (ms) ms[i] = enactor.trace[i].ms;
-        }
-        return n;
+        return CopyTrace(enactor.trace.size(), max_rounds, Column(entries, [&](int i) { return enactor.trace[i].entries; }),
+                         Column(ms, [&](int i) { return enactor.trace[i].ms; }));
     }
     hipError_t Extract(int *ids, long long *summary) override
     {
-        if (!ready) return hipErrorNotReady;
+        if (!state.ready) return hipErrorNotReady;
         const hipError_t rc = problem.Extract(ids);
         if (summary) *summary = problem.summary;
         return rc;
     }
-    int *DeviceIds() override { return ready ? problem.data_slices[0]->d_mis_ids : nullptr; }
+    int *DeviceIds() override { return state.ready ? problem.data_slices[0]->d_mis_ids : nullptr; }
 };
 
 }  // namespace
 
 struct grx_mis {
-    MisRunner *runner = nullptr;
+    std::unique_ptr<MisRunner> runner;
 };
 
 extern "C" {
@@ -123,9 +96,7 @@ extern "C" {
 int grx_mis_create(grx_mis **out, int instrument, int device)
 {
     if (!out) return -1;
-    grx_mis *h = new grx_mis();
-    h->runner = instrument ? static_cast<MisRunner *>(new MisRunnerT<true>(device)) : new MisRunnerT<false>(device);
-    *out = h;
+    *out = new grx_mis{MakeRunner<MisRunner, MisRunnerT>(instrument != 0, device)};
     return 0;
 }
 
@@ -133,27 +104,17 @@ int grx_mis_init(grx_mis *p, int nodes, int edges, const int *row_offsets, const
 {
     if (!p || !row_offsets || nodes < 1 || edges < 0) return -1;
     if (edges > 0 && !col_indices) return -1;
-    if (p->runner->Used()) return -3;
-    Csr<int, int, int> wrap(false);
-    wrap.nodes = nodes;
-    wrap.edges = edges;
-    wrap.row_offsets = const_cast<int *>(row_offsets);
-    wrap.column_indices = const_cast<int *>(col_indices);
-    hipError_t rc = p->runner->Init(wrap, priorities, seed);
-    wrap.row_offsets = nullptr;
-    wrap.column_indices = nullptr;
-    if (rc && p->runner->Malformed()) return -2;
-    return static_cast<int>(rc);
+    if (int taken = p->runner->state.Taken()) return taken;
+    BorrowedCsr<> wrap(nodes, edges, row_offsets, col_indices);
+    return p->runner->Init(wrap.graph, priorities, seed);
 }
 
 int grx_mis_init_device(grx_mis *p, int nodes, int edges, int *d_row_offsets, int *d_col_indices, int *d_priorities, unsigned seed)
 {
     if (!p || !d_row_offsets || nodes < 1 || edges < 0) return -1;
     if (edges > 0 && !d_col_indices) return -1;
-    if (p->runner->Used()) return -3;
-    const hipError_t rc = p->runner->InitDevice(nodes, edges, d_row_offsets, d_col_indices, d_priorities, seed);
-    if (rc && p->runner->Malformed()) return -2;
-    return static_cast<int>(rc);
+    if (int taken = p->runner->state.Taken()) return taken;
+    return p->runner->InitDevice(nodes, edges, d_row_offsets, d_col_indices, d_priorities, seed);
 }
 
 int grx_mis_set_tail(grx_mis *p, int enable)
@@ -206,11 +167,6 @@ int grx_mis_device_results(grx_mis *p, int **d_ids)
     return 0;
 }
 
-void grx_mis_destroy(grx_mis *p)
-{
-    if (!p) return;
-    delete p->runner;
-    delete p;
-}
+void grx_mis_destroy(grx_mis *p) { delete p; }
 
 }  // extern "C"

@@ -7,6 +7,7 @@
 
 #include <gunrock/app/mst/mst_enactor.hpp>
 #include <gunrock/app/mst/mst_problem.hpp>
+#include <gunrock/app/handle_runner.hpp>
 #include <gunrock/csr.hpp>
 
 using namespace gunrock;
@@ -16,10 +17,10 @@ using namespace gunrock::app::mst;
 namespace {
 
 struct MstRunner {
+    InitState state;  // (MST reads `state.ready` only: its handle may be initialised again)
     virtual ~MstRunner() {}
-    virtual hipError_t Init(const Csr<int, int, int> &g) = 0;
-    virtual hipError_t InitDevice(int nodes, int edges, int *d_ro, int *d_ci, int *d_w) = 0;
-    virtual bool Malformed() = 0;
+    virtual int Init(const Csr<int, int, int> &g) = 0;
+    virtual int InitDevice(int nodes, int edges, int *d_ro, int *d_ci, int *d_w) = 0;
     virtual hipError_t Reset() = 0;
     virtual hipError_t Enact(int max_grid_size, float *ms) = 0;
     virtual void Stats(long long &rounds, long long &scanned, long long &launches, double &kernel_ms) = 0;
@@ -33,46 +34,27 @@ struct MstRunnerT : MstRunner {
     typedef MSTProblem<true> Problem;
     Problem problem;
     MSTEnactor<INSTR> enactor;
-    hipEvent_t start = nullptr, stop = nullptr;
-    bool ready = false;  // Init succeeded: the other phases may run
+    EventPair timer;
     explicit MstRunnerT(int device) : enactor(false)
     {
         util::GRError(hipSetDevice(device), "hipSetDevice failed", __FILE__, __LINE__);
-        util::GRError(hipEventCreate(&start), "hipEventCreate failed", __FILE__, __LINE__);
-        util::GRError(hipEventCreate(&stop), "hipEventCreate failed", __FILE__, __LINE__);
+        timer.Create();
     }
-    ~MstRunnerT() override
-    {
-        if (start) hipEventDestroy(start);
-        if (stop) hipEventDestroy(stop);
-    }
-    hipError_t Init(const Csr<int, int, int> &g) override
+    int Init(const Csr<int, int, int> &g) override
     {
         const hipError_t rc = problem.Init(false, g, 1);
-        ready = rc == hipSuccess;
-        return rc;
+        return state.AdmitCode(rc, problem.malformed != 0);
     }
-    hipError_t InitDevice(int nodes, int edges, int *d_ro, int *d_ci, int *d_w) override
+    int InitDevice(int nodes, int edges, int *d_ro, int *d_ci, int *d_w) override
     {
         const hipError_t rc = problem.InitFromDevice(nodes, edges, d_ro, d_ci, d_w);
-        ready = rc == hipSuccess;
-        return rc;
+        return state.AdmitCode(rc, problem.malformed != 0);
     }
-    bool Malformed() override { return problem.malformed != 0; }
-    hipError_t Reset() override { return ready ? problem.Reset() : hipErrorNotReady; }
+    hipError_t Reset() override { return state.ready ? problem.Reset() : hipErrorNotReady; }
     hipError_t Enact(int max_grid_size, float *ms) override
     {
-        if (!ready) return hipErrorNotReady;
-        hipStream_t stream = problem.graph_slices[0]->stream;
-        hipError_t retval = hipSuccess;
-        GR_CHECK(hipEventRecord(start, stream), "hipEventRecord failed");
-        hipError_t run = enactor.template Enact<Problem>(&problem, max_grid_size);
-        GR_CHECK(hipEventRecord(stop, stream), "hipEventRecord failed");
-        GR_CHECK(hipEventSynchronize(stop), "hipEventSynchronize failed");
-        float t = 0;
-        GR_CHECK(hipEventElapsedTime(&t, start, stop), "hipEventElapsedTime failed");
-        if (ms) *ms = t;
-        return run;
+        if (!state.ready) return hipErrorNotReady;
+        return timer.Timed(problem.graph_slices[0]->stream, ms, [&]() { return enactor.template Enact<Problem>(&problem, max_grid_size); });
     }
     void Stats(long long &rounds, long long &scanned, long long &launches, double &kernel_ms) override
     {
@@ -83,28 +65,24 @@ struct MstRunnerT : MstRunner {
     }
     int Trace(int max_rounds, long long *entries, double *ms) override
     {
-        const int n = static_cast<int>(enactor.trace.size());
-        for (int i = 0; i < n && i < max_rounds; ++i) {
-            if (entries) entries[i] = enactor.trace[i].entries;
-            if (ms) ms[i] = enactor.trace[i].ms;
-        }
-        return n;
+        return CopyTrace(enactor.trace.size(), max_rounds, Column(entries, [&](int i) { return enactor.trace[i].entries; }),
+                         Column(ms, [&](int i) { return enactor.trace[i].ms; }));
     }
     hipError_t Extract(int *selected, long long *total_weight, int *forest_edges) override
     {
-        if (!ready) return hipErrorNotReady;
+        if (!state.ready) return hipErrorNotReady;
         const hipError_t rc = problem.Extract(selected);
         if (total_weight) *total_weight = problem.total_weight;
         if (forest_edges) *forest_edges = static_cast<int>(problem.forest_edges);
         return rc;
     }
-    int *DeviceSelected() override { return ready ? problem.data_slices[0]->d_selected : nullptr; }
+    int *DeviceSelected() override { return state.ready ? problem.data_slices[0]->d_selected : nullptr; }
 };
 
 }  // namespace
 
 struct grx_mst {
-    MstRunner *runner = nullptr;
+    std::unique_ptr<MstRunner> runner;
 };
 
 extern "C" {
@@ -112,9 +90,7 @@ extern "C" {
 int grx_mst_create(grx_mst **out, int instrument, int device)
 {
     if (!out) return -1;
-    grx_mst *h = new grx_mst();
-    h->runner = instrument ? static_cast<MstRunner *>(new MstRunnerT<true>(device)) : new MstRunnerT<false>(device);
-    *out = h;
+    *out = new grx_mst{MakeRunner<MstRunner, MstRunnerT>(instrument != 0, device)};
     return 0;
 }
 
@@ -122,27 +98,15 @@ int grx_mst_init(grx_mst *p, int nodes, int edges, const int *row_offsets, const
 {
     if (!p || !row_offsets || nodes < 1 || edges < 0) return -1;
     if (edges > 0 && (!col_indices || !edge_values)) return -1;
-    Csr<int, int, int> wrap(false);
-    wrap.nodes = nodes;
-    wrap.edges = edges;
-    wrap.row_offsets = const_cast<int *>(row_offsets);
-    wrap.column_indices = const_cast<int *>(col_indices);
-    wrap.edge_values = const_cast<int *>(edge_values);
-    hipError_t rc = p->runner->Init(wrap);
-    wrap.row_offsets = nullptr;
-    wrap.column_indices = nullptr;
-    wrap.edge_values = nullptr;
-    if (rc && p->runner->Malformed()) return -2;
-    return static_cast<int>(rc);
+    BorrowedCsr<> wrap(nodes, edges, row_offsets, col_indices, edge_values);
+    return p->runner->Init(wrap.graph);
 }
 
 int grx_mst_init_device(grx_mst *p, int nodes, int edges, int *d_row_offsets, int *d_col_indices, int *d_edge_values)
 {
     if (!p || !d_row_offsets || nodes < 1 || edges < 0) return -1;
     if (edges > 0 && (!d_col_indices || !d_edge_values)) return -1;
-    const hipError_t rc = p->runner->InitDevice(nodes, edges, d_row_offsets, d_col_indices, d_edge_values);
-    if (rc && p->runner->Malformed()) return -2;
-    return static_cast<int>(rc);
+    return p->runner->InitDevice(nodes, edges, d_row_offsets, d_col_indices, d_edge_values);
 }
 
 int grx_mst_reset(grx_mst *p) { return p ? static_cast<int>(p->runner->Reset()) : -1; }
@@ -184,11 +148,6 @@ int grx_mst_device_results(grx_mst *p, int **d_selected)
     return 0;
 }
 
-void grx_mst_destroy(grx_mst *p)
-{
-    if (!p) return;
-    delete p->runner;
-    delete p;
-}
+void grx_mst_destroy(grx_mst *p) { delete p; }
 
 }  // extern "C"

@@ -19,6 +19,7 @@
 
 #include <gunrock/app/pr/pr_enactor.hpp>
 #include <gunrock/app/pr/pr_problem.hpp>
+#include <gunrock/app/handle_runner.hpp>
 #include <gunrock/csr.hpp>
 #include <gunrock/graphio/symmetry.hpp>
 #include <gunrock/graphio/utils.hpp>
@@ -34,29 +35,11 @@ struct PrRunner {
     Problem problem;
     PREnactor<false> enactor;
     util::DeviceContext context;
-    hipEvent_t start = nullptr, stop = nullptr;
-    explicit PrRunner(int device) : enactor(false), context(device)
-    {
-        util::GRError(hipEventCreate(&start), "hipEventCreate failed", __FILE__, __LINE__);
-        util::GRError(hipEventCreate(&stop), "hipEventCreate failed", __FILE__, __LINE__);
-    }
-    ~PrRunner()
-    {
-        if (start) hipEventDestroy(start);
-        if (stop) hipEventDestroy(stop);
-    }
+    EventPair timer;
+    explicit PrRunner(int device) : enactor(false), context(device) { timer.Create(); }
     hipError_t Enact(int max_iter, int max_grid_size, float *ms)
     {
-        hipStream_t stream = problem.graph_slices[0]->stream;
-        hipError_t retval = hipSuccess;
-        GR_CHECK(hipEventRecord(start, stream), "hipEventRecord failed");
-        hipError_t run = enactor.template Enact<Problem>(context, &problem, max_iter, 0, max_grid_size);
-        GR_CHECK(hipEventRecord(stop, stream), "hipEventRecord failed");
-        GR_CHECK(hipEventSynchronize(stop), "hipEventSynchronize failed");
-        float t = 0;
-        GR_CHECK(hipEventElapsedTime(&t, start, stop), "hipEventElapsedTime failed");
-        if (ms) *ms = t;
-        return run;
+        return timer.Timed(problem.graph_slices[0]->stream, ms, [&]() { return enactor.template Enact<Problem>(context, &problem, max_iter, 0, max_grid_size); });
     }
 };
 
@@ -102,15 +85,8 @@ int grx_pr_create(grx_pr **out, int device)
 int grx_pr_init(grx_pr *p, int nodes, int edges, const int *row_offsets, const int *col_indices)
 {
     if (!p || !row_offsets || nodes < 0 || edges < 0) return -1;
-    Csr<int, float, int> wrap(false);
-    wrap.nodes = nodes;
-    wrap.edges = edges;
-    wrap.row_offsets = const_cast<int *>(row_offsets);
-    wrap.column_indices = const_cast<int *>(col_indices);
-    hipError_t rc = p->runner->problem.Init(false, wrap, 1);
-    wrap.row_offsets = nullptr;
-    wrap.column_indices = nullptr;
-    return static_cast<int>(rc);
+    BorrowedCsr<float> wrap(nodes, edges, row_offsets, col_indices);
+    return static_cast<int>(p->runner->problem.Init(false, wrap.graph, 1));
 }
 
 int grx_pr_init_device(grx_pr *p, int nodes, int edges, int *d_row_offsets, int *d_col_indices)
@@ -186,11 +162,9 @@ void gunrock_pr_func(struct GunrockGraph *graph_out, void *node_ids, void *page_
         std::printf("Not Yet Support This DataType Combination.\n");  // pr_app.cu:201-210
         return;
     }
-    Csr<int, float, int> csr(false);
-    csr.nodes = static_cast<int>(graph_in->num_nodes);
-    csr.edges = static_cast<int>(graph_in->num_edges);
-    csr.row_offsets = static_cast<int *>(graph_in->row_offsets);
-    csr.column_indices = static_cast<int *>(graph_in->col_indices);
+    BorrowedCsr<float> borrowed(static_cast<int>(graph_in->num_nodes), static_cast<int>(graph_in->num_edges), static_cast<int *>(graph_in->row_offsets),
+                                static_cast<int *>(graph_in->col_indices));
+    Csr<int, float, int> &csr = borrowed.graph;
     int src_node = -1;
     switch (pr_config.src_mode) {  // pr_app.cu:229-252
         case randomize: src_node = graphio::RandomNode(csr.nodes); break;
@@ -224,8 +198,6 @@ void gunrock_pr_func(struct GunrockGraph *graph_out, void *node_ids, void *page_
     if (!rc) rc = util::GRError(runner.problem.Extract(static_cast<float *>(page_rank), static_cast<int *>(node_ids), count),
                                 "Page Rank Problem Data Extraction Failed", __FILE__, __LINE__);
     std::printf("[GPU PageRank] finished.  elapsed: %.3f ms\n", elapsed);
-    csr.row_offsets = nullptr;
-    csr.column_indices = nullptr;
     util::GRError(hipDeviceSynchronize(), "hipDeviceSynchronize failed", __FILE__, __LINE__);
 }
 

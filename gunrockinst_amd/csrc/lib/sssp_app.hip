@@ -13,6 +13,7 @@
 
 #include <gunrock/app/sssp/sssp_enactor.hpp>
 #include <gunrock/app/sssp/sssp_problem.hpp>
+#include <gunrock/app/handle_runner.hpp>
 #include <gunrock/csr.hpp>
 #include <gunrock/graphio/utils.hpp>
 #include <gunrock/util/context.hpp>
@@ -43,17 +44,8 @@ struct SsspRunnerT : SsspRunner {
     util::DeviceContext context;
     Problem problem;
     SSSPEnactor<INSTR> enactor;
-    hipEvent_t start = nullptr, stop = nullptr;
-    explicit SsspRunnerT(int device) : context(device), enactor(false)
-    {
-        util::GRError(hipEventCreate(&start), "hipEventCreate failed", __FILE__, __LINE__);
-        util::GRError(hipEventCreate(&stop), "hipEventCreate failed", __FILE__, __LINE__);
-    }
-    ~SsspRunnerT() override
-    {
-        if (start) hipEventDestroy(start);
-        if (stop) hipEventDestroy(stop);
-    }
+    EventPair timer;
+    explicit SsspRunnerT(int device) : context(device), enactor(false) { timer.Create(); }
     hipError_t Init(Csr<int, int, int> &g, int delta_factor) override { return problem.Init(false, g, 1, delta_factor); }
     hipError_t InitDevice(int nodes, int edges, int *d_ro, int *d_ci, const unsigned *d_w, float delta) override
     {
@@ -70,16 +62,7 @@ struct SsspRunnerT : SsspRunner {
     hipError_t Reset(int src, double queue_sizing) override { return problem.Reset(src, enactor.GetFrontierType(), queue_sizing); }
     hipError_t Enact(int src, int max_grid_size, float *ms) override
     {
-        hipStream_t stream = problem.graph_slices[0]->stream;
-        hipError_t retval = hipSuccess;
-        GR_CHECK(hipEventRecord(start, stream), "hipEventRecord failed");
-        hipError_t run = enactor.template Enact<Problem>(context, &problem, src, 1.0, max_grid_size, 0);
-        GR_CHECK(hipEventRecord(stop, stream), "hipEventRecord failed");
-        GR_CHECK(hipEventSynchronize(stop), "hipEventSynchronize failed");
-        float t = 0;
-        GR_CHECK(hipEventElapsedTime(&t, start, stop), "hipEventElapsedTime failed");
-        if (ms) *ms = t;
-        return run;
+        return timer.Timed(problem.graph_slices[0]->stream, ms, [&]() { return enactor.template Enact<Problem>(context, &problem, src, 1.0, max_grid_size, 0); });
     }
     void Stats(long long &vertices, long long &edges, long long &iters, long long &launches, double &kernel_ms) override
     {
@@ -122,17 +105,8 @@ int grx_sssp_init(grx_sssp *p, int nodes, int edges, const int *row_offsets, con
                   const unsigned *edge_weights, int delta_factor)
 {
     if (!p || !row_offsets || !edge_weights || nodes < 0 || edges < 0) return -1;
-    Csr<int, int, int> wrap(false);
-    wrap.nodes = nodes;
-    wrap.edges = edges;
-    wrap.row_offsets = const_cast<int *>(row_offsets);
-    wrap.column_indices = const_cast<int *>(col_indices);
-    wrap.edge_values = reinterpret_cast<int *>(const_cast<unsigned *>(edge_weights));
-    hipError_t rc = p->runner->Init(wrap, delta_factor);
-    wrap.row_offsets = nullptr;
-    wrap.column_indices = nullptr;
-    wrap.edge_values = nullptr;
-    return static_cast<int>(rc);
+    BorrowedCsr<> wrap(nodes, edges, row_offsets, col_indices, reinterpret_cast<const int *>(edge_weights));
+    return static_cast<int>(p->runner->Init(wrap.graph, delta_factor));
 }
 
 int grx_sssp_init_device(grx_sssp *p, int nodes, int edges, int *d_row_offsets, int *d_col_indices,
@@ -201,12 +175,9 @@ void gunrock_sssp_func(struct GunrockGraph *graph_out, void *predecessor, const 
         std::printf("Not Yet Support This DataType Combination.\n");
         return;
     }
-    Csr<int, int, int> csr(false);
-    csr.nodes = static_cast<int>(graph_in->num_nodes);
-    csr.edges = static_cast<int>(graph_in->num_edges);
-    csr.row_offsets = static_cast<int *>(graph_in->row_offsets);
-    csr.column_indices = static_cast<int *>(graph_in->col_indices);
-    csr.edge_values = static_cast<int *>(graph_in->edge_values);
+    BorrowedCsr<> borrowed(static_cast<int>(graph_in->num_nodes), static_cast<int>(graph_in->num_edges), static_cast<int *>(graph_in->row_offsets),
+                           static_cast<int *>(graph_in->col_indices), static_cast<int *>(graph_in->edge_values));
+    Csr<int, int, int> &csr = borrowed.graph;
 
     int src = 0;
     switch (configs.src_mode) {  // same rules as BFS (bfs_app.cu:271-294)
@@ -229,9 +200,6 @@ void gunrock_sssp_func(struct GunrockGraph *graph_out, void *predecessor, const 
     graph_out->node_values = h_dist;  // caller frees
     if (!rc) std::printf("GPU Single-Source Shortest Path finished in %lf msec. source: %d\n", elapsed, src);
     delete runner;
-    csr.row_offsets = nullptr;
-    csr.column_indices = nullptr;
-    csr.edge_values = nullptr;
     util::GRError(hipDeviceSynchronize(), "hipDeviceSynchronize failed", __FILE__, __LINE__);
 }
 

@@ -7,6 +7,7 @@
 
 #include <gunrock/app/tc/tc_enactor.hpp>
 #include <gunrock/app/tc/tc_problem.hpp>
+#include <gunrock/app/handle_runner.hpp>
 #include <gunrock/csr.hpp>
 
 using namespace gunrock;
@@ -20,11 +21,10 @@ static_assert(sizeof(long long) == sizeof(Count), "counts are 64-bit");
 namespace {
 
 struct TcRunner {
+    InitState state;
     virtual ~TcRunner() {}
-    virtual hipError_t Init(const Csr<int, int, int> &g) = 0;
-    virtual hipError_t InitDevice(int nodes, int edges, int *d_ro, int *d_ci) = 0;
-    virtual bool Malformed() = 0;
-    virtual bool Used() = 0;
+    virtual int Init(const Csr<int, int, int> &g) = 0;
+    virtual int InitDevice(int nodes, int edges, int *d_ro, int *d_ci) = 0;
     virtual int SetOption(const char *name, double value) = 0;
     virtual hipError_t Reset() = 0;
     virtual hipError_t Enact(int max_grid_size, float *ms) = 0;
@@ -40,36 +40,22 @@ struct TcRunnerT : TcRunner {
     typedef TCProblem<false> Problem;
     Problem problem;
     TCEnactor<INSTR> enactor;
-    hipEvent_t start = nullptr, stop = nullptr;
-    bool ready = false;  // Init succeeded: the other phases may run
-    bool used = false;   // Init was called: a handle takes one graph
+    EventPair timer;
     explicit TcRunnerT(int device) : enactor(false)
     {
         util::GRError(hipSetDevice(device), "hipSetDevice failed", __FILE__, __LINE__);
-        util::GRError(hipEventCreate(&start), "hipEventCreate failed", __FILE__, __LINE__);
-        util::GRError(hipEventCreate(&stop), "hipEventCreate failed", __FILE__, __LINE__);
+        timer.Create();
     }
-    ~TcRunnerT() override
+    int Init(const Csr<int, int, int> &g) override
     {
-        if (start) hipEventDestroy(start);
-        if (stop) hipEventDestroy(stop);
-    }
-    hipError_t Init(const Csr<int, int, int> &g) override
-    {
-        used = true;
         const hipError_t rc = problem.Init(false, g, 1);
-        ready = rc == hipSuccess;
-        return rc;
+        return state.AdmitCode(rc, problem.malformed != 0);
     }
-    hipError_t InitDevice(int nodes, int edges, int *d_ro, int *d_ci) override
+    int InitDevice(int nodes, int edges, int *d_ro, int *d_ci) override
     {
-        used = true;
         const hipError_t rc = problem.InitFromDevice(nodes, edges, d_ro, d_ci);
-        ready = rc == hipSuccess;
-        return rc;
+        return state.AdmitCode(rc, problem.malformed != 0);
     }
-    bool Malformed() override { return problem.malformed != 0; }
-    bool Used() override { return used; }
     int SetOption(const char *name, double value) override
     {
         const long long v = static_cast<long long>(value);
@@ -87,20 +73,11 @@ struct TcRunnerT : TcRunner {
         }
         return 0;
     }
-    hipError_t Reset() override { return ready ? problem.Reset() : hipErrorNotReady; }
+    hipError_t Reset() override { return state.ready ? problem.Reset() : hipErrorNotReady; }
     hipError_t Enact(int max_grid_size, float *ms) override
     {
-        if (!ready) return hipErrorNotReady;
-        hipStream_t stream = problem.graph_slices[0]->stream;
-        hipError_t retval = hipSuccess;
-        GR_CHECK(hipEventRecord(start, stream), "hipEventRecord failed");
-        hipError_t run = enactor.template Enact<Problem>(&problem, max_grid_size);
-        GR_CHECK(hipEventRecord(stop, stream), "hipEventRecord failed");
-        GR_CHECK(hipEventSynchronize(stop), "hipEventSynchronize failed");
-        float t = 0;
-        GR_CHECK(hipEventElapsedTime(&t, start, stop), "hipEventElapsedTime failed");
-        if (ms) *ms = t;
-        return run;
+        if (!state.ready) return hipErrorNotReady;
+        return timer.Timed(problem.graph_slices[0]->stream, ms, [&]() { return enactor.template Enact<Problem>(&problem, max_grid_size); });
     }
     void Stats(long long &oriented, long long &longest, long long &probed, long long &launches, long long *regime_rows, double &kernel_ms,
                double &build_ms) override
@@ -116,27 +93,27 @@ struct TcRunnerT : TcRunner {
     }
     hipError_t Extract(long long *triangles, long long *total) override
     {
-        if (!ready) return hipErrorNotReady;
+        if (!state.ready) return hipErrorNotReady;
         const hipError_t rc = problem.Extract(triangles);
         if (total) *total = problem.total;
         return rc;
     }
     hipError_t Clustering(double *coeff, double *transitivity) override
     {
-        if (!ready) return hipErrorNotReady;
+        if (!state.ready) return hipErrorNotReady;
         return problem.Clustering(coeff, transitivity);
     }
     void DeviceResults(long long **d_triangles, int **d_degrees) override
     {
-        if (d_triangles) *d_triangles = ready ? reinterpret_cast<long long *>(problem.data_slices[0]->d_triangles) : nullptr;
-        if (d_degrees) *d_degrees = ready ? reinterpret_cast<int *>(problem.data_slices[0]->d_degrees) : nullptr;
+        if (d_triangles) *d_triangles = state.ready ? reinterpret_cast<long long *>(problem.data_slices[0]->d_triangles) : nullptr;
+        if (d_degrees) *d_degrees = state.ready ? reinterpret_cast<int *>(problem.data_slices[0]->d_degrees) : nullptr;
     }
 };
 
 }  // namespace
 
 struct grx_tc {
-    TcRunner *runner = nullptr;
+    std::unique_ptr<TcRunner> runner;
 };
 
 extern "C" {
@@ -144,9 +121,7 @@ extern "C" {
 int grx_tc_create(grx_tc **out, int instrument, int device)
 {
     if (!out) return -1;
-    grx_tc *h = new grx_tc();
-    h->runner = instrument ? static_cast<TcRunner *>(new TcRunnerT<true>(device)) : new TcRunnerT<false>(device);
-    *out = h;
+    *out = new grx_tc{MakeRunner<TcRunner, TcRunnerT>(instrument != 0, device)};
     return 0;
 }
 
@@ -154,27 +129,17 @@ int grx_tc_init(grx_tc *p, int nodes, int edges, const int *row_offsets, const i
 {
     if (!p || !row_offsets || nodes < 1 || edges < 0) return -1;
     if (edges > 0 && !col_indices) return -1;
-    if (p->runner->Used()) return -3;
-    Csr<int, int, int> wrap(false);
-    wrap.nodes = nodes;
-    wrap.edges = edges;
-    wrap.row_offsets = const_cast<int *>(row_offsets);
-    wrap.column_indices = const_cast<int *>(col_indices);
-    hipError_t rc = p->runner->Init(wrap);
-    wrap.row_offsets = nullptr;
-    wrap.column_indices = nullptr;
-    if (rc && p->runner->Malformed()) return -2;
-    return static_cast<int>(rc);
+    if (int taken = p->runner->state.Taken()) return taken;
+    BorrowedCsr<> wrap(nodes, edges, row_offsets, col_indices);
+    return p->runner->Init(wrap.graph);
 }
 
 int grx_tc_init_device(grx_tc *p, int nodes, int edges, int *d_row_offsets, int *d_col_indices)
 {
     if (!p || !d_row_offsets || nodes < 1 || edges < 0) return -1;
     if (edges > 0 && !d_col_indices) return -1;
-    if (p->runner->Used()) return -3;
-    const hipError_t rc = p->runner->InitDevice(nodes, edges, d_row_offsets, d_col_indices);
-    if (rc && p->runner->Malformed()) return -2;
-    return static_cast<int>(rc);
+    if (int taken = p->runner->state.Taken()) return taken;
+    return p->runner->InitDevice(nodes, edges, d_row_offsets, d_col_indices);
 }
 
 int grx_tc_set_option(grx_tc *p, const char *name, double value)
@@ -226,11 +191,6 @@ int grx_tc_device_results(grx_tc *p, long long **d_triangles, int **d_degrees)
     return 0;
 }
 
-void grx_tc_destroy(grx_tc *p)
-{
-    if (!p) return;
-    delete p->runner;
-    delete p;
-}
+void grx_tc_destroy(grx_tc *p) { delete p; }
 
 }  // extern "C"

@@ -7,6 +7,7 @@
 
 #include <gunrock/app/truss/truss_enactor.hpp>
 #include <gunrock/app/truss/truss_problem.hpp>
+#include <gunrock/app/handle_runner.hpp>
 #include <gunrock/csr.hpp>
 
 using namespace gunrock;
@@ -18,12 +19,10 @@ static_assert(GRX_TRUSS_AUTO == TRUSS_AUTO && GRX_TRUSS_ROUNDS == TRUSS_ROUNDS, 
 namespace {
 
 struct TrussRunner {
+    InitState state;
     virtual ~TrussRunner() {}
-    virtual hipError_t Init(const Csr<int, int, int> &g) = 0;
-    virtual hipError_t InitDevice(int nodes, int edges, int *d_ro, int *d_ci) = 0;
-    virtual bool Malformed() = 0;
-    virtual bool Used() = 0;
-    virtual bool Ready() = 0;
+    virtual int Init(const Csr<int, int, int> &g) = 0;
+    virtual int InitDevice(int nodes, int edges, int *d_ro, int *d_ci) = 0;
     virtual int SetOption(const char *name, double value) = 0;
     virtual hipError_t Reset() = 0;
     virtual hipError_t Enact(int k_limit, int max_grid_size, float *ms) = 0;
@@ -43,39 +42,24 @@ struct TrussRunnerT : TrussRunner {
     typedef TrussProblem<false> Problem;
     Problem problem;
     TrussEnactor<INSTR> enactor;
-    hipEvent_t start = nullptr, stop = nullptr;
-    bool ready = false;  // Init succeeded: the other phases may run
-    bool used = false;   // Init was called: a handle takes one graph
+    EventPair timer;
     explicit TrussRunnerT(int device) : enactor(false)
     {
         util::GRError(hipSetDevice(device), "hipSetDevice failed", __FILE__, __LINE__);
-        util::GRError(hipEventCreate(&start), "hipEventCreate failed", __FILE__, __LINE__);
-        util::GRError(hipEventCreate(&stop), "hipEventCreate failed", __FILE__, __LINE__);
+        timer.Create();
     }
-    ~TrussRunnerT() override
+    int Init(const Csr<int, int, int> &g) override
     {
-        if (start) hipEventDestroy(start);
-        if (stop) hipEventDestroy(stop);
-    }
-    hipError_t Init(const Csr<int, int, int> &g) override
-    {
-        used = true;
         problem.wave_min_row = enactor.wave_min_row;
         const hipError_t rc = problem.Init(false, g, 1);
-        ready = rc == hipSuccess;
-        return rc;
+        return state.AdmitCode(rc, problem.malformed != 0);
     }
-    hipError_t InitDevice(int nodes, int edges, int *d_ro, int *d_ci) override
+    int InitDevice(int nodes, int edges, int *d_ro, int *d_ci) override
     {
-        used = true;
         problem.wave_min_row = enactor.wave_min_row;
         const hipError_t rc = problem.InitFromDevice(nodes, edges, d_ro, d_ci);
-        ready = rc == hipSuccess;
-        return rc;
+        return state.AdmitCode(rc, problem.malformed != 0);
     }
-    bool Malformed() override { return problem.malformed != 0; }
-    bool Used() override { return used; }
-    bool Ready() override { return ready; }
     int SetOption(const char *name, double value) override
     {
         const long long v = static_cast<long long>(value);
@@ -96,20 +80,11 @@ struct TrussRunnerT : TrussRunner {
         }
         return 0;
     }
-    hipError_t Reset() override { return ready ? problem.Reset() : hipErrorNotReady; }
+    hipError_t Reset() override { return state.ready ? problem.Reset() : hipErrorNotReady; }
     hipError_t Enact(int k_limit, int max_grid_size, float *ms) override
     {
-        if (!ready) return hipErrorNotReady;
-        hipStream_t stream = problem.graph_slices[0]->stream;
-        hipError_t retval = hipSuccess;
-        GR_CHECK(hipEventRecord(start, stream), "hipEventRecord failed");
-        hipError_t run = enactor.template Enact<Problem>(&problem, k_limit, max_grid_size);
-        GR_CHECK(hipEventRecord(stop, stream), "hipEventRecord failed");
-        GR_CHECK(hipEventSynchronize(stop), "hipEventSynchronize failed");
-        float t = 0;
-        GR_CHECK(hipEventElapsedTime(&t, start, stop), "hipEventElapsedTime failed");
-        if (ms) *ms = t;
-        return run;
+        if (!state.ready) return hipErrorNotReady;
+        return timer.Timed(problem.graph_slices[0]->stream, ms, [&]() { return enactor.template Enact<Problem>(&problem, k_limit, max_grid_size); });
     }
     void Stats(long long *out, double *ms) override
     {
@@ -129,51 +104,46 @@ struct TrussRunnerT : TrussRunner {
     }
     int LevelTrace(int max_levels, int *k, long long *edges, double *ms) override
     {
-        const int count = static_cast<int>(enactor.trace_k.size());
-        for (int i = 0; i < count && i < max_levels; ++i) {
-            if (k) k[i] = enactor.trace_k[i];
-            if (edges) edges[i] = enactor.trace_edges[i];
-            if (ms) ms[i] = enactor.trace_ms[i];
-        }
-        return count;
+        return CopyTrace(enactor.trace_k.size(), max_levels, Column(k, [&](int i) { return enactor.trace_k[i]; }),
+                         Column(edges, [&](int i) { return enactor.trace_edges[i]; }), Column(ms, [&](int i) { return enactor.trace_ms[i]; }));
     }
     hipError_t Edges(int *src, int *dst, long long *count) override
     {
-        if (!ready) return hipErrorNotReady;
+        if (!state.ready) return hipErrorNotReady;
         *count = problem.simple_edges;
         return problem.Edges(src, dst);
     }
     hipError_t Support(int *support, long long *total) override
     {
-        if (!ready) return hipErrorNotReady;
+        if (!state.ready) return hipErrorNotReady;
         if (total) *total = problem.triangles;
         return problem.Support(support);
     }
     hipError_t Extract(int *truss_out, int *max_truss) override
     {
-        if (!ready || !problem.enacted) return hipErrorNotReady;
+        if (!state.ready || !problem.enacted) return hipErrorNotReady;
         const hipError_t rc = problem.Extract(truss_out);
         if (max_truss) *max_truss = problem.max_truss;
         return rc;
     }
     hipError_t Classes(int max_entries, long long *sizes, int *count) override
     {
-        if (!ready || !problem.enacted) return hipErrorNotReady;
+        if (!state.ready || !problem.enacted) return hipErrorNotReady;
         return problem.Classes(max_entries, sizes, count);
     }
     hipError_t Members(int k, unsigned char *mask, long long *edges, long long *vertices) override
     {
-        if (!ready || !problem.enacted) return hipErrorNotReady;
+        if (!state.ready || !problem.enacted) return hipErrorNotReady;
         return problem.Members(k, mask, edges, vertices);
     }
     hipError_t VertexTruss(int *out) override
     {
-        if (!ready || !problem.enacted) return hipErrorNotReady;
+        if (!state.ready || !problem.enacted) return hipErrorNotReady;
         return problem.VertexTruss(out);
     }
     void DeviceResults(int **d_truss, int **d_support, int **d_src, int **d_dst) override
     {
-        typename Problem::DataSlice *ds = ready ? problem.data_slices[0] : nullptr;
+        typename Problem::DataSlice *ds = state.ready ? problem.data_slices[0] : nullptr;
         if (d_truss) *d_truss = ds ? ds->d_truss : nullptr;
         if (d_support) *d_support = ds ? ds->d_support : nullptr;
         if (d_src) *d_src = ds ? ds->d_src : nullptr;
@@ -184,7 +154,7 @@ struct TrussRunnerT : TrussRunner {
 }  // namespace
 
 struct grx_truss {
-    TrussRunner *runner = nullptr;
+    std::unique_ptr<TrussRunner> runner;
 };
 
 extern "C" {
@@ -192,9 +162,7 @@ extern "C" {
 int grx_truss_create(grx_truss **out, int instrument, int device)
 {
     if (!out) return -1;
-    grx_truss *h = new grx_truss();
-    h->runner = instrument ? static_cast<TrussRunner *>(new TrussRunnerT<true>(device)) : new TrussRunnerT<false>(device);
-    *out = h;
+    *out = new grx_truss{MakeRunner<TrussRunner, TrussRunnerT>(instrument != 0, device)};
     return 0;
 }
 
@@ -202,27 +170,17 @@ int grx_truss_init(grx_truss *p, int nodes, int edges, const int *row_offsets, c
 {
     if (!p || !row_offsets || nodes < 1 || edges < 0) return -1;
     if (edges > 0 && !col_indices) return -1;
-    if (p->runner->Used()) return -3;
-    Csr<int, int, int> wrap(false);
-    wrap.nodes = nodes;
-    wrap.edges = edges;
-    wrap.row_offsets = const_cast<int *>(row_offsets);
-    wrap.column_indices = const_cast<int *>(col_indices);
-    hipError_t rc = p->runner->Init(wrap);
-    wrap.row_offsets = nullptr;
-    wrap.column_indices = nullptr;
-    if (rc && p->runner->Malformed()) return -2;
-    return static_cast<int>(rc);
+    if (int taken = p->runner->state.Taken()) return taken;
+    BorrowedCsr<> wrap(nodes, edges, row_offsets, col_indices);
+    return p->runner->Init(wrap.graph);
 }
 
 int grx_truss_init_device(grx_truss *p, int nodes, int edges, int *d_row_offsets, int *d_col_indices)
 {
     if (!p || !d_row_offsets || nodes < 1 || edges < 0) return -1;
     if (edges > 0 && !d_col_indices) return -1;
-    if (p->runner->Used()) return -3;
-    const hipError_t rc = p->runner->InitDevice(nodes, edges, d_row_offsets, d_col_indices);
-    if (rc && p->runner->Malformed()) return -2;
-    return static_cast<int>(rc);
+    if (int taken = p->runner->state.Taken()) return taken;
+    return p->runner->InitDevice(nodes, edges, d_row_offsets, d_col_indices);
 }
 
 int grx_truss_set_option(grx_truss *p, const char *name, double value)
@@ -310,11 +268,6 @@ int grx_truss_device_results(grx_truss *p, int **d_truss, int **d_support, int *
     return 0;
 }
 
-void grx_truss_destroy(grx_truss *p)
-{
-    if (!p) return;
-    delete p->runner;
-    delete p;
-}
+void grx_truss_destroy(grx_truss *p) { delete p; }
 
 }  // extern "C"
