@@ -282,12 +282,19 @@ class BFSEnactor : public EnactorBase {
                                    stream, bargs, *ds, lookup);
                 return util::GRError("BottomUpHeadsKernel launch failed", __FILE__, __LINE__);
             }
+            typedef oprtr::advance::BitmapLookup<VertexId> L;
+            const bool walk_queue = problem->walk_queue != 0;  // (two instantiations of the dense body: bottom_up.hpp)
             const long long cap = max_grid_size > 0 ? max_grid_size
-                : util::ResidentGrid(oprtr::advance::BottomUpKernel<BU_THREADS, 8, 32, BFSProblem, oprtr::advance::BitmapLookup<VertexId>>, BU_THREADS);
+                : walk_queue ? util::ResidentGrid(oprtr::advance::BottomUpKernel<BU_THREADS, 8, 32, BFSProblem, L, true>, BU_THREADS)
+                             : util::ResidentGrid(oprtr::advance::BottomUpKernel<BU_THREADS, 8, 32, BFSProblem, L, false>, BU_THREADS);
             if (grid > cap) grid = cap;
             if (grid < 1) grid = 1;
-            hipLaunchKernelGGL((oprtr::advance::BottomUpKernel<BU_THREADS, 8, 32, BFSProblem, oprtr::advance::BitmapLookup<VertexId>>),
-                               dim3(static_cast<unsigned>(grid)), dim3(BU_THREADS), 0, stream, bargs, *ds, lookup);
+            if (walk_queue)
+                hipLaunchKernelGGL((oprtr::advance::BottomUpKernel<BU_THREADS, 8, 32, BFSProblem, L, true>),
+                                   dim3(static_cast<unsigned>(grid)), dim3(BU_THREADS), 0, stream, bargs, *ds, lookup);
+            else
+                hipLaunchKernelGGL((oprtr::advance::BottomUpKernel<BU_THREADS, 8, 32, BFSProblem, L, false>),
+                                   dim3(static_cast<unsigned>(grid)), dim3(BU_THREADS), 0, stream, bargs, *ds, lookup);
             return util::GRError("BottomUpKernel launch failed", __FILE__, __LINE__);
         };
         // ---- a CHAIN of bottom-up sweeps behind one host round trip (bottom_up.hpp BottomUpAutoKernel) ----
@@ -314,8 +321,10 @@ class BFSEnactor : public EnactorBase {
             int queued = 0;
             const long long bu_steps = ((static_cast<long long>(problem->nodes) + 63) / 64 + oprtr::advance::kBottomUpStepWords - 1) / oprtr::advance::kBottomUpStepWords;
             long long grid = (bu_steps + (BU_THREADS / 64) - 1) / (BU_THREADS / 64);
+            const bool walk_queue = problem->walk_queue != 0;  // (two instantiations of the dense body: bottom_up.hpp)
             const long long cap = max_grid_size > 0 ? max_grid_size
-                : util::ResidentGrid(oprtr::advance::BottomUpAutoKernel<BU_THREADS, 8, 32, BFSProblem, L>, BU_THREADS);
+                : walk_queue ? util::ResidentGrid(oprtr::advance::BottomUpAutoKernel<BU_THREADS, 8, 32, BFSProblem, L, true>, BU_THREADS)
+                             : util::ResidentGrid(oprtr::advance::BottomUpAutoKernel<BU_THREADS, 8, 32, BFSProblem, L, false>, BU_THREADS);
             if (grid > cap) grid = cap;
             if (grid < 1) grid = 1;
             const long long chunks = ((static_cast<long long>(problem->nodes) + 63) / 64 + oprtr::advance::kSparseChunkWords - 1) / oprtr::advance::kSparseChunkWords;
@@ -358,9 +367,14 @@ class BFSEnactor : public EnactorBase {
                 chain.d_log = work_progress.d_chain_log;
                 typename BFSProblem::DataSlice level_slice = *ds;
                 level_slice.iteration = static_cast<VertexId>(level);
-                hipLaunchKernelGGL((oprtr::advance::BottomUpAutoKernel<BU_THREADS, 8, 32, BFSProblem, L>), dim3(static_cast<unsigned>(grid)),
-                                   dim3(BU_THREADS), 0, stream, bargs, level_slice, lookup, chain, static_cast<unsigned>(sparse_grid),
-                                   static_cast<unsigned>(emit_grid));
+                if (walk_queue)
+                    hipLaunchKernelGGL((oprtr::advance::BottomUpAutoKernel<BU_THREADS, 8, 32, BFSProblem, L, true>), dim3(static_cast<unsigned>(grid)),
+                                       dim3(BU_THREADS), 0, stream, bargs, level_slice, lookup, chain, static_cast<unsigned>(sparse_grid),
+                                       static_cast<unsigned>(emit_grid));
+                else
+                    hipLaunchKernelGGL((oprtr::advance::BottomUpAutoKernel<BU_THREADS, 8, 32, BFSProblem, L, false>), dim3(static_cast<unsigned>(grid)),
+                                       dim3(BU_THREADS), 0, stream, bargs, level_slice, lookup, chain, static_cast<unsigned>(sparse_grid),
+                                       static_cast<unsigned>(emit_grid));
                 if ((rc = util::GRError("BottomUpAutoKernel launch failed", __FILE__, __LINE__))) return rc;
                 queued = k;
             }

@@ -991,6 +991,8 @@ struct BFSProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
     bool emit_current = false;      // state: a speculative emit pass has run and no vertex has been discovered since
     bool labels_deferred = false;   // state: d_labels is incomplete until EmitLabels has run (set by Reset, cleared by EmitLabels)
     int label_pass = 1;             // policy, read at every launch: 1 the tiled closing pass (TiledLabelsKernel), 0 the per-lane kernels
+    int walk_queue = 1;             // policy, read at every launch: 1 the dense bottom-up sweep queues its row walks per wave (bottom_up.hpp
+                                    // DenseSweepQueued), 0 it walks them step by step (DenseSweep)
     int level_mask_limit = kLevelMasks;  // bitmaps of the pool a search may use (tests shrink it to force mid-search flushes)
     LevelMaskList<VertexId> level_masks; // (bitmap, label) of every kept level
     int mask_ring = 0;

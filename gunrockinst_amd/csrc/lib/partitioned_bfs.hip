@@ -500,6 +500,7 @@ struct Pbfs : app::EnactorBase {
     unsigned *d_never = nullptr;
     unsigned *d_head_base = nullptr;
     long long with_in_edges = 0;
+    int walk_queue = 1;                  // the dense sweep queues its row walks per wave (bottom_up.hpp DenseSweepQueued); 0: walks them step by step
     int sparse_sweep_div = 6;            // compacting sweep when at most n_local / 6 local vertices can still be unvisited (64-word chunks)
     bool never_applied = false;          // step-wise path: visited |= never happened since the last Reset
     util::Frontier<int, int> queues[2];
@@ -847,11 +848,16 @@ struct Pbfs : app::EnactorBase {
         }
         const long long bu_steps = (words64 + oprtr::advance::kBottomUpStepWords - 1) / oprtr::advance::kBottomUpStepWords;
         long long grid = (bu_steps + 3) / 4;
-        const long long cap = util::ResidentGrid(oprtr::advance::BottomUpKernel<256, 8, 32, PbfsProblem, L>, 256);
+        const long long cap = walk_queue ? util::ResidentGrid(oprtr::advance::BottomUpKernel<256, 8, 32, PbfsProblem, L, true>, 256)
+                                         : util::ResidentGrid(oprtr::advance::BottomUpKernel<256, 8, 32, PbfsProblem, L, false>, 256);
         if (grid > cap) grid = cap;
         if (grid < 1) grid = 1;
-        hipLaunchKernelGGL((oprtr::advance::BottomUpKernel<256, 8, 32, PbfsProblem, L>), dim3(static_cast<unsigned>(grid)), dim3(256), 0, stream,
-                           b, ds, lookup);
+        if (walk_queue)
+            hipLaunchKernelGGL((oprtr::advance::BottomUpKernel<256, 8, 32, PbfsProblem, L, true>), dim3(static_cast<unsigned>(grid)), dim3(256), 0,
+                               stream, b, ds, lookup);
+        else
+            hipLaunchKernelGGL((oprtr::advance::BottomUpKernel<256, 8, 32, PbfsProblem, L, false>), dim3(static_cast<unsigned>(grid)), dim3(256), 0,
+                               stream, b, ds, lookup);
         GR_CHECK(hipGetLastError(), "BottomUpKernel launch failed");
         return retval;
     }
@@ -1249,6 +1255,7 @@ int grx_pbfs_set_option(grx_pbfs *p, const char *name, double value)
     if (key == "lite_factor") p->impl.lite_factor = value;
     else if (key == "alpha") p->impl.alpha = value;
     else if (key == "sparse_sweep_div") p->impl.sparse_sweep_div = static_cast<int>(value);
+    else if (key == "walk_queue") p->impl.walk_queue = value != 0.0 ? 1 : 0;
     else return 1;
     return 0;
 }

@@ -133,7 +133,9 @@ int grx_bfs_set_label_deferral(grx_bfs *p, int enabled, int mask_limit);
  * "sparse_sweep_div", "speculative_emit" (1/0: the label pass is queued behind the closing top-down launch without waiting
  * for its read-back), "chain_sweeps" (bottom-up sweeps queued per host round trip), "label_pass" (1, the default: the closing
  * label pass loads every bitmap word once per workgroup tile; 0: the per-lane kernels it replaced; read at every launch of
- * the pass, so it can be flipped between searches).
+ * the pass, so it can be flipped between searches), "walk_queue" (1, the default: the dense bottom-up sweep queues the row walks
+ * of its pending vertices per wave and walks them 64 at a time, DESIGN.md 3.3 m; 0: the step-by-step walk loop it replaced; read
+ * at every launch of a sweep).
  * Relabelled copy (DESIGN.md 3.3 k): a symmetric problem (grx_bfs_set_inverse_graph without arrays, or grx_bfs_auto_inverse
  * on a symmetric graph) also builds a copy of its CSR renumbered hub-first, edgeless-last, and searches it; labels and
  * predecessors still come back in the caller's numbering.  "relabel" (1: search the copy; 0: the caller's numbering; -1, the
@@ -598,7 +600,7 @@ int grx_pbfs_set_options(grx_pbfs *p, int mark_pred, float alpha);
 int grx_pbfs_search(grx_pbfs *p, int src, int direction_optimizing, int *levels, float *elapsed_ms);
 /* Tuning of the level loop by name (1 = unknown name): "lite_factor" (a top-down level runs count-only -- destinations marked with
  * byte stores, ONE all-to-all of per-owner bitmap slices, then bottom-up to the end -- when global frontier edges * alpha *
- * lite_factor > unexplored edges and no parents are wanted; 0 = never), "alpha", "sparse_sweep_div".  grx_pbfs_stat:
+ * lite_factor > unexplored edges and no parents are wanted; 0 = never), "alpha", "sparse_sweep_div", "walk_queue" (as grx_bfs_set_option).  grx_pbfs_stat:
  * "marked_levels" = count-only levels run since the handle was created (-1 = unknown name). */
 int grx_pbfs_set_option(grx_pbfs *p, const char *name, double value);
 long long grx_pbfs_stat(grx_pbfs *p, const char *name);
