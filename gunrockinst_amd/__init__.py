@@ -1,4 +1,4 @@
-"""gunrockinst_amd -- MI355X-native frontier engine (BFS / CC / SSSP / BC / PageRank / TopK / MST / MIS / TC / k-core) behind Gunrock's C ABI.
+"""gunrockinst_amd -- MI355X-native frontier engine (BFS / CC / SSSP / BC / PageRank / TopK / MST / MIS / TC / k-core / k-truss / SCC) behind Gunrock's C ABI.
 
 The product is the shared library ``gunrockinst_amd/lib/libgunrock.so`` (hand-written HIP for gfx950,
 built by ``gunrockinst_amd/csrc/Makefile``).  This package is only the host-side binding: ctypes
@@ -14,6 +14,7 @@ from .capi import (  # noqa: F401
     TcProblem, gunrock_tc, gunrock_clustering, TC_AUTO, TC_LANE, TC_LDS, TC_GLOBAL,
     KcoreProblem, gunrock_kcore, gunrock_kcore_members, KCORE_AUTO, KCORE_ROUNDS, KCORE_DEVICE_LOOP,
     TrussProblem, gunrock_truss, gunrock_edge_support, gunrock_ktruss, TRUSS_AUTO, TRUSS_ROUNDS,
+    SccProblem, gunrock_scc, gunrock_condensation, SCC_AUTO, SCC_ROUNDS, SCC_DEVICE_LOOP, SCC_TRIM, SCC_PIVOT, SCC_COLOUR,
     advance_frontier, advance_queue, advance_reduce,
 )
 
@@ -25,5 +26,6 @@ __all__ = [
     "TcProblem", "gunrock_tc", "gunrock_clustering", "TC_AUTO", "TC_LANE", "TC_LDS", "TC_GLOBAL",
     "KcoreProblem", "gunrock_kcore", "gunrock_kcore_members", "KCORE_AUTO", "KCORE_ROUNDS", "KCORE_DEVICE_LOOP",
     "TrussProblem", "gunrock_truss", "gunrock_edge_support", "gunrock_ktruss", "TRUSS_AUTO", "TRUSS_ROUNDS",
+    "SccProblem", "gunrock_scc", "gunrock_condensation", "SCC_AUTO", "SCC_ROUNDS", "SCC_DEVICE_LOOP", "SCC_TRIM", "SCC_PIVOT", "SCC_COLOUR",
     "advance_frontier", "advance_queue", "advance_reduce",
 ]

@@ -192,6 +192,20 @@ _SIGNATURES = {
     "grx_truss_vertex_truss": (C.c_int, [C.c_void_p, i32p]),
     "grx_truss_device_results": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 4),
     "grx_truss_destroy": (None, [C.c_void_p]),
+    "grx_scc_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int]),
+    "grx_scc_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p]),
+    "grx_scc_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "grx_scc_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
+    "grx_scc_reset": (C.c_int, [C.c_void_p]),
+    "grx_scc_enact": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
+    "grx_scc_stats": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_longlong)] * 8 + [C.POINTER(C.c_double)] * 2),
+    "grx_scc_phase_trace": (C.c_int, [C.c_void_p, C.c_int, i32p, C.POINTER(C.c_longlong), C.POINTER(C.c_double)]),
+    "grx_scc_extract": (C.c_int, [C.c_void_p, i32p, C.POINTER(C.c_longlong)]),
+    "grx_scc_summary": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_longlong)] * 3 + [C.POINTER(C.c_int)]),
+    "grx_scc_sizes": (C.c_int, [C.c_void_p, i32p]),
+    "grx_scc_condensation": (C.c_int, [C.c_void_p, C.c_int, i32p, i32p]),
+    "grx_scc_device_results": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 3),
+    "grx_scc_destroy": (None, [C.c_void_p]),
     "grx_sssp_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int]),
     "grx_sssp_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p, C.POINTER(C.c_uint32), C.c_int]),
     "grx_sssp_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float]),
@@ -1130,6 +1144,124 @@ def gunrock_ktruss(nodes, row_offsets, col_indices, k, device=0):
     """One-shot k-truss extraction (peels the levels below k only): returns (src, dst, mask uint8 per edge, edges, vertices)."""
     return _one_shot(TrussProblem(device=device).init(nodes, row_offsets, col_indices),
                      TrussProblem.reset, lambda p: p.enact(k_limit=k), lambda p: p.edges() + p.members(k))
+
+
+SCC_AUTO, SCC_ROUNDS, SCC_DEVICE_LOOP = 0, 1, 2  # enum GRX_SCC_* (gunrock_mi355x.h)
+SCC_TRIM, SCC_PIVOT, SCC_COLOUR = 0, 1, 2  # enum GRX_SCC_PHASE_* (gunrock_mi355x.h): the kinds of phase_trace()
+
+
+class SccProblem(_Handle):
+    """SccProblem + SccEnactor behind the handle C ABI: the strongly connected components of the CSR read as a directed
+    multigraph: comp[v] = the smallest vertex id of v's component (int32), the component sizes and the condensation."""
+
+    _destroy = "grx_scc_destroy"
+
+    _STATS = ("trimmed", "trim_rounds", "pivot_component", "colour_rounds", "sweeps", "bfs_levels", "entries_read", "kernel_launches")
+
+    def __init__(self, instrument=False, device=0):
+        self._create("grx_scc_create", int(instrument), device)
+        self.nodes = 0
+        self.edges = 0
+
+    def init(self, nodes, row_offsets, col_indices):
+        ro, ci = _csr_arrays(row_offsets, col_indices, nodes)
+        self.nodes, self.edges = int(nodes), int(ci.shape[0])
+        _check(lib().grx_scc_init(self._h, self.nodes, self.edges, _p(ro), _p(ci)), "SccProblem::Init")
+        return self
+
+    def init_device(self, nodes, edges, d_row_offsets, d_col_indices, d_inv_row_offsets=None, d_inv_col_indices=None):
+        """a CSR in HBM (borrowed); the transpose too when both inverse pointers are given, else it is built"""
+        self.nodes, self.edges = int(nodes), int(edges)
+        _check(lib().grx_scc_init_device(self._h, self.nodes, self.edges, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices),
+                                         C.c_void_p(d_inv_row_offsets), C.c_void_p(d_inv_col_indices)), "SccProblem::Init(device)")
+        return self
+
+    def set_option(self, name, value):
+        """"schedule" (SCC_AUTO / SCC_ROUNDS / SCC_DEVICE_LOOP), "pivot_phase", "trim", "pair_trim", "wave_min_row", "loop_max_list",
+        "loop_max_entries"; returns the library's code: 0 = set, 1 = unknown name (a value out of range raises)"""
+        rc = lib().grx_scc_set_option(self._h, name.encode(), float(value))
+        if rc not in (0, 1):
+            _check(rc, "grx_scc_set_option(%s)" % name)
+        return rc
+
+    def reset(self):
+        _check(lib().grx_scc_reset(self._h), "SccProblem::Reset")
+
+    def enact(self, max_grid_size=0):
+        return self._timed(lib().grx_scc_enact, "SccEnactor::Enact", max_grid_size)
+
+    def stats(self):
+        v = [C.c_longlong() for _ in self._STATS]
+        k, b = C.c_double(), C.c_double()
+        _check(lib().grx_scc_stats(self._h, *([C.byref(x) for x in v] + [C.byref(k), C.byref(b)])), "grx_scc_stats")
+        out = {name: x.value for name, x in zip(self._STATS, v)}
+        out["kernel_ms"], out["build_ms"] = k.value, b.value
+        return out
+
+    def phase_trace(self):
+        """the phases of the last enact in order: (kind as int32: SCC_TRIM / SCC_PIVOT / SCC_COLOUR, vertices finished in it as
+        int64, milliseconds as float64)"""
+        count = lib().grx_scc_phase_trace(self._h, 0, None, None, None)
+        if count < 0:
+            _check(count, "grx_scc_phase_trace")
+        kind = np.empty(max(count, 1), dtype=np.int32)
+        vertices = np.empty(max(count, 1), dtype=np.int64)
+        ms = np.empty(max(count, 1), dtype=np.float64)
+        lib().grx_scc_phase_trace(self._h, count, _p(kind), vertices.ctypes.data_as(C.POINTER(C.c_longlong)),
+                                  ms.ctypes.data_as(C.POINTER(C.c_double)))
+        return kind[:count], vertices[:count], ms[:count]
+
+    def extract(self, comp=True):
+        """(comp as int32 per vertex, or None; the number of components)"""
+        out = np.empty(max(self.nodes, 1), dtype=np.int32) if comp else None
+        n = C.c_longlong()
+        _check(lib().grx_scc_extract(self._h, None if out is None else _p(out), C.byref(n)), "SccProblem::Extract")
+        return (None if out is None else out[:self.nodes]), int(n.value)
+
+    def summary(self):
+        """{"components", "trivial", "largest", "largest_root"}"""
+        c, t, l = C.c_longlong(), C.c_longlong(), C.c_longlong()
+        r = C.c_int()
+        _check(lib().grx_scc_summary(self._h, C.byref(c), C.byref(t), C.byref(l), C.byref(r)), "SccProblem::Summary")
+        return {"components": int(c.value), "trivial": int(t.value), "largest": int(l.value), "largest_root": int(r.value)}
+
+    def sizes(self):
+        """size[v] as int32: the vertex count of v's component"""
+        out = np.empty(max(self.nodes, 1), dtype=np.int32)
+        _check(lib().grx_scc_sizes(self._h, _p(out)), "SccProblem::Sizes")
+        return out[:self.nodes]
+
+    def condensation(self, max_edges=None):
+        """the condensation sorted by (from, to): (from as int32, to as int32, the number of pairs); max_edges caps what is
+        copied (0: the count only)"""
+        count = lib().grx_scc_condensation(self._h, 0, None, None)
+        if count < 0:
+            _check(-count, "SccProblem::Condensation")
+        take = count if max_edges is None else min(count, int(max_edges))
+        f = np.empty(max(take, 1), dtype=np.int32)
+        t = np.empty(max(take, 1), dtype=np.int32)
+        if take > 0:
+            rc = lib().grx_scc_condensation(self._h, take, _p(f), _p(t))
+            if rc < 0:
+                _check(-rc, "SccProblem::Condensation")
+        return f[:take], t[:take], count
+
+    def device_results(self):
+        """(device pointers of comp (int32 per vertex), of the transpose's row offsets and of its column indices)"""
+        c, r, i = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(lib().grx_scc_device_results(self._h, C.byref(c), C.byref(r), C.byref(i)), "grx_scc_device_results")
+        return c.value, r.value, i.value
+
+
+def gunrock_scc(nodes, row_offsets, col_indices, device=0):
+    """One-shot strongly connected components: returns (comp int32 per vertex: the smallest id of its component, components)."""
+    return _one_shot(SccProblem(device=device).init(nodes, row_offsets, col_indices), SccProblem.reset, SccProblem.enact, SccProblem.extract)
+
+
+def gunrock_condensation(nodes, row_offsets, col_indices, device=0):
+    """One-shot condensation: returns (comp, from, to), the pairs sorted by (from, to)."""
+    return _one_shot(SccProblem(device=device).init(nodes, row_offsets, col_indices), SccProblem.reset, SccProblem.enact,
+                     lambda p: (p.extract()[0],) + p.condensation()[:2])
 
 
 def gunrock_bc(nodes, row_offsets, col_indices, src=-1, queue_size=1.0, src_mode=SRC_MANUALLY, device=0):

@@ -501,6 +501,81 @@ int grx_truss_device_results(grx_truss *p, int **d_truss, int **d_support, int *
 void grx_truss_destroy(grx_truss *p);
 
 /* ------------------------------------------------------------------------------------------------
+ * SCC: SccProblem + SccEnactor: strongly connected components (the reference snapshot has no app/scc; later Gunrock releases
+ * do).  The directed counterpart of grx_cc_*: the CSR is read as a directed multigraph (duplicates and self-loops allowed and
+ * without effect, rows unsorted, nothing symmetrised).  Every result has one value:
+ *   comp[v]       the smallest vertex id of v's strongly connected component (int32)
+ *   components    the number of components; trivial: those of one vertex; largest: the vertex count of the largest one and
+ *                 largest_root its comp value (ties go to the smaller root)
+ *   size[v]       the vertex count of v's component (int32)
+ *   condensation  the distinct pairs (comp[u], comp[v]) over the edges u -> v between components, sorted by (from, to): a DAG
+ * A topological order of the condensation is not offered: it is not unique.
+ * Init adds the transpose; Enact trims (a vertex without a live in- or out-edge is a component, and so are two vertices whose
+ * only live in-edges, or out-edges, are each other's), splits off the component of
+ * one high-degree pivot by a forward and a backward search, and finishes the rest in colouring rounds (the largest id
+ * propagated forward, a backward search from every vertex that kept its own), in wide launches or in a loop on the device.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct grx_scc grx_scc;
+enum { GRX_SCC_AUTO = 0, GRX_SCC_ROUNDS = 1, GRX_SCC_DEVICE_LOOP = 2 };
+enum { GRX_SCC_PHASE_TRIM = 0, GRX_SCC_PHASE_PIVOT = 1, GRX_SCC_PHASE_COLOUR = 2 }; /* the kinds of grx_scc_phase_trace */
+
+/* (no counterpart in the reference snapshot: this call and the ones below are shaped like grx_kcore_*) */
+int grx_scc_create(grx_scc **out, int instrument, int device);
+/* SccProblem::Init: validates the CSR and builds its transpose on the device (no reference counterpart).  -1: nodes < 1,
+ * edges < 0 or a NULL array; -2: not a CSR of `nodes` vertices, as grx_tc_init; -3: the handle has been given a graph before
+ * (accepted or rejected) */
+int grx_scc_init(grx_scc *p, int nodes, int edges, const int *row_offsets, const int *col_indices);
+/* the same for a CSR already in HBM (borrowed, not freed; no reference counterpart).  d_inv_row_offsets / d_inv_col_indices: the
+ * transpose, borrowed and validated too, or both NULL: then it is built.  One of the two NULL is -1 */
+int grx_scc_init_device(grx_scc *p, int nodes, int edges, int *d_row_offsets, int *d_col_indices, int *d_inv_row_offsets,
+                        int *d_inv_col_indices);
+/* named options, for the next Enact; 0: set, 1: unknown name, -1: a value out of range.  None changes a result (no reference
+ * counterpart).
+ *   "schedule"          GRX_SCC_AUTO (default): a step (a pass over the live list, a trim sub-round, a search level, a
+ *                       propagation sweep) is a launch of its own while it is wide, and everything else runs in a loop on the
+ *                       device, one launch and one read-back for a whole stretch of steps; GRX_SCC_ROUNDS: every step is a launch
+ *                       and a read-back (the plain form, for comparison); GRX_SCC_DEVICE_LOOP: every step runs in the device loop
+ *   "pivot_phase"       0 / 1 (default 1): 0 leaves everything after the first trim to the colouring rounds
+ *   "trim"              0 / 1 (default 1).  0 is there for comparison and can be very slow: without trimming every component,
+ *                       single vertices included, is left to the colouring rounds, and a chain of k small components whose ids
+ *                       fall along the edges then costs k rounds of up to k sweeps each (2000 two-cycles with "pivot_phase" 0:
+ *                       4.0 M sweeps, about 100 s measured)
+ *   "pair_trim"         0 / 1 (default 1; it needs "trim"): when the peel has run dry, two vertices whose only live in-edges, or
+ *                       out-edges, are each other's are finished as a component of two and the peel goes on from them
+ *   "wave_min_row"      >= 1: rows of at least this many entries are walked by the whole wave, shorter ones by a lane (default 16)
+ *   "loop_max_list"     under AUTO the device loop takes a step over at most this many vertices (default 32768)
+ *   "loop_max_entries"  ... whose rows hold at most this many entries (default 8192) */
+int grx_scc_set_option(grx_scc *p, const char *name, double value);
+/* SccProblem::Reset: every vertex live in one region (no reference counterpart) */
+int grx_scc_reset(grx_scc *p);
+/* SccEnactor::Enact(problem, max_grid_size), HIP-event timed (no reference counterpart).  An Enact that does not follow a Reset
+ * makes its own */
+int grx_scc_enact(grx_scc *p, int max_grid_size, float *elapsed_ms);
+/* of the last Enact (no reference counterpart): the vertices finished by trimming and the trim sub-rounds, the size of the
+ * pivot's component (0 without a pivot phase), the colouring rounds, their propagation sweeps, the levels of all searches, row
+ * entries walked, kernel launches and -- when instrumented -- the summed kernel time; build_ms: the HIP-event time of Init's
+ * transpose (0 for a borrowed one) */
+int grx_scc_stats(grx_scc *p, long long *trimmed, long long *trim_rounds, long long *pivot_component, long long *colour_rounds,
+                  long long *sweeps, long long *bfs_levels, long long *entries_read, long long *kernel_launches, double *kernel_ms,
+                  double *build_ms);
+/* the phases of the last Enact in order, at most max_phases of them (no reference counterpart): the kind
+ * (GRX_SCC_PHASE_*), the vertices finished in it and the time to the next phase's start by the device's constant-rate counter; returns the number of phases (the first 65536 are recorded) */
+int grx_scc_phase_trace(grx_scc *p, int max_phases, int *kind, long long *vertices, double *ms);
+/* (no reference counterpart) */
+int grx_scc_extract(grx_scc *p, int *h_comp /* may be NULL */, long long *components);
+/* (no reference counterpart) any pointer may be NULL */
+int grx_scc_summary(grx_scc *p, long long *components, long long *trivial, long long *largest, int *largest_root);
+/* (no reference counterpart) */
+int grx_scc_sizes(grx_scc *p, int *h_size);
+/* the first max_edges pairs of the condensation into h_from / h_to (either NULL, or max_edges 0: none is copied); returns the
+ * number of pairs, which must fit an int, or a negated hipError_t (no reference counterpart) */
+int grx_scc_condensation(grx_scc *p, int max_edges, int *h_from, int *h_to);
+/* device arrays of the handle (no reference counterpart): comp (`nodes` int32) and the transpose it runs on (its own or the
+ * borrowed one) */
+int grx_scc_device_results(grx_scc *p, int **d_comp, int **d_inv_row_offsets, int **d_inv_col_indices);
+void grx_scc_destroy(grx_scc *p);
+
+/* ------------------------------------------------------------------------------------------------
  * SSSP: SSSPProblem + SSSPEnactor (reference gunrock/app/sssp/sssp_problem.cuh:35-387, sssp_enactor.cuh:36-563)
  * ---------------------------------------------------------------------------------------------- */
 typedef struct grx_sssp grx_sssp;
