@@ -1,4 +1,4 @@
-"""gunrockinst_amd -- MI355X-native frontier engine (BFS / CC / SSSP / BC / PageRank / TopK / MST / MIS / TC / k-core / k-truss / SCC) behind Gunrock's C ABI.
+"""gunrockinst_amd -- MI355X-native frontier engine (BFS / CC / SSSP / BC / PageRank / TopK / MST / MIS / TC / k-core / k-truss / SCC / MS-BFS) behind Gunrock's C ABI.
 
 The product is the shared library ``gunrockinst_amd/lib/libgunrock.so`` (hand-written HIP for gfx950,
 built by ``gunrockinst_amd/csrc/Makefile``).  This package is only the host-side binding: ctypes
@@ -15,6 +15,9 @@ from .capi import (  # noqa: F401
     KcoreProblem, gunrock_kcore, gunrock_kcore_members, KCORE_AUTO, KCORE_ROUNDS, KCORE_DEVICE_LOOP,
     TrussProblem, gunrock_truss, gunrock_edge_support, gunrock_ktruss, TRUSS_AUTO, TRUSS_ROUNDS,
     SccProblem, gunrock_scc, gunrock_condensation, SCC_AUTO, SCC_ROUNDS, SCC_DEVICE_LOOP, SCC_TRIM, SCC_PIVOT, SCC_COLOUR,
+    MsbfsProblem, gunrock_msbfs, gunrock_closeness, gunrock_eccentricity, closeness_from_sums, MSBFS_AUTO, MSBFS_PUSH, MSBFS_PULL, MSBFS_ALTERNATE,
+    MSBFS_INVERSE_AUTO, MSBFS_INVERSE_NONE, MSBFS_INVERSE_SELF, MSBFS_INVERSE_BUILD, MSBFS_LEVEL_PUSH, MSBFS_LEVEL_PULL,
+    MSBFS_DEPTHS_NOT_STORED, MSBFS_INVERSE_NOT_SYMMETRIC,
     advance_frontier, advance_queue, advance_reduce,
 )
 
@@ -27,5 +30,8 @@ __all__ = [
     "KcoreProblem", "gunrock_kcore", "gunrock_kcore_members", "KCORE_AUTO", "KCORE_ROUNDS", "KCORE_DEVICE_LOOP",
     "TrussProblem", "gunrock_truss", "gunrock_edge_support", "gunrock_ktruss", "TRUSS_AUTO", "TRUSS_ROUNDS",
     "SccProblem", "gunrock_scc", "gunrock_condensation", "SCC_AUTO", "SCC_ROUNDS", "SCC_DEVICE_LOOP", "SCC_TRIM", "SCC_PIVOT", "SCC_COLOUR",
+    "MsbfsProblem", "gunrock_msbfs", "gunrock_closeness", "gunrock_eccentricity", "closeness_from_sums", "MSBFS_AUTO", "MSBFS_PUSH", "MSBFS_PULL",
+    "MSBFS_ALTERNATE", "MSBFS_INVERSE_AUTO", "MSBFS_INVERSE_NONE", "MSBFS_INVERSE_SELF", "MSBFS_INVERSE_BUILD", "MSBFS_LEVEL_PUSH", "MSBFS_LEVEL_PULL",
+    "MSBFS_DEPTHS_NOT_STORED", "MSBFS_INVERSE_NOT_SYMMETRIC",
     "advance_frontier", "advance_queue", "advance_reduce",
 ]

@@ -206,6 +206,20 @@ _SIGNATURES = {
     "grx_scc_condensation": (C.c_int, [C.c_void_p, C.c_int, i32p, i32p]),
     "grx_scc_device_results": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 3),
     "grx_scc_destroy": (None, [C.c_void_p]),
+    "grx_msbfs_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int]),
+    "grx_msbfs_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p]),
+    "grx_msbfs_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "grx_msbfs_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
+    "grx_msbfs_reset": (C.c_int, [C.c_void_p, i32p, C.c_int, C.c_int]),
+    "grx_msbfs_enact": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
+    "grx_msbfs_stats": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_longlong)] * 6 + [C.POINTER(C.c_double)] * 2),
+    "grx_msbfs_level_trace": (C.c_int, [C.c_void_p, C.c_int, i32p, i32p, i32p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
+                                        C.POINTER(C.c_double)]),
+    "grx_msbfs_extract_depths": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p]),
+    "grx_msbfs_source_summary": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), i32p]),
+    "grx_msbfs_vertex_summary": (C.c_int, [C.c_void_p, i32p, C.POINTER(C.c_longlong)]),
+    "grx_msbfs_device_results": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 6),
+    "grx_msbfs_destroy": (None, [C.c_void_p]),
     "grx_sssp_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int]),
     "grx_sssp_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p, C.POINTER(C.c_uint32), C.c_int]),
     "grx_sssp_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float]),
@@ -1262,6 +1276,150 @@ def gunrock_condensation(nodes, row_offsets, col_indices, device=0):
     """One-shot condensation: returns (comp, from, to), the pairs sorted by (from, to)."""
     return _one_shot(SccProblem(device=device).init(nodes, row_offsets, col_indices), SccProblem.reset, SccProblem.enact,
                      lambda p: (p.extract()[0],) + p.condensation()[:2])
+
+
+MSBFS_AUTO, MSBFS_PUSH, MSBFS_PULL, MSBFS_ALTERNATE = 0, 1, 2, 3  # enum GRX_MSBFS_* (gunrock_mi355x.h): option "direction"
+MSBFS_INVERSE_AUTO, MSBFS_INVERSE_NONE, MSBFS_INVERSE_SELF, MSBFS_INVERSE_BUILD = 0, 1, 2, 3  # enum GRX_MSBFS_INVERSE_*: option "inverse"
+MSBFS_LEVEL_PUSH, MSBFS_LEVEL_PULL = 0, 1  # enum GRX_MSBFS_LEVEL_*: the kinds of level_trace()
+MSBFS_DEPTHS_NOT_STORED, MSBFS_INVERSE_NOT_SYMMETRIC = -4, -5  # the family's codes next to -1 / -2 / -3
+
+
+def _i64p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_longlong))
+
+
+class MsbfsProblem(_Handle):
+    """MsbfsProblem + MsbfsEnactor behind the handle C ABI: breadth-first searches from k sources on the CSR read as a directed
+    multigraph, 64 sources per pass over the edges.  All results are integers: depths(), source_summary(), vertex_summary()."""
+
+    _destroy = "grx_msbfs_destroy"
+
+    _STATS = ("batches", "levels", "push_levels", "pull_levels", "entries_read", "kernel_launches")
+
+    def __init__(self, instrument=False, device=0):
+        self._create("grx_msbfs_create", int(instrument), device)
+        self.nodes = 0
+        self.edges = 0
+        self.sources = 0
+
+    def init(self, nodes, row_offsets, col_indices):
+        ro, ci = _csr_arrays(row_offsets, col_indices, nodes)
+        self.nodes, self.edges = int(nodes), int(ci.shape[0])
+        _check(lib().grx_msbfs_init(self._h, self.nodes, self.edges, _p(ro), _p(ci)), "MsbfsProblem::Init")
+        return self
+
+    def init_device(self, nodes, edges, d_row_offsets, d_col_indices, d_inv_row_offsets=None, d_inv_col_indices=None):
+        """a CSR in HBM (borrowed); the in-neighbour lists too when both inverse pointers are given"""
+        self.nodes, self.edges = int(nodes), int(edges)
+        _check(lib().grx_msbfs_init_device(self._h, self.nodes, self.edges, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices),
+                                           C.c_void_p(d_inv_row_offsets), C.c_void_p(d_inv_col_indices)), "MsbfsProblem::Init(device)")
+        return self
+
+    def set_option(self, name, value):
+        """"direction" (MSBFS_AUTO / MSBFS_PUSH / MSBFS_PULL / MSBFS_ALTERNATE), "inverse" (MSBFS_INVERSE_*, settled by the next
+        reset), "alpha", "beta", "wave_min_row"; returns the library's code: 0 = set, 1 = unknown name (a value out of range raises)"""
+        rc = lib().grx_msbfs_set_option(self._h, name.encode(), float(value))
+        if rc not in (0, 1):
+            _check(rc, "grx_msbfs_set_option(%s)" % name)
+        return rc
+
+    def reset(self, sources, store_depths=True):
+        """the sources (vertex ids, repeats allowed, at least one) of the next enact.  Raises with code -1 for a source outside
+        [0, nodes) and with code -5 when "inverse" is MSBFS_INVERSE_SELF and the graph is not symmetric; the handle stays usable"""
+        src = _i32(sources).reshape(-1)
+        _check(lib().grx_msbfs_reset(self._h, _p(src), int(src.shape[0]), int(bool(store_depths))), "MsbfsProblem::Reset")
+        self.sources = int(src.shape[0])
+
+    def enact(self, max_grid_size=0):
+        return self._timed(lib().grx_msbfs_enact, "MsbfsEnactor::Enact", max_grid_size)
+
+    def stats(self):
+        v = [C.c_longlong() for _ in self._STATS]
+        k, b = C.c_double(), C.c_double()
+        _check(lib().grx_msbfs_stats(self._h, *([C.byref(x) for x in v] + [C.byref(k), C.byref(b)])), "grx_msbfs_stats")
+        out = {name: x.value for name, x in zip(self._STATS, v)}
+        out["kernel_ms"], out["build_ms"] = k.value, b.value
+        return out
+
+    def level_trace(self):
+        """the levels of the last enact in order: (batch, level, kind: MSBFS_LEVEL_PUSH / MSBFS_LEVEL_PULL) as int32, (frontier
+        vertices, frontier out-row entries) as int64, milliseconds as float64 (0 unless instrumented)"""
+        count = lib().grx_msbfs_level_trace(self._h, 0, None, None, None, None, None, None)
+        if count < 0:
+            _check(count, "grx_msbfs_level_trace")
+        batch, level, kind = (np.empty(max(count, 1), dtype=np.int32) for _ in range(3))
+        frontier, edges = (np.empty(max(count, 1), dtype=np.int64) for _ in range(2))
+        ms = np.empty(max(count, 1), dtype=np.float64)
+        lib().grx_msbfs_level_trace(self._h, count, _p(batch), _p(level), _p(kind), _i64p(frontier), _i64p(edges), ms.ctypes.data_as(C.POINTER(C.c_double)))
+        return batch[:count], level[:count], kind[:count], frontier[:count], edges[:count], ms[:count]
+
+    def depths(self, first=0, count=None):
+        """depth[first : first + count] as int32 [count, nodes]; raises with code -4 after a reset with store_depths off"""
+        count = self.sources - int(first) if count is None else int(count)
+        out = np.empty((max(count, 0), self.nodes), dtype=np.int32)
+        _check(lib().grx_msbfs_extract_depths(self._h, int(first), count, _p(out)), "MsbfsProblem::ExtractDepths")
+        return out
+
+    def source_summary(self):
+        """(reached int64, dist_sum int64, ecc int32), one entry per source"""
+        reached, dist_sum = (np.empty(max(self.sources, 1), dtype=np.int64) for _ in range(2))
+        ecc = np.empty(max(self.sources, 1), dtype=np.int32)
+        _check(lib().grx_msbfs_source_summary(self._h, _i64p(reached), _i64p(dist_sum), _p(ecc)), "MsbfsProblem::SourceSummary")
+        return reached[:self.sources], dist_sum[:self.sources], ecc[:self.sources]
+
+    def vertex_summary(self):
+        """(sources_reaching int32, in_dist_sum int64), one entry per vertex"""
+        reaching = np.empty(max(self.nodes, 1), dtype=np.int32)
+        in_dist_sum = np.empty(max(self.nodes, 1), dtype=np.int64)
+        _check(lib().grx_msbfs_vertex_summary(self._h, _p(reaching), _i64p(in_dist_sum)), "MsbfsProblem::VertexSummary")
+        return reaching[:self.nodes], in_dist_sum[:self.nodes]
+
+    def device_results(self):
+        """device pointers of (depth or None, reached, dist_sum, ecc, sources_reaching, in_dist_sum)"""
+        v = [C.c_void_p() for _ in range(6)]
+        _check(lib().grx_msbfs_device_results(self._h, *[C.byref(x) for x in v]), "grx_msbfs_device_results")
+        return tuple(x.value for x in v)
+
+
+def closeness_from_sums(nodes, sources, sources_reaching, in_dist_sum, wf_improved=True):
+    """float64 closeness per vertex from MS-BFS's integers, in the formula of networkx.closeness_centrality on incoming distances:
+    r = the sources other than v itself that reach v, c = r / in_dist_sum (0 where the sum is 0), times r / (nodes - 1) with
+    wf_improved (Wasserman-Faust).  With every vertex as a source this is networkx's value."""
+    own = np.bincount(np.asarray(sources, dtype=np.int64).reshape(-1), minlength=int(nodes))
+    r = (np.asarray(sources_reaching, dtype=np.int64) - own).astype(np.float64)
+    total = np.asarray(in_dist_sum, dtype=np.int64).astype(np.float64)
+    c = np.zeros(int(nodes), dtype=np.float64)
+    some = total > 0
+    c[some] = r[some] / total[some]
+    if wf_improved and nodes > 1:
+        c *= r / (float(nodes) - 1.0)
+    return c
+
+
+def gunrock_msbfs(nodes, row_offsets, col_indices, sources, device=0):
+    """One-shot multi-source BFS: returns (depth int32 [k, nodes], reached int64 [k], dist_sum int64 [k], ecc int32 [k])."""
+    return _one_shot(MsbfsProblem(device=device).init(nodes, row_offsets, col_indices), lambda p: p.reset(sources), MsbfsProblem.enact,
+                     lambda p: (p.depths(),) + p.source_summary())
+
+
+def gunrock_closeness(nodes, row_offsets, col_indices, sources=None, wf_improved=True, device=0):
+    """One-shot closeness centrality on incoming distances (float64 per vertex, closeness_from_sums' formula).  sources None: every
+    vertex, which gives networkx.closeness_centrality(G, wf_improved=wf_improved) of the digraph; the depths are not stored."""
+    src = np.arange(int(nodes), dtype=np.int32) if sources is None else _i32(sources).reshape(-1)
+    reaching, in_dist_sum = _one_shot(MsbfsProblem(device=device).init(nodes, row_offsets, col_indices),
+                                      lambda p: p.reset(src, store_depths=False), MsbfsProblem.enact, MsbfsProblem.vertex_summary)
+    return closeness_from_sums(nodes, src, reaching, in_dist_sum, wf_improved)
+
+
+def gunrock_eccentricity(nodes, row_offsets, col_indices, device=0):
+    """One-shot eccentricities: returns (ecc int32 per vertex, diameter, radius).  ecc[v] is the largest FINITE distance from v, so
+    on a graph that is not strongly connected it is taken inside what v reaches (0 for a vertex without out-edges); diameter and
+    radius are the largest and the smallest ecc, i.e. the diameter is the largest finite distance between any two vertices and
+    is not infinite for a disconnected graph."""
+    src = np.arange(int(nodes), dtype=np.int32)
+    ecc = _one_shot(MsbfsProblem(device=device).init(nodes, row_offsets, col_indices), lambda p: p.reset(src, store_depths=False),
+                    MsbfsProblem.enact, lambda p: p.source_summary()[2].copy())
+    return ecc, int(ecc.max()), int(ecc.min())
 
 
 def gunrock_bc(nodes, row_offsets, col_indices, src=-1, queue_size=1.0, src_mode=SRC_MANUALLY, device=0):

@@ -576,6 +576,83 @@ int grx_scc_device_results(grx_scc *p, int **d_comp, int **d_inv_row_offsets, in
 void grx_scc_destroy(grx_scc *p);
 
 /* ------------------------------------------------------------------------------------------------
+ * MS-BFS: MsbfsProblem + MsbfsEnactor: breadth-first searches from k sources, 64 per pass over the edges (bit-parallel multi-source
+ * BFS, Then et al., VLDB 2014; the reference snapshot has no counterpart).  The CSR is read as a directed multigraph, as grx_scc_*
+ * reads it (duplicates and self-loops allowed and without effect, rows unsorted, nothing symmetrised).  Sources may repeat; each
+ * gets its own row.  Every result is an integer with one value:
+ *   depth[s][v]          int32, layout [source][vertex]: what grx_bfs_* labels v from sources[s]: 0 at the source, -1 where
+ *                        unreachable.  Stored only on request: it is 4 * k * nodes bytes
+ *   reached[s]           int64: the vertices with depth[s][v] >= 0, the source included
+ *   dist_sum[s]          int64: the sum of those depths
+ *   ecc[s]               int32: the largest of them
+ *   sources_reaching[v]  int32: the sources s of the call with depth[s][v] >= 0 (a repeated source counts each time)
+ *   in_dist_sum[v]       int64: the sum of depth[s][v] over them: the incoming distances of closeness centrality
+ * Every vertex carries one 64-bit word per state array, bit b for the batch's source b.  A level is a push (the queue of frontier
+ * vertices ORs its bits into the words of its out-neighbours with a returning atomic; the lane that finds a word empty queues the
+ * vertex) or a pull (every vertex that some search has not reached ORs the frontier words of its in-neighbours and stops as soon
+ * as nothing is missing).  Batches of 64 sources run one after another.  No float is produced on the device.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct grx_msbfs grx_msbfs;
+enum { GRX_MSBFS_AUTO = 0, GRX_MSBFS_PUSH = 1, GRX_MSBFS_PULL = 2, GRX_MSBFS_ALTERNATE = 3 };               /* option "direction" */
+enum { GRX_MSBFS_INVERSE_AUTO = 0, GRX_MSBFS_INVERSE_NONE = 1, GRX_MSBFS_INVERSE_SELF = 2, GRX_MSBFS_INVERSE_BUILD = 3 }; /* option "inverse" */
+enum { GRX_MSBFS_LEVEL_PUSH = 0, GRX_MSBFS_LEVEL_PULL = 1 };                                                 /* the kinds of the level trace */
+enum { GRX_MSBFS_DEPTHS_NOT_STORED = -4, GRX_MSBFS_INVERSE_NOT_SYMMETRIC = -5 };                             /* codes next to -1 / -2 / -3 */
+
+/* (no counterpart in the reference snapshot: this call and the ones below are shaped like the SCC handle's) */
+int grx_msbfs_create(grx_msbfs **out, int instrument, int device);
+/* MsbfsProblem::Init: validates the CSR (no reference counterpart).  -1: nodes < 1, edges < 0 or a NULL array; -2: not a CSR of
+ * `nodes` vertices; -3: the handle has been given a graph before (accepted or rejected) */
+int grx_msbfs_init(grx_msbfs *p, int nodes, int edges, const int *row_offsets, const int *col_indices);
+/* the same for a CSR already in HBM (borrowed, not freed; no reference counterpart).  d_inv_row_offsets / d_inv_col_indices: the
+ * in-neighbour lists (the transpose), borrowed and validated too, or both NULL.  One of the two NULL is -1 */
+int grx_msbfs_init_device(grx_msbfs *p, int nodes, int edges, int *d_row_offsets, int *d_col_indices, int *d_inv_row_offsets,
+                          int *d_inv_col_indices);
+/* named options; 0: set, 1: unknown name, -1: a value out of range.  None changes a result (no reference counterpart).
+ *   "direction"     GRX_MSBFS_AUTO (default): push until the frontier's out-row entries times "alpha" exceed the row entries of
+ *                   the vertices some search of the batch has not reached, then pull until the frontier's vertices times "beta"
+ *                   fall below `nodes`; GRX_MSBFS_PUSH / GRX_MSBFS_PULL: every level that way; GRX_MSBFS_ALTERNATE: odd levels push,
+ *                   even levels pull (both hand-overs on every graph, for tests).  Without in-neighbour lists every level is a push
+ *   "inverse"       where a pull's in-neighbour lists come from, settled by the next Reset.  GRX_MSBFS_INVERSE_AUTO (default): the
+ *                   ones lent at init_device, else the graph itself when the device symmetry check passes (sorted, duplicate-free
+ *                   rows, every entry mirrored), else a transpose built on the device; GRX_MSBFS_INVERSE_NONE: none;
+ *                   GRX_MSBFS_INVERSE_SELF: the graph itself, which that Reset refuses with GRX_MSBFS_INVERSE_NOT_SYMMETRIC when the
+ *                   check does not pass (the check is conservative: unsorted rows or duplicates fail it); GRX_MSBFS_INVERSE_BUILD:
+ *                   the lent ones, else a built transpose, without asking the check
+ *   "alpha", "beta" > 0 (defaults 4 and 24)
+ *   "wave_min_row"  >= 1: rows of at least this many entries are walked by the whole wave, shorter ones by a lane (default 16) */
+int grx_msbfs_set_option(grx_msbfs *p, const char *name, double value);
+/* MsbfsProblem::Reset: takes `count` >= 1 sources (copied) and sets every result to its value before the first level: depth 0 and
+ * reached 1 at each source, nothing else reached (no reference counterpart).  store_depths 0: no depth array is kept.  -1: a NULL
+ * array, count < 1 or a source outside [0, nodes), and GRX_MSBFS_INVERSE_NOT_SYMMETRIC as above: in both cases nothing has changed
+ * and the handle stays usable (after the latter, with another "inverse") */
+int grx_msbfs_reset(grx_msbfs *p, const int *sources, int count, int store_depths);
+/* MsbfsEnactor::Enact(problem, max_grid_size), HIP-event timed (no reference counterpart).  An Enact that does not follow a Reset
+ * repeats the last one */
+int grx_msbfs_enact(grx_msbfs *p, int max_grid_size, float *elapsed_ms);
+/* of the last Enact (no reference counterpart): batches, levels of all batches and how many were pushes and pulls, row entries
+ * walked, kernel launches and -- when instrumented -- the summed level time; build_ms: the HIP-event time of a built transpose (0
+ * when none was built).  Any pointer may be NULL */
+int grx_msbfs_stats(grx_msbfs *p, long long *batches, long long *levels, long long *push_levels, long long *pull_levels,
+                    long long *entries_read, long long *kernel_launches, double *kernel_ms, double *build_ms);
+/* the levels of the last Enact in order, at most max_levels of them (no reference counterpart): the batch, the depth the level
+ * assigns (1, 2, ...; a batch's last level reaches nothing, so a batch has its largest eccentricity + 1 levels), the kind
+ * (GRX_MSBFS_LEVEL_*), the vertices and out-row entries of the frontier it starts from and -- when instrumented -- its time;
+ * returns the number of levels.  Any array may be NULL */
+int grx_msbfs_level_trace(grx_msbfs *p, int max_levels, int *batch, int *level, int *kind, long long *frontier, long long *edges,
+                          double *ms);
+/* rows [first_source, first_source + source_count) of depth[][] into h_depth, source_count * nodes int32 (no reference
+ * counterpart).  GRX_MSBFS_DEPTHS_NOT_STORED after a Reset with store_depths 0; -1: a range outside the sources */
+int grx_msbfs_extract_depths(grx_msbfs *p, int first_source, int source_count, int *h_depth);
+/* `count` entries each, any pointer may be NULL (no reference counterpart) */
+int grx_msbfs_source_summary(grx_msbfs *p, long long *reached, long long *dist_sum, int *ecc);
+/* `nodes` entries each, any pointer may be NULL (no reference counterpart) */
+int grx_msbfs_vertex_summary(grx_msbfs *p, int *sources_reaching, long long *in_dist_sum);
+/* device arrays of the handle (no reference counterpart): depth (NULL when not stored) and the five summaries */
+int grx_msbfs_device_results(grx_msbfs *p, int **d_depth, long long **d_reached, long long **d_dist_sum, int **d_ecc,
+                             int **d_sources_reaching, long long **d_in_dist_sum);
+void grx_msbfs_destroy(grx_msbfs *p);
+
+/* ------------------------------------------------------------------------------------------------
  * SSSP: SSSPProblem + SSSPEnactor (reference gunrock/app/sssp/sssp_problem.cuh:35-387, sssp_enactor.cuh:36-563)
  * ---------------------------------------------------------------------------------------------- */
 typedef struct grx_sssp grx_sssp;
