@@ -220,6 +220,21 @@ _SIGNATURES = {
     "grx_msbfs_vertex_summary": (C.c_int, [C.c_void_p, i32p, C.POINTER(C.c_longlong)]),
     "grx_msbfs_device_results": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 6),
     "grx_msbfs_destroy": (None, [C.c_void_p]),
+    "grx_bcc_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int]),
+    "grx_bcc_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p]),
+    "grx_bcc_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "grx_bcc_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
+    "grx_bcc_reset": (C.c_int, [C.c_void_p]),
+    "grx_bcc_enact": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
+    "grx_bcc_stats": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_longlong)] * 6 + [C.POINTER(C.c_double)] * 2),
+    "grx_bcc_phase_trace": (C.c_int, [C.c_void_p, C.c_int, i32p, C.POINTER(C.c_longlong), C.POINTER(C.c_double)]),
+    "grx_bcc_edges": (C.c_int, [C.c_void_p, i32p, i32p]),
+    "grx_bcc_extract": (C.c_int, [C.c_void_p, i32p, C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte), i32p, i32p]),
+    "grx_bcc_summary": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_longlong)] * 4 + [C.POINTER(C.c_int)] + [C.POINTER(C.c_longlong)] * 2 +
+                        [C.POINTER(C.c_int)]),
+    "grx_bcc_block_cut": (C.c_int, [C.c_void_p, C.c_int, i32p, i32p]),
+    "grx_bcc_device_results": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 8),
+    "grx_bcc_destroy": (None, [C.c_void_p]),
     "grx_sssp_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int]),
     "grx_sssp_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p, C.POINTER(C.c_uint32), C.c_int]),
     "grx_sssp_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float]),
@@ -1276,6 +1291,155 @@ def gunrock_condensation(nodes, row_offsets, col_indices, device=0):
     """One-shot condensation: returns (comp, from, to), the pairs sorted by (from, to)."""
     return _one_shot(SccProblem(device=device).init(nodes, row_offsets, col_indices), SccProblem.reset, SccProblem.enact,
                      lambda p: (p.extract()[0],) + p.condensation()[:2])
+
+
+BCC_AUTO, BCC_ROUNDS, BCC_DEVICE_LOOP = 0, 1, 2  # enum GRX_BCC_* (gunrock_mi355x.h)
+BCC_FOREST, BCC_SIZES, BCC_NUMBER, BCC_LOWHIGH, BCC_LINK, BCC_LABEL = range(6)  # enum GRX_BCC_PHASE_*: the kinds of phase_trace()
+
+
+def _u8p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_ubyte))
+
+
+class BccProblem(_Handle):
+    """BccProblem + BccEnactor behind the handle C ABI: the biconnected components (bcc[e] = the smallest canonical edge index of
+    e's block, int32), the bridges and the articulation points (uint8 masks), the 2-edge-connected components (tecc[v] = the
+    smallest id, int32) and the block-cut tree, of the CSR read as an undirected simple graph; per-edge arrays in the canonical
+    edge order ((a, b) with a < b, sorted)."""
+
+    _destroy = "grx_bcc_destroy"
+
+    _STATS = ("simple_edges", "trees", "levels", "entries_read", "kernel_launches", "readbacks")
+    _SUMMARY = ("blocks", "bridges", "articulation_points", "largest_block", "largest_block_id", "tecc_components", "largest_tecc",
+                "largest_tecc_root")
+
+    def __init__(self, instrument=False, device=0):
+        self._create("grx_bcc_create", int(instrument), device)
+        self.nodes = 0
+        self.entries = 0
+        self.simple_edges = 0
+
+    def _ready(self):
+        m = lib().grx_bcc_edges(self._h, None, None)
+        if m < 0:
+            _check(-m, "BccProblem::Edges")
+        self.simple_edges = int(m)
+
+    def init(self, nodes, row_offsets, col_indices):
+        ro, ci = _csr_arrays(row_offsets, col_indices, nodes)
+        self.nodes, self.entries = int(nodes), int(ci.shape[0])
+        _check(lib().grx_bcc_init(self._h, self.nodes, self.entries, _p(ro), _p(ci)), "BccProblem::Init")
+        self._ready()
+        return self
+
+    def init_device(self, nodes, edges, d_row_offsets, d_col_indices):
+        self.nodes, self.entries = int(nodes), int(edges)
+        _check(lib().grx_bcc_init_device(self._h, self.nodes, self.entries, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices)),
+               "BccProblem::Init(device)")
+        self._ready()
+        return self
+
+    def set_option(self, name, value):
+        """"schedule" (BCC_AUTO / BCC_ROUNDS / BCC_DEVICE_LOOP), "wave_min_row", "loop_max_list", "loop_max_entries"; returns the
+        library's code: 0 = set, 1 = unknown name (a value out of range raises)"""
+        rc = lib().grx_bcc_set_option(self._h, name.encode(), float(value))
+        if rc not in (0, 1):
+            _check(rc, "grx_bcc_set_option(%s)" % name)
+        return rc
+
+    def reset(self):
+        _check(lib().grx_bcc_reset(self._h), "BccProblem::Reset")
+
+    def enact(self, max_grid_size=0):
+        return self._timed(lib().grx_bcc_enact, "BccEnactor::Enact", max_grid_size)
+
+    def stats(self):
+        v = [C.c_longlong() for _ in self._STATS]
+        k, b = C.c_double(), C.c_double()
+        _check(lib().grx_bcc_stats(self._h, *([C.byref(x) for x in v] + [C.byref(k), C.byref(b)])), "grx_bcc_stats")
+        out = {name: x.value for name, x in zip(self._STATS, v)}
+        out["kernel_ms"], out["build_ms"] = k.value, b.value
+        return out
+
+    def phase_trace(self):
+        """the six phases of the last enact: (kind as int32: BCC_FOREST .. BCC_LABEL, vertices or edges touched as int64,
+        milliseconds as float64)"""
+        count = lib().grx_bcc_phase_trace(self._h, 0, None, None, None)
+        if count < 0:
+            _check(count, "grx_bcc_phase_trace")
+        kind = np.empty(max(count, 1), dtype=np.int32)
+        items = np.empty(max(count, 1), dtype=np.int64)
+        ms = np.empty(max(count, 1), dtype=np.float64)
+        lib().grx_bcc_phase_trace(self._h, count, _p(kind), items.ctypes.data_as(C.POINTER(C.c_longlong)),
+                                  ms.ctypes.data_as(C.POINTER(C.c_double)))
+        return kind[:count], items[:count], ms[:count]
+
+    def edges(self):
+        """the canonical edges (src, dst) as int32, src < dst, sorted by (src, dst)"""
+        src, dst = (np.empty(max(self.simple_edges, 1), dtype=np.int32) for _ in range(2))
+        m = lib().grx_bcc_edges(self._h, _p(src), _p(dst))
+        if m < 0:
+            _check(-m, "BccProblem::Edges")
+        return src[:m], dst[:m]
+
+    def extract(self):
+        """{"bcc": int32 per edge, "bridge": uint8 per edge, "articulation": uint8 per vertex, "tecc": int32 per vertex,
+        "block_size": int32 per edge}"""
+        m, n = max(self.simple_edges, 1), max(self.nodes, 1)
+        bcc, size, tecc = np.empty(m, np.int32), np.empty(m, np.int32), np.empty(n, np.int32)
+        bridge, art = np.empty(m, np.uint8), np.empty(n, np.uint8)
+        _check(lib().grx_bcc_extract(self._h, _p(bcc), _u8p(bridge), _u8p(art), _p(tecc), _p(size)), "BccProblem::Extract")
+        M, N = self.simple_edges, self.nodes
+        return {"bcc": bcc[:M], "bridge": bridge[:M], "articulation": art[:N], "tecc": tecc[:N], "block_size": size[:M]}
+
+    def summary(self):
+        """{"blocks", "bridges", "articulation_points", "largest_block", "largest_block_id", "tecc_components", "largest_tecc",
+        "largest_tecc_root"}"""
+        v = [C.c_int() if name in ("largest_block_id", "largest_tecc_root") else C.c_longlong() for name in self._SUMMARY]
+        _check(lib().grx_bcc_summary(self._h, *[C.byref(x) for x in v]), "BccProblem::Summary")
+        return {name: int(x.value) for name, x in zip(self._SUMMARY, v)}
+
+    def block_cut(self, max_edges=None):
+        """the block-cut tree sorted by (vertex, block): (articulation point as int32, bcc id as int32, the number of pairs);
+        max_edges caps what is copied (0: the count only).  The library builds the pairs once per enact: the second call copies"""
+        count = lib().grx_bcc_block_cut(self._h, 0, None, None)
+        if count < 0:
+            _check(-count, "BccProblem::BlockCut")
+        take = count if max_edges is None else min(count, int(max_edges))
+        v = np.empty(max(take, 1), dtype=np.int32)
+        b = np.empty(max(take, 1), dtype=np.int32)
+        if take > 0:
+            rc = lib().grx_bcc_block_cut(self._h, take, _p(v), _p(b))
+            if rc < 0:
+                _check(-rc, "BccProblem::BlockCut")
+        return v[:take], b[:take], count
+
+    def device_results(self):
+        """device pointers {"bcc", "tecc", "bridge", "articulation", "src", "dst", "parent", "level"}: int32 arrays but for the two
+        uint8 masks; per edge: bcc, bridge, src, dst; per vertex: the rest.  parent / level are the spanning forest (not unique)"""
+        names = ("bcc", "tecc", "bridge", "articulation", "src", "dst", "parent", "level")
+        p = [C.c_void_p() for _ in names]
+        _check(lib().grx_bcc_device_results(self._h, *[C.byref(x) for x in p]), "grx_bcc_device_results")
+        return {name: x.value for name, x in zip(names, p)}
+
+
+def gunrock_bcc(nodes, row_offsets, col_indices, device=0):
+    """One-shot biconnected components: returns (src, dst, bcc int32 per canonical edge: the smallest edge index of its block,
+    blocks)."""
+    return _one_shot(BccProblem(device=device).init(nodes, row_offsets, col_indices), BccProblem.reset, BccProblem.enact,
+                     lambda p: p.edges() + (p.extract()["bcc"], p.summary()["blocks"]))
+
+
+def gunrock_bridges(nodes, row_offsets, col_indices, device=0):
+    """One-shot bridges: returns (src, dst, mask uint8 per canonical edge, bridges)."""
+    return _one_shot(BccProblem(device=device).init(nodes, row_offsets, col_indices), BccProblem.reset, BccProblem.enact,
+                     lambda p: p.edges() + (p.extract()["bridge"], p.summary()["bridges"]))
+
+
+def gunrock_articulation_points(nodes, row_offsets, col_indices, device=0):
+    """One-shot articulation points: returns (mask uint8 per vertex, articulation points)."""
+    return _one_shot(BccProblem(device=device).init(nodes, row_offsets, col_indices), BccProblem.reset, BccProblem.enact,
+                     lambda p: (p.extract()["articulation"], p.summary()["articulation_points"]))
 
 
 MSBFS_AUTO, MSBFS_PUSH, MSBFS_PULL, MSBFS_ALTERNATE = 0, 1, 2, 3  # enum GRX_MSBFS_* (gunrock_mi355x.h): option "direction"

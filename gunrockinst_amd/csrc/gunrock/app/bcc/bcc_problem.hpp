@@ -1,0 +1,406 @@
+// app/bcc/bcc_problem.hpp -- device data for the biconnected components, articulation points, bridges and 2-edge-connected
+// components.
+//
+// The reference snapshot has no app/bcc; the shape is this tree's Problem (compare app/truss/truss_problem.hpp).  The input CSR is
+// read as MIS, TC, k-core and truss read it: the simple undirected graph G.  Init validates it and builds, with truss's build kernels
+// (truss_functor.hpp is included, not changed), the M canonical edges src[e] < dst[e] in (src, dst) order and the neighbour CSR with
+// the edge id on every entry.  The per-vertex and per-edge arrays are bcc_functor.hpp's.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <gunrock/app/bcc/bcc_functor.hpp>
+#include <gunrock/app/problem_base.hpp>
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wunused-function"  // (only the build kernels of truss and TC are used here)
+#include <gunrock/app/truss/truss_functor.hpp>
+#pragma clang diagnostic pop
+#include <gunrock/graphio/device_sort.hpp>
+
+namespace gunrock {
+namespace app {
+namespace bcc {
+
+struct Summary {
+    long long blocks = 0, bridges = 0, articulation_points = 0, largest_block = 0, tecc_components = 0, largest_tecc = 0;
+    int largest_block_id = -1, largest_tecc_root = -1;
+};
+
+template <bool _USE_DOUBLE_BUFFER>
+struct BccProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
+    typedef ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> Base;
+
+    struct DataSlice {
+        int *d_src = nullptr, *d_dst = nullptr;                   // the canonical edges
+        int *d_nro = nullptr, *d_nci = nullptr, *d_neid = nullptr;  // the neighbour CSR, rows ascending, and the edge of every entry
+        // per vertex
+        int *d_comp = nullptr, *d_parent = nullptr, *d_level = nullptr, *d_pedge = nullptr, *d_size = nullptr, *d_pre = nullptr, *d_low = nullptr,
+            *d_high = nullptr, *d_queue = nullptr, *d_uf = nullptr, *d_set = nullptr, *d_first = nullptr, *d_tecc = nullptr, *d_tsize = nullptr, *d_min_of = nullptr,
+            *d_cnt_of = nullptr;
+        int *d_bounds = nullptr;       // nodes + 2
+        unsigned *d_ents = nullptr;    // nodes + 2
+        // per edge
+        int *d_bcc = nullptr, *d_bsize = nullptr;
+        unsigned char *d_bridge = nullptr, *d_art = nullptr;
+        int *d_cut_vertex = nullptr, *d_cut_block = nullptr;  // the block-cut tree of the last Enact, built at the first request
+        unsigned *d_words = nullptr;
+        unsigned long long *d_counters = nullptr;  // [0] row entries walked, [1] articulation points, [2..4] and [5..7] SummaryKernel's
+        unsigned long long *d_clock = nullptr;     // PHASE_COUNT + 1 stamps
+        Front *d_front = nullptr;
+    };
+
+    DataSlice **data_slices = nullptr;
+    int malformed = 0;
+    long long simple_edges = 0;  // M
+    bool fresh = false;          // Reset has run and Enact has not
+    bool enacted = false;        // the arrays hold a result
+    double build_ms = 0;         // HIP-event time of the build of the edges and the neighbour CSR
+    Summary summary;             // of the last Enact
+    long long cut_pairs = -1;    // the pairs in d_cut_vertex / d_cut_block (-1: not built)
+
+    ~BccProblem() override
+    {
+        if (data_slices) {
+            DataSlice *ds = data_slices[0];
+            if (ds) {
+                void *bufs[] = {ds->d_src, ds->d_dst, ds->d_nro, ds->d_nci, ds->d_neid, ds->d_comp, ds->d_parent, ds->d_level, ds->d_pedge, ds->d_size,
+                                ds->d_pre, ds->d_low, ds->d_high, ds->d_queue, ds->d_uf, ds->d_set, ds->d_first, ds->d_tecc, ds->d_tsize, ds->d_min_of, ds->d_cnt_of,
+                                ds->d_bounds, ds->d_ents, ds->d_bcc, ds->d_bsize, ds->d_bridge, ds->d_art, ds->d_cut_vertex, ds->d_cut_block, ds->d_words, ds->d_counters, ds->d_clock,
+                                ds->d_front};
+                for (void *b : bufs)
+                    if (b) util::GRError(hipFree(b), "BccProblem hipFree failed", __FILE__, __LINE__);
+                delete ds;
+            }
+            delete[] data_slices;
+        }
+    }
+
+    static int Grid(long long work)
+    {
+        long long blocks = (work + 255) / 256;
+        if (blocks < 1) blocks = 1;
+        if (blocks > 2048) blocks = 2048;  // 256 CUs x 8 workgroups, grid-stride the rest
+        return static_cast<int>(blocks);
+    }
+
+    Ctx DeviceCtx(int wave_min_row) const
+    {
+        const DataSlice *ds = data_slices[0];
+        Ctx c;
+        c.ro = ds->d_nro;
+        c.ci = ds->d_nci;
+        c.eid = ds->d_neid;
+        c.parent = ds->d_parent;
+        c.level = ds->d_level;
+        c.pedge = ds->d_pedge;
+        c.size = ds->d_size;
+        c.pre = ds->d_pre;
+        c.low = ds->d_low;
+        c.high = ds->d_high;
+        c.queue = ds->d_queue;
+        c.bounds = ds->d_bounds;
+        c.ents = ds->d_ents;
+        c.words = ds->d_words;
+        c.reads = ds->d_counters;
+        c.nodes = this->nodes;
+        c.wave_min_row = wave_min_row;
+        return c;
+    }
+
+    Tree DeviceTree() const
+    {
+        const DataSlice *ds = data_slices[0];
+        return Tree{ds->d_parent, ds->d_pedge, ds->d_size, ds->d_pre, ds->d_low, ds->d_high};
+    }
+
+    hipError_t Build()
+    {
+        hipError_t retval = hipSuccess;
+        DataSlice *ds = data_slices[0];
+        GraphSlice<int, int, int> *gs = this->graph_slices[0];
+        hipStream_t stream = gs->stream;
+        const long long n = this->nodes, m = this->edges;
+        const size_t n1 = static_cast<size_t>(n > 0 ? n : 1);
+        GR_CHECK(hipMalloc(&ds->d_words, sizeof(unsigned) * W_COUNT), "BccProblem hipMalloc failed");
+        GR_CHECK(hipMalloc(&ds->d_counters, sizeof(unsigned long long) * 8), "BccProblem hipMalloc failed");
+        GR_CHECK(hipMalloc(&ds->d_clock, sizeof(unsigned long long) * (PHASE_COUNT + 1)), "BccProblem hipMalloc failed");
+        GR_CHECK(hipMalloc(&ds->d_front, sizeof(Front)), "BccProblem hipMalloc failed");
+
+        // the CSR must be one: the build indexes with what it reads
+        int bad = 0;
+        GR_CHECK(hipMemsetAsync(ds->d_words, 0, sizeof(unsigned) * W_COUNT, stream), "BccProblem memset failed");
+        hipLaunchKernelGGL(tc::ValidateCsrKernel, dim3(Grid((n > m ? n : m) + 1)), dim3(256), 0, stream, gs->d_row_offsets, gs->d_column_indices,
+                           n, m, reinterpret_cast<int *>(ds->d_words));
+        GR_CHECK(hipGetLastError(), "ValidateCsrKernel launch failed");
+        GR_CHECK(hipMemcpyAsync(&bad, ds->d_words, sizeof(int), hipMemcpyDeviceToHost, stream), "BccProblem read-back failed");
+        GR_CHECK(hipStreamSynchronize(stream), "BccProblem read-back sync failed");
+        if (bad) {
+            malformed = 1;
+            return hipErrorInvalidValue;
+        }
+
+        // (the events and the build's scratch go on every path out: run() may return early, release() follows it)
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        unsigned *d_keep = nullptr, *d_deg = nullptr;
+        unsigned long long *d_pos = nullptr, *d_sums = nullptr, *d_ckeys = nullptr;
+        int *d_up = nullptr, *d_low = nullptr;
+        long long M = 0;
+        auto release = [&]() {
+            for (int i = 0; i < 2; ++i)
+                if (ev[i]) hipEventDestroy(ev[i]);
+            void *scratch[] = {d_keep, d_pos, d_sums, d_ckeys, d_up, d_low, d_deg};
+            for (void *b : scratch)
+                if (b) util::GRError(hipFree(b), "BccProblem hipFree failed", __FILE__, __LINE__);
+        };
+        auto run = [&]() -> hipError_t {
+            hipError_t retval = hipSuccess;
+            for (int i = 0; i < 2; ++i) GR_CHECK(hipEventCreate(&ev[i]), "BccProblem hipEventCreate failed");
+            GR_CHECK(hipEventRecord(ev[0], stream), "BccProblem hipEventRecord failed");
+
+            GR_CHECK(hipMalloc(&ds->d_nro, sizeof(int) * (n1 + 1)), "BccProblem hipMalloc d_nro failed");
+            GR_CHECK(hipMemsetAsync(ds->d_nro, 0, sizeof(int) * (n1 + 1), stream), "BccProblem memset failed");
+
+            // (the sequence of TrussProblem::Build, steps 1 to 3, with its kernels)
+            int col_bits = 1;
+            while ((1ll << col_bits) < n) ++col_bits;
+            const int key_bits = 2 * col_bits;  // <= 62
+            const unsigned long long sentinel = (1ull << key_bits) - 1ull;  // min = max = 2^cb - 1: never an edge
+            graphio::DeviceKeySort edge_sort;
+            if (m > 0) {
+                const long long scan_words = m > n + 1 ? m : n + 1;
+                GR_CHECK(hipMalloc(&d_keep, sizeof(unsigned) * static_cast<size_t>(m)), "BccProblem hipMalloc failed");
+                GR_CHECK(hipMalloc(&d_pos, sizeof(unsigned long long) * static_cast<size_t>(m)), "BccProblem hipMalloc failed");
+                GR_CHECK(hipMalloc(&d_sums, sizeof(unsigned long long) * static_cast<size_t>(graphio::ScanScratchWords(scan_words))),
+                         "BccProblem hipMalloc failed");
+                GR_CHECK(edge_sort.Reserve(m), "BccProblem sort scratch failed");
+                hipLaunchKernelGGL(tc::EdgeKeysKernel, dim3(Grid(m)), dim3(256), 0, stream, gs->d_row_offsets, gs->d_column_indices, static_cast<int>(n),
+                                   m, col_bits, sentinel, edge_sort.Keys());
+                GR_CHECK(hipGetLastError(), "EdgeKeysKernel launch failed");
+                unsigned long long *d_sorted = nullptr;
+                GR_CHECK(edge_sort.Sort(m, key_bits, stream, &d_sorted), "BccProblem edge sort failed");
+                hipLaunchKernelGGL(graphio::FlagKernel, dim3(Grid(m)), dim3(256), 0, stream, d_sorted, m, sentinel, d_keep);
+                GR_CHECK(hipGetLastError(), "FlagKernel launch failed");
+                GR_CHECK(graphio::DeviceExclusiveScan<unsigned long long>(d_keep, d_pos, m, d_sums, stream), "BccProblem flag scan failed");
+                unsigned long long last_pos = 0;
+                unsigned last_keep = 0;
+                GR_CHECK(hipMemcpyAsync(&last_pos, d_pos + (m - 1), sizeof(last_pos), hipMemcpyDeviceToHost, stream), "BccProblem read-back failed");
+                GR_CHECK(hipMemcpyAsync(&last_keep, d_keep + (m - 1), sizeof(last_keep), hipMemcpyDeviceToHost, stream), "BccProblem read-back failed");
+                GR_CHECK(hipStreamSynchronize(stream), "BccProblem read-back sync failed");
+                M = static_cast<long long>(last_pos) + last_keep;
+                if (2 * M > 0x7FFFFFFFll) return hipErrorInvalidValue;  // every offset of the 2M entries is an int
+                if (M > 0) {
+                    const size_t ms = static_cast<size_t>(M);
+                    GR_CHECK(hipMalloc(&d_ckeys, sizeof(unsigned long long) * ms), "BccProblem hipMalloc failed");
+                    GR_CHECK(hipMalloc(&ds->d_src, sizeof(int) * ms), "BccProblem hipMalloc d_src failed");
+                    GR_CHECK(hipMalloc(&ds->d_dst, sizeof(int) * ms), "BccProblem hipMalloc d_dst failed");
+                    GR_CHECK(hipMalloc(&ds->d_nci, sizeof(int) * 2 * ms), "BccProblem hipMalloc d_nci failed");
+                    GR_CHECK(hipMalloc(&ds->d_neid, sizeof(int) * 2 * ms), "BccProblem hipMalloc d_neid failed");
+                    GR_CHECK(hipMalloc(&d_up, sizeof(int) * (n1 + 1)), "BccProblem hipMalloc failed");
+                    GR_CHECK(hipMalloc(&d_low, sizeof(int) * (n1 + 1)), "BccProblem hipMalloc failed");
+                    GR_CHECK(hipMalloc(&d_deg, sizeof(unsigned) * (n1 + 1)), "BccProblem hipMalloc failed");
+                    hipLaunchKernelGGL(truss::CanonicalKernel, dim3(Grid(m)), dim3(256), 0, stream, d_sorted, d_keep, d_pos, m, col_bits, d_ckeys,
+                                       ds->d_src, ds->d_dst);
+                    GR_CHECK(hipGetLastError(), "CanonicalKernel launch failed");
+                    hipLaunchKernelGGL(truss::SwapKeysKernel, dim3(Grid(M)), dim3(256), 0, stream, d_ckeys, M, col_bits, edge_sort.Keys());
+                    GR_CHECK(hipGetLastError(), "SwapKeysKernel launch failed");
+                    unsigned long long *d_skeys = nullptr;
+                    GR_CHECK(edge_sort.Sort(M, key_bits, stream, &d_skeys), "BccProblem edge sort failed");
+                    hipLaunchKernelGGL(truss::RowStartsKernel, dim3(Grid(n + 1)), dim3(256), 0, stream, d_ckeys, d_skeys, M, n, col_bits, d_up, d_low);
+                    GR_CHECK(hipGetLastError(), "RowStartsKernel launch failed");
+                    hipLaunchKernelGGL(truss::DegreesKernel, dim3(Grid(n + 1)), dim3(256), 0, stream, d_up, d_low, n, d_deg);
+                    GR_CHECK(hipGetLastError(), "DegreesKernel launch failed");
+                    GR_CHECK(graphio::DeviceExclusiveScan<int>(d_deg, ds->d_nro, n + 1, d_sums, stream), "BccProblem offset scan failed");
+                    hipLaunchKernelGGL(truss::FillRowsKernel, dim3(Grid(M)), dim3(256), 0, stream, d_ckeys, d_skeys, M, col_bits, d_up, d_low, ds->d_nro,
+                                       ds->d_nci, ds->d_neid);
+                    GR_CHECK(hipGetLastError(), "FillRowsKernel launch failed");
+                }
+            }
+            simple_edges = M;
+            GR_CHECK(hipEventRecord(ev[1], stream), "BccProblem hipEventRecord failed");
+            GR_CHECK(hipStreamSynchronize(stream), "BccProblem build sync failed");
+            float ms = 0;
+            GR_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]), "BccProblem hipEventElapsedTime failed");
+            build_ms = ms;
+            return retval;
+        };
+        retval = run();
+        release();
+        if (retval) return retval;
+
+        const size_t m1 = static_cast<size_t>(M > 0 ? M : 1);
+        int **vertex_arrays[] = {&ds->d_comp, &ds->d_parent, &ds->d_level, &ds->d_pedge, &ds->d_size, &ds->d_pre, &ds->d_low, &ds->d_high, &ds->d_queue,
+                                 &ds->d_uf, &ds->d_set, &ds->d_first, &ds->d_tecc, &ds->d_tsize, &ds->d_min_of, &ds->d_cnt_of};
+        for (int **a : vertex_arrays) GR_CHECK(hipMalloc(a, sizeof(int) * n1), "BccProblem hipMalloc failed");
+        GR_CHECK(hipMalloc(&ds->d_bounds, sizeof(int) * (n1 + 2)), "BccProblem hipMalloc failed");
+        GR_CHECK(hipMalloc(&ds->d_ents, sizeof(unsigned) * (n1 + 2)), "BccProblem hipMalloc failed");
+        GR_CHECK(hipMalloc(&ds->d_bcc, sizeof(int) * m1), "BccProblem hipMalloc failed");
+        GR_CHECK(hipMalloc(&ds->d_bsize, sizeof(int) * m1), "BccProblem hipMalloc failed");
+        GR_CHECK(hipMalloc(&ds->d_bridge, m1), "BccProblem hipMalloc failed");
+        GR_CHECK(hipMalloc(&ds->d_art, n1), "BccProblem hipMalloc failed");
+        return retval;
+    }
+
+    // One Init per object (grx_bcc_init refuses a second one)
+    hipError_t Init(bool stream_from_host, const Csr<int, int, int> &graph, int num_gpus = 1)
+    {
+        hipError_t retval = hipSuccess;
+        if ((retval = Base::Init(stream_from_host, graph, num_gpus, false))) return retval;
+        data_slices = new DataSlice *[1];
+        data_slices[0] = new DataSlice();
+        return Build();
+    }
+
+    hipError_t InitFromDevice(int nodes, int edges, int *d_row_offsets, int *d_column_indices)
+    {
+        hipError_t retval = hipSuccess;
+        if ((retval = Base::InitFromDevice(nodes, edges, d_row_offsets, d_column_indices))) return retval;
+        data_slices = new DataSlice *[1];
+        data_slices[0] = new DataSlice();
+        return Build();
+    }
+
+    // the words, the counters, the two masks and the level table at 0 (everything else is written before it is read)
+    hipError_t Reset(FrontierType /*frontier_type*/ = VERTEX_FRONTIERS)
+    {
+        hipError_t retval = hipSuccess;
+        DataSlice *ds = data_slices[0];
+        hipStream_t stream = this->graph_slices[0]->stream;
+        const size_t n = static_cast<size_t>(this->nodes), M = static_cast<size_t>(simple_edges);
+        GR_CHECK(hipMemsetAsync(ds->d_words, 0, sizeof(unsigned) * W_COUNT, stream), "BccProblem memset failed");
+        GR_CHECK(hipMemsetAsync(ds->d_counters, 0, sizeof(unsigned long long) * 8, stream), "BccProblem memset failed");
+        GR_CHECK(hipMemsetAsync(ds->d_clock, 0, sizeof(unsigned long long) * (PHASE_COUNT + 1), stream), "BccProblem memset failed");
+        GR_CHECK(hipMemsetAsync(ds->d_bounds, 0, sizeof(int) * (n + 2), stream), "BccProblem memset failed");
+        GR_CHECK(hipMemsetAsync(ds->d_ents, 0, sizeof(unsigned) * (n + 2), stream), "BccProblem memset failed");
+        GR_CHECK(hipMemsetAsync(ds->d_art, 0, n, stream), "BccProblem memset failed");
+        if (M) GR_CHECK(hipMemsetAsync(ds->d_bridge, 0, M, stream), "BccProblem memset failed");
+        GR_CHECK(hipStreamSynchronize(stream), "BccProblem Reset sync failed");
+        fresh = true;
+        enacted = false;
+        summary = Summary();
+        DropBlockCut();
+        return retval;
+    }
+
+    template <typename T>
+    hipError_t Read(T *h_out, const T *d_in, size_t count)
+    {
+        hipError_t retval = hipSuccess;
+        hipStream_t stream = this->graph_slices[0]->stream;
+        if (h_out && count) {
+            GR_CHECK(hipMemcpyAsync(h_out, d_in, sizeof(T) * count, hipMemcpyDeviceToHost, stream), "BccProblem read failed");
+            GR_CHECK(hipStreamSynchronize(stream), "BccProblem read sync failed");
+        }
+        return retval;
+    }
+
+    hipError_t Edges(int *h_src, int *h_dst)
+    {
+        hipError_t retval = hipSuccess;
+        DataSlice *ds = data_slices[0];
+        const size_t M = static_cast<size_t>(simple_edges);
+        if ((retval = Read(h_src, ds->d_src, M))) return retval;
+        return Read(h_dst, ds->d_dst, M);
+    }
+
+    // every pointer may be NULL
+    hipError_t Extract(int *h_bcc, unsigned char *h_bridge, unsigned char *h_art, int *h_tecc, int *h_block_size)
+    {
+        hipError_t retval = hipSuccess;
+        DataSlice *ds = data_slices[0];
+        const size_t n = static_cast<size_t>(this->nodes), M = static_cast<size_t>(simple_edges);
+        if ((retval = Read(h_bcc, ds->d_bcc, M))) return retval;
+        if ((retval = Read(h_bridge, ds->d_bridge, M))) return retval;
+        if ((retval = Read(h_art, ds->d_art, n))) return retval;
+        if ((retval = Read(h_tecc, ds->d_tecc, n))) return retval;
+        return Read(h_block_size, ds->d_bsize, M);
+    }
+
+    void DropBlockCut()
+    {
+        DataSlice *ds = data_slices[0];
+        if (ds->d_cut_vertex) util::GRError(hipFree(ds->d_cut_vertex), "BccProblem hipFree failed", __FILE__, __LINE__);
+        if (ds->d_cut_block) util::GRError(hipFree(ds->d_cut_block), "BccProblem hipFree failed", __FILE__, __LINE__);
+        ds->d_cut_vertex = ds->d_cut_block = nullptr;
+        cut_pairs = -1;
+    }
+
+    // the distinct pairs (v, block) over the articulation points v and the blocks at them, sorted by (v, block), into d_cut_vertex /
+    // d_cut_block (SccProblem::Condensation's sequence).  Kept until the next Reset: asking for the count and then for the pairs sorts
+    // the 2M keys once.
+    hipError_t BuildBlockCut()
+    {
+        hipError_t retval = hipSuccess;
+        DataSlice *ds = data_slices[0];
+        hipStream_t stream = this->graph_slices[0]->stream;
+        const long long n = this->nodes, keys = 2 * simple_edges;
+        if (keys == 0 || summary.articulation_points == 0) {
+            cut_pairs = 0;
+            return retval;
+        }
+        int col_bits = 1, edge_bits = 1;
+        while ((1ll << col_bits) < n + 1) ++col_bits;  // (+ 1: the sentinel's vertex part is no vertex)
+        while ((1ll << edge_bits) < simple_edges) ++edge_bits;
+        const int key_bits = col_bits + edge_bits;  // <= 63
+        const unsigned long long sentinel = (1ull << key_bits) - 1ull;
+        graphio::DeviceKeySort sort;
+        unsigned *d_keep = nullptr;
+        unsigned long long *d_pos = nullptr, *d_sums = nullptr;
+        auto release = [&]() {
+            void *bufs[] = {d_keep, d_pos, d_sums};
+            for (void *b : bufs)
+                if (b) util::GRError(hipFree(b), "BccProblem hipFree failed", __FILE__, __LINE__);
+        };
+        auto run = [&]() -> hipError_t {
+            hipError_t retval = hipSuccess;
+            GR_CHECK(sort.Reserve(keys), "BccProblem sort scratch failed");
+            GR_CHECK(hipMalloc(&d_keep, sizeof(unsigned) * static_cast<size_t>(keys)), "BccProblem hipMalloc failed");
+            GR_CHECK(hipMalloc(&d_pos, sizeof(unsigned long long) * static_cast<size_t>(keys)), "BccProblem hipMalloc failed");
+            GR_CHECK(hipMalloc(&d_sums, sizeof(unsigned long long) * static_cast<size_t>(graphio::ScanScratchWords(keys))), "BccProblem hipMalloc failed");
+            hipLaunchKernelGGL(BlockCutKeysKernel, dim3(Grid(simple_edges)), dim3(256), 0, stream, ds->d_src, ds->d_dst, ds->d_bcc, ds->d_art, simple_edges,
+                               edge_bits, sentinel, sort.Keys());
+            GR_CHECK(hipGetLastError(), "BlockCutKeysKernel launch failed");
+            unsigned long long *d_sorted = nullptr;
+            GR_CHECK(sort.Sort(keys, key_bits, stream, &d_sorted), "BccProblem key sort failed");
+            hipLaunchKernelGGL(graphio::FlagKernel, dim3(Grid(keys)), dim3(256), 0, stream, d_sorted, keys, sentinel, d_keep);
+            GR_CHECK(hipGetLastError(), "FlagKernel launch failed");
+            GR_CHECK(graphio::DeviceExclusiveScan<unsigned long long>(d_keep, d_pos, keys, d_sums, stream), "BccProblem flag scan failed");
+            const long long scan_tiles = (keys + graphio::kScanTile - 1) / graphio::kScanTile;  // (the total is behind the tile offsets)
+            unsigned long long total = 0;
+            GR_CHECK(hipMemcpyAsync(&total, d_sums + scan_tiles, sizeof(total), hipMemcpyDeviceToHost, stream), "BccProblem read total failed");
+            GR_CHECK(hipStreamSynchronize(stream), "BccProblem BlockCut sync failed");
+            const long long pairs = static_cast<long long>(total);
+            if (pairs > 0) {
+                GR_CHECK(hipMalloc(&ds->d_cut_vertex, sizeof(int) * static_cast<size_t>(pairs)), "BccProblem hipMalloc failed");
+                GR_CHECK(hipMalloc(&ds->d_cut_block, sizeof(int) * static_cast<size_t>(pairs)), "BccProblem hipMalloc failed");
+                hipLaunchKernelGGL(scc::CondensationEmitKernel, dim3(Grid(keys)), dim3(256), 0, stream, d_sorted, d_keep, d_pos, keys, edge_bits, pairs,
+                                   ds->d_cut_vertex, ds->d_cut_block);
+                GR_CHECK(hipGetLastError(), "CondensationEmitKernel launch failed");
+                GR_CHECK(hipStreamSynchronize(stream), "BccProblem BlockCut sync failed");
+            }
+            cut_pairs = pairs;
+            return retval;
+        };
+        retval = run();
+        release();
+        if (retval) DropBlockCut();
+        return retval;
+    }
+
+    // the first max_edges pairs go to h_vertex / h_block, *count is how many there are
+    hipError_t BlockCut(long long max_edges, int *h_vertex, int *h_block, long long *count)
+    {
+        hipError_t retval = hipSuccess;
+        DataSlice *ds = data_slices[0];
+        *count = 0;
+        if (cut_pairs < 0 && (retval = BuildBlockCut())) return retval;
+        *count = cut_pairs;
+        const long long take = cut_pairs < max_edges ? cut_pairs : max_edges;
+        if (take < 1 || !h_vertex || !h_block) return retval;
+        if ((retval = Read(h_vertex, ds->d_cut_vertex, static_cast<size_t>(take)))) return retval;
+        return Read(h_block, ds->d_cut_block, static_cast<size_t>(take));
+    }
+};
+
+}  // namespace bcc
+}  // namespace app
+}  // namespace gunrock

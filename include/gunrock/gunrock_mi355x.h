@@ -653,6 +653,91 @@ int grx_msbfs_device_results(grx_msbfs *p, int **d_depth, long long **d_reached,
 void grx_msbfs_destroy(grx_msbfs *p);
 
 /* ------------------------------------------------------------------------------------------------
+ * BCC: BccProblem + BccEnactor: biconnected components (blocks), articulation points, bridges and 2-edge-connected components
+ * (Tarjan and Vishkin, SIAM J. Comput. 1985, on a breadth-first forest; the reference snapshot has no counterpart, later Gunrock
+ * releases do).  The CSR is read as grx_mis_*, grx_tc_*, grx_kcore_* and grx_truss_* read it: the simple undirected graph G (entries
+ * symmetrised, duplicates and self-loops dropped, rows may be unsorted, a directed input is read undirected).  Parallel entries
+ * collapse to one edge, so a doubled edge can still be a bridge.  The M canonical edges are (a, b), a < b, sorted by (a, b); edge
+ * index e is the position in that list, as in grx_truss_edges.  Every result is an integer with one value:
+ *   bcc[e]           the smallest canonical edge index in the block that holds edge e (int32, M entries)
+ *   block_size[e]    the number of edges in the block of e (int32)
+ *   bridge[e]        1 iff the block of e is that edge alone (uint8, M entries)
+ *   articulation[v]  1 iff the edges at v carry at least two block ids (uint8, `nodes` entries)
+ *   tecc[v]          the smallest vertex id in the 2-edge-connected component of v: its component in G minus the bridges (int32,
+ *                    `nodes` entries; a vertex without a neighbour is its own)
+ *   block-cut tree   the distinct pairs (v, bcc id) over the articulation points v and the blocks at them, sorted by (v, id)
+ * An order of the block-cut tree (a root, a traversal) is not offered: it is not unique.
+ * Init builds the neighbour CSR with edge ids; Enact finds the component minima by hook-and-jump, searches breadth-first from all of
+ * them at once, computes subtree sizes, preorder numbers and low / high level by level, joins tree edges in a union-find, and labels
+ * edges and vertices from the sets, in wide launches or in a loop on the device.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct grx_bcc grx_bcc;
+enum { GRX_BCC_AUTO = 0, GRX_BCC_ROUNDS = 1, GRX_BCC_DEVICE_LOOP = 2 };
+enum {
+    GRX_BCC_PHASE_FOREST = 0,
+    GRX_BCC_PHASE_SIZES = 1,
+    GRX_BCC_PHASE_NUMBER = 2,
+    GRX_BCC_PHASE_LOWHIGH = 3,
+    GRX_BCC_PHASE_LINK = 4,
+    GRX_BCC_PHASE_LABEL = 5
+}; /* the kinds of grx_bcc_phase_trace */
+
+/* (no counterpart in the reference snapshot: this call and the ones below are shaped like grx_scc_* and grx_truss_*) */
+int grx_bcc_create(grx_bcc **out, int instrument, int device);
+/* BccProblem::Init: validates the CSR and builds the canonical edges and the neighbour CSR on the device (no reference counterpart).
+ * -1: nodes < 1, edges < 0 or a NULL array; -2: not a CSR of `nodes` vertices, as grx_kcore_init; -3: the handle has been given a
+ * graph before (accepted or rejected) */
+int grx_bcc_init(grx_bcc *p, int nodes, int edges, const int *row_offsets, const int *col_indices);
+/* the same for a CSR already in HBM (borrowed, not freed; no reference counterpart) */
+int grx_bcc_init_device(grx_bcc *p, int nodes, int edges, int *d_row_offsets, int *d_col_indices);
+/* named options, for the next Enact; 0: set, 1: unknown name, -1: a value out of range.  None changes a result (no reference
+ * counterpart).
+ *   "schedule"          GRX_BCC_AUTO (default): a level of one of the four level chains (search, sizes, numbering, low / high) is a
+ *                       launch of its own while it is wide, and a stretch of narrow levels runs in a loop on the device, one launch
+ *                       for up to 4096 levels; GRX_BCC_ROUNDS: every level is a launch (the plain form, for comparison);
+ *                       GRX_BCC_DEVICE_LOOP: every level runs in the device loop
+ *   "wave_min_row"      >= 1: rows of at least this many entries are walked by the whole wave, shorter ones by a lane (default 16,
+ *                       taken over from grx_scc_*, not tuned).  A large value is a performance cliff, not an error: a hub's row is
+ *                       then walked by one lane while the other 63 of its wave wait
+ *   "loop_max_list"     under AUTO the device loop takes a level of at most this many vertices (default 32768, not tuned)
+ *   "loop_max_entries"  ... whose rows hold at most this many entries (default 8192, not tuned) */
+int grx_bcc_set_option(grx_bcc *p, const char *name, double value);
+/* BccProblem::Reset (no reference counterpart) */
+int grx_bcc_reset(grx_bcc *p);
+/* BccEnactor::Enact(problem, max_grid_size), HIP-event timed (no reference counterpart).  An Enact that does not follow a Reset
+ * makes its own */
+int grx_bcc_enact(grx_bcc *p, int max_grid_size, float *elapsed_ms);
+/* the simple edges M of the graph and, of the last Enact (no reference counterpart): the trees of the forest (components with an
+ * edge), the levels of the search, row entries walked, kernel launches, host read-backs and -- when instrumented -- the summed
+ * kernel time; build_ms: the HIP-event time of Init's build.  The seven one-thread launches that stamp the phase trace and the
+ * memsets of an Enact are in neither kernel_launches nor kernel_ms */
+int grx_bcc_stats(grx_bcc *p, long long *simple_edges, long long *trees, long long *levels, long long *entries_read,
+                  long long *kernel_launches, long long *readbacks, double *kernel_ms, double *build_ms);
+/* the six phases of the last Enact in order, at most max_phases of them (no reference counterpart): the kind (GRX_BCC_PHASE_*), the
+ * vertices (forest, sizes, numbering, low / high), edges (link) or edges and vertices (label) it touched, and the time to the next
+ * phase's start by the device's constant-rate counter; returns the number of phases (0 before the first Enact) */
+int grx_bcc_phase_trace(grx_bcc *p, int max_phases, int *kind, long long *items, double *ms);
+/* the canonical edges (either pointer may be NULL); returns M or a negated hipError_t; valid after init (no reference counterpart) */
+int grx_bcc_edges(grx_bcc *p, int *h_src, int *h_dst);
+/* the results of the last Enact; every pointer may be NULL.  Before an Enact: hipErrorNotReady (no reference counterpart) */
+int grx_bcc_extract(grx_bcc *p, int *h_bcc, unsigned char *h_bridge, unsigned char *h_articulation, int *h_tecc, int *h_block_size);
+/* any pointer may be NULL: the blocks, the bridges, the articulation points, the edges of the largest block and its id (ties go to
+ * the smaller id; -1 without an edge), the 2-edge-connected components (single vertices counted), the vertices of the largest one
+ * and its root (ties go to the smaller root).  Before an Enact: hipErrorNotReady (no reference counterpart) */
+int grx_bcc_summary(grx_bcc *p, long long *blocks, long long *bridges, long long *articulation_points, long long *largest_block,
+                    int *largest_block_id, long long *tecc_components, long long *largest_tecc, int *largest_tecc_root);
+/* the first max_edges pairs of the block-cut tree into h_vertex / h_block (either NULL, or max_edges 0: none is copied); returns the
+ * number of pairs, which must fit an int, or a negated hipError_t.  The pairs are built at the first call after an Enact and kept
+ * on the device until the next Reset, so a count call followed by a fetch sorts once (no reference counterpart) */
+int grx_bcc_block_cut(grx_bcc *p, int max_edges, int *h_vertex, int *h_block);
+/* device arrays of the handle (no reference counterpart): bcc (M int32), tecc (`nodes` int32), the two masks (M and `nodes` uint8),
+ * the canonical edges (M int32 each) and the spanning forest: parent (-1 at a root and at a vertex without a neighbour) and level
+ * (`nodes` int32 each).  The forest is not unique: which neighbour of the level above is the parent depends on the run */
+int grx_bcc_device_results(grx_bcc *p, int **d_bcc, int **d_tecc, unsigned char **d_bridge, unsigned char **d_articulation, int **d_src,
+                           int **d_dst, int **d_parent, int **d_level);
+void grx_bcc_destroy(grx_bcc *p);
+
+/* ------------------------------------------------------------------------------------------------
  * SSSP: SSSPProblem + SSSPEnactor (reference gunrock/app/sssp/sssp_problem.cuh:35-387, sssp_enactor.cuh:36-563)
  * ---------------------------------------------------------------------------------------------- */
 typedef struct grx_sssp grx_sssp;
