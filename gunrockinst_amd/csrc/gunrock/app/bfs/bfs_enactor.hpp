@@ -227,6 +227,8 @@ class BFSEnactor : public EnactorBase {
             bargs.d_inv_column_indices = ds->d_inv_column_indices;
             bargs.d_inv_heads = ds->d_inv_heads;
             oprtr::advance::BitmapLookup<VertexId> lookup{ds->d_frontier_mask[in_mask]};
+            // the dense sweeps answer probes of ids below hub_slice from an LDS copy of the bitmap's first words (bottom_up.hpp HubSliceLookup)
+            oprtr::advance::HubSliceLookup<VertexId> slice_lookup{ds->d_frontier_mask[in_mask], problem->HubSlice()};
             bargs.d_frontier_out = reinterpret_cast<unsigned long long *>(ds->d_frontier_mask[out_mask]);
             bargs.d_visited = reinterpret_cast<unsigned long long *>(ds->d_visited_mask);
             bargs.d_tail_out = work_progress.d_tail + ((iteration + 1) & 3);
@@ -273,29 +275,33 @@ class BFSEnactor : public EnactorBase {
                                    dim3(static_cast<unsigned>(sgrid)), dim3(BU_THREADS), 0, stream, bargs, *ds, lookup);
                 return util::GRError("BottomUpSparseKernel launch failed", __FILE__, __LINE__);
             }
-            if (heads_only) {  // the lean instantiation (no row walks: fewer registers, more waves)
-                typedef oprtr::advance::BitmapLookup<VertexId> L;
-                const long long hcap = max_grid_size > 0 ? max_grid_size : util::ResidentGrid(oprtr::advance::BottomUpHeadsKernel<BU_THREADS, BFSProblem, L>, BU_THREADS);
-                if (grid > hcap) grid = hcap;
+            // With a slice the dense sweeps take HubSliceLookup; without one (hub_slice = 0, or a search in the caller's numbering) they
+            // take BitmapLookup, the instantiation without the LDS read and the fill.
+            auto launch_dense = [&](auto probe) -> hipError_t {
+                typedef decltype(probe) L;
+                if (heads_only) {  // the lean instantiation (no row walks: fewer registers, more waves)
+                    const long long hcap = max_grid_size > 0 ? max_grid_size : util::ResidentGrid(oprtr::advance::BottomUpHeadsKernel<BU_THREADS, BFSProblem, L>, BU_THREADS);
+                    if (grid > hcap) grid = hcap;
+                    if (grid < 1) grid = 1;
+                    hipLaunchKernelGGL((oprtr::advance::BottomUpHeadsKernel<BU_THREADS, BFSProblem, L>), dim3(static_cast<unsigned>(grid)), dim3(BU_THREADS), 0,
+                                       stream, bargs, *ds, probe);
+                    return util::GRError("BottomUpHeadsKernel launch failed", __FILE__, __LINE__);
+                }
+                const bool walk_queue = problem->walk_queue != 0;  // (two instantiations of the dense body: bottom_up.hpp)
+                const long long cap = max_grid_size > 0 ? max_grid_size
+                    : walk_queue ? util::ResidentGrid(oprtr::advance::BottomUpKernel<BU_THREADS, 8, 32, BFSProblem, L, true>, BU_THREADS)
+                                 : util::ResidentGrid(oprtr::advance::BottomUpKernel<BU_THREADS, 8, 32, BFSProblem, L, false>, BU_THREADS);
+                if (grid > cap) grid = cap;
                 if (grid < 1) grid = 1;
-                hipLaunchKernelGGL((oprtr::advance::BottomUpHeadsKernel<BU_THREADS, BFSProblem, L>), dim3(static_cast<unsigned>(grid)), dim3(BU_THREADS), 0,
-                                   stream, bargs, *ds, lookup);
-                return util::GRError("BottomUpHeadsKernel launch failed", __FILE__, __LINE__);
-            }
-            typedef oprtr::advance::BitmapLookup<VertexId> L;
-            const bool walk_queue = problem->walk_queue != 0;  // (two instantiations of the dense body: bottom_up.hpp)
-            const long long cap = max_grid_size > 0 ? max_grid_size
-                : walk_queue ? util::ResidentGrid(oprtr::advance::BottomUpKernel<BU_THREADS, 8, 32, BFSProblem, L, true>, BU_THREADS)
-                             : util::ResidentGrid(oprtr::advance::BottomUpKernel<BU_THREADS, 8, 32, BFSProblem, L, false>, BU_THREADS);
-            if (grid > cap) grid = cap;
-            if (grid < 1) grid = 1;
-            if (walk_queue)
-                hipLaunchKernelGGL((oprtr::advance::BottomUpKernel<BU_THREADS, 8, 32, BFSProblem, L, true>),
-                                   dim3(static_cast<unsigned>(grid)), dim3(BU_THREADS), 0, stream, bargs, *ds, lookup);
-            else
-                hipLaunchKernelGGL((oprtr::advance::BottomUpKernel<BU_THREADS, 8, 32, BFSProblem, L, false>),
-                                   dim3(static_cast<unsigned>(grid)), dim3(BU_THREADS), 0, stream, bargs, *ds, lookup);
-            return util::GRError("BottomUpKernel launch failed", __FILE__, __LINE__);
+                if (walk_queue)
+                    hipLaunchKernelGGL((oprtr::advance::BottomUpKernel<BU_THREADS, 8, 32, BFSProblem, L, true>),
+                                       dim3(static_cast<unsigned>(grid)), dim3(BU_THREADS), 0, stream, bargs, *ds, probe);
+                else
+                    hipLaunchKernelGGL((oprtr::advance::BottomUpKernel<BU_THREADS, 8, 32, BFSProblem, L, false>),
+                                       dim3(static_cast<unsigned>(grid)), dim3(BU_THREADS), 0, stream, bargs, *ds, probe);
+                return util::GRError("BottomUpKernel launch failed", __FILE__, __LINE__);
+            };
+            return slice_lookup.slice != 0 ? launch_dense(slice_lookup) : launch_dense(lookup);
         };
         // ---- a CHAIN of bottom-up sweeps behind one host round trip (bottom_up.hpp BottomUpAutoKernel) ----
         // The frontier is d_frontier_mask[cur_mask]; its size is `first_in`, or -- when the host has not read it back (the chain
@@ -312,7 +318,9 @@ class BFSEnactor : public EnactorBase {
         sweep_rule.emit_factor = problem->emit_queue_factor;
         sweep_rule.sparse_div = problem->sparse_sweep_div;
         auto run_sweep_chain = [&](long long first_in) -> hipError_t {
-            typedef oprtr::advance::BitmapLookup<VertexId> L;
+            typedef oprtr::advance::HubSliceLookup<VertexId> SliceL;  // with a slice; without one BitmapLookup, as launch_bottom_up
+            typedef oprtr::advance::BitmapLookup<VertexId> PlainL;
+            const unsigned hub_slice = problem->HubSlice();
             hipError_t rc = hipSuccess;
             const long long it0 = iteration;
             const long long base_total = enactor_stats.total_queued;
@@ -322,9 +330,12 @@ class BFSEnactor : public EnactorBase {
             const long long bu_steps = ((static_cast<long long>(problem->nodes) + 63) / 64 + oprtr::advance::kBottomUpStepWords - 1) / oprtr::advance::kBottomUpStepWords;
             long long grid = (bu_steps + (BU_THREADS / 64) - 1) / (BU_THREADS / 64);
             const bool walk_queue = problem->walk_queue != 0;  // (two instantiations of the dense body: bottom_up.hpp)
-            const long long cap = max_grid_size > 0 ? max_grid_size
-                : walk_queue ? util::ResidentGrid(oprtr::advance::BottomUpAutoKernel<BU_THREADS, 8, 32, BFSProblem, L, true>, BU_THREADS)
-                             : util::ResidentGrid(oprtr::advance::BottomUpAutoKernel<BU_THREADS, 8, 32, BFSProblem, L, false>, BU_THREADS);
+            auto resident = [&](auto probe) -> long long {
+                typedef decltype(probe) L;
+                return walk_queue ? util::ResidentGrid(oprtr::advance::BottomUpAutoKernel<BU_THREADS, 8, 32, BFSProblem, L, true>, BU_THREADS)
+                                  : util::ResidentGrid(oprtr::advance::BottomUpAutoKernel<BU_THREADS, 8, 32, BFSProblem, L, false>, BU_THREADS);
+            };
+            const long long cap = max_grid_size > 0 ? max_grid_size : (hub_slice != 0 ? resident(SliceL{}) : resident(PlainL{}));
             if (grid > cap) grid = cap;
             if (grid < 1) grid = 1;
             const long long chunks = ((static_cast<long long>(problem->nodes) + 63) / 64 + oprtr::advance::kSparseChunkWords - 1) / oprtr::advance::kSparseChunkWords;
@@ -340,7 +351,6 @@ class BFSEnactor : public EnactorBase {
                 bargs.d_inv_row_offsets = ds->d_inv_row_offsets;
                 bargs.d_inv_column_indices = ds->d_inv_column_indices;
                 bargs.d_inv_heads = ds->d_inv_heads;
-                L lookup{ds->d_frontier_mask[masks[k - 1]]};
                 bargs.d_frontier_out = reinterpret_cast<unsigned long long *>(ds->d_frontier_mask[masks[k]]);
                 bargs.d_visited = reinterpret_cast<unsigned long long *>(ds->d_visited_mask);
                 const long long level = it0 + k - 1;  // the BSP iteration this sweep is
@@ -367,14 +377,19 @@ class BFSEnactor : public EnactorBase {
                 chain.d_log = work_progress.d_chain_log;
                 typename BFSProblem::DataSlice level_slice = *ds;
                 level_slice.iteration = static_cast<VertexId>(level);
-                if (walk_queue)
-                    hipLaunchKernelGGL((oprtr::advance::BottomUpAutoKernel<BU_THREADS, 8, 32, BFSProblem, L, true>), dim3(static_cast<unsigned>(grid)),
-                                       dim3(BU_THREADS), 0, stream, bargs, level_slice, lookup, chain, static_cast<unsigned>(sparse_grid),
-                                       static_cast<unsigned>(emit_grid));
-                else
-                    hipLaunchKernelGGL((oprtr::advance::BottomUpAutoKernel<BU_THREADS, 8, 32, BFSProblem, L, false>), dim3(static_cast<unsigned>(grid)),
-                                       dim3(BU_THREADS), 0, stream, bargs, level_slice, lookup, chain, static_cast<unsigned>(sparse_grid),
-                                       static_cast<unsigned>(emit_grid));
+                auto launch_sweep = [&](auto lookup) {
+                    typedef decltype(lookup) L;
+                    if (walk_queue)
+                        hipLaunchKernelGGL((oprtr::advance::BottomUpAutoKernel<BU_THREADS, 8, 32, BFSProblem, L, true>), dim3(static_cast<unsigned>(grid)),
+                                           dim3(BU_THREADS), 0, stream, bargs, level_slice, lookup, chain, static_cast<unsigned>(sparse_grid),
+                                           static_cast<unsigned>(emit_grid));
+                    else
+                        hipLaunchKernelGGL((oprtr::advance::BottomUpAutoKernel<BU_THREADS, 8, 32, BFSProblem, L, false>), dim3(static_cast<unsigned>(grid)),
+                                           dim3(BU_THREADS), 0, stream, bargs, level_slice, lookup, chain, static_cast<unsigned>(sparse_grid),
+                                           static_cast<unsigned>(emit_grid));
+                };
+                if (hub_slice != 0) launch_sweep(SliceL{ds->d_frontier_mask[masks[k - 1]], hub_slice});
+                else launch_sweep(PlainL{ds->d_frontier_mask[masks[k - 1]]});
                 if ((rc = util::GRError("BottomUpAutoKernel launch failed", __FILE__, __LINE__))) return rc;
                 queued = k;
             }

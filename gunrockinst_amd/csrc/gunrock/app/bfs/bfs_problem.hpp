@@ -733,7 +733,21 @@ struct BFSProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
     int relabel = -1;                 // policy (effective at the next Reset): 1 search the relabelled copy, 0 the caller's numbering,
                                       // -1 the copy on graphs of at least relabel_min_nodes vertices
     long long relabel_min_nodes = 1ll << 23;  // (scale-22 R-MAT: the label pass costs more than the sweeps save, DESIGN §3.3 k)
-    long long relabel_hubs = 0;       // size limit of the hub tier (0: two tiers, with edges / without; DESIGN §3.3 k: hubs first measured no gain)
+    long long relabel_hubs = 65536;   // size limit of the hub tier (0: two tiers, with edges / without).  65536 = the ids an 8 KiB hub slice of the
+                                      // frontier bitmap answers from LDS (hub_slice below, DESIGN §3.3 n)
+    // ids the dense bottom-up sweeps answer from an LDS copy of the frontier bitmap's first words (bottom_up.hpp HubSliceLookup,
+    // DESIGN §3.3 n); read at every launch.  -1: the copy's hub tier while a search runs on the copy, nothing in the caller's
+    // numbering; 0: off.  Whatever is asked for, HubSlice() caps it by the LDS array and by the bitmap.
+    long long hub_slice = -1;
+    unsigned HubSlice() const
+    {
+        long long ids = hub_slice >= 0 ? hub_slice : (active == 1 ? relabelled.hubs : 0);
+        const long long cap = static_cast<long long>(oprtr::advance::kHubSliceWords) * 32;
+        const long long bitmap = static_cast<long long>(MaskWords()) * 32;
+        if (ids > cap) ids = cap;
+        if (ids > bitmap) ids = bitmap;
+        return static_cast<unsigned>(ids < 0 ? 0 : ids);
+    }
     bool build_relabelled = false;    // policy: InverseIsSelf builds the copy (the one-shot entry point leaves it off)
     int active = 0;                   // state: numbering of the running search
     bool translate_pending = false;   // state: a non-deferred search on the copy still owes its caller-order pass

@@ -20,6 +20,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include <gunrock/oprtr/advance/sweep_chain.hpp>
 #include <gunrock/oprtr/frontier_writer.hpp>
 #include <gunrock/util/device_intrinsics.hpp>
@@ -140,6 +142,77 @@ struct BitmapLookup {
         return (bits[static_cast<unsigned>(u) >> 5] >> (u & 31)) & 1u;
     }
 };
+// ---- HubSliceLookup: BitmapLookup with the first words of the bitmap in LDS (hub_slice, DESIGN §3.3 n) ----
+// A probe costs the vector-memory path one lane address whether it hits L1 or not, and most probes of a sweep on the relabelled
+// copy ask about hub ids (graphio/relabel.hpp puts them at 0..H-1).  The bitmap a sweep probes is complete before the launch and
+// nothing writes it meanwhile, so every workgroup copies its first ceil(slice / 32) words into LDS once (SliceFill) and ids below
+// `slice` are answered there.  Branch-free like the probe blocks that call it: every lane issues both loads and selects; the
+// load that is not used goes to word 0 of its memory (the hot word that a lane with nothing to ask reads anyway: it probes id 0).
+// The slice covers ids [0, slice) whatever the tiers of the numbering are: which vertices those are decides only how many
+// probes stay in LDS.  slice = 0: every probe goes to global memory, as BitmapLookup.
+#ifndef GRX_BU_SLICE_WORDS
+#define GRX_BU_SLICE_WORDS 4096
+#endif
+constexpr int kHubSliceWords = GRX_BU_SLICE_WORDS;  // capacity of the LDS array in 32-bit words (16 KiB: ids below 131072)
+typedef __attribute__((address_space(3))) const unsigned LdsWord;
+template <typename VertexId>
+struct HubSliceLookup {
+    const unsigned *bits;
+    unsigned slice;                 // ids below it are answered from LDS (the launch code caps it: BFSProblem::HubSlice)
+    // set by SliceFill on the device.  A kernel that takes this lookup MUST call SliceFill before its first probe, with slice = 0
+    // too: operator() reads LDS word 0 through this pointer for every lane, whatever the slice is.
+    const unsigned *lds = nullptr;
+    __device__ __forceinline__ bool operator()(VertexId u) const
+    {
+        const unsigned x = static_cast<unsigned>(u);
+        const bool local = x < slice;
+        const unsigned far = bits[local ? 0u : x >> 5];
+        const unsigned near = ((LdsWord *)lds)[local ? x >> 5 : 0u];  // (a ds_read, not a flat load)
+        return ((local ? near : far) >> (x & 31)) & 1u;
+    }
+};
+// LDS words a kernel sets aside for its lookup's slice, and the lookup a body without a slice gets
+template <typename Lookup> struct SliceOf {
+    static constexpr int kWords = 1;
+    typedef Lookup Plain;
+    static __device__ __forceinline__ Plain Global(const Lookup &l) { return l; }
+};
+template <typename VertexId> struct SliceOf<HubSliceLookup<VertexId>> {
+    static constexpr int kWords = kHubSliceWords;
+    typedef BitmapLookup<VertexId> Plain;
+    static __device__ __forceinline__ Plain Global(const HubSliceLookup<VertexId> &l) { return Plain{l.bits}; }
+};
+// The fill: whole workgroup, before its first step; ends with the one barrier.  `nodes` bounds the copy by the bitmap itself
+// (bitmaps are whole 64-bit words plus two 32-bit words of padding, bfs_problem.hpp MaskWords: a 16-byte load of the last
+// words stays inside), kHubSliceWords by the array.
+template <int THREADS, typename Lookup>
+__device__ __forceinline__ void SliceFill(Lookup &, unsigned *, long long) {}
+template <int THREADS, typename VertexId>
+__device__ __forceinline__ void SliceFill(HubSliceLookup<VertexId> &l, unsigned *s_slice, long long nodes)
+{
+    const unsigned long long mask_words = static_cast<unsigned long long>((nodes + 63) / 64) * 2ull;
+    unsigned ids = l.slice;
+    if (ids > static_cast<unsigned>(kHubSliceWords) * 32u) ids = static_cast<unsigned>(kHubSliceWords) * 32u;
+    if (ids > mask_words * 32ull) ids = static_cast<unsigned>(mask_words * 32ull);
+    const unsigned words = (ids + 31u) >> 5;
+    static_assert(kHubSliceWords % (4 * THREADS) == 0, "the fill copies 16 bytes per thread and round, whole rounds");
+    constexpr int ROUNDS = kHubSliceWords / (4 * THREADS);
+    uint4 q[ROUNDS];
+#pragma unroll
+    for (int k = 0; k < ROUNDS; ++k) {  // all loads of the thread in flight together
+        const unsigned at = static_cast<unsigned>(k * THREADS + threadIdx.x);
+        q[k] = (4u * at < words) ? reinterpret_cast<const uint4 *>(l.bits)[at] : make_uint4(0, 0, 0, 0);
+    }
+#pragma unroll
+    for (int k = 0; k < ROUNDS; ++k) {
+        const unsigned at = static_cast<unsigned>(k * THREADS + threadIdx.x);
+        if (4u * at < words) reinterpret_cast<uint4 *>(s_slice)[at] = q[k];
+    }
+    __syncthreads();
+    l.slice = ids;
+    l.lds = s_slice;
+}
+
 // Frontier bitmaps of `parts` ranks, one after the other (the all-gather's layout); vertex u is bit (u / parts) of rank
 // (u mod parts).  The quotient comes from a multiplication by a precomputed reciprocal: gfx950 has no integer divide, a
 // runtime-divisor u / parts is a ~35-instruction sequence, and this runs once per probed in-edge of a bottom-up sweep.
@@ -365,14 +438,22 @@ __device__ __forceinline__ VertexId WalkRow(const BottomUpArgs<VertexId, SizeT> 
 // The dense sweep (whole workgroup).  BottomUpKernel is this body alone; BottomUpAutoKernel picks it or the compacting sweep on
 // the device.
 // HEADS_ONLY: the body without its row walks (the first cut of a "heads, then the rest" level): a third of the registers.
+// LDS of the sweep bodies, as structs: a kernel that holds one body declares it, BottomUpAutoKernel overlays those of the two
+// bodies it chooses between (they never run in one launch).
+template <int WAVES>
+struct DenseShared {
+    unsigned long long s_total[WAVES];
+};
+
 template <int THREADS, int PROBE, int SOLO_LIMIT, typename ProblemData, typename Lookup, bool HEADS_ONLY = false>
 __device__ __forceinline__ void DenseSweep(const BottomUpArgs<typename ProblemData::VertexId, typename ProblemData::SizeT> &a,
-                                           typename ProblemData::DataSlice &slice, const Lookup &in_frontier)
+                                           typename ProblemData::DataSlice &slice, const Lookup &in_frontier,
+                                           DenseShared<THREADS / util::kWaveSize> &sh)
 {
     typedef typename ProblemData::VertexId VertexId;
     constexpr int WAVES = THREADS / util::kWaveSize;
     constexpr int STEP_WORDS = kBottomUpStepWords;  // bitmap words (x64 vertices) a wave takes per step; lanes 0..STEP_WORDS-1 own one word each
-    __shared__ unsigned long long s_total[WAVES];
+    auto &s_total = sh.s_total;
     util::DutyStamp duty(a.d_duty);
 
     const int tid = threadIdx.x;
@@ -563,9 +644,23 @@ constexpr int kWalkBatch = GRX_BU_WALK_BATCH;
 constexpr int kWalkDrain = GRX_BU_WALK_DRAIN;
 constexpr int kWalkQueue = 128;
 
+template <int WAVES>
+struct DenseQueuedShared {
+    static constexpr int BATCH_WORDS = kWalkBatch * kBottomUpStepWords;
+    unsigned long long s_total[WAVES];
+    unsigned s_found[WAVES][BATCH_WORDS * 2];  // found bits of the wave's batch, 32-bit halves
+    // the batch's words as loaded, kept out of the registers: visited (for the write-back), open, and the rank tables of compacted heads
+    unsigned long long s_visited[WAVES][BATCH_WORDS];
+    unsigned long long s_open[WAVES][BATCH_WORDS];
+    unsigned long long s_with_edges[WAVES][BATCH_WORDS];
+    unsigned s_base[WAVES][BATCH_WORDS];
+    unsigned short s_walker[WAVES][kWalkQueue];  // (word of the batch) << 6 | bit
+};
+
 template <int THREADS, int PROBE, int SOLO_LIMIT, typename ProblemData, typename Lookup>
 __device__ __forceinline__ void DenseSweepQueued(const BottomUpArgs<typename ProblemData::VertexId, typename ProblemData::SizeT> &a,
-                                                 typename ProblemData::DataSlice &slice, const Lookup &in_frontier)
+                                                 typename ProblemData::DataSlice &slice, const Lookup &in_frontier,
+                                                 DenseQueuedShared<THREADS / util::kWaveSize> &sh)
 {
     typedef typename ProblemData::VertexId VertexId;
     typedef typename ProblemData::SizeT SizeT;
@@ -577,14 +672,13 @@ __device__ __forceinline__ void DenseSweepQueued(const BottomUpArgs<typename Pro
     static_assert((kWalkDrain - 1) + util::kWaveSize <= kWalkQueue, "the queue holds what waits plus one word's append");
     static_assert((kWalkQueue & (kWalkQueue - 1)) == 0, "ring positions are masked");
     static_assert(BATCH_WORDS * 64 <= 65536, "an entry names its vertex by (word of the batch, bit)");
-    __shared__ unsigned long long s_total[WAVES];
-    __shared__ unsigned s_found[WAVES][BATCH_WORDS * 2];  // found bits of the wave's batch, 32-bit halves
-    // the batch's words as loaded, kept out of the registers: visited (for the write-back), open, and the rank tables of compacted heads
-    __shared__ unsigned long long s_visited[WAVES][BATCH_WORDS];
-    __shared__ unsigned long long s_open[WAVES][BATCH_WORDS];
-    __shared__ unsigned long long s_with_edges[WAVES][BATCH_WORDS];
-    __shared__ unsigned s_base[WAVES][BATCH_WORDS];
-    __shared__ unsigned short s_walker[WAVES][kWalkQueue];  // (word of the batch) << 6 | bit
+    auto &s_total = sh.s_total;
+    auto &s_found = sh.s_found;
+    auto &s_visited = sh.s_visited;
+    auto &s_open = sh.s_open;
+    auto &s_with_edges = sh.s_with_edges;
+    auto &s_base = sh.s_base;
+    auto &s_walker = sh.s_walker;
     util::DutyStamp duty(a.d_duty);
 
     const int tid = threadIdx.x;
@@ -779,8 +873,12 @@ __global__ __launch_bounds__(THREADS, GRX_BU_MIN_WAVES) void BottomUpKernel(
     BottomUpArgs<typename ProblemData::VertexId, typename ProblemData::SizeT> a, typename ProblemData::DataSlice slice,
     Lookup in_frontier)
 {
-    if (WALK_QUEUE) DenseSweepQueued<THREADS, PROBE, SOLO_LIMIT, ProblemData, Lookup>(a, slice, in_frontier);
-    else DenseSweep<THREADS, PROBE, SOLO_LIMIT, ProblemData, Lookup>(a, slice, in_frontier);
+    constexpr int WAVES = THREADS / util::kWaveSize;
+    __shared__ typename std::conditional<WALK_QUEUE, DenseQueuedShared<WAVES>, DenseShared<WAVES>>::type s_body;
+    __shared__ __attribute__((aligned(16))) unsigned s_slice[SliceOf<Lookup>::kWords];
+    SliceFill<THREADS>(in_frontier, s_slice, static_cast<long long>(a.nodes));
+    if constexpr (WALK_QUEUE) DenseSweepQueued<THREADS, PROBE, SOLO_LIMIT, ProblemData, Lookup>(a, slice, in_frontier, s_body);
+    else DenseSweep<THREADS, PROBE, SOLO_LIMIT, ProblemData, Lookup>(a, slice, in_frontier, s_body);
 }
 
 #ifndef GRX_BU_HEADS_MIN_WAVES
@@ -791,7 +889,10 @@ __global__ __launch_bounds__(THREADS, GRX_BU_HEADS_MIN_WAVES) void BottomUpHeads
     BottomUpArgs<typename ProblemData::VertexId, typename ProblemData::SizeT> a, typename ProblemData::DataSlice slice,
     Lookup in_frontier)
 {
-    DenseSweep<THREADS, 8, 32, ProblemData, Lookup, true>(a, slice, in_frontier);
+    __shared__ DenseShared<THREADS / util::kWaveSize> s_body;
+    __shared__ __attribute__((aligned(16))) unsigned s_slice[SliceOf<Lookup>::kWords];
+    SliceFill<THREADS>(in_frontier, s_slice, static_cast<long long>(a.nodes));
+    DenseSweep<THREADS, 8, 32, ProblemData, Lookup, true>(a, slice, in_frontier, s_body);
 }
 
 // ---- bottom-up sweep for a nearly finished search (few unvisited vertices) ----
@@ -817,10 +918,22 @@ __device__ __forceinline__ int NthSetBit(unsigned long long x, int r)  // positi
 
 // EMIT_QUEUE: the body CAN stage its finds and flush them as a queue (LDS for the staging buffer); `emit` says whether this launch
 // does.  `grid_limit`: workgroups that take part (the caller has sent the others home).
+template <int THREADS, typename VertexId, typename SizeT, bool EMIT_QUEUE>
+struct SparseShared {
+    static constexpr int WAVES = THREADS / util::kWaveSize;
+    static constexpr int CAPACITY = 16 * THREADS;
+    typedef FrontierWriter<THREADS, EMIT_QUEUE ? CAPACITY : THREADS, VertexId, SizeT> Writer;
+    unsigned long long s_total[WAVES];
+    unsigned s_found[WAVES][kSparseChunkWords * 2];  // found bits of the wave's current chunk, 32-bit halves
+    struct NoStaging {};
+    typename std::conditional<EMIT_QUEUE, typename Writer::Storage, NoStaging>::type s_writer;  // (the staging buffer only where a queue can be emitted)
+};
+
 template <int THREADS, int PROBE, int SOLO_LIMIT, typename ProblemData, typename Lookup, bool EMIT_QUEUE>
 __device__ __forceinline__ void SparseSweep(const BottomUpArgs<typename ProblemData::VertexId, typename ProblemData::SizeT> &a,
                                             typename ProblemData::DataSlice &slice, const Lookup &in_frontier, const bool emit,
-                                            const unsigned grid_limit)
+                                            const unsigned grid_limit,
+                                            SparseShared<THREADS, typename ProblemData::VertexId, typename ProblemData::SizeT, EMIT_QUEUE> &sh)
 {
     typedef typename ProblemData::VertexId VertexId;
     typedef typename ProblemData::SizeT SizeT;
@@ -829,13 +942,16 @@ __device__ __forceinline__ void SparseSweep(const BottomUpArgs<typename ProblemD
     static_assert(CHUNK_WORDS <= 64 && (CHUNK_WORDS & (CHUNK_WORDS - 1)) == 0, "one bitmap word per lane, a power of two");
     constexpr int CAPACITY = 16 * THREADS;
     typedef FrontierWriter<THREADS, EMIT_QUEUE ? CAPACITY : THREADS, VertexId, SizeT> Writer;
-    __shared__ unsigned long long s_total[WAVES];
-    __shared__ unsigned s_found[WAVES][CHUNK_WORDS * 2];  // found bits of the wave's current chunk, 32-bit halves
+    auto &s_total = sh.s_total;
+    auto &s_found = sh.s_found;
     util::DutyStamp duty(a.d_duty);
-    __shared__ typename Writer::Storage s_writer;
-    if (EMIT_QUEUE && emit) {
-        Writer::Init(s_writer);
-        __syncthreads();
+    auto &s_writer = sh.s_writer;
+    (void)s_writer;
+    if constexpr (EMIT_QUEUE) {
+        if (emit) {
+            Writer::Init(s_writer);
+            __syncthreads();
+        }
     }
 
     const int tid = threadIdx.x;
@@ -920,14 +1036,16 @@ __device__ __forceinline__ void SparseSweep(const BottomUpArgs<typename ProblemD
                 if (ProblemData::MARK_PREDECESSORS) slice.d_preds[v] = parent;
                 atomicOr(&s_found[wave][2 * j + (bit >> 5)], 1u << (bit & 31));
             }
-            if (EMIT_QUEUE && emit) {  // stage the finds for the queue (one LDS atomic per wave; past the capacity they are only counted)
-                const unsigned long long fm = __ballot(parent >= 0);
-                if (fm) {
-                    const int leader = __ffsll(static_cast<long long>(fm)) - 1;
-                    int at = 0;
-                    if (static_cast<int>(lane) == leader) at = atomicAdd(&s_writer.count, __popcll(fm));
-                    at = __shfl(at, leader, util::kWaveSize);
-                    if (parent >= 0 && at + __popcll(fm) <= CAPACITY) s_writer.buf[at + util::RankInMask(fm)] = v;
+            if constexpr (EMIT_QUEUE) {
+                if (emit) {  // stage the finds for the queue (one LDS atomic per wave; past the capacity they are only counted)
+                    const unsigned long long fm = __ballot(parent >= 0);
+                    if (fm) {
+                        const int leader = __ffsll(static_cast<long long>(fm)) - 1;
+                        int at = 0;
+                        if (static_cast<int>(lane) == leader) at = atomicAdd(&s_writer.count, __popcll(fm));
+                        at = __shfl(at, leader, util::kWaveSize);
+                        if (parent >= 0 && at + __popcll(fm) <= CAPACITY) s_writer.buf[at + util::RankInMask(fm)] = v;
+                    }
                 }
             }
         }
@@ -952,13 +1070,15 @@ __device__ __forceinline__ void SparseSweep(const BottomUpArgs<typename ProblemD
         unsigned long long *slot = util::WideTailSlot(a.d_wide);
         if (sum) atomicAdd(slot ? slot : a.d_tail_out, sum);
     }
-    if (EMIT_QUEUE && emit) {
-        const int staged = Writer::Count(s_writer);  // (the barrier above ordered it after every append)
-        __syncthreads();
-        if (staged > CAPACITY) {
-            if (tid == 0) *a.d_queue_invalid = 1;
-        } else {
-            Writer::template Flush<true>(s_writer, staged, a.queue_out, a.d_queue_tail, a.d_overflow, a.d_fwd_row_offsets);
+    if constexpr (EMIT_QUEUE) {
+        if (emit) {
+            const int staged = Writer::Count(s_writer);  // (the barrier above ordered it after every append)
+            __syncthreads();
+            if (staged > CAPACITY) {
+                if (tid == 0) *a.d_queue_invalid = 1;
+            } else {
+                Writer::template Flush<true>(s_writer, staged, a.queue_out, a.d_queue_tail, a.d_overflow, a.d_fwd_row_offsets);
+            }
         }
     }
 }
@@ -968,7 +1088,8 @@ __global__ __launch_bounds__(THREADS) void BottomUpSparseKernel(
     BottomUpArgs<typename ProblemData::VertexId, typename ProblemData::SizeT> a, typename ProblemData::DataSlice slice,
     Lookup in_frontier)
 {
-    SparseSweep<THREADS, PROBE, SOLO_LIMIT, ProblemData, Lookup, EMIT_QUEUE>(a, slice, in_frontier, EMIT_QUEUE, gridDim.x);
+    __shared__ SparseShared<THREADS, typename ProblemData::VertexId, typename ProblemData::SizeT, EMIT_QUEUE> s_body;
+    SparseSweep<THREADS, PROBE, SOLO_LIMIT, ProblemData, Lookup, EMIT_QUEUE>(a, slice, in_frontier, EMIT_QUEUE, gridDim.x, s_body);
 }
 
 template <int THREADS, int PROBE, int SOLO_LIMIT, typename ProblemData, typename Lookup, bool WALK_QUEUE = true>
@@ -982,15 +1103,34 @@ __global__ __launch_bounds__(THREADS, GRX_BU_MIN_WAVES) void BottomUpAutoKernel(
         // a sweep that emits no queue leaves its queue-tail slot zero, so that a bitmap -> queue conversion can follow directly
         if (action >= kSweepDense && action != kSweepSparseEmit && a.d_queue_tail) *a.d_queue_tail = 0ull;
     }
-    if (action < kSweepDense) return;  // (uniform over the grid)
+    if (action < kSweepDense) return;  // (uniform over the grid; a skipped sweep has loaded nothing)
+    // One LDS union for both bodies: the dense body's arrays and the lookup's slice, or the compacting body's staging.  As
+    // separate arrays they add up (the compiler gives every one its own bytes) and the slice would cost the kernel two of its six
+    // workgroups per CU.
+    constexpr int WAVES = THREADS / util::kWaveSize;
+    struct DensePart {
+        typename std::conditional<WALK_QUEUE, DenseQueuedShared<WAVES>, DenseShared<WAVES>>::type body;
+        __attribute__((aligned(16))) unsigned slice[SliceOf<Lookup>::kWords];
+    };
+    typedef SparseShared<THREADS, typename ProblemData::VertexId, typename ProblemData::SizeT, true> SparsePart;
+    union Overlay {
+        DensePart dense;
+        SparsePart sparse;
+    };
+    __shared__ Overlay s_overlay;
     if (action == kSweepDense) {
-        if (WALK_QUEUE) DenseSweepQueued<THREADS, PROBE, SOLO_LIMIT, ProblemData, Lookup>(a, slice, in_frontier);
-        else DenseSweep<THREADS, PROBE, SOLO_LIMIT, ProblemData, Lookup>(a, slice, in_frontier);
+        DensePart &sh = s_overlay.dense;
+        SliceFill<THREADS>(in_frontier, sh.slice, static_cast<long long>(a.nodes));
+        if constexpr (WALK_QUEUE) DenseSweepQueued<THREADS, PROBE, SOLO_LIMIT, ProblemData, Lookup>(a, slice, in_frontier, sh.body);
+        else DenseSweep<THREADS, PROBE, SOLO_LIMIT, ProblemData, Lookup>(a, slice, in_frontier, sh.body);
     } else {
         const unsigned want = action == kSweepSparseEmit ? emit_grid : sparse_grid;  // (emitting: every workgroup ends with an atomic on one word)
         const unsigned limit = want < gridDim.x ? want : gridDim.x;
         if (blockIdx.x >= limit) return;
-        SparseSweep<THREADS, PROBE, SOLO_LIMIT, ProblemData, Lookup, true>(a, slice, in_frontier, action == kSweepSparseEmit, limit);
+        // (the compacting sweep probes global memory only: its launches take 4-10 us, DESIGN §3.3 n)
+        typedef typename SliceOf<Lookup>::Plain Plain;
+        SparseSweep<THREADS, PROBE, SOLO_LIMIT, ProblemData, Plain, true>(a, slice, SliceOf<Lookup>::Global(in_frontier), action == kSweepSparseEmit,
+                                                                          limit, s_overlay.sparse);
     }
 }
 

@@ -138,6 +138,7 @@ struct BfsRunnerT : BfsRunner {
         else if (key == "chain_closing") problem.chain_closing = value != 0.0;
         else if (key == "label_pass") problem.label_pass = value != 0.0 ? 1 : 0;
         else if (key == "walk_queue") problem.walk_queue = value != 0.0 ? 1 : 0;
+        else if (key == "hub_slice") problem.hub_slice = value < 0.0 ? -1 : static_cast<long long>(value);
         else if (key == "relabel") {  // from the next Reset: 1 the relabelled copy, 0 the caller's numbering, -1 by graph size
             if (value > 0.0 && !problem.HasRelabelled()) return 2;
             problem.relabel = value > 0.0 ? 1 : (value < 0.0 ? -1 : 0);

@@ -140,8 +140,11 @@ int grx_bfs_set_label_deferral(grx_bfs *p, int enabled, int mask_limit);
  * on a symmetric graph) also builds a copy of its CSR renumbered hub-first, edgeless-last, and searches it; labels and
  * predecessors still come back in the caller's numbering.  "relabel" (1: search the copy; 0: the caller's numbering; -1, the
  * default: the copy on graphs of at least "relabel_min_nodes" vertices, default 2^23; effective at the next grx_bfs_reset, both
- * numberings are kept; returns 2 for 1 on a problem without a copy), "relabel_hubs" (most vertices in the hub tier, default 0;
- * rebuilds the copy).  Results never depend on any of them. */
+ * numberings are kept; returns 2 for 1 on a problem without a copy), "relabel_hubs" (most vertices in the hub tier, default
+ * 65536, 0 = none; rebuilds the copy), "hub_slice" (DESIGN.md 3.3 n: the dense bottom-up sweeps answer probes of vertex ids
+ * below this value from a copy of the frontier bitmap's first words in LDS; -1, the default: the size of the copy's hub tier
+ * while a search runs on the copy, nothing in the caller's numbering; 0: off; capped at 131072 ids and at the bitmap's length;
+ * read at every launch of a sweep).  Results never depend on any of them. */
 int grx_bfs_set_option(grx_bfs *p, const char *name, double value);
 /* The relabelled copy: hub-tier size, vertices with edges, the hub degree threshold, build time (ms) and the device bytes it
  * adds.  hubs = -1 when the problem has no copy. */
