@@ -1,4 +1,4 @@
-"""gunrockinst_amd -- MI355X-native frontier engine (BFS / CC / SSSP / BC / PageRank / TopK / MST / MIS / TC / k-core / k-truss / SCC / MS-BFS / BCC) behind Gunrock's C ABI.
+"""gunrockinst_amd -- MI355X-native frontier engine (BFS / CC / SSSP / BC / PageRank / TopK / MST / MIS / TC / k-core / k-truss / SCC / MS-BFS / BCC / max-flow) behind Gunrock's C ABI.
 
 The product is the shared library ``gunrockinst_amd/lib/libgunrock.so`` (hand-written HIP for gfx950,
 built by ``gunrockinst_amd/csrc/Makefile``).  This package is only the host-side binding: ctypes
@@ -20,6 +20,8 @@ from .capi import (  # noqa: F401
     MSBFS_DEPTHS_NOT_STORED, MSBFS_INVERSE_NOT_SYMMETRIC,
     BccProblem, gunrock_bcc, gunrock_bridges, gunrock_articulation_points, BCC_AUTO, BCC_ROUNDS, BCC_DEVICE_LOOP,
     BCC_FOREST, BCC_SIZES, BCC_NUMBER, BCC_LOWHIGH, BCC_LINK, BCC_LABEL,
+    MaxflowProblem, MaxflowGaveUp, gunrock_maxflow, gunrock_mincut, MAXFLOW_AUTO, MAXFLOW_ROUNDS, MAXFLOW_DEVICE_LOOP,
+    MAXFLOW_PREFLOW, MAXFLOW_RETURN, MAXFLOW_CUT, MAXFLOW_GAVE_UP,
     advance_frontier, advance_queue, advance_reduce,
 )
 
@@ -36,5 +38,7 @@ __all__ = [
     "MSBFS_ALTERNATE", "MSBFS_INVERSE_AUTO", "MSBFS_INVERSE_NONE", "MSBFS_INVERSE_SELF", "MSBFS_INVERSE_BUILD", "MSBFS_LEVEL_PUSH", "MSBFS_LEVEL_PULL",
     "MSBFS_DEPTHS_NOT_STORED", "MSBFS_INVERSE_NOT_SYMMETRIC",
     "BccProblem", "gunrock_bcc", "gunrock_bridges", "gunrock_articulation_points", "BCC_AUTO", "BCC_ROUNDS", "BCC_DEVICE_LOOP", "BCC_FOREST", "BCC_SIZES", "BCC_NUMBER", "BCC_LOWHIGH", "BCC_LINK", "BCC_LABEL",
+    "MaxflowProblem", "MaxflowGaveUp", "gunrock_maxflow", "gunrock_mincut", "MAXFLOW_AUTO", "MAXFLOW_ROUNDS", "MAXFLOW_DEVICE_LOOP", "MAXFLOW_PREFLOW",
+    "MAXFLOW_RETURN", "MAXFLOW_CUT", "MAXFLOW_GAVE_UP",
     "advance_frontier", "advance_queue", "advance_reduce",
 ]

@@ -235,6 +235,20 @@ _SIGNATURES = {
     "grx_bcc_block_cut": (C.c_int, [C.c_void_p, C.c_int, i32p, i32p]),
     "grx_bcc_device_results": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 8),
     "grx_bcc_destroy": (None, [C.c_void_p]),
+    "grx_maxflow_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int]),
+    "grx_maxflow_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p, i32p]),
+    "grx_maxflow_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "grx_maxflow_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
+    "grx_maxflow_reset": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "grx_maxflow_enact": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
+    "grx_maxflow_stats": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_longlong)] * 8 + [C.POINTER(C.c_double)] * 2),
+    "grx_maxflow_phase_trace": (C.c_int, [C.c_void_p, C.c_int, i32p, C.POINTER(C.c_longlong), C.POINTER(C.c_double)]),
+    "grx_maxflow_pairs": (C.c_longlong, [C.c_void_p, i32p, i32p, i32p, i32p]),
+    "grx_maxflow_extract": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), i32p, C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte)]),
+    "grx_maxflow_arc_flow": (C.c_int, [C.c_void_p, i32p]),
+    "grx_maxflow_summary": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
+    "grx_maxflow_device_results": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 7),
+    "grx_maxflow_destroy": (None, [C.c_void_p]),
     "grx_sssp_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int]),
     "grx_sssp_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p, C.POINTER(C.c_uint32), C.c_int]),
     "grx_sssp_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float]),
@@ -1440,6 +1454,152 @@ def gunrock_articulation_points(nodes, row_offsets, col_indices, device=0):
     """One-shot articulation points: returns (mask uint8 per vertex, articulation points)."""
     return _one_shot(BccProblem(device=device).init(nodes, row_offsets, col_indices), BccProblem.reset, BccProblem.enact,
                      lambda p: (p.extract()["articulation"], p.summary()["articulation_points"]))
+
+
+MAXFLOW_AUTO, MAXFLOW_ROUNDS, MAXFLOW_DEVICE_LOOP = 0, 1, 2  # enum GRX_MAXFLOW_* (gunrock_mi355x.h)
+MAXFLOW_PREFLOW, MAXFLOW_RETURN, MAXFLOW_CUT = range(3)  # enum GRX_MAXFLOW_PHASE_*: the kinds of phase_trace()
+MAXFLOW_GAVE_UP = -4  # grx_maxflow_enact: more than "max_rounds" rounds
+
+
+class MaxflowGaveUp(RuntimeError):
+    """MaxflowProblem.enact passed "max_rounds" (GRX_MAXFLOW_GAVE_UP): the handle holds no result and takes the next reset"""
+
+
+class MaxflowProblem(_Handle):
+    """MaxflowProblem + MaxflowEnactor behind the handle C ABI: the maximum flow from src to sink and the minimum cuts of the CSR read
+    as a directed multigraph with int32 capacities (None: 1 each; parallel arcs add up, self-loops are ignored).  Per-pair arrays in
+    the canonical pair order ((a, b) with a < b and an arc either way, sorted).  value, side and cut have one value each; flow and
+    arc_flow are a valid maximum flow that depends on the run."""
+
+    _destroy = "grx_maxflow_destroy"
+
+    _STATS = ("pairs", "rounds", "global_relabels", "pushes", "relabels", "entries_read", "kernel_launches", "readbacks")
+    _SUMMARY = ("value", "side0", "side1", "side2", "cut0", "cut1")
+
+    def __init__(self, instrument=False, device=0):
+        self._create("grx_maxflow_create", int(instrument), device)
+        self.nodes = 0
+        self.entries = 0
+        self.num_pairs = 0
+
+    def _ready(self):
+        m = lib().grx_maxflow_pairs(self._h, None, None, None, None)
+        if m < 0:
+            _check(-m, "MaxflowProblem::Pairs")
+        self.num_pairs = int(m)
+
+    def init(self, nodes, row_offsets, col_indices, capacities=None):
+        ro, ci = _csr_arrays(row_offsets, col_indices, nodes)
+        cap = None if capacities is None else _i32(capacities)
+        if cap is not None and cap.shape[0] != ci.shape[0]:
+            raise ValueError("gunrockinst_amd: %d capacities for %d arcs" % (cap.shape[0], ci.shape[0]))
+        self.nodes, self.entries = int(nodes), int(ci.shape[0])
+        _check(lib().grx_maxflow_init(self._h, self.nodes, self.entries, _p(ro), _p(ci), None if cap is None else _p(cap)),
+               "MaxflowProblem::Init")
+        self._ready()
+        return self
+
+    def init_device(self, nodes, edges, d_row_offsets, d_col_indices, d_capacities=None):
+        """the CSR (and the capacities) stay the caller's and must outlive the handle"""
+        self.nodes, self.entries = int(nodes), int(edges)
+        _check(lib().grx_maxflow_init_device(self._h, self.nodes, self.entries, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices),
+                                             C.c_void_p(d_capacities) if d_capacities else None), "MaxflowProblem::Init(device)")
+        self._ready()
+        return self
+
+    def set_option(self, name, value):
+        """"schedule" (MAXFLOW_AUTO / MAXFLOW_ROUNDS / MAXFLOW_DEVICE_LOOP), "wave_min_row", "discharge_steps", "relabel_interval",
+        "max_rounds", "loop_max_list", "loop_max_entries"; returns the library's code: 0 = set, 1 = unknown name (a value out of
+        range raises)"""
+        rc = lib().grx_maxflow_set_option(self._h, name.encode(), float(value))
+        if rc not in (0, 1):
+            _check(rc, "grx_maxflow_set_option(%s)" % name)
+        return rc
+
+    def reset(self, src, sink):
+        _check(lib().grx_maxflow_reset(self._h, int(src), int(sink)), "MaxflowProblem::Reset")
+
+    def enact(self, max_grid_size=0):
+        """the elapsed milliseconds; MaxflowGaveUp when the rounds passed the option max_rounds"""
+        ms = C.c_float()
+        rc = lib().grx_maxflow_enact(self._h, int(max_grid_size), C.byref(ms))
+        if rc == MAXFLOW_GAVE_UP:
+            raise MaxflowGaveUp("gunrockinst_amd: MaxflowEnactor::Enact gave up (code %d)" % rc)
+        _check(rc, "MaxflowEnactor::Enact")
+        return ms.value
+
+    def stats(self):
+        v = [C.c_longlong() for _ in self._STATS]
+        k, b = C.c_double(), C.c_double()
+        _check(lib().grx_maxflow_stats(self._h, *([C.byref(x) for x in v] + [C.byref(k), C.byref(b)])), "grx_maxflow_stats")
+        out = {name: x.value for name, x in zip(self._STATS, v)}
+        out["kernel_ms"], out["build_ms"] = k.value, b.value
+        return out
+
+    def phase_trace(self):
+        """the three phases of the last enact: (kind as int32: MAXFLOW_PREFLOW / MAXFLOW_RETURN / MAXFLOW_CUT, rounds as int64,
+        milliseconds as float64)"""
+        count = lib().grx_maxflow_phase_trace(self._h, 0, None, None, None)
+        if count < 0:
+            _check(count, "grx_maxflow_phase_trace")
+        kind = np.empty(max(count, 1), dtype=np.int32)
+        rounds = np.empty(max(count, 1), dtype=np.int64)
+        ms = np.empty(max(count, 1), dtype=np.float64)
+        lib().grx_maxflow_phase_trace(self._h, count, _p(kind), rounds.ctypes.data_as(C.POINTER(C.c_longlong)),
+                                      ms.ctypes.data_as(C.POINTER(C.c_double)))
+        return kind[:count], rounds[:count], ms[:count]
+
+    def pairs(self):
+        """the canonical pairs (a, b, cap_ab, cap_ba) as int32, a < b, sorted by (a, b)"""
+        a, b, cab, cba = (np.empty(max(self.num_pairs, 1), dtype=np.int32) for _ in range(4))
+        m = lib().grx_maxflow_pairs(self._h, _p(a), _p(b), _p(cab), _p(cba))
+        if m < 0:
+            _check(-m, "MaxflowProblem::Pairs")
+        return a[:m], b[:m], cab[:m], cba[:m]
+
+    def extract(self):
+        """{"value": int, "flow": int32 per pair, "side": uint8 per vertex, "cut": uint8 per pair}"""
+        m, n = max(self.num_pairs, 1), max(self.nodes, 1)
+        value = C.c_longlong()
+        flow, side, cut = np.empty(m, np.int32), np.empty(n, np.uint8), np.empty(m, np.uint8)
+        _check(lib().grx_maxflow_extract(self._h, C.byref(value), _p(flow), _u8p(side), _u8p(cut)), "MaxflowProblem::Extract")
+        return {"value": int(value.value), "flow": flow[:self.num_pairs], "side": side[:self.nodes], "cut": cut[:self.num_pairs]}
+
+    def arc_flow(self):
+        """int32 per CSR entry of the input"""
+        out = np.empty(max(self.entries, 1), dtype=np.int32)
+        _check(lib().grx_maxflow_arc_flow(self._h, _p(out)), "MaxflowProblem::ArcFlow")
+        return out[:self.entries]
+
+    def summary(self):
+        """{"value", "side0", "side1", "side2", "cut0", "cut1"}"""
+        v = (C.c_longlong * 6)()
+        _check(lib().grx_maxflow_summary(self._h, v), "MaxflowProblem::Summary")
+        return {name: int(x) for name, x in zip(self._SUMMARY, v)}
+
+    def device_results(self):
+        """device pointers {"flow", "side", "cut", "a", "b", "excess", "height"}: per pair flow (int32), cut (uint8), a, b (int32);
+        per vertex side (uint8), excess (int64) and height (int32, not unique)"""
+        names = ("flow", "side", "cut", "a", "b", "excess", "height")
+        p = [C.c_void_p() for _ in names]
+        _check(lib().grx_maxflow_device_results(self._h, *[C.byref(x) for x in p]), "grx_maxflow_device_results")
+        return {name: x.value for name, x in zip(names, p)}
+
+
+def gunrock_maxflow(nodes, row_offsets, col_indices, capacities, src, sink, device=0):
+    """One-shot maximum flow: returns (value, arc_flow int32 per CSR entry)."""
+    return _one_shot(MaxflowProblem(device=device).init(nodes, row_offsets, col_indices, capacities), lambda p: p.reset(src, sink),
+                     MaxflowProblem.enact, lambda p: (p.extract()["value"], p.arc_flow()))
+
+
+def gunrock_mincut(nodes, row_offsets, col_indices, capacities, src, sink, device=0):
+    """One-shot minimum cut: returns (value, side uint8 per vertex, a, b, cut uint8 per canonical pair)."""
+    def result(p):
+        r = p.extract()
+        a, b = p.pairs()[:2]
+        return r["value"], r["side"], a, b, r["cut"]
+    return _one_shot(MaxflowProblem(device=device).init(nodes, row_offsets, col_indices, capacities), lambda p: p.reset(src, sink),
+                     MaxflowProblem.enact, result)
 
 
 MSBFS_AUTO, MSBFS_PUSH, MSBFS_PULL, MSBFS_ALTERNATE = 0, 1, 2, 3  # enum GRX_MSBFS_* (gunrock_mi355x.h): option "direction"

@@ -1,0 +1,364 @@
+// app/maxflow/maxflow_problem.hpp -- device data for the maximum flow and the minimum cut.
+//
+// The reference snapshot has no app/mf; the shape is this tree's Problem (compare app/bcc/bcc_problem.hpp).  The input CSR is read
+// as a directed multigraph with int capacities in edge_values (NULL: 1 each).  Init validates it and builds, with truss's build
+// kernels (truss_functor.hpp is included, not changed), the M canonical pairs a[p] < b[p] in (a, b) order and the residual CSR: the
+// symmetric neighbour CSR over the pairs, rows ascending, with the capacity and the reverse entry on every entry.  The input CSR
+// stays on the device (borrowed after InitFromDevice: the caller keeps it alive) because arc_flow[] is per input entry.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <gunrock/app/maxflow/maxflow_functor.hpp>
+#include <gunrock/app/problem_base.hpp>
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wunused-function"  // (only the build kernels of truss and TC are used here)
+#include <gunrock/app/truss/truss_functor.hpp>
+#pragma clang diagnostic pop
+#include <gunrock/graphio/device_sort.hpp>
+
+namespace gunrock {
+namespace app {
+namespace maxflow {
+
+struct Summary {
+    long long value = 0, side0 = 0, side1 = 0, side2 = 0, cut0 = 0, cut1 = 0;
+    long long cap0 = 0, cap1 = 0;  // the capacity under each cut bit (both equal value: the enactor's second look at the certificate)
+};
+
+template <bool _USE_DOUBLE_BUFFER>
+struct MaxflowProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
+    typedef ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> Base;
+
+    struct DataSlice {
+        int *d_a = nullptr, *d_b = nullptr, *d_cap_ab = nullptr, *d_cap_ba = nullptr, *d_pent = nullptr;  // per pair (pent: the entry a -> b)
+        int *d_nro = nullptr, *d_nci = nullptr, *d_neid = nullptr;                                      // the residual CSR and the pair of every entry
+        int *d_mate = nullptr, *d_cap = nullptr, *d_res = nullptr;                                      // per entry
+        // per vertex
+        long long *d_excess = nullptr;
+        int *d_height = nullptr, *d_queue = nullptr, *d_mark = nullptr, *d_list[2] = {nullptr, nullptr}, *d_fwd = nullptr, *d_bwd = nullptr;
+        unsigned char *d_side = nullptr;
+        // per pair
+        int *d_flow = nullptr;
+        unsigned char *d_cut = nullptr;
+        int *d_arc_flow = nullptr;  // per input entry, built at the first request behind an Enact
+        unsigned *d_words = nullptr;
+        unsigned long long *d_counters = nullptr;
+        unsigned long long *d_clock = nullptr;  // PHASE_COUNT + 1 stamps
+        Front *d_front = nullptr;
+        Active *d_active = nullptr;
+    };
+
+    DataSlice **data_slices = nullptr;
+    int malformed = 0;
+    long long pairs = 0;   // M
+    int src = -1, sink = -1;
+    bool fresh = false;    // Reset has run and Enact has not
+    bool enacted = false;  // the arrays hold a result
+    bool have_arc_flow = false;
+    double build_ms = 0;   // HIP-event time of the build of the pairs and the residual CSR
+    Summary summary;       // of the last Enact
+
+    ~MaxflowProblem() override
+    {
+        if (data_slices) {
+            DataSlice *ds = data_slices[0];
+            if (ds) {
+                void *bufs[] = {ds->d_a, ds->d_b, ds->d_cap_ab, ds->d_cap_ba, ds->d_pent, ds->d_nro, ds->d_nci, ds->d_neid, ds->d_mate, ds->d_cap, ds->d_res,
+                                ds->d_excess, ds->d_height, ds->d_queue, ds->d_mark, ds->d_list[0], ds->d_list[1], ds->d_fwd, ds->d_bwd, ds->d_side, ds->d_flow,
+                                ds->d_cut, ds->d_arc_flow, ds->d_words, ds->d_counters, ds->d_clock, ds->d_front, ds->d_active};
+                for (void *b : bufs)
+                    if (b) util::GRError(hipFree(b), "MaxflowProblem hipFree failed", __FILE__, __LINE__);
+                delete ds;
+            }
+            delete[] data_slices;
+        }
+    }
+
+    static int Grid(long long work)
+    {
+        long long blocks = (work + 255) / 256;
+        if (blocks < 1) blocks = 1;
+        if (blocks > 2048) blocks = 2048;  // 256 CUs x 8 workgroups, grid-stride the rest
+        return static_cast<int>(blocks);
+    }
+
+    Ctx DeviceCtx(int wave_min_row, int discharge_steps) const
+    {
+        const DataSlice *ds = data_slices[0];
+        Ctx c;
+        c.ro = ds->d_nro;
+        c.ci = ds->d_nci;
+        c.mate = ds->d_mate;
+        c.res = ds->d_res;
+        c.excess = ds->d_excess;
+        c.height = ds->d_height;
+        c.queue = ds->d_queue;
+        c.mark = ds->d_mark;
+        c.words = ds->d_words;
+        c.counters = ds->d_counters;
+        c.nodes = this->nodes;
+        c.src = src;
+        c.sink = sink;
+        c.wave_min_row = wave_min_row;
+        c.discharge_steps = discharge_steps;
+        return c;
+    }
+
+    hipError_t Build()
+    {
+        hipError_t retval = hipSuccess;
+        DataSlice *ds = data_slices[0];
+        GraphSlice<int, int, int> *gs = this->graph_slices[0];
+        hipStream_t stream = gs->stream;
+        const long long n = this->nodes, m = this->edges;
+        const size_t n1 = static_cast<size_t>(n > 0 ? n : 1);
+        GR_CHECK(hipMalloc(&ds->d_words, sizeof(unsigned) * W_COUNT), "MaxflowProblem hipMalloc failed");
+        GR_CHECK(hipMalloc(&ds->d_counters, sizeof(unsigned long long) * C_COUNT), "MaxflowProblem hipMalloc failed");
+        GR_CHECK(hipMalloc(&ds->d_clock, sizeof(unsigned long long) * (PHASE_COUNT + 1)), "MaxflowProblem hipMalloc failed");
+        GR_CHECK(hipMalloc(&ds->d_front, sizeof(Front)), "MaxflowProblem hipMalloc failed");
+        GR_CHECK(hipMalloc(&ds->d_active, sizeof(Active)), "MaxflowProblem hipMalloc failed");
+
+        // the CSR must be one: the build indexes with what it reads
+        int bad = 0;
+        GR_CHECK(hipMemsetAsync(ds->d_words, 0, sizeof(unsigned) * W_COUNT, stream), "MaxflowProblem memset failed");
+        hipLaunchKernelGGL(tc::ValidateCsrKernel, dim3(Grid((n > m ? n : m) + 1)), dim3(256), 0, stream, gs->d_row_offsets, gs->d_column_indices,
+                           n, m, reinterpret_cast<int *>(ds->d_words));
+        GR_CHECK(hipGetLastError(), "ValidateCsrKernel launch failed");
+        GR_CHECK(hipMemcpyAsync(&bad, ds->d_words, sizeof(int), hipMemcpyDeviceToHost, stream), "MaxflowProblem read-back failed");
+        GR_CHECK(hipStreamSynchronize(stream), "MaxflowProblem read-back sync failed");
+        if (bad) {
+            malformed = 1;
+            return hipErrorInvalidValue;
+        }
+
+        // (the events and the build's scratch go on every path out: run() may return early, release() follows it)
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        unsigned *d_keep = nullptr, *d_deg = nullptr;
+        unsigned long long *d_pos = nullptr, *d_sums = nullptr, *d_ckeys = nullptr, *d_cap64 = nullptr;
+        int *d_up = nullptr, *d_low = nullptr;
+        long long M = 0;
+        auto release = [&]() {
+            for (int i = 0; i < 2; ++i)
+                if (ev[i]) hipEventDestroy(ev[i]);
+            void *scratch[] = {d_keep, d_pos, d_sums, d_ckeys, d_up, d_low, d_deg, d_cap64};
+            for (void *b : scratch)
+                if (b) util::GRError(hipFree(b), "MaxflowProblem hipFree failed", __FILE__, __LINE__);
+        };
+        auto run = [&]() -> hipError_t {
+            hipError_t retval = hipSuccess;
+            for (int i = 0; i < 2; ++i) GR_CHECK(hipEventCreate(&ev[i]), "MaxflowProblem hipEventCreate failed");
+            GR_CHECK(hipEventRecord(ev[0], stream), "MaxflowProblem hipEventRecord failed");
+
+            GR_CHECK(hipMalloc(&ds->d_nro, sizeof(int) * (n1 + 1)), "MaxflowProblem hipMalloc d_nro failed");
+            GR_CHECK(hipMemsetAsync(ds->d_nro, 0, sizeof(int) * (n1 + 1), stream), "MaxflowProblem memset failed");
+
+            // (the sequence of BccProblem::Build: the pairs and their neighbour CSR)
+            int col_bits = 1;
+            while ((1ll << col_bits) < n) ++col_bits;
+            const int key_bits = 2 * col_bits;  // <= 62
+            const unsigned long long sentinel = (1ull << key_bits) - 1ull;  // min = max = 2^cb - 1: never a pair
+            graphio::DeviceKeySort edge_sort;
+            if (m > 0) {
+                const long long scan_words = m > n + 1 ? m : n + 1;
+                GR_CHECK(hipMalloc(&d_keep, sizeof(unsigned) * static_cast<size_t>(m)), "MaxflowProblem hipMalloc failed");
+                GR_CHECK(hipMalloc(&d_pos, sizeof(unsigned long long) * static_cast<size_t>(m)), "MaxflowProblem hipMalloc failed");
+                GR_CHECK(hipMalloc(&d_sums, sizeof(unsigned long long) * static_cast<size_t>(graphio::ScanScratchWords(scan_words))),
+                         "MaxflowProblem hipMalloc failed");
+                GR_CHECK(edge_sort.Reserve(m), "MaxflowProblem sort scratch failed");
+                hipLaunchKernelGGL(tc::EdgeKeysKernel, dim3(Grid(m)), dim3(256), 0, stream, gs->d_row_offsets, gs->d_column_indices, static_cast<int>(n),
+                                   m, col_bits, sentinel, edge_sort.Keys());
+                GR_CHECK(hipGetLastError(), "EdgeKeysKernel launch failed");
+                unsigned long long *d_sorted = nullptr;
+                GR_CHECK(edge_sort.Sort(m, key_bits, stream, &d_sorted), "MaxflowProblem edge sort failed");
+                hipLaunchKernelGGL(graphio::FlagKernel, dim3(Grid(m)), dim3(256), 0, stream, d_sorted, m, sentinel, d_keep);
+                GR_CHECK(hipGetLastError(), "FlagKernel launch failed");
+                GR_CHECK(graphio::DeviceExclusiveScan<unsigned long long>(d_keep, d_pos, m, d_sums, stream), "MaxflowProblem flag scan failed");
+                unsigned long long last_pos = 0;
+                unsigned last_keep = 0;
+                GR_CHECK(hipMemcpyAsync(&last_pos, d_pos + (m - 1), sizeof(last_pos), hipMemcpyDeviceToHost, stream), "MaxflowProblem read-back failed");
+                GR_CHECK(hipMemcpyAsync(&last_keep, d_keep + (m - 1), sizeof(last_keep), hipMemcpyDeviceToHost, stream), "MaxflowProblem read-back failed");
+                GR_CHECK(hipStreamSynchronize(stream), "MaxflowProblem read-back sync failed");
+                M = static_cast<long long>(last_pos) + last_keep;
+                if (2 * M > 0x7FFFFFFFll) return hipErrorInvalidValue;  // every offset of the 2M entries is an int
+                if (M > 0) {
+                    const size_t ms = static_cast<size_t>(M);
+                    GR_CHECK(hipMalloc(&d_ckeys, sizeof(unsigned long long) * ms), "MaxflowProblem hipMalloc failed");
+                    GR_CHECK(hipMalloc(&ds->d_a, sizeof(int) * ms), "MaxflowProblem hipMalloc d_a failed");
+                    GR_CHECK(hipMalloc(&ds->d_b, sizeof(int) * ms), "MaxflowProblem hipMalloc d_b failed");
+                    GR_CHECK(hipMalloc(&ds->d_nci, sizeof(int) * 2 * ms), "MaxflowProblem hipMalloc d_nci failed");
+                    GR_CHECK(hipMalloc(&ds->d_neid, sizeof(int) * 2 * ms), "MaxflowProblem hipMalloc d_neid failed");
+                    GR_CHECK(hipMalloc(&d_up, sizeof(int) * (n1 + 1)), "MaxflowProblem hipMalloc failed");
+                    GR_CHECK(hipMalloc(&d_low, sizeof(int) * (n1 + 1)), "MaxflowProblem hipMalloc failed");
+                    GR_CHECK(hipMalloc(&d_deg, sizeof(unsigned) * (n1 + 1)), "MaxflowProblem hipMalloc failed");
+                    hipLaunchKernelGGL(truss::CanonicalKernel, dim3(Grid(m)), dim3(256), 0, stream, d_sorted, d_keep, d_pos, m, col_bits, d_ckeys,
+                                       ds->d_a, ds->d_b);
+                    GR_CHECK(hipGetLastError(), "CanonicalKernel launch failed");
+                    hipLaunchKernelGGL(truss::SwapKeysKernel, dim3(Grid(M)), dim3(256), 0, stream, d_ckeys, M, col_bits, edge_sort.Keys());
+                    GR_CHECK(hipGetLastError(), "SwapKeysKernel launch failed");
+                    unsigned long long *d_skeys = nullptr;
+                    GR_CHECK(edge_sort.Sort(M, key_bits, stream, &d_skeys), "MaxflowProblem edge sort failed");
+                    hipLaunchKernelGGL(truss::RowStartsKernel, dim3(Grid(n + 1)), dim3(256), 0, stream, d_ckeys, d_skeys, M, n, col_bits, d_up, d_low);
+                    GR_CHECK(hipGetLastError(), "RowStartsKernel launch failed");
+                    hipLaunchKernelGGL(truss::DegreesKernel, dim3(Grid(n + 1)), dim3(256), 0, stream, d_up, d_low, n, d_deg);
+                    GR_CHECK(hipGetLastError(), "DegreesKernel launch failed");
+                    GR_CHECK(graphio::DeviceExclusiveScan<int>(d_deg, ds->d_nro, n + 1, d_sums, stream), "MaxflowProblem offset scan failed");
+                    hipLaunchKernelGGL(truss::FillRowsKernel, dim3(Grid(M)), dim3(256), 0, stream, d_ckeys, d_skeys, M, col_bits, d_up, d_low, ds->d_nro,
+                                       ds->d_nci, ds->d_neid);
+                    GR_CHECK(hipGetLastError(), "FillRowsKernel launch failed");
+
+                    // the capacities: every arc finds its entry by bisecting the sorted row (the key sort carries no payload) and adds
+                    // in 64 bits; then a pair's two sums must fit one int together
+                    GR_CHECK(hipMalloc(&d_cap64, sizeof(unsigned long long) * 2 * ms), "MaxflowProblem hipMalloc failed");
+                    GR_CHECK(hipMemsetAsync(d_cap64, 0, sizeof(unsigned long long) * 2 * ms, stream), "MaxflowProblem memset failed");
+                    GR_CHECK(hipMalloc(&ds->d_mate, sizeof(int) * 2 * ms), "MaxflowProblem hipMalloc d_mate failed");
+                    GR_CHECK(hipMalloc(&ds->d_cap, sizeof(int) * 2 * ms), "MaxflowProblem hipMalloc d_cap failed");
+                    GR_CHECK(hipMalloc(&ds->d_res, sizeof(int) * 2 * ms), "MaxflowProblem hipMalloc d_res failed");
+                    GR_CHECK(hipMalloc(&ds->d_cap_ab, sizeof(int) * ms), "MaxflowProblem hipMalloc failed");
+                    GR_CHECK(hipMalloc(&ds->d_cap_ba, sizeof(int) * ms), "MaxflowProblem hipMalloc failed");
+                    GR_CHECK(hipMalloc(&ds->d_pent, sizeof(int) * ms), "MaxflowProblem hipMalloc failed");
+                    hipLaunchKernelGGL(AccumulateKernel, dim3(Grid(m)), dim3(256), 0, stream, gs->d_row_offsets, gs->d_column_indices, gs->d_edge_values,
+                                       static_cast<int>(n), m, ds->d_nro, ds->d_nci, d_cap64, ds->d_words + W_BAD);
+                    GR_CHECK(hipGetLastError(), "AccumulateKernel launch failed");
+                    hipLaunchKernelGGL(PairEntriesKernel, dim3(Grid(M)), dim3(256), 0, stream, ds->d_a, ds->d_b, M, ds->d_nro, ds->d_nci, d_cap64, ds->d_pent,
+                                       ds->d_mate, ds->d_cap, ds->d_cap_ab, ds->d_cap_ba, ds->d_words + W_BAD);
+                    GR_CHECK(hipGetLastError(), "PairEntriesKernel launch failed");
+                } else {
+                    // (self-loops only: their capacities are still looked at)
+                    hipLaunchKernelGGL(AccumulateKernel, dim3(Grid(m)), dim3(256), 0, stream, gs->d_row_offsets, gs->d_column_indices, gs->d_edge_values,
+                                       static_cast<int>(n), m, ds->d_nro, ds->d_nci, d_cap64, ds->d_words + W_BAD);
+                    GR_CHECK(hipGetLastError(), "AccumulateKernel launch failed");
+                }
+                unsigned bad_cap = 0;
+                GR_CHECK(hipMemcpyAsync(&bad_cap, ds->d_words + W_BAD, sizeof(bad_cap), hipMemcpyDeviceToHost, stream), "MaxflowProblem read-back failed");
+                GR_CHECK(hipStreamSynchronize(stream), "MaxflowProblem read-back sync failed");
+                if (bad_cap) {
+                    malformed = 1;
+                    return hipErrorInvalidValue;
+                }
+            }
+            pairs = M;
+            GR_CHECK(hipEventRecord(ev[1], stream), "MaxflowProblem hipEventRecord failed");
+            GR_CHECK(hipStreamSynchronize(stream), "MaxflowProblem build sync failed");
+            float ms = 0;
+            GR_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]), "MaxflowProblem hipEventElapsedTime failed");
+            build_ms = ms;
+            return retval;
+        };
+        retval = run();
+        release();
+        if (retval) return retval;
+
+        const size_t m1 = static_cast<size_t>(M > 0 ? M : 1);
+        int **vertex_arrays[] = {&ds->d_height, &ds->d_queue, &ds->d_mark, &ds->d_list[0], &ds->d_list[1], &ds->d_fwd, &ds->d_bwd};
+        for (int **a : vertex_arrays) GR_CHECK(hipMalloc(a, sizeof(int) * n1), "MaxflowProblem hipMalloc failed");
+        GR_CHECK(hipMalloc(&ds->d_excess, sizeof(long long) * n1), "MaxflowProblem hipMalloc failed");
+        GR_CHECK(hipMalloc(&ds->d_side, n1), "MaxflowProblem hipMalloc failed");
+        GR_CHECK(hipMalloc(&ds->d_flow, sizeof(int) * m1), "MaxflowProblem hipMalloc failed");
+        GR_CHECK(hipMalloc(&ds->d_cut, m1), "MaxflowProblem hipMalloc failed");
+        GR_CHECK(hipMalloc(&ds->d_arc_flow, sizeof(int) * static_cast<size_t>(m > 0 ? m : 1)), "MaxflowProblem hipMalloc failed");
+        return retval;
+    }
+
+    // One Init per object (grx_maxflow_init refuses a second one)
+    hipError_t Init(bool stream_from_host, const Csr<int, int, int> &graph, int num_gpus = 1)
+    {
+        hipError_t retval = hipSuccess;
+        if ((retval = Base::Init(stream_from_host, graph, num_gpus, true))) return retval;
+        data_slices = new DataSlice *[1];
+        data_slices[0] = new DataSlice();
+        return Build();
+    }
+
+    hipError_t InitFromDevice(int nodes, int edges, int *d_row_offsets, int *d_column_indices, int *d_capacities)
+    {
+        hipError_t retval = hipSuccess;
+        if ((retval = Base::InitFromDevice(nodes, edges, d_row_offsets, d_column_indices, d_capacities))) return retval;
+        data_slices = new DataSlice *[1];
+        data_slices[0] = new DataSlice();
+        return Build();
+    }
+
+    // the residuals back at the capacities; excess, heights, marks, words and counters at 0.  The caller has checked the pair.
+    hipError_t Reset(int new_src, int new_sink)
+    {
+        hipError_t retval = hipSuccess;
+        DataSlice *ds = data_slices[0];
+        hipStream_t stream = this->graph_slices[0]->stream;
+        const size_t n = static_cast<size_t>(this->nodes), M = static_cast<size_t>(pairs);
+        src = new_src;
+        sink = new_sink;
+        GR_CHECK(hipMemsetAsync(ds->d_words, 0, sizeof(unsigned) * W_COUNT, stream), "MaxflowProblem memset failed");
+        GR_CHECK(hipMemsetAsync(ds->d_counters, 0, sizeof(unsigned long long) * C_COUNT, stream), "MaxflowProblem memset failed");
+        GR_CHECK(hipMemsetAsync(ds->d_clock, 0, sizeof(unsigned long long) * (PHASE_COUNT + 1), stream), "MaxflowProblem memset failed");
+        GR_CHECK(hipMemsetAsync(ds->d_excess, 0, sizeof(long long) * n, stream), "MaxflowProblem memset failed");
+        GR_CHECK(hipMemsetAsync(ds->d_height, 0, sizeof(int) * n, stream), "MaxflowProblem memset failed");
+        GR_CHECK(hipMemsetAsync(ds->d_mark, 0, sizeof(int) * n, stream), "MaxflowProblem memset failed");
+        if (M) GR_CHECK(hipMemcpyAsync(ds->d_res, ds->d_cap, sizeof(int) * 2 * M, hipMemcpyDeviceToDevice, stream), "MaxflowProblem copy failed");
+        GR_CHECK(hipStreamSynchronize(stream), "MaxflowProblem Reset sync failed");
+        fresh = true;
+        enacted = false;
+        have_arc_flow = false;
+        summary = Summary();
+        return retval;
+    }
+
+    template <typename T>
+    hipError_t Read(T *h_out, const T *d_in, size_t count)
+    {
+        hipError_t retval = hipSuccess;
+        hipStream_t stream = this->graph_slices[0]->stream;
+        if (h_out && count) {
+            GR_CHECK(hipMemcpyAsync(h_out, d_in, sizeof(T) * count, hipMemcpyDeviceToHost, stream), "MaxflowProblem read failed");
+            GR_CHECK(hipStreamSynchronize(stream), "MaxflowProblem read sync failed");
+        }
+        return retval;
+    }
+
+    // every pointer may be NULL
+    hipError_t Pairs(int *h_a, int *h_b, int *h_cap_ab, int *h_cap_ba)
+    {
+        hipError_t retval = hipSuccess;
+        DataSlice *ds = data_slices[0];
+        const size_t M = static_cast<size_t>(pairs);
+        if ((retval = Read(h_a, ds->d_a, M))) return retval;
+        if ((retval = Read(h_b, ds->d_b, M))) return retval;
+        if ((retval = Read(h_cap_ab, ds->d_cap_ab, M))) return retval;
+        return Read(h_cap_ba, ds->d_cap_ba, M);
+    }
+
+    hipError_t Extract(int *h_flow, unsigned char *h_side, unsigned char *h_cut)
+    {
+        hipError_t retval = hipSuccess;
+        DataSlice *ds = data_slices[0];
+        const size_t n = static_cast<size_t>(this->nodes), M = static_cast<size_t>(pairs);
+        if ((retval = Read(h_flow, ds->d_flow, M))) return retval;
+        if ((retval = Read(h_side, ds->d_side, n))) return retval;
+        return Read(h_cut, ds->d_cut, M);
+    }
+
+    // arc_flow[] per input entry: a function of the residuals and the input, computed once per Enact
+    hipError_t ArcFlow(int *h_arc_flow)
+    {
+        hipError_t retval = hipSuccess;
+        DataSlice *ds = data_slices[0];
+        GraphSlice<int, int, int> *gs = this->graph_slices[0];
+        const long long m = this->edges;
+        if (m < 1) return retval;
+        if (!have_arc_flow) {
+            if (pairs > 0) {
+                hipLaunchKernelGGL(ArcFlowKernel, dim3(Grid(m)), dim3(256), 0, gs->stream, gs->d_row_offsets, gs->d_column_indices, gs->d_edge_values,
+                                   static_cast<int>(this->nodes), m, ds->d_nro, ds->d_nci, ds->d_cap, ds->d_res, ds->d_arc_flow);
+                GR_CHECK(hipGetLastError(), "ArcFlowKernel launch failed");
+            } else {
+                GR_CHECK(hipMemsetAsync(ds->d_arc_flow, 0, sizeof(int) * static_cast<size_t>(m), gs->stream), "MaxflowProblem memset failed");
+            }
+            have_arc_flow = true;
+        }
+        return Read(h_arc_flow, ds->d_arc_flow, static_cast<size_t>(m));
+    }
+};
+
+}  // namespace maxflow
+}  // namespace app
+}  // namespace gunrock

@@ -741,6 +741,92 @@ int grx_bcc_device_results(grx_bcc *p, int **d_bcc, int **d_tecc, unsigned char 
 void grx_bcc_destroy(grx_bcc *p);
 
 /* ------------------------------------------------------------------------------------------------
+ * Maximum flow and minimum cut: MaxflowProblem + MaxflowEnactor in app/maxflow/{maxflow_problem,maxflow_enactor,maxflow_functor}.hpp
+ * (push-relabel: Goldberg and Tarjan, J. ACM 1988, with the global relabelling of Cherkassky and Goldberg, Algorithmica 1997; the
+ * reference snapshot has no counterpart, later Gunrock releases ship `mf`).  The CSR is read as a directed multigraph with int32
+ * capacities (NULL: 1 each): rows may be unsorted, self-loops are ignored, parallel arcs u -> v add up, u -> v and v -> u are
+ * different arcs, so a symmetric CSR is an undirected network.  The M canonical pairs are the distinct {a < b} with an arc in either
+ * direction (capacity 0 included), sorted by (a, b); pair p has cap_ab[p] and cap_ba[p], each the 64-bit sum of its direction, and
+ * every per-pair array is indexed by p.  The results of Enact for (src, sink):
+ *   value       the maximum flow (int64)
+ *   side[v]     0: v is reachable from src in the residual graph of the final flow; 2: sink is reachable from v; 1: neither (uint8,
+ *               `nodes` entries).  The sets 0 and 2 are the smallest and the largest source side of a minimum cut: one value each
+ *   cut[p]      bit 0: positive capacity from a side-0 end to an end that is not side 0; bit 1: positive capacity from an end that
+ *               is not side 2 to a side-2 end (uint8, M entries).  The capacities under either bit sum to value
+ *   flow[p]     the net flow a -> b (negative: b -> a), -cap_ba[p] <= flow[p] <= cap_ab[p], conserved at every vertex but src and
+ *               sink (int32, M entries).  Not unique: it depends on the run.  It is a valid maximum flow every time
+ *   arc_flow[e] per CSR entry: a pair's net flow in a direction goes to that direction's entries in CSR order, each filled to its
+ *               capacity before the next; entries of the other direction and self-loops get 0 (int32).  A function of flow[] and
+ *               the input
+ *   summary     value, the sizes of side 0, side 1 and side 2, the pairs with cut bit 0, the pairs with cut bit 1
+ * Init builds the residual graph (a symmetric CSR over the pairs with the reverse entry on every entry); Enact runs the preflow
+ * phase, the return phase and the cut, and reports only a flow it has certified on the device: no excess outside src and sink, and
+ * sink not reachable from src.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct grx_maxflow grx_maxflow;
+enum { GRX_MAXFLOW_AUTO = 0, GRX_MAXFLOW_ROUNDS = 1, GRX_MAXFLOW_DEVICE_LOOP = 2 };
+enum { GRX_MAXFLOW_PHASE_PREFLOW = 0, GRX_MAXFLOW_PHASE_RETURN = 1, GRX_MAXFLOW_PHASE_CUT = 2 }; /* the kinds of grx_maxflow_phase_trace */
+enum { GRX_MAXFLOW_GAVE_UP = -4 }; /* grx_maxflow_enact: more than "max_rounds" rounds; next to -1 / -2 / -3 */
+
+/* (no counterpart in the reference snapshot: this call and the ones below are shaped like grx_bcc_*) */
+int grx_maxflow_create(grx_maxflow **out, int instrument, int device);
+/* MaxflowProblem::Init: validates the CSR and builds the pairs and the residual graph on the device (no counterpart in the reference
+ * snapshot).  -1: nodes < 1, nodes > 2^30, edges < 0 or a NULL array; -2: not a CSR of `nodes` vertices, a negative capacity, or a
+ * pair with cap_ab + cap_ba > 2^31 - 1 (one int32 residual per direction holds the whole pair); -3: the handle has been given a
+ * graph before (accepted or rejected) */
+int grx_maxflow_init(grx_maxflow *p, int nodes, int edges, const int *row_offsets, const int *col_indices, const int *capacities);
+/* the same for a CSR already in HBM (borrowed, not freed: it must outlive the handle, grx_maxflow_arc_flow reads it; no counterpart
+ * in the reference snapshot) */
+int grx_maxflow_init_device(grx_maxflow *p, int nodes, int edges, int *d_row_offsets, int *d_col_indices, int *d_capacities);
+/* 0: set; 1: unknown name; -1: a value out of range (no counterpart in the reference snapshot).  No option changes a unique result.
+ *   "schedule"          GRX_MAXFLOW_AUTO (default): a stretch of narrow steps (rounds, search levels) is one loop launch on the
+ *                       device, a wide step is a launch of its own; GRX_MAXFLOW_ROUNDS: every step is a launch and a read-back;
+ *                       GRX_MAXFLOW_DEVICE_LOOP: every step runs in the one-workgroup loop
+ *   "wave_min_row"      rows of at least this many entries are walked by a whole wave (default 16, >= 1)
+ *   "discharge_steps"   pushes or relabels of one vertex per round (default 4, 1 .. 1024)
+ *   "relabel_interval"  a global relabel after this many relabels, as a multiple of `nodes` (default 0.1, >= 0; 0: after every
+ *                       round that relabelled; 1e18: never again after the first of a phase)
+ *   "max_rounds"        Enact stops with GRX_MAXFLOW_GAVE_UP behind this many rounds (default 4000000, 1 .. 2^30)
+ *   "loop_max_list"     under AUTO the device loop takes a step of at most this many vertices (default 32768, not tuned)
+ *   "loop_max_entries"  ... whose rows hold at most this many entries (default 8192, not tuned) */
+int grx_maxflow_set_option(grx_maxflow *p, const char *name, double value);
+/* MaxflowProblem::Reset (no counterpart in the reference snapshot): the residuals back at the capacities, excess and heights cleared.
+ * -1: src or sink outside [0, nodes), or src == sink */
+int grx_maxflow_reset(grx_maxflow *p, int src, int sink);
+/* MaxflowEnactor::Enact(problem, max_grid_size), HIP-event timed (no counterpart in the reference snapshot).  Without a Reset since
+ * the last Enact it resets to the last pair; before any Reset: hipErrorNotReady.  GRX_MAXFLOW_GAVE_UP: the rounds passed
+ * "max_rounds" (or the certificate failed 64 times); the handle then holds no result and takes the next Reset */
+int grx_maxflow_enact(grx_maxflow *p, int max_grid_size, float *elapsed_ms);
+/* of the last Enact, any pointer may be NULL (no counterpart in the reference snapshot): M, the discharge rounds, the global
+ * relabels, pushes and relabels (both depend on the schedule), row entries walked, kernel launches, host read-backs and -- when
+ * instrumented -- the summed kernel time; build_ms: the HIP-event time of Init's build.  The one-thread launches that stamp the
+ * phase trace and the memsets of an Enact are in neither kernel_launches nor kernel_ms */
+int grx_maxflow_stats(grx_maxflow *p, long long *pairs, long long *rounds, long long *global_relabels, long long *pushes, long long *relabels,
+                      long long *entries_read, long long *kernel_launches, long long *readbacks, double *kernel_ms, double *build_ms);
+/* the three phases of the last Enact in order, at most max_phases of them (no counterpart in the reference snapshot): the kind
+ * (GRX_MAXFLOW_PHASE_*), the rounds it ran (the cut: its search levels) and its time by the device's constant-rate counter, both
+ * summed over the trips a failed certificate caused; returns the number of phases (0 before the first Enact) */
+int grx_maxflow_phase_trace(grx_maxflow *p, int max_phases, int *kind, long long *rounds, double *ms);
+/* the canonical pairs and their capacities (any pointer may be NULL); returns M or a negated hipError_t; valid after init (no
+ * counterpart in the reference snapshot) */
+long long grx_maxflow_pairs(grx_maxflow *p, int *h_a, int *h_b, int *h_cap_ab, int *h_cap_ba);
+/* the results of the last Enact; every pointer may be NULL.  Before a finished Enact: hipErrorNotReady (no counterpart in the
+ * reference snapshot) */
+int grx_maxflow_extract(grx_maxflow *p, long long *value, int *h_flow, unsigned char *h_side, unsigned char *h_cut);
+/* arc_flow[] of the last Enact, `edges` entries, computed at the first call behind an Enact.  Before a finished Enact:
+ * hipErrorNotReady (no counterpart in the reference snapshot) */
+int grx_maxflow_arc_flow(grx_maxflow *p, int *h_arc_flow);
+/* value, |side 0|, |side 1|, |side 2|, pairs with cut bit 0, pairs with cut bit 1.  Before a finished Enact: hipErrorNotReady (no
+ * counterpart in the reference snapshot) */
+int grx_maxflow_summary(grx_maxflow *p, long long out[6]);
+/* device arrays of the handle (no counterpart in the reference snapshot): flow (M int32), side (`nodes` uint8), cut (M uint8), the
+ * canonical pairs (M int32 each), excess (`nodes` int64: sink's is value, src's is -value) and height (`nodes` int32: the labels of
+ * the return phase, not unique) */
+int grx_maxflow_device_results(grx_maxflow *p, int **d_flow, unsigned char **d_side, unsigned char **d_cut, int **d_a, int **d_b,
+                               long long **d_excess, int **d_height);
+void grx_maxflow_destroy(grx_maxflow *p);
+
+/* ------------------------------------------------------------------------------------------------
  * SSSP: SSSPProblem + SSSPEnactor (reference gunrock/app/sssp/sssp_problem.cuh:35-387, sssp_enactor.cuh:36-563)
  * ---------------------------------------------------------------------------------------------- */
 typedef struct grx_sssp grx_sssp;
