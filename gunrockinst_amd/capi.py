@@ -113,6 +113,8 @@ _SIGNATURES = {
     "grx_bfs_extract": (C.c_int, [C.c_void_p, i32p, i32p]),
     "grx_bfs_device_results": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "grx_bfs_mask_flushes": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
+    "grx_bfs_stream_idle": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "grx_bfs_fused_publications": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
     "grx_bfs_relabel_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_int),
                                        C.POINTER(C.c_float), C.POINTER(C.c_longlong)]),
     "grx_bfs_destroy": (None, [C.c_void_p]),
@@ -585,6 +587,18 @@ class BfsProblem(_Handle):
         v = C.c_longlong()
         _check(lib().grx_bfs_mask_flushes(self._h, C.byref(v)), "grx_bfs_mask_flushes")
         return v.value
+
+    def fused_publications(self):
+        """read-backs a label pass published for the enactor (option fused_publish), over the handle's life"""
+        v = C.c_longlong()
+        _check(lib().grx_bfs_fused_publications(self._h, C.byref(v)), "grx_bfs_fused_publications")
+        return v.value
+
+    def stream_idle(self):
+        """True when nothing is queued or running on the handle's stream (always so right after enact)"""
+        v = C.c_int()
+        _check(lib().grx_bfs_stream_idle(self._h, C.byref(v)), "grx_bfs_stream_idle")
+        return bool(v.value)
 
     def relabel_info(self):
         """The relabelled copy of a symmetric problem: hub-tier size (-1 = no copy), vertices with edges, hub degree

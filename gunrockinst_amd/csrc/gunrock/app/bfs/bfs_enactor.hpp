@@ -40,6 +40,8 @@ class BFSEnactor : public EnactorBase {
         kernel_ms = enactor_stats.kernel_ms;
     }
 
+    long long FusedPublications() const { return fused_publications; }
+
     const std::vector<EnactorStats::LevelRecord> &GetLevelTrace() const { return enactor_stats.levels; }
 
     void GetStatistics(long long &total_queued, long long &search_depth, double &avg_duty)
@@ -80,9 +82,12 @@ class BFSEnactor : public EnactorBase {
     //                 1 = the reference's TWC choice for low-degree graphs: TWC workgroup for small frontiers
     //                     (oprtr/advance/twc.hpp), persistent mid-size levels, LB advance for the rest;
     //                 2 = direction-optimizing (reference app/dobfs): needs BFSProblem::SetInverseGraph.
+    // completion: an event of the caller's that Enact records behind the last kernel it queues and waits for before it
+    //             returns (a runner's stop event: handle_runner.hpp EventPair::TimedLent).  Without one Enact waits for the
+    //             stream when a kernel may still run behind its last read-back.
     template <typename BFSProblem>
     hipError_t Enact(util::DeviceContext & /*context*/, BFSProblem *problem, typename BFSProblem::VertexId src,
-                     int max_grid_size = 0, int traversal_mode = 0)
+                     int max_grid_size = 0, int traversal_mode = 0, hipEvent_t completion = nullptr)
     {
         // The reference's driver picks mode 1 (TWC) for graphs of average degree <= 8 (tests/bfs/test_bfs.cu:563-566): long
         // runs of small levels.  Here that case is served by the TWC workgroup and the persistent levels kernel, enabled by
@@ -90,10 +95,34 @@ class BFSEnactor : public EnactorBase {
         const bool low_degree = static_cast<long long>(problem->edges) <= 8ll * problem->nodes;
         return EnactBFS<LBAdvancePolicy, BFSProblem>(problem, src, max_grid_size,
                                                      traversal_mode == 2 && problem->direction_optimizing,
-                                                     traversal_mode == 1 || low_degree);
+                                                     traversal_mode == 1 || low_degree, completion);
     }
 
    protected:
+    // ---- the read-back a tiled label pass carries (bfs_problem.hpp TiledLabelsKernel, frontier.hpp PublishBody) ----
+    // Behind the launch that usually ends a search the label pass is queued before the host knows how the search ended.  Every
+    // word of the read-back that tells it is final before that pass starts, so the pass's workgroup 0 publishes them and the
+    // host replays its rules -- and the completion event is recorded -- while the tiles are still being written.
+    bool fuse_publish = false;              // this Enact hands its closing read-back to a queued tiled pass (option fused_publish)
+    hipEvent_t completion_event = nullptr;  // lent for one Enact
+    bool completion_recorded = false;       // ... and recorded behind the last kernel queued so far
+    bool pass_pending = false;              // a label pass may still be running behind the last read-back
+    long long fused_publications = 0;       // read-backs handed to a label pass, over the enactor's life (tests: the path was taken)
+    hipError_t MarkPassQueued(hipStream_t stream)
+    {
+        ++fused_publications;
+        pass_pending = true;
+        if (!completion_event) return hipSuccess;
+        completion_recorded = true;
+        return util::GRError(hipEventRecord(completion_event, stream), "BFSEnactor hipEventRecord failed", __FILE__, __LINE__);
+    }
+    // the search queues more kernels: whatever was recorded is no longer behind the last of them (recording again later wins)
+    void SearchGoesOn()
+    {
+        completion_recorded = false;
+        pass_pending = false;  // (every later read-back follows the pass on the stream)
+    }
+
     // Launch the multi-level tail kernel on queue[selector] (its length lives in ring slot iteration & 3), wait, and
     // bring the host's view (iteration, selector, frontier size, statistics) up to date.
     // `persistent`: use the multi-workgroup kernel with a grid barrier (mid-size frontiers) instead of the single workgroup;
@@ -152,9 +181,16 @@ class BFSEnactor : public EnactorBase {
             return retval;
         // closing = this launch usually ends the search (the levels after the return to top-down): the deferred labels' emit pass
         // is queued behind it without waiting for the read-back that confirms it -- one host round trip less per search
-        if (closing && (retval = problem->EmitLabelsSpeculative(stream))) return retval;
+        bool fused = false;  // the pass publishes this launch's read-back
+        if (closing) {
+            util::PublishArgs publish;
+            fused = fuse_publish && problem->TiledPassReady(0);
+            if (fused && (retval = work_progress.Post(stream, 0u, 0u, &publish))) return retval;
+            if ((retval = problem->EmitLabelsSpeculative(stream, fused ? &publish : nullptr))) return retval;
+            if (fused && (retval = MarkPassQueued(stream))) return retval;
+        }
         if (INSTRUMENT && (retval = InstrumentEnd(stream))) return retval;
-        if ((retval = work_progress.GetAll(stream))) return retval;
+        if ((retval = fused ? work_progress.Wait(stream) : work_progress.GetAll(stream))) return retval;
         if (persistent && work_progress.HostBarrierTimedOut())
             return util::GRError(hipErrorLaunchTimeOut, "BFSEnactor persistent levels kernel: grid barrier timed out", __FILE__,
                                  __LINE__);
@@ -171,9 +207,32 @@ class BFSEnactor : public EnactorBase {
         return retval;
     }
 
+    // The search, then the wait for whatever it left running behind its last read-back.
     template <typename AdvancePolicy, typename BFSProblem>
     hipError_t EnactBFS(BFSProblem *problem, typename BFSProblem::VertexId src, int max_grid_size, bool dobfs,
-                        bool persistent_levels)
+                        bool persistent_levels, hipEvent_t completion = nullptr)
+    {
+        hipStream_t stream = problem->graph_slices[0]->stream;
+        fuse_publish = !INSTRUMENT && problem->fused_publish != 0;  // (the instrumented enactor attributes time per kernel)
+        completion_event = completion;
+        completion_recorded = false;
+        pass_pending = false;
+        const hipError_t retval = SearchBFS<AdvancePolicy, BFSProblem>(problem, src, max_grid_size, dobfs, persistent_levels);
+        hipError_t rc = hipSuccess;
+        if (completion) {
+            if (!completion_recorded) rc = util::GRError(hipEventRecord(completion, stream), "BFSEnactor hipEventRecord failed", __FILE__, __LINE__);
+            if (!rc) rc = util::GRError(hipEventSynchronize(completion), "BFSEnactor hipEventSynchronize failed", __FILE__, __LINE__);
+        } else if (pass_pending) {
+            rc = util::GRError(hipStreamSynchronize(stream), "BFSEnactor hipStreamSynchronize failed", __FILE__, __LINE__);
+        }
+        completion_event = nullptr;
+        pass_pending = false;
+        return retval ? retval : rc;
+    }
+
+    template <typename AdvancePolicy, typename BFSProblem>
+    hipError_t SearchBFS(BFSProblem *problem, typename BFSProblem::VertexId src, int max_grid_size, bool dobfs,
+                         bool persistent_levels)
     {
         typedef typename BFSProblem::VertexId VertexId;
         typedef typename BFSProblem::SizeT SizeT;
@@ -187,7 +246,10 @@ class BFSEnactor : public EnactorBase {
         GraphSlice<VertexId, SizeT, Value> *gs = problem->graph_slices[0];
         typename BFSProblem::DataSlice *ds = problem->data_slices[0];
         hipStream_t stream = gs->stream;
-        if (src < 0 || src >= problem->nodes) return problem->FinishSearch(stream);
+        if (src < 0 || src >= problem->nodes) {
+            pass_pending = true;
+            return problem->FinishSearch(stream);
+        }
         // deferred labels (bfs_problem.hpp): vertex-ordered sweeps keep their output bitmap instead of storing labels
         const bool deferring = dobfs && problem->labels_deferred;
         ds->defer_labels = deferring ? 1 : 0;
@@ -400,7 +462,7 @@ class BFSEnactor : public EnactorBase {
             //      chain's bitmaps were filled.  Otherwise both exit at once and the host carries on as before. ----
             const bool closing_queued = problem->chain_closing && problem->persistent_edge_limit > 0;
             int *d_gate = work_progress.d_chain_log + 8;
-            bool emit_queued = false;
+            bool emit_queued = false, fused = false;  // fused: the label pass publishes this chain's read-back
             if (closing_queued) {
                 oprtr::advance::PersistentArgs<VertexId, SizeT> p;
                 p.t.queue[0] = gs->frontier_queues[0];
@@ -434,12 +496,16 @@ class BFSEnactor : public EnactorBase {
                 if (deferring && problem->speculative_emit && problem->level_masks.count + queued <= app::bfs::kLevelMasks) {
                     VertexId labels[oprtr::advance::kChainMax];
                     for (int k = 1; k <= queued; ++k) labels[k - 1] = static_cast<VertexId>(it0 + k);
-                    if ((rc = problem->EmitLabelsGated(stream, masks + 1, labels, queued, d_gate))) return rc;
+                    util::PublishArgs publish;
+                    fused = fuse_publish && problem->TiledPassReady(queued);
+                    if (fused && (rc = work_progress.Post(stream, 0u, 0u, &publish))) return rc;
+                    if ((rc = problem->EmitLabelsGated(stream, masks + 1, labels, queued, d_gate, fused ? &publish : nullptr))) return rc;
                     emit_queued = true;
+                    if (fused && (rc = MarkPassQueued(stream))) return rc;
                 }
             }
             if (INSTRUMENT && (rc = InstrumentEnd(stream))) return rc;
-            if ((rc = work_progress.Sync(stream))) return rc;
+            if ((rc = fused ? work_progress.Wait(stream) : work_progress.Sync(stream))) return rc;
             // ---- replay (the same SweepRule on the same numbers) ----
             long long total = base_total;
             int ran = 0, last_action = oprtr::advance::kSweepStop;
@@ -468,6 +534,7 @@ class BFSEnactor : public EnactorBase {
             if (queue_emitted && work_progress.h_tail[util::WorkProgress::kAux] != 0) {  // a staging buffer overflowed: no usable queue
                 queue_emitted = false;
                 if ((rc = work_progress.ClearAux(stream))) return rc;
+                SearchGoesOn();  // (something is queued behind the read-back: whatever was recorded no longer closes the stream)
             }
             if (INSTRUMENT) InstrumentCollect(static_cast<long long>(first_in >= 0 ? first_in : 0), 0, 1);
             // ---- did the closing levels run?  (the kernel's own test, replayed) ----
@@ -537,6 +604,7 @@ class BFSEnactor : public EnactorBase {
             return util::GRError("BitmapDiffKernel launch failed", __FILE__, __LINE__);
         };
         while (queue_length > 0) {
+            SearchGoesOn();
             const unsigned in_len = queue_length, in_edges = queue_edges;
             bool binned_level = false;
             if (INSTRUMENT && (retval = InstrumentBegin(stream))) break;
@@ -805,7 +873,12 @@ class BFSEnactor : public EnactorBase {
         // ran on the relabelled copy)
         if (problem->labels_deferred || problem->translate_pending) {
             if (INSTRUMENT && (retval = InstrumentBegin(stream))) return retval;
-            if ((retval = problem->FinishSearch(stream))) return retval;
+            bool launched = false;
+            if ((retval = problem->FinishSearch(stream, &launched))) return retval;
+            if (launched) {  // a pass of its own (no speculative one stands), and no read-back behind it
+                SearchGoesOn();
+                pass_pending = true;
+            }
             if (INSTRUMENT) {
                 if ((retval = InstrumentEnd(stream))) return retval;
                 if ((retval = util::GRError(hipStreamSynchronize(stream), "BFSEnactor EmitLabels sync failed", __FILE__, __LINE__))) return retval;
@@ -814,7 +887,8 @@ class BFSEnactor : public EnactorBase {
         }
         if (INSTRUMENT && (retval = DutyCollect(stream))) return retval;
 
-        // (the loop's last read-back followed its last kernel, and SetTail cleared the flag of the previous search)
+        // (the only kernel behind the loop's last read-back is a label pass, which overflows nothing, and SetTail cleared the flag
+        //  of the previous search)
         const bool overflow = work_progress.OverflowAtLastSync();
         if (overflow) {
             // same diagnosis as bfs_enactor.cuh:540-545

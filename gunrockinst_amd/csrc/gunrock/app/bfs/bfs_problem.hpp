@@ -24,6 +24,7 @@
 #include <gunrock/graphio/relabel.hpp>
 #include <gunrock/oprtr/advance/binned.hpp>
 #include <gunrock/oprtr/advance/bottom_up.hpp>
+#include <gunrock/util/frontier.hpp>
 #include <gunrock/util/memset_kernel.hpp>
 
 namespace gunrock {
@@ -371,9 +372,14 @@ template <typename VertexId, bool RELABEL, bool PRED>
 __global__ __launch_bounds__(256) void TiledLabelsKernel(LevelMaskList<VertexId> levels, const unsigned long long *d_visited,
                                                          const unsigned long long *d_never, graphio::RelabelView map, long long nodes,
                                                          VertexId src, const VertexId *d_work_labels, const VertexId *d_work_preds,
-                                                         const VertexId *d_old_of_new, VertexId *d_labels, VertexId *d_preds)
+                                                         const VertexId *d_old_of_new, VertexId *d_labels, VertexId *d_preds,
+                                                         util::PublishArgs publish)
 {
     typedef __attribute__((ext_vector_type(4))) int V4;
+    // The enactor's closing read-back rides on this pass (frontier.hpp PublishBody): every word it mirrors was final before
+    // the pass started and the pass reads none of the words it re-arms, so the host learns how the search ended while the
+    // tiles are still being written.  First of all, before the gate: a pass that does not run must still publish.
+    if (publish.box && blockIdx.x == 0 && threadIdx.x < 64) util::PublishBody(publish);  // (uniform per wave; only read)
     __shared__ LabelPlanes planes[2][2 * kLabelSpan];  // [0]: tier 1 (or the caller's numbering), [1]: tier 0; per 32-bit half
     __shared__ uint2 s_tier[2][2 * kLabelTileWords];   // per half of a caller word: (tier mask, new id of its first tier vertex)
     __shared__ int table[16];
@@ -1007,6 +1013,8 @@ struct BFSProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
     int label_pass = 1;             // policy, read at every launch: 1 the tiled closing pass (TiledLabelsKernel), 0 the per-lane kernels
     int walk_queue = 1;             // policy, read at every launch: 1 the dense bottom-up sweep queues its row walks per wave (bottom_up.hpp
                                     // DenseSweepQueued), 0 it walks them step by step (DenseSweep)
+    int fused_publish = 1;          // policy, read at every Enact: 1 the read-back behind a queued tiled label pass is published by that pass
+                                    // (workgroup 0, frontier.hpp PublishBody), 0 by a PublishKernel behind it
     int level_mask_limit = kLevelMasks;  // bitmaps of the pool a search may use (tests shrink it to force mid-search flushes)
     LevelMaskList<VertexId> level_masks; // (bitmap, label) of every kept level
     int mask_ring = 0;
@@ -1059,10 +1067,13 @@ struct BFSProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
         level_masks.label[level_masks.count] = label;
         ++level_masks.count;
     }
+    // publish: the enactor's pending read-back, carried by the tiled pass (TiledPassReady says beforehand whether the launch
+    // will be one); every other kernel here ignores it
     template <bool FULL>
-    hipError_t LaunchEmit(hipStream_t stream, VertexId src)
+    hipError_t LaunchEmit(hipStream_t stream, VertexId src, const util::PublishArgs *publish = nullptr)
     {
         DataSlice *ds = data_slices[0];
+        const util::PublishArgs carried = (FULL && publish) ? *publish : util::PublishArgs();
         long long grid = ((static_cast<long long>(this->nodes) + 3) / 4 + 255) / 256;  // one quad of vertices per thread
         if (grid > (1 << 20)) grid = 1 << 20;
         if (grid < 1) grid = 1;
@@ -1088,11 +1099,11 @@ struct BFSProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
             if (copy) {
                 const VertexId csrc = (caller_source >= 0 && caller_source < this->nodes) ? caller_source : static_cast<VertexId>(-1);
                 hipLaunchKernelGGL((TiledLabelsKernel<VertexId, true, MARK_PREDECESSORS>), tg, b, 0, stream, list, vis, nev, relabelled.View(), n, csrc,
-                                   d_work_labels, d_work_preds, relabelled.d_old_of_new, d_out_labels, d_out_preds);
+                                   d_work_labels, d_work_preds, relabelled.d_old_of_new, d_out_labels, d_out_preds, carried);
                 translate_pending = false;
             } else {
                 hipLaunchKernelGGL((TiledLabelsKernel<VertexId, false, false>), tg, b, 0, stream, list, vis, nev, graphio::RelabelView(), n, src,
-                                   ds->d_labels, nullptr, nullptr, ds->d_labels, nullptr);
+                                   ds->d_labels, nullptr, nullptr, ds->d_labels, nullptr, carried);
             }
             level_masks.count = 0;
             return util::GRError(hipGetLastError(), "TiledLabelsKernel launch failed", __FILE__, __LINE__);
@@ -1124,6 +1135,11 @@ struct BFSProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
         level_masks.count = 0;
         return util::GRError(hipGetLastError(), "EmitLabelsKernel launch failed", __FILE__, __LINE__);
     }
+    // Would EmitLabelsGated (with `extra` chain bitmaps) or EmitLabelsSpeculative (extra = 0) queue the tiled pass now?
+    bool TiledPassReady(int extra) const
+    {
+        return labels_deferred && speculative_emit && label_pass != 0 && level_masks.count + extra <= kLevelMasks;
+    }
     long long mask_flushes = 0;  // kept bitmaps flushed in the middle of a search (counted over the problem's life)
     hipError_t FlushLevelMasks(hipStream_t stream)
     {
@@ -1133,8 +1149,10 @@ struct BFSProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
     }
     // What every Enact ends with (and Extract, for a search that was reset but not run): the deferred label pass, or, for a
     // search on the relabelled copy that labelled at discovery, the pass that brings its results into the caller's order.
-    hipError_t FinishSearch(hipStream_t stream)
+    // launched (when given): did it queue a kernel?
+    hipError_t FinishSearch(hipStream_t stream, bool *launched = nullptr)
     {
+        if (launched) *launched = (labels_deferred && !emit_current) || (!labels_deferred && translate_pending);
         if (labels_deferred) return EmitLabels(stream);
         if (!translate_pending) return hipSuccess;
         level_masks.count = 0;
@@ -1158,7 +1176,8 @@ struct BFSProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
     // when anything is discovered after this.
     // ... and the same pass queued behind a CHAIN of sweeps and the closing levels that follow it on the device
     // (kernel.hpp ChainedPersistentLevelsKernel): the chain's bitmaps go in as candidates, the gate words say how many were filled
-    hipError_t EmitLabelsGated(hipStream_t stream, const int *chain_masks, const VertexId *chain_labels, int chain_count, const int *d_gate)
+    hipError_t EmitLabelsGated(hipStream_t stream, const int *chain_masks, const VertexId *chain_labels, int chain_count, const int *d_gate,
+                               const util::PublishArgs *publish = nullptr)
     {
         if (!labels_deferred || !speculative_emit) return hipSuccess;
         if (level_masks.count + chain_count > kLevelMasks) return hipSuccess;  // (no room in the list: the ordinary pass will do)
@@ -1166,15 +1185,15 @@ struct BFSProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
         level_masks.chain_first = level_masks.count;
         for (int k = 0; k < chain_count; ++k) KeepMask(chain_masks[k], chain_labels[k]);
         level_masks.d_gate = d_gate;
-        const hipError_t rc = LaunchEmit<true>(stream, (source >= 0 && source < this->nodes) ? source : static_cast<VertexId>(-1));
+        const hipError_t rc = LaunchEmit<true>(stream, (source >= 0 && source < this->nodes) ? source : static_cast<VertexId>(-1), publish);
         level_masks = keep;
         return rc;
     }
-    hipError_t EmitLabelsSpeculative(hipStream_t stream)
+    hipError_t EmitLabelsSpeculative(hipStream_t stream, const util::PublishArgs *publish = nullptr)
     {
         if (!labels_deferred || !speculative_emit) return hipSuccess;
         const LevelMaskList<VertexId> keep = level_masks;
-        const hipError_t rc = LaunchEmit<true>(stream, (source >= 0 && source < this->nodes) ? source : static_cast<VertexId>(-1));
+        const hipError_t rc = LaunchEmit<true>(stream, (source >= 0 && source < this->nodes) ? source : static_cast<VertexId>(-1), publish);
         level_masks = keep;
         emit_current = true;
         return rc;

@@ -55,6 +55,21 @@ class EventPair {
         if (ms) *ms = t;
         return result;
     }
+    // The same for a run(stop_event) that records the stop event itself, behind the last kernel it queues (recording it again
+    // when it queues more: the later record wins), and returns only when the event has completed.  It is neither recorded
+    // nor waited for again here (an event that has not completed makes hipEventElapsedTime fail): a run whose last kernel is
+    // still executing when it knows its result spares the host calls behind that kernel.
+    template <typename Run>
+    hipError_t TimedLent(hipStream_t stream, float *ms, Run run)
+    {
+        hipError_t retval = hipSuccess;
+        GR_CHECK(hipEventRecord(start, stream), "hipEventRecord failed");
+        const hipError_t result = run(stop);
+        float t = 0;
+        GR_CHECK(hipEventElapsedTime(&t, start, stop), "hipEventElapsedTime failed");
+        if (ms) *ms = t;
+        return result;
+    }
 };
 
 // A host Csr over arrays the caller owns (reference bfs_app.cu:256-260).  ~Csr() frees its arrays, so the pointers are

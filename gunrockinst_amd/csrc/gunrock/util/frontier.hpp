@@ -69,50 +69,66 @@ struct HostMailbox {
     int chain_log[8];             // action each sweep of the last chain took (oprtr/advance/bottom_up.hpp SweepAction)
 };
 
-// One wave: mirror the enactor's device words into the mailbox, fold + re-arm the wide tail, then publish `seq`.
-static __global__ void PublishKernel(unsigned long long *d_tail, const unsigned long long *d_sums, unsigned long long *d_wide,
-                                     const int *d_overflow, HostMailbox *box, unsigned long long seq, unsigned clear_mask,
-                                     unsigned ones_mask, int wide_sets, const int *d_chain_log)
-{
+// What one publication needs.  A kernel that publishes on behalf of PublishKernel (the BFS label pass, bfs_problem.hpp)
+// takes one of these by value and only reads it; box == nullptr means "do not publish".
+struct PublishArgs {
+    unsigned long long *d_tail = nullptr;
+    const unsigned long long *d_sums = nullptr;
+    unsigned long long *d_wide = nullptr;
+    const int *d_overflow = nullptr;
+    HostMailbox *box = nullptr;
+    unsigned long long seq = 0;
     // clear_mask / ones_mask: slots to zero / to set to all ones AFTER mirroring -- the re-arming an enactor
     // would otherwise do with one hipMemsetAsync per word before its next kernel
-    const unsigned lane = threadIdx.x;
+    unsigned clear_mask = 0, ones_mask = 0;
+    int wide_sets = 1;
+    const int *d_chain_log = nullptr;
+};
+
+// One wave (every lane of it, and no other wave of the grid): mirror the enactor's device words into the mailbox, fold +
+// re-arm the wide tail, then publish `seq`.  Every word it reads must be final before the calling kernel starts.
+__device__ __forceinline__ void PublishBody(const PublishArgs &a)
+{
+    const unsigned lane = threadIdx.x & 63u;
+    HostMailbox *box = a.box;
     if (lane < 8) {
-        const unsigned long long v = d_tail[lane];
+        const unsigned long long v = a.d_tail[lane];
         box->tail[lane] = v;
-        if (lane == 7 || ((clear_mask >> lane) & 1u)) d_tail[lane] = 0ull;  // slot 7: grid barrier of the persistent levels kernel
-        else if ((ones_mask >> lane) & 1u) d_tail[lane] = ~0ull;
+        if (lane == 7 || ((a.clear_mask >> lane) & 1u)) a.d_tail[lane] = 0ull;  // slot 7: grid barrier of the persistent levels kernel
+        else if ((a.ones_mask >> lane) & 1u) a.d_tail[lane] = ~0ull;
     }
-    if (lane < 2) box->sums[lane] = d_sums[lane];
+    if (lane < 2) box->sums[lane] = a.d_sums[lane];
     unsigned long long w = 0;
     if (lane < 32) {
-        w = d_wide[lane * 16];
-        if (w) d_wide[lane * 16] = 0;
+        w = a.d_wide[lane * 16];
+        if (w) a.d_wide[lane * 16] = 0;
     }
     for (int o = 16; o; o >>= 1) w += __shfl_xor(w, o, 64);  // packed halves add independently (counts stay below 2^32)
     if (lane == 0) {
         box->wide = w;
-        box->overflow = static_cast<unsigned long long>(*d_overflow);
+        box->overflow = static_cast<unsigned long long>(*a.d_overflow);
     }
-    if (wide_sets > 1) {  // (uniform) the sets of a sweep chain: all loads first, then fold, mirror and re-arm each
+    if (a.wide_sets > 1) {  // (uniform) the sets of a sweep chain: all loads first, then fold, mirror and re-arm each
         unsigned long long ws[7];
 #pragma unroll
-        for (int k = 1; k < 8; ++k) ws[k - 1] = (k < wide_sets && lane < 32) ? d_wide[k * 512 + lane * 16] : 0ull;
+        for (int k = 1; k < 8; ++k) ws[k - 1] = (k < a.wide_sets && lane < 32) ? a.d_wide[k * 512 + lane * 16] : 0ull;
 #pragma unroll
         for (int k = 1; k < 8; ++k) {
-            if (k < wide_sets) {
-                if (ws[k - 1]) d_wide[k * 512 + lane * 16] = 0ull;
+            if (k < a.wide_sets) {
+                if (ws[k - 1]) a.d_wide[k * 512 + lane * 16] = 0ull;
                 unsigned long long t = ws[k - 1];
                 for (int o = 16; o; o >>= 1) t += __shfl_xor(t, o, 64);
                 if (lane == 0) box->wide_set[k] = t;
             }
         }
-        if (lane < 8) box->chain_log[lane] = d_chain_log[lane];
+        if (lane < 8) box->chain_log[lane] = a.d_chain_log[lane];
     }
-    __threadfence_system();
-    __syncthreads();
-    if (lane == 0) __hip_atomic_store(&box->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    __threadfence_system();  // (one wave: the fence covers the stores of all its lanes)
+    if (lane == 0) __hip_atomic_store(&box->seq, a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
+
+// The publication as a kernel of its own: one workgroup of one wave.
+static __global__ void PublishKernel(PublishArgs args) { PublishBody(args); }
 
 // One wave: what WorkProgress::Reset + SetTail do with three fill blits and one copy blit (4-5 us each, serialised at the
 // start of every Enact) -- zero the ring, the overflow flag and the wide tail, then seed one ring slot.
@@ -217,14 +233,34 @@ struct WorkProgress {
                        "WorkProgress SetTail failed", __FILE__, __LINE__);
     }
 
-    // Mirror all device words into the mailbox and wait for them (the only host<->device sync of a BSP step).
-    hipError_t Sync(hipStream_t stream, unsigned clear_mask = 0, unsigned ones_mask = 0)
+    // A read-back in two steps.  Post: the next sequence number and the publication that will write it -- PublishKernel on
+    // `stream`, or, with `hand_over`, the filled arguments for a kernel the caller queues next and which publishes on its
+    // behalf (every word mirrored must be final before that kernel starts).
+    hipError_t Post(hipStream_t stream, unsigned clear_mask = 0, unsigned ones_mask = 0, PublishArgs *hand_over = nullptr)
+    {
+        PublishArgs a;
+        a.d_tail = d_tail;
+        a.d_sums = d_sums;
+        a.d_wide = d_wide;
+        a.d_overflow = d_overflow;
+        a.box = box;
+        a.seq = ++seq;
+        a.clear_mask = clear_mask;
+        a.ones_mask = ones_mask;
+        a.wide_sets = publish_sets;
+        a.d_chain_log = d_chain_log;
+        if (hand_over) {
+            *hand_over = a;
+            return hipSuccess;
+        }
+        hipLaunchKernelGGL(PublishKernel, dim3(1), dim3(64), 0, stream, a);
+        return GRError(hipGetLastError(), "WorkProgress PublishKernel launch failed", __FILE__, __LINE__);
+    }
+
+    // Wait: host spin on the sequence word of the last Post.
+    hipError_t Wait(hipStream_t stream)
     {
         hipError_t retval = hipSuccess;
-        ++seq;
-        hipLaunchKernelGGL(PublishKernel, dim3(1), dim3(64), 0, stream, d_tail, d_sums, d_wide, d_overflow, box, seq, clear_mask,
-                           ones_mask, publish_sets, d_chain_log);
-        GR_CHECK(hipGetLastError(), "WorkProgress PublishKernel launch failed");
         volatile unsigned long long *flag = &box->seq;
         unsigned spins = 0;
         while (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq) {
@@ -238,6 +274,14 @@ struct WorkProgress {
             }
         }
         return retval;
+    }
+
+    // Mirror all device words into the mailbox and wait for them (the only host<->device sync of a BSP step).
+    hipError_t Sync(hipStream_t stream, unsigned clear_mask = 0, unsigned ones_mask = 0)
+    {
+        hipError_t retval = hipSuccess;
+        GR_CHECK(Post(stream, clear_mask, ones_mask), "WorkProgress Post failed");
+        return Wait(stream);
     }
 
     // Blocking read of one slot.
@@ -285,7 +329,9 @@ struct WorkProgress {
         return retval;
     }
 
-    // Overflow flag as of the last Sync (every enactor loop ends on a Sync that follows its last kernel).
+    // Overflow flag as of the last read-back.  Every enactor loop ends on a read-back that follows its last kernel; the only
+    // kernel that may run behind the last read-back is the BFS label pass that carried it (PublishBody), and that pass writes
+    // labels only: it cannot overflow anything.
     bool OverflowAtLastSync() const { return box->overflow != 0; }
 
     hipError_t CheckOverflow(bool &overflow, hipStream_t stream)

@@ -51,6 +51,8 @@ struct BfsRunner {
     virtual void DeviceResults(int **labels, int **preds) = 0;
     virtual void BuildRelabelled(bool on) = 0;
     virtual long long MaskFlushes() = 0;
+    virtual hipError_t StreamIdle(bool &idle) = 0;
+    virtual long long FusedPublications() = 0;
     virtual void RelabelInfo(long long &hubs, long long &with_edges, int &threshold, float &build_ms, long long &bytes) = 0;
 };
 
@@ -138,6 +140,7 @@ struct BfsRunnerT : BfsRunner {
         else if (key == "chain_closing") problem.chain_closing = value != 0.0;
         else if (key == "label_pass") problem.label_pass = value != 0.0 ? 1 : 0;
         else if (key == "walk_queue") problem.walk_queue = value != 0.0 ? 1 : 0;
+        else if (key == "fused_publish") problem.fused_publish = value != 0.0 ? 1 : 0;
         else if (key == "hub_slice") problem.hub_slice = value < 0.0 ? -1 : static_cast<long long>(value);
         else if (key == "relabel") {  // from the next Reset: 1 the relabelled copy, 0 the caller's numbering, -1 by graph size
             if (value > 0.0 && !problem.HasRelabelled()) return 2;
@@ -189,7 +192,18 @@ struct BfsRunnerT : BfsRunner {
     }
     hipError_t Enact(int src, int max_grid_size, int traversal_mode, float *ms) override
     {
-        return timer.Timed(problem.graph_slices[0]->stream, ms, [&]() { return enactor.template Enact<Problem>(context, &problem, src, max_grid_size, traversal_mode); });
+        // (the enactor records the stop event behind its last kernel, usually the label pass, while that kernel still runs)
+        return timer.TimedLent(problem.graph_slices[0]->stream, ms, [&](hipEvent_t stop) {
+            return enactor.template Enact<Problem>(context, &problem, src, max_grid_size, traversal_mode, stop);
+        });
+    }
+    long long FusedPublications() override { return enactor.FusedPublications(); }
+    hipError_t StreamIdle(bool &idle) override
+    {
+        if (!problem.graph_slices) return hipErrorNotInitialized;
+        const hipError_t rc = hipStreamQuery(problem.graph_slices[0]->stream);
+        idle = rc == hipSuccess;
+        return rc == hipErrorNotReady ? hipSuccess : rc;
     }
     void Stats(long long &queued, long long &depth, double &duty, long long &launches, double &kernel_ms) override
     {
@@ -406,6 +420,22 @@ int grx_bfs_mask_flushes(grx_bfs *p, long long *flushes)
     if (!p || !p->runner || !flushes) return -1;
     *flushes = p->runner->MaskFlushes();
     return 0;
+}
+
+int grx_bfs_fused_publications(grx_bfs *p, long long *count)
+{
+    if (!p || !p->runner || !count) return -1;
+    *count = p->runner->FusedPublications();
+    return 0;
+}
+
+int grx_bfs_stream_idle(grx_bfs *p, int *idle)
+{
+    if (!p || !p->runner || !idle) return -1;
+    bool none = false;
+    const hipError_t rc = p->runner->StreamIdle(none);
+    *idle = none ? 1 : 0;
+    return static_cast<int>(rc);
 }
 
 int grx_bfs_relabel_info(grx_bfs *p, long long *hubs, long long *with_edges, int *threshold, float *build_ms, long long *bytes)

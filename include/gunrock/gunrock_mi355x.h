@@ -135,7 +135,9 @@ int grx_bfs_set_label_deferral(grx_bfs *p, int enabled, int mask_limit);
  * label pass loads every bitmap word once per workgroup tile; 0: the per-lane kernels it replaced; read at every launch of
  * the pass, so it can be flipped between searches), "walk_queue" (1, the default: the dense bottom-up sweep queues the row walks
  * of its pending vertices per wave and walks them 64 at a time, DESIGN.md 3.3 m; 0: the step-by-step walk loop it replaced; read
- * at every launch of a sweep).
+ * at every launch of a sweep), "fused_publish" (1, the default: where a tiled label pass is queued behind the launch that
+ * usually ends the search, its workgroup 0 publishes the read-back that tells the host how the search ended, and Enact records
+ * its completion event while the pass still runs, DESIGN.md 3.3 o; 0: a publishing kernel behind the pass; read at every Enact).
  * Relabelled copy (DESIGN.md 3.3 k): a symmetric problem (grx_bfs_set_inverse_graph without arrays, or grx_bfs_auto_inverse
  * on a symmetric graph) also builds a copy of its CSR renumbered hub-first, edgeless-last, and searches it; labels and
  * predecessors still come back in the caller's numbering.  "relabel" (1: search the copy; 0: the caller's numbering; -1, the
@@ -151,6 +153,11 @@ int grx_bfs_set_option(grx_bfs *p, const char *name, double value);
 /* Deferred labels: how many times a search of this handle ran out of frontier bitmaps and flushed its kept levels into the
  * labels (summed over the handle's life; see grx_bfs_set_label_deferral's mask_limit). */
 int grx_bfs_mask_flushes(grx_bfs *p, long long *flushes);
+/* *idle = 1 when nothing is queued or running on the handle's stream (hipStreamQuery says hipSuccess), else 0.  grx_bfs_enact
+ * returns only when everything it queued has completed, so right after it the answer is 1. */
+int grx_bfs_stream_idle(grx_bfs *p, int *idle);
+/* Read-backs that a label pass published on the enactor's behalf ("fused_publish"), summed over the handle's life. */
+int grx_bfs_fused_publications(grx_bfs *p, long long *count);
 int grx_bfs_relabel_info(grx_bfs *p, long long *hubs, long long *with_edges, int *threshold, float *build_ms, long long *bytes);
 /* Direction-optimizing only: a level that would run count-only or bottom-up and has between `min_edges` and `max_edges`
  * frontier edges starts with a bottom-up pass that probes only the adjacency heads (the highest-degree in-neighbours); the
