@@ -22,6 +22,8 @@ from .capi import (  # noqa: F401
     BCC_FOREST, BCC_SIZES, BCC_NUMBER, BCC_LOWHIGH, BCC_LINK, BCC_LABEL,
     MaxflowProblem, MaxflowGaveUp, gunrock_maxflow, gunrock_mincut, MAXFLOW_AUTO, MAXFLOW_ROUNDS, MAXFLOW_DEVICE_LOOP,
     MAXFLOW_PREFLOW, MAXFLOW_RETURN, MAXFLOW_CUT, MAXFLOW_GAVE_UP,
+    MatchingProblem, MatchingGaveUp, MatchingOverflow, gunrock_matching, gunrock_coarsen, matching_keys, MATCHING_AUTO, MATCHING_ROUNDS,
+    MATCHING_DEVICE_LOOP, MATCHING_STEP_WIDE, MATCHING_STEP_LOOP, MATCHING_GAVE_UP, MATCHING_OVERFLOW,
     advance_frontier, advance_queue, advance_reduce,
 )
 
@@ -40,5 +42,7 @@ __all__ = [
     "BccProblem", "gunrock_bcc", "gunrock_bridges", "gunrock_articulation_points", "BCC_AUTO", "BCC_ROUNDS", "BCC_DEVICE_LOOP", "BCC_FOREST", "BCC_SIZES", "BCC_NUMBER", "BCC_LOWHIGH", "BCC_LINK", "BCC_LABEL",
     "MaxflowProblem", "MaxflowGaveUp", "gunrock_maxflow", "gunrock_mincut", "MAXFLOW_AUTO", "MAXFLOW_ROUNDS", "MAXFLOW_DEVICE_LOOP", "MAXFLOW_PREFLOW",
     "MAXFLOW_RETURN", "MAXFLOW_CUT", "MAXFLOW_GAVE_UP",
+    "MatchingProblem", "MatchingGaveUp", "MatchingOverflow", "gunrock_matching", "gunrock_coarsen", "matching_keys", "MATCHING_AUTO",
+    "MATCHING_ROUNDS", "MATCHING_DEVICE_LOOP", "MATCHING_STEP_WIDE", "MATCHING_STEP_LOOP", "MATCHING_GAVE_UP", "MATCHING_OVERFLOW",
     "advance_frontier", "advance_queue", "advance_reduce",
 ]

@@ -251,6 +251,22 @@ _SIGNATURES = {
     "grx_maxflow_summary": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
     "grx_maxflow_device_results": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 7),
     "grx_maxflow_destroy": (None, [C.c_void_p]),
+    "grx_matching_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int]),
+    "grx_matching_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p, i32p, C.c_uint]),
+    "grx_matching_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint]),
+    "grx_matching_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
+    "grx_matching_reset": (C.c_int, [C.c_void_p]),
+    "grx_matching_enact": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
+    "grx_matching_stats": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_longlong)] * 6 + [C.POINTER(C.c_double)] * 2),
+    "grx_matching_round_trace": (C.c_int, [C.c_void_p, C.c_int, i32p] + [C.POINTER(C.c_longlong)] * 3),
+    "grx_matching_pairs": (C.c_longlong, [C.c_void_p, i32p, i32p, i32p]),
+    "grx_matching_extract": (C.c_int, [C.c_void_p, C.POINTER(C.c_ubyte), i32p, i32p]),
+    "grx_matching_summary": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
+    "grx_matching_device_results": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 6),
+    "grx_matching_contract": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "grx_matching_coarse_extract": (C.c_int, [C.c_void_p, i32p, i32p, i32p, i32p, i32p]),
+    "grx_matching_coarse_device": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 5),
+    "grx_matching_destroy": (None, [C.c_void_p]),
     "grx_sssp_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int]),
     "grx_sssp_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p, C.POINTER(C.c_uint32), C.c_int]),
     "grx_sssp_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float]),
@@ -1614,6 +1630,213 @@ def gunrock_mincut(nodes, row_offsets, col_indices, capacities, src, sink, devic
         return r["value"], r["side"], a, b, r["cut"]
     return _one_shot(MaxflowProblem(device=device).init(nodes, row_offsets, col_indices, capacities), lambda p: p.reset(src, sink),
                      MaxflowProblem.enact, result)
+
+
+MATCHING_AUTO, MATCHING_ROUNDS, MATCHING_DEVICE_LOOP = 0, 1, 2  # enum GRX_MATCHING_* (gunrock_mi355x.h)
+MATCHING_STEP_WIDE, MATCHING_STEP_LOOP = 0, 1  # enum GRX_MATCHING_STEP_*: the kinds of round_trace()
+MATCHING_GAVE_UP, MATCHING_OVERFLOW = -4, -5  # grx_matching_enact: more than "max_rounds" rounds; grx_matching_contract: a sum outside int32
+
+
+class MatchingGaveUp(RuntimeError):
+    """MatchingProblem.enact passed "max_rounds" (GRX_MATCHING_GAVE_UP): the handle holds no result and takes the next reset"""
+
+
+class MatchingOverflow(ArithmeticError):
+    """MatchingProblem.contract: a coarse pair weight or vertex weight is outside int32 (GRX_MATCHING_OVERFLOW); nothing is kept"""
+
+
+def matching_keys(pair_weights, seed=0):
+    """The keys grx_matching_* orders the pairs by, as uint64 (host helper): ((uint32)w(i) ^ 0x80000000) << 32 | fmix32((uint32)i +
+    seed * 0x9E3779B9) for the pair weights in canonical pair order; heavier is larger, ties go by mis_priorities' hash."""
+    w = np.asarray(pair_weights, dtype=np.int64)
+    high = ((w & 0xFFFFFFFF) ^ 0x80000000).astype(np.uint64)
+    return (high << np.uint64(32)) | mis_priorities(w.shape[0], seed).astype(np.uint64)
+
+
+class MatchingProblem(_Handle):
+    """MatchingProblem + MatchingEnactor behind the handle C ABI: the locally dominant (heavy-edge) matching of the CSR read as an
+    undirected simple graph with int32 weights (None: 1 each; a pair's weight is the largest of its entries), unique under the order
+    matching_keys(); and its contraction into the coarse graph.  Per-pair arrays in the canonical pair order ((a, b) with a < b,
+    sorted)."""
+
+    _destroy = "grx_matching_destroy"
+
+    _STATS = ("pairs", "rounds", "loop_rounds", "entries_read", "polls", "kernel_launches")
+    _SUMMARY = ("pairs", "matched", "weight", "unmatched", "unmatched_with_neighbours")
+
+    def __init__(self, instrument=False, device=0):
+        self._create("grx_matching_create", int(instrument), device)
+        self.nodes = 0
+        self.entries = 0
+        self.num_pairs = 0
+        self.coarse_nodes = self.coarse_entries = 0
+
+    def _ready(self):
+        m = lib().grx_matching_pairs(self._h, None, None, None)
+        if m < 0:
+            _check(-m, "MatchingProblem::Pairs")
+        self.num_pairs = int(m)
+
+    def init(self, nodes, row_offsets, col_indices, weights=None, seed=0):
+        ro, ci = _csr_arrays(row_offsets, col_indices, nodes)
+        w = None if weights is None else _i32(weights)
+        if w is not None and w.shape[0] != ci.shape[0]:
+            raise ValueError("gunrockinst_amd: %d weights for %d entries" % (w.shape[0], ci.shape[0]))
+        self.nodes, self.entries = int(nodes), int(ci.shape[0])
+        _check(lib().grx_matching_init(self._h, self.nodes, self.entries, _p(ro), _p(ci), None if w is None else _p(w), int(seed) & 0xFFFFFFFF),
+               "MatchingProblem::Init")
+        self._ready()
+        return self
+
+    def init_device(self, nodes, edges, d_row_offsets, d_col_indices, d_weights=None, seed=0):
+        """the CSR (and the weights) stay the caller's; the build reads them, nothing later does"""
+        self.nodes, self.entries = int(nodes), int(edges)
+        _check(lib().grx_matching_init_device(self._h, self.nodes, self.entries, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices),
+                                              C.c_void_p(d_weights) if d_weights else None, int(seed) & 0xFFFFFFFF),
+               "MatchingProblem::Init(device)")
+        self._ready()
+        return self
+
+    def set_option(self, name, value):
+        """"schedule" (MATCHING_AUTO / MATCHING_ROUNDS / MATCHING_DEVICE_LOOP), "wave_min_row", "max_rounds", "loop_max_list",
+        "loop_max_entries"; returns the library's code: 0 = set, 1 = unknown name (a value out of range raises)"""
+        rc = lib().grx_matching_set_option(self._h, name.encode(), float(value))
+        if rc not in (0, 1):
+            _check(rc, "grx_matching_set_option(%s)" % name)
+        return rc
+
+    def reset(self):
+        _check(lib().grx_matching_reset(self._h), "MatchingProblem::Reset")
+
+    def enact(self, max_grid_size=0):
+        """the elapsed milliseconds; MatchingGaveUp when the rounds passed the option max_rounds"""
+        ms = C.c_float()
+        rc = lib().grx_matching_enact(self._h, int(max_grid_size), C.byref(ms))
+        if rc == MATCHING_GAVE_UP:
+            raise MatchingGaveUp("gunrockinst_amd: MatchingEnactor::Enact gave up (code %d)" % rc)
+        _check(rc, "MatchingEnactor::Enact")
+        return ms.value
+
+    def stats(self):
+        v = [C.c_longlong() for _ in self._STATS]
+        k, b = C.c_double(), C.c_double()
+        _check(lib().grx_matching_stats(self._h, *([C.byref(x) for x in v] + [C.byref(k), C.byref(b)])), "grx_matching_stats")
+        out = {name: x.value for name, x in zip(self._STATS, v)}
+        out["kernel_ms"], out["build_ms"] = k.value, b.value
+        return out
+
+    def round_trace(self):
+        """the host's steps of the last enact: (kind as int32: MATCHING_STEP_WIDE / MATCHING_STEP_LOOP, rounds, live list, matched
+        pairs as int64)"""
+        count = lib().grx_matching_round_trace(self._h, 0, None, None, None, None)
+        if count < 0:
+            _check(count, "grx_matching_round_trace")
+        kind = np.empty(max(count, 1), dtype=np.int32)
+        rounds, live, matched = (np.empty(max(count, 1), dtype=np.int64) for _ in range(3))
+        lib().grx_matching_round_trace(self._h, count, _p(kind), _i64p(rounds), _i64p(live), _i64p(matched))
+        return kind[:count], rounds[:count], live[:count], matched[:count]
+
+    def pairs(self):
+        """the canonical pairs (src, dst, weight) as int32, src < dst, sorted by (src, dst)"""
+        a, b, w = (np.empty(max(self.num_pairs, 1), dtype=np.int32) for _ in range(3))
+        m = lib().grx_matching_pairs(self._h, _p(a), _p(b), _p(w))
+        if m < 0:
+            _check(-m, "MatchingProblem::Pairs")
+        return a[:m], b[:m], w[:m]
+
+    def extract(self):
+        """{"in_matching": uint8 per pair, "mate": int32 per vertex (-1: unmatched), "medge": int32 per vertex (-1: unmatched)}"""
+        m, n = max(self.num_pairs, 1), max(self.nodes, 1)
+        in_matching, mate, medge = np.empty(m, np.uint8), np.empty(n, np.int32), np.empty(n, np.int32)
+        _check(lib().grx_matching_extract(self._h, _u8p(in_matching), _p(mate), _p(medge)), "MatchingProblem::Extract")
+        return {"in_matching": in_matching[:self.num_pairs], "mate": mate[:self.nodes], "medge": medge[:self.nodes]}
+
+    def summary(self):
+        """{"pairs", "matched", "weight", "unmatched", "unmatched_with_neighbours"}"""
+        v = (C.c_longlong * 5)()
+        _check(lib().grx_matching_summary(self._h, v), "MatchingProblem::Summary")
+        return {name: int(x) for name, x in zip(self._SUMMARY, v)}
+
+    def device_results(self):
+        """device pointers {"in_matching", "mate", "medge", "src", "dst", "weight"}: per pair in_matching (uint8), src, dst, weight
+        (int32); per vertex mate and medge (int32)"""
+        names = ("in_matching", "mate", "medge", "src", "dst", "weight")
+        p = [C.c_void_p() for _ in names]
+        _check(lib().grx_matching_device_results(self._h, *[C.byref(x) for x in p]), "grx_matching_device_results")
+        return {name: x.value for name, x in zip(names, p)}
+
+    def contract(self, vertex_weights=None):
+        """builds the coarse graph of the last enact on the device; returns (coarse_nodes, coarse_entries).  vertex_weights: None (1
+        each), an int32 array, or a device pointer as int (the "vweight" of a level before).  MatchingOverflow when a sum leaves
+        int32."""
+        nc, ne = C.c_longlong(), C.c_longlong()
+        if vertex_weights is None or isinstance(vertex_weights, int):
+            vw, ptr = None, C.c_void_p(vertex_weights) if vertex_weights else None
+        else:
+            vw = _i32(vertex_weights)
+            if vw.shape[0] != self.nodes:
+                raise ValueError("gunrockinst_amd: %d vertex weights for %d nodes" % (vw.shape[0], self.nodes))
+            ptr = C.c_void_p(vw.ctypes.data)
+        rc = lib().grx_matching_contract(self._h, ptr, C.byref(nc), C.byref(ne))
+        if rc == MATCHING_OVERFLOW:
+            raise MatchingOverflow("gunrockinst_amd: MatchingProblem::Contract: a sum outside int32 (code %d)" % rc)
+        _check(rc, "MatchingProblem::Contract")
+        self.coarse_nodes, self.coarse_entries = int(nc.value), int(ne.value)
+        return self.coarse_nodes, self.coarse_entries
+
+    def coarse_extract(self):
+        """(map, coarse_nodes, row_offsets, col_indices, weights, vweight) of the last contract, int32 arrays"""
+        n, nc, ne = max(self.nodes, 1), self.coarse_nodes, max(self.coarse_entries, 1)
+        cmap, ro, ci, w, vw = np.empty(n, np.int32), np.empty(nc + 1, np.int32), np.empty(ne, np.int32), np.empty(ne, np.int32), np.empty(max(nc, 1), np.int32)
+        _check(lib().grx_matching_coarse_extract(self._h, _p(cmap), _p(ro), _p(ci), _p(w), _p(vw)), "MatchingProblem::CoarseExtract")
+        return cmap[:self.nodes], nc, ro, ci[:self.coarse_entries], w[:self.coarse_entries], vw[:nc]
+
+    def coarse_device(self):
+        """device pointers {"map", "row_offsets", "col_indices", "weights", "vweight"} of the last contract: they live until this
+        handle's next reset, contract or close"""
+        names = ("map", "row_offsets", "col_indices", "weights", "vweight")
+        p = [C.c_void_p() for _ in names]
+        _check(lib().grx_matching_coarse_device(self._h, *[C.byref(x) for x in p]), "grx_matching_coarse_device")
+        return {name: x.value for name, x in zip(names, p)}
+
+
+def gunrock_matching(nodes, row_offsets, col_indices, weights=None, seed=0, device=0):
+    """One-shot heavy-edge matching: returns (src, dst, in_matching uint8 per canonical pair, mate int32 per vertex, matched pairs,
+    total matched weight)."""
+    def result(p):
+        r, s = p.extract(), p.summary()
+        return p.pairs()[:2] + (r["in_matching"], r["mate"], s["matched"], s["weight"])
+    return _one_shot(MatchingProblem(device=device).init(nodes, row_offsets, col_indices, weights, seed), MatchingProblem.reset,
+                     MatchingProblem.enact, result)
+
+
+def gunrock_coarsen(nodes, row_offsets, col_indices, weights=None, vertex_weights=None, seed=0, levels=1, device=0):
+    """One-shot multilevel coarsening: a list with (map, coarse_nodes, row_offsets, col_indices, weights, vweight) per level, each
+    level matched and contracted on the device from the level before's device arrays; stops early behind a level that matched
+    nothing."""
+    out, handles, p = [], [], None
+    try:
+        p = MatchingProblem(device=device).init(nodes, row_offsets, col_indices, weights, seed)
+        vw = vertex_weights
+        for _ in range(int(levels)):
+            handles.append(p)
+            p.reset()
+            p.enact()
+            matched = p.summary()["matched"]
+            nc, ne = p.contract(vw)
+            out.append(p.coarse_extract())
+            if matched == 0:
+                break
+            d = p.coarse_device()
+            vw = d["vweight"]
+            if len(out) < int(levels):
+                p = MatchingProblem(device=device).init_device(nc, ne, d["row_offsets"], d["col_indices"], d["weights"] if ne else None, seed)
+    finally:
+        for h in reversed(handles):
+            h.close()
+        if p is not None and p not in handles:
+            p.close()
+    return out
 
 
 MSBFS_AUTO, MSBFS_PUSH, MSBFS_PULL, MSBFS_ALTERNATE = 0, 1, 2, 3  # enum GRX_MSBFS_* (gunrock_mi355x.h): option "direction"

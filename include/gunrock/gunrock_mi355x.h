@@ -834,6 +834,86 @@ int grx_maxflow_device_results(grx_maxflow *p, int **d_flow, unsigned char **d_s
 void grx_maxflow_destroy(grx_maxflow *p);
 
 /* ------------------------------------------------------------------------------------------------
+ * Heavy-edge matching and graph contraction: MatchingProblem + MatchingEnactor in
+ * app/matching/{matching_problem,matching_enactor,matching_functor}.hpp (the locally dominant matching: Preis, STACS 1999; Manne and
+ * Bisseling, PPAM 2007; the reference snapshot has no counterpart).  One level of multilevel coarsening.  The CSR is read as an
+ * undirected simple graph, as grx_bcc_* and grx_truss_* read it: either row may hold the edge, self-loops are ignored, rows may be
+ * unsorted and hold duplicates.  The M canonical pairs {a < b} are sorted by (a, b) and every per-pair array is indexed by that
+ * order.  `weights` is an int32 per CSR entry (any value) or NULL, which means 1 each; the weight w(i) of pair i is the largest of
+ * its entries in both directions.  Pairs are strictly ordered by
+ *     key(i) = ((uint32)w(i) ^ 0x80000000) << 32 | fmix32((uint32)i + seed * 0x9E3779B9)       (uint64; fmix32 of grx_mis_*)
+ * and in_matching[i] = 1 iff no pair j that shares an end with i and has key(j) > key(i) has in_matching[j] = 1.  That equation has
+ * one solution: the matching the greedy pass over the pairs in descending key order writes.  It is maximal, and its weight is at
+ * least half of the maximum weight matching's.  The results of Enact:
+ *   in_matching[i]  uint8, M entries
+ *   mate[v]         the other end of v's pair, -1: unmatched (int32, `nodes` entries)
+ *   medge[v]        the canonical index of v's pair, -1: unmatched (int32, `nodes` entries)
+ *   summary         M, the matched pairs, their total weight (int64), the unmatched vertices, those of them with a neighbour
+ * Contract builds the coarse graph of the last Enact: rep(v) = min(v, mate[v]) (v when unmatched), map[v] = the rank of rep(v) among
+ * the representatives ascending, vweight[c] = the sum of the cluster's vertex weights, a coarse pair {map[a], map[b]} for every fine
+ * pair with map[a] != map[b], its weight the sum of the w(i) that fall on it; it comes out as a mirrored CSR with ascending rows and
+ * the pair's weight on both copies, which a next handle reads back unchanged.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct grx_matching grx_matching;
+enum { GRX_MATCHING_AUTO = 0, GRX_MATCHING_ROUNDS = 1, GRX_MATCHING_DEVICE_LOOP = 2 };
+enum { GRX_MATCHING_STEP_WIDE = 0, GRX_MATCHING_STEP_LOOP = 1 }; /* the kinds of grx_matching_round_trace */
+enum { GRX_MATCHING_GAVE_UP = -4, GRX_MATCHING_OVERFLOW = -5 };  /* next to -1 / -2 / -3 */
+
+/* (no counterpart in the reference snapshot: this call and the ones below are shaped like grx_maxflow_*) */
+int grx_matching_create(grx_matching **out, int instrument, int device);
+/* MatchingProblem::Init: validates the CSR and builds the pairs, their weights and the neighbour CSR on the device.  -1: nodes < 1,
+ * edges < 0 or a NULL array; -2: not a CSR of `nodes` vertices; -3: the handle has been given a graph before (accepted or rejected) */
+int grx_matching_init(grx_matching *p, int nodes, int edges, const int *row_offsets, const int *col_indices, const int *weights, unsigned seed);
+/* the same for a CSR (and weights, or NULL) already in HBM: borrowed, not freed, read by the build only */
+int grx_matching_init_device(grx_matching *p, int nodes, int edges, int *d_row_offsets, int *d_col_indices, int *d_weights, unsigned seed);
+/* 0: set; 1: unknown name; -1: a value out of range.  No option changes a result.
+ *   "schedule"          GRX_MATCHING_AUTO (default): a stretch of narrow rounds is one loop launch on the device, a wide round is a
+ *                       launch pair of its own; GRX_MATCHING_ROUNDS: every round is a launch pair and a read-back;
+ *                       GRX_MATCHING_DEVICE_LOOP: every round runs in the one-workgroup loop
+ *   "wave_min_row"      rows with at least this many entries left are walked by a whole wave (default 16, >= 1)
+ *   "max_rounds"        Enact stops with GRX_MATCHING_GAVE_UP behind this many rounds (default 0: nodes / 2 + 1, which no run
+ *                       passes; 0 .. 2^31)
+ *   "loop_max_list"     under AUTO the device loop takes a round of at most this many vertices (default 32768, not tuned)
+ *   "loop_max_entries"  ... whose rows hold at most this many entries (default 65536, not tuned) */
+int grx_matching_set_option(grx_matching *p, const char *name, double value);
+/* MatchingProblem::Reset: nobody matched, every vertex with a neighbour live; the coarse graph of a Contract is freed */
+int grx_matching_reset(grx_matching *p);
+/* MatchingEnactor::Enact(problem, max_grid_size), HIP-event timed.  Without a Reset since the last Enact it resets itself.
+ * GRX_MATCHING_GAVE_UP: the rounds passed "max_rounds"; the handle then holds no result and takes the next Reset */
+int grx_matching_enact(grx_matching *p, int max_grid_size, float *elapsed_ms);
+/* of the last Enact, any pointer may be NULL: M, the rounds that matched a pair (the round count of the mutual-best form of the
+ * definition; the closing round that only retires vertices is not in it), the rounds run inside the device loop, row entries
+ * walked, one-entry polls, kernel launches and -- when instrumented -- the summed kernel time; build_ms: the HIP-event time of
+ * Init's build */
+int grx_matching_stats(grx_matching *p, long long *pairs, long long *rounds, long long *loop_rounds, long long *entries_read, long long *polls,
+                       long long *kernel_launches, double *kernel_ms, double *build_ms);
+/* the host's steps of the last Enact in order, at most max_steps of them: the kind (GRX_MATCHING_STEP_*), the rounds it ran (1 for a
+ * wide round), the live list it started from and the pairs it matched; returns the number of steps (0 before the first Enact) */
+int grx_matching_round_trace(grx_matching *p, int max_steps, int *kind, long long *rounds, long long *list, long long *matched);
+/* the canonical pairs and their weights (any pointer may be NULL); returns M or a negated hipError_t; valid after init */
+long long grx_matching_pairs(grx_matching *p, int *h_src, int *h_dst, int *h_weight);
+/* the results of the last Enact; every pointer may be NULL.  Before a finished Enact: hipErrorNotReady */
+int grx_matching_extract(grx_matching *p, unsigned char *h_in_matching, int *h_mate, int *h_medge);
+/* M, matched pairs, their total weight, unmatched vertices, unmatched vertices of degree > 0.  Before a finished Enact:
+ * hipErrorNotReady */
+int grx_matching_summary(grx_matching *p, long long out[5]);
+/* device arrays of the handle: in_matching (M uint8), mate and medge (`nodes` int32), the canonical pairs and their weights (M
+ * int32 each) */
+int grx_matching_device_results(grx_matching *p, unsigned char **d_in_matching, int **d_mate, int **d_medge, int **d_src, int **d_dst,
+                                int **d_weight);
+/* the coarse graph of the last Enact, built on the device and kept until the next Reset or Contract.  vertex_weights: `nodes` int32
+ * in host or device memory, or NULL (1 each).  -1: no finished Enact; GRX_MATCHING_OVERFLOW: a coarse pair weight or vertex weight
+ * is outside int32 (nothing is kept, nothing is wrapped).  *coarse_entries is twice the coarse pairs */
+int grx_matching_contract(grx_matching *p, const int *vertex_weights, long long *coarse_nodes, long long *coarse_entries);
+/* map (`nodes`), the coarse CSR (coarse_nodes + 1 offsets, coarse_entries columns and weights) and vweight (coarse_nodes), all int32;
+ * every pointer may be NULL.  Without a Contract: hipErrorNotReady */
+int grx_matching_coarse_extract(grx_matching *p, int *h_map, int *h_row_offsets, int *h_col_indices, int *h_weights, int *h_vweight);
+/* the same arrays on the device, for grx_matching_init_device of the next level (they live until this handle's next Reset,
+ * Contract or destroy).  Without a Contract: hipErrorNotReady and NULLs */
+int grx_matching_coarse_device(grx_matching *p, int **d_map, int **d_row_offsets, int **d_col_indices, int **d_weights, int **d_vweight);
+void grx_matching_destroy(grx_matching *p);
+
+/* ------------------------------------------------------------------------------------------------
  * SSSP: SSSPProblem + SSSPEnactor (reference gunrock/app/sssp/sssp_problem.cuh:35-387, sssp_enactor.cuh:36-563)
  * ---------------------------------------------------------------------------------------------- */
 typedef struct grx_sssp grx_sssp;
