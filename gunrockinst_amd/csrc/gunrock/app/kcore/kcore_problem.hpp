@@ -4,7 +4,7 @@
 // as MIS and TC read it: an undirected simple graph G in which u and v are neighbours when either row holds the other, self-loops
 // ignored, unsorted rows, duplicates and one-way edges allowed.  Init builds on the device, with the in-tree radix sort and scan:
 //   1. one key (min << cb | max) per CSR entry, self-loops as the sentinel; sorted; duplicates flagged off: the M edges of G
-//      (TC's first step, with TC's kernels: tc_functor.hpp is included, not changed)
+//      (graphio::PairGraph's Keys step, graphio/pair_graph.hpp)
 //   2. d(v) by two atomic adds per edge; its exclusive scan is the offsets of the neighbour CSR, 2M entries
 //   3. both directions of every edge scattered through per-row cursors: the symmetric simple neighbour CSR (rows unordered)
 // core[] is the working array and the result (kcore_functor.hpp): Reset copies d(v) into it.
@@ -15,10 +15,10 @@
 #include <gunrock/app/kcore/kcore_functor.hpp>
 #include <gunrock/app/problem_base.hpp>
 #pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunused-function"  // (only TC's build kernels are used here)
+#pragma clang diagnostic ignored "-Wunused-function"  // (only TC's DegreeKernel is used here)
 #include <gunrock/app/tc/tc_functor.hpp>
 #pragma clang diagnostic pop
-#include <gunrock/graphio/device_sort.hpp>
+#include <gunrock/graphio/pair_graph.hpp>
 
 namespace gunrock {
 namespace app {
@@ -113,22 +113,18 @@ struct KcoreProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         GR_CHECK(hipMalloc(&ds->d_counters, sizeof(unsigned long long) * 4), "KcoreProblem hipMalloc failed");
 
         // 1. the CSR must be one: the build indexes with what it reads
-        int bad = 0;
+        bool bad = false;
         GR_CHECK(hipMemsetAsync(ds->d_words, 0, sizeof(unsigned) * (W_COUNT + 4), stream), "KcoreProblem memset failed");
-        hipLaunchKernelGGL(tc::ValidateCsrKernel, dim3(Grid((n > m ? n : m) + 1)), dim3(256), 0, stream, gs->d_row_offsets, gs->d_column_indices,
-                           n, m, reinterpret_cast<int *>(ds->d_words));
-        GR_CHECK(hipGetLastError(), "ValidateCsrKernel launch failed");
-        GR_CHECK(hipMemcpyAsync(&bad, ds->d_words, sizeof(int), hipMemcpyDeviceToHost, stream), "KcoreProblem read-back failed");
-        GR_CHECK(hipStreamSynchronize(stream), "KcoreProblem read-back sync failed");
+        if ((retval = graphio::DeviceValidateCsr(gs->d_row_offsets, gs->d_column_indices, n, m, reinterpret_cast<int *>(ds->d_words), stream, &bad)))
+            return retval;
         if (bad) {
             malformed = 1;
             return hipErrorInvalidValue;
         }
 
-        hipEvent_t ev[2] = {nullptr, nullptr};
-        GR_CHECK(hipEventCreate(&ev[0]), "KcoreProblem hipEventCreate failed");
-        GR_CHECK(hipEventCreate(&ev[1]), "KcoreProblem hipEventCreate failed");
-        GR_CHECK(hipEventRecord(ev[0], stream), "KcoreProblem hipEventRecord failed");
+        graphio::BuildEvents ev;
+        if ((retval = ev.Create(2))) return retval;
+        if ((retval = ev.Record(0, stream))) return retval;
 
         GR_CHECK(hipMalloc(&ds->d_core, sizeof(int) * n1), "KcoreProblem hipMalloc d_core failed");
         GR_CHECK(hipMalloc(&ds->d_degrees, sizeof(int) * (n1 + 1)), "KcoreProblem hipMalloc d_degrees failed");
@@ -139,32 +135,19 @@ struct KcoreProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         GR_CHECK(hipMemsetAsync(ds->d_degrees, 0, sizeof(int) * (n1 + 1), stream), "KcoreProblem memset failed");
         GR_CHECK(hipMemsetAsync(ds->d_nro, 0, sizeof(int) * (n1 + 1), stream), "KcoreProblem memset failed");
 
-        int col_bits = 1;
-        while ((1ll << col_bits) < n) ++col_bits;
-        const int key_bits = 2 * col_bits;  // <= 62
-        const unsigned long long sentinel = (1ull << key_bits) - 1ull;  // min = max = 2^cb - 1: never an edge
-        unsigned *d_keep = nullptr, *d_cursor = nullptr;
-        unsigned long long *d_sums = nullptr;
-        graphio::DeviceKeySort edge_sort;
+        graphio::PairGraph pg(n);  // (its keys and keep flags; the unordered rows are k-core's own)
+        graphio::DeviceScratch<unsigned> cursor;
+        graphio::DeviceScratch<unsigned long long> sums;
         simple_edges = 0;
         if (m > 0) {
-            GR_CHECK(hipMalloc(&d_keep, sizeof(unsigned) * static_cast<size_t>(m)), "KcoreProblem hipMalloc failed");
-            GR_CHECK(hipMalloc(&d_cursor, sizeof(unsigned) * n1), "KcoreProblem hipMalloc failed");
-            GR_CHECK(hipMalloc(&d_sums, sizeof(unsigned long long) * static_cast<size_t>(graphio::ScanScratchWords(n + 1))),
-                     "KcoreProblem hipMalloc failed");
-            GR_CHECK(hipMemsetAsync(d_cursor, 0, sizeof(unsigned) * n1, stream), "KcoreProblem memset failed");
-            GR_CHECK(edge_sort.Reserve(m), "KcoreProblem sort scratch failed");
-            hipLaunchKernelGGL(tc::EdgeKeysKernel, dim3(Grid(m)), dim3(256), 0, stream, gs->d_row_offsets, gs->d_column_indices, static_cast<int>(n),
-                               m, col_bits, sentinel, edge_sort.Keys());
-            GR_CHECK(hipGetLastError(), "EdgeKeysKernel launch failed");
-            unsigned long long *d_sorted = nullptr;
-            GR_CHECK(edge_sort.Sort(m, key_bits, stream, &d_sorted), "KcoreProblem edge sort failed");
-            hipLaunchKernelGGL(graphio::FlagKernel, dim3(Grid(m)), dim3(256), 0, stream, d_sorted, m, sentinel, d_keep);
-            GR_CHECK(hipGetLastError(), "FlagKernel launch failed");
-            hipLaunchKernelGGL(tc::DegreeKernel, dim3(Grid(m)), dim3(256), 0, stream, d_sorted, d_keep, m, col_bits,
+            if ((retval = cursor.Alloc(n1))) return retval;
+            if ((retval = sums.Alloc(static_cast<size_t>(graphio::ScanScratchWords(n + 1))))) return retval;
+            GR_CHECK(hipMemsetAsync(cursor.p, 0, sizeof(unsigned) * n1, stream), "KcoreProblem memset failed");
+            if ((retval = pg.Keys(gs->d_row_offsets, gs->d_column_indices, m, stream))) return retval;
+            hipLaunchKernelGGL(tc::DegreeKernel, dim3(Grid(m)), dim3(256), 0, stream, pg.d_sorted, pg.d_keep, m, pg.col_bits,
                                reinterpret_cast<unsigned *>(ds->d_degrees));
             GR_CHECK(hipGetLastError(), "DegreeKernel launch failed");
-            GR_CHECK(graphio::DeviceExclusiveScan<int>(reinterpret_cast<unsigned *>(ds->d_degrees), ds->d_nro, n + 1, d_sums, stream),
+            GR_CHECK(graphio::DeviceExclusiveScan<int>(reinterpret_cast<unsigned *>(ds->d_degrees), ds->d_nro, n + 1, sums.p, stream),
                      "KcoreProblem offset scan failed");
             int entries = 0;  // 2M <= 2 * edges; edges is an int, and so is every offset: refuse what does not fit
             GR_CHECK(hipMemcpyAsync(&entries, ds->d_nro + n, sizeof(int), hipMemcpyDeviceToHost, stream), "KcoreProblem read-back failed");
@@ -173,20 +156,16 @@ struct KcoreProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
             simple_edges = entries / 2;
             if (entries > 0) {
                 GR_CHECK(hipMalloc(&ds->d_nci, sizeof(int) * static_cast<size_t>(entries)), "KcoreProblem hipMalloc d_nci failed");
-                hipLaunchKernelGGL(NeighbourScatterKernel, dim3(Grid(m)), dim3(256), 0, stream, d_sorted, d_keep, m, col_bits, ds->d_nro, d_cursor,
-                                   ds->d_nci);
+                hipLaunchKernelGGL(NeighbourScatterKernel, dim3(Grid(m)), dim3(256), 0, stream, pg.d_sorted, pg.d_keep, m, pg.col_bits, ds->d_nro,
+                                   cursor.p, ds->d_nci);
                 GR_CHECK(hipGetLastError(), "NeighbourScatterKernel launch failed");
             }
         }
         unsigned summary[3] = {0, 0, 0};
         if ((retval = Summary(ds->d_degrees, summary))) return retval;
-        GR_CHECK(hipEventRecord(ev[1], stream), "KcoreProblem hipEventRecord failed");
+        if ((retval = ev.Record(1, stream))) return retval;
         GR_CHECK(hipStreamSynchronize(stream), "KcoreProblem build sync failed");
-        float ms = 0;
-        GR_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]), "KcoreProblem hipEventElapsedTime failed");
-        build_ms = ms;
-        hipEventDestroy(ev[0]);
-        hipEventDestroy(ev[1]);
+        if ((retval = ev.Elapsed(0, 1, &build_ms))) return retval;
         max_degree = summary[0];
         min_degree = summary[1] == kNoLevel ? 0 : summary[1];
         zeros = summary[2];
@@ -194,9 +173,6 @@ struct KcoreProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         GR_CHECK(hipMalloc(&ds->d_trace_k, sizeof(int) * static_cast<size_t>(trace_capacity)), "KcoreProblem hipMalloc failed");
         GR_CHECK(hipMalloc(&ds->d_trace_tail, sizeof(int) * static_cast<size_t>(trace_capacity)), "KcoreProblem hipMalloc failed");
         GR_CHECK(hipMalloc(&ds->d_trace_clock, sizeof(unsigned long long) * static_cast<size_t>(trace_capacity)), "KcoreProblem hipMalloc failed");
-        if (d_keep) GR_CHECK(hipFree(d_keep), "KcoreProblem hipFree failed");
-        if (d_cursor) GR_CHECK(hipFree(d_cursor), "KcoreProblem hipFree failed");
-        if (d_sums) GR_CHECK(hipFree(d_sums), "KcoreProblem hipFree failed");
         return retval;
     }
 

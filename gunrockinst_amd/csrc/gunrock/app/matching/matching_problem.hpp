@@ -2,7 +2,7 @@
 //
 // The reference snapshot has no matching; the shape is this tree's Problem (compare app/maxflow/maxflow_problem.hpp).  The input CSR
 // is read as BCC and truss read it: the simple undirected graph G, with int weights in edge_values (NULL: 1 each).  Init validates
-// it and builds, with truss's build kernels (truss_functor.hpp is included, not changed), the M canonical pairs src[e] < dst[e] in
+// it and builds, with graphio::PairGraph (graphio/pair_graph.hpp), the M canonical pairs src[e] < dst[e] in
 // (src, dst) order and the neighbour CSR with the pair id on every entry; a pair's weight is the largest of its input entries.
 // Contract builds the coarse graph of the last Enact on the device and keeps it until the next Reset.
 #pragma once
@@ -11,11 +11,7 @@
 
 #include <gunrock/app/matching/matching_functor.hpp>
 #include <gunrock/app/problem_base.hpp>
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunused-function"  // (only the build kernels of truss and TC are used here)
-#include <gunrock/app/truss/truss_functor.hpp>
-#pragma clang diagnostic pop
-#include <gunrock/graphio/device_sort.hpp>
+#include <gunrock/graphio/pair_graph.hpp>
 
 namespace gunrock {
 namespace app {
@@ -115,119 +111,49 @@ struct MatchingProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         GR_CHECK(hipMalloc(&ds->d_active, sizeof(Active)), "MatchingProblem hipMalloc failed");
 
         // the CSR must be one: the build indexes with what it reads
-        int bad = 0;
-        GR_CHECK(hipMemsetAsync(ds->d_words, 0, sizeof(unsigned) * W_COUNT, stream), "MatchingProblem memset failed");
-        hipLaunchKernelGGL(tc::ValidateCsrKernel, dim3(Grid((n > m ? n : m) + 1)), dim3(256), 0, stream, gs->d_row_offsets, gs->d_column_indices,
-                           n, m, reinterpret_cast<int *>(ds->d_words));
-        GR_CHECK(hipGetLastError(), "ValidateCsrKernel launch failed");
-        GR_CHECK(hipMemcpyAsync(&bad, ds->d_words, sizeof(int), hipMemcpyDeviceToHost, stream), "MatchingProblem read-back failed");
-        GR_CHECK(hipStreamSynchronize(stream), "MatchingProblem read-back sync failed");
+        bool bad = false;
+        if ((retval = graphio::DeviceValidateCsr(gs->d_row_offsets, gs->d_column_indices, n, m, reinterpret_cast<int *>(ds->d_words), stream, &bad)))
+            return retval;
         if (bad) {
             malformed = 1;
             return hipErrorInvalidValue;
         }
 
-        // (the events and the build's scratch go on every path out: run() may return early, release() follows it)
-        hipEvent_t ev[2] = {nullptr, nullptr};
-        unsigned *d_keep = nullptr, *d_deg = nullptr;
-        unsigned long long *d_pos = nullptr, *d_sums = nullptr, *d_ckeys = nullptr;
-        int *d_up = nullptr, *d_low = nullptr;
         long long M = 0;
-        auto release = [&]() {
-            for (int i = 0; i < 2; ++i)
-                if (ev[i]) hipEventDestroy(ev[i]);
-            void *scratch[] = {d_keep, d_pos, d_sums, d_ckeys, d_up, d_low, d_deg};
-            for (void *b : scratch)
-                if (b) util::GRError(hipFree(b), "MatchingProblem hipFree failed", __FILE__, __LINE__);
-        };
-        auto run = [&]() -> hipError_t {
-            hipError_t retval = hipSuccess;
-            for (int i = 0; i < 2; ++i) GR_CHECK(hipEventCreate(&ev[i]), "MatchingProblem hipEventCreate failed");
-            GR_CHECK(hipEventRecord(ev[0], stream), "MatchingProblem hipEventRecord failed");
-
-            GR_CHECK(hipMalloc(&ds->d_nro, sizeof(int) * (n1 + 1)), "MatchingProblem hipMalloc d_nro failed");
-            GR_CHECK(hipMemsetAsync(ds->d_nro, 0, sizeof(int) * (n1 + 1), stream), "MatchingProblem memset failed");
-
-            // (the sequence of BccProblem::Build: the pairs and their neighbour CSR)
-            int col_bits = 1;
-            while ((1ll << col_bits) < n) ++col_bits;
-            const int key_bits = 2 * col_bits;  // <= 62
-            const unsigned long long sentinel = (1ull << key_bits) - 1ull;  // min = max = 2^cb - 1: never a pair
-            graphio::DeviceKeySort edge_sort;
-            if (m > 0) {
-                const long long scan_words = m > n + 1 ? m : n + 1;
-                GR_CHECK(hipMalloc(&d_keep, sizeof(unsigned) * static_cast<size_t>(m)), "MatchingProblem hipMalloc failed");
-                GR_CHECK(hipMalloc(&d_pos, sizeof(unsigned long long) * static_cast<size_t>(m)), "MatchingProblem hipMalloc failed");
-                GR_CHECK(hipMalloc(&d_sums, sizeof(unsigned long long) * static_cast<size_t>(graphio::ScanScratchWords(scan_words))),
-                         "MatchingProblem hipMalloc failed");
-                GR_CHECK(edge_sort.Reserve(m), "MatchingProblem sort scratch failed");
-                hipLaunchKernelGGL(tc::EdgeKeysKernel, dim3(Grid(m)), dim3(256), 0, stream, gs->d_row_offsets, gs->d_column_indices, static_cast<int>(n),
-                                   m, col_bits, sentinel, edge_sort.Keys());
-                GR_CHECK(hipGetLastError(), "EdgeKeysKernel launch failed");
-                unsigned long long *d_sorted = nullptr;
-                GR_CHECK(edge_sort.Sort(m, key_bits, stream, &d_sorted), "MatchingProblem edge sort failed");
-                hipLaunchKernelGGL(graphio::FlagKernel, dim3(Grid(m)), dim3(256), 0, stream, d_sorted, m, sentinel, d_keep);
-                GR_CHECK(hipGetLastError(), "FlagKernel launch failed");
-                GR_CHECK(graphio::DeviceExclusiveScan<unsigned long long>(d_keep, d_pos, m, d_sums, stream), "MatchingProblem flag scan failed");
-                unsigned long long last_pos = 0;
-                unsigned last_keep = 0;
-                GR_CHECK(hipMemcpyAsync(&last_pos, d_pos + (m - 1), sizeof(last_pos), hipMemcpyDeviceToHost, stream), "MatchingProblem read-back failed");
-                GR_CHECK(hipMemcpyAsync(&last_keep, d_keep + (m - 1), sizeof(last_keep), hipMemcpyDeviceToHost, stream), "MatchingProblem read-back failed");
-                GR_CHECK(hipStreamSynchronize(stream), "MatchingProblem read-back sync failed");
-                M = static_cast<long long>(last_pos) + last_keep;
-                if (2 * M > 0x7FFFFFFFll) return hipErrorInvalidValue;  // every offset of the 2M entries is an int
-                if (M > 0) {
-                    const size_t ms = static_cast<size_t>(M);
-                    GR_CHECK(hipMalloc(&d_ckeys, sizeof(unsigned long long) * ms), "MatchingProblem hipMalloc failed");
-                    GR_CHECK(hipMalloc(&ds->d_src, sizeof(int) * ms), "MatchingProblem hipMalloc d_src failed");
-                    GR_CHECK(hipMalloc(&ds->d_dst, sizeof(int) * ms), "MatchingProblem hipMalloc d_dst failed");
-                    GR_CHECK(hipMalloc(&ds->d_nci, sizeof(int) * 2 * ms), "MatchingProblem hipMalloc d_nci failed");
-                    GR_CHECK(hipMalloc(&ds->d_neid, sizeof(int) * 2 * ms), "MatchingProblem hipMalloc d_neid failed");
-                    GR_CHECK(hipMalloc(&d_up, sizeof(int) * (n1 + 1)), "MatchingProblem hipMalloc failed");
-                    GR_CHECK(hipMalloc(&d_low, sizeof(int) * (n1 + 1)), "MatchingProblem hipMalloc failed");
-                    GR_CHECK(hipMalloc(&d_deg, sizeof(unsigned) * (n1 + 1)), "MatchingProblem hipMalloc failed");
-                    hipLaunchKernelGGL(truss::CanonicalKernel, dim3(Grid(m)), dim3(256), 0, stream, d_sorted, d_keep, d_pos, m, col_bits, d_ckeys,
-                                       ds->d_src, ds->d_dst);
-                    GR_CHECK(hipGetLastError(), "CanonicalKernel launch failed");
-                    hipLaunchKernelGGL(truss::SwapKeysKernel, dim3(Grid(M)), dim3(256), 0, stream, d_ckeys, M, col_bits, edge_sort.Keys());
-                    GR_CHECK(hipGetLastError(), "SwapKeysKernel launch failed");
-                    unsigned long long *d_skeys = nullptr;
-                    GR_CHECK(edge_sort.Sort(M, key_bits, stream, &d_skeys), "MatchingProblem edge sort failed");
-                    hipLaunchKernelGGL(truss::RowStartsKernel, dim3(Grid(n + 1)), dim3(256), 0, stream, d_ckeys, d_skeys, M, n, col_bits, d_up, d_low);
-                    GR_CHECK(hipGetLastError(), "RowStartsKernel launch failed");
-                    hipLaunchKernelGGL(truss::DegreesKernel, dim3(Grid(n + 1)), dim3(256), 0, stream, d_up, d_low, n, d_deg);
-                    GR_CHECK(hipGetLastError(), "DegreesKernel launch failed");
-                    GR_CHECK(graphio::DeviceExclusiveScan<int>(d_deg, ds->d_nro, n + 1, d_sums, stream), "MatchingProblem offset scan failed");
-                    hipLaunchKernelGGL(truss::FillRowsKernel, dim3(Grid(M)), dim3(256), 0, stream, d_ckeys, d_skeys, M, col_bits, d_up, d_low, ds->d_nro,
-                                       ds->d_nci, ds->d_neid);
-                    GR_CHECK(hipGetLastError(), "FillRowsKernel launch failed");
-
-                    // the weights: every input entry finds its pair by bisecting the sorted row (the key sort carries no payload) and
-                    // raises the pair's weight to its own, as max-flow's build adds its capacities up
-                    GR_CHECK(hipMalloc(&ds->d_pw, sizeof(int) * ms), "MatchingProblem hipMalloc d_pw failed");
-                    hipLaunchKernelGGL(FillKernel, dim3(Grid(M)), dim3(256), 0, stream, ds->d_pw, M, weighted ? INT_MIN : 1);
-                    GR_CHECK(hipGetLastError(), "FillKernel launch failed");
-                    if (weighted) {
-                        GR_CHECK(hipMalloc(&ds->d_ew, sizeof(int) * 2 * ms), "MatchingProblem hipMalloc d_ew failed");
-                        hipLaunchKernelGGL(PairWeightKernel, dim3(Grid(m)), dim3(256), 0, stream, gs->d_row_offsets, gs->d_column_indices,
-                                           gs->d_edge_values, static_cast<int>(n), m, ds->d_nro, ds->d_nci, ds->d_neid, ds->d_pw);
-                        GR_CHECK(hipGetLastError(), "PairWeightKernel launch failed");
-                        hipLaunchKernelGGL(EntryWeightKernel, dim3(Grid(2 * M)), dim3(256), 0, stream, ds->d_neid, ds->d_pw, 2 * M, ds->d_ew);
-                        GR_CHECK(hipGetLastError(), "EntryWeightKernel launch failed");
-                    }
+        {  // (the build's scratch goes with this scope)
+            graphio::BuildEvents ev;
+            if ((retval = ev.Create(2))) return retval;
+            if ((retval = ev.Record(0, stream))) return retval;
+            graphio::PairGraph pg(n);
+            if ((retval = pg.Keys(gs->d_row_offsets, gs->d_column_indices, m, stream))) return retval;
+            if ((retval = pg.Pairs(stream))) return retval;
+            if ((retval = pg.Rows(stream))) return retval;
+            ds->d_src = graphio::Take(pg.d_src);
+            ds->d_dst = graphio::Take(pg.d_dst);
+            ds->d_nro = graphio::Take(pg.d_ro);
+            ds->d_nci = graphio::Take(pg.d_ci);
+            ds->d_neid = graphio::Take(pg.d_eid);
+            pairs = M = pg.pairs;
+            if (M > 0) {
+                // the weights: every input entry finds its pair by bisecting the sorted row (the key sort carries no payload) and
+                // raises the pair's weight to its own, as max-flow's build adds its capacities up
+                const size_t ms = static_cast<size_t>(M);
+                GR_CHECK(hipMalloc(&ds->d_pw, sizeof(int) * ms), "MatchingProblem hipMalloc d_pw failed");
+                hipLaunchKernelGGL(FillKernel, dim3(Grid(M)), dim3(256), 0, stream, ds->d_pw, M, weighted ? INT_MIN : 1);
+                GR_CHECK(hipGetLastError(), "FillKernel launch failed");
+                if (weighted) {
+                    GR_CHECK(hipMalloc(&ds->d_ew, sizeof(int) * 2 * ms), "MatchingProblem hipMalloc d_ew failed");
+                    hipLaunchKernelGGL(PairWeightKernel, dim3(Grid(m)), dim3(256), 0, stream, gs->d_row_offsets, gs->d_column_indices,
+                                       gs->d_edge_values, static_cast<int>(n), m, ds->d_nro, ds->d_nci, ds->d_neid, ds->d_pw);
+                    GR_CHECK(hipGetLastError(), "PairWeightKernel launch failed");
+                    hipLaunchKernelGGL(EntryWeightKernel, dim3(Grid(2 * M)), dim3(256), 0, stream, ds->d_neid, ds->d_pw, 2 * M, ds->d_ew);
+                    GR_CHECK(hipGetLastError(), "EntryWeightKernel launch failed");
                 }
             }
-            pairs = M;
-            GR_CHECK(hipEventRecord(ev[1], stream), "MatchingProblem hipEventRecord failed");
+            if ((retval = ev.Record(1, stream))) return retval;
             GR_CHECK(hipStreamSynchronize(stream), "MatchingProblem build sync failed");
-            float ms = 0;
-            GR_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]), "MatchingProblem hipEventElapsedTime failed");
-            build_ms = ms;
-            return retval;
-        };
-        retval = run();
-        release();
-        if (retval) return retval;
+            if ((retval = ev.Elapsed(0, 1, &build_ms))) return retval;
+        }
 
         const size_t m1 = static_cast<size_t>(M > 0 ? M : 1);
         int **vertex_arrays[] = {&ds->d_mate, &ds->d_tgt, &ds->d_pp, &ds->d_cur, &ds->d_list[0], &ds->d_list[1]};
@@ -326,119 +252,80 @@ struct MatchingProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         coarse_entries = 0;
     }
 
-    // The coarse graph of the matching: map[] from a flag and a scan over the representatives, the coarse pairs from a sort, a flag
-    // pass and a scan over the fine pairs' images (SccProblem::Condensation's sequence), their weights by bisection and a 64-bit
-    // atomic add, the mirrored CSR by truss's row kernels.  d_vertex_weights is on the device (NULL: 1 each).  *overflow is set when a
-    // sum left int32: then nothing is kept.
+    // The coarse graph of the matching, kept until the next Reset.  d_vertex_weights is on the device (NULL: 1 each).  *overflow is
+    // set when a sum left int32: then nothing is kept.
     hipError_t Contract(const int *d_vertex_weights, bool *overflow)
+    {
+        *overflow = false;
+        DropCoarse();
+        const hipError_t retval = BuildCoarse(d_vertex_weights, overflow);
+        if (retval || *overflow) DropCoarse();
+        return retval;
+    }
+
+    // map[] from a flag and a scan over the representatives, the coarse pairs and their mirrored CSR by graphio::PairGraph from the
+    // fine pairs' images, their weights by bisection and a 64-bit atomic add
+    hipError_t BuildCoarse(const int *d_vertex_weights, bool *overflow)
     {
         hipError_t retval = hipSuccess;
         DataSlice *ds = data_slices[0];
         hipStream_t stream = this->graph_slices[0]->stream;
         const long long n = this->nodes, M = pairs;
-        *overflow = false;
-        DropCoarse();
-        graphio::DeviceKeySort sort;
-        unsigned *d_keep = nullptr, *d_deg = nullptr;
-        unsigned long long *d_pos = nullptr, *d_sums = nullptr, *d_ckeys = nullptr, *d_w64 = nullptr;
-        int *d_rank = nullptr, *d_up = nullptr, *d_low = nullptr, *d_csrc = nullptr, *d_cdst = nullptr, *d_ceid = nullptr;
-        auto release = [&]() {
-            void *bufs[] = {d_keep, d_deg, d_pos, d_sums, d_ckeys, d_w64, d_rank, d_up, d_low, d_csrc, d_cdst, d_ceid};
-            for (void *b : bufs)
-                if (b) util::GRError(hipFree(b), "MatchingProblem hipFree failed", __FILE__, __LINE__);
-        };
-        auto run = [&]() -> hipError_t {
-            hipError_t retval = hipSuccess;
-            const long long most = (M > n ? M : n) + 1;
-            const long long scan_tiles_n = (n + graphio::kScanTile - 1) / graphio::kScanTile;
-            GR_CHECK(hipMalloc(&d_keep, sizeof(unsigned) * static_cast<size_t>(most)), "MatchingProblem hipMalloc failed");
-            GR_CHECK(hipMalloc(&d_pos, sizeof(unsigned long long) * static_cast<size_t>(most)), "MatchingProblem hipMalloc failed");
-            GR_CHECK(hipMalloc(&d_sums, sizeof(unsigned long long) * static_cast<size_t>(graphio::ScanScratchWords(most))), "MatchingProblem hipMalloc failed");
-            GR_CHECK(hipMalloc(&d_rank, sizeof(int) * static_cast<size_t>(n)), "MatchingProblem hipMalloc failed");
-            GR_CHECK(hipMalloc(&ds->d_map, sizeof(int) * static_cast<size_t>(n)), "MatchingProblem hipMalloc failed");
-            GR_CHECK(hipMemsetAsync(ds->d_words + W_FLAG, 0, sizeof(unsigned), stream), "MatchingProblem memset failed");
+        const long long scan_tiles_n = (n + graphio::kScanTile - 1) / graphio::kScanTile;
+        graphio::DeviceScratch<unsigned> rep;
+        graphio::DeviceScratch<unsigned long long> sums, w64;
+        graphio::DeviceScratch<int> rank;
+        if ((retval = rep.Alloc(static_cast<size_t>(n)))) return retval;
+        if ((retval = sums.Alloc(static_cast<size_t>(graphio::ScanScratchWords(n))))) return retval;
+        if ((retval = rank.Alloc(static_cast<size_t>(n)))) return retval;
+        GR_CHECK(hipMalloc(&ds->d_map, sizeof(int) * static_cast<size_t>(n)), "MatchingProblem hipMalloc failed");
+        GR_CHECK(hipMemsetAsync(ds->d_words + W_FLAG, 0, sizeof(unsigned), stream), "MatchingProblem memset failed");
 
-            // the representatives and their ranks (the total is behind the scan's tile offsets)
-            hipLaunchKernelGGL(RepFlagKernel, dim3(Grid(n)), dim3(256), 0, stream, ds->d_mate, n, d_keep);
-            GR_CHECK(hipGetLastError(), "RepFlagKernel launch failed");
-            GR_CHECK(graphio::DeviceExclusiveScan<int>(d_keep, d_rank, n, d_sums, stream), "MatchingProblem rank scan failed");
-            unsigned long long total = 0;
-            GR_CHECK(hipMemcpyAsync(&total, d_sums + scan_tiles_n, sizeof(total), hipMemcpyDeviceToHost, stream), "MatchingProblem read total failed");
-            GR_CHECK(hipStreamSynchronize(stream), "MatchingProblem Contract sync failed");
-            const long long nc = static_cast<long long>(total);
-            GR_CHECK(hipMalloc(&ds->d_vweight, sizeof(int) * static_cast<size_t>(nc)), "MatchingProblem hipMalloc failed");
-            GR_CHECK(hipMalloc(&ds->d_cro, sizeof(int) * static_cast<size_t>(nc + 1)), "MatchingProblem hipMalloc failed");
-            GR_CHECK(hipMemsetAsync(ds->d_cro, 0, sizeof(int) * static_cast<size_t>(nc + 1), stream), "MatchingProblem memset failed");
-            hipLaunchKernelGGL(MapKernel, dim3(Grid(n)), dim3(256), 0, stream, ds->d_mate, d_rank, d_vertex_weights, n, ds->d_map, ds->d_vweight,
-                               ds->d_words + W_FLAG);
-            GR_CHECK(hipGetLastError(), "MapKernel launch failed");
+        // the representatives and their ranks (the total is behind the scan's tile offsets)
+        hipLaunchKernelGGL(RepFlagKernel, dim3(Grid(n)), dim3(256), 0, stream, ds->d_mate, n, rep.p);
+        GR_CHECK(hipGetLastError(), "RepFlagKernel launch failed");
+        GR_CHECK(graphio::DeviceExclusiveScan<int>(rep.p, rank.p, n, sums.p, stream), "MatchingProblem rank scan failed");
+        unsigned long long total = 0;
+        GR_CHECK(hipMemcpyAsync(&total, sums.p + scan_tiles_n, sizeof(total), hipMemcpyDeviceToHost, stream), "MatchingProblem read total failed");
+        GR_CHECK(hipStreamSynchronize(stream), "MatchingProblem Contract sync failed");
+        const long long nc = static_cast<long long>(total);
+        GR_CHECK(hipMalloc(&ds->d_vweight, sizeof(int) * static_cast<size_t>(nc)), "MatchingProblem hipMalloc failed");
+        hipLaunchKernelGGL(MapKernel, dim3(Grid(n)), dim3(256), 0, stream, ds->d_mate, rank.p, d_vertex_weights, n, ds->d_map, ds->d_vweight,
+                           ds->d_words + W_FLAG);
+        GR_CHECK(hipGetLastError(), "MapKernel launch failed");
 
-            // the coarse pairs
-            long long Mc = 0;
-            int col_bits = 1;
-            while ((1ll << col_bits) < nc) ++col_bits;
-            const int key_bits = 2 * col_bits;
-            const unsigned long long sentinel = (1ull << key_bits) - 1ull;
-            if (M > 0) {
-                GR_CHECK(sort.Reserve(M), "MatchingProblem sort scratch failed");
-                hipLaunchKernelGGL(CoarseKeysKernel, dim3(Grid(M)), dim3(256), 0, stream, ds->d_src, ds->d_dst, ds->d_map, M, col_bits, sentinel, sort.Keys());
-                GR_CHECK(hipGetLastError(), "CoarseKeysKernel launch failed");
-                unsigned long long *d_sorted = nullptr;
-                GR_CHECK(sort.Sort(M, key_bits, stream, &d_sorted), "MatchingProblem key sort failed");
-                hipLaunchKernelGGL(graphio::FlagKernel, dim3(Grid(M)), dim3(256), 0, stream, d_sorted, M, sentinel, d_keep);
-                GR_CHECK(hipGetLastError(), "FlagKernel launch failed");
-                GR_CHECK(graphio::DeviceExclusiveScan<unsigned long long>(d_keep, d_pos, M, d_sums, stream), "MatchingProblem flag scan failed");
-                const long long scan_tiles = (M + graphio::kScanTile - 1) / graphio::kScanTile;
-                GR_CHECK(hipMemcpyAsync(&total, d_sums + scan_tiles, sizeof(total), hipMemcpyDeviceToHost, stream), "MatchingProblem read total failed");
-                GR_CHECK(hipStreamSynchronize(stream), "MatchingProblem Contract sync failed");
-                Mc = static_cast<long long>(total);
-                if (Mc > 0) {
-                    const size_t mc = static_cast<size_t>(Mc);
-                    GR_CHECK(hipMalloc(&d_ckeys, sizeof(unsigned long long) * mc), "MatchingProblem hipMalloc failed");
-                    GR_CHECK(hipMalloc(&d_w64, sizeof(unsigned long long) * mc), "MatchingProblem hipMalloc failed");
-                    GR_CHECK(hipMemsetAsync(d_w64, 0, sizeof(unsigned long long) * mc, stream), "MatchingProblem memset failed");
-                    GR_CHECK(hipMalloc(&d_csrc, sizeof(int) * mc), "MatchingProblem hipMalloc failed");
-                    GR_CHECK(hipMalloc(&d_cdst, sizeof(int) * mc), "MatchingProblem hipMalloc failed");
-                    GR_CHECK(hipMalloc(&d_ceid, sizeof(int) * 2 * mc), "MatchingProblem hipMalloc failed");
-                    GR_CHECK(hipMalloc(&d_up, sizeof(int) * static_cast<size_t>(nc + 1)), "MatchingProblem hipMalloc failed");
-                    GR_CHECK(hipMalloc(&d_low, sizeof(int) * static_cast<size_t>(nc + 1)), "MatchingProblem hipMalloc failed");
-                    GR_CHECK(hipMalloc(&d_deg, sizeof(unsigned) * static_cast<size_t>(nc + 1)), "MatchingProblem hipMalloc failed");
-                    GR_CHECK(hipMalloc(&ds->d_cci, sizeof(int) * 2 * mc), "MatchingProblem hipMalloc failed");
-                    GR_CHECK(hipMalloc(&ds->d_cw, sizeof(int) * 2 * mc), "MatchingProblem hipMalloc failed");
-                    hipLaunchKernelGGL(truss::CanonicalKernel, dim3(Grid(M)), dim3(256), 0, stream, d_sorted, d_keep, d_pos, M, col_bits, d_ckeys, d_csrc,
-                                       d_cdst);
-                    GR_CHECK(hipGetLastError(), "CanonicalKernel launch failed");
-                    hipLaunchKernelGGL(CoarseWeightKernel, dim3(Grid(M)), dim3(256), 0, stream, ds->d_src, ds->d_dst, ds->d_pw, ds->d_map, M, col_bits,
-                                       sentinel, d_ckeys, Mc, d_w64);
-                    GR_CHECK(hipGetLastError(), "CoarseWeightKernel launch failed");
-                    // the mirrored rows (the sequence of the build, on the coarse pairs)
-                    hipLaunchKernelGGL(truss::SwapKeysKernel, dim3(Grid(Mc)), dim3(256), 0, stream, d_ckeys, Mc, col_bits, sort.Keys());
-                    GR_CHECK(hipGetLastError(), "SwapKeysKernel launch failed");
-                    unsigned long long *d_skeys = nullptr;
-                    GR_CHECK(sort.Sort(Mc, key_bits, stream, &d_skeys), "MatchingProblem key sort failed");
-                    hipLaunchKernelGGL(truss::RowStartsKernel, dim3(Grid(nc + 1)), dim3(256), 0, stream, d_ckeys, d_skeys, Mc, nc, col_bits, d_up, d_low);
-                    GR_CHECK(hipGetLastError(), "RowStartsKernel launch failed");
-                    hipLaunchKernelGGL(truss::DegreesKernel, dim3(Grid(nc + 1)), dim3(256), 0, stream, d_up, d_low, nc, d_deg);
-                    GR_CHECK(hipGetLastError(), "DegreesKernel launch failed");
-                    GR_CHECK(graphio::DeviceExclusiveScan<int>(d_deg, ds->d_cro, nc + 1, d_sums, stream), "MatchingProblem offset scan failed");
-                    hipLaunchKernelGGL(truss::FillRowsKernel, dim3(Grid(Mc)), dim3(256), 0, stream, d_ckeys, d_skeys, Mc, col_bits, d_up, d_low, ds->d_cro,
-                                       ds->d_cci, d_ceid);
-                    GR_CHECK(hipGetLastError(), "FillRowsKernel launch failed");
-                    hipLaunchKernelGGL(CoarseEntriesKernel, dim3(Grid(2 * Mc)), dim3(256), 0, stream, d_ceid, d_w64, 2 * Mc, ds->d_cw, ds->d_words + W_FLAG);
-                    GR_CHECK(hipGetLastError(), "CoarseEntriesKernel launch failed");
-                }
-            }
-            unsigned flag = 0;
-            GR_CHECK(hipMemcpyAsync(&flag, ds->d_words + W_FLAG, sizeof(flag), hipMemcpyDeviceToHost, stream), "MatchingProblem read-back failed");
-            GR_CHECK(hipStreamSynchronize(stream), "MatchingProblem Contract sync failed");
-            *overflow = flag != 0;
-            coarse_nodes = nc;
-            coarse_entries = 2 * Mc;
-            return retval;
-        };
-        retval = run();
-        release();
-        if (retval || *overflow) DropCoarse();
+        // the coarse pairs: the fine pairs' images as keys, then the build's steps on them
+        graphio::PairGraph pg(nc);
+        if (M > 0) {
+            if ((retval = pg.Reserve(M))) return retval;
+            hipLaunchKernelGGL(CoarseKeysKernel, dim3(Grid(M)), dim3(256), 0, stream, ds->d_src, ds->d_dst, ds->d_map, M, pg.col_bits, pg.sentinel,
+                               pg.sort.Keys());
+            GR_CHECK(hipGetLastError(), "CoarseKeysKernel launch failed");
+            if ((retval = pg.SortKeys(stream))) return retval;
+            if ((retval = pg.Pairs(stream))) return retval;
+        }
+        const long long Mc = pg.pairs;
+        if (Mc > 0) {
+            if ((retval = w64.Alloc(static_cast<size_t>(Mc)))) return retval;
+            GR_CHECK(hipMemsetAsync(w64.p, 0, sizeof(unsigned long long) * static_cast<size_t>(Mc), stream), "MatchingProblem memset failed");
+            hipLaunchKernelGGL(CoarseWeightKernel, dim3(Grid(M)), dim3(256), 0, stream, ds->d_src, ds->d_dst, ds->d_pw, ds->d_map, M, pg.col_bits,
+                               pg.sentinel, pg.d_ckeys, Mc, w64.p);
+            GR_CHECK(hipGetLastError(), "CoarseWeightKernel launch failed");
+        }
+        if ((retval = pg.Rows(stream))) return retval;
+        ds->d_cro = graphio::Take(pg.d_ro);
+        ds->d_cci = graphio::Take(pg.d_ci);
+        if (Mc > 0) {
+            GR_CHECK(hipMalloc(&ds->d_cw, sizeof(int) * 2 * static_cast<size_t>(Mc)), "MatchingProblem hipMalloc failed");
+            hipLaunchKernelGGL(CoarseEntriesKernel, dim3(Grid(2 * Mc)), dim3(256), 0, stream, pg.d_eid, w64.p, 2 * Mc, ds->d_cw, ds->d_words + W_FLAG);
+            GR_CHECK(hipGetLastError(), "CoarseEntriesKernel launch failed");
+        }
+        unsigned flag = 0;
+        GR_CHECK(hipMemcpyAsync(&flag, ds->d_words + W_FLAG, sizeof(flag), hipMemcpyDeviceToHost, stream), "MatchingProblem read-back failed");
+        GR_CHECK(hipStreamSynchronize(stream), "MatchingProblem Contract sync failed");
+        *overflow = flag != 0;
+        coarse_nodes = nc;
+        coarse_entries = 2 * Mc;
         return retval;
     }
 

@@ -1,8 +1,8 @@
 // app/maxflow/maxflow_problem.hpp -- device data for the maximum flow and the minimum cut.
 //
 // The reference snapshot has no app/mf; the shape is this tree's Problem (compare app/bcc/bcc_problem.hpp).  The input CSR is read
-// as a directed multigraph with int capacities in edge_values (NULL: 1 each).  Init validates it and builds, with truss's build
-// kernels (truss_functor.hpp is included, not changed), the M canonical pairs a[p] < b[p] in (a, b) order and the residual CSR: the
+// as a directed multigraph with int capacities in edge_values (NULL: 1 each).  Init validates it and builds, with
+// graphio::PairGraph (graphio/pair_graph.hpp), the M canonical pairs a[p] < b[p] in (a, b) order and the residual CSR: the
 // symmetric neighbour CSR over the pairs, rows ascending, with the capacity and the reverse entry on every entry.  The input CSR
 // stays on the device (borrowed after InitFromDevice: the caller keeps it alive) because arc_flow[] is per input entry.
 #pragma once
@@ -11,11 +11,7 @@
 
 #include <gunrock/app/maxflow/maxflow_functor.hpp>
 #include <gunrock/app/problem_base.hpp>
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunused-function"  // (only the build kernels of truss and TC are used here)
-#include <gunrock/app/truss/truss_functor.hpp>
-#pragma clang diagnostic pop
-#include <gunrock/graphio/device_sort.hpp>
+#include <gunrock/graphio/pair_graph.hpp>
 
 namespace gunrock {
 namespace app {
@@ -120,114 +116,53 @@ struct MaxflowProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         GR_CHECK(hipMalloc(&ds->d_active, sizeof(Active)), "MaxflowProblem hipMalloc failed");
 
         // the CSR must be one: the build indexes with what it reads
-        int bad = 0;
-        GR_CHECK(hipMemsetAsync(ds->d_words, 0, sizeof(unsigned) * W_COUNT, stream), "MaxflowProblem memset failed");
-        hipLaunchKernelGGL(tc::ValidateCsrKernel, dim3(Grid((n > m ? n : m) + 1)), dim3(256), 0, stream, gs->d_row_offsets, gs->d_column_indices,
-                           n, m, reinterpret_cast<int *>(ds->d_words));
-        GR_CHECK(hipGetLastError(), "ValidateCsrKernel launch failed");
-        GR_CHECK(hipMemcpyAsync(&bad, ds->d_words, sizeof(int), hipMemcpyDeviceToHost, stream), "MaxflowProblem read-back failed");
-        GR_CHECK(hipStreamSynchronize(stream), "MaxflowProblem read-back sync failed");
+        bool bad = false;
+        GR_CHECK(hipMemsetAsync(ds->d_words, 0, sizeof(unsigned) * W_COUNT, stream), "MaxflowProblem memset failed");  // (W_BAD, for the build)
+        if ((retval = graphio::DeviceValidateCsr(gs->d_row_offsets, gs->d_column_indices, n, m, reinterpret_cast<int *>(ds->d_words), stream, &bad)))
+            return retval;
         if (bad) {
             malformed = 1;
             return hipErrorInvalidValue;
         }
 
-        // (the events and the build's scratch go on every path out: run() may return early, release() follows it)
-        hipEvent_t ev[2] = {nullptr, nullptr};
-        unsigned *d_keep = nullptr, *d_deg = nullptr;
-        unsigned long long *d_pos = nullptr, *d_sums = nullptr, *d_ckeys = nullptr, *d_cap64 = nullptr;
-        int *d_up = nullptr, *d_low = nullptr;
         long long M = 0;
-        auto release = [&]() {
-            for (int i = 0; i < 2; ++i)
-                if (ev[i]) hipEventDestroy(ev[i]);
-            void *scratch[] = {d_keep, d_pos, d_sums, d_ckeys, d_up, d_low, d_deg, d_cap64};
-            for (void *b : scratch)
-                if (b) util::GRError(hipFree(b), "MaxflowProblem hipFree failed", __FILE__, __LINE__);
-        };
-        auto run = [&]() -> hipError_t {
-            hipError_t retval = hipSuccess;
-            for (int i = 0; i < 2; ++i) GR_CHECK(hipEventCreate(&ev[i]), "MaxflowProblem hipEventCreate failed");
-            GR_CHECK(hipEventRecord(ev[0], stream), "MaxflowProblem hipEventRecord failed");
-
-            GR_CHECK(hipMalloc(&ds->d_nro, sizeof(int) * (n1 + 1)), "MaxflowProblem hipMalloc d_nro failed");
-            GR_CHECK(hipMemsetAsync(ds->d_nro, 0, sizeof(int) * (n1 + 1), stream), "MaxflowProblem memset failed");
-
-            // (the sequence of BccProblem::Build: the pairs and their neighbour CSR)
-            int col_bits = 1;
-            while ((1ll << col_bits) < n) ++col_bits;
-            const int key_bits = 2 * col_bits;  // <= 62
-            const unsigned long long sentinel = (1ull << key_bits) - 1ull;  // min = max = 2^cb - 1: never a pair
-            graphio::DeviceKeySort edge_sort;
+        {  // (the build's scratch goes with this scope)
+            graphio::BuildEvents ev;
+            if ((retval = ev.Create(2))) return retval;
+            if ((retval = ev.Record(0, stream))) return retval;
+            graphio::PairGraph pg(n);
+            graphio::DeviceScratch<unsigned long long> cap64;
+            if ((retval = pg.Keys(gs->d_row_offsets, gs->d_column_indices, m, stream))) return retval;
+            if ((retval = pg.Pairs(stream))) return retval;
+            if ((retval = pg.Rows(stream))) return retval;
+            ds->d_a = graphio::Take(pg.d_src);
+            ds->d_b = graphio::Take(pg.d_dst);
+            ds->d_nro = graphio::Take(pg.d_ro);
+            ds->d_nci = graphio::Take(pg.d_ci);
+            ds->d_neid = graphio::Take(pg.d_eid);
+            M = pg.pairs;
             if (m > 0) {
-                const long long scan_words = m > n + 1 ? m : n + 1;
-                GR_CHECK(hipMalloc(&d_keep, sizeof(unsigned) * static_cast<size_t>(m)), "MaxflowProblem hipMalloc failed");
-                GR_CHECK(hipMalloc(&d_pos, sizeof(unsigned long long) * static_cast<size_t>(m)), "MaxflowProblem hipMalloc failed");
-                GR_CHECK(hipMalloc(&d_sums, sizeof(unsigned long long) * static_cast<size_t>(graphio::ScanScratchWords(scan_words))),
-                         "MaxflowProblem hipMalloc failed");
-                GR_CHECK(edge_sort.Reserve(m), "MaxflowProblem sort scratch failed");
-                hipLaunchKernelGGL(tc::EdgeKeysKernel, dim3(Grid(m)), dim3(256), 0, stream, gs->d_row_offsets, gs->d_column_indices, static_cast<int>(n),
-                                   m, col_bits, sentinel, edge_sort.Keys());
-                GR_CHECK(hipGetLastError(), "EdgeKeysKernel launch failed");
-                unsigned long long *d_sorted = nullptr;
-                GR_CHECK(edge_sort.Sort(m, key_bits, stream, &d_sorted), "MaxflowProblem edge sort failed");
-                hipLaunchKernelGGL(graphio::FlagKernel, dim3(Grid(m)), dim3(256), 0, stream, d_sorted, m, sentinel, d_keep);
-                GR_CHECK(hipGetLastError(), "FlagKernel launch failed");
-                GR_CHECK(graphio::DeviceExclusiveScan<unsigned long long>(d_keep, d_pos, m, d_sums, stream), "MaxflowProblem flag scan failed");
-                unsigned long long last_pos = 0;
-                unsigned last_keep = 0;
-                GR_CHECK(hipMemcpyAsync(&last_pos, d_pos + (m - 1), sizeof(last_pos), hipMemcpyDeviceToHost, stream), "MaxflowProblem read-back failed");
-                GR_CHECK(hipMemcpyAsync(&last_keep, d_keep + (m - 1), sizeof(last_keep), hipMemcpyDeviceToHost, stream), "MaxflowProblem read-back failed");
-                GR_CHECK(hipStreamSynchronize(stream), "MaxflowProblem read-back sync failed");
-                M = static_cast<long long>(last_pos) + last_keep;
-                if (2 * M > 0x7FFFFFFFll) return hipErrorInvalidValue;  // every offset of the 2M entries is an int
                 if (M > 0) {
-                    const size_t ms = static_cast<size_t>(M);
-                    GR_CHECK(hipMalloc(&d_ckeys, sizeof(unsigned long long) * ms), "MaxflowProblem hipMalloc failed");
-                    GR_CHECK(hipMalloc(&ds->d_a, sizeof(int) * ms), "MaxflowProblem hipMalloc d_a failed");
-                    GR_CHECK(hipMalloc(&ds->d_b, sizeof(int) * ms), "MaxflowProblem hipMalloc d_b failed");
-                    GR_CHECK(hipMalloc(&ds->d_nci, sizeof(int) * 2 * ms), "MaxflowProblem hipMalloc d_nci failed");
-                    GR_CHECK(hipMalloc(&ds->d_neid, sizeof(int) * 2 * ms), "MaxflowProblem hipMalloc d_neid failed");
-                    GR_CHECK(hipMalloc(&d_up, sizeof(int) * (n1 + 1)), "MaxflowProblem hipMalloc failed");
-                    GR_CHECK(hipMalloc(&d_low, sizeof(int) * (n1 + 1)), "MaxflowProblem hipMalloc failed");
-                    GR_CHECK(hipMalloc(&d_deg, sizeof(unsigned) * (n1 + 1)), "MaxflowProblem hipMalloc failed");
-                    hipLaunchKernelGGL(truss::CanonicalKernel, dim3(Grid(m)), dim3(256), 0, stream, d_sorted, d_keep, d_pos, m, col_bits, d_ckeys,
-                                       ds->d_a, ds->d_b);
-                    GR_CHECK(hipGetLastError(), "CanonicalKernel launch failed");
-                    hipLaunchKernelGGL(truss::SwapKeysKernel, dim3(Grid(M)), dim3(256), 0, stream, d_ckeys, M, col_bits, edge_sort.Keys());
-                    GR_CHECK(hipGetLastError(), "SwapKeysKernel launch failed");
-                    unsigned long long *d_skeys = nullptr;
-                    GR_CHECK(edge_sort.Sort(M, key_bits, stream, &d_skeys), "MaxflowProblem edge sort failed");
-                    hipLaunchKernelGGL(truss::RowStartsKernel, dim3(Grid(n + 1)), dim3(256), 0, stream, d_ckeys, d_skeys, M, n, col_bits, d_up, d_low);
-                    GR_CHECK(hipGetLastError(), "RowStartsKernel launch failed");
-                    hipLaunchKernelGGL(truss::DegreesKernel, dim3(Grid(n + 1)), dim3(256), 0, stream, d_up, d_low, n, d_deg);
-                    GR_CHECK(hipGetLastError(), "DegreesKernel launch failed");
-                    GR_CHECK(graphio::DeviceExclusiveScan<int>(d_deg, ds->d_nro, n + 1, d_sums, stream), "MaxflowProblem offset scan failed");
-                    hipLaunchKernelGGL(truss::FillRowsKernel, dim3(Grid(M)), dim3(256), 0, stream, d_ckeys, d_skeys, M, col_bits, d_up, d_low, ds->d_nro,
-                                       ds->d_nci, ds->d_neid);
-                    GR_CHECK(hipGetLastError(), "FillRowsKernel launch failed");
-
                     // the capacities: every arc finds its entry by bisecting the sorted row (the key sort carries no payload) and adds
                     // in 64 bits; then a pair's two sums must fit one int together
-                    GR_CHECK(hipMalloc(&d_cap64, sizeof(unsigned long long) * 2 * ms), "MaxflowProblem hipMalloc failed");
-                    GR_CHECK(hipMemsetAsync(d_cap64, 0, sizeof(unsigned long long) * 2 * ms, stream), "MaxflowProblem memset failed");
+                    const size_t ms = static_cast<size_t>(M);
+                    if ((retval = cap64.Alloc(2 * ms))) return retval;
+                    GR_CHECK(hipMemsetAsync(cap64.p, 0, sizeof(unsigned long long) * 2 * ms, stream), "MaxflowProblem memset failed");
                     GR_CHECK(hipMalloc(&ds->d_mate, sizeof(int) * 2 * ms), "MaxflowProblem hipMalloc d_mate failed");
                     GR_CHECK(hipMalloc(&ds->d_cap, sizeof(int) * 2 * ms), "MaxflowProblem hipMalloc d_cap failed");
                     GR_CHECK(hipMalloc(&ds->d_res, sizeof(int) * 2 * ms), "MaxflowProblem hipMalloc d_res failed");
                     GR_CHECK(hipMalloc(&ds->d_cap_ab, sizeof(int) * ms), "MaxflowProblem hipMalloc failed");
                     GR_CHECK(hipMalloc(&ds->d_cap_ba, sizeof(int) * ms), "MaxflowProblem hipMalloc failed");
                     GR_CHECK(hipMalloc(&ds->d_pent, sizeof(int) * ms), "MaxflowProblem hipMalloc failed");
-                    hipLaunchKernelGGL(AccumulateKernel, dim3(Grid(m)), dim3(256), 0, stream, gs->d_row_offsets, gs->d_column_indices, gs->d_edge_values,
-                                       static_cast<int>(n), m, ds->d_nro, ds->d_nci, d_cap64, ds->d_words + W_BAD);
-                    GR_CHECK(hipGetLastError(), "AccumulateKernel launch failed");
-                    hipLaunchKernelGGL(PairEntriesKernel, dim3(Grid(M)), dim3(256), 0, stream, ds->d_a, ds->d_b, M, ds->d_nro, ds->d_nci, d_cap64, ds->d_pent,
+                }
+                // (self-loops only, M = 0: their capacities are still looked at)
+                hipLaunchKernelGGL(AccumulateKernel, dim3(Grid(m)), dim3(256), 0, stream, gs->d_row_offsets, gs->d_column_indices, gs->d_edge_values,
+                                   static_cast<int>(n), m, ds->d_nro, ds->d_nci, cap64.p, ds->d_words + W_BAD);
+                GR_CHECK(hipGetLastError(), "AccumulateKernel launch failed");
+                if (M > 0) {
+                    hipLaunchKernelGGL(PairEntriesKernel, dim3(Grid(M)), dim3(256), 0, stream, ds->d_a, ds->d_b, M, ds->d_nro, ds->d_nci, cap64.p, ds->d_pent,
                                        ds->d_mate, ds->d_cap, ds->d_cap_ab, ds->d_cap_ba, ds->d_words + W_BAD);
                     GR_CHECK(hipGetLastError(), "PairEntriesKernel launch failed");
-                } else {
-                    // (self-loops only: their capacities are still looked at)
-                    hipLaunchKernelGGL(AccumulateKernel, dim3(Grid(m)), dim3(256), 0, stream, gs->d_row_offsets, gs->d_column_indices, gs->d_edge_values,
-                                       static_cast<int>(n), m, ds->d_nro, ds->d_nci, d_cap64, ds->d_words + W_BAD);
-                    GR_CHECK(hipGetLastError(), "AccumulateKernel launch failed");
                 }
                 unsigned bad_cap = 0;
                 GR_CHECK(hipMemcpyAsync(&bad_cap, ds->d_words + W_BAD, sizeof(bad_cap), hipMemcpyDeviceToHost, stream), "MaxflowProblem read-back failed");
@@ -238,16 +173,10 @@ struct MaxflowProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
                 }
             }
             pairs = M;
-            GR_CHECK(hipEventRecord(ev[1], stream), "MaxflowProblem hipEventRecord failed");
+            if ((retval = ev.Record(1, stream))) return retval;
             GR_CHECK(hipStreamSynchronize(stream), "MaxflowProblem build sync failed");
-            float ms = 0;
-            GR_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]), "MaxflowProblem hipEventElapsedTime failed");
-            build_ms = ms;
-            return retval;
-        };
-        retval = run();
-        release();
-        if (retval) return retval;
+            if ((retval = ev.Elapsed(0, 1, &build_ms))) return retval;
+        }
 
         const size_t m1 = static_cast<size_t>(M > 0 ? M : 1);
         int **vertex_arrays[] = {&ds->d_height, &ds->d_queue, &ds->d_mark, &ds->d_list[0], &ds->d_list[1], &ds->d_fwd, &ds->d_bwd};

@@ -423,24 +423,6 @@ static __global__ void OrderedListKernel(const unsigned long long *d_sorted, lon
         d_list[i] = static_cast<int>(static_cast<unsigned>(~d_sorted[i]));
 }
 
-// d_bad = 1 unless row_offsets[0] = 0, row_offsets[nodes] = edges, the offsets never decrease and every column is a vertex
-// (the test grx_mst_init makes; runs at Init: a malformed CSR must not reach the sweeps, which index with what they read)
-static __global__ void ValidateCsrKernel(const int *d_row_offsets, const int *d_cols, long long nodes, long long edges, int *d_bad)
-{
-    const long long stride = static_cast<long long>(gridDim.x) * blockDim.x;
-    const long long count = nodes > edges ? nodes : edges;
-    bool bad = false;
-    for (long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; i <= count; i += stride) {
-        if (i < nodes) bad |= d_row_offsets[i] > d_row_offsets[i + 1];
-        if (i == 0) bad |= d_row_offsets[0] != 0 || d_row_offsets[nodes] != edges;
-        if (i < edges) {
-            const int t = d_cols[i];
-            bad |= t < 0 || t >= nodes;
-        }
-    }
-    if (__ballot(bad) && util::LaneId() == 0) *d_bad = 1;
-}
-
 // d_summary[0] = sum of ids (the size of the set), d_summary[1] = max of ids (the number of colours)
 static __global__ void SummaryKernel(const int *d_ids, long long nodes, unsigned long long *d_summary)
 {

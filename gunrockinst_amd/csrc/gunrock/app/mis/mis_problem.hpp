@@ -15,7 +15,7 @@
 
 #include <gunrock/app/mis/mis_functor.hpp>
 #include <gunrock/app/problem_base.hpp>
-#include <gunrock/graphio/device_sort.hpp>
+#include <gunrock/graphio/pair_graph.hpp>
 #include <gunrock/graphio/symmetry.hpp>
 
 namespace gunrock {
@@ -134,12 +134,9 @@ struct MISProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         GR_CHECK(hipMalloc(&ds->d_reads, sizeof(unsigned long long) * 4), "MISProblem hipMalloc failed");
 
         // 1. the CSR must be one: nothing in the sweeps indexes with an unchecked value
-        GR_CHECK(hipMemsetAsync(ds->d_words, 0, sizeof(int) * 4, stream), "MISProblem memset failed");
-        hipLaunchKernelGGL(ValidateCsrKernel, dim3(Grid((n > m ? n : m) + 1)), dim3(256), 0, stream, gs->d_row_offsets, gs->d_column_indices,
-                           n, m, ds->d_words);
-        GR_CHECK(hipGetLastError(), "ValidateCsrKernel launch failed");
-        if ((retval = ReadWords(ds->d_words, 1, stream))) return retval;
-        if (h_words[0]) {
+        bool bad = false;
+        if ((retval = graphio::DeviceValidateCsr(gs->d_row_offsets, gs->d_column_indices, n, m, ds->d_words, stream, &bad))) return retval;
+        if (bad) {
             malformed = 1;
             return hipErrorInvalidValue;
         }

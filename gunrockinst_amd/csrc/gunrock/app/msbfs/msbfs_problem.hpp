@@ -14,11 +14,7 @@
 
 #include <gunrock/app/msbfs/msbfs_functor.hpp>
 #include <gunrock/app/problem_base.hpp>
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunused-function"  // (only TC's validation kernel is used here)
-#include <gunrock/app/tc/tc_functor.hpp>
-#pragma clang diagnostic pop
-#include <gunrock/graphio/device_sort.hpp>
+#include <gunrock/graphio/pair_graph.hpp>
 #include <gunrock/graphio/symmetry.hpp>
 
 namespace gunrock {
@@ -117,18 +113,8 @@ struct MsbfsProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     // a CSR of `nodes` vertices?  (the kernels index with what they read)
     hipError_t Validate(const int *d_ro, const int *d_ci, bool *bad)
     {
-        hipError_t retval = hipSuccess;
-        DataSlice *ds = data_slices[0];
-        hipStream_t stream = this->graph_slices[0]->stream;
-        const long long n = this->nodes, m = this->edges;
-        int flag = 0;
-        GR_CHECK(hipMemsetAsync(ds->d_words, 0, sizeof(Word) * W_COUNT, stream), "MsbfsProblem memset failed");
-        hipLaunchKernelGGL(tc::ValidateCsrKernel, dim3(Grid((n > m ? n : m) + 1)), dim3(256), 0, stream, d_ro, d_ci, n, m, reinterpret_cast<int *>(ds->d_words));
-        GR_CHECK(hipGetLastError(), "ValidateCsrKernel launch failed");
-        GR_CHECK(hipMemcpyAsync(&flag, ds->d_words, sizeof(int), hipMemcpyDeviceToHost, stream), "MsbfsProblem read-back failed");
-        GR_CHECK(hipStreamSynchronize(stream), "MsbfsProblem read-back sync failed");
-        *bad = flag != 0;
-        return retval;
+        return graphio::DeviceValidateCsr(d_ro, d_ci, this->nodes, this->edges, reinterpret_cast<int *>(data_slices[0]->d_words),
+                                          this->graph_slices[0]->stream, bad);
     }
 
     hipError_t Build(int *d_inv_row_offsets, int *d_inv_col_indices)

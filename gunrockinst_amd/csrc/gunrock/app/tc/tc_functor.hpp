@@ -41,44 +41,9 @@ struct Oriented {
     const int *src;  // [M] the row of every entry
 };
 
-// ---------------- the build ----------------
+// ---------------- the build (the keys, their sort and the keep flags are graphio/pair_graph.hpp's) ----------------
 
-// d_bad = 1 unless row_offsets[0] = 0, row_offsets[nodes] = edges, the offsets never decrease and every column is a vertex
-// (the test grx_mis_init makes)
-static __global__ void ValidateCsrKernel(const int *d_row_offsets, const int *d_cols, long long nodes, long long edges, int *d_bad)
-{
-    const long long stride = static_cast<long long>(gridDim.x) * blockDim.x;
-    const long long count = nodes > edges ? nodes : edges;
-    bool bad = false;
-    for (long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; i <= count; i += stride) {
-        if (i < nodes) bad |= d_row_offsets[i] > d_row_offsets[i + 1];
-        if (i == 0) bad |= d_row_offsets[0] != 0 || d_row_offsets[nodes] != edges;
-        if (i < edges) {
-            const int t = d_cols[i];
-            bad |= t < 0 || t >= nodes;
-        }
-    }
-    if (__ballot(bad) && util::LaneId() == 0) *d_bad = 1;
-}
-
-// one key per CSR entry: (min << col_bits) | max, or the sentinel for a self-loop.  The row of entry e is found by bisection of the
-// offsets (validated: non-decreasing, from 0 to edges).
-static __global__ void EdgeKeysKernel(const int *d_row_offsets, const int *d_cols, int nodes, long long edges, int col_bits,
-                                      unsigned long long sentinel, unsigned long long *d_keys)
-{
-    const long long stride = static_cast<long long>(gridDim.x) * blockDim.x;
-    for (long long e = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; e < edges; e += stride) {
-        int lo = 0, hi = nodes;  // first index in [0, nodes] whose offset exceeds e (offsets[nodes] = edges > e)
-        while (lo < hi) {
-            const int mid = lo + (hi - lo) / 2;
-            if (d_row_offsets[mid] > e) hi = mid; else lo = mid + 1;
-        }
-        const unsigned r = static_cast<unsigned>(lo - 1), c = static_cast<unsigned>(d_cols[e]);
-        const unsigned a = r < c ? r : c, b = r < c ? c : r;
-        d_keys[e] = (a == b) ? sentinel : ((static_cast<unsigned long long>(a) << col_bits) | b);
-    }
-}
-
+// d_deg[v] += the kept keys with an end at v
 static __global__ void DegreeKernel(const unsigned long long *d_keys, const unsigned *d_keep, long long count, int col_bits, unsigned *d_deg)
 {
     const long long stride = static_cast<long long>(gridDim.x) * blockDim.x;

@@ -4,6 +4,7 @@
 // as MIS reads it: an undirected simple graph G in which u and v are neighbours when either row holds the other, self-loops
 // ignored, unsorted rows, duplicates and one-way edges allowed.  Init builds on the device, with the in-tree radix sort and scan:
 //   1. one key (min << cb | max) per CSR entry, self-loops as the sentinel; sorted; duplicates flagged off: the M edges of G
+//      (graphio::PairGraph's Keys and CountKept, graphio/pair_graph.hpp)
 //   2. d(v) by two atomic adds per edge
 //   3. every edge oriented from the endpoint with the smaller (d, id) to the larger, keyed (src << cb | dst) at its rank, sorted
 //      again: the oriented CSR with rows ascending by id; its offsets are the scanned out-degrees
@@ -15,7 +16,7 @@
 
 #include <gunrock/app/problem_base.hpp>
 #include <gunrock/app/tc/tc_functor.hpp>
-#include <gunrock/graphio/device_sort.hpp>
+#include <gunrock/graphio/pair_graph.hpp>
 
 namespace gunrock {
 namespace app {
@@ -86,22 +87,16 @@ struct TCProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         GR_CHECK(hipMalloc(&ds->d_counters, sizeof(Count) * 4), "TCProblem hipMalloc failed");
 
         // 1. the CSR must be one: the build indexes with what it reads
-        int bad = 0;
-        GR_CHECK(hipMemsetAsync(ds->d_words, 0, sizeof(int) * 4, stream), "TCProblem memset failed");
-        hipLaunchKernelGGL(ValidateCsrKernel, dim3(Grid((n > m ? n : m) + 1)), dim3(256), 0, stream, gs->d_row_offsets, gs->d_column_indices, n,
-                           m, ds->d_words);
-        GR_CHECK(hipGetLastError(), "ValidateCsrKernel launch failed");
-        GR_CHECK(hipMemcpyAsync(&bad, ds->d_words, sizeof(int), hipMemcpyDeviceToHost, stream), "TCProblem read-back failed");
-        GR_CHECK(hipStreamSynchronize(stream), "TCProblem read-back sync failed");
+        bool bad = false;
+        if ((retval = graphio::DeviceValidateCsr(gs->d_row_offsets, gs->d_column_indices, n, m, ds->d_words, stream, &bad))) return retval;
         if (bad) {
             malformed = 1;
             return hipErrorInvalidValue;
         }
 
-        hipEvent_t ev[2] = {nullptr, nullptr};
-        GR_CHECK(hipEventCreate(&ev[0]), "TCProblem hipEventCreate failed");
-        GR_CHECK(hipEventCreate(&ev[1]), "TCProblem hipEventCreate failed");
-        GR_CHECK(hipEventRecord(ev[0], stream), "TCProblem hipEventRecord failed");
+        graphio::BuildEvents ev;
+        if ((retval = ev.Create(2))) return retval;
+        if ((retval = ev.Record(0, stream))) return retval;
 
         GR_CHECK(hipMalloc(&ds->d_triangles, sizeof(Count) * n1), "TCProblem hipMalloc d_triangles failed");
         GR_CHECK(hipMalloc(&ds->d_degrees, sizeof(unsigned) * n1), "TCProblem hipMalloc d_degrees failed");
@@ -112,73 +107,39 @@ struct TCProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         GR_CHECK(hipMemsetAsync(ds->d_oro, 0, sizeof(int) * (n1 + 1), stream), "TCProblem memset failed");
         GR_CHECK(hipMemsetAsync(ds->d_counters, 0, sizeof(Count) * 4, stream), "TCProblem memset failed");
 
-        int col_bits = 1;
-        while ((1ll << col_bits) < n) ++col_bits;
-        const int key_bits = 2 * col_bits;  // <= 62
-        const unsigned long long sentinel = (1ull << key_bits) - 1ull;  // min = max = 2^cb - 1: never an edge
-        unsigned *d_keep = nullptr;  // the keep flags, then the out-degrees
-        unsigned long long *d_pos = nullptr, *d_sums = nullptr;
-        const long long flag_words = m > n + 1 ? m : n + 1;
-        graphio::DeviceKeySort edge_sort, oriented_sort;
-        oriented_edges = 0;
-        if (m > 0) {
-            GR_CHECK(hipMalloc(&d_keep, sizeof(unsigned) * static_cast<size_t>(flag_words)), "TCProblem hipMalloc failed");
-            GR_CHECK(hipMalloc(&d_pos, sizeof(unsigned long long) * static_cast<size_t>(m)), "TCProblem hipMalloc failed");
-            GR_CHECK(hipMalloc(&d_sums, sizeof(unsigned long long) * static_cast<size_t>(graphio::ScanScratchWords(flag_words))),
-                     "TCProblem hipMalloc failed");
-            GR_CHECK(edge_sort.Reserve(m), "TCProblem sort scratch failed");
-            hipLaunchKernelGGL(EdgeKeysKernel, dim3(Grid(m)), dim3(256), 0, stream, gs->d_row_offsets, gs->d_column_indices, static_cast<int>(n), m,
-                               col_bits, sentinel, edge_sort.Keys());
-            GR_CHECK(hipGetLastError(), "EdgeKeysKernel launch failed");
-            unsigned long long *d_sorted = nullptr;
-            GR_CHECK(edge_sort.Sort(m, key_bits, stream, &d_sorted), "TCProblem edge sort failed");
-            hipLaunchKernelGGL(graphio::FlagKernel, dim3(Grid(m)), dim3(256), 0, stream, d_sorted, m, sentinel, d_keep);
-            GR_CHECK(hipGetLastError(), "FlagKernel launch failed");
-            GR_CHECK(graphio::DeviceExclusiveScan<unsigned long long>(d_keep, d_pos, m, d_sums, stream), "TCProblem flag scan failed");
-            unsigned long long kept = 0;  // ScanSumsKernel leaves the total behind the tile offsets
-            const long long scan_tiles = (m + graphio::kScanTile - 1) / graphio::kScanTile;
-            GR_CHECK(hipMemcpyAsync(&kept, d_sums + scan_tiles, sizeof(kept), hipMemcpyDeviceToHost, stream), "TCProblem read-back failed");
-            GR_CHECK(hipStreamSynchronize(stream), "TCProblem read-back sync failed");
-            oriented_edges = static_cast<long long>(kept);
-
-            if (oriented_edges > 0) {
-                hipLaunchKernelGGL(DegreeKernel, dim3(Grid(m)), dim3(256), 0, stream, d_sorted, d_keep, m, col_bits, ds->d_degrees);
-                GR_CHECK(hipGetLastError(), "DegreeKernel launch failed");
-                GR_CHECK(oriented_sort.Reserve(oriented_edges), "TCProblem sort scratch failed");
-                unsigned *d_outdeg = nullptr;  // n + 1 words, the last one 0: its scan is the offsets
-                GR_CHECK(hipMalloc(&d_outdeg, sizeof(unsigned) * (n1 + 1)), "TCProblem hipMalloc failed");
-                GR_CHECK(hipMemsetAsync(d_outdeg, 0, sizeof(unsigned) * (n1 + 1), stream), "TCProblem memset failed");
-                hipLaunchKernelGGL(OrientKernel, dim3(Grid(m)), dim3(256), 0, stream, d_sorted, d_keep, d_pos, m, col_bits, ds->d_degrees,
-                                   oriented_sort.Keys(), d_outdeg);
-                GR_CHECK(hipGetLastError(), "OrientKernel launch failed");
-                GR_CHECK(graphio::DeviceExclusiveScan<int>(d_outdeg, ds->d_oro, n + 1, d_sums, stream), "TCProblem offset scan failed");
-                unsigned long long *d_osorted = nullptr;
-                GR_CHECK(oriented_sort.Sort(oriented_edges, key_bits, stream, &d_osorted), "TCProblem oriented sort failed");
-                GR_CHECK(hipMalloc(&ds->d_oci, sizeof(int) * static_cast<size_t>(oriented_edges)), "TCProblem hipMalloc d_oci failed");
-                GR_CHECK(hipMalloc(&ds->d_osrc, sizeof(int) * static_cast<size_t>(oriented_edges)), "TCProblem hipMalloc d_osrc failed");
-                hipLaunchKernelGGL(EmitOrientedKernel, dim3(Grid(oriented_edges)), dim3(256), 0, stream, d_osorted, oriented_edges, col_bits, ds->d_oci,
-                                   ds->d_osrc);
-                GR_CHECK(hipGetLastError(), "EmitOrientedKernel launch failed");
-                GR_CHECK(hipStreamSynchronize(stream), "TCProblem build sync failed");
-                GR_CHECK(hipFree(d_outdeg), "TCProblem hipFree failed");
-            }
+        graphio::PairGraph pg(n);  // (its keys, keep flags and positions; the orientation is TC's own)
+        graphio::DeviceKeySort oriented_sort;
+        if ((retval = pg.Keys(gs->d_row_offsets, gs->d_column_indices, m, stream))) return retval;
+        if ((retval = pg.CountKept(stream, &oriented_edges))) return retval;
+        if (oriented_edges > 0) {
+            hipLaunchKernelGGL(DegreeKernel, dim3(Grid(m)), dim3(256), 0, stream, pg.d_sorted, pg.d_keep, m, pg.col_bits, ds->d_degrees);
+            GR_CHECK(hipGetLastError(), "DegreeKernel launch failed");
+            GR_CHECK(oriented_sort.Reserve(oriented_edges), "TCProblem sort scratch failed");
+            graphio::DeviceScratch<unsigned> outdeg;  // n + 1 words, the last one 0: its scan is the offsets
+            if ((retval = outdeg.Alloc(n1 + 1))) return retval;
+            GR_CHECK(hipMemsetAsync(outdeg.p, 0, sizeof(unsigned) * (n1 + 1), stream), "TCProblem memset failed");
+            hipLaunchKernelGGL(OrientKernel, dim3(Grid(m)), dim3(256), 0, stream, pg.d_sorted, pg.d_keep, pg.d_pos, m, pg.col_bits, ds->d_degrees,
+                               oriented_sort.Keys(), outdeg.p);
+            GR_CHECK(hipGetLastError(), "OrientKernel launch failed");
+            GR_CHECK(graphio::DeviceExclusiveScan<int>(outdeg.p, ds->d_oro, n + 1, pg.d_sums, stream), "TCProblem offset scan failed");
+            unsigned long long *d_osorted = nullptr;
+            GR_CHECK(oriented_sort.Sort(oriented_edges, pg.key_bits, stream, &d_osorted), "TCProblem oriented sort failed");
+            GR_CHECK(hipMalloc(&ds->d_oci, sizeof(int) * static_cast<size_t>(oriented_edges)), "TCProblem hipMalloc d_oci failed");
+            GR_CHECK(hipMalloc(&ds->d_osrc, sizeof(int) * static_cast<size_t>(oriented_edges)), "TCProblem hipMalloc d_osrc failed");
+            hipLaunchKernelGGL(EmitOrientedKernel, dim3(Grid(oriented_edges)), dim3(256), 0, stream, d_osorted, oriented_edges, pg.col_bits, ds->d_oci,
+                               ds->d_osrc);
+            GR_CHECK(hipGetLastError(), "EmitOrientedKernel launch failed");
+            GR_CHECK(hipStreamSynchronize(stream), "TCProblem build sync failed");  // (outdeg goes here)
         }
         hipLaunchKernelGGL(RowSummaryKernel, dim3(Grid(n)), dim3(256), 0, stream, ds->d_degrees, ds->d_oro, n, ds->d_counters + 2);
         GR_CHECK(hipGetLastError(), "RowSummaryKernel launch failed");
         Count summary[2] = {0, 0};
         GR_CHECK(hipMemcpyAsync(summary, ds->d_counters + 2, sizeof(summary), hipMemcpyDeviceToHost, stream), "TCProblem read-back failed");
-        GR_CHECK(hipEventRecord(ev[1], stream), "TCProblem hipEventRecord failed");
+        if ((retval = ev.Record(1, stream))) return retval;
         GR_CHECK(hipStreamSynchronize(stream), "TCProblem build sync failed");
-        float ms = 0;
-        GR_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]), "TCProblem hipEventElapsedTime failed");
-        build_ms = ms;
-        hipEventDestroy(ev[0]);
-        hipEventDestroy(ev[1]);
+        if ((retval = ev.Elapsed(0, 1, &build_ms))) return retval;
         wedges = static_cast<long long>(summary[0]);
         max_out_row = static_cast<long long>(summary[1]);
-        if (d_keep) GR_CHECK(hipFree(d_keep), "TCProblem hipFree failed");
-        if (d_pos) GR_CHECK(hipFree(d_pos), "TCProblem hipFree failed");
-        if (d_sums) GR_CHECK(hipFree(d_sums), "TCProblem hipFree failed");
         return retval;
     }
 

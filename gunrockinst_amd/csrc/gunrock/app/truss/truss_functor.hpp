@@ -440,89 +440,6 @@ static __global__ __launch_bounds__(kTrussThreads) void SupportKernel(Graph g, l
     if (lane == 0 && reads) atomicAdd(d_reads, reads);
 }
 
-// ---------------- the build ----------------
-
-// the kept keys (a << cb | b) in order: the canonical edges
-static __global__ void CanonicalKernel(const unsigned long long *d_keys, const unsigned *d_keep, const unsigned long long *d_pos, long long count,
-                                       int col_bits, unsigned long long *d_ckeys, int *d_src, int *d_dst)
-{
-    const long long stride = static_cast<long long>(gridDim.x) * blockDim.x;
-    const unsigned long long mask = (1ull << col_bits) - 1ull;
-    for (long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; i < count; i += stride) {
-        if (!d_keep[i]) continue;
-        const unsigned long long key = d_keys[i], at = d_pos[i];
-        d_ckeys[at] = key;
-        d_src[at] = static_cast<int>(key >> col_bits);
-        d_dst[at] = static_cast<int>(key & mask);
-    }
-}
-
-// the same edges keyed (b << cb | a): sorted, they are the lower parts of the rows
-static __global__ void SwapKeysKernel(const unsigned long long *d_ckeys, long long edges, int col_bits, unsigned long long *d_out)
-{
-    const long long stride = static_cast<long long>(gridDim.x) * blockDim.x;
-    const unsigned long long mask = (1ull << col_bits) - 1ull;
-    for (long long e = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; e < edges; e += stride) {
-        const unsigned long long key = d_ckeys[e];
-        d_out[e] = ((key & mask) << col_bits) | (key >> col_bits);
-    }
-}
-
-// first index in [0, n) of keys with keys[i] >= x
-__device__ __forceinline__ long long KeyLowerBound(const unsigned long long *keys, long long n, unsigned long long x)
-{
-    long long lo = 0, hi = n;
-    while (lo < hi) {
-        const long long mid = lo + (hi - lo) / 2;
-        if (keys[mid] < x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// for v = 0 .. nodes: up[v] = the edges (a, .) with a < v, low[v] = the edges (., b) with b < v; d(v) for v < nodes (deg[nodes] = 0)
-static __global__ void RowStartsKernel(const unsigned long long *d_ckeys, const unsigned long long *d_skeys, long long edges, long long nodes,
-                                       int col_bits, int *d_up, int *d_low)
-{
-    const long long stride = static_cast<long long>(gridDim.x) * blockDim.x;
-    for (long long v = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; v <= nodes; v += stride) {
-        const unsigned long long x = static_cast<unsigned long long>(v) << col_bits;
-        d_up[v] = static_cast<int>(KeyLowerBound(d_ckeys, edges, x));
-        d_low[v] = static_cast<int>(KeyLowerBound(d_skeys, edges, x));
-    }
-}
-
-static __global__ void DegreesKernel(const int *d_up, const int *d_low, long long nodes, unsigned *d_deg)
-{
-    const long long stride = static_cast<long long>(gridDim.x) * blockDim.x;
-    for (long long v = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; v <= nodes; v += stride)
-        d_deg[v] = v < nodes ? static_cast<unsigned>((d_up[v + 1] - d_up[v]) + (d_low[v + 1] - d_low[v])) : 0u;
-}
-
-// row v = its lower neighbours ascending (the edges (., v) in the order of the swapped keys), then its upper ones (the edges
-// (v, .) in canonical order): ascending by id without a sort of the rows
-static __global__ void FillRowsKernel(const unsigned long long *d_ckeys, const unsigned long long *d_skeys, long long edges, int col_bits,
-                                      const int *d_up, const int *d_low, const int *d_ro, int *d_ci, int *d_eid)
-{
-    const long long stride = static_cast<long long>(gridDim.x) * blockDim.x;
-    const unsigned long long mask = (1ull << col_bits) - 1ull;
-    for (long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; i < edges; i += stride) {
-        {
-            const unsigned long long key = d_ckeys[i];
-            const int a = static_cast<int>(key >> col_bits), b = static_cast<int>(key & mask);
-            const long long at = static_cast<long long>(d_ro[a]) + (d_low[a + 1] - d_low[a]) + (i - d_up[a]);
-            d_ci[at] = b;
-            d_eid[at] = static_cast<int>(i);
-        }
-        {
-            const unsigned long long key = d_skeys[i];
-            const int b = static_cast<int>(key >> col_bits), a = static_cast<int>(key & mask);
-            const long long at = static_cast<long long>(d_ro[b]) + (i - d_low[b]);
-            d_ci[at] = a;
-            d_eid[at] = static_cast<int>(KeyLowerBound(d_ckeys, edges, (static_cast<unsigned long long>(a) << col_bits) | static_cast<unsigned>(b)));
-        }
-    }
-}
-
 // ---------------- around the peel ----------------
 
 // d_out[0] = the largest value, d_out[1] = the smallest (UINT_MAX: no edges); d_sum += the values

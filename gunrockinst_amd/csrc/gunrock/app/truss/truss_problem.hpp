@@ -2,11 +2,8 @@
 //
 // The reference snapshot has no app/truss; the shape is this tree's Problem (compare app/kcore/kcore_problem.hpp).  The input CSR
 // is read as MIS, TC and k-core read it.  Init builds on the device, with the in-tree radix sort and scan:
-//   1. one key (min << cb | max) per CSR entry, self-loops as the sentinel; sorted; duplicates flagged off; the kept keys
-//      compacted: the M canonical edges src[e] < dst[e] in (src, dst) order (TC's first step, with TC's kernels)
-//   2. the same edges keyed (max << cb | min) and sorted: the lower parts of the rows; both key arrays bisected per vertex give
-//      d(v) and, scanned, the offsets of the neighbour CSR, 2M entries
-//   3. row v = its lower neighbours, then its upper ones: ascending by id, every entry with the id of its edge
+//   1. to 3. graphio::PairGraph's Keys, Pairs and Rows (graphio/pair_graph.hpp): the M canonical edges src[e] < dst[e] in
+//      (src, dst) order and the neighbour CSR, 2M entries, rows ascending by id, every entry with the id of its edge
 //   4. the support pass (truss_functor.hpp) into support[], kept: Reset copies it into the working array val[]
 #pragma once
 
@@ -14,7 +11,7 @@
 
 #include <gunrock/app/problem_base.hpp>
 #include <gunrock/app/truss/truss_functor.hpp>
-#include <gunrock/graphio/device_sort.hpp>
+#include <gunrock/graphio/pair_graph.hpp>
 
 namespace gunrock {
 namespace app {
@@ -104,87 +101,31 @@ struct TrussProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         GR_CHECK(hipMalloc(&ds->d_counters, sizeof(unsigned long long) * 8), "TrussProblem hipMalloc failed");
 
         // the CSR must be one: the build indexes with what it reads
-        int bad = 0;
-        GR_CHECK(hipMemsetAsync(ds->d_words, 0, sizeof(unsigned) * (W_COUNT + 4), stream), "TrussProblem memset failed");
+        bool bad = false;
         GR_CHECK(hipMemsetAsync(ds->d_counters, 0, sizeof(unsigned long long) * 8, stream), "TrussProblem memset failed");
-        hipLaunchKernelGGL(tc::ValidateCsrKernel, dim3(Grid((n > m ? n : m) + 1)), dim3(256), 0, stream, gs->d_row_offsets, gs->d_column_indices,
-                           n, m, reinterpret_cast<int *>(ds->d_words));
-        GR_CHECK(hipGetLastError(), "ValidateCsrKernel launch failed");
-        GR_CHECK(hipMemcpyAsync(&bad, ds->d_words, sizeof(int), hipMemcpyDeviceToHost, stream), "TrussProblem read-back failed");
-        GR_CHECK(hipStreamSynchronize(stream), "TrussProblem read-back sync failed");
+        if ((retval = graphio::DeviceValidateCsr(gs->d_row_offsets, gs->d_column_indices, n, m, reinterpret_cast<int *>(ds->d_words), stream, &bad)))
+            return retval;
         if (bad) {
             malformed = 1;
             return hipErrorInvalidValue;
         }
         GR_CHECK(hipMemsetAsync(ds->d_words, 0, sizeof(unsigned) * (W_COUNT + 4), stream), "TrussProblem memset failed");
 
-        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-        for (int i = 0; i < 3; ++i) GR_CHECK(hipEventCreate(&ev[i]), "TrussProblem hipEventCreate failed");
-        GR_CHECK(hipEventRecord(ev[0], stream), "TrussProblem hipEventRecord failed");
+        graphio::BuildEvents ev;
+        if ((retval = ev.Create(3))) return retval;
+        if ((retval = ev.Record(0, stream))) return retval;
 
-        GR_CHECK(hipMalloc(&ds->d_nro, sizeof(int) * (n1 + 1)), "TrussProblem hipMalloc d_nro failed");
         GR_CHECK(hipMalloc(&ds->d_vertex, sizeof(int) * n1), "TrussProblem hipMalloc d_vertex failed");
-        GR_CHECK(hipMemsetAsync(ds->d_nro, 0, sizeof(int) * (n1 + 1), stream), "TrussProblem memset failed");
-
-        int col_bits = 1;
-        while ((1ll << col_bits) < n) ++col_bits;
-        const int key_bits = 2 * col_bits;  // <= 62
-        const unsigned long long sentinel = (1ull << key_bits) - 1ull;  // min = max = 2^cb - 1: never an edge
-        unsigned *d_keep = nullptr, *d_deg = nullptr;
-        unsigned long long *d_pos = nullptr, *d_sums = nullptr, *d_ckeys = nullptr;
-        int *d_up = nullptr, *d_low = nullptr;
-        graphio::DeviceKeySort edge_sort;
-        long long M = 0;
-        if (m > 0) {
-            const long long scan_words = m > n + 1 ? m : n + 1;
-            GR_CHECK(hipMalloc(&d_keep, sizeof(unsigned) * static_cast<size_t>(m)), "TrussProblem hipMalloc failed");
-            GR_CHECK(hipMalloc(&d_pos, sizeof(unsigned long long) * static_cast<size_t>(m)), "TrussProblem hipMalloc failed");
-            GR_CHECK(hipMalloc(&d_sums, sizeof(unsigned long long) * static_cast<size_t>(graphio::ScanScratchWords(scan_words))),
-                     "TrussProblem hipMalloc failed");
-            GR_CHECK(edge_sort.Reserve(m), "TrussProblem sort scratch failed");
-            hipLaunchKernelGGL(tc::EdgeKeysKernel, dim3(Grid(m)), dim3(256), 0, stream, gs->d_row_offsets, gs->d_column_indices, static_cast<int>(n),
-                               m, col_bits, sentinel, edge_sort.Keys());
-            GR_CHECK(hipGetLastError(), "EdgeKeysKernel launch failed");
-            unsigned long long *d_sorted = nullptr;
-            GR_CHECK(edge_sort.Sort(m, key_bits, stream, &d_sorted), "TrussProblem edge sort failed");
-            hipLaunchKernelGGL(graphio::FlagKernel, dim3(Grid(m)), dim3(256), 0, stream, d_sorted, m, sentinel, d_keep);
-            GR_CHECK(hipGetLastError(), "FlagKernel launch failed");
-            GR_CHECK(graphio::DeviceExclusiveScan<unsigned long long>(d_keep, d_pos, m, d_sums, stream), "TrussProblem flag scan failed");
-            unsigned long long last_pos = 0;
-            unsigned last_keep = 0;
-            GR_CHECK(hipMemcpyAsync(&last_pos, d_pos + (m - 1), sizeof(last_pos), hipMemcpyDeviceToHost, stream), "TrussProblem read-back failed");
-            GR_CHECK(hipMemcpyAsync(&last_keep, d_keep + (m - 1), sizeof(last_keep), hipMemcpyDeviceToHost, stream), "TrussProblem read-back failed");
-            GR_CHECK(hipStreamSynchronize(stream), "TrussProblem read-back sync failed");
-            M = static_cast<long long>(last_pos) + last_keep;
-            if (2 * M > 0x7FFFFFFFll) return hipErrorInvalidValue;  // every offset of the 2M entries is an int
-            if (M > 0) {
-                const size_t ms = static_cast<size_t>(M);
-                GR_CHECK(hipMalloc(&d_ckeys, sizeof(unsigned long long) * ms), "TrussProblem hipMalloc failed");
-                GR_CHECK(hipMalloc(&ds->d_src, sizeof(int) * ms), "TrussProblem hipMalloc d_src failed");
-                GR_CHECK(hipMalloc(&ds->d_dst, sizeof(int) * ms), "TrussProblem hipMalloc d_dst failed");
-                GR_CHECK(hipMalloc(&ds->d_nci, sizeof(int) * 2 * ms), "TrussProblem hipMalloc d_nci failed");
-                GR_CHECK(hipMalloc(&ds->d_neid, sizeof(int) * 2 * ms), "TrussProblem hipMalloc d_neid failed");
-                GR_CHECK(hipMalloc(&d_up, sizeof(int) * (n1 + 1)), "TrussProblem hipMalloc failed");
-                GR_CHECK(hipMalloc(&d_low, sizeof(int) * (n1 + 1)), "TrussProblem hipMalloc failed");
-                GR_CHECK(hipMalloc(&d_deg, sizeof(unsigned) * (n1 + 1)), "TrussProblem hipMalloc failed");
-                hipLaunchKernelGGL(CanonicalKernel, dim3(Grid(m)), dim3(256), 0, stream, d_sorted, d_keep, d_pos, m, col_bits, d_ckeys, ds->d_src,
-                                   ds->d_dst);
-                GR_CHECK(hipGetLastError(), "CanonicalKernel launch failed");
-                // (the sort's buffers are free again: the canonical keys are in their own array)
-                hipLaunchKernelGGL(SwapKeysKernel, dim3(Grid(M)), dim3(256), 0, stream, d_ckeys, M, col_bits, edge_sort.Keys());
-                GR_CHECK(hipGetLastError(), "SwapKeysKernel launch failed");
-                unsigned long long *d_skeys = nullptr;
-                GR_CHECK(edge_sort.Sort(M, key_bits, stream, &d_skeys), "TrussProblem edge sort failed");
-                hipLaunchKernelGGL(RowStartsKernel, dim3(Grid(n + 1)), dim3(256), 0, stream, d_ckeys, d_skeys, M, n, col_bits, d_up, d_low);
-                GR_CHECK(hipGetLastError(), "RowStartsKernel launch failed");
-                hipLaunchKernelGGL(DegreesKernel, dim3(Grid(n + 1)), dim3(256), 0, stream, d_up, d_low, n, d_deg);
-                GR_CHECK(hipGetLastError(), "DegreesKernel launch failed");
-                GR_CHECK(graphio::DeviceExclusiveScan<int>(d_deg, ds->d_nro, n + 1, d_sums, stream), "TrussProblem offset scan failed");
-                hipLaunchKernelGGL(FillRowsKernel, dim3(Grid(M)), dim3(256), 0, stream, d_ckeys, d_skeys, M, col_bits, d_up, d_low, ds->d_nro,
-                                   ds->d_nci, ds->d_neid);
-                GR_CHECK(hipGetLastError(), "FillRowsKernel launch failed");
-            }
-        }
+        graphio::PairGraph pg(n);  // steps 1 to 3
+        if ((retval = pg.Keys(gs->d_row_offsets, gs->d_column_indices, m, stream))) return retval;
+        if ((retval = pg.Pairs(stream))) return retval;
+        if ((retval = pg.Rows(stream))) return retval;
+        ds->d_src = graphio::Take(pg.d_src);
+        ds->d_dst = graphio::Take(pg.d_dst);
+        ds->d_nro = graphio::Take(pg.d_ro);
+        ds->d_nci = graphio::Take(pg.d_ci);
+        ds->d_neid = graphio::Take(pg.d_eid);
+        const long long M = pg.pairs;
         simple_edges = M;
         const size_t m1 = static_cast<size_t>(M > 0 ? M : 1);
         GR_CHECK(hipMalloc(&ds->d_support, sizeof(int) * m1), "TrussProblem hipMalloc d_support failed");
@@ -194,7 +135,7 @@ struct TrussProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         GR_CHECK(hipMalloc(&ds->d_queue, sizeof(int) * m1), "TrussProblem hipMalloc d_queue failed");
         GR_CHECK(hipMemsetAsync(ds->d_support, 0, sizeof(int) * m1, stream), "TrussProblem memset failed");
         GR_CHECK(hipMemsetAsync(ds->d_truss, 0, sizeof(int) * m1, stream), "TrussProblem memset failed");
-        GR_CHECK(hipEventRecord(ev[1], stream), "TrussProblem hipEventRecord failed");
+        if ((retval = ev.Record(1, stream))) return retval;
 
         unsigned summary[2] = {0u, kNoLevel};
         unsigned *d_out = ds->d_words + W_COUNT;
@@ -206,17 +147,13 @@ struct TrussProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
             hipLaunchKernelGGL(SupportSummaryKernel, dim3(Grid(M)), dim3(256), 0, stream, ds->d_support, M, d_out, ds->d_counters + 5);
             GR_CHECK(hipGetLastError(), "SupportSummaryKernel launch failed");
         }
-        GR_CHECK(hipEventRecord(ev[2], stream), "TrussProblem hipEventRecord failed");
+        if ((retval = ev.Record(2, stream))) return retval;
         unsigned long long sums[2] = {0, 0};
         GR_CHECK(hipMemcpyAsync(summary, d_out, sizeof(summary), hipMemcpyDeviceToHost, stream), "TrussProblem read-back failed");
         GR_CHECK(hipMemcpyAsync(sums, ds->d_counters + 4, sizeof(sums), hipMemcpyDeviceToHost, stream), "TrussProblem read-back failed");
         GR_CHECK(hipStreamSynchronize(stream), "TrussProblem build sync failed");
-        float ms = 0;
-        GR_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]), "TrussProblem hipEventElapsedTime failed");
-        build_ms = ms;
-        GR_CHECK(hipEventElapsedTime(&ms, ev[1], ev[2]), "TrussProblem hipEventElapsedTime failed");
-        support_ms = ms;
-        for (int i = 0; i < 3; ++i) hipEventDestroy(ev[i]);
+        if ((retval = ev.Elapsed(0, 1, &build_ms))) return retval;
+        if ((retval = ev.Elapsed(1, 2, &support_ms))) return retval;
         max_support = summary[0];
         min_support = summary[1] == kNoLevel ? 0 : summary[1];
         support_entries = static_cast<long long>(sums[0]);
@@ -225,9 +162,6 @@ struct TrussProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         GR_CHECK(hipMalloc(&ds->d_trace_k, sizeof(int) * static_cast<size_t>(trace_capacity)), "TrussProblem hipMalloc failed");
         GR_CHECK(hipMalloc(&ds->d_trace_tail, sizeof(int) * static_cast<size_t>(trace_capacity)), "TrussProblem hipMalloc failed");
         GR_CHECK(hipMalloc(&ds->d_trace_clock, sizeof(unsigned long long) * static_cast<size_t>(trace_capacity)), "TrussProblem hipMalloc failed");
-        void *scratch[] = {d_keep, d_pos, d_sums, d_ckeys, d_up, d_low, d_deg};
-        for (void *b : scratch)
-            if (b) GR_CHECK(hipFree(b), "TrussProblem hipFree failed");
         return retval;
     }
 
