@@ -128,6 +128,10 @@ int main(int argc, char **argv)
             for (int s = 0; ok && s < csr.nodes; ++s) {
                 ok = !util::GRError(bc_problem.Reset(s, bc_enactor.GetFrontierType(), 1.3), "BC Problem Data Reset Failed", __FILE__, __LINE__) &&
                      !util::GRError(bc_enactor.Enact<BcProblem>(context, &bc_problem, s, 0), "BC Problem Enact Failed", __FILE__, __LINE__);
+                if (ok && bc_enactor.PathCountOverflow()) {
+                    std::fprintf(stderr, "BC: the shortest-path counts from vertex %d do not fit float32\n", s);
+                    ok = false;
+                }
             }
             if (ok) ok = !util::GRError(bc_problem.ScaleBcValues(0.5f), "BC scale failed", __FILE__, __LINE__);
             bc_timer.Stop(bc_problem.graph_slices[0]->stream);

@@ -24,6 +24,7 @@ from .capi import (  # noqa: F401
     MAXFLOW_PREFLOW, MAXFLOW_RETURN, MAXFLOW_CUT, MAXFLOW_GAVE_UP,
     MatchingProblem, MatchingGaveUp, MatchingOverflow, gunrock_matching, gunrock_coarsen, matching_keys, MATCHING_AUTO, MATCHING_ROUNDS,
     MATCHING_DEVICE_LOOP, MATCHING_STEP_WIDE, MATCHING_STEP_LOOP, MATCHING_GAVE_UP, MATCHING_OVERFLOW,
+    BcOverflow, BC_OVERFLOW,
     advance_frontier, advance_queue, advance_reduce,
 )
 
@@ -44,5 +45,6 @@ __all__ = [
     "MAXFLOW_RETURN", "MAXFLOW_CUT", "MAXFLOW_GAVE_UP",
     "MatchingProblem", "MatchingGaveUp", "MatchingOverflow", "gunrock_matching", "gunrock_coarsen", "matching_keys", "MATCHING_AUTO",
     "MATCHING_ROUNDS", "MATCHING_DEVICE_LOOP", "MATCHING_STEP_WIDE", "MATCHING_STEP_LOOP", "MATCHING_GAVE_UP", "MATCHING_OVERFLOW",
+    "BcOverflow", "BC_OVERFLOW",
     "advance_frontier", "advance_queue", "advance_reduce",
 ]

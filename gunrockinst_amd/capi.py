@@ -2092,6 +2092,14 @@ class PrProblem(_Handle):
         return r.value, i.value
 
 
+BC_OVERFLOW = -6  # enum GRX_BC_OVERFLOW (gunrock_mi355x.h)
+
+
+class BcOverflow(ArithmeticError):
+    """BcProblem.run: a source's shortest-path counts do not fit float32 (GRX_BC_OVERFLOW); bc_values are all 0 and the handle takes
+    the next run"""
+
+
 class BcProblem(_Handle):
     """BCProblem + BCEnactor behind the handle ABI (grx_bc_*)."""
 
@@ -2116,7 +2124,14 @@ class BcProblem(_Handle):
         return self
 
     def run(self, src=-1, max_grid_size=0, queue_sizing=1.0):
-        return self._timed(lib().grx_bc_run, "BCEnactor::Enact", int(src), max_grid_size, float(queue_sizing))
+        """one source, or every vertex in turn (src = -1); returns the elapsed milliseconds.  BcOverflow when a path count leaves
+        float32."""
+        ms = C.c_float()
+        rc = lib().grx_bc_run(self._h, int(src), max_grid_size, float(queue_sizing), C.byref(ms))
+        if rc == BC_OVERFLOW:
+            raise BcOverflow("gunrockinst_amd: BCEnactor::Enact: more than 2^126 shortest paths to a vertex (code %d)" % rc)
+        _check(rc, "BCEnactor::Enact")
+        return float(ms.value)
 
     def extract(self):
         sig = np.empty(max(self.nodes, 1), dtype=np.float32)

@@ -26,14 +26,20 @@ namespace gunrock {
 namespace app {
 namespace bc {
 
-// d_packed[v] = (label, 1 / sigma): the term a vertex offers before anything was accumulated into its delta (deltas are zero)
+// d_packed[v] = (label, 1 / sigma): the term a vertex offers before anything was accumulated into its delta (deltas are zero).
+// This pass sees every path count, so it is also where a count that left float32 is noticed: above 2^126 the reciprocal is
+// subnormal, at inf it is 0 and every contribution from that vertex upward would silently vanish (inf * 0 = NaN where the parent
+// overflowed too).  `!(sigma <= 2^126)` also catches NaN.  Such a search is reported, not returned (GRX_BC_OVERFLOW): the kernel
+// raises the host's word (BCProblem::h_overflow; every writer stores the same value, and only an overflowing search stores at all).
 template <typename VertexId, typename Value>
-__global__ void PackTermsKernel(const VertexId *d_labels, const Value *d_sigmas, int2 *d_packed, long long nodes)
+__global__ void PackTermsKernel(const VertexId *d_labels, const Value *d_sigmas, int2 *d_packed, long long nodes, int *h_overflow)
 {
     const long long stride = static_cast<long long>(gridDim.x) * blockDim.x;
     for (long long v = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; v < nodes; v += stride) {
         const VertexId l = d_labels[v];
-        d_packed[v] = make_int2(l, l >= 0 ? __float_as_int(static_cast<Value>(1) / d_sigmas[v]) : 0);
+        const Value sigma = d_sigmas[v];
+        if (l >= 0 && !(sigma <= static_cast<Value>(0x1p126f))) *h_overflow = 1;
+        d_packed[v] = make_int2(l, l >= 0 ? __float_as_int(static_cast<Value>(1) / sigma) : 0);
     }
 }
 // ... and (1 + delta) / sigma once the deltas of a level's vertices are final
@@ -73,6 +79,8 @@ class BCEnactor : public EnactorBase {
         typedef BackwardReduceFunctor<VertexId, SizeT, Value, BCProblem> Backward;
 
         hipError_t retval = hipSuccess;
+        overflow = false;
+        *problem->h_overflow = 0;  // (the last search was synchronised: nothing on the device is writing it)
         if ((retval = EnactorBase::Setup(max_grid_size, AdvancePolicy::MIN_BLOCKS, 8))) return retval;
         GraphSlice<VertexId, SizeT, Value> *gs = problem->graph_slices[0];
         typename BCProblem::DataSlice *ds = problem->data_slices[0];
@@ -131,7 +139,7 @@ class BCEnactor : public EnactorBase {
 
         // (label, 1 / sigma) side by side for the backward gathers (bc_functor.hpp BackwardReduceFunctor)
         hipLaunchKernelGGL((PackTermsKernel<VertexId, Value>), dim3(util::MemsetGrid(problem->nodes)), dim3(256), 0, stream, ds->d_labels,
-                           ds->d_sigmas, ds->d_packed, static_cast<long long>(problem->nodes));
+                           ds->d_sigmas, ds->d_packed, static_cast<long long>(problem->nodes), problem->h_overflow);
         if ((retval = util::GRError("PackTermsKernel launch failed", __FILE__, __LINE__))) return retval;
 
         // ---- backward: dependencies, deepest recorded frontier first.  The recorded levels are the ones that have out-edges: the
@@ -167,11 +175,23 @@ class BCEnactor : public EnactorBase {
         hipLaunchKernelGGL((AccumulateKernel<Value>), dim3(util::MemsetGrid(problem->nodes)), dim3(256), 0, stream, ds->d_bc_values,
                            ds->d_deltas, static_cast<long long>(problem->nodes));
         if ((retval = util::GRError("AccumulateKernel launch failed", __FILE__, __LINE__))) return retval;
-        return util::GRError(hipStreamSynchronize(stream), "BCEnactor sync failed", __FILE__, __LINE__);
+        if ((retval = util::GRError(hipStreamSynchronize(stream), "BCEnactor sync failed", __FILE__, __LINE__))) return retval;
+        // the flag came back with that synchronisation.  After an overflow the deltas just added are garbage: bc_values are cleared
+        // (what earlier sources of a loop had added goes with them -- the loop's result is void anyway)
+        overflow = *static_cast<volatile int *>(problem->h_overflow) != 0;
+        if (overflow) {
+            if ((retval = problem->ClearBcValues())) return retval;
+            retval = util::GRError(hipStreamSynchronize(stream), "BCEnactor sync failed", __FILE__, __LINE__);
+        }
+        return retval;
     }
+
+    // the last Enact met a path count outside float32: its sigmas and deltas are not results and bc_values are all 0
+    bool PathCountOverflow() const { return overflow; }
 
    private:
     std::vector<int> level_offset, level_len, level_edges;
+    bool overflow = false;
 };
 
 }  // namespace bc

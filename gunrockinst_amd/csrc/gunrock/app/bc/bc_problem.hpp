@@ -27,6 +27,8 @@ __global__ void ScaleKernel(Value *d_out, Value factor, long long length)
     for (long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; i < length; i += stride) d_out[i] *= factor;
 }
 
+constexpr int kPathCountOverflow = -6;  // GRX_BC_OVERFLOW
+
 // bc_values[v] += deltas[v] (the source's delta is never accumulated, so it adds 0)
 template <typename Value>
 __global__ void AccumulateKernel(Value *d_bc, const Value *d_deltas, long long length)
@@ -59,6 +61,10 @@ struct BCProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
 
     DataSlice **data_slices = nullptr;
     SizeT src_row[2] = {0, 0};
+    // path-count overflow: one word of pinned + mapped host memory that BCEnactor clears before a search and its PackTermsKernel
+    // sets when a labelled vertex has a sigma above 2^126 (inf, NaN, or a count whose reciprocal is subnormal).  Only an overflowing
+    // search stores to it; the synchronisation that ends Enact makes the store readable.
+    int *h_overflow = nullptr;
 
     ~BCProblem() override
     {
@@ -75,6 +81,7 @@ struct BCProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
             }
             delete[] data_slices;
         }
+        if (h_overflow) hipHostFree(h_overflow);
     }
 
     hipError_t AllocData()
@@ -91,6 +98,8 @@ struct BCProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
         GR_CHECK(hipMalloc(&ds->d_packed, sizeof(int2) * n), "BCProblem hipMalloc d_packed failed");
         GR_CHECK(hipMalloc(&ds->d_bc_values, sizeof(Value) * n), "BCProblem hipMalloc d_bc_values failed");
         GR_CHECK(hipMalloc(&ds->d_ebc_values, sizeof(Value) * m), "BCProblem hipMalloc d_ebc_values failed");
+        GR_CHECK(hipHostMalloc(reinterpret_cast<void **>(&h_overflow), sizeof(int), hipHostMallocMapped), "BCProblem hipHostMalloc failed");
+        *h_overflow = 0;
         GR_CHECK(hipMemset(ds->d_bc_values, 0, sizeof(Value) * n), "BCProblem hipMemset failed");
         GR_CHECK(hipMemset(ds->d_ebc_values, 0, sizeof(Value) * m), "BCProblem hipMemset failed");
         GR_CHECK(hipDeviceSynchronize(), "BCProblem sync failed");  // (null-stream memsets: the problem's stream is not ordered behind them)

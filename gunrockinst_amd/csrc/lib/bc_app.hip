@@ -25,6 +25,7 @@ using namespace gunrock::app::bc;
 namespace {
 typedef BCProblem<int, int, float, true, false> Problem;  // the reference's instantiation (bc_app.cu:61-66)
 }
+static_assert(GRX_BC_OVERFLOW == kPathCountOverflow, "the header's code is the problem's");
 
 struct grx_bc {
     util::DeviceContext context;
@@ -32,12 +33,13 @@ struct grx_bc {
     BCEnactor<false> enactor;
     EventPair timer;
     explicit grx_bc(int device) : context(device), enactor(false) { timer.Create(); }
-    // one or all sources, then the reference's 0.5 scaling; elapsed = device time of the whole loop
-    hipError_t Run(int src, int max_grid_size, double queue_sizing, float *ms)
+    // one or all sources, then the reference's 0.5 scaling; elapsed = device time of the whole loop.  GRX_BC_OVERFLOW when a
+    // source's path counts left float32: the loop stops there, bc_values are all 0
+    int Run(int src, int max_grid_size, double queue_sizing, float *ms)
     {
-        hipError_t retval = hipSuccess;
-        GR_CHECK(problem.ClearBcValues(), "BC clear failed");
-        return timer.Timed(problem.graph_slices[0]->stream, ms, [&]() { return RunSources(src, max_grid_size, queue_sizing); });
+        if (hipError_t rc = problem.ClearBcValues()) return static_cast<int>(rc);
+        const hipError_t rc = timer.Timed(problem.graph_slices[0]->stream, ms, [&]() { return RunSources(src, max_grid_size, queue_sizing); });
+        return rc == hipSuccess && enactor.PathCountOverflow() ? kPathCountOverflow : static_cast<int>(rc);
     }
     hipError_t RunSources(int src, int max_grid_size, double queue_sizing)
     {
@@ -47,6 +49,7 @@ struct grx_bc {
         for (int s = first; s < last; ++s) {
             GR_CHECK(problem.Reset(s, enactor.GetFrontierType(), queue_sizing), "BC Problem Data Reset Failed");
             GR_CHECK(enactor.Enact<Problem>(context, &problem, s, max_grid_size), "BC Problem Enact Failed");
+            if (enactor.PathCountOverflow()) return retval;  // (Enact left bc_values cleared; no scaling)
         }
         GR_CHECK(problem.ScaleBcValues(0.5f), "BC scale failed");
         return retval;
@@ -78,7 +81,7 @@ int grx_bc_init_device(grx_bc *p, int nodes, int edges, int *d_row_offsets, int 
 int grx_bc_run(grx_bc *p, int src, int max_grid_size, double queue_sizing, float *elapsed_ms)
 {
     if (!p || !p->problem.data_slices || src < -1 || src >= p->problem.nodes) return -1;
-    return static_cast<int>(p->Run(src, max_grid_size, queue_sizing, elapsed_ms));
+    return p->Run(src, max_grid_size, queue_sizing, elapsed_ms);
 }
 
 int grx_bc_extract(grx_bc *p, float *h_sigmas, float *h_bc_values, float *h_ebc_values)

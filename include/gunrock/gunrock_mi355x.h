@@ -858,6 +858,7 @@ typedef struct grx_matching grx_matching;
 enum { GRX_MATCHING_AUTO = 0, GRX_MATCHING_ROUNDS = 1, GRX_MATCHING_DEVICE_LOOP = 2 };
 enum { GRX_MATCHING_STEP_WIDE = 0, GRX_MATCHING_STEP_LOOP = 1 }; /* the kinds of grx_matching_round_trace */
 enum { GRX_MATCHING_GAVE_UP = -4, GRX_MATCHING_OVERFLOW = -5 };  /* next to -1 / -2 / -3 */
+enum { GRX_BC_OVERFLOW = -6 };  /* grx_bc_run: a source's shortest-path counts do not fit float32 */
 
 /* (no counterpart in the reference snapshot: this call and the ones below are shaped like grx_maxflow_*) */
 int grx_matching_create(grx_matching **out, int instrument, int device);
@@ -1030,7 +1031,10 @@ int grx_bc_create(grx_bc **out, int device);
 int grx_bc_init(grx_bc *p, int nodes, int edges, const int *row_offsets, const int *col_indices);
 int grx_bc_init_device(grx_bc *p, int nodes, int edges, int *d_row_offsets, int *d_col_indices);
 /* The driver loop of run_bc (bc_app.cu:86-113): bc_values = 0; for src (or, when src == -1, every vertex in turn)
- * Reset + Enact; bc_values *= 0.5.  elapsed_ms = device time of the whole loop. */
+ * Reset + Enact; bc_values *= 0.5.  elapsed_ms = device time of the whole loop.
+ * Path counts are float32.  GRX_BC_OVERFLOW: a vertex the source reaches has more than 2^126 shortest paths to it (the count, or
+ * its reciprocal, is no normal float: the dependencies above it would come out 0 or NaN).  The loop stops at that source, bc_values
+ * are all 0, the sigmas are not results, and the handle takes the next run. */
 int grx_bc_run(grx_bc *p, int src, int max_grid_size, double queue_sizing, float *elapsed_ms);
 /* BCProblem::Extract (bc_problem.cuh:140-192); sigmas are those of the LAST source; any pointer may be NULL */
 int grx_bc_extract(grx_bc *p, float *h_sigmas, float *h_bc_values, float *h_ebc_values);
