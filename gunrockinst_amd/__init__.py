@@ -1,4 +1,4 @@
-"""gunrockinst_amd -- MI355X-native frontier engine (BFS / CC / SSSP / BC / PageRank / TopK / MST / MIS / TC / k-core / k-truss / SCC / MS-BFS / BCC / max-flow) behind Gunrock's C ABI.
+"""gunrockinst_amd -- MI355X-native frontier engine (BFS / CC / SSSP / BC / PageRank / TopK / MST / MIS / TC / k-core / k-truss / SCC / MS-BFS / BCC / max-flow / matching / k-cliques) behind Gunrock's C ABI.
 
 The product is the shared library ``gunrockinst_amd/lib/libgunrock.so`` (hand-written HIP for gfx950,
 built by ``gunrockinst_amd/csrc/Makefile``).  This package is only the host-side binding: ctypes
@@ -25,6 +25,7 @@ from .capi import (  # noqa: F401
     MatchingProblem, MatchingGaveUp, MatchingOverflow, gunrock_matching, gunrock_coarsen, matching_keys, MATCHING_AUTO, MATCHING_ROUNDS,
     MATCHING_DEVICE_LOOP, MATCHING_STEP_WIDE, MATCHING_STEP_LOOP, MATCHING_GAVE_UP, MATCHING_OVERFLOW,
     BcOverflow, BC_OVERFLOW,
+    CliqueProblem, CliqueOverflow, gunrock_cliques, CLIQUE_AUTO, CLIQUE_BITMAP, CLIQUE_LIST, CLIQUE_OVERFLOW,
     advance_frontier, advance_queue, advance_reduce,
 )
 
@@ -46,5 +47,6 @@ __all__ = [
     "MatchingProblem", "MatchingGaveUp", "MatchingOverflow", "gunrock_matching", "gunrock_coarsen", "matching_keys", "MATCHING_AUTO",
     "MATCHING_ROUNDS", "MATCHING_DEVICE_LOOP", "MATCHING_STEP_WIDE", "MATCHING_STEP_LOOP", "MATCHING_GAVE_UP", "MATCHING_OVERFLOW",
     "BcOverflow", "BC_OVERFLOW",
+    "CliqueProblem", "CliqueOverflow", "gunrock_cliques", "CLIQUE_AUTO", "CLIQUE_BITMAP", "CLIQUE_LIST", "CLIQUE_OVERFLOW",
     "advance_frontier", "advance_queue", "advance_reduce",
 ]

@@ -267,6 +267,17 @@ _SIGNATURES = {
     "grx_matching_coarse_extract": (C.c_int, [C.c_void_p, i32p, i32p, i32p, i32p, i32p]),
     "grx_matching_coarse_device": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 5),
     "grx_matching_destroy": (None, [C.c_void_p]),
+    "grx_clique_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int]),
+    "grx_clique_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p, i32p]),
+    "grx_clique_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "grx_clique_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
+    "grx_clique_reset": (C.c_int, [C.c_void_p]),
+    "grx_clique_enact": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "grx_clique_stats": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_longlong)] * 6 + [C.POINTER(C.c_double), C.POINTER(C.c_longlong)]
+                         + [C.POINTER(C.c_double)] * 2),
+    "grx_clique_extract": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "grx_clique_device_results": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "grx_clique_destroy": (None, [C.c_void_p]),
     "grx_sssp_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int]),
     "grx_sssp_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p, C.POINTER(C.c_uint32), C.c_int]),
     "grx_sssp_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float]),
@@ -1837,6 +1848,93 @@ def gunrock_coarsen(nodes, row_offsets, col_indices, weights=None, vertex_weight
         if p is not None and p not in handles:
             p.close()
     return out
+
+
+CLIQUE_AUTO, CLIQUE_BITMAP, CLIQUE_LIST = 0, 1, 2  # enum GRX_CLIQUE_* (gunrock_mi355x.h)
+CLIQUE_OVERFLOW = -7  # grx_clique_enact: the bound on the counts reached "count_limit"
+
+
+class CliqueOverflow(ArithmeticError):
+    """CliqueProblem.enact: sum over u of C(d+(u), k - 1) reached "count_limit" (GRX_CLIQUE_OVERFLOW): nothing ran, the handle holds
+    no result and takes the next enact"""
+
+
+class CliqueProblem(_Handle):
+    """CliqueProblem + CliqueEnactor behind the handle C ABI: for k = 3 .. 6 the number of k-cliques through every vertex (int64)
+    and their total, of the CSR read as an undirected simple graph.  `rank` (int32 per vertex, or None) orients the build; no rank
+    changes a result."""
+
+    _destroy = "grx_clique_destroy"
+
+    def __init__(self, instrument=False, device=0):
+        self._create("grx_clique_create", int(instrument), device)
+        self.nodes = 0
+        self.edges = 0
+
+    def init(self, nodes, row_offsets, col_indices, rank=None):
+        ro, ci = _csr_arrays(row_offsets, col_indices, nodes)
+        rk = None if rank is None else _i32(rank)
+        if rk is not None and rk.shape[0] != int(nodes):
+            raise ValueError("gunrockinst_amd: %d ranks for %d nodes" % (rk.shape[0], int(nodes)))
+        self.nodes, self.edges = int(nodes), int(ci.shape[0])
+        _check(lib().grx_clique_init(self._h, self.nodes, self.edges, _p(ro), _p(ci), None if rk is None else _p(rk)), "CliqueProblem::Init")
+        return self
+
+    def init_device(self, nodes, edges, d_row_offsets, d_col_indices, d_rank=None):
+        self.nodes, self.edges = int(nodes), int(edges)
+        _check(lib().grx_clique_init_device(self._h, self.nodes, self.edges, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices),
+                                            C.c_void_p(d_rank)), "CliqueProblem::Init(device)")
+        return self
+
+    def set_option(self, name, value):
+        """"strategy" (CLIQUE_AUTO / CLIQUE_BITMAP / CLIQUE_LIST), "bitmap_rows", "count_limit"; returns the library's code:
+        0 = set, 1 = unknown name (a value out of range raises)"""
+        rc = lib().grx_clique_set_option(self._h, name.encode(), float(value))
+        if rc not in (0, 1):
+            _check(rc, "grx_clique_set_option(%s)" % name)
+        return rc
+
+    def reset(self):
+        _check(lib().grx_clique_reset(self._h), "CliqueProblem::Reset")
+
+    def enact(self, k, max_grid_size=0):
+        """the elapsed milliseconds; CliqueOverflow when the bound on the counts reached the option count_limit"""
+        ms = C.c_float()
+        rc = lib().grx_clique_enact(self._h, int(k), int(max_grid_size), C.byref(ms))
+        if rc == CLIQUE_OVERFLOW:
+            raise CliqueOverflow("gunrockinst_amd: CliqueEnactor::Enact refused: the bound %.17g reached count_limit (code %d)"
+                                 % (self.stats()["bound"], rc))
+        _check(rc, "CliqueEnactor::Enact")
+        return float(ms.value)
+
+    def stats(self):
+        o, r, a, l, n = (C.c_longlong() for _ in range(5))
+        rows, edges = (C.c_longlong * 2)(), (C.c_longlong * 2)()
+        bound, k, b = C.c_double(), C.c_double(), C.c_double()
+        _check(lib().grx_clique_stats(self._h, C.byref(o), C.byref(r), rows, edges, C.byref(a), C.byref(l), C.byref(bound), C.byref(n),
+                                      C.byref(k), C.byref(b)), "grx_clique_stats")
+        return {"oriented_edges": o.value, "max_out_row": r.value, "bitmap_rows": rows[0], "list_rows": rows[1],
+                "bitmap_edges": edges[0], "list_edges": edges[1], "bit_ands": a.value, "list_lookups": l.value, "bound": bound.value,
+                "kernel_launches": n.value, "kernel_ms": k.value, "build_ms": b.value}
+
+    def extract(self, cliques=True):
+        """(cliques as int64 per vertex, or None; the number of k-cliques of the graph)"""
+        out = np.empty(max(self.nodes, 1), dtype=np.int64) if cliques else None
+        total = C.c_longlong()
+        _check(lib().grx_clique_extract(self._h, None if out is None else _i64p(out), C.byref(total)), "CliqueProblem::Extract")
+        return (None if out is None else out[:self.nodes]), int(total.value)
+
+    def device_results(self):
+        """(device pointer of the int64 counts, device pointer of the int32 degrees)"""
+        t, d = C.c_void_p(), C.c_void_p()
+        _check(lib().grx_clique_device_results(self._h, C.byref(t), C.byref(d)), "grx_clique_device_results")
+        return t.value, d.value
+
+
+def gunrock_cliques(nodes, row_offsets, col_indices, k, rank=None, device=0):
+    """One-shot k-clique counting, k = 3 .. 6: returns (cliques int64 per vertex, the number of k-cliques)."""
+    return _one_shot(CliqueProblem(device=device).init(nodes, row_offsets, col_indices, rank), CliqueProblem.reset,
+                     lambda p: p.enact(k), CliqueProblem.extract)
 
 
 MSBFS_AUTO, MSBFS_PUSH, MSBFS_PULL, MSBFS_ALTERNATE = 0, 1, 2, 3  # enum GRX_MSBFS_* (gunrock_mi355x.h): option "direction"

@@ -915,6 +915,58 @@ int grx_matching_coarse_device(grx_matching *p, int **d_map, int **d_row_offsets
 void grx_matching_destroy(grx_matching *p);
 
 /* ------------------------------------------------------------------------------------------------
+ * CLIQUE: CliqueProblem + CliqueEnactor: k-clique counts for k = 3 .. 6 (no counterpart in the reference snapshot).  The CSR is
+ * read exactly as grx_tc_* / grx_kcore_* read it, as the simple undirected graph G: u and v are neighbours when either row holds the
+ * other, self-loops are ignored, rows may be unsorted and may hold duplicates and one-way entries.  Every result has one value:
+ *   cliques[v]  the number of k-cliques of G that contain v (int64, `nodes` entries)
+ *   total       the number of k-cliques of G (int64); sum(cliques) = k * total
+ * For k = 3 both are byte-identical to grx_tc_*'s triangles[] and total.  Init orients every edge from the end with the smaller
+ * (rank[v], d(v), v) to the larger; every clique is then found once, at its smallest member u, inside N+(u).  `rank` is an int32
+ * per vertex or NULL (all equal: TC's (d, id) orientation, no out-row beyond floor(sqrt(2 M))).  Among vertices of one rank those
+ * go first that a peel lets go: a vertex leaves once at most max(rank, 0) neighbours of its own or a higher rank are left; the rest
+ * follow by (d, id).  With grx_kcore_*'s core numbers as the rank that is the degeneracy orientation: no out-row is longer than the
+ * degeneracy.  No rank changes a result.  Enact counts a row of up to "bitmap_rows" entries as nested ANDs and popcounts of the bit
+ * matrix of N+(u) in LDS, a longer one by list intersections in global scratch.
+ * Counts never wrap: Enact refuses (GRX_CLIQUE_OVERFLOW) when sum over u of C(d+(u), k - 1), a float64 computed on the device that
+ * is at least `total` and every cliques[v], reaches "count_limit".
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct grx_clique grx_clique;
+enum { GRX_CLIQUE_AUTO = 0, GRX_CLIQUE_BITMAP = 1, GRX_CLIQUE_LIST = 2 };
+enum { GRX_CLIQUE_OVERFLOW = -7 };  /* next to -1 / -2 / -3 */
+
+int grx_clique_create(grx_clique **out, int instrument, int device);
+/* CliqueProblem::Init: validates the CSR and builds the oriented graph on the device.  rank: `nodes` int32 or NULL.  -1: nodes < 1,
+ * edges < 0 or a NULL array; -2: not a CSR of `nodes` vertices, as grx_tc_init; -3: the handle has been given a graph before
+ * (accepted or rejected) */
+int grx_clique_init(grx_clique *p, int nodes, int edges, const int *row_offsets, const int *col_indices, const int *rank /* or NULL */);
+/* the same for a CSR (and a rank, or NULL) already in HBM: borrowed, not freed, the rank read by the build only */
+int grx_clique_init_device(grx_clique *p, int nodes, int edges, int *d_row_offsets, int *d_col_indices, const int *d_rank /* or NULL */);
+/* named options, for the next Enact; 0: set, 1: unknown name, -1: a value out of range.  None changes a result.
+ *   "strategy"     GRX_CLIQUE_AUTO (default): rows up to "bitmap_rows" entries take the bitmap regime, longer ones the list regime;
+ *                  GRX_CLIQUE_BITMAP / GRX_CLIQUE_LIST force that regime for every row (under GRX_CLIQUE_BITMAP a row beyond 1024
+ *                  entries still takes the list regime)
+ *   "bitmap_rows"  the longest row of the bitmap regime under GRX_CLIQUE_AUTO (default 512, 32 .. 1024; 512 rows take 32 KiB of LDS
+ *                  for the matrix, 1024 rows 128 KiB)
+ *   "count_limit"  Enact refuses when the bound reaches it (default and at most 2^62, at least 1); changes refusals only */
+int grx_clique_set_option(grx_clique *p, const char *name, double value);
+/* CliqueProblem::Reset: the counts to zero */
+int grx_clique_reset(grx_clique *p);
+/* CliqueEnactor::Enact(problem, k, max_grid_size), HIP-event timed.  -1: k outside 3 .. 6.  Without a Reset since the last Enact it
+ * resets itself.  GRX_CLIQUE_OVERFLOW: the bound reached "count_limit"; no kernel ran, the handle holds no result and takes the next
+ * Enact */
+int grx_clique_enact(grx_clique *p, int k, int max_grid_size, float *elapsed_ms);
+/* any pointer may be NULL.  Oriented edges (M) and the longest out-row of the graph; of the last Enact: the rows of at least
+ * k - 1 entries (a shorter one holds no clique) and their oriented edges that the bitmap and the list regime took (regime_rows[2], regime_edges[2]), bit-row ANDs, list look-ups, the bound
+ * of its k, kernel launches and -- when instrumented -- the summed kernel time; build_ms: the HIP-event time of Init's build */
+int grx_clique_stats(grx_clique *p, long long *oriented_edges, long long *max_out_row, long long *regime_rows, long long *regime_edges,
+                     long long *bit_ands, long long *list_lookups, double *bound, long long *kernel_launches, double *kernel_ms, double *build_ms);
+/* Before a finished Enact (none yet, a Reset since, or a refused one): hipErrorNotReady */
+int grx_clique_extract(grx_clique *p, long long *h_cliques /* may be NULL */, long long *total);
+/* device arrays of the handle: 64-bit counts and 32-bit degrees d(v), `nodes` each */
+int grx_clique_device_results(grx_clique *p, long long **d_cliques, int **d_degrees);
+void grx_clique_destroy(grx_clique *p);
+
+/* ------------------------------------------------------------------------------------------------
  * SSSP: SSSPProblem + SSSPEnactor (reference gunrock/app/sssp/sssp_problem.cuh:35-387, sssp_enactor.cuh:36-563)
  * ---------------------------------------------------------------------------------------------- */
 typedef struct grx_sssp grx_sssp;
