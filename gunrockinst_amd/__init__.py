@@ -1,4 +1,4 @@
-"""gunrockinst_amd -- MI355X-native frontier engine (BFS / CC / SSSP / BC / PageRank / TopK / MST / MIS / TC / k-core / k-truss / SCC / MS-BFS / BCC / max-flow / matching / k-cliques) behind Gunrock's C ABI.
+"""gunrockinst_amd -- MI355X-native frontier engine (BFS / CC / SSSP / BC / PageRank / TopK / MST / MIS / TC / k-core / k-truss / SCC / MS-BFS / BCC / max-flow / matching / k-cliques / label propagation) behind Gunrock's C ABI.
 
 The product is the shared library ``gunrockinst_amd/lib/libgunrock.so`` (hand-written HIP for gfx950,
 built by ``gunrockinst_amd/csrc/Makefile``).  This package is only the host-side binding: ctypes
@@ -26,6 +26,8 @@ from .capi import (  # noqa: F401
     MATCHING_DEVICE_LOOP, MATCHING_STEP_WIDE, MATCHING_STEP_LOOP, MATCHING_GAVE_UP, MATCHING_OVERFLOW,
     BcOverflow, BC_OVERFLOW,
     CliqueProblem, CliqueOverflow, gunrock_cliques, CLIQUE_AUTO, CLIQUE_BITMAP, CLIQUE_LIST, CLIQUE_OVERFLOW,
+    LpProblem, gunrock_label_propagation, modularity_from_sums, LP_SYNC, LP_CLASSES, LP_AUTO, LP_LANE, LP_WAVE, LP_BLOCK,
+    LP_CONVERGED, LP_PERIOD2, LP_CAPPED, LP_BAD_CLASSES,
     advance_frontier, advance_queue, advance_reduce,
 )
 
@@ -48,5 +50,7 @@ __all__ = [
     "MATCHING_ROUNDS", "MATCHING_DEVICE_LOOP", "MATCHING_STEP_WIDE", "MATCHING_STEP_LOOP", "MATCHING_GAVE_UP", "MATCHING_OVERFLOW",
     "BcOverflow", "BC_OVERFLOW",
     "CliqueProblem", "CliqueOverflow", "gunrock_cliques", "CLIQUE_AUTO", "CLIQUE_BITMAP", "CLIQUE_LIST", "CLIQUE_OVERFLOW",
+    "LpProblem", "gunrock_label_propagation", "modularity_from_sums", "LP_SYNC", "LP_CLASSES", "LP_AUTO", "LP_LANE", "LP_WAVE", "LP_BLOCK",
+    "LP_CONVERGED", "LP_PERIOD2", "LP_CAPPED", "LP_BAD_CLASSES",
     "advance_frontier", "advance_queue", "advance_reduce",
 ]

@@ -278,6 +278,19 @@ _SIGNATURES = {
     "grx_clique_extract": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "grx_clique_device_results": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "grx_clique_destroy": (None, [C.c_void_p]),
+    "grx_lp_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int]),
+    "grx_lp_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p, i32p]),
+    "grx_lp_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "grx_lp_set_classes": (C.c_int, [C.c_void_p, i32p, C.c_int]),
+    "grx_lp_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
+    "grx_lp_reset": (C.c_int, [C.c_void_p, i32p]),
+    "grx_lp_enact": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
+    "grx_lp_stats": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_longlong)] * 9 + [C.POINTER(C.c_double)] * 2),
+    "grx_lp_round_trace": (C.c_int, [C.c_void_p, C.c_int] + [C.POINTER(C.c_longlong)] * 2),
+    "grx_lp_extract": (C.c_int, [C.c_void_p, i32p, i32p, C.POINTER(C.c_longlong)]),
+    "grx_lp_summary": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_longlong)] * 4),
+    "grx_lp_device_results": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "grx_lp_destroy": (None, [C.c_void_p]),
     "grx_sssp_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int]),
     "grx_sssp_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p, C.POINTER(C.c_uint32), C.c_int]),
     "grx_sssp_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float]),
@@ -1935,6 +1948,148 @@ def gunrock_cliques(nodes, row_offsets, col_indices, k, rank=None, device=0):
     """One-shot k-clique counting, k = 3 .. 6: returns (cliques int64 per vertex, the number of k-cliques)."""
     return _one_shot(CliqueProblem(device=device).init(nodes, row_offsets, col_indices, rank), CliqueProblem.reset,
                      lambda p: p.enact(k), CliqueProblem.extract)
+
+
+LP_SYNC, LP_CLASSES = 0, 1  # enum GRX_LP_* (gunrock_mi355x.h): option "mode"
+LP_AUTO, LP_LANE, LP_WAVE, LP_BLOCK = 0, 1, 2, 3  # option "strategy"
+LP_CONVERGED, LP_PERIOD2, LP_CAPPED = 0, 1, 2  # stats()["state"]: how the last enact ended
+LP_BAD_CLASSES = -8  # grx_lp_set_classes: a pair has both ends in one class
+
+
+class LpProblem(_Handle):
+    """LpProblem + LpEnactor behind the handle C ABI: label-propagation communities of the CSR read as an undirected simple graph
+    with int32 weights of at least 1 (None: 1 each; a pair's weight is the largest of its entries).  Integer scores and a total tie
+    rule (keep the current label, else the smallest): every label has one value after any number of rounds."""
+
+    _destroy = "grx_lp_destroy"
+
+    _STATS = ("pairs", "rounds", "state", "visits", "entries_read")
+    _STATS_TAIL = ("fallback_rows", "kernel_launches", "readbacks")
+
+    def __init__(self, instrument=False, device=0):
+        self._create("grx_lp_create", int(instrument), device)
+        self.nodes = 0
+        self.entries = 0
+
+    def init(self, nodes, row_offsets, col_indices, weights=None):
+        ro, ci = _csr_arrays(row_offsets, col_indices, nodes)
+        w = None if weights is None else _i32(weights)
+        if w is not None and w.shape[0] != ci.shape[0]:
+            raise ValueError("gunrockinst_amd: %d weights for %d entries" % (w.shape[0], ci.shape[0]))
+        self.nodes, self.entries = int(nodes), int(ci.shape[0])
+        _check(lib().grx_lp_init(self._h, self.nodes, self.entries, _p(ro), _p(ci), None if w is None else _p(w)), "LpProblem::Init")
+        return self
+
+    def init_device(self, nodes, edges, d_row_offsets, d_col_indices, d_weights=None):
+        """the CSR (and the weights) stay the caller's; the build reads them, nothing later does"""
+        self.nodes, self.entries = int(nodes), int(edges)
+        _check(lib().grx_lp_init_device(self._h, self.nodes, self.entries, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices),
+                                        C.c_void_p(d_weights) if d_weights else None), "LpProblem::Init(device)")
+        return self
+
+    def set_classes(self, classes, num_classes=None):
+        """a proper colouring for LP_CLASSES: int32 per vertex in [0, num_classes) (None: max + 1); returns the library's code:
+        0 = installed, LP_BAD_CLASSES = a pair has both ends in one class and nothing is installed (anything else raises)"""
+        cl = _i32(classes)
+        if cl.shape[0] != self.nodes:
+            raise ValueError("gunrockinst_amd: %d classes for %d nodes" % (cl.shape[0], self.nodes))
+        count = int(cl.max()) + 1 if num_classes is None else int(num_classes)
+        rc = lib().grx_lp_set_classes(self._h, _p(cl), count)
+        if rc not in (0, LP_BAD_CLASSES):
+            _check(rc, "LpProblem::SetClasses")
+        return rc
+
+    def set_option(self, name, value):
+        """"mode" (LP_CLASSES / LP_SYNC), "strategy" (LP_AUTO / LP_LANE / LP_WAVE / LP_BLOCK), "lane_max_row", "wave_max_row",
+        "table_slots", "max_rounds"; returns the library's code: 0 = set, 1 = unknown name (a value out of range raises)"""
+        rc = lib().grx_lp_set_option(self._h, name.encode(), float(value))
+        if rc not in (0, 1):
+            _check(rc, "grx_lp_set_option(%s)" % name)
+        return rc
+
+    def reset(self, labels=None):
+        """L[v] = labels[v] (int32 in [0, nodes)), or v for None"""
+        lb = None if labels is None else _i32(labels)
+        if lb is not None and lb.shape[0] != self.nodes:
+            raise ValueError("gunrockinst_amd: %d labels for %d nodes" % (lb.shape[0], self.nodes))
+        _check(lib().grx_lp_reset(self._h, None if lb is None else _p(lb)), "LpProblem::Reset")
+
+    def enact(self, max_grid_size=0):
+        """the elapsed milliseconds; stats()["state"] tells how it ended"""
+        return self._timed(lib().grx_lp_enact, "LpEnactor::Enact", int(max_grid_size))
+
+    def stats(self):
+        v = [C.c_longlong() for _ in self._STATS]
+        regime = (C.c_longlong * 3)()
+        tail = [C.c_longlong() for _ in self._STATS_TAIL]
+        k, b = C.c_double(), C.c_double()
+        _check(lib().grx_lp_stats(self._h, *([C.byref(x) for x in v] + [regime] + [C.byref(x) for x in tail] + [C.byref(k), C.byref(b)])),
+               "grx_lp_stats")
+        out = {name: x.value for name, x in zip(self._STATS + self._STATS_TAIL, v + tail)}
+        out["regime_rows"] = [int(x) for x in regime]
+        out["kernel_ms"], out["build_ms"] = k.value, b.value
+        return out
+
+    def round_trace(self):
+        """per round of the last enact, the closing one included: (vertices visited, labels changed) as int64"""
+        count = lib().grx_lp_round_trace(self._h, 0, None, None)
+        if count < 0:
+            _check(count, "grx_lp_round_trace")
+        visited, changed = (np.empty(max(count, 1), dtype=np.int64) for _ in range(2))
+        lib().grx_lp_round_trace(self._h, count, _i64p(visited), _i64p(changed))
+        return visited[:count], changed[:count]
+
+    def extract(self):
+        """(labels int32 per vertex, community int32 per vertex: the rank of its label among the labels in use, communities)"""
+        n = max(self.nodes, 1)
+        labels, community = np.empty(n, np.int32), np.empty(n, np.int32)
+        count = C.c_longlong()
+        _check(lib().grx_lp_extract(self._h, _p(labels), _p(community), C.byref(count)), "LpProblem::Extract")
+        return labels[:self.nodes], community[:self.nodes], int(count.value)
+
+    def summary(self):
+        """{"size", "internal", "volume": int64 per community, "W": the sum of all pair weights}"""
+        count = C.c_longlong()
+        _check(lib().grx_lp_extract(self._h, None, None, C.byref(count)), "LpProblem::Extract")
+        k = int(count.value)
+        size, internal, volume = (np.empty(max(k, 1), np.int64) for _ in range(3))
+        total = C.c_longlong()
+        _check(lib().grx_lp_summary(self._h, _i64p(size), _i64p(internal), _i64p(volume), C.byref(total)), "LpProblem::Summary")
+        return {"size": size[:k], "internal": internal[:k], "volume": volume[:k], "W": int(total.value)}
+
+    def device_results(self):
+        """device pointers {"labels", "community"}: int32 per vertex"""
+        a, b = C.c_void_p(), C.c_void_p()
+        _check(lib().grx_lp_device_results(self._h, C.byref(a), C.byref(b)), "grx_lp_device_results")
+        return {"labels": a.value, "community": b.value}
+
+
+def modularity_from_sums(internal, volume, W):
+    """Newman's modularity in float64 from LpProblem.summary()'s integers: sum(internal / W - (volume / (2 W))^2); 0.0 without a pair"""
+    if int(W) == 0:
+        return 0.0
+    internal, volume = np.asarray(internal, np.float64), np.asarray(volume, np.float64)
+    return float(np.sum(internal / float(W) - (volume / (2.0 * float(W))) ** 2))
+
+
+def gunrock_label_propagation(nodes, row_offsets, col_indices, weights=None, mode=LP_CLASSES, labels=None, max_rounds=0, seed=0, device=0):
+    """One-shot label propagation: returns (labels, community, communities, state, rounds).  In LP_CLASSES mode the classes are
+    gunrock_color(seed=seed)'s colours."""
+    colours = None
+    if mode == LP_CLASSES:
+        colours = gunrock_color(nodes, row_offsets, col_indices, seed=seed, device=device)[0]
+
+    def prepare(p):
+        p.set_option("mode", mode)
+        p.set_option("max_rounds", max_rounds)
+        if colours is not None:
+            _check(p.set_classes(np.asarray(colours, np.int32) - 1), "LpProblem::SetClasses")
+        p.reset(labels)
+
+    def result(p):
+        st = p.stats()
+        return p.extract() + (st["state"], st["rounds"])
+    return _one_shot(LpProblem(device=device).init(nodes, row_offsets, col_indices, weights), prepare, LpProblem.enact, result)
 
 
 MSBFS_AUTO, MSBFS_PUSH, MSBFS_PULL, MSBFS_ALTERNATE = 0, 1, 2, 3  # enum GRX_MSBFS_* (gunrock_mi355x.h): option "direction"

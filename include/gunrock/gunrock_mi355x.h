@@ -967,6 +967,74 @@ int grx_clique_device_results(grx_clique *p, long long **d_cliques, int **d_degr
 void grx_clique_destroy(grx_clique *p);
 
 /* ------------------------------------------------------------------------------------------------
+ * LP: LpProblem + LpEnactor: label-propagation communities with integer scores and a total tie rule (no counterpart in the
+ * reference snapshot).  The CSR is read exactly as grx_matching_* reads it, as the simple undirected graph G with int32 weights
+ * (NULL: 1 each; a pair's weight is the largest of its entries in both directions); a pair weight below 1 is refused.  L[v] is an
+ * int32 label in [0, nodes).  The vote of a vertex with a neighbour: score(l) = the sum of w(v, u) over the neighbours u with
+ * L[u] = l, in 64 bits; the new label is L[v] when its score is the largest, else the smallest label of the largest score.  An
+ * isolated vertex keeps its label.
+ *   GRX_LP_SYNC     every round computes all new labels from the labels of the round before
+ *   GRX_LP_CLASSES  a round is one sub-step per class of a proper colouring (grx_lp_set_classes), in class order; a sub-step
+ *                   updates its class in place from the current labels, so a round is the sequential sweep in (class, id) order.
+ *                   This mode always reaches a fixed point.
+ * A vertex is visited at its turn when it has not been visited since the Reset or a neighbour's label changed since its last
+ * visit; no result depends on that, the counters `visits` and `entries_read` (the rows of the visits) are defined by it.  An Enact
+ * ends in one of three states, none an error: GRX_LP_CONVERGED (a round changed nothing), GRX_LP_PERIOD2 (SYNC: the labels behind
+ * round r are those behind round r - 2; the result is those behind r) or GRX_LP_CAPPED ("max_rounds" rounds have run).  Every
+ * result has one value; the library returns integers only.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct grx_lp grx_lp;
+enum { GRX_LP_SYNC = 0, GRX_LP_CLASSES = 1 };                                  /* option "mode" */
+enum { GRX_LP_AUTO = 0, GRX_LP_LANE = 1, GRX_LP_WAVE = 2, GRX_LP_BLOCK = 3 };  /* option "strategy" */
+enum { GRX_LP_CONVERGED = 0, GRX_LP_PERIOD2 = 1, GRX_LP_CAPPED = 2 };          /* `state` of grx_lp_stats */
+enum { GRX_LP_BAD_CLASSES = -8 };  /* next to -1 / -2 / -3 */
+
+int grx_lp_create(grx_lp **out, int instrument, int device);
+/* LpProblem::Init: validates the CSR and builds the pairs and the neighbour CSR on the device.  weights: `edges` int32 or NULL.
+ * -1: nodes < 1, edges < 0 or a NULL array; -2: not a CSR of `nodes` vertices, or a pair weight below 1; -3: the handle has been
+ * given a graph before (accepted or rejected) */
+int grx_lp_init(grx_lp *p, int nodes, int edges, const int *row_offsets, const int *col_indices, const int *weights /* or NULL */);
+/* the same for a CSR (and weights, or NULL) already in HBM: borrowed, not freed, read by the build only */
+int grx_lp_init_device(grx_lp *p, int nodes, int edges, int *d_row_offsets, int *d_col_indices, int *d_weights /* or NULL */);
+/* classes: `nodes` int32 in [0, num_classes), num_classes in 1 .. nodes (else -1), a proper colouring of G.  Validated on the device
+ * over the pairs: GRX_LP_BAD_CLASSES when a pair has both ends in one class; then no classes are installed (an Enact in
+ * GRX_LP_CLASSES mode answers hipErrorNotReady) */
+int grx_lp_set_classes(grx_lp *p, const int *classes, int num_classes);
+/* named options, for the next Enact; 0: set, 1: unknown name, -1: a value out of range.  None changes a result.
+ *   "mode"          GRX_LP_CLASSES (default) or GRX_LP_SYNC
+ *   "strategy"      GRX_LP_AUTO (default): a row of up to "lane_max_row" entries is voted by one lane, one of up to "wave_max_row"
+ *                   by a wave with a table in LDS, a longer one by a workgroup; GRX_LP_LANE / _WAVE / _BLOCK force one for all rows
+ *   "lane_max_row"  default 16, at least 0
+ *   "wave_max_row"  default 512, at least 0
+ *   "table_slots"   slots of a wave's label table, a power of two in 64 .. 1024 (default 1024); a workgroup's has four times as many.
+ *                   A row with more distinct labels is voted in several passes and counted in fallback_rows
+ *   "max_rounds"    an Enact stops behind this many rounds (default 0: 2 * nodes + 64; at most 2^30) */
+int grx_lp_set_option(grx_lp *p, const char *name, double value);
+/* LpProblem::Reset: L[v] = labels[v], or v for NULL; -1: a label outside [0, nodes) */
+int grx_lp_reset(grx_lp *p, const int *labels /* or NULL */);
+/* LpEnactor::Enact(problem, max_grid_size), HIP-event timed.  Without a Reset since the last Enact it resets itself to L[v] = v.
+ * 0 in all three end states (grx_lp_stats tells which) */
+int grx_lp_enact(grx_lp *p, int max_grid_size, float *elapsed_ms);
+/* any pointer may be NULL.  The pairs (M) of the graph; of the last Enact: the rounds that changed a label, the end state, visits,
+ * entries_read, the visited rows per regime (regime_rows[3]: lane, wave, workgroup), the rows that needed several passes, kernel
+ * launches, host read-backs (at most rounds + 2) and -- when instrumented -- the summed kernel time; build_ms: the HIP-event time
+ * of Init's build */
+int grx_lp_stats(grx_lp *p, long long *pairs, long long *rounds, long long *state, long long *visits, long long *entries_read, long long *regime_rows,
+                 long long *fallback_rows, long long *kernel_launches, long long *readbacks, double *kernel_ms, double *build_ms);
+/* per round of the last Enact, the closing one included: the vertices visited and the labels changed; copies at most max_rounds
+ * entries and returns how many there are */
+int grx_lp_round_trace(grx_lp *p, int max_rounds, long long *list, long long *changed);
+/* labels[] and community[] (the rank of a vertex's label among the labels in use, ascending), `nodes` int32 each, either may be
+ * NULL; *communities: how many labels are in use.  Before a finished Enact (none yet, or a Reset since): hipErrorNotReady */
+int grx_lp_extract(grx_lp *p, int *h_labels, int *h_community, long long *communities);
+/* int64 per community of the last Enact: vertices, the sum of w over the pairs with both ends inside, the sum of the weighted
+ * degrees; *total_weight: the sum of w over all pairs.  Any pointer may be NULL.  Before a finished Enact: hipErrorNotReady */
+int grx_lp_summary(grx_lp *p, long long *h_size, long long *h_internal, long long *h_volume, long long *total_weight);
+/* device arrays of the handle: labels and community, `nodes` int32 each */
+int grx_lp_device_results(grx_lp *p, int **d_labels, int **d_community);
+void grx_lp_destroy(grx_lp *p);
+
+/* ------------------------------------------------------------------------------------------------
  * SSSP: SSSPProblem + SSSPEnactor (reference gunrock/app/sssp/sssp_problem.cuh:35-387, sssp_enactor.cuh:36-563)
  * ---------------------------------------------------------------------------------------------- */
 typedef struct grx_sssp grx_sssp;
