@@ -20,35 +20,26 @@
 #include <gunrock/app/bcc/bcc_functor.hpp>
 #include <gunrock/app/bcc/bcc_problem.hpp>
 #include <gunrock/app/enactor_base.hpp>
+#include <gunrock/app/step_host.hpp>
 
 namespace gunrock {
 namespace app {
 namespace bcc {
 
 constexpr int kStepWavesPerBlock = kBccThreads / util::kWaveSize;
-constexpr int kStepBlocks = 2048;  // 256 CUs x 8 workgroups
 constexpr int kStepWaves = kStepBlocks * kStepWavesPerBlock;
+static_assert(BCC_AUTO == SCHEDULE_AUTO && BCC_ROUNDS == SCHEDULE_ROUNDS && BCC_DEVICE_LOOP == SCHEDULE_DEVICE_LOOP, "LoopOptions' schedules");
 
 template <bool INSTRUMENT>
 class BccEnactor : public EnactorBase {
    public:
     explicit BccEnactor(bool DEBUG = false) : EnactorBase(VERTEX_FRONTIERS, DEBUG) {}
-    ~BccEnactor() override
-    {
-        if (ev[0]) hipEventDestroy(ev[0]);
-        if (ev[1]) hipEventDestroy(ev[1]);
-        if (h_pinned) hipHostFree(h_pinned);
-    }
 
-    // options (grx_bcc_set_option)
-    int schedule = BCC_AUTO;
-    int wave_min_row = kWaveMinRow;
-    long long loop_max_list = kLoopMaxList;
-    long long loop_max_entries = kLoopMaxEntries;
+    LoopOptions loop;  // options (grx_bcc_set_option)
 
-    // of the last Enact
-    long long trees = 0, levels = 0, entries_read = 0, launches = 0, readbacks = 0;
-    double kernel_ms = 0;             // INSTRUMENT: summed kernel time
+    // of the last Enact (step: its launches, read-backs and summed kernel time)
+    StepHost<INSTRUMENT> step{"BccEnactor"};
+    long long trees = 0, levels = 0, entries_read = 0;
     std::vector<long long> trace_items;  // one row per phase: the vertices or edges it touched,
     std::vector<double> trace_ms;        // and the time to the next phase's start (the device's constant-rate counter)
 
@@ -61,56 +52,22 @@ class BccEnactor : public EnactorBase {
         typename Problem::DataSlice *ds = problem->data_slices[0];
         hipStream_t stream = problem->graph_slices[0]->stream;
         const long long n = problem->nodes, M = problem->simple_edges;
-        trees = levels = entries_read = launches = readbacks = 0;
-        kernel_ms = 0;
+        trees = levels = entries_read = 0;
         trace_items.assign(PHASE_COUNT, 0);
         trace_ms.assign(PHASE_COUNT, 0.0);
-        if (INSTRUMENT && !ev[0]) {
-            GR_CHECK(hipEventCreate(&ev[0]), "BccEnactor hipEventCreate failed");
-            GR_CHECK(hipEventCreate(&ev[1]), "BccEnactor hipEventCreate failed");
-        }
-        // run(launch): one kernel launch, counted, and timed when instrumented
-        auto run = [&](auto launch) -> hipError_t {
-            hipError_t retval = hipSuccess;
-            if (INSTRUMENT) GR_CHECK(hipEventRecord(ev[0], stream), "BccEnactor hipEventRecord failed");
-            launch();
-            GR_CHECK(hipGetLastError(), "BccEnactor kernel launch failed");
-            ++launches;
-            if (INSTRUMENT) {
-                float ms = 0;
-                GR_CHECK(hipEventRecord(ev[1], stream), "BccEnactor hipEventRecord failed");
-                GR_CHECK(hipEventSynchronize(ev[1]), "BccEnactor hipEventSynchronize failed");
-                GR_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]), "BccEnactor hipEventElapsedTime failed");
-                kernel_ms += ms;
-            }
-            return retval;
-        };
-        auto stamp = [&](int phase) -> hipError_t {
-            hipLaunchKernelGGL(StampKernel, dim3(1), dim3(1), 0, stream, ds->d_clock + phase);
-            return util::GRError(hipGetLastError(), "StampKernel launch failed", __FILE__, __LINE__);
-        };
-        auto grid_for = [&](long long work) {
-            int g = Problem::Grid(work);
-            if (max_grid_size > 0 && g > max_grid_size) g = max_grid_size;
-            return dim3(static_cast<unsigned>(g));
-        };
-        auto step_grid = [&](long long count, int tile) {
-            long long blocks = ((count + tile - 1) / tile + kStepWavesPerBlock - 1) / kStepWavesPerBlock;
-            if (blocks > kStepBlocks) blocks = kStepBlocks;
-            if (max_grid_size > 0 && blocks > max_grid_size) blocks = max_grid_size;
-            if (blocks < 1) blocks = 1;
-            return dim3(static_cast<unsigned>(blocks));
-        };
+        // pinned: the words, LoopKernel's front, the counters and the clocks
+        if ((retval = step.Begin(256))) return retval;
+        auto run = [&](auto launch) { return step.Run(stream, launch); };
+        auto stamp = [&](int phase) { return step.Stamp(ds->d_clock + phase, stream); };
+        auto grid_for = [&](long long work) { return GridFor(work, max_grid_size); };
+        auto step_grid = [&](long long count, int tile) { return StepGrid(count, tile, kStepWavesPerBlock, max_grid_size); };
 
-        const Ctx c = problem->DeviceCtx(wave_min_row);
+        const Ctx c = problem->DeviceCtx(loop.wave_min_row);
         const Tree tr = problem->DeviceTree();
-        const bool all = schedule == BCC_DEVICE_LOOP;
-        const Limits lim = {all ? LLONG_MAX : loop_max_list, all ? LLONG_MAX : loop_max_entries, kLoopMaxSteps};
-        // pinned: the read-backs land here without a staging copy (the words, LoopKernel's front, the counters and the clocks)
-        if (!h_pinned) GR_CHECK(hipHostMalloc(&h_pinned, 256), "BccEnactor hipHostMalloc failed");
-        unsigned *words = reinterpret_cast<unsigned *>(h_pinned);
-        Front *h_front = reinterpret_cast<Front *>(h_pinned + 32);
-        unsigned long long *h_counters = reinterpret_cast<unsigned long long *>(h_pinned + 64);  // 8, then PHASE_COUNT + 1 clocks
+        const Limits lim = loop.LimitsFor();
+        unsigned *words = reinterpret_cast<unsigned *>(step.pinned);
+        Front *h_front = reinterpret_cast<Front *>(step.pinned + 32);
+        unsigned long long *h_counters = reinterpret_cast<unsigned long long *>(step.pinned + 64);  // 8, then PHASE_COUNT + 1 clocks
         unsigned long long *h_clock = h_counters + 8;
 
         // ---- forest ----
@@ -124,19 +81,15 @@ class BccEnactor : public EnactorBase {
             if ((retval = run([&]() { hipLaunchKernelGGL(scc::IotaKernel, grid_for(n), dim3(256), 0, stream, ds->d_comp, n); }))) return retval;
         }
         if ((retval = run([&]() { hipLaunchKernelGGL(RootsKernel, grid_for(n), dim3(256), 0, stream, c, ds->d_comp); }))) return retval;
-        GR_CHECK(hipMemcpyAsync(words, ds->d_words, sizeof(unsigned) * W_COUNT, hipMemcpyDeviceToHost, stream), "BccEnactor read-back failed");
-        GR_CHECK(hipStreamSynchronize(stream), "BccEnactor read-back sync failed");
-        ++readbacks;
+        if ((retval = step.Read(words, ds->d_words, sizeof(unsigned) * W_COUNT, stream))) return retval;
         trees = words[W_TAIL];
         Front s = {0, 0u, words[W_TAIL], words[W_ENTRIES], words[W_ENTRIES]};
         while (s.head < s.tail) {
             const long long count = s.tail - s.head;
-            if (all || (schedule == BCC_AUTO && Narrow(count, s.step_entries, lim))) {
+            if (loop.InLoop(count, s.step_entries)) {
                 if ((retval = run([&]() { hipLaunchKernelGGL(ForestLoopKernel, dim3(1), dim3(kLoopThreads), 0, stream, c, s, lim, ds->d_front); })))
                     return retval;
-                GR_CHECK(hipMemcpyAsync(h_front, ds->d_front, sizeof(Front), hipMemcpyDeviceToHost, stream), "BccEnactor read-back failed");
-                GR_CHECK(hipStreamSynchronize(stream), "BccEnactor read-back sync failed");
-                ++readbacks;
+                if ((retval = step.Read(h_front, ds->d_front, sizeof(Front), stream))) return retval;
                 s = *h_front;
                 continue;
             }
@@ -146,9 +99,7 @@ class BccEnactor : public EnactorBase {
                                         s.entries_seen, tile);
                  })))
                 return retval;
-            GR_CHECK(hipMemcpyAsync(words, ds->d_words, sizeof(unsigned) * W_COUNT, hipMemcpyDeviceToHost, stream), "BccEnactor read-back failed");
-            GR_CHECK(hipStreamSynchronize(stream), "BccEnactor read-back sync failed");
-            ++readbacks;
+            if ((retval = step.Read(words, ds->d_words, sizeof(unsigned) * W_COUNT, stream))) return retval;
             ++s.level;
             s.head = s.tail;
             s.tail = words[W_TAIL];
@@ -163,14 +114,12 @@ class BccEnactor : public EnactorBase {
         std::vector<int> bounds(static_cast<size_t>(levels) + 1, 0);
         std::vector<unsigned> ents(static_cast<size_t>(levels) + 1, 0u);
         if (levels > 0) {
-            GR_CHECK(hipMemcpyAsync(bounds.data(), ds->d_bounds, sizeof(int) * bounds.size(), hipMemcpyDeviceToHost, stream), "BccEnactor read-back failed");
-            GR_CHECK(hipMemcpyAsync(ents.data(), ds->d_ents, sizeof(unsigned) * ents.size(), hipMemcpyDeviceToHost, stream), "BccEnactor read-back failed");
-            GR_CHECK(hipStreamSynchronize(stream), "BccEnactor read-back sync failed");
-            ++readbacks;
+            if ((retval = step.Copy(bounds.data(), ds->d_bounds, sizeof(int) * bounds.size(), stream))) return retval;
+            if ((retval = step.Read(ents.data(), ds->d_ents, sizeof(unsigned) * ents.size(), stream))) return retval;
         }
         auto width = [&](long long L) { return static_cast<long long>(bounds[L + 1]) - bounds[L]; };
         auto weight = [&](long long L) { return static_cast<long long>(ents[L + 1] - ents[L]); };
-        auto in_loop = [&](long long L) { return all || (schedule == BCC_AUTO && Narrow(width(L), weight(L), lim)); };
+        auto in_loop = [&](long long L) { return loop.InLoop(width(L), weight(L)); };
 
         // one chain: the levels from `first` on in direction dir
         auto chain = [&](auto kind, int dir) -> hipError_t {
@@ -225,7 +174,7 @@ class BccEnactor : public EnactorBase {
         if (M > 0) {
             if ((retval = run([&]() { hipLaunchKernelGGL(EdgeSetKernel, grid_for(M), dim3(256), 0, stream, tr, ds->d_src, ds->d_dst, M, ds->d_set, ds->d_bcc); })))
                 return retval;
-            if ((retval = run([&]() { hipLaunchKernelGGL(FillKernel, grid_for(n), dim3(256), 0, stream, ds->d_min_of, n, INT_MAX); }))) return retval;
+            if ((retval = run([&]() { hipLaunchKernelGGL(oprtr::FillKernel<int>, grid_for(n), dim3(256), 0, stream, ds->d_min_of, n, INT_MAX); }))) return retval;
             GR_CHECK(hipMemsetAsync(ds->d_cnt_of, 0, sizeof(int) * static_cast<size_t>(n), stream), "BccEnactor memset failed");
             if ((retval = run([&]() { hipLaunchKernelGGL(scc::MergeKernel<false>, grid_for(M), dim3(256), 0, stream, ds->d_bcc, M, ds->d_min_of); })))
                 return retval;
@@ -261,11 +210,8 @@ class BccEnactor : public EnactorBase {
         if ((retval = stamp(PHASE_COUNT))) return retval;
 
         // the counters and the clocks
-        GR_CHECK(hipMemcpyAsync(h_counters, ds->d_counters, sizeof(unsigned long long) * 8, hipMemcpyDeviceToHost, stream), "BccEnactor read-back failed");
-        GR_CHECK(hipMemcpyAsync(h_clock, ds->d_clock, sizeof(unsigned long long) * (PHASE_COUNT + 1), hipMemcpyDeviceToHost, stream),
-                 "BccEnactor read-back failed");
-        GR_CHECK(hipStreamSynchronize(stream), "BccEnactor read-back sync failed");
-        ++readbacks;
+        if ((retval = step.Copy(h_counters, ds->d_counters, sizeof(unsigned long long) * 8, stream))) return retval;
+        if ((retval = step.Read(h_clock, ds->d_clock, sizeof(unsigned long long) * (PHASE_COUNT + 1), stream))) return retval;
         entries_read = static_cast<long long>(h_counters[0]);
         Summary &out = problem->summary;
         out = Summary();
@@ -285,10 +231,6 @@ class BccEnactor : public EnactorBase {
         problem->enacted = true;
         return retval;
     }
-
-   private:
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    unsigned char *h_pinned = nullptr;
 };
 
 }  // namespace bcc

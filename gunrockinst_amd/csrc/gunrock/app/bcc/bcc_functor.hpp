@@ -27,9 +27,10 @@
 #include <hip/hip_runtime.h>
 
 #pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunused-function"  // (only SCC's accessors, tile rule and canonical-id kernels are used here)
+#pragma clang diagnostic ignored "-Wunused-function"  // (only SCC's canonical-id kernels are used here)
 #include <gunrock/app/scc/scc_functor.hpp>
 #pragma clang diagnostic pop
+#include <gunrock/oprtr/step.hpp>
 #include <gunrock/util/device_intrinsics.hpp>
 
 namespace gunrock {
@@ -40,16 +41,15 @@ enum { BCC_AUTO = 0, BCC_ROUNDS = 1, BCC_DEVICE_LOOP = 2 };
 enum { PHASE_FOREST = 0, PHASE_SIZES, PHASE_NUMBER, PHASE_LOWHIGH, PHASE_LINK, PHASE_LABEL, PHASE_COUNT };
 
 constexpr int kBccThreads = 256;
-constexpr int kLoopThreads = 1024;
-constexpr int kWaveMinRow = 16;              // default "wave_min_row" (taken over from SCC, not tuned)
-constexpr long long kLoopMaxList = 32768;    // AUTO: the device loop takes a level of up to this many vertices ...
-constexpr long long kLoopMaxEntries = 8192;  // ... whose rows hold up to this many entries (both taken over, not tuned)
-constexpr int kLoopMaxSteps = 4096;          // steps per loop launch
 constexpr int kUnseen = -2;                  // parent[]: not reached (-1: a root, or a vertex without a neighbour)
 
-using scc::Ld;
-using scc::St;
-using scc::TileFor;
+using oprtr::kLoopMaxSteps;
+using oprtr::kLoopThreads;
+using oprtr::Ld;
+using oprtr::Limits;
+using oprtr::Narrow;
+using oprtr::St;
+using oprtr::TileFor;
 
 // the words the forest's kernels and the host share: none is reset during a run
 enum {
@@ -81,16 +81,6 @@ struct Front {
     unsigned step_entries;  // row entries of [head, tail)
 };
 
-struct Limits {
-    long long max_list, max_entries;
-    int max_steps;
-};
-
-__host__ __device__ __forceinline__ bool Narrow(long long count, long long entries, const Limits &lim)
-{
-    return count <= lim.max_list && entries <= lim.max_entries;
-}
-
 struct Tally {
     unsigned entries = 0;  // row entries of the vertices this lane queued
     unsigned reads = 0;    // row entries this lane walked
@@ -114,12 +104,8 @@ __device__ __forceinline__ void Append(const Ctx &c, bool hit, int w, Tally &t)
 {
     const unsigned long long mask = __ballot(hit);
     if (!mask) return;
-    const int lane = static_cast<int>(util::LaneId());
-    unsigned at = 0;
-    if (lane == 0) at = atomicAdd(c.words + W_TAIL, static_cast<unsigned>(__popcll(mask)));
-    at = __shfl(at, 0, util::kWaveSize);
+    const unsigned pos = oprtr::WaveTicket(c.words + W_TAIL, mask);
     if (hit) {
-        const unsigned pos = at + __popcll(mask & ((1ull << lane) - 1ull));
         if (pos < static_cast<unsigned>(c.nodes)) St<FRESH>(c.queue + pos, w);
         t.entries += static_cast<unsigned>(c.ro[w + 1] - c.ro[w]);
     }
@@ -448,8 +434,6 @@ static __global__ void RootsKernel(Ctx c, const int *d_comp)
     Flush(t, c);
 }
 
-static __global__ void StampKernel(unsigned long long *d_clock) { *d_clock = wall_clock64(); }
-
 // ---------------- the wide passes behind the chains ----------------
 
 struct Tree {
@@ -537,12 +521,6 @@ static __global__ void CutForestKernel(Tree tr, long long nodes, const unsigned 
         const int p = tr.parent[v];
         d_up[v] = p < 0 || d_bridge[tr.pedge[v]] ? static_cast<int>(v) : p;
     }
-}
-
-static __global__ void FillKernel(int *d_out, long long count, int value)
-{
-    const long long stride = static_cast<long long>(gridDim.x) * blockDim.x;
-    for (long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; i < count; i += stride) d_out[i] = value;
 }
 
 static __global__ void CountBytesKernel(const unsigned char *d_flag, long long count, unsigned long long *d_out)

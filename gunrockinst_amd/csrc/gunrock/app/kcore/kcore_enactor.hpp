@@ -19,41 +19,33 @@
 #include <gunrock/app/enactor_base.hpp>
 #include <gunrock/app/kcore/kcore_functor.hpp>
 #include <gunrock/app/kcore/kcore_problem.hpp>
+#include <gunrock/app/step_host.hpp>
 
 namespace gunrock {
 namespace app {
 namespace kcore {
 
 constexpr int kPeelWavesPerBlock = kKcoreThreads / util::kWaveSize;
-constexpr int kPeelWaves = 2048 * kPeelWavesPerBlock;  // 256 CUs x 8 workgroups x 4 waves
+constexpr int kPeelWaves = kStepBlocks * kPeelWavesPerBlock;  // 256 CUs x 8 workgroups x 4 waves
+static_assert(KCORE_AUTO == SCHEDULE_AUTO && KCORE_ROUNDS == SCHEDULE_ROUNDS && KCORE_DEVICE_LOOP == SCHEDULE_DEVICE_LOOP, "LoopOptions' schedules");
 
 template <bool INSTRUMENT>
 class KcoreEnactor : public EnactorBase {
    public:
     explicit KcoreEnactor(bool DEBUG = false) : EnactorBase(VERTEX_FRONTIERS, DEBUG) {}
-    ~KcoreEnactor() override
-    {
-        if (ev[0]) hipEventDestroy(ev[0]);
-        if (ev[1]) hipEventDestroy(ev[1]);
-        if (h_words) hipHostFree(h_words);
-    }
 
     // options (grx_kcore_set_option)
-    int schedule = KCORE_AUTO;
+    LoopOptions loop;
     double compact_below = kCompactBelow;
-    int wave_min_row = kWaveMinRow;
-    long long loop_max_list = kLoopMaxList;
-    long long loop_max_entries = kLoopMaxEntries;
 
-    // of the last Enact
+    // of the last Enact (step: its launches and summed kernel time)
+    StepHost<INSTRUMENT> step{"KcoreEnactor"};
     long long levels = 0;           // non-empty levels
     long long rounds = 0;           // host-visible read-backs
     long long vertices_peeled = 0;
     long long entries_read = 0;
     long long compactions = 0;
-    long long launches = 0;
     long long device_subrounds = 0;  // sub-rounds that ran inside LoopKernel
-    double kernel_ms = 0;            // INSTRUMENT: summed kernel time
     std::vector<int> trace_k;        // the non-empty levels: the level,
     std::vector<long long> trace_vertices;  // the vertices peeled at it,
     std::vector<double> trace_ms;    // and the time from its scan to the next one's (the device's constant-rate counter)
@@ -68,47 +60,20 @@ class KcoreEnactor : public EnactorBase {
         typename Problem::DataSlice *ds = problem->data_slices[0];
         hipStream_t stream = problem->graph_slices[0]->stream;
         const long long n = problem->nodes, zeros = problem->zeros;
-        levels = rounds = entries_read = compactions = launches = device_subrounds = 0;
+        levels = rounds = entries_read = compactions = device_subrounds = 0;
         vertices_peeled = zeros;
-        kernel_ms = 0;
         trace_k.clear();
         trace_vertices.clear();
         trace_ms.clear();
-        if (INSTRUMENT && !ev[0]) {
-            GR_CHECK(hipEventCreate(&ev[0]), "KcoreEnactor hipEventCreate failed");
-            GR_CHECK(hipEventCreate(&ev[1]), "KcoreEnactor hipEventCreate failed");
-        }
-        auto grid = [&](long long blocks, int cap) {
-            if (blocks > cap) blocks = cap;
-            if (blocks < 1) blocks = 1;
-            return static_cast<int>(max_grid_size > 0 && max_grid_size < blocks ? max_grid_size : blocks);
-        };
-        auto begin = [&]() -> hipError_t {
-            return INSTRUMENT ? util::GRError(hipEventRecord(ev[0], stream), "KcoreEnactor hipEventRecord failed", __FILE__, __LINE__) : hipSuccess;
-        };
-        auto end = [&]() -> hipError_t {
-            ++launches;
-            if (INSTRUMENT) {
-                float ms = 0;
-                GR_CHECK(hipEventRecord(ev[1], stream), "KcoreEnactor hipEventRecord failed");
-                GR_CHECK(hipEventSynchronize(ev[1]), "KcoreEnactor hipEventSynchronize failed");
-                GR_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]), "KcoreEnactor hipEventElapsedTime failed");
-                kernel_ms += ms;
-            }
-            return hipSuccess;
-        };
+        if ((retval = step.Begin(sizeof(unsigned) * W_COUNT))) return retval;
+        auto run = [&](auto launch) { return step.Run(stream, launch); };
+        auto grid_for = [&](long long work) { return GridFor(work, max_grid_size); };
 
         const Graph g = problem->DeviceGraph();
         const Trace tr = {ds->d_trace_k, ds->d_trace_tail, ds->d_trace_clock};
-        if (!h_words) GR_CHECK(hipHostMalloc(&h_words, sizeof(unsigned) * W_COUNT), "KcoreEnactor hipHostMalloc failed");
-        unsigned *words = h_words;  // pinned: the read-back of every round lands here without a staging copy
+        unsigned *words = reinterpret_cast<unsigned *>(step.pinned);
         for (int i = 0; i < W_COUNT; ++i) words[i] = 0;
-        auto read_words = [&]() -> hipError_t {
-            GR_CHECK(hipMemcpyAsync(words, ds->d_words, sizeof(unsigned) * W_COUNT, hipMemcpyDeviceToHost, stream), "KcoreEnactor read-back failed");
-            GR_CHECK(hipStreamSynchronize(stream), "KcoreEnactor read-back sync failed");
-            ++rounds;
-            return hipSuccess;
-        };
+        auto read_words = [&]() { return step.Read(words, ds->d_words, sizeof(unsigned) * W_COUNT, stream); };  // (one per round)
 
         // the state of the peel (LoopKernel carries the same in registers)
         long long head = 0, tail = 0, list_len = n;
@@ -129,12 +94,13 @@ class KcoreEnactor : public EnactorBase {
                 if (n - zeros - tail <= 0) break;
                 if (k_limit >= 0 && k >= k_limit) { limited = true; break; }
             }
-            const bool in_loop = !wide_once && (schedule == KCORE_DEVICE_LOOP ||
-                                                (schedule == KCORE_AUTO && (open ? static_cast<long long>(words[W_ENTRIES] - entries_seen) <= loop_max_entries
-                                                                                 : list_len <= loop_max_list)));
+            const bool in_loop =
+                !wide_once && (loop.schedule == KCORE_DEVICE_LOOP ||
+                               (loop.schedule == KCORE_AUTO && (open ? static_cast<long long>(words[W_ENTRIES] - entries_seen) <= loop.loop_max_entries
+                                                                     : list_len <= loop.loop_max_list)));
             wide_once = false;
             if (in_loop) {
-                const bool all = schedule == KCORE_DEVICE_LOOP;
+                const oprtr::Limits lim = loop.LimitsFor();
                 LoopArgs a;
                 a.d_list[0] = ds->d_list[0];
                 a.d_list[1] = ds->d_list[1];
@@ -148,15 +114,15 @@ class KcoreEnactor : public EnactorBase {
                 a.kprev = kprev;
                 a.k_limit = k_limit;
                 a.level_open = open ? 1 : 0;
-                a.wave_min_row = wave_min_row;
+                a.wave_min_row = loop.wave_min_row;
                 a.compact_below = compact_below;
-                a.max_list = all ? LLONG_MAX : loop_max_list;
-                a.max_entries = all ? LLONG_MAX : loop_max_entries;
-                a.max_steps = kLoopMaxSteps;
-                if ((retval = begin())) return retval;
-                hipLaunchKernelGGL(LoopKernel, dim3(1), dim3(kLoopThreads), 0, stream, g, ds->d_core, ds->d_queue, ds->d_words, ds->d_counters, tr, a);
-                GR_CHECK(hipGetLastError(), "LoopKernel launch failed");
-                if ((retval = end())) return retval;
+                a.max_list = lim.max_list;
+                a.max_entries = lim.max_entries;
+                a.max_steps = lim.max_steps;
+                if ((retval = run([&]() {
+                         hipLaunchKernelGGL(LoopKernel, dim3(1), dim3(kLoopThreads), 0, stream, g, ds->d_core, ds->d_queue, ds->d_words, ds->d_counters, tr, a);
+                     })))
+                    return retval;
                 if ((retval = read_words())) return retval;
                 head = static_cast<int>(words[W_HEAD]);
                 tail = words[W_TAIL];
@@ -173,14 +139,12 @@ class KcoreEnactor : public EnactorBase {
                 continue;
             }
             if (open) {  // one sub-round, wide
-                if ((retval = begin())) return retval;
                 const int tile = TileFor(tail - head, kPeelWaves, static_cast<long long>(words[W_ENTRIES] - entries_seen));
-                const long long tiles = (tail - head + tile - 1) / tile;
-                hipLaunchKernelGGL(PeelKernel, dim3(grid((tiles + kPeelWavesPerBlock - 1) / kPeelWavesPerBlock, kPeelWaves / kPeelWavesPerBlock)),
-                                   dim3(kKcoreThreads), 0, stream, g, ds->d_core, ds->d_queue, head, tail, k, wave_min_row, tile, ds->d_words,
-                                   ds->d_counters);
-                GR_CHECK(hipGetLastError(), "PeelKernel launch failed");
-                if ((retval = end())) return retval;
+                if ((retval = run([&]() {
+                         hipLaunchKernelGGL(PeelKernel, StepGrid(tail - head, tile, kPeelWavesPerBlock, max_grid_size), dim3(kKcoreThreads), 0, stream, g,
+                                            ds->d_core, ds->d_queue, head, tail, k, loop.wave_min_row, tile, ds->d_words, ds->d_counters);
+                     })))
+                    return retval;
                 head = tail;
                 entries_seen = words[W_ENTRIES];
                 if ((retval = read_words())) return retval;
@@ -192,41 +156,38 @@ class KcoreEnactor : public EnactorBase {
             if (compact_below > 0 && static_cast<double>(alive) <= compact_below * static_cast<double>(list_len)) {
                 const int to = list_buf == 0 ? 1 : 0;
                 GR_CHECK(hipMemsetAsync(ds->d_words + W_SCRATCH, 0, sizeof(unsigned), stream), "KcoreEnactor memset failed");
-                if ((retval = begin())) return retval;
-                hipLaunchKernelGGL(CompactKernel, dim3(grid((list_len + kKcoreThreads - 1) / kKcoreThreads, 2048)), dim3(kKcoreThreads), 0, stream,
-                                   ds->d_core, list_buf < 0 ? nullptr : ds->d_list[list_buf], list_len, kprev, ds->d_list[to], ds->d_words + W_SCRATCH);
-                GR_CHECK(hipGetLastError(), "CompactKernel launch failed");
-                if ((retval = end())) return retval;
+                if ((retval = run([&]() {
+                         hipLaunchKernelGGL(CompactKernel, grid_for(list_len), dim3(kKcoreThreads), 0, stream, ds->d_core,
+                                            list_buf < 0 ? nullptr : ds->d_list[list_buf], list_len, kprev, ds->d_list[to], ds->d_words + W_SCRATCH);
+                     })))
+                    return retval;
                 list_buf = to;
                 list_len = alive;  // (every live vertex is in the list, and only those are kept: no read-back)
                 ++compactions;
             }
             GR_CHECK(hipMemsetAsync(ds->d_words + W_LOW, 0xFF, sizeof(unsigned), stream), "KcoreEnactor memset failed");
-            if ((retval = begin())) return retval;
-            hipLaunchKernelGGL(ScanKernel, dim3(grid((list_len + kKcoreThreads - 1) / kKcoreThreads, 2048)), dim3(kKcoreThreads), 0, stream, g, ds->d_core,
-                               list_buf < 0 ? nullptr : ds->d_list[list_buf], list_len, kprev, k, ds->d_queue, ds->d_words, ds->d_counters, tr,
-                               static_cast<unsigned>(tail));
-            GR_CHECK(hipGetLastError(), "ScanKernel launch failed");
-            if ((retval = end())) return retval;
+            if ((retval = run([&]() {
+                     hipLaunchKernelGGL(ScanKernel, grid_for(list_len), dim3(kKcoreThreads), 0, stream, g, ds->d_core,
+                                        list_buf < 0 ? nullptr : ds->d_list[list_buf], list_len, kprev, k, ds->d_queue, ds->d_words, ds->d_counters, tr,
+                                        static_cast<unsigned>(tail));
+                 })))
+                return retval;
             if ((retval = read_words())) return retval;
             tail = words[W_TAIL];
             open = true;
         }
 
         if (limited) {  // what is live at level k_limit has a core number of at least k_limit
-            if ((retval = begin())) return retval;
-            hipLaunchKernelGGL(ClampKernel, dim3(grid((n + 255) / 256, 2048)), dim3(256), 0, stream, ds->d_core, n, k_limit);
-            GR_CHECK(hipGetLastError(), "ClampKernel launch failed");
-            if ((retval = end())) return retval;
+            if ((retval = run([&]() { hipLaunchKernelGGL(ClampKernel, grid_for(n), dim3(256), 0, stream, ds->d_core, n, k_limit); }))) return retval;
         }
         vertices_peeled = zeros + tail;
+        rounds = step.readbacks;
 
         // the trace and the counters: one more read, not counted as a round of the peel
-        hipLaunchKernelGGL(EndStampKernel, dim3(1), dim3(1), 0, stream, ds->d_counters + 3);
-        GR_CHECK(hipGetLastError(), "EndStampKernel launch failed");
+        if ((retval = step.Stamp(ds->d_counters + 3, stream))) return retval;
         unsigned long long counters[4] = {0, 0, 0, 0};
-        GR_CHECK(hipMemcpyAsync(words, ds->d_words, sizeof(unsigned) * W_COUNT, hipMemcpyDeviceToHost, stream), "KcoreEnactor read-back failed");
-        GR_CHECK(hipMemcpyAsync(counters, ds->d_counters, sizeof(counters), hipMemcpyDeviceToHost, stream), "KcoreEnactor read-back failed");
+        if ((retval = step.Copy(words, ds->d_words, sizeof(unsigned) * W_COUNT, stream))) return retval;
+        if ((retval = step.Copy(counters, ds->d_counters, sizeof(counters), stream))) return retval;
         GR_CHECK(hipStreamSynchronize(stream), "KcoreEnactor read-back sync failed");
         entries_read = static_cast<long long>(counters[0]);
         compactions += words[W_COMPACTIONS];
@@ -256,10 +217,6 @@ class KcoreEnactor : public EnactorBase {
         levels = static_cast<long long>(trace_k.size());
         return retval;
     }
-
-   private:
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    unsigned *h_words = nullptr;
 };
 
 }  // namespace kcore

@@ -28,22 +28,23 @@
 
 #include <hip/hip_runtime.h>
 
+#include <gunrock/oprtr/step.hpp>
 #include <gunrock/util/device_intrinsics.hpp>
 
 namespace gunrock {
 namespace app {
 namespace kcore {
 
+using oprtr::kLoopThreads;
+using oprtr::Ld;
+using oprtr::St;
+using oprtr::TileFor;
+
 enum { KCORE_AUTO = 0, KCORE_ROUNDS = 1, KCORE_DEVICE_LOOP = 2 };
 
 constexpr int kKcoreThreads = 256;
-constexpr int kLoopThreads = 1024;
 constexpr int kWaveUnroll = 4;             // chunks of 64 row entries a wave keeps in flight per step of a long row
-constexpr int kWaveMinRow = 16;            // default "wave_min_row" 
 constexpr double kCompactBelow = 0.75;     // default "compact_below"
-constexpr long long kLoopMaxList = 32768;  // AUTO: the device loop scans a live list up to this length ...
-constexpr long long kLoopMaxEntries = 8192;   // ... and walks sub-rounds whose rows hold up to this many entries
-constexpr int kLoopMaxSteps = 4096;        // sub-rounds and level scans per LoopKernel launch
 
 // the words the kernels and the host share
 enum {
@@ -78,18 +79,6 @@ struct Trace {
     int *tail;                   // the queue tail when it began,
     unsigned long long *clock;   // the constant-rate counter then
 };
-
-template <bool FRESH>
-__device__ __forceinline__ int Ld(const int *p)
-{
-    return FRESH ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *p;
-}
-template <bool FRESH>
-__device__ __forceinline__ void St(int *p, int v)
-{
-    if (FRESH) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else *p = v;
-}
 
 // what a lane carries through a pass and leaves in the words at its end
 struct Tally {
@@ -128,12 +117,9 @@ __device__ __forceinline__ void Append(const Graph &g, bool hit, int u, int *d_q
 {
     const unsigned long long mask = __ballot(hit);
     if (!mask) return;
-    const int lane = static_cast<int>(util::LaneId());
-    unsigned at = 0;
-    if (lane == 0) at = atomicAdd(d_words + W_TAIL, static_cast<unsigned>(__popcll(mask)));
-    at = __shfl(at, 0, util::kWaveSize);
+    const unsigned pos = oprtr::WaveTicket(d_words + W_TAIL, mask);
     if (hit) {
-        St<FRESH>(d_queue + at + __popcll(mask & ((1ull << lane) - 1ull)), u);
+        St<FRESH>(d_queue + pos, u);
         t.entries += static_cast<unsigned>(g.ro[u + 1] - g.ro[u]);
     }
 }
@@ -210,18 +196,6 @@ __device__ __forceinline__ void PeelTile(const Graph &g, int *d_core, int *d_que
     }
 }
 
-// Queue entries a wave takes at a time, a power of two up to 64.  Long rows want few (the rows of a short sub-round are spread over
-// the waves and not walked one after the other by one of them); short rows want 64 (a wave's appends are one atomic on the tail
-// per step whatever the tile: waves of 2 lanes on a grid's front sent 30 000 atomics per sub-round to that one word, which takes
-// them at under 100 per microsecond).  So: about kTileEntries row entries per wave, and never more waves than there are.
-constexpr long long kTileEntries = 512;
-__host__ __device__ __forceinline__ int TileFor(long long count, long long waves, long long entries)
-{
-    int tile = 1;
-    while (tile < util::kWaveSize && (count > tile * waves || entries * tile < kTileEntries * count)) tile <<= 1;
-    return tile;
-}
-
 // the sub-round [head, tail) of level k by the waves wave0, wave0 + nwaves, ..., `tile` entries each at a time
 template <bool FRESH>
 __device__ __forceinline__ void PeelRange(const Graph &g, int *d_core, int *d_queue, unsigned *d_words, long long head, long long tail, int k,
@@ -271,10 +245,8 @@ __device__ __forceinline__ void CompactRange(const int *d_core, const int *d_lis
         }
         const unsigned long long mask = __ballot(keep);
         if (!mask) continue;
-        unsigned at = 0;
-        if (lane == 0) at = atomicAdd(d_count, static_cast<unsigned>(__popcll(mask)));
-        at = __shfl(at, 0, util::kWaveSize);
-        if (keep) St<FRESH>(d_out + at + __popcll(mask & ((1ull << lane) - 1ull)), v);
+        const unsigned pos = oprtr::WaveTicket(d_count, mask);
+        if (keep) St<FRESH>(d_out + pos, v);
     }
 }
 
@@ -428,8 +400,6 @@ static __global__ void ClampKernel(int *d_core, long long nodes, int k_limit)
     for (long long v = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; v < nodes; v += stride)
         if (d_core[v] > k_limit) d_core[v] = k_limit;
 }
-
-static __global__ void EndStampKernel(unsigned long long *d_clock) { *d_clock = wall_clock64(); }
 
 // both directions of every kept edge, each at its row's cursor (the order inside a row is the arrival order: nothing reads it)
 static __global__ void NeighbourScatterKernel(const unsigned long long *d_keys, const unsigned *d_keep, long long count, int col_bits,

@@ -17,6 +17,7 @@
 #include <gunrock/app/enactor_base.hpp>
 #include <gunrock/app/lp/lp_functor.hpp>
 #include <gunrock/app/lp/lp_problem.hpp>
+#include <gunrock/app/step_host.hpp>
 
 namespace gunrock {
 namespace app {
@@ -30,12 +31,6 @@ template <bool INSTRUMENT>
 class LpEnactor : public EnactorBase {
    public:
     explicit LpEnactor(bool DEBUG = false) : EnactorBase(VERTEX_FRONTIERS, DEBUG) {}
-    ~LpEnactor() override
-    {
-        if (ev[0]) hipEventDestroy(ev[0]);
-        if (ev[1]) hipEventDestroy(ev[1]);
-        if (h_words) hipHostFree(h_words);
-    }
 
     // options (grx_lp_set_option)
     int mode = LP_CLASSES;
@@ -45,10 +40,10 @@ class LpEnactor : public EnactorBase {
     int table_slots = kTableSlots;
     long long max_rounds = 0;  // 0: 2 n + 64 (a policy value)
 
-    // of the last Enact
-    long long rounds = 0, visits = 0, entries_read = 0, regime_rows[3] = {0, 0, 0}, fallback_rows = 0, launches = 0, readbacks = 0;
+    // of the last Enact (step: its launches, read-backs and summed kernel time)
+    StepHost<INSTRUMENT> step{"LpEnactor"};
+    long long rounds = 0, visits = 0, entries_read = 0, regime_rows[3] = {0, 0, 0}, fallback_rows = 0;
     int state = LP_CONVERGED;
-    double kernel_ms = 0;  // INSTRUMENT: summed kernel time
     std::vector<long long> trace_list, trace_changed;  // per round: the vertices visited and the labels changed
 
     // hipSuccess or a hipError_t (hipErrorNotReady: CLASSES without classes)
@@ -62,32 +57,13 @@ class LpEnactor : public EnactorBase {
         typename Problem::DataSlice *ds = problem->data_slices[0];
         hipStream_t stream = problem->graph_slices[0]->stream;
         const long long n = problem->nodes;
-        rounds = visits = entries_read = fallback_rows = launches = readbacks = 0;
+        rounds = visits = entries_read = fallback_rows = 0;
         regime_rows[0] = regime_rows[1] = regime_rows[2] = 0;
         state = LP_CONVERGED;
-        kernel_ms = 0;
         trace_list.clear();
         trace_changed.clear();
-        if (INSTRUMENT && !ev[0]) {
-            GR_CHECK(hipEventCreate(&ev[0]), "LpEnactor hipEventCreate failed");
-            GR_CHECK(hipEventCreate(&ev[1]), "LpEnactor hipEventCreate failed");
-        }
-        // run(launch): one kernel launch, counted, and timed when instrumented
-        auto run = [&](auto launch) -> hipError_t {
-            hipError_t retval = hipSuccess;
-            if (INSTRUMENT) GR_CHECK(hipEventRecord(ev[0], stream), "LpEnactor hipEventRecord failed");
-            launch();
-            GR_CHECK(hipGetLastError(), "LpEnactor kernel launch failed");
-            ++launches;
-            if (INSTRUMENT) {
-                float ms = 0;
-                GR_CHECK(hipEventRecord(ev[1], stream), "LpEnactor hipEventRecord failed");
-                GR_CHECK(hipEventSynchronize(ev[1]), "LpEnactor hipEventSynchronize failed");
-                GR_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]), "LpEnactor hipEventElapsedTime failed");
-                kernel_ms += ms;
-            }
-            return retval;
-        };
+        if ((retval = step.Begin(sizeof(unsigned long long) * W_COUNT))) return retval;
+        auto run = [&](auto launch) { return step.Run(stream, launch); };
         auto grid = [&](long long count, int per_block, int most) {
             long long blocks = (count + per_block - 1) / per_block;
             if (blocks > most) blocks = most;
@@ -119,16 +95,8 @@ class LpEnactor : public EnactorBase {
         };
 
         const long long bound = max_rounds > 0 ? max_rounds : 2 * n + 64;
-        // pinned: the read-backs land here without a staging copy
-        if (!h_words) GR_CHECK(hipHostMalloc(&h_words, sizeof(unsigned long long) * W_COUNT), "LpEnactor hipHostMalloc failed");
-        auto read_words = [&]() -> hipError_t {
-            hipError_t retval = hipSuccess;
-            GR_CHECK(hipMemcpyAsync(h_words, ds->d_words, sizeof(unsigned long long) * W_COUNT, hipMemcpyDeviceToHost, stream),
-                     "LpEnactor read-back failed");
-            GR_CHECK(hipStreamSynchronize(stream), "LpEnactor read-back sync failed");
-            ++readbacks;
-            return retval;
-        };
+        unsigned long long *h_words = reinterpret_cast<unsigned long long *>(step.pinned);
+        auto read_words = [&]() { return step.Read(h_words, ds->d_words, sizeof(unsigned long long) * W_COUNT, stream); };
 
         long long count = n, changed_before = 0, visits_before = 0;
         int cur = 0;
@@ -180,10 +148,6 @@ class LpEnactor : public EnactorBase {
         problem->enacted = true;
         return retval;
     }
-
-   private:
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    unsigned long long *h_words = nullptr;
 };
 
 }  // namespace lp

@@ -30,10 +30,7 @@
 
 #include <climits>
 
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunused-function"  // (only MIS's hash is used here)
-#include <gunrock/app/mis/mis_functor.hpp>
-#pragma clang diagnostic pop
+#include <gunrock/oprtr/step.hpp>
 #include <gunrock/util/device_intrinsics.hpp>
 
 namespace gunrock {
@@ -52,7 +49,7 @@ constexpr int kTableSlots = 1024;   // default and largest "table_slots": 12 KiB
 constexpr int kMinTableSlots = 64;
 constexpr int kMaxLogSlices = 26;   // 2^26 slices of the 32-bit hash space hold 64 labels each
 
-using mis::Fmix32;
+using util::Fmix32;
 
 // the 64-bit words the kernels and the host share; the first kRoundWords are cleared in front of every round
 enum {
@@ -145,12 +142,8 @@ __device__ __forceinline__ void Append(const Ctx &c, int word, int *list, bool h
 {
     const unsigned long long mask = __ballot(hit);
     if (!mask) return;
-    const int lane = static_cast<int>(util::LaneId());
-    unsigned long long at = 0;
-    if (lane == 0) at = atomicAdd(c.words + word, static_cast<unsigned long long>(__popcll(mask)));
-    at = __shfl(at, 0, util::kWaveSize);
+    const unsigned long long pos = oprtr::WaveTicket(c.words + word, mask);
     if (hit) {
-        const unsigned long long pos = at + __popcll(mask & ((1ull << lane) - 1ull));
         if (pos < static_cast<unsigned long long>(c.nodes)) list[pos] = v;
     }
 }

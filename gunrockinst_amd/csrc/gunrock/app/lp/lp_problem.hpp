@@ -140,7 +140,7 @@ struct LpProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
                 // the weights as matching builds them: every input entry raises its pair's weight to its own
                 const size_t ms = static_cast<size_t>(M);
                 GR_CHECK(hipMalloc(&ds->d_pw, sizeof(int) * ms), "LpProblem hipMalloc d_pw failed");
-                hipLaunchKernelGGL(matching::FillKernel, dim3(Grid(M)), dim3(256), 0, stream, ds->d_pw, M, weighted ? INT_MIN : 1);
+                hipLaunchKernelGGL(oprtr::FillKernel<int>, dim3(Grid(M)), dim3(256), 0, stream, ds->d_pw, M, weighted ? INT_MIN : 1);
                 GR_CHECK(hipGetLastError(), "FillKernel launch failed");
                 if (weighted) {
                     GR_CHECK(hipMalloc(&ds->d_ew, sizeof(int) * 2 * ms), "LpProblem hipMalloc d_ew failed");

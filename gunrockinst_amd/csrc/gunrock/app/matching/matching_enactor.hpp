@@ -21,39 +21,32 @@
 #include <gunrock/app/enactor_base.hpp>
 #include <gunrock/app/matching/matching_functor.hpp>
 #include <gunrock/app/matching/matching_problem.hpp>
+#include <gunrock/app/step_host.hpp>
 
 namespace gunrock {
 namespace app {
 namespace matching {
 
 constexpr int kStepWavesPerBlock = kMatchingThreads / util::kWaveSize;
-constexpr int kStepBlocks = 2048;  // 256 CUs x 8 workgroups
 constexpr int kStepWaves = kStepBlocks * kStepWavesPerBlock;
+static_assert(MATCHING_AUTO == SCHEDULE_AUTO && MATCHING_ROUNDS == SCHEDULE_ROUNDS && MATCHING_DEVICE_LOOP == SCHEDULE_DEVICE_LOOP,
+              "LoopOptions' schedules");
 constexpr long long kMaxMaxRounds = 1ll << 31;
 constexpr int kGaveUp = -4;  // GRX_MATCHING_GAVE_UP
 
 template <bool INSTRUMENT>
 class MatchingEnactor : public EnactorBase {
    public:
-    explicit MatchingEnactor(bool DEBUG = false) : EnactorBase(VERTEX_FRONTIERS, DEBUG) {}
-    ~MatchingEnactor() override
-    {
-        if (ev[0]) hipEventDestroy(ev[0]);
-        if (ev[1]) hipEventDestroy(ev[1]);
-        if (h_pinned) hipHostFree(h_pinned);
-    }
+    explicit MatchingEnactor(bool DEBUG = false) : EnactorBase(VERTEX_FRONTIERS, DEBUG) { loop.loop_max_entries = kLoopMaxEntries; }
 
     // options (grx_matching_set_option)
-    int schedule = MATCHING_AUTO;
-    int wave_min_row = kWaveMinRow;
+    LoopOptions loop;          // (loop_max_entries starts at matching's own default)
     long long max_rounds = 0;  // 0: n / 2 + 1
-    long long loop_max_list = kLoopMaxList;
-    long long loop_max_entries = kLoopMaxEntries;
 
-    // of the last Enact
-    long long rounds = 0, sweeps = 0, loop_rounds = 0, entries_read = 0, polls = 0, launches = 0, readbacks = 0;
+    // of the last Enact (step: its launches, read-backs and summed kernel time)
+    StepHost<INSTRUMENT> step{"MatchingEnactor"};
+    long long rounds = 0, sweeps = 0, loop_rounds = 0, entries_read = 0, polls = 0;
     bool gave_up = false;
-    double kernel_ms = 0;  // INSTRUMENT: summed kernel time
     // one row per host step: a wide round or a loop launch, the rounds it ran, the list it started from and the pairs it matched
     std::vector<int> trace_kind;
     std::vector<long long> trace_rounds, trace_list, trace_matched;
@@ -68,58 +61,25 @@ class MatchingEnactor : public EnactorBase {
         typename Problem::DataSlice *ds = problem->data_slices[0];
         hipStream_t stream = problem->graph_slices[0]->stream;
         const long long n = problem->nodes, M = problem->pairs;
-        rounds = sweeps = loop_rounds = entries_read = polls = launches = readbacks = 0;
+        rounds = sweeps = loop_rounds = entries_read = polls = 0;
         gave_up = false;
-        kernel_ms = 0;
         trace_kind.clear();
         trace_rounds.clear();
         trace_list.clear();
         trace_matched.clear();
-        if (INSTRUMENT && !ev[0]) {
-            GR_CHECK(hipEventCreate(&ev[0]), "MatchingEnactor hipEventCreate failed");
-            GR_CHECK(hipEventCreate(&ev[1]), "MatchingEnactor hipEventCreate failed");
-        }
-        // run(launch): one kernel launch, counted, and timed when instrumented
-        auto run = [&](auto launch) -> hipError_t {
-            hipError_t retval = hipSuccess;
-            if (INSTRUMENT) GR_CHECK(hipEventRecord(ev[0], stream), "MatchingEnactor hipEventRecord failed");
-            launch();
-            GR_CHECK(hipGetLastError(), "MatchingEnactor kernel launch failed");
-            ++launches;
-            if (INSTRUMENT) {
-                float ms = 0;
-                GR_CHECK(hipEventRecord(ev[1], stream), "MatchingEnactor hipEventRecord failed");
-                GR_CHECK(hipEventSynchronize(ev[1]), "MatchingEnactor hipEventSynchronize failed");
-                GR_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]), "MatchingEnactor hipEventElapsedTime failed");
-                kernel_ms += ms;
-            }
-            return retval;
-        };
-        auto step_grid = [&](long long count, int tile) {
-            long long blocks = ((count + tile - 1) / tile + kStepWavesPerBlock - 1) / kStepWavesPerBlock;
-            if (blocks > kStepBlocks) blocks = kStepBlocks;
-            if (max_grid_size > 0 && blocks > max_grid_size) blocks = max_grid_size;
-            if (blocks < 1) blocks = 1;
-            return dim3(static_cast<unsigned>(blocks));
-        };
+        if ((retval = step.Begin(256))) return retval;
+        auto run = [&](auto launch) { return step.Run(stream, launch); };
+        auto step_grid = [&](long long count, int tile) { return StepGrid(count, tile, kStepWavesPerBlock, max_grid_size); };
 
-        const Ctx c = problem->DeviceCtx(wave_min_row);
-        const bool all = schedule == MATCHING_DEVICE_LOOP;
-        const Limits lim = {all ? LLONG_MAX : loop_max_list, all ? LLONG_MAX : loop_max_entries, kLoopMaxSteps};
-        auto in_loop = [&](long long count, long long entries) { return all || (schedule == MATCHING_AUTO && Narrow(count, entries, lim)); };
+        const Ctx c = problem->DeviceCtx(loop.wave_min_row);
+        const Limits lim = loop.LimitsFor();
+        auto in_loop = [&](long long count, long long entries) { return loop.InLoop(count, entries); };
         const long long bound = max_rounds > 0 ? max_rounds : n / 2 + 1;
-        // pinned: the read-backs land here without a staging copy
-        if (!h_pinned) GR_CHECK(hipHostMalloc(&h_pinned, 256), "MatchingEnactor hipHostMalloc failed");
+        unsigned char *h_pinned = step.pinned;  // the read-backs land here without a staging copy
         unsigned *words = reinterpret_cast<unsigned *>(h_pinned);  // W_COUNT
         Active *h_active = reinterpret_cast<Active *>(h_pinned + 64);
         unsigned long long *h_counters = reinterpret_cast<unsigned long long *>(h_pinned + 128);  // C_COUNT
-        auto read_words = [&]() -> hipError_t {
-            hipError_t retval = hipSuccess;
-            GR_CHECK(hipMemcpyAsync(words, ds->d_words, sizeof(unsigned) * W_COUNT, hipMemcpyDeviceToHost, stream), "MatchingEnactor read-back failed");
-            GR_CHECK(hipStreamSynchronize(stream), "MatchingEnactor read-back sync failed");
-            ++readbacks;
-            return retval;
-        };
+        auto read_words = [&]() { return step.Read(words, ds->d_words, sizeof(unsigned) * W_COUNT, stream); };
         // W_NEXT and W_NEXT_ENTRIES at 0 in front of everything that appends to a list
         auto clear_next = [&]() -> hipError_t {
             return util::GRError(hipMemsetAsync(ds->d_words + W_NEXT, 0, sizeof(unsigned) * 2, stream), "MatchingEnactor memset failed", __FILE__, __LINE__);
@@ -149,9 +109,7 @@ class MatchingEnactor : public EnactorBase {
                          hipLaunchKernelGGL(LoopKernel, dim3(1), dim3(kLoopThreads), 0, stream, c, ds->d_list[0], ds->d_list[1], a, now, ds->d_active);
                      })))
                     return retval;
-                GR_CHECK(hipMemcpyAsync(h_active, ds->d_active, sizeof(Active), hipMemcpyDeviceToHost, stream), "MatchingEnactor read-back failed");
-                GR_CHECK(hipStreamSynchronize(stream), "MatchingEnactor read-back sync failed");
-                ++readbacks;
+                if ((retval = step.Read(h_active, ds->d_active, sizeof(Active), stream))) return retval;
                 a = *h_active;
                 sweeps += a.steps;
                 loop_rounds += a.steps;
@@ -178,10 +136,7 @@ class MatchingEnactor : public EnactorBase {
             trace(STEP_WIDE, 1, list, static_cast<long long>(a.matched - before));
         }
 
-        GR_CHECK(hipMemcpyAsync(h_counters, ds->d_counters, sizeof(unsigned long long) * C_COUNT, hipMemcpyDeviceToHost, stream),
-                 "MatchingEnactor read-back failed");
-        GR_CHECK(hipStreamSynchronize(stream), "MatchingEnactor read-back sync failed");
-        ++readbacks;
+        if ((retval = step.Read(h_counters, ds->d_counters, sizeof(unsigned long long) * C_COUNT, stream))) return retval;
         entries_read = static_cast<long long>(h_counters[C_READS]);
         polls = static_cast<long long>(h_counters[C_POLLS]);
         Summary &out = problem->summary;
@@ -194,10 +149,6 @@ class MatchingEnactor : public EnactorBase {
         problem->enacted = true;
         return retval;
     }
-
-   private:
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    unsigned char *h_pinned = nullptr;
 };
 
 }  // namespace matching

@@ -28,11 +28,7 @@
 
 #include <climits>
 
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunused-function"  // (only MIS's hash and SCC's accessors and tile rule are used here)
-#include <gunrock/app/mis/mis_functor.hpp>
-#include <gunrock/app/scc/scc_functor.hpp>
-#pragma clang diagnostic pop
+#include <gunrock/oprtr/step.hpp>
 #include <gunrock/util/device_intrinsics.hpp>
 
 namespace gunrock {
@@ -43,18 +39,20 @@ enum { MATCHING_AUTO = 0, MATCHING_ROUNDS = 1, MATCHING_DEVICE_LOOP = 2 };
 enum { STEP_WIDE = 0, STEP_LOOP = 1 };  // the kinds of the round trace
 
 constexpr int kMatchingThreads = 256;
-constexpr int kLoopThreads = 1024;
-constexpr int kWaveMinRow = 16;              // default "wave_min_row" (taken over from max-flow)
-constexpr long long kLoopMaxList = 32768;     // AUTO: the device loop takes a round of up to this many vertices (taken over) ...
-constexpr long long kLoopMaxEntries = 65536;  // ... whose rows hold up to this many entries: an upper bound of the round's reads that
-                                              // is loose here, most of a list polls one entry (by reasoning, not tuned)
-constexpr int kLoopMaxSteps = 4096;          // rounds per loop launch
+constexpr long long kLoopMaxEntries = 65536;  // AUTO: the device loop takes a round whose rows hold up to this many entries, not the
+                                              // shared 8192: an upper bound of the round's reads that is loose here, most of a list
+                                              // polls one entry (by reasoning, not tuned)
 constexpr int kWaveUnroll = 4;               // chunks of 64 row entries a wave keeps in flight on a long row (as MIS's sweep does)
 
-using mis::Fmix32;
-using scc::Ld;
-using scc::St;
-using scc::TileFor;
+using oprtr::kLoopMaxSteps;
+using oprtr::kLoopThreads;
+using oprtr::kWaveMinRow;
+using oprtr::Ld;
+using oprtr::Limits;
+using oprtr::Narrow;
+using oprtr::St;
+using oprtr::TileFor;
+using util::Fmix32;
 
 // the words the kernels and the host share
 enum {
@@ -88,16 +86,6 @@ struct Active {
     int steps;                // rounds run by the loop launch ...
     int match_steps;          // ... and those of them that matched a pair
 };
-
-struct Limits {
-    long long max_list, max_entries;
-    int max_steps;
-};
-
-__host__ __device__ __forceinline__ bool Narrow(long long count, long long entries, const Limits &lim)
-{
-    return count <= lim.max_list && entries <= lim.max_entries;
-}
 
 __host__ __device__ __forceinline__ unsigned long long PairKey(int weight, int pair, unsigned seed_mul)
 {
@@ -137,12 +125,8 @@ __device__ __forceinline__ void Append(const Ctx &c, int *list, bool hit, int v,
 {
     const unsigned long long mask = __ballot(hit);
     if (!mask) return;
-    const int lane = static_cast<int>(util::LaneId());
-    unsigned at = 0;
-    if (lane == 0) at = atomicAdd(c.words + W_NEXT, static_cast<unsigned>(__popcll(mask)));
-    at = __shfl(at, 0, util::kWaveSize);
+    const unsigned pos = oprtr::WaveTicket(c.words + W_NEXT, mask);
     if (hit) {
-        const unsigned pos = at + __popcll(mask & ((1ull << lane) - 1ull));
         if (pos < static_cast<unsigned>(c.nodes)) St<FRESH>(list + pos, v);
         t.entries += static_cast<unsigned>(c.ro[v + 1] - c.ro[v]);
     }
@@ -371,12 +355,6 @@ __device__ __forceinline__ int RowFind(const int *ro, const int *ci, int u, int 
         if (ci[mid] < w) lo = mid + 1; else hi = mid;
     }
     return lo;
-}
-
-static __global__ void FillKernel(int *d_out, long long count, int value)
-{
-    const long long stride = static_cast<long long>(gridDim.x) * blockDim.x;
-    for (long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; i < count; i += stride) d_out[i] = value;
 }
 
 // every entry of the input raises the weight of its pair to its own (the pair's weight is the largest of its entries, either way).

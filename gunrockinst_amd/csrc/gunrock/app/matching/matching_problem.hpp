@@ -139,7 +139,7 @@ struct MatchingProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
                 // raises the pair's weight to its own, as max-flow's build adds its capacities up
                 const size_t ms = static_cast<size_t>(M);
                 GR_CHECK(hipMalloc(&ds->d_pw, sizeof(int) * ms), "MatchingProblem hipMalloc d_pw failed");
-                hipLaunchKernelGGL(FillKernel, dim3(Grid(M)), dim3(256), 0, stream, ds->d_pw, M, weighted ? INT_MIN : 1);
+                hipLaunchKernelGGL(oprtr::FillKernel<int>, dim3(Grid(M)), dim3(256), 0, stream, ds->d_pw, M, weighted ? INT_MIN : 1);
                 GR_CHECK(hipGetLastError(), "FillKernel launch failed");
                 if (weighted) {
                     GR_CHECK(hipMalloc(&ds->d_ew, sizeof(int) * 2 * ms), "MatchingProblem hipMalloc d_ew failed");

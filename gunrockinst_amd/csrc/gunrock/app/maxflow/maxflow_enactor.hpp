@@ -27,14 +27,16 @@
 #include <gunrock/app/enactor_base.hpp>
 #include <gunrock/app/maxflow/maxflow_functor.hpp>
 #include <gunrock/app/maxflow/maxflow_problem.hpp>
+#include <gunrock/app/step_host.hpp>
 
 namespace gunrock {
 namespace app {
 namespace maxflow {
 
 constexpr int kStepWavesPerBlock = kMaxflowThreads / util::kWaveSize;
-constexpr int kStepBlocks = 2048;  // 256 CUs x 8 workgroups
 constexpr int kStepWaves = kStepBlocks * kStepWavesPerBlock;
+static_assert(MAXFLOW_AUTO == SCHEDULE_AUTO && MAXFLOW_ROUNDS == SCHEDULE_ROUNDS && MAXFLOW_DEVICE_LOOP == SCHEDULE_DEVICE_LOOP,
+              "LoopOptions' schedules");
 constexpr long long kDefaultMaxRounds = 4000000;  // the largest count measured and the margin over it
 constexpr long long kMaxMaxRounds = 1ll << 30;    // (a round's stamp is an int)
 constexpr int kMaxRestarts = 64;                  // trips back from a failed certificate before Enact gives up
@@ -44,26 +46,17 @@ template <bool INSTRUMENT>
 class MaxflowEnactor : public EnactorBase {
    public:
     explicit MaxflowEnactor(bool DEBUG = false) : EnactorBase(VERTEX_FRONTIERS, DEBUG) {}
-    ~MaxflowEnactor() override
-    {
-        if (ev[0]) hipEventDestroy(ev[0]);
-        if (ev[1]) hipEventDestroy(ev[1]);
-        if (h_pinned) hipHostFree(h_pinned);
-    }
 
     // options (grx_maxflow_set_option)
-    int schedule = MAXFLOW_AUTO;
-    int wave_min_row = kWaveMinRow;
+    LoopOptions loop;
     int discharge_steps = kDischargeSteps;
     double relabel_interval = 0.1;  // relabels between two global relabels, as a multiple of n (the sweep)
     long long max_rounds = kDefaultMaxRounds;
-    long long loop_max_list = kLoopMaxList;
-    long long loop_max_entries = kLoopMaxEntries;
 
-    // of the last Enact
-    long long rounds = 0, global_relabels = 0, pushes = 0, relabels = 0, entries_read = 0, launches = 0, readbacks = 0, restarts = 0;
+    // of the last Enact (step: its launches, read-backs and summed kernel time)
+    StepHost<INSTRUMENT> step{"MaxflowEnactor"};
+    long long rounds = 0, global_relabels = 0, pushes = 0, relabels = 0, entries_read = 0, restarts = 0;
     bool gave_up = false;
-    double kernel_ms = 0;                 // INSTRUMENT: summed kernel time
     std::vector<long long> trace_rounds;  // one row per phase: the rounds it ran (the cut: its search levels),
     std::vector<double> trace_ms;         // and its time, summed over the restarts (the device's constant-rate counter)
 
@@ -78,72 +71,32 @@ class MaxflowEnactor : public EnactorBase {
         typename Problem::DataSlice *ds = problem->data_slices[0];
         hipStream_t stream = problem->graph_slices[0]->stream;
         const long long n = problem->nodes, M = problem->pairs;
-        rounds = global_relabels = pushes = relabels = entries_read = launches = readbacks = restarts = 0;
+        rounds = global_relabels = pushes = relabels = entries_read = restarts = 0;
         gave_up = false;
-        kernel_ms = 0;
         trace_rounds.assign(PHASE_COUNT, 0);
         trace_ms.assign(PHASE_COUNT, 0.0);
-        if (INSTRUMENT && !ev[0]) {
-            GR_CHECK(hipEventCreate(&ev[0]), "MaxflowEnactor hipEventCreate failed");
-            GR_CHECK(hipEventCreate(&ev[1]), "MaxflowEnactor hipEventCreate failed");
-        }
-        // run(launch): one kernel launch, counted, and timed when instrumented
-        auto run = [&](auto launch) -> hipError_t {
-            hipError_t retval = hipSuccess;
-            if (INSTRUMENT) GR_CHECK(hipEventRecord(ev[0], stream), "MaxflowEnactor hipEventRecord failed");
-            launch();
-            GR_CHECK(hipGetLastError(), "MaxflowEnactor kernel launch failed");
-            ++launches;
-            if (INSTRUMENT) {
-                float ms = 0;
-                GR_CHECK(hipEventRecord(ev[1], stream), "MaxflowEnactor hipEventRecord failed");
-                GR_CHECK(hipEventSynchronize(ev[1]), "MaxflowEnactor hipEventSynchronize failed");
-                GR_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]), "MaxflowEnactor hipEventElapsedTime failed");
-                kernel_ms += ms;
-            }
-            return retval;
-        };
-        auto stamp_clock = [&](int slot) -> hipError_t {
-            hipLaunchKernelGGL(StampKernel, dim3(1), dim3(1), 0, stream, ds->d_clock + slot);
-            return util::GRError(hipGetLastError(), "StampKernel launch failed", __FILE__, __LINE__);
-        };
-        auto grid_for = [&](long long work) {
-            int g = Problem::Grid(work);
-            if (max_grid_size > 0 && g > max_grid_size) g = max_grid_size;
-            return dim3(static_cast<unsigned>(g));
-        };
-        auto step_grid = [&](long long count, int tile) {
-            long long blocks = ((count + tile - 1) / tile + kStepWavesPerBlock - 1) / kStepWavesPerBlock;
-            if (blocks > kStepBlocks) blocks = kStepBlocks;
-            if (max_grid_size > 0 && blocks > max_grid_size) blocks = max_grid_size;
-            if (blocks < 1) blocks = 1;
-            return dim3(static_cast<unsigned>(blocks));
-        };
+        if ((retval = step.Begin(512))) return retval;
+        auto run = [&](auto launch) { return step.Run(stream, launch); };
+        auto stamp_clock = [&](int slot) { return step.Stamp(ds->d_clock + slot, stream); };
+        auto grid_for = [&](long long work) { return GridFor(work, max_grid_size); };
+        auto step_grid = [&](long long count, int tile) { return StepGrid(count, tile, kStepWavesPerBlock, max_grid_size); };
 
-        const Ctx c = problem->DeviceCtx(wave_min_row, discharge_steps);
-        const bool all = schedule == MAXFLOW_DEVICE_LOOP;
-        const Limits lim = {all ? LLONG_MAX : loop_max_list, all ? LLONG_MAX : loop_max_entries, kLoopMaxSteps};
-        auto in_loop = [&](long long count, long long entries) { return all || (schedule == MAXFLOW_AUTO && Narrow(count, entries, lim)); };
+        const Ctx c = problem->DeviceCtx(loop.wave_min_row, discharge_steps);
+        const Limits lim = loop.LimitsFor();
+        auto in_loop = [&](long long count, long long entries) { return loop.InLoop(count, entries); };
         unsigned relabel_limit = kNever;
         {
             const double want = relabel_interval * static_cast<double>(n);
             if (want < 4.0e9) relabel_limit = want < 1.0 ? 1u : static_cast<unsigned>(want);
         }
-        // pinned: the read-backs land here without a staging copy
-        if (!h_pinned) GR_CHECK(hipHostMalloc(&h_pinned, 512), "MaxflowEnactor hipHostMalloc failed");
+        unsigned char *h_pinned = step.pinned;  // the read-backs land here without a staging copy
         unsigned *words = reinterpret_cast<unsigned *>(h_pinned);                            // W_COUNT
         Front *h_front = reinterpret_cast<Front *>(h_pinned + 64);
         Active *h_active = reinterpret_cast<Active *>(h_pinned + 128);
         unsigned long long *h_counters = reinterpret_cast<unsigned long long *>(h_pinned + 192);  // C_COUNT
         unsigned long long *h_clock = reinterpret_cast<unsigned long long *>(h_pinned + 320);     // 2 stamps
         long long *h_value = reinterpret_cast<long long *>(h_pinned + 352);
-        auto read_words = [&]() -> hipError_t {
-            hipError_t retval = hipSuccess;
-            GR_CHECK(hipMemcpyAsync(words, ds->d_words, sizeof(unsigned) * W_COUNT, hipMemcpyDeviceToHost, stream), "MaxflowEnactor read-back failed");
-            GR_CHECK(hipStreamSynchronize(stream), "MaxflowEnactor read-back sync failed");
-            ++readbacks;
-            return retval;
-        };
+        auto read_words = [&]() { return step.Read(words, ds->d_words, sizeof(unsigned) * W_COUNT, stream); };
         int khz = 0, device = 0;
         GR_CHECK(hipGetDevice(&device), "MaxflowEnactor hipGetDevice failed");
         GR_CHECK(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device), "MaxflowEnactor clock rate failed");
@@ -160,7 +113,7 @@ class MaxflowEnactor : public EnactorBase {
         // one search from `root` at level `base`; *levels receives the levels it ran
         auto search = [&](const Search &s, int root, int base, long long *levels) -> hipError_t {
             hipError_t retval = hipSuccess;
-            if ((retval = run([&]() { hipLaunchKernelGGL(FillKernel, grid_for(n), dim3(256), 0, stream, s.out, n, s.unseen); }))) return retval;
+            if ((retval = run([&]() { hipLaunchKernelGGL(oprtr::FillKernel<int>, grid_for(n), dim3(256), 0, stream, s.out, n, s.unseen); }))) return retval;
             if ((retval = run([&]() { hipLaunchKernelGGL(SeedKernel, dim3(1), dim3(1), 0, stream, c, s, root, base); }))) return retval;
             if ((retval = read_words())) return retval;
             Front f = {base, 0u, words[W_TAIL], words[W_ENTRIES], words[W_ENTRIES]};
@@ -169,9 +122,7 @@ class MaxflowEnactor : public EnactorBase {
                 if (in_loop(count, f.step_entries)) {
                     if ((retval = run([&]() { hipLaunchKernelGGL(SearchLoopKernel, dim3(1), dim3(kLoopThreads), 0, stream, c, s, f, lim, ds->d_front); })))
                         return retval;
-                    GR_CHECK(hipMemcpyAsync(h_front, ds->d_front, sizeof(Front), hipMemcpyDeviceToHost, stream), "MaxflowEnactor read-back failed");
-                    GR_CHECK(hipStreamSynchronize(stream), "MaxflowEnactor read-back sync failed");
-                    ++readbacks;
+                    if ((retval = step.Read(h_front, ds->d_front, sizeof(Front), stream))) return retval;
                     f = *h_front;
                     continue;
                 }
@@ -227,9 +178,7 @@ class MaxflowEnactor : public EnactorBase {
                                                     relabel_limit, ds->d_active);
                              })))
                             return retval;
-                        GR_CHECK(hipMemcpyAsync(h_active, ds->d_active, sizeof(Active), hipMemcpyDeviceToHost, stream), "MaxflowEnactor read-back failed");
-                        GR_CHECK(hipStreamSynchronize(stream), "MaxflowEnactor read-back sync failed");
-                        ++readbacks;
+                        if ((retval = step.Read(h_active, ds->d_active, sizeof(Active), stream))) return retval;
                         a = *h_active;
                         rounds += a.steps;
                         trace_rounds[which] += a.steps;
@@ -312,10 +261,6 @@ class MaxflowEnactor : public EnactorBase {
         problem->enacted = true;
         return retval;
     }
-
-   private:
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    unsigned char *h_pinned = nullptr;
 };
 
 }  // namespace maxflow

@@ -27,10 +27,7 @@
 
 #include <climits>
 
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunused-function"  // (only SCC's accessors and tile rule are used here)
-#include <gunrock/app/scc/scc_functor.hpp>
-#pragma clang diagnostic pop
+#include <gunrock/oprtr/step.hpp>
 #include <gunrock/util/device_intrinsics.hpp>
 
 namespace gunrock {
@@ -41,18 +38,17 @@ enum { MAXFLOW_AUTO = 0, MAXFLOW_ROUNDS = 1, MAXFLOW_DEVICE_LOOP = 2 };
 enum { PHASE_PREFLOW = 0, PHASE_RETURN, PHASE_CUT, PHASE_COUNT };
 
 constexpr int kMaxflowThreads = 256;
-constexpr int kLoopThreads = 1024;
-constexpr int kWaveMinRow = 16;              // default "wave_min_row" (taken over from SCC and BCC, not tuned)
-constexpr long long kLoopMaxList = 32768;    // AUTO: the device loop takes a step of up to this many vertices ...
-constexpr long long kLoopMaxEntries = 8192;  // ... whose rows hold up to this many entries (both taken over, not tuned)
-constexpr int kLoopMaxSteps = 4096;          // steps per loop launch
 constexpr int kDischargeSteps = 4;           // default "discharge_steps"
 constexpr int kFar = INT_MAX;                // the cut's searches: not reached
 constexpr unsigned kNever = 0xFFFFFFFFu;     // relabel limit: no global relabel on account of the count
 
-using scc::Ld;
-using scc::St;
-using scc::TileFor;
+using oprtr::kLoopMaxSteps;
+using oprtr::kLoopThreads;
+using oprtr::Ld;
+using oprtr::Limits;
+using oprtr::Narrow;
+using oprtr::St;
+using oprtr::TileFor;
 
 // the words the kernels and the host share
 enum {
@@ -105,16 +101,6 @@ struct Active {
     int steps;                // rounds run by the loop launch
 };
 
-struct Limits {
-    long long max_list, max_entries;
-    int max_steps;
-};
-
-__host__ __device__ __forceinline__ bool Narrow(long long count, long long entries, const Limits &lim)
-{
-    return count <= lim.max_list && entries <= lim.max_entries;
-}
-
 __device__ __forceinline__ long long LdExcess(const long long *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void AddExcess(long long *p, long long d)
 {
@@ -153,12 +139,8 @@ __device__ __forceinline__ void Append(const Ctx &c, int *list, int word, bool h
 {
     const unsigned long long mask = __ballot(hit);
     if (!mask) return;
-    const int lane = static_cast<int>(util::LaneId());
-    unsigned at = 0;
-    if (lane == 0) at = atomicAdd(c.words + word, static_cast<unsigned>(__popcll(mask)));
-    at = __shfl(at, 0, util::kWaveSize);
+    const unsigned pos = oprtr::WaveTicket(c.words + word, mask);
     if (hit) {
-        const unsigned pos = at + __popcll(mask & ((1ull << lane) - 1ull));
         if (pos < static_cast<unsigned>(c.nodes)) St<FRESH>(list + pos, w);
         t.entries += static_cast<unsigned>(c.ro[w + 1] - c.ro[w]);
     }
@@ -235,12 +217,6 @@ __device__ __forceinline__ void SearchLevel(const Ctx &c, const Search &s, int L
         if (lane < tile && i < tail) v = Ld<FRESH>(c.queue + i);
         SearchTile<FRESH>(c, s, v, L, t);
     }
-}
-
-static __global__ void FillKernel(int *d_out, long long count, int value)
-{
-    const long long stride = static_cast<long long>(gridDim.x) * blockDim.x;
-    for (long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; i < count; i += stride) d_out[i] = value;
 }
 
 // the root at level `base`, alone in the queue
@@ -460,8 +436,6 @@ static __global__ void BuildActiveKernel(Ctx c, int *list, int bound)
     }
     Flush(t, c, W_NEXT_ENTRIES);
 }
-
-static __global__ void StampKernel(unsigned long long *d_clock) { *d_clock = wall_clock64(); }
 
 // ---------------- the cut ----------------
 

@@ -45,16 +45,7 @@ constexpr int kLaneRow = 32;      // rows with more entries left than this are w
 constexpr int kSweepThreads = 256;
 constexpr int kWaveUnroll = 4;    // chunks of 64 row entries a wave keeps in flight per step of a long row
 
-// MurmurHash3's 32-bit finaliser
-__host__ __device__ __forceinline__ unsigned Fmix32(unsigned h)
-{
-    h ^= h >> 16;
-    h *= 0x85EBCA6Bu;
-    h ^= h >> 13;
-    h *= 0xC2B2AE35u;
-    h ^= h >> 16;
-    return h;
-}
+using util::Fmix32;
 
 struct Graph {
     const int *d_row_offsets;

@@ -18,33 +18,27 @@
 #include <gunrock/app/enactor_base.hpp>
 #include <gunrock/app/msbfs/msbfs_functor.hpp>
 #include <gunrock/app/msbfs/msbfs_problem.hpp>
+#include <gunrock/app/step_host.hpp>
 
 namespace gunrock {
 namespace app {
 namespace msbfs {
 
 constexpr int kPushWavesPerBlock = kThreads / util::kWaveSize;
-constexpr int kPushBlocks = 2048;  // 256 CUs x 8 workgroups
 
 template <bool INSTRUMENT>
 class MsbfsEnactor : public EnactorBase {
    public:
     explicit MsbfsEnactor(bool DEBUG = false) : EnactorBase(VERTEX_FRONTIERS, DEBUG) {}
-    ~MsbfsEnactor() override
-    {
-        if (ev[0]) hipEventDestroy(ev[0]);
-        if (ev[1]) hipEventDestroy(ev[1]);
-        if (h_words) hipHostFree(h_words);
-    }
 
     // options (grx_msbfs_set_option)
     int direction = MSBFS_AUTO;
     double alpha = kAlpha, beta = kBeta;
     int wave_min_row = kWaveMinRow;
 
-    // of the last Enact
-    long long batches = 0, levels = 0, push_levels = 0, pull_levels = 0, entries_read = 0, launches = 0;
-    double kernel_ms = 0;  // INSTRUMENT: summed level time
+    // of the last Enact (step: its launches and, summed over the levels, their time)
+    StepHost<INSTRUMENT> step{"MsbfsEnactor"};
+    long long batches = 0, levels = 0, push_levels = 0, pull_levels = 0, entries_read = 0;
     std::vector<int> trace_batch, trace_level, trace_kind;        // one row per level: its batch, its depth, LEVEL_PUSH / LEVEL_PULL,
     std::vector<long long> trace_frontier, trace_edges;           // the frontier it started from: vertices and out-row entries,
     std::vector<double> trace_ms;                                 // and (INSTRUMENT) its time
@@ -60,31 +54,21 @@ class MsbfsEnactor : public EnactorBase {
         typename Problem::DataSlice *ds = problem->data_slices[0];
         hipStream_t stream = problem->graph_slices[0]->stream;
         const long long n = problem->nodes, m = problem->edges;
-        batches = levels = push_levels = pull_levels = entries_read = launches = 0;
-        kernel_ms = 0;
+        batches = levels = push_levels = pull_levels = entries_read = 0;
         trace_batch.clear();
         trace_level.clear();
         trace_kind.clear();
         trace_frontier.clear();
         trace_edges.clear();
         trace_ms.clear();
-        if (INSTRUMENT && !ev[0]) {
-            GR_CHECK(hipEventCreate(&ev[0]), "MsbfsEnactor hipEventCreate failed");
-            GR_CHECK(hipEventCreate(&ev[1]), "MsbfsEnactor hipEventCreate failed");
-        }
-        // pinned: the read-back of every level lands here without a staging copy
-        if (!h_words) GR_CHECK(hipHostMalloc(&h_words, sizeof(Word) * W_COUNT), "MsbfsEnactor hipHostMalloc failed");
+        if ((retval = step.Begin(sizeof(Word) * W_COUNT))) return retval;
+        Word *h_words = reinterpret_cast<Word *>(step.pinned);
         auto cap = [&](long long blocks) {
             if (max_grid_size > 0 && blocks > max_grid_size) blocks = max_grid_size;
             return dim3(static_cast<unsigned>(blocks < 1 ? 1 : blocks));
         };
         auto clear_words = [&]() { return util::GRError(hipMemsetAsync(ds->d_words, 0, sizeof(Word) * W_COUNT, stream), "MsbfsEnactor memset failed", __FILE__, __LINE__); };
-        auto read_words = [&]() -> hipError_t {
-            hipError_t retval = hipSuccess;
-            GR_CHECK(hipMemcpyAsync(h_words, ds->d_words, sizeof(Word) * W_COUNT, hipMemcpyDeviceToHost, stream), "MsbfsEnactor read-back failed");
-            GR_CHECK(hipStreamSynchronize(stream), "MsbfsEnactor read-back sync failed");
-            return retval;
-        };
+        auto read_words = [&]() { return step.Read(h_words, ds->d_words, sizeof(Word) * W_COUNT, stream); };
 
         const size_t state_bytes = sizeof(Word) * static_cast<size_t>(n);
         const dim3 block(kThreads);
@@ -98,7 +82,7 @@ class MsbfsEnactor : public EnactorBase {
             if ((retval = clear_words())) return retval;
             hipLaunchKernelGGL(InitKernel, dim3(1), dim3(kBatch), 0, stream, c, ds->d_sources + batch * kBatch, static_cast<int>(in_batch < kBatch ? in_batch : kBatch));
             GR_CHECK(hipGetLastError(), "InitKernel launch failed");
-            ++launches;
+            ++step.launches;
             if ((retval = read_words())) return retval;
             long long count = static_cast<long long>(h_words[W_NEW]);
             long long frontier_edges = static_cast<long long>(h_words[W_FRONTIER_EDGES]);
@@ -122,12 +106,12 @@ class MsbfsEnactor : public EnactorBase {
                 trace_kind.push_back(pull ? LEVEL_PULL : LEVEL_PUSH);
                 trace_frontier.push_back(count);
                 trace_edges.push_back(frontier_edges);
-                if (INSTRUMENT) GR_CHECK(hipEventRecord(ev[0], stream), "MsbfsEnactor hipEventRecord failed");
+                if ((retval = step.Start(stream))) return retval;  // (a level is timed as a whole)
                 if (pull) {
                     if ((retval = clear_words())) return retval;
                     hipLaunchKernelGGL(PullKernel, cap(Problem::Grid(n)), block, 0, stream, c);
                     GR_CHECK(hipGetLastError(), "PullKernel launch failed");
-                    ++launches;
+                    ++step.launches;
                     ++pull_levels;
                     Word *was = c.frontier;  // next[] holds the new frontier for every vertex
                     c.frontier = c.next;
@@ -143,29 +127,25 @@ class MsbfsEnactor : public EnactorBase {
                         if ((retval = clear_words())) return retval;
                         hipLaunchKernelGGL(CompactKernel, cap(Problem::Grid(n)), block, 0, stream, c);
                         GR_CHECK(hipGetLastError(), "CompactKernel launch failed");
-                        ++launches;
+                        ++step.launches;
                         queued = true;
                     }
                     if ((retval = clear_words())) return retval;
-                    const int tile = TileFor(count, static_cast<long long>(kPushBlocks) * kPushWavesPerBlock, frontier_edges);
-                    long long blocks = ((count + tile - 1) / tile + kPushWavesPerBlock - 1) / kPushWavesPerBlock;
-                    if (blocks > kPushBlocks) blocks = kPushBlocks;
-                    hipLaunchKernelGGL(PushKernel, cap(blocks), block, 0, stream, c, count, tile);
+                    const int tile = TileFor(count, static_cast<long long>(kStepBlocks) * kPushWavesPerBlock, frontier_edges);
+                    hipLaunchKernelGGL(PushKernel, StepGrid(count, tile, kPushWavesPerBlock, max_grid_size), block, 0, stream, c, count, tile);
                     GR_CHECK(hipGetLastError(), "PushKernel launch failed");
                     // a push reaches at most one vertex per entry it walks
                     hipLaunchKernelGGL(UpdateKernel, cap(Problem::Grid(frontier_edges < n ? frontier_edges : n)), block, 0, stream, c);
                     GR_CHECK(hipGetLastError(), "UpdateKernel launch failed");
-                    launches += 2;
+                    step.launches += 2;
                     ++push_levels;
                     int *was = c.queue_in;
                     c.queue_in = c.queue_out;
                     c.queue_out = was;
                 }
-                if (INSTRUMENT) GR_CHECK(hipEventRecord(ev[1], stream), "MsbfsEnactor hipEventRecord failed");
-                if ((retval = read_words())) return retval;
                 float ms = 0;
-                if (INSTRUMENT) GR_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]), "MsbfsEnactor hipEventElapsedTime failed");
-                kernel_ms += ms;
+                if ((retval = step.Stop(stream, &ms))) return retval;
+                if ((retval = read_words())) return retval;
                 trace_ms.push_back(ms);
                 ++levels;
                 count = static_cast<long long>(h_words[W_NEW]);
@@ -176,10 +156,6 @@ class MsbfsEnactor : public EnactorBase {
         }
         return retval;
     }
-
-   private:
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    Word *h_words = nullptr;
 };
 
 }  // namespace msbfs

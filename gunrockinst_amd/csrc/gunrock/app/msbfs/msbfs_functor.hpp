@@ -16,11 +16,15 @@
 
 #include <hip/hip_runtime.h>
 
+#include <gunrock/oprtr/step.hpp>
 #include <gunrock/util/device_intrinsics.hpp>
 
 namespace gunrock {
 namespace app {
 namespace msbfs {
+
+using oprtr::kWaveMinRow;  // default "wave_min_row"
+using oprtr::TileFor;
 
 enum { MSBFS_AUTO = 0, MSBFS_PUSH = 1, MSBFS_PULL = 2, MSBFS_ALTERNATE = 3 };
 enum { INVERSE_AUTO = 0, INVERSE_NONE = 1, INVERSE_SELF = 2, INVERSE_BUILD = 3 };
@@ -30,7 +34,6 @@ typedef unsigned long long Word;
 
 constexpr int kThreads = 256;
 constexpr int kBatch = 64;        // sources per batch: the bits of a Word, the lanes of a wave
-constexpr int kWaveMinRow = 16;   // default "wave_min_row"
 constexpr double kAlpha = 4.0;    // default "alpha": push -> pull when frontier edges * alpha > unexplored edges
 constexpr double kBeta = 24.0;    // default "beta": pull -> push when frontier vertices * beta < nodes
 
@@ -354,16 +357,6 @@ static __global__ void ResetKernel(const int *d_sources, long long count, int no
         atomicAdd(d_sources_reaching + v, 1);
         if (d_depth) d_depth[static_cast<size_t>(s) * static_cast<size_t>(nodes) + static_cast<size_t>(v)] = 0;
     }
-}
-
-// Queue entries a wave takes at a time, a power of two up to 64: about kTileEntries row entries per wave and never more waves than
-// there are (app/kcore/kcore_functor.hpp's TileFor and what it records)
-constexpr long long kTileEntries = 512;
-inline int TileFor(long long count, long long waves, long long entries)
-{
-    int tile = 1;
-    while (tile < util::kWaveSize && (count > tile * waves || entries * tile < kTileEntries * count)) tile <<= 1;
-    return tile;
 }
 
 }  // namespace msbfs

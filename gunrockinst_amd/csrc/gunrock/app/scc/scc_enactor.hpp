@@ -17,38 +17,30 @@
 #include <gunrock/app/enactor_base.hpp>
 #include <gunrock/app/scc/scc_functor.hpp>
 #include <gunrock/app/scc/scc_problem.hpp>
+#include <gunrock/app/step_host.hpp>
 
 namespace gunrock {
 namespace app {
 namespace scc {
 
 constexpr int kStepWavesPerBlock = kSccThreads / util::kWaveSize;
-constexpr int kStepBlocks = 2048;  // 256 CUs x 8 workgroups
 constexpr int kStepWaves = kStepBlocks * kStepWavesPerBlock;
+static_assert(SCC_AUTO == SCHEDULE_AUTO && SCC_ROUNDS == SCHEDULE_ROUNDS && SCC_DEVICE_LOOP == SCHEDULE_DEVICE_LOOP, "LoopOptions' schedules");
 
 template <bool INSTRUMENT>
 class SccEnactor : public EnactorBase {
    public:
     explicit SccEnactor(bool DEBUG = false) : EnactorBase(VERTEX_FRONTIERS, DEBUG) {}
-    ~SccEnactor() override
-    {
-        if (ev[0]) hipEventDestroy(ev[0]);
-        if (ev[1]) hipEventDestroy(ev[1]);
-        if (h_words) hipHostFree(h_words);
-    }
 
     // options (grx_scc_set_option)
-    int schedule = SCC_AUTO;
+    LoopOptions loop;
     int pivot_phase = 1;
     int trim = 1;
     int pair_trim = 1;
-    int wave_min_row = kWaveMinRow;
-    long long loop_max_list = kLoopMaxList;
-    long long loop_max_entries = kLoopMaxEntries;
 
-    // of the last Enact
-    long long trimmed = 0, trim_rounds = 0, pivot_component = 0, colour_rounds = 0, sweeps = 0, bfs_levels = 0, entries_read = 0, launches = 0;
-    double kernel_ms = 0;             // INSTRUMENT: summed kernel time
+    // of the last Enact (step: its launches and summed kernel time)
+    StepHost<INSTRUMENT> step{"SccEnactor"};
+    long long trimmed = 0, trim_rounds = 0, pivot_component = 0, colour_rounds = 0, sweeps = 0, bfs_levels = 0, entries_read = 0;
     std::vector<int> trace_kind;      // one row per phase: PHASE_*,
     std::vector<long long> trace_vertices;  // the vertices finished in it,
     std::vector<double> trace_ms;     // and the time to the next phase's start (the device's constant-rate counter)
@@ -63,87 +55,59 @@ class SccEnactor : public EnactorBase {
         typename Problem::DataSlice *ds = problem->data_slices[0];
         hipStream_t stream = problem->graph_slices[0]->stream;
         const long long n = problem->nodes;
-        trimmed = trim_rounds = pivot_component = colour_rounds = sweeps = bfs_levels = entries_read = launches = 0;
-        kernel_ms = 0;
+        trimmed = trim_rounds = pivot_component = colour_rounds = sweeps = bfs_levels = entries_read = 0;
         trace_kind.clear();
         trace_vertices.clear();
         trace_ms.clear();
-        if (INSTRUMENT && !ev[0]) {
-            GR_CHECK(hipEventCreate(&ev[0]), "SccEnactor hipEventCreate failed");
-            GR_CHECK(hipEventCreate(&ev[1]), "SccEnactor hipEventCreate failed");
-        }
-        auto begin = [&]() -> hipError_t {
-            return INSTRUMENT ? util::GRError(hipEventRecord(ev[0], stream), "SccEnactor hipEventRecord failed", __FILE__, __LINE__) : hipSuccess;
-        };
-        auto end = [&]() -> hipError_t {
-            ++launches;
-            if (INSTRUMENT) {
-                float ms = 0;
-                GR_CHECK(hipEventRecord(ev[1], stream), "SccEnactor hipEventRecord failed");
-                GR_CHECK(hipEventSynchronize(ev[1]), "SccEnactor hipEventSynchronize failed");
-                GR_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]), "SccEnactor hipEventElapsedTime failed");
-                kernel_ms += ms;
-            }
-            return hipSuccess;
-        };
+        // pinned: the words, and behind them LoopKernel's state
+        if ((retval = step.Begin(sizeof(unsigned) * W_COUNT + sizeof(State)))) return retval;
+        auto run = [&](auto launch) { return step.Run(stream, launch); };
 
-        const Ctx c = problem->DeviceCtx(wave_min_row);
-        // pinned: the read-back of every round lands here without a staging copy (the words, and behind them LoopKernel's state)
-        if (!h_words) GR_CHECK(hipHostMalloc(&h_words, sizeof(unsigned) * W_COUNT + sizeof(State)), "SccEnactor hipHostMalloc failed");
-        unsigned *words = h_words;
-        State *h_state = reinterpret_cast<State *>(h_words + W_COUNT);
+        const Ctx c = problem->DeviceCtx(loop.wave_min_row);
+        unsigned *words = reinterpret_cast<unsigned *>(step.pinned);
+        State *h_state = reinterpret_cast<State *>(words + W_COUNT);
         for (int i = 0; i < W_COUNT; ++i) words[i] = 0;
         State s = StartState(static_cast<unsigned>(n), 2ull * static_cast<unsigned long long>(problem->edges), trim != 0, pair_trim != 0, pivot_phase != 0, words);
-        const bool all = schedule == SCC_DEVICE_LOOP;
-        const Limits lim = {all ? LLONG_MAX : loop_max_list, all ? LLONG_MAX : loop_max_entries, kLoopMaxSteps};
+        const Limits lim = loop.LimitsFor();
 
         while (s.kind < K_DONE) {
-            if (all || (schedule == SCC_AUTO && Narrow(s, lim))) {
-                if ((retval = begin())) return retval;
-                hipLaunchKernelGGL(LoopKernel, dim3(1), dim3(kLoopThreads), 0, stream, c, s, lim, ds->d_state);
-                GR_CHECK(hipGetLastError(), "LoopKernel launch failed");
-                if ((retval = end())) return retval;
-                GR_CHECK(hipMemcpyAsync(h_state, ds->d_state, sizeof(State), hipMemcpyDeviceToHost, stream), "SccEnactor read-back failed");
-                GR_CHECK(hipStreamSynchronize(stream), "SccEnactor read-back sync failed");
+            if (loop.schedule == SCC_DEVICE_LOOP || (loop.schedule == SCC_AUTO && Narrow(s, lim))) {
+                if ((retval = run([&]() { hipLaunchKernelGGL(LoopKernel, dim3(1), dim3(kLoopThreads), 0, stream, c, s, lim, ds->d_state); }))) return retval;
+                if ((retval = step.Read(h_state, ds->d_state, sizeof(State), stream))) return retval;
                 s = *h_state;
                 continue;
             }
             const bool by_list = ByList(s.kind);
             const long long count = by_list ? s.list_len : static_cast<long long>(s.tail - s.head);
             const int tile = by_list || s.seed >= 0 ? util::kWaveSize : TileFor(count, kStepWaves, s.step_entries);
-            long long blocks = ((count + tile - 1) / tile + kStepWavesPerBlock - 1) / kStepWavesPerBlock;
-            if (blocks > kStepBlocks) blocks = kStepBlocks;
-            if (max_grid_size > 0 && blocks > max_grid_size) blocks = max_grid_size;
-            if (blocks < 1) blocks = 1;
-            if ((retval = begin())) return retval;
-            const dim3 grid(static_cast<unsigned>(blocks)), block(kSccThreads);
-            switch (s.kind) {
-                case K_COUNT: hipLaunchKernelGGL(StepKernel<K_COUNT>, grid, block, 0, stream, c, s, tile); break;
-                case K_SCAN: hipLaunchKernelGGL(StepKernel<K_SCAN>, grid, block, 0, stream, c, s, tile); break;
-                case K_TRIM: hipLaunchKernelGGL(StepKernel<K_TRIM>, grid, block, 0, stream, c, s, tile); break;
-                case K_PICK: hipLaunchKernelGGL(StepKernel<K_PICK>, grid, block, 0, stream, c, s, tile); break;
-                case K_FWD: hipLaunchKernelGGL(StepKernel<K_FWD>, grid, block, 0, stream, c, s, tile); break;
-                case K_BWD: hipLaunchKernelGGL(StepKernel<K_BWD>, grid, block, 0, stream, c, s, tile); break;
-                case K_SPLIT: hipLaunchKernelGGL(StepKernel<K_SPLIT>, grid, block, 0, stream, c, s, tile); break;
-                case K_INIT: hipLaunchKernelGGL(StepKernel<K_INIT>, grid, block, 0, stream, c, s, tile); break;
-                case K_SWEEP: hipLaunchKernelGGL(StepKernel<K_SWEEP>, grid, block, 0, stream, c, s, tile); break;
-                case K_ROOTS: hipLaunchKernelGGL(StepKernel<K_ROOTS>, grid, block, 0, stream, c, s, tile); break;
-                case K_BACK: hipLaunchKernelGGL(StepKernel<K_BACK>, grid, block, 0, stream, c, s, tile); break;
-                case K_PAIR: hipLaunchKernelGGL(StepKernel<K_PAIR>, grid, block, 0, stream, c, s, tile); break;
-                default: hipLaunchKernelGGL(StepKernel<K_FINISH>, grid, block, 0, stream, c, s, tile); break;
-            }
-            GR_CHECK(hipGetLastError(), "StepKernel launch failed");
-            if ((retval = end())) return retval;
-            GR_CHECK(hipMemcpyAsync(words, ds->d_words, sizeof(unsigned) * W_COUNT, hipMemcpyDeviceToHost, stream), "SccEnactor read-back failed");
-            GR_CHECK(hipStreamSynchronize(stream), "SccEnactor read-back sync failed");
+            const dim3 grid = StepGrid(count, tile, kStepWavesPerBlock, max_grid_size), block(kSccThreads);
+            retval = run([&]() {
+                switch (s.kind) {
+                    case K_COUNT: hipLaunchKernelGGL(StepKernel<K_COUNT>, grid, block, 0, stream, c, s, tile); break;
+                    case K_SCAN: hipLaunchKernelGGL(StepKernel<K_SCAN>, grid, block, 0, stream, c, s, tile); break;
+                    case K_TRIM: hipLaunchKernelGGL(StepKernel<K_TRIM>, grid, block, 0, stream, c, s, tile); break;
+                    case K_PICK: hipLaunchKernelGGL(StepKernel<K_PICK>, grid, block, 0, stream, c, s, tile); break;
+                    case K_FWD: hipLaunchKernelGGL(StepKernel<K_FWD>, grid, block, 0, stream, c, s, tile); break;
+                    case K_BWD: hipLaunchKernelGGL(StepKernel<K_BWD>, grid, block, 0, stream, c, s, tile); break;
+                    case K_SPLIT: hipLaunchKernelGGL(StepKernel<K_SPLIT>, grid, block, 0, stream, c, s, tile); break;
+                    case K_INIT: hipLaunchKernelGGL(StepKernel<K_INIT>, grid, block, 0, stream, c, s, tile); break;
+                    case K_SWEEP: hipLaunchKernelGGL(StepKernel<K_SWEEP>, grid, block, 0, stream, c, s, tile); break;
+                    case K_ROOTS: hipLaunchKernelGGL(StepKernel<K_ROOTS>, grid, block, 0, stream, c, s, tile); break;
+                    case K_BACK: hipLaunchKernelGGL(StepKernel<K_BACK>, grid, block, 0, stream, c, s, tile); break;
+                    case K_PAIR: hipLaunchKernelGGL(StepKernel<K_PAIR>, grid, block, 0, stream, c, s, tile); break;
+                    default: hipLaunchKernelGGL(StepKernel<K_FINISH>, grid, block, 0, stream, c, s, tile); break;
+                }
+            });
+            if (retval) return retval;
+            if ((retval = step.Read(words, ds->d_words, sizeof(unsigned) * W_COUNT, stream))) return retval;
             Advance(s, words, static_cast<unsigned>(n));
         }
 
         if (s.kind == K_STUCK) return util::GRError(hipErrorUnknown, "SccEnactor: a colouring round made no progress", __FILE__, __LINE__);
-        if ((retval = begin())) return retval;
-        if ((retval = problem->Canonical())) return retval;
-        launches += 2;
-        if ((retval = end())) return retval;
+        hipError_t canonical = hipSuccess;
+        if ((retval = run([&]() { canonical = problem->Canonical(); }))) return retval;
+        if (canonical) return canonical;
+        step.launches += 2;  // (Canonical is three kernels)
         trimmed = s.trimmed;
         trim_rounds = s.trim_rounds;
         pivot_component = s.pivot_component;
@@ -152,8 +116,7 @@ class SccEnactor : public EnactorBase {
         bfs_levels = s.bfs_levels;
 
         // the trace and the counters
-        hipLaunchKernelGGL(EndStampKernel, dim3(1), dim3(1), 0, stream, ds->d_counters + 1);
-        GR_CHECK(hipGetLastError(), "EndStampKernel launch failed");
+        if ((retval = step.Stamp(ds->d_counters + 1, stream))) return retval;
         unsigned long long counters[2] = {0, 0};
         GR_CHECK(hipMemcpyAsync(counters, ds->d_counters, sizeof(counters), hipMemcpyDeviceToHost, stream), "SccEnactor read-back failed");
         GR_CHECK(hipStreamSynchronize(stream), "SccEnactor read-back sync failed");
@@ -183,10 +146,6 @@ class SccEnactor : public EnactorBase {
         }
         return retval;
     }
-
-   private:
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    unsigned *h_words = nullptr;
 };
 
 }  // namespace scc

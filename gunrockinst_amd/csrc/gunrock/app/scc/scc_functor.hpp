@@ -35,22 +35,24 @@
 
 #include <hip/hip_runtime.h>
 
+#include <gunrock/oprtr/step.hpp>
 #include <gunrock/util/device_intrinsics.hpp>
 
 namespace gunrock {
 namespace app {
 namespace scc {
 
+using oprtr::kLoopThreads;
+using oprtr::Ld;
+using oprtr::Limits;
+using oprtr::St;
+using oprtr::TileFor;
+
 enum { SCC_AUTO = 0, SCC_ROUNDS = 1, SCC_DEVICE_LOOP = 2 };
 enum { PHASE_TRIM = 0, PHASE_PIVOT = 1, PHASE_COLOUR = 2 };
 
 constexpr int kSccThreads = 256;
-constexpr int kLoopThreads = 1024;
 constexpr int kWaveUnroll = 4;             // chunks of 64 row entries a wave keeps in flight per step of a long row
-constexpr int kWaveMinRow = 16;            // default "wave_min_row"
-constexpr long long kLoopMaxList = 32768;  // AUTO: the device loop takes a step over up to this many vertices ...
-constexpr long long kLoopMaxEntries = 8192;   // ... whose rows hold up to this many entries
-constexpr int kLoopMaxSteps = 4096;        // steps per LoopKernel launch
 constexpr int kDone = static_cast<int>(0x80000000u);  // region[]: finished
 constexpr unsigned kTraceRows = 1u << 16;  // phases recorded (a run has at most 2 * nodes + 3)
 
@@ -109,23 +111,6 @@ struct State {
     unsigned trimmed, trim_rounds, pivot_component, colour_rounds, sweeps, bfs_levels;
 };
 
-struct Limits {
-    long long max_list, max_entries;
-    int max_steps;
-};
-
-template <bool FRESH>
-__device__ __forceinline__ int Ld(const int *p)
-{
-    return FRESH ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *p;
-}
-template <bool FRESH>
-__device__ __forceinline__ void St(int *p, int v)
-{
-    if (FRESH) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else *p = v;
-}
-
 struct Tally {
     unsigned entries = 0;   // row entries of the vertices this lane queued
     unsigned lentries = 0;  // ... listed
@@ -156,15 +141,8 @@ __device__ __forceinline__ void Append(const Ctx &c, bool hit, int u, int *d_out
 {
     const unsigned long long mask = __ballot(hit);
     if (!mask) return;
-    const int lane = static_cast<int>(util::LaneId());
-    unsigned at = 0;
-    if (lane == 0) {
-        at = atomicAdd(c.words + (LIST ? W_LIST : W_TAIL), static_cast<unsigned>(__popcll(mask)));
-        if (FINISHES) atomicAdd(c.words + W_FINISHED, static_cast<unsigned>(__popcll(mask)));
-    }
-    at = __shfl(at, 0, util::kWaveSize) - base;
+    const unsigned pos = oprtr::WaveTicket(c.words + (LIST ? W_LIST : W_TAIL), mask, FINISHES ? c.words + W_FINISHED : nullptr) - base;
     if (hit) {
-        const unsigned pos = at + __popcll(mask & ((1ull << lane) - 1ull));
         if (pos < static_cast<unsigned>(c.nodes)) St<FRESH>(d_out + pos, u);
         if (LIST) t.lentries += RowEntries(c, u);
         else t.entries += RowEntries(c, u);
@@ -325,17 +303,6 @@ __device__ __forceinline__ int MateOf(const Ctx &c, const int *ro, const int *ci
     const int u = OnlyLive<FRESH>(c, ro, ci, v, key, t);
     if (u < 0 || Ld<FRESH>(counter + u) != 1) return -1;
     return OnlyLive<FRESH>(c, ro, ci, u, key, t) == v ? u : -1;
-}
-
-// Queue entries a wave takes at a time, a power of two up to 64: about kTileEntries row entries per wave and never more waves
-// than there are (kcore_functor.hpp's TileFor and what it records: a tile sized by vertices sends an atomic per two lanes to one
-// word on a front of short rows, and walks the rows of a front of hubs one after the other).
-constexpr long long kTileEntries = 512;
-__host__ __device__ __forceinline__ int TileFor(long long count, long long waves, long long entries)
-{
-    int tile = 1;
-    while (tile < util::kWaveSize && (count > tile * waves || entries * tile < kTileEntries * count)) tile <<= 1;
-    return tile;
 }
 
 // ---------------- one step ----------------
@@ -660,7 +627,7 @@ __host__ __device__ __forceinline__ bool Narrow(const State &s, const Limits &li
 {
     if (ByList(s.kind)) return s.list_len <= lim.max_list && (s.kind != K_COUNT || s.list_entries <= lim.max_entries);
     if (s.seed >= 0) return true;
-    return static_cast<long long>(s.tail - s.head) <= lim.max_list && s.step_entries <= lim.max_entries;
+    return oprtr::Narrow(static_cast<long long>(s.tail - s.head), s.step_entries, lim);
 }
 
 // ---------------- the wide form and the device loop ----------------
@@ -712,8 +679,6 @@ static __global__ __launch_bounds__(kLoopThreads) void LoopKernel(Ctx c, State s
 }
 
 // ---------------- after the run ----------------
-
-static __global__ void EndStampKernel(unsigned long long *d_clock) { *d_clock = wall_clock64(); }
 
 static __global__ void IotaKernel(int *d_out, long long nodes)
 {

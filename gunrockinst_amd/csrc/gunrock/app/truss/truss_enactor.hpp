@@ -16,6 +16,7 @@
 #include <vector>
 
 #include <gunrock/app/enactor_base.hpp>
+#include <gunrock/app/step_host.hpp>
 #include <gunrock/app/truss/truss_functor.hpp>
 #include <gunrock/app/truss/truss_problem.hpp>
 
@@ -24,33 +25,22 @@ namespace app {
 namespace truss {
 
 constexpr int kPeelWavesPerBlock = kTrussThreads / util::kWaveSize;
-constexpr int kPeelWaves = 2048 * kPeelWavesPerBlock;  // 256 CUs x 8 workgroups x 4 waves
+constexpr int kPeelWaves = kStepBlocks * kPeelWavesPerBlock;  // 256 CUs x 8 workgroups x 4 waves
+static_assert(TRUSS_AUTO == SCHEDULE_AUTO && TRUSS_ROUNDS == SCHEDULE_ROUNDS, "LoopOptions' schedules");
 
 template <bool INSTRUMENT>
 class TrussEnactor : public EnactorBase {
    public:
-    explicit TrussEnactor(bool DEBUG = false) : EnactorBase(EDGE_FRONTIERS, DEBUG) {}
-    ~TrussEnactor() override
-    {
-        if (ev[0]) hipEventDestroy(ev[0]);
-        if (ev[1]) hipEventDestroy(ev[1]);
-        if (h_words) hipHostFree(h_words);
-    }
+    explicit TrussEnactor(bool DEBUG = false) : EnactorBase(EDGE_FRONTIERS, DEBUG) { loop.wave_min_row = kWaveMinRow; }
 
-    // options (grx_truss_set_option)
-    int schedule = TRUSS_AUTO;
-    int wave_min_row = kWaveMinRow;
-    long long loop_max_list = kLoopMaxList;
-    long long loop_max_entries = kLoopMaxEntries;
+    LoopOptions loop;  // options (grx_truss_set_option); wave_min_row starts at truss's own default
 
-    // of the last Enact
+    // of the last Enact (step: its launches, read-backs of the words and summed kernel time)
+    StepHost<INSTRUMENT> step{"TrussEnactor"};
     long long levels = 0;            // non-empty levels
     long long rounds = 0;            // sub-rounds
     long long edges_peeled = 0;
     long long entries_read = 0;
-    long long launches = 0;
-    long long readbacks = 0;         // host-visible read-backs of the words
-    double kernel_ms = 0;            // INSTRUMENT: summed kernel time
     std::vector<int> trace_k;        // the non-empty levels: k,
     std::vector<long long> trace_edges;  // the edges peeled at it,
     std::vector<double> trace_ms;    // and the time from its scan to the next one's (the device's constant-rate counter)
@@ -66,46 +56,19 @@ class TrussEnactor : public EnactorBase {
         hipStream_t stream = problem->graph_slices[0]->stream;
         const long long M = problem->simple_edges;
         const int s_limit = k_limit < 0 ? INT_MAX : k_limit - 2;
-        levels = rounds = edges_peeled = entries_read = launches = readbacks = 0;
-        kernel_ms = 0;
+        levels = rounds = edges_peeled = entries_read = 0;
         trace_k.clear();
         trace_edges.clear();
         trace_ms.clear();
-        if (INSTRUMENT && !ev[0]) {
-            GR_CHECK(hipEventCreate(&ev[0]), "TrussEnactor hipEventCreate failed");
-            GR_CHECK(hipEventCreate(&ev[1]), "TrussEnactor hipEventCreate failed");
-        }
-        auto grid = [&](long long blocks, int cap) {
-            if (blocks > cap) blocks = cap;
-            if (blocks < 1) blocks = 1;
-            return static_cast<int>(max_grid_size > 0 && max_grid_size < blocks ? max_grid_size : blocks);
-        };
-        auto begin = [&]() -> hipError_t {
-            return INSTRUMENT ? util::GRError(hipEventRecord(ev[0], stream), "TrussEnactor hipEventRecord failed", __FILE__, __LINE__) : hipSuccess;
-        };
-        auto end = [&]() -> hipError_t {
-            ++launches;
-            if (INSTRUMENT) {
-                float ms = 0;
-                GR_CHECK(hipEventRecord(ev[1], stream), "TrussEnactor hipEventRecord failed");
-                GR_CHECK(hipEventSynchronize(ev[1]), "TrussEnactor hipEventSynchronize failed");
-                GR_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]), "TrussEnactor hipEventElapsedTime failed");
-                kernel_ms += ms;
-            }
-            return hipSuccess;
-        };
+        if ((retval = step.Begin(sizeof(unsigned) * W_COUNT))) return retval;
+        auto run = [&](auto launch) { return step.Run(stream, launch); };
+        auto grid_for = [&](long long work) { return GridFor(work, max_grid_size); };
 
         const Graph g = problem->DeviceGraph();
         const Trace tr = {ds->d_trace_k, ds->d_trace_tail, ds->d_trace_clock};
-        if (!h_words) GR_CHECK(hipHostMalloc(&h_words, sizeof(unsigned) * W_COUNT), "TrussEnactor hipHostMalloc failed");
-        unsigned *words = h_words;  // pinned: the read-back of every round lands here without a staging copy
+        unsigned *words = reinterpret_cast<unsigned *>(step.pinned);
         for (int i = 0; i < W_COUNT; ++i) words[i] = 0;
-        auto read_words = [&]() -> hipError_t {
-            GR_CHECK(hipMemcpyAsync(words, ds->d_words, sizeof(unsigned) * W_COUNT, hipMemcpyDeviceToHost, stream), "TrussEnactor read-back failed");
-            GR_CHECK(hipStreamSynchronize(stream), "TrussEnactor read-back sync failed");
-            ++readbacks;
-            return hipSuccess;
-        };
+        auto read_words = [&]() { return step.Read(words, ds->d_words, sizeof(unsigned) * W_COUNT, stream); };
 
         // the state of the peel (LoopKernel carries the same in registers)
         long long head = 0, tail = 0;
@@ -125,8 +88,8 @@ class TrussEnactor : public EnactorBase {
                 if (M - tail <= 0) break;
                 if (s >= s_limit) break;
             }
-            const bool in_loop = !wide_once && schedule == TRUSS_AUTO &&
-                                 (open ? static_cast<long long>(words[W_ENTRIES] - entries_seen) <= loop_max_entries : M <= loop_max_list);
+            const bool in_loop = !wide_once && loop.schedule == TRUSS_AUTO &&
+                                 (open ? static_cast<long long>(words[W_ENTRIES] - entries_seen) <= loop.loop_max_entries : M <= loop.loop_max_list);
             wide_once = false;
             if (in_loop) {
                 LoopArgs a;
@@ -138,15 +101,15 @@ class TrussEnactor : public EnactorBase {
                 a.s_limit = s_limit;
                 a.round = cur;
                 a.level_open = open ? 1 : 0;
-                a.wave_min_row = wave_min_row;
-                a.max_list = loop_max_list;
-                a.max_entries = loop_max_entries;
+                a.wave_min_row = loop.wave_min_row;
+                a.max_list = loop.loop_max_list;
+                a.max_entries = loop.loop_max_entries;
                 a.max_steps = kLoopMaxSteps;
-                if ((retval = begin())) return retval;
-                hipLaunchKernelGGL(LoopKernel, dim3(1), dim3(kLoopThreads), 0, stream, g, ds->d_val, ds->d_stamp, ds->d_queue, ds->d_words,
-                                   ds->d_counters, tr, a);
-                GR_CHECK(hipGetLastError(), "LoopKernel launch failed");
-                if ((retval = end())) return retval;
+                if ((retval = run([&]() {
+                         hipLaunchKernelGGL(LoopKernel, dim3(1), dim3(kLoopThreads), 0, stream, g, ds->d_val, ds->d_stamp, ds->d_queue, ds->d_words,
+                                            ds->d_counters, tr, a);
+                     })))
+                    return retval;
                 if ((retval = read_words())) return retval;
                 head = static_cast<int>(words[W_HEAD]);
                 tail = words[W_TAIL];
@@ -161,14 +124,12 @@ class TrussEnactor : public EnactorBase {
                 continue;
             }
             if (open) {  // one sub-round, wide
-                if ((retval = begin())) return retval;
                 const int tile = TileFor(tail - head, kPeelWaves, static_cast<long long>(words[W_ENTRIES] - entries_seen));
-                const long long tiles = (tail - head + tile - 1) / tile;
-                hipLaunchKernelGGL(PeelKernel, dim3(grid((tiles + kPeelWavesPerBlock - 1) / kPeelWavesPerBlock, kPeelWaves / kPeelWavesPerBlock)),
-                                   dim3(kTrussThreads), 0, stream, g, ds->d_val, ds->d_stamp, ds->d_queue, head, tail, s, cur, wave_min_row, tile,
-                                   ds->d_words, ds->d_counters);
-                GR_CHECK(hipGetLastError(), "PeelKernel launch failed");
-                if ((retval = end())) return retval;
+                if ((retval = run([&]() {
+                         hipLaunchKernelGGL(PeelKernel, StepGrid(tail - head, tile, kPeelWavesPerBlock, max_grid_size), dim3(kTrussThreads), 0, stream, g,
+                                            ds->d_val, ds->d_stamp, ds->d_queue, head, tail, s, cur, loop.wave_min_row, tile, ds->d_words, ds->d_counters);
+                     })))
+                    return retval;
                 head = tail;
                 entries_seen = words[W_ENTRIES];
                 ++cur;
@@ -179,30 +140,26 @@ class TrussEnactor : public EnactorBase {
             }
             // the start of level s, wide: the scan of every edge
             GR_CHECK(hipMemsetAsync(ds->d_words + W_LOW, 0xFF, sizeof(unsigned), stream), "TrussEnactor memset failed");
-            if ((retval = begin())) return retval;
-            hipLaunchKernelGGL(ScanKernel, dim3(grid((M + kTrussThreads - 1) / kTrussThreads, 2048)), dim3(kTrussThreads), 0, stream, g, ds->d_val,
-                               ds->d_stamp, M, sprev, s, cur, ds->d_queue, ds->d_words, tr, static_cast<unsigned>(tail));
-            GR_CHECK(hipGetLastError(), "ScanKernel launch failed");
-            if ((retval = end())) return retval;
+            if ((retval = run([&]() {
+                     hipLaunchKernelGGL(ScanKernel, grid_for(M), dim3(kTrussThreads), 0, stream, g, ds->d_val, ds->d_stamp, M, sprev, s, cur, ds->d_queue,
+                                        ds->d_words, tr, static_cast<unsigned>(tail));
+                 })))
+                return retval;
             if ((retval = read_words())) return retval;
             tail = words[W_TAIL];
             open = true;
         }
 
         // truss = min(val, the level a limited run stopped at) + 2
-        if ((retval = begin())) return retval;
-        hipLaunchKernelGGL(FinishKernel, dim3(grid((M + 255) / 256, 2048)), dim3(256), 0, stream, ds->d_val, M, s_limit, ds->d_truss);
-        GR_CHECK(hipGetLastError(), "FinishKernel launch failed");
-        if ((retval = end())) return retval;
+        if ((retval = run([&]() { hipLaunchKernelGGL(FinishKernel, grid_for(M), dim3(256), 0, stream, ds->d_val, M, s_limit, ds->d_truss); }))) return retval;
         problem->enacted = true;
         edges_peeled = tail;
 
         // the trace and the counters: one more read, not counted as a read-back of the peel
-        hipLaunchKernelGGL(kcore::EndStampKernel, dim3(1), dim3(1), 0, stream, ds->d_counters + 3);
-        GR_CHECK(hipGetLastError(), "EndStampKernel launch failed");
+        if ((retval = step.Stamp(ds->d_counters + 3, stream))) return retval;
         unsigned long long counters[4] = {0, 0, 0, 0};
-        GR_CHECK(hipMemcpyAsync(words, ds->d_words, sizeof(unsigned) * W_COUNT, hipMemcpyDeviceToHost, stream), "TrussEnactor read-back failed");
-        GR_CHECK(hipMemcpyAsync(counters, ds->d_counters, sizeof(counters), hipMemcpyDeviceToHost, stream), "TrussEnactor read-back failed");
+        if ((retval = step.Copy(words, ds->d_words, sizeof(unsigned) * W_COUNT, stream))) return retval;
+        if ((retval = step.Copy(counters, ds->d_counters, sizeof(counters), stream))) return retval;
         GR_CHECK(hipStreamSynchronize(stream), "TrussEnactor read-back sync failed");
         entries_read = static_cast<long long>(counters[0]);
         rounds += words[W_SUBROUNDS];
@@ -231,10 +188,6 @@ class TrussEnactor : public EnactorBase {
         levels = static_cast<long long>(trace_k.size());
         return retval;
     }
-
-   private:
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    unsigned *h_words = nullptr;
 };
 
 }  // namespace truss

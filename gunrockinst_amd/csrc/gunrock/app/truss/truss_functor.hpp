@@ -25,7 +25,7 @@
 //
 // Rows: a lane per intersection whose shorter row has fewer than `wave_min_row` entries, the whole wave for the others; both loops
 // are wave-uniform, so the appends of one step are one ballot and one atomic on the tail per wave.  A wave's tile of frontier edges
-// is sized by the entries of their shorter rows (kcore::TileFor), not by their number.
+// is sized by the entries of their shorter rows (oprtr::TileFor), not by their number.
 //
 // Kernels: ScanKernel / PeelKernel are the wide forms, one launch per step, the host reading the words in between.  LoopKernel is
 // one workgroup of 1024 that runs the same steps in a loop on the device (agent-scope accesses on everything a step hands to the
@@ -40,6 +40,7 @@
 #include <gunrock/app/kcore/kcore_functor.hpp>
 #include <gunrock/app/tc/tc_functor.hpp>
 #pragma clang diagnostic pop
+#include <gunrock/oprtr/step.hpp>
 #include <gunrock/util/device_intrinsics.hpp>
 
 namespace gunrock {
@@ -49,16 +50,14 @@ namespace truss {
 enum { TRUSS_AUTO = 0, TRUSS_ROUNDS = 1 };
 
 constexpr int kTrussThreads = 256;
-constexpr int kLoopThreads = 1024;
-constexpr int kWaveMinRow = 32;             // default "wave_min_row" 
-constexpr long long kLoopMaxList = 32768;   // AUTO: the device loop scans an edge list up to this length ...
-constexpr long long kLoopMaxEntries = 8192; // ... and runs sub-rounds whose shorter rows hold up to this many entries
-constexpr int kLoopMaxSteps = 4096;
+constexpr int kWaveMinRow = 32;  // default "wave_min_row", not the shared 16
 
 using kcore::kNoLevel;
-using kcore::Ld;
-using kcore::St;
-using kcore::TileFor;
+using oprtr::kLoopMaxSteps;
+using oprtr::kLoopThreads;
+using oprtr::Ld;
+using oprtr::St;
+using oprtr::TileFor;
 using tc::LowerBound;
 
 // the words the kernels and the host share
@@ -141,12 +140,9 @@ __device__ __forceinline__ void Append(const Graph &g, bool hit, int e, int next
 {
     const unsigned long long mask = __ballot(hit);
     if (!mask) return;
-    const int lane = static_cast<int>(util::LaneId());
-    unsigned at = 0;
-    if (lane == 0) at = atomicAdd(d_words + W_TAIL, static_cast<unsigned>(__popcll(mask)));
-    at = __shfl(at, 0, util::kWaveSize);
+    const unsigned pos = oprtr::WaveTicket(d_words + W_TAIL, mask);
     if (hit) {
-        St<FRESH>(d_queue + at + __popcll(mask & ((1ull << lane) - 1ull)), e);
+        St<FRESH>(d_queue + pos, e);
         St<FRESH>(d_stamp + e, next);
         int sb, se, lb, le;
         RowsOf(g, e, sb, se, lb, le);

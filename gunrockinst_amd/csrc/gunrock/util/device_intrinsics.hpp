@@ -27,6 +27,17 @@ __device__ __forceinline__ unsigned RankInMask(unsigned long long mask)
                                      __builtin_amdgcn_mbcnt_lo(static_cast<unsigned>(mask), 0u));
 }
 
+// MurmurHash3's 32-bit finaliser (a bijection of the 32-bit words)
+__host__ __device__ __forceinline__ unsigned Fmix32(unsigned h)
+{
+    h ^= h >> 16;
+    h *= 0x85EBCA6Bu;
+    h ^= h >> 13;
+    h *= 0xC2B2AE35u;
+    h ^= h >> 16;
+    return h;
+}
+
 // Workgroup barrier for LDS hand-offs only: waits for this wave's LDS operations, NOT for its outstanding global stores.
 // __syncthreads() drains vmcnt too (s_waitcnt vmcnt(0) lgkmcnt(0); s_barrier), i.e. a wave that has just issued scattered
 // global stores sits at the barrier for their full round trip (~3 us under load on MI355X) although nobody in the workgroup

@@ -62,23 +62,7 @@ struct BccRunnerT : BccRunner {
     }
     int SetOption(const char *name, double value) override
     {
-        const long long v = static_cast<long long>(value);
-        if (!std::strcmp(name, "schedule")) {
-            if (v < BCC_AUTO || v > BCC_DEVICE_LOOP) return -1;
-            enactor.schedule = static_cast<int>(v);
-        } else if (!std::strcmp(name, "wave_min_row")) {
-            if (v < 1) return -1;
-            enactor.wave_min_row = static_cast<int>(v < (1 << 30) ? v : (1 << 30));
-        } else if (!std::strcmp(name, "loop_max_list")) {
-            if (v < 0) return -1;
-            enactor.loop_max_list = v;
-        } else if (!std::strcmp(name, "loop_max_entries")) {
-            if (v < 0) return -1;
-            enactor.loop_max_entries = v;
-        } else {
-            return 1;
-        }
-        return 0;
+        return enactor.loop.Set(name, value, BCC_DEVICE_LOOP);  // (no option of its own)
     }
     bool Done() const { return state.ready && problem.enacted; }
     hipError_t Reset() override { return state.ready ? problem.Reset() : hipErrorNotReady; }
@@ -93,9 +77,9 @@ struct BccRunnerT : BccRunner {
         out[1] = enactor.trees;
         out[2] = enactor.levels;
         out[3] = enactor.entries_read;
-        out[4] = enactor.launches;
-        out[5] = enactor.readbacks;
-        kernel_ms = enactor.kernel_ms;
+        out[4] = enactor.step.launches;
+        out[5] = enactor.step.readbacks;
+        kernel_ms = enactor.step.kernel_ms;
         build_ms = problem.build_ms;
     }
     int PhaseTrace(int max_phases, int *kind, long long *items, double *ms) override

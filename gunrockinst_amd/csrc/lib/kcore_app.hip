@@ -58,25 +58,11 @@ struct KcoreRunnerT : KcoreRunner {
     }
     int SetOption(const char *name, double value) override
     {
-        const long long v = static_cast<long long>(value);
-        if (!std::strcmp(name, "schedule")) {
-            if (v < KCORE_AUTO || v > KCORE_DEVICE_LOOP) return -1;
-            enactor.schedule = static_cast<int>(v);
-        } else if (!std::strcmp(name, "compact_below")) {
-            if (!(value >= 0.0 && value <= 1.0)) return -1;
-            enactor.compact_below = value;
-        } else if (!std::strcmp(name, "wave_min_row")) {
-            if (v < 1) return -1;
-            enactor.wave_min_row = static_cast<int>(v < (1 << 30) ? v : (1 << 30));
-        } else if (!std::strcmp(name, "loop_max_list")) {
-            if (v < 0) return -1;
-            enactor.loop_max_list = v;
-        } else if (!std::strcmp(name, "loop_max_entries")) {
-            if (v < 0) return -1;
-            enactor.loop_max_entries = v;
-        } else {
-            return 1;
-        }
+        const int shared = enactor.loop.Set(name, value, KCORE_DEVICE_LOOP);
+        if (shared != 1) return shared;
+        if (std::strcmp(name, "compact_below")) return 1;
+        if (!(value >= 0.0 && value <= 1.0)) return -1;
+        enactor.compact_below = value;
         return 0;
     }
     hipError_t Reset() override { return state.ready ? problem.Reset() : hipErrorNotReady; }
@@ -94,8 +80,8 @@ struct KcoreRunnerT : KcoreRunner {
         out[4] = enactor.vertices_peeled;
         out[5] = enactor.entries_read;
         out[6] = enactor.compactions;
-        out[7] = enactor.launches;
-        kernel_ms = enactor.kernel_ms;
+        out[7] = enactor.step.launches;
+        kernel_ms = enactor.step.kernel_ms;
         build_ms = problem.build_ms;
     }
     int LevelTrace(int max_levels, int *k, long long *vertices, double *ms) override
@@ -118,7 +104,7 @@ struct KcoreRunnerT : KcoreRunner {
     hipError_t Members(int k, unsigned char *mask, long long *vertices, long long *edges) override
     {
         if (!state.ready) return hipErrorNotReady;
-        return problem.Members(k, enactor.wave_min_row, mask, vertices, edges);
+        return problem.Members(k, enactor.loop.wave_min_row, mask, vertices, edges);
     }
     void DeviceResults(int **d_core, int **d_degrees) override
     {

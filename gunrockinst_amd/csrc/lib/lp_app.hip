@@ -122,9 +122,9 @@ struct LpRunnerT : LpRunner {
         out[4] = enactor.entries_read;
         for (int i = 0; i < 3; ++i) out[5 + i] = enactor.regime_rows[i];
         out[8] = enactor.fallback_rows;
-        out[9] = enactor.launches;
-        out[10] = enactor.readbacks;
-        kernel_ms = enactor.kernel_ms;
+        out[9] = enactor.step.launches;
+        out[10] = enactor.step.readbacks;
+        kernel_ms = enactor.step.kernel_ms;
         build_ms = problem.build_ms;
     }
     int RoundTrace(int max_rounds, long long *list, long long *changed) override

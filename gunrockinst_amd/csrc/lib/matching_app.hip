@@ -64,22 +64,12 @@ struct MatchingRunnerT : MatchingRunner {
     int SetOption(const char *name, double value) override
     {
         if (!(value == value)) return -1;  // (NaN)
-        const long long v = value >= 9.0e18 ? LLONG_MAX : (value <= -9.0e18 ? LLONG_MIN : static_cast<long long>(value));
-        if (!std::strcmp(name, "schedule")) {
-            if (v < MATCHING_AUTO || v > MATCHING_DEVICE_LOOP) return -1;
-            enactor.schedule = static_cast<int>(v);
-        } else if (!std::strcmp(name, "wave_min_row")) {
-            if (v < 1) return -1;
-            enactor.wave_min_row = static_cast<int>(v < (1 << 30) ? v : (1 << 30));
-        } else if (!std::strcmp(name, "max_rounds")) {
+        const int shared = enactor.loop.Set(name, value, MATCHING_DEVICE_LOOP);
+        if (shared != 1) return shared;
+        const long long v = LoopOptions::Whole(value);
+        if (!std::strcmp(name, "max_rounds")) {
             if (v < 0 || v > kMaxMaxRounds) return -1;  // (0: back to the derived bound)
             enactor.max_rounds = v;
-        } else if (!std::strcmp(name, "loop_max_list")) {
-            if (v < 0) return -1;
-            enactor.loop_max_list = v;
-        } else if (!std::strcmp(name, "loop_max_entries")) {
-            if (v < 0) return -1;
-            enactor.loop_max_entries = v;
         } else {
             return 1;
         }
@@ -105,8 +95,8 @@ struct MatchingRunnerT : MatchingRunner {
         out[2] = enactor.loop_rounds;
         out[3] = enactor.entries_read;
         out[4] = enactor.polls;
-        out[5] = enactor.launches;
-        kernel_ms = enactor.kernel_ms;
+        out[5] = enactor.step.launches;
+        kernel_ms = enactor.step.kernel_ms;
         build_ms = problem.build_ms;
     }
     int RoundTrace(int max_steps, int *kind, long long *rounds, long long *list, long long *matched) override

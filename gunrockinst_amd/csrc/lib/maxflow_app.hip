@@ -63,14 +63,10 @@ struct MaxflowRunnerT : MaxflowRunner {
     int SetOption(const char *name, double value) override
     {
         if (!(value == value)) return -1;  // (NaN)
-        const long long v = value >= 9.0e18 ? LLONG_MAX : (value <= -9.0e18 ? LLONG_MIN : static_cast<long long>(value));
-        if (!std::strcmp(name, "schedule")) {
-            if (v < MAXFLOW_AUTO || v > MAXFLOW_DEVICE_LOOP) return -1;
-            enactor.schedule = static_cast<int>(v);
-        } else if (!std::strcmp(name, "wave_min_row")) {
-            if (v < 1) return -1;
-            enactor.wave_min_row = static_cast<int>(v < (1 << 30) ? v : (1 << 30));
-        } else if (!std::strcmp(name, "discharge_steps")) {
+        const int shared = enactor.loop.Set(name, value, MAXFLOW_DEVICE_LOOP);
+        if (shared != 1) return shared;
+        const long long v = LoopOptions::Whole(value);
+        if (!std::strcmp(name, "discharge_steps")) {
             if (v < 1 || v > 1024) return -1;
             enactor.discharge_steps = static_cast<int>(v);
         } else if (!std::strcmp(name, "relabel_interval")) {
@@ -79,12 +75,6 @@ struct MaxflowRunnerT : MaxflowRunner {
         } else if (!std::strcmp(name, "max_rounds")) {
             if (v < 1 || v > kMaxMaxRounds) return -1;
             enactor.max_rounds = v;
-        } else if (!std::strcmp(name, "loop_max_list")) {
-            if (v < 0) return -1;
-            enactor.loop_max_list = v;
-        } else if (!std::strcmp(name, "loop_max_entries")) {
-            if (v < 0) return -1;
-            enactor.loop_max_entries = v;
         } else {
             return 1;
         }
@@ -112,9 +102,9 @@ struct MaxflowRunnerT : MaxflowRunner {
         out[3] = enactor.pushes;
         out[4] = enactor.relabels;
         out[5] = enactor.entries_read;
-        out[6] = enactor.launches;
-        out[7] = enactor.readbacks;
-        kernel_ms = enactor.kernel_ms;
+        out[6] = enactor.step.launches;
+        out[7] = enactor.step.readbacks;
+        kernel_ms = enactor.step.kernel_ms;
         build_ms = problem.build_ms;
     }
     int PhaseTrace(int max_phases, int *kind, long long *rounds, double *ms) override

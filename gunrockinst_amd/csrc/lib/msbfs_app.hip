@@ -111,8 +111,8 @@ struct MsbfsRunnerT : MsbfsRunner {
         out[2] = enactor.push_levels;
         out[3] = enactor.pull_levels;
         out[4] = enactor.entries_read;
-        out[5] = enactor.launches;
-        kernel_ms = enactor.kernel_ms;
+        out[5] = enactor.step.launches;
+        kernel_ms = enactor.step.kernel_ms;
         build_ms = problem.build_ms;
     }
     int LevelTrace(int max_levels, int *batch, int *level, int *kind, long long *frontier, long long *edges, double *ms) override

@@ -62,11 +62,10 @@ struct SccRunnerT : SccRunner {
     }
     int SetOption(const char *name, double value) override
     {
-        const long long v = static_cast<long long>(value);
-        if (!std::strcmp(name, "schedule")) {
-            if (v < SCC_AUTO || v > SCC_DEVICE_LOOP) return -1;
-            enactor.schedule = static_cast<int>(v);
-        } else if (!std::strcmp(name, "pivot_phase")) {
+        const int shared = enactor.loop.Set(name, value, SCC_DEVICE_LOOP);
+        if (shared != 1) return shared;
+        const long long v = LoopOptions::Whole(value);
+        if (!std::strcmp(name, "pivot_phase")) {
             if (v < 0 || v > 1) return -1;
             enactor.pivot_phase = static_cast<int>(v);
         } else if (!std::strcmp(name, "trim")) {
@@ -75,15 +74,6 @@ struct SccRunnerT : SccRunner {
         } else if (!std::strcmp(name, "pair_trim")) {
             if (v < 0 || v > 1) return -1;
             enactor.pair_trim = static_cast<int>(v);
-        } else if (!std::strcmp(name, "wave_min_row")) {
-            if (v < 1) return -1;
-            enactor.wave_min_row = static_cast<int>(v < (1 << 30) ? v : (1 << 30));
-        } else if (!std::strcmp(name, "loop_max_list")) {
-            if (v < 0) return -1;
-            enactor.loop_max_list = v;
-        } else if (!std::strcmp(name, "loop_max_entries")) {
-            if (v < 0) return -1;
-            enactor.loop_max_entries = v;
         } else {
             return 1;
         }
@@ -104,8 +94,8 @@ struct SccRunnerT : SccRunner {
         out[4] = enactor.sweeps;
         out[5] = enactor.bfs_levels;
         out[6] = enactor.entries_read;
-        out[7] = enactor.launches;
-        kernel_ms = enactor.kernel_ms;
+        out[7] = enactor.step.launches;
+        kernel_ms = enactor.step.kernel_ms;
         build_ms = problem.build_ms;
     }
     int PhaseTrace(int max_phases, int *kind, long long *vertices, double *ms) override

@@ -50,35 +50,19 @@ struct TrussRunnerT : TrussRunner {
     }
     int Init(const Csr<int, int, int> &g) override
     {
-        problem.wave_min_row = enactor.wave_min_row;
+        problem.wave_min_row = enactor.loop.wave_min_row;
         const hipError_t rc = problem.Init(false, g, 1);
         return state.AdmitCode(rc, problem.malformed != 0);
     }
     int InitDevice(int nodes, int edges, int *d_ro, int *d_ci) override
     {
-        problem.wave_min_row = enactor.wave_min_row;
+        problem.wave_min_row = enactor.loop.wave_min_row;
         const hipError_t rc = problem.InitFromDevice(nodes, edges, d_ro, d_ci);
         return state.AdmitCode(rc, problem.malformed != 0);
     }
     int SetOption(const char *name, double value) override
     {
-        const long long v = static_cast<long long>(value);
-        if (!std::strcmp(name, "schedule")) {
-            if (v < TRUSS_AUTO || v > TRUSS_ROUNDS) return -1;
-            enactor.schedule = static_cast<int>(v);
-        } else if (!std::strcmp(name, "wave_min_row")) {
-            if (v < 1) return -1;
-            enactor.wave_min_row = static_cast<int>(v < (1 << 30) ? v : (1 << 30));
-        } else if (!std::strcmp(name, "loop_max_list")) {
-            if (v < 0) return -1;
-            enactor.loop_max_list = v;
-        } else if (!std::strcmp(name, "loop_max_entries")) {
-            if (v < 0) return -1;
-            enactor.loop_max_entries = v;
-        } else {
-            return 1;
-        }
-        return 0;
+        return enactor.loop.Set(name, value, TRUSS_ROUNDS);  // (no option of its own, and no DEVICE_LOOP schedule)
     }
     hipError_t Reset() override { return state.ready ? problem.Reset() : hipErrorNotReady; }
     hipError_t Enact(int k_limit, int max_grid_size, float *ms) override
@@ -96,9 +80,9 @@ struct TrussRunnerT : TrussRunner {
         out[5] = enactor.edges_peeled;
         out[6] = problem.support_entries;
         out[7] = enactor.entries_read;
-        out[8] = enactor.launches;
-        out[9] = enactor.readbacks;
-        ms[0] = enactor.kernel_ms;
+        out[8] = enactor.step.launches;
+        out[9] = enactor.step.readbacks;
+        ms[0] = enactor.step.kernel_ms;
         ms[1] = problem.build_ms;
         ms[2] = problem.support_ms;
     }
