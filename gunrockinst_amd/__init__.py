@@ -1,4 +1,4 @@
-"""gunrockinst_amd -- MI355X-native frontier engine (BFS / CC / SSSP / BC / PageRank / TopK / MST / MIS / TC / k-core / k-truss / SCC / MS-BFS / BCC / max-flow / matching / k-cliques / label propagation) behind Gunrock's C ABI.
+"""gunrockinst_amd -- MI355X-native frontier engine (BFS / CC / SSSP / BC / PageRank / TopK / MST / MIS / TC / k-core / k-truss / SCC / MS-BFS / BCC / max-flow / matching / k-cliques / label propagation / 4-cycles) behind Gunrock's C ABI.
 
 The product is the shared library ``gunrockinst_amd/lib/libgunrock.so`` (hand-written HIP for gfx950,
 built by ``gunrockinst_amd/csrc/Makefile``).  This package is only the host-side binding: ctypes
@@ -28,6 +28,7 @@ from .capi import (  # noqa: F401
     CliqueProblem, CliqueOverflow, gunrock_cliques, CLIQUE_AUTO, CLIQUE_BITMAP, CLIQUE_LIST, CLIQUE_OVERFLOW,
     LpProblem, gunrock_label_propagation, modularity_from_sums, LP_SYNC, LP_CLASSES, LP_AUTO, LP_LANE, LP_WAVE, LP_BLOCK,
     LP_CONVERGED, LP_PERIOD2, LP_CAPPED, LP_BAD_CLASSES,
+    C4Problem, C4Overflow, gunrock_four_cycles, gunrock_edge_four_cycles, C4_AUTO, C4_LANE, C4_WAVE, C4_BLOCK, C4_GLOBAL, C4_OVERFLOW,
     advance_frontier, advance_queue, advance_reduce,
 )
 
@@ -52,5 +53,7 @@ __all__ = [
     "CliqueProblem", "CliqueOverflow", "gunrock_cliques", "CLIQUE_AUTO", "CLIQUE_BITMAP", "CLIQUE_LIST", "CLIQUE_OVERFLOW",
     "LpProblem", "gunrock_label_propagation", "modularity_from_sums", "LP_SYNC", "LP_CLASSES", "LP_AUTO", "LP_LANE", "LP_WAVE", "LP_BLOCK",
     "LP_CONVERGED", "LP_PERIOD2", "LP_CAPPED", "LP_BAD_CLASSES",
+    "C4Problem", "C4Overflow", "gunrock_four_cycles", "gunrock_edge_four_cycles", "C4_AUTO", "C4_LANE", "C4_WAVE", "C4_BLOCK", "C4_GLOBAL",
+    "C4_OVERFLOW",
     "advance_frontier", "advance_queue", "advance_reduce",
 ]

@@ -278,6 +278,19 @@ _SIGNATURES = {
     "grx_clique_extract": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "grx_clique_device_results": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "grx_clique_destroy": (None, [C.c_void_p]),
+    "grx_c4_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int]),
+    "grx_c4_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p]),
+    "grx_c4_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "grx_c4_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
+    "grx_c4_reset": (C.c_int, [C.c_void_p]),
+    "grx_c4_enact": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
+    "grx_c4_stats": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_longlong)] * 5 + [C.POINTER(C.c_double), C.POINTER(C.c_longlong)]
+                     + [C.POINTER(C.c_double)] * 2),
+    "grx_c4_extract": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "grx_c4_edges": (C.c_int, [C.c_void_p, i32p, i32p]),
+    "grx_c4_extract_edges": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
+    "grx_c4_device_results": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 4),
+    "grx_c4_destroy": (None, [C.c_void_p]),
     "grx_lp_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int]),
     "grx_lp_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p, i32p]),
     "grx_lp_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -1948,6 +1961,127 @@ def gunrock_cliques(nodes, row_offsets, col_indices, k, rank=None, device=0):
     """One-shot k-clique counting, k = 3 .. 6: returns (cliques int64 per vertex, the number of k-cliques)."""
     return _one_shot(CliqueProblem(device=device).init(nodes, row_offsets, col_indices, rank), CliqueProblem.reset,
                      lambda p: p.enact(k), CliqueProblem.extract)
+
+
+C4_AUTO, C4_LANE, C4_WAVE, C4_BLOCK, C4_GLOBAL = 0, 1, 2, 3, 4  # enum GRX_C4_* (gunrock_mi355x.h): option "strategy"
+C4_OVERFLOW = -7  # grx_c4_enact: the bound on the counts reached "count_limit"
+
+
+class C4Overflow(ArithmeticError):
+    """C4Problem.enact: sum over u of W(u) (dlow(u) - 1) / 2 reached "count_limit" (GRX_C4_OVERFLOW): nothing ran, the handle holds no
+    result and takes the next enact"""
+
+
+class C4Problem(_Handle):
+    """C4Problem + C4Enactor behind the handle C ABI: the 4-cycles (butterflies) through every vertex and every edge (int64, the edges
+    in the canonical order: (a, b) with a < b, sorted) and their total, of the CSR read as an undirected simple graph."""
+
+    _destroy = "grx_c4_destroy"
+
+    _REGIMES = ("lane", "wave", "block", "global")
+
+    def __init__(self, instrument=False, device=0):
+        self._create("grx_c4_create", int(instrument), device)
+        self.nodes = 0
+        self.entries = 0
+        self.simple_edges = 0
+
+    def _ready(self):
+        m = lib().grx_c4_edges(self._h, None, None)
+        if m < 0:
+            _check(-m, "C4Problem::Edges")
+        self.simple_edges = int(m)
+
+    def init(self, nodes, row_offsets, col_indices):
+        ro, ci = _csr_arrays(row_offsets, col_indices, nodes)
+        self.nodes, self.entries = int(nodes), int(ci.shape[0])
+        _check(lib().grx_c4_init(self._h, self.nodes, self.entries, _p(ro), _p(ci)), "C4Problem::Init")
+        self._ready()
+        return self
+
+    def init_device(self, nodes, edges, d_row_offsets, d_col_indices):
+        """the CSR stays the caller's; the build reads it, nothing later does"""
+        self.nodes, self.entries = int(nodes), int(edges)
+        _check(lib().grx_c4_init_device(self._h, self.nodes, self.entries, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices)),
+               "C4Problem::Init(device)")
+        self._ready()
+        return self
+
+    def set_option(self, name, value):
+        """"strategy" (C4_AUTO / C4_LANE / C4_WAVE / C4_BLOCK / C4_GLOBAL), "lane_max_wedges", "table_slots", "block_slots",
+        "scratch_mib", "edges", "count_limit"; returns the library's code: 0 = set, 1 = unknown name (a value out of range raises)"""
+        rc = lib().grx_c4_set_option(self._h, name.encode(), float(value))
+        if rc not in (0, 1):
+            _check(rc, "grx_c4_set_option(%s)" % name)
+        return rc
+
+    def reset(self):
+        _check(lib().grx_c4_reset(self._h), "C4Problem::Reset")
+
+    def enact(self, max_grid_size=0):
+        """the elapsed milliseconds; C4Overflow when the bound on the counts reached the option count_limit"""
+        ms = C.c_float()
+        rc = lib().grx_c4_enact(self._h, int(max_grid_size), C.byref(ms))
+        if rc == C4_OVERFLOW:
+            raise C4Overflow("gunrockinst_amd: C4Enactor::Enact refused: the bound %.17g reached count_limit (code %d)"
+                             % (self.stats()["bound"], rc))
+        _check(rc, "C4Enactor::Enact")
+        return float(ms.value)
+
+    def stats(self):
+        m, w, probes, n = (C.c_longlong() for _ in range(4))
+        vertices, wedges = (C.c_longlong * 4)(), (C.c_longlong * 4)()
+        bound, k, b = C.c_double(), C.c_double(), C.c_double()
+        _check(lib().grx_c4_stats(self._h, C.byref(m), C.byref(w), vertices, wedges, C.byref(probes), C.byref(bound), C.byref(n), C.byref(k),
+                                  C.byref(b)), "grx_c4_stats")
+        out = {"simple_edges": m.value, "wedges": w.value, "table_probes": probes.value, "bound": bound.value, "kernel_launches": n.value,
+               "kernel_ms": k.value, "build_ms": b.value}
+        for i, name in enumerate(self._REGIMES):
+            out[name + "_vertices"], out[name + "_wedges"] = int(vertices[i]), int(wedges[i])
+        return out
+
+    def extract(self, cycles=True):
+        """(4-cycles as int64 per vertex, or None; the 4-cycles of the graph)"""
+        out = np.empty(max(self.nodes, 1), dtype=np.int64) if cycles else None
+        total = C.c_longlong()
+        _check(lib().grx_c4_extract(self._h, None if out is None else _i64p(out), C.byref(total)), "C4Problem::Extract")
+        return (None if out is None else out[:self.nodes]), int(total.value)
+
+    def edges(self):
+        """the canonical edges (src, dst) as int32, src < dst, sorted by (src, dst)"""
+        src, dst = (np.empty(max(self.simple_edges, 1), dtype=np.int32) for _ in range(2))
+        m = lib().grx_c4_edges(self._h, _p(src), _p(dst))
+        if m < 0:
+            _check(-m, "C4Problem::Edges")
+        return src[:m], dst[:m]
+
+    def extract_edges(self):
+        """4-cycles as int64 per canonical edge; refused (code -1) when the last enact ran with the option edges = 0"""
+        out = np.empty(max(self.simple_edges, 1), dtype=np.int64)
+        _check(lib().grx_c4_extract_edges(self._h, _i64p(out)), "C4Problem::ExtractEdges")
+        return out[:self.simple_edges]
+
+    def device_results(self):
+        """device pointers {"cycles", "edge_cycles": int64 per vertex and per canonical edge; "src", "dst": int32 per edge}"""
+        names = ("cycles", "edge_cycles", "src", "dst")
+        p = [C.c_void_p() for _ in names]
+        _check(lib().grx_c4_device_results(self._h, *[C.byref(x) for x in p]), "grx_c4_device_results")
+        return {name: x.value for name, x in zip(names, p)}
+
+
+def gunrock_four_cycles(nodes, row_offsets, col_indices, device=0):
+    """One-shot 4-cycle (butterfly) counting per vertex: returns (cycles int64 per vertex, the 4-cycles of the graph)."""
+    def prepare(p):
+        p.set_option("edges", 0)
+        p.reset()
+    return _one_shot(C4Problem(device=device).init(nodes, row_offsets, col_indices), prepare, C4Problem.enact, C4Problem.extract)
+
+
+def gunrock_edge_four_cycles(nodes, row_offsets, col_indices, device=0):
+    """One-shot 4-cycle (butterfly) counting per edge: returns (src, dst, edge_cycles int64 per canonical edge, the 4-cycles of the
+    graph)."""
+    return _one_shot(C4Problem(device=device).init(nodes, row_offsets, col_indices), C4Problem.reset, C4Problem.enact,
+                     lambda p: p.edges() + (p.extract_edges(), p.extract(cycles=False)[1]))
 
 
 LP_SYNC, LP_CLASSES = 0, 1  # enum GRX_LP_* (gunrock_mi355x.h): option "mode"

@@ -967,6 +967,69 @@ int grx_clique_device_results(grx_clique *p, long long **d_cliques, int **d_degr
 void grx_clique_destroy(grx_clique *p);
 
 /* ------------------------------------------------------------------------------------------------
+ * C4: C4Problem + C4Enactor: 4-cycle (butterfly) counts per vertex, per edge and in total (no counterpart in the reference
+ * snapshot).  The CSR is read exactly as grx_tc_* / grx_clique_* read it, as the simple undirected graph G: u and v are neighbours
+ * when either row holds the other, self-loops are ignored, rows may be unsorted and may hold duplicates and one-way entries.  A
+ * 4-cycle is four distinct vertices a, b, c, d with the edges ab, bc, cd, da, counted as a subgraph (chords allowed: K_4 holds
+ * three).  Every result has one value:
+ *   cycles[v]       the 4-cycles through vertex v (int64, `nodes` entries)
+ *   edge_cycles[e]  the 4-cycles through edge e (int64), in the canonical edge order of grx_c4_edges, which is grx_truss_edges': (a, b)
+ *                   with a < b, sorted
+ *   total           the 4-cycles of G (int64); sum(cycles) = sum(edge_cycles) = 4 * total
+ * Init ranks the vertices by (degree, id) and renumbers the neighbour CSR by rank.  A 4-cycle is counted at its highest-ranked
+ * vertex u as a pair of wedges u - v - w (v and w below u) with the same end w; W(u) is the number of wedges of u.  Enact counts a
+ * start vertex in one of four regimes by W(u): by one lane, by a wave or a workgroup with an end -> count table in LDS, or by a
+ * workgroup with a dense counter row in global scratch.
+ * Counts never wrap: Enact refuses (GRX_C4_OVERFLOW) when sum over u of W(u) (dlow(u) - 1) / 2 (dlow: the neighbours of u below it), a
+ * float64 computed on the device that is at least `total` and every single count, reaches "count_limit".
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct grx_c4 grx_c4;
+enum { GRX_C4_AUTO = 0, GRX_C4_LANE = 1, GRX_C4_WAVE = 2, GRX_C4_BLOCK = 3, GRX_C4_GLOBAL = 4 };  /* option "strategy" */
+enum { GRX_C4_OVERFLOW = -7 };  /* next to -1 / -2 / -3; the value of GRX_CLIQUE_OVERFLOW */
+
+int grx_c4_create(grx_c4 **out, int instrument, int device);
+/* C4Problem::Init: validates the CSR and builds the canonical pairs and the rank-renumbered graph on the device.  -1: nodes < 1,
+ * edges < 0 or a NULL array; -2: not a CSR of `nodes` vertices, as grx_tc_init; -3: the handle has been given a graph before
+ * (accepted or rejected) */
+int grx_c4_init(grx_c4 *p, int nodes, int edges, const int *row_offsets, const int *col_indices);
+/* the same for a CSR already in HBM: borrowed, not freed, read by the build only */
+int grx_c4_init_device(grx_c4 *p, int nodes, int edges, int *d_row_offsets, int *d_col_indices);
+/* named options, for the next Enact; 0: set, 1: unknown name, -1: a value out of range.  None changes a count.
+ *   "strategy"         GRX_C4_AUTO (default): every start vertex takes the smallest regime that holds its W; GRX_C4_LANE / _WAVE /
+ *                      _BLOCK / _GLOBAL: no start vertex takes a smaller regime than this one (one whose W exceeds the forced regime's
+ *                      capacity still takes the next larger one)
+ *   "lane_max_wedges"  the largest W of the LANE regime (default 16, 0 .. 32)
+ *   "table_slots"      slots of a wave's table, a power of two in 64 .. 1024 (default 1024); the WAVE regime holds W <= table_slots / 2
+ *   "block_slots"      slots of a workgroup's table, a power of two in 256 .. 8192 (default 8192, 64 KiB of LDS); the BLOCK regime
+ *                      holds W <= block_slots / 2
+ *   "scratch_mib"      the GLOBAL regime runs min(grid, scratch_mib 2^20 / (4 nodes)) workgroups, at least 1, each with a counter row
+ *                      of `nodes` int32 in global scratch (default 1024, 1 .. 65536)
+ *   "edges"            1 (default): edge_cycles[] is counted too; 0: it is neither counted nor allocated
+ *   "count_limit"      Enact refuses when the bound reaches it (default and at most 2^62, at least 1); changes refusals only */
+int grx_c4_set_option(grx_c4 *p, const char *name, double value);
+/* C4Problem::Reset: the counts to zero */
+int grx_c4_reset(grx_c4 *p);
+/* C4Enactor::Enact(problem, max_grid_size), HIP-event timed.  Without a Reset since the last Enact it resets itself.
+ * GRX_C4_OVERFLOW: the bound reached "count_limit"; no kernel ran, the handle holds no result and takes the next Enact */
+int grx_c4_enact(grx_c4 *p, int max_grid_size, float *elapsed_ms);
+/* any pointer may be NULL.  The edges (M) and the wedges (the sum of W) of the graph; of the last Enact: the start vertices (W >= 2)
+ * and their wedges per regime (regime_vertices[4], regime_wedges[4]: lane, wave, workgroup, global), the table probes of the wave and
+ * workgroup regimes, kernel launches and -- when instrumented -- the summed kernel time; the bound; build_ms: the HIP-event time of
+ * Init's build */
+int grx_c4_stats(grx_c4 *p, long long *simple_edges, long long *wedges, long long *regime_vertices, long long *regime_wedges, long long *table_probes,
+                 double *bound, long long *kernel_launches, double *kernel_ms, double *build_ms);
+/* Before a finished Enact (none yet, a Reset since, or a refused one): hipErrorNotReady */
+int grx_c4_extract(grx_c4 *p, long long *h_cycles /* may be NULL */, long long *total);
+/* the canonical edges after Init: M int32 each, either may be NULL; returns M, or -(hipError_t) */
+int grx_c4_edges(grx_c4 *p, int *h_src, int *h_dst);
+/* M int64.  Before a finished Enact: hipErrorNotReady; -1 when that Enact ran with "edges" = 0 */
+int grx_c4_extract_edges(grx_c4 *p, long long *h_edge_cycles);
+/* device arrays of the handle: cycles (`nodes` int64), edge_cycles (M int64; NULL unless the last Enact finished with "edges" = 1),
+ * the canonical pairs (M int32 each; NULL without an edge) */
+int grx_c4_device_results(grx_c4 *p, long long **d_cycles, long long **d_edge_cycles, int **d_src, int **d_dst);
+void grx_c4_destroy(grx_c4 *p);
+
+/* ------------------------------------------------------------------------------------------------
  * LP: LpProblem + LpEnactor: label-propagation communities with integer scores and a total tie rule (no counterpart in the
  * reference snapshot).  The CSR is read exactly as grx_matching_* reads it, as the simple undirected graph G with int32 weights
  * (NULL: 1 each; a pair's weight is the largest of its entries in both directions); a pair weight below 1 is refused.  L[v] is an
