@@ -291,6 +291,16 @@ _SIGNATURES = {
     "grx_c4_extract_edges": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
     "grx_c4_device_results": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 4),
     "grx_c4_destroy": (None, [C.c_void_p]),
+    "grx_rw_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int]),
+    "grx_rw_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p, i32p]),
+    "grx_rw_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "grx_rw_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
+    "grx_rw_reset": (C.c_int, [C.c_void_p, C.c_int, i32p]),
+    "grx_rw_enact": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
+    "grx_rw_stats": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_longlong)] * 6 + [C.POINTER(C.c_double)] * 2),
+    "grx_rw_extract": (C.c_int, [C.c_void_p, i32p, i32p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "grx_rw_device_results": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 3 + [C.POINTER(C.c_longlong)]),
+    "grx_rw_destroy": (None, [C.c_void_p]),
     "grx_lp_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int]),
     "grx_lp_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p, i32p]),
     "grx_lp_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -2082,6 +2092,127 @@ def gunrock_edge_four_cycles(nodes, row_offsets, col_indices, device=0):
     graph)."""
     return _one_shot(C4Problem(device=device).init(nodes, row_offsets, col_indices), C4Problem.reset, C4Problem.enact,
                      lambda p: p.edges() + (p.extract_edges(), p.extract(cycles=False)[1]))
+
+
+RW_AUTO, RW_LANE, RW_TILE = 0, 1, 2  # enum GRX_RW_* (gunrock_mi355x.h): option "strategy"
+
+
+def rw_draw(seed, walk, step, t):
+    """The draws of grx_rw_*: Mix(seed ^ Mix((walk << 32) | (step << 8) | t)) as uint64, Mix the splitmix64 finaliser
+    (devgraph._splitmix64).  Host helper; the arguments may be arrays (walk < 2^31, step < 2^24, t < 2^8)."""
+    def mix(x):
+        x = x + np.uint64(0x9E3779B97F4A7C15)
+        x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return x ^ (x >> np.uint64(31))
+    seed, walk, step, t = (np.asarray(a).astype(np.uint64) for a in (seed, walk, step, t))
+    with np.errstate(over="ignore"):
+        out = mix(seed ^ mix((walk << np.uint64(32)) | (step << np.uint64(8)) | t))
+    return out if out.ndim else np.uint64(out)
+
+
+class RwProblem(_Handle):
+    """RwProblem + RwEnactor behind the handle C ABI: uniform, weighted and node2vec-biased random walks on the CSR as given (directed,
+    self-loops and duplicates kept).  Every draw is rw_draw(seed, walk, step, try) and every choice exact integer arithmetic on it
+    (gunrock_mi355x.h has the definition), so the walks are integers with one value: no option but "length", "seed", "weighted",
+    the biases and "tries" changes them."""
+
+    _destroy = "grx_rw_destroy"
+
+    def __init__(self, instrument=False, device=0):
+        self._create("grx_rw_create", int(instrument), device)
+        self.nodes = 0
+        self.entries = 0
+        self.num_walks = 0
+        self.length = 0  # of the last enact
+        self._length = 0  # the option
+
+    def init(self, nodes, row_offsets, col_indices, weights=None):
+        ro, ci = _csr_arrays(row_offsets, col_indices, nodes)
+        w = None if weights is None else _i32(weights)
+        if w is not None and w.shape[0] != ci.shape[0]:
+            raise ValueError("gunrockinst_amd: %d weights for %d entries" % (w.shape[0], ci.shape[0]))
+        self.nodes, self.entries = int(nodes), int(ci.shape[0])
+        _check(lib().grx_rw_init(self._h, self.nodes, self.entries, _p(ro), _p(ci), None if w is None else _p(w)), "RwProblem::Init")
+        return self
+
+    def init_device(self, nodes, edges, d_row_offsets, d_col_indices, d_weights=None):
+        """the CSR (and the weights) stay the caller's; the build reads them, nothing later does"""
+        self.nodes, self.entries = int(nodes), int(edges)
+        _check(lib().grx_rw_init_device(self._h, self.nodes, self.entries, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices),
+                                        C.c_void_p(d_weights)), "RwProblem::Init(device)")
+        return self
+
+    def set_option(self, name, value):
+        """"strategy" (RW_AUTO / RW_LANE / RW_TILE), "length", "seed", "weighted", "bias_return", "bias_in", "bias_out", "tries",
+        "visits"; returns the library's code: 0 = set, 1 = unknown name (a value out of range raises)"""
+        rc = lib().grx_rw_set_option(self._h, name.encode(), float(value))
+        if rc not in (0, 1):
+            _check(rc, "grx_rw_set_option(%s)" % name)
+        if rc == 0 and name == "length":
+            self._length = int(value)
+        return rc
+
+    def reset(self, starts):
+        """the start vertices, one walk each"""
+        s = _i32(starts).reshape(-1)
+        _check(lib().grx_rw_reset(self._h, int(s.shape[0]), _p(s)), "RwProblem::Reset")
+        self.num_walks = int(s.shape[0])
+
+    def enact(self, max_grid_size=0):
+        """the elapsed milliseconds"""
+        ms = self._timed(lib().grx_rw_enact, "RwEnactor::Enact", int(max_grid_size))
+        self.length = self._length
+        return ms
+
+    def stats(self):
+        w, s, e, t, f, n = (C.c_longlong() for _ in range(6))
+        k, b = C.c_double(), C.c_double()
+        _check(lib().grx_rw_stats(self._h, *[C.byref(x) for x in (w, s, e, t, f, n, k, b)]), "grx_rw_stats")
+        return {"walks": w.value, "steps": s.value, "ended_early": e.value, "biased_tries": t.value, "forced_fallbacks": f.value,
+                "kernel_launches": n.value, "kernel_ms": k.value, "build_ms": b.value}
+
+    def extract(self, walks=True, lengths=True, visits=False):
+        """(walks int32 num_walks x (length + 1), lengths int32, visits int64 per vertex, steps); None for what was not asked for"""
+        out_w = np.empty((max(self.num_walks, 1), self.length + 1), dtype=np.int32) if walks else None
+        out_l = np.empty(max(self.num_walks, 1), dtype=np.int32) if lengths else None
+        out_v = np.empty(max(self.nodes, 1), dtype=np.int64) if visits else None
+        steps = C.c_longlong()
+        _check(lib().grx_rw_extract(self._h, None if out_w is None else _p(out_w), None if out_l is None else _p(out_l),
+                                    None if out_v is None else _i64p(out_v), C.byref(steps)), "RwProblem::Extract")
+        return (None if out_w is None else out_w[:self.num_walks], None if out_l is None else out_l[:self.num_walks],
+                None if out_v is None else out_v[:self.nodes], int(steps.value))
+
+    def device_results(self):
+        """device pointers {"walks": int32, rows "pitch" entries apart; "lengths": int32 per walk; "visits": int64 per vertex or None}
+        and "pitch" """
+        names = ("walks", "lengths", "visits")
+        p = [C.c_void_p() for _ in names]
+        pitch = C.c_longlong()
+        _check(lib().grx_rw_device_results(self._h, *([C.byref(x) for x in p] + [C.byref(pitch)])), "grx_rw_device_results")
+        out = {name: x.value for name, x in zip(names, p)}
+        out["pitch"] = int(pitch.value)
+        return out
+
+
+def gunrock_random_walks(nodes, row_offsets, col_indices, starts, length, weights=None, seed=0, bias=None, tries=32, visits=False, device=0):
+    """One-shot random walks, one from every vertex of `starts`: returns (walks int32 len(starts) x (length + 1), -1 behind the end of
+    a walk; lengths int32), and the visits (int64 per vertex) when asked for.  With `weights` (int32 >= 0 per entry) the steps are
+    weighted; `bias` is a (return, in, out) triple of integers in 0 .. 65535, node2vec's 1/p, 1 and 1/q scaled to integers."""
+    def prepare(p):
+        p.set_option("length", length)
+        p.set_option("seed", seed)
+        p.set_option("weighted", 0 if weights is None else 1)
+        for name, b in zip(("bias_return", "bias_in", "bias_out"), (1, 1, 1) if bias is None else bias):
+            p.set_option(name, b)
+        p.set_option("tries", tries)
+        p.set_option("visits", 1 if visits else 0)
+        p.reset(starts)
+
+    def result(p):
+        w, l, v, _ = p.extract(visits=bool(visits))
+        return (w, l, v) if visits else (w, l)
+    return _one_shot(RwProblem(device=device).init(nodes, row_offsets, col_indices, weights), prepare, RwProblem.enact, result)
 
 
 LP_SYNC, LP_CLASSES = 0, 1  # enum GRX_LP_* (gunrock_mi355x.h): option "mode"

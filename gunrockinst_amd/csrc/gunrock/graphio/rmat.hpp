@@ -12,6 +12,7 @@
 #include <cstdlib>
 
 #include <gunrock/csr.hpp>
+#include <gunrock/graphio/splitmix.hpp>
 #include <gunrock/graphio/utils.hpp>
 
 namespace gunrock {
@@ -51,13 +52,7 @@ int BuildRmatGraph(SizeT nodes, SizeT edges, Csr<VertexId, Value, SizeT> &graph,
 
 // ---- seeded counter-based stream (shared spec with the device generator and the test oracle) ----
 struct SeededRmat {
-    static inline uint64_t Mix(uint64_t x)
-    {
-        x += 0x9E3779B97F4A7C15ull;
-        x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-        x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-        return x ^ (x >> 31);
-    }
+    static inline uint64_t Mix(uint64_t x) { return Mix64(x); }  // (splitmix.hpp)
     static inline uint64_t Draw(uint64_t seed, uint64_t edge, unsigned level, unsigned k)
     {
         return Mix(seed ^ Mix((edge << 10) | (uint64_t(level) << 4) | k));

@@ -10,18 +10,13 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include <gunrock/graphio/splitmix.hpp>
 #include <gunrock/util/error_utils.hpp>
 
 namespace gunrock {
 namespace graphio {
 
-__device__ __forceinline__ uint64_t RmatMix(uint64_t x)
-{
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
+__device__ __forceinline__ uint64_t RmatMix(uint64_t x) { return Mix64(x); }  // (splitmix.hpp)
 __device__ __forceinline__ uint64_t RmatDraw(uint64_t seed, uint64_t edge, unsigned level, unsigned k)
 {
     return RmatMix(seed ^ RmatMix((edge << 10) | (uint64_t(level) << 4) | k));

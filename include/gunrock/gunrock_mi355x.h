@@ -1030,6 +1030,69 @@ int grx_c4_device_results(grx_c4 *p, long long **d_cycles, long long **d_edge_cy
 void grx_c4_destroy(grx_c4 *p);
 
 /* ------------------------------------------------------------------------------------------------
+ * RW: RwProblem + RwEnactor: random walks -- uniform, weighted and node2vec-biased (no counterpart in the reference snapshot).
+ * Every draw is a fixed hash of (seed, walk, step, try) and every choice is exact integer arithmetic on it, so every output is an
+ * integer with one value, whatever the grid, the strategy or the schedule.
+ *   Graph.  The CSR is taken as given: directed, with self-loops and duplicate entries kept (a duplicate arc is twice as likely).
+ *   Weights are optional, int32, >= 0.  Init builds its own device copy with every row sorted by (column, weight) and an inclusive
+ *   int64 prefix sum of the weights per row.  All choices index the SORTED row: the walks do not depend on the order of the entries
+ *   within a row.
+ *   Draw(seed, walk, step, t) = Mix(seed ^ Mix((walk << 32) | (step << 8) | t)), Mix the splitmix64 finaliser
+ *   (x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) * 0x94D049BB133111EB; x ^ x >> 31);
+ *   walk < 2^31, step < 2^24, t < 2^8.
+ *   First-order choice at vertex v with sorted row of d entries, given a draw r.  Unweighted: d == 0 ends the walk, otherwise
+ *   k = ((r >> 32) * d) >> 32.  Weighted: T is the row's weight total, T == 0 ends the walk, otherwise t = (r * T) >> 64 (the full
+ *   128-bit product) and k is the smallest index whose inclusive prefix exceeds t, found by bisection; zero-weight entries are never
+ *   chosen.
+ *   Step s of walk w (s = 0 .. length - 1), standing at v, having come from p (none at s = 0), with integer biases
+ *   (b_return, b_in, b_out), each in 0 .. 65535.  First-order step, taken when the three biases are equal or at s = 0: the next
+ *   vertex is the first-order choice with Draw(seed, w, s, 0).  Biased step, otherwise: amax is the largest of the three biases; for
+ *   j = 0 .. tries - 1 the candidate x is the first-order choice with Draw(seed, w, s, 2j), its bias b is b_return if x == p, b_in
+ *   if x occurs in the sorted out-row of p (bisection), else b_out, and it is accepted if
+ *   ((Draw(seed, w, s, 2j + 1) >> 32) * amax) >> 32 < b.  If no try accepts, the candidate of the last try is taken.
+ *   Outputs.  walks: int32, num_walks x (length + 1), row w starts with starts[w], and after a walk ends its row is filled with -1;
+ *   lengths: int32 per walk, the number of vertices in the row; visits: int64 per vertex, the number of times it occurs in walks
+ *   (only with "visits" = 1); steps: the total number of steps taken.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct grx_rw grx_rw;
+enum { GRX_RW_AUTO = 0, GRX_RW_LANE = 1, GRX_RW_TILE = 2 };  /* option "strategy" */
+
+int grx_rw_create(grx_rw **out, int instrument, int device);
+/* RwProblem::Init: validates the CSR and builds the sorted copy on the device.  weights may be NULL.  -1: nodes < 1, edges < 0 or a
+ * NULL array; -2: offsets or columns that are not a CSR of `nodes` vertices, or a negative weight; -3: the handle took a graph */
+int grx_rw_init(grx_rw *p, int nodes, int edges, const int *row_offsets, const int *col_indices, const int *weights);
+/* the same for a CSR (and weights, or NULL) in device memory: borrowed, and read only by the build */
+int grx_rw_init_device(grx_rw *p, int nodes, int edges, int *d_row_offsets, int *d_col_indices, int *d_weights);
+/* 0: set, 1: unknown name, -1: a value out of range
+ *   "strategy"     GRX_RW_AUTO (default): by "length"; GRX_RW_LANE: every lane stores each vertex of its walk; GRX_RW_TILE: a wave
+ *                  stages 64 walkers x 16 steps in LDS and writes whole 64-byte segments.  Never changes a result.
+ *   "length"       0 .. 2^24 - 1 (default 0): the steps of a walk
+ *   "seed"         an integer in [0, 2^53) (default 0)
+ *   "weighted"     0 (default) or 1; 1 on a handle whose Init had no weights is -1
+ *   "bias_return", "bias_in", "bias_out"   0 .. 65535 each (default 1)
+ *   "tries"        1 .. 128 (default 32)
+ *   "visits"       0 (default) or 1: Enact also counts the visits
+ * "length", "seed", "weighted", the biases and "tries" define the result; nothing else changes it. */
+int grx_rw_set_option(grx_rw *p, const char *name, double value);
+/* RwProblem::Reset: the start vertices, one walk each.  -1: num_walks < 1, a NULL pointer or a start vertex outside 0 .. nodes - 1 */
+int grx_rw_reset(grx_rw *p, int num_walks, const int *h_starts);
+/* RwEnactor::Enact(problem, max_grid_size), HIP-event timed: one launch walks every walk from start to end.  max_grid_size never
+ * changes a result.  Before a Reset: hipErrorNotReady */
+int grx_rw_enact(grx_rw *p, int max_grid_size, float *elapsed_ms);
+/* any pointer may be NULL.  Of the last Enact: its walks, the steps taken, the walks that ended early, the tries of the biased steps,
+ * the biased steps no try accepted (forced fallbacks), kernel launches and -- when instrumented -- the summed kernel time; build_ms:
+ * the HIP-event time of Init's build */
+int grx_rw_stats(grx_rw *p, long long *walks, long long *steps, long long *ended_early, long long *biased_tries, long long *forced_fallbacks,
+                 long long *kernel_launches, double *kernel_ms, double *build_ms);
+/* any pointer may be NULL.  h_walks: num_walks x (length + 1) int32, dense; h_lengths: num_walks int32; h_visits: `nodes` int64.
+ * Before a finished Enact: hipErrorNotReady; -1 for h_visits when the last Enact ran with "visits" = 0 */
+int grx_rw_extract(grx_rw *p, int *h_walks, int *h_lengths, long long *h_visits, long long *steps);
+/* device arrays of the handle after a finished Enact: walks (rows *walks_pitch entries apart, a multiple of 16, the first length + 1
+ * of a row written), lengths, visits (NULL unless the last Enact ran with "visits" = 1) */
+int grx_rw_device_results(grx_rw *p, int **d_walks, int **d_lengths, long long **d_visits, long long *walks_pitch);
+void grx_rw_destroy(grx_rw *p);
+
+/* ------------------------------------------------------------------------------------------------
  * LP: LpProblem + LpEnactor: label-propagation communities with integer scores and a total tie rule (no counterpart in the
  * reference snapshot).  The CSR is read exactly as grx_matching_* reads it, as the simple undirected graph G with int32 weights
  * (NULL: 1 each; a pair's weight is the largest of its entries in both directions); a pair weight below 1 is refused.  L[v] is an
