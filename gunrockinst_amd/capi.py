@@ -301,6 +301,18 @@ _SIGNATURES = {
     "grx_rw_extract": (C.c_int, [C.c_void_p, i32p, i32p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "grx_rw_device_results": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 3 + [C.POINTER(C.c_longlong)]),
     "grx_rw_destroy": (None, [C.c_void_p]),
+    "grx_sample_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int]),
+    "grx_sample_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p, i32p]),
+    "grx_sample_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "grx_sample_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
+    "grx_sample_set_fanouts": (C.c_int, [C.c_void_p, C.c_int, i32p]),
+    "grx_sample_reset": (C.c_int, [C.c_void_p, C.c_int, i32p]),
+    "grx_sample_enact": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
+    "grx_sample_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)] + [C.POINTER(C.c_longlong)] * 6 + [C.POINTER(C.c_double)] * 3),
+    "grx_sample_sizes": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_longlong)] * 4),
+    "grx_sample_extract": (C.c_int, [C.c_void_p, i32p, C.POINTER(C.c_longlong), i32p, i32p]),
+    "grx_sample_device_results": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 4),
+    "grx_sample_destroy": (None, [C.c_void_p]),
     "grx_lp_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int]),
     "grx_lp_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p, i32p]),
     "grx_lp_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -2213,6 +2225,128 @@ def gunrock_random_walks(nodes, row_offsets, col_indices, starts, length, weight
         w, l, v, _ = p.extract(visits=bool(visits))
         return (w, l, v) if visits else (w, l)
     return _one_shot(RwProblem(device=device).init(nodes, row_offsets, col_indices, weights), prepare, RwProblem.enact, result)
+
+
+SAMPLE_AUTO, SAMPLE_LANE, SAMPLE_GROUP = 0, 1, 2  # enum GRX_SAMPLE_* (gunrock_mi355x.h): option "strategy"
+SAMPLE_TOO_LARGE = -4  # grx_sample_enact: a hop would have passed "edge_limit"
+
+
+class SampleTooLarge(ArithmeticError):
+    """SampleProblem.enact: the sampled edges would have passed the option "edge_limit" (GRX_SAMPLE_TOO_LARGE): the sampler of that hop
+    did not run, the handle holds no result and takes the next reset / enact."""
+
+
+class SampleProblem(_Handle):
+    """SampleProblem + SampleEnactor behind the handle C ABI: multi-hop fanout neighbourhood samples of the CSR as given (directed,
+    self-loops and duplicates kept), renumbered to dense local ids.  Every draw is rw_draw(seed, vertex, hop, slot); without
+    replacement the picks of a row are Robert Floyd's subset over those draws (gunrock_mi355x.h has the definition), so the sample is
+    integers with one value: no option but "seed", "replace" and "weighted", the fanouts and the seeds changes it."""
+
+    _destroy = "grx_sample_destroy"
+
+    def __init__(self, instrument=False, device=0):
+        self._create("grx_sample_create", int(instrument), device)
+        self.nodes = 0
+        self.entries = 0
+        self.hops = 0
+
+    def init(self, nodes, row_offsets, col_indices, weights=None):
+        ro, ci = _csr_arrays(row_offsets, col_indices, nodes)
+        w = None if weights is None else _i32(weights)
+        if w is not None and w.shape[0] != ci.shape[0]:
+            raise ValueError("gunrockinst_amd: %d weights for %d entries" % (w.shape[0], ci.shape[0]))
+        self.nodes, self.entries = int(nodes), int(ci.shape[0])
+        _check(lib().grx_sample_init(self._h, self.nodes, self.entries, _p(ro), _p(ci), None if w is None else _p(w)), "SampleProblem::Init")
+        return self
+
+    def init_device(self, nodes, edges, d_row_offsets, d_col_indices, d_weights=None):
+        """the CSR (and the weights) stay the caller's; the build reads them, nothing later does"""
+        self.nodes, self.entries = int(nodes), int(edges)
+        _check(lib().grx_sample_init_device(self._h, self.nodes, self.entries, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices),
+                                            C.c_void_p(d_weights)), "SampleProblem::Init(device)")
+        return self
+
+    def set_option(self, name, value):
+        """"strategy" (SAMPLE_AUTO / SAMPLE_LANE / SAMPLE_GROUP), "seed", "replace", "weighted", "edge_limit", "long_row", "eids";
+        returns the library's code: 0 = set, 1 = unknown name (a value out of range raises)"""
+        rc = lib().grx_sample_set_option(self._h, name.encode(), float(value))
+        if rc not in (0, 1):
+            _check(rc, "grx_sample_set_option(%s)" % name)
+        return rc
+
+    def set_fanouts(self, fanouts):
+        """the fanout of every hop: -1 (the whole row) or 1 .. 64, for 1 .. 16 hops"""
+        f = _i32(fanouts).reshape(-1)
+        _check(lib().grx_sample_set_fanouts(self._h, int(f.shape[0]), _p(f)), "grx_sample_set_fanouts")
+        self.hops = int(f.shape[0])
+
+    def reset(self, seeds):
+        """the seeds: distinct vertices, the local ids 0 .. len(seeds) - 1"""
+        s = _i32(seeds).reshape(-1)
+        _check(lib().grx_sample_reset(self._h, int(s.shape[0]), _p(s)), "SampleProblem::Reset")
+
+    def enact(self, max_grid_size=0):
+        """the elapsed milliseconds; SampleTooLarge when a hop would have passed the option edge_limit"""
+        ms = C.c_float()
+        rc = lib().grx_sample_enact(self._h, int(max_grid_size), C.byref(ms))
+        if rc == SAMPLE_TOO_LARGE:
+            raise SampleTooLarge("gunrockinst_amd: SampleEnactor::Enact refused: the sampled edges would pass edge_limit (code %d)" % rc)
+        _check(rc, "SampleEnactor::Enact")
+        return float(ms.value)
+
+    def stats(self):
+        hops = C.c_int()
+        expanded, sampled, copied = ((C.c_longlong * 16)() for _ in range(3))
+        long_rows, n, r = (C.c_longlong() for _ in range(3))
+        k, b = C.c_double(), C.c_double()
+        phases = (C.c_double * 4)()
+        _check(lib().grx_sample_stats(self._h, C.byref(hops), expanded, sampled, copied, C.byref(long_rows), C.byref(n), C.byref(r), C.byref(k),
+                                      phases, C.byref(b)), "grx_sample_stats")
+        h = hops.value
+        out = {"rows_expanded": [int(x) for x in expanded[:h]], "rows_sampled": [int(x) for x in sampled[:h]],
+               "rows_copied": [int(x) for x in copied[:h]], "long_rows": long_rows.value, "kernel_launches": n.value, "readbacks": r.value,
+               "kernel_ms": k.value, "build_ms": b.value}
+        for name, ms in zip(("count_ms", "sample_ms", "renumber_ms", "relabel_ms"), phases):
+            out[name] = float(ms)
+        return out
+
+    def sizes(self):
+        """(V, E, vertex_ptr int64[H + 2], edge_ptr int64[H + 1]) of the last enact"""
+        v, e = C.c_longlong(), C.c_longlong()
+        vp, ep = np.zeros(self.hops + 2, dtype=np.int64), np.zeros(self.hops + 1, dtype=np.int64)
+        _check(lib().grx_sample_sizes(self._h, C.byref(v), C.byref(e), _i64p(vp), _i64p(ep)), "grx_sample_sizes")
+        return int(v.value), int(e.value), vp, ep
+
+    def extract(self, eids=True):
+        """{"vertices", "vertex_ptr", "offsets", "cols", "eids" (None when not asked for), "edge_ptr"}"""
+        v, e, vp, ep = self.sizes()
+        vertices, offsets = np.empty(max(v, 1), dtype=np.int32), np.empty(v + 1, dtype=np.int64)
+        cols = np.empty(max(e, 1), dtype=np.int32)
+        ids = np.empty(max(e, 1), dtype=np.int32) if eids else None
+        _check(lib().grx_sample_extract(self._h, _p(vertices), _i64p(offsets), _p(cols), None if ids is None else _p(ids)), "SampleProblem::Extract")
+        return {"vertices": vertices[:v], "vertex_ptr": vp, "offsets": offsets, "cols": cols[:e], "eids": None if ids is None else ids[:e],
+                "edge_ptr": ep}
+
+    def device_results(self):
+        """device pointers {"vertices": int32[V], "offsets": int64[V + 1], "cols": int32[E], "eids": int32[E] or None}"""
+        names = ("vertices", "offsets", "cols", "eids")
+        p = [C.c_void_p() for _ in names]
+        _check(lib().grx_sample_device_results(self._h, *[C.byref(x) for x in p]), "grx_sample_device_results")
+        return {name: x.value for name, x in zip(names, p)}
+
+
+def gunrock_sample_neighbors(nodes, row_offsets, col_indices, seeds, fanouts, weights=None, replace=False, seed=0, device=0):
+    """One-shot neighbourhood sample: the multi-hop subgraph of the distinct `seeds` under one fanout per hop (-1: whole rows), as a
+    dict of the six arrays "vertices", "vertex_ptr", "offsets", "cols", "eids", "edge_ptr".  With `weights` (int32 >= 0 per entry)
+    the picks are weighted, which needs `replace`."""
+    def prepare(p):
+        p.set_option("seed", seed)
+        p.set_option("replace", 1 if replace else 0)
+        p.set_option("weighted", 0 if weights is None else 1)
+        p.set_fanouts(fanouts)
+        p.reset(seeds)
+    return _one_shot(SampleProblem(device=device).init(nodes, row_offsets, col_indices, weights), prepare, SampleProblem.enact,
+                     SampleProblem.extract)
 
 
 LP_SYNC, LP_CLASSES = 0, 1  # enum GRX_LP_* (gunrock_mi355x.h): option "mode"

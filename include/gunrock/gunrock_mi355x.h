@@ -1093,6 +1093,122 @@ int grx_rw_device_results(grx_rw *p, int **d_walks, int **d_lengths, long long *
 void grx_rw_destroy(grx_rw *p);
 
 /* ------------------------------------------------------------------------------------------------
+ * SAMPLE: SampleProblem + SampleEnactor: neighbourhood sampling, multi-hop fanout subgraphs renumbered to dense local ids (no
+ * counterpart in the reference snapshot).  A sample without replacement is Robert Floyd's subset algorithm over counter-based
+ * draws, so every output is an integer with one value, exactly as for the walks.
+ *   Graph.
+ *   - The graph is taken as grx_rw_init takes it.  It is the CSR as given: directed, with self-loops and duplicate entries kept.
+ *   - Weights are optional int32 >= 0.
+ *   - The same -1 / -2 / -3 codes apply.
+ *   - Init builds a device copy with every row sorted by (column, weight, entry).
+ *   - `entry` is the index of the entry in the caller's col_indices.
+ *   - For every sorted position the copy keeps that `entry`.
+ *   - With weights it also keeps the inclusive int64 prefix sums per row.
+ *   - Every pick indexes the SORTED row.
+ *   Draw.  Draw(seed, v, hop, s) is rw's Draw(seed, walk = v, step = hop, t = s).  The function, the Python rw_draw and the limits
+ *   are the same ones; s < 64 here.
+ *   Picks of vertex v expanded at hop h, with sorted row of d entries and fanout f:
+ *   - f = -1: the positions 0 .. d-1 in order, whatever the mode.  Weights are not consulted.
+ *   - replace = 0 (unweighted only), 1 <= f <= 64:
+ *     - If d <= f, the positions 0 .. d-1 in order.
+ *     - Otherwise, for s = 0 .. f-1:
+ *       - i = d - f + s;
+ *       - t = ((Draw(seed, v, h, s) >> 32) * (i + 1)) >> 32;
+ *       - pick_s = t, unless t equals an earlier pick of this row, in which case pick_s = i.
+ *     - The picks are f distinct positions, in slot order.
+ *   - replace = 1:
+ *     - If d == 0 (weighted: the row total T == 0), there are no picks.
+ *     - Otherwise there are f picks.
+ *     - pick_s is rw's first-order choice with Draw(seed, v, h, s): ChooseUniform, or ChooseWeighted with option "weighted" = 1.
+ *     - The picks are in slot order.
+ *   Literals, computed with rw_draw:
+ *   - (seed 7, v 5, hop 0, d 10, f 4) -> [2, 0, 8, 3].  This case has one collision.
+ *   - (7, 5, 2, 10, 4) -> [2, 0, 7, 5].
+ *   - (1, 0, 1, 9, 6) -> [2, 4, 3, 0, 7, 5].  This case has two collisions.
+ *   Hops.
+ *   - fanouts[0 .. H-1] with 1 <= H <= 16.
+ *   - There are B >= 1 seeds.  They must be DISTINCT vertices, otherwise Reset returns -1.
+ *   - The seeds take the local ids 0 .. B-1 in the given order and are frontier 0.
+ *   - Hop h expands every vertex of frontier h in local-id order with fanouts[h].
+ *   - A pick at position k of v's sorted row is one sampled edge with three fields:
+ *     - row = local id of v;
+ *     - col = the column at k;
+ *     - eid = the entry kept at k.
+ *   - The distinct columns that have no local id yet take the next local ids IN ASCENDING VERTEX ID.  They are frontier h+1.
+ *   - A vertex is therefore expanded at most once.
+ *   - An empty frontier ends the run, and the remaining hops add nothing.
+ *   - Repeated picks and duplicate entries stay as parallel edges.
+ *   Outputs.
+ *   - vertices: int32[V], the vertex of every local id.
+ *   - vertex_ptr: int64[H+2].  Local ids vertex_ptr[h] .. vertex_ptr[h+1]-1 were first reached at hop h, and hop 0 holds the seeds.
+ *   - The sampled edges, as a CSR over local rows:
+ *     - offsets: int64[V+1].  The rows of the last frontier are empty.
+ *     - cols: int32[E], local ids.
+ *     - eids: int32[E].
+ *   - edge_ptr: int64[H+1].  The edges of hop h are edge_ptr[h] .. edge_ptr[h+1]-1.  This follows from the order of expansion.
+ *   Only seed, replace, weighted, the fanouts and the seeds define the result.  The strategy, long_row, the grid, host or device
+ *   input, and the order of entries within a row never change vertices, vertex_ptr, offsets, cols or edge_ptr.  A different entry
+ *   order only changes which caller entry an eid names, by the tie rule above.
+ *   Refusals.
+ *   - The edge count of a hop is known before its sampler runs.
+ *   - If E would exceed option "edge_limit", Enact returns GRX_SAMPLE_TOO_LARGE (-4, next to -1 / -2 / -3).
+ *   - "edge_limit" defaults to 2^31 - 1, which is also its maximum; its minimum is 1.
+ *   - On that refusal no further kernel runs, and the handle holds no result (hipErrorNotReady on extract).
+ *   - The handle takes the next Reset / Enact normally.
+ *   - replace = 0 with weighted = 1 is refused: set_option returns -1.
+ *   - A fanout outside {-1, 1 .. 64} is -1, and so is H outside 1 .. 16.
+ *   Explicitly out.  DESIGN.md 7 says why, in one clause each:
+ *   - Weighted sampling without replacement is out.  Exponential keys are floats, so there is no one-valued integer form.
+ *   - Fanouts above 64 are out.
+ *   - First-occurrence local order is out, because it is schedule-dependent on a GPU.
+ *   - The multi-GPU path is out.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct grx_sample grx_sample;
+enum { GRX_SAMPLE_AUTO = 0, GRX_SAMPLE_LANE = 1, GRX_SAMPLE_GROUP = 2 };  /* option "strategy" */
+enum { GRX_SAMPLE_TOO_LARGE = -4 };  /* next to -1 / -2 / -3 */
+
+int grx_sample_create(grx_sample **out, int instrument, int device);
+/* SampleProblem::Init: validates the CSR and builds the sorted copy on the device.  weights may be NULL.  -1: nodes < 1, edges < 0
+ * or a NULL array; -2: offsets or columns that are not a CSR of `nodes` vertices, or a negative weight; -3: the handle took a graph */
+int grx_sample_init(grx_sample *p, int nodes, int edges, const int *row_offsets, const int *col_indices, const int *weights);
+/* the same for a CSR (and weights, or NULL) in device memory: borrowed, and read only by the build */
+int grx_sample_init_device(grx_sample *p, int nodes, int edges, int *d_row_offsets, int *d_col_indices, int *d_weights);
+/* 0: set, 1: unknown name, -1: a value out of range
+ *   "strategy"     GRX_SAMPLE_AUTO (default): GROUP, and LANE with "replace" = 1 from 65 536 seeds on; GRX_SAMPLE_LANE: one lane per
+ *                  frontier vertex runs the slots in order; GRX_SAMPLE_GROUP: g lanes per vertex, g the power of two with
+ *                  f <= g <= 64.  Never changes a result.
+ *   "seed"         an integer in [0, 2^53) (default 0)
+ *   "replace"      0 (default) or 1; 0 while "weighted" is 1 is -1
+ *   "weighted"     0 (default) or 1; 1 while "replace" is 0, or on a handle whose Init had no weights, is -1
+ *   "edge_limit"   1 .. 2^31 - 1 (default 2^31 - 1): the sampled edges an Enact may hold
+ *   "long_row"     at least 8 (default 4096): under a fanout of -1, longer rows are copied by workgroups.  Never changes a result.
+ *   "eids"         1 (default) or 0: the entries are neither gathered nor allocated */
+int grx_sample_set_option(grx_sample *p, const char *name, double value);
+/* the fanout of every hop.  -1: hops outside 1 .. 16, a NULL list or a fanout outside {-1, 1 .. 64}; the list before stays */
+int grx_sample_set_fanouts(grx_sample *p, int hops, const int *fanouts);
+/* SampleProblem::Reset: the seeds.  -1: num_seeds < 1, a NULL pointer, a seed outside 0 .. nodes - 1 or two equal seeds */
+int grx_sample_reset(grx_sample *p, int num_seeds, const int *h_seeds);
+/* SampleEnactor::Enact(problem, max_grid_size), HIP-event timed: a host loop over the hops, one read-back each and one for the seeds'
+ * own count.  max_grid_size never changes a result.  Before a Reset or set_fanouts: hipErrorNotReady.  GRX_SAMPLE_TOO_LARGE: a hop
+ * would have passed "edge_limit"; its sampler did not run, the handle holds no result and takes the next Reset / Enact */
+int grx_sample_enact(grx_sample *p, int max_grid_size, float *elapsed_ms);
+/* any pointer may be NULL.  Of the last Enact: *hops = H; per hop (arrays of H) the rows expanded, the rows whose picks were drawn
+ * (replace = 0: d > f) and the rows copied whole; the rows a fanout of -1 left to the long-row kernel; kernel launches, read-backs
+ * and -- when instrumented -- the summed kernel time and its four parts phase_ms[4]: count + scan, sample, renumber, relabel;
+ * build_ms: the HIP-event time of Init's build */
+int grx_sample_stats(grx_sample *p, int *hops, long long *rows_expanded, long long *rows_sampled, long long *rows_copied, long long *long_rows,
+                     long long *kernel_launches, long long *readbacks, double *kernel_ms, double *phase_ms, double *build_ms);
+/* any pointer may be NULL.  V, E, vertex_ptr (H + 2 int64) and edge_ptr (H + 1 int64).  Before a finished Enact: hipErrorNotReady */
+int grx_sample_sizes(grx_sample *p, long long *vertices, long long *edges, long long *vertex_ptr, long long *edge_ptr);
+/* any pointer may be NULL.  h_vertices: V int32; h_offsets: V + 1 int64; h_cols, h_eids: E int32.  Before a finished Enact:
+ * hipErrorNotReady; -1 for h_eids when the last Enact ran with "eids" = 0 */
+int grx_sample_extract(grx_sample *p, int *h_vertices, long long *h_offsets, int *h_cols, int *h_eids);
+/* device arrays of the handle after a finished Enact (NULL before; cols and eids NULL without an edge, eids NULL with "eids" = 0).
+ * They stay valid until the next Reset or Enact */
+int grx_sample_device_results(grx_sample *p, int **d_vertices, long long **d_offsets, int **d_cols, int **d_eids);
+void grx_sample_destroy(grx_sample *p);
+
+/* ------------------------------------------------------------------------------------------------
  * LP: LpProblem + LpEnactor: label-propagation communities with integer scores and a total tie rule (no counterpart in the
  * reference snapshot).  The CSR is read exactly as grx_matching_* reads it, as the simple undirected graph G with int32 weights
  * (NULL: 1 each; a pair's weight is the largest of its entries in both directions); a pair weight below 1 is refused.  L[v] is an
