@@ -313,6 +313,21 @@ _SIGNATURES = {
     "grx_sample_extract": (C.c_int, [C.c_void_p, i32p, C.POINTER(C.c_longlong), i32p, i32p]),
     "grx_sample_device_results": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 4),
     "grx_sample_destroy": (None, [C.c_void_p]),
+    "grx_sim_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int]),
+    "grx_sim_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p]),
+    "grx_sim_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "grx_sim_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
+    "grx_sim_reset": (C.c_int, [C.c_void_p]),
+    "grx_sim_pairs": (C.c_int, [C.c_void_p, C.c_longlong, i32p, i32p, C.c_int, C.POINTER(C.c_float)]),
+    "grx_sim_pairs_device": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
+    "grx_sim_topk": (C.c_int, [C.c_void_p, C.c_longlong, i32p, C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "grx_sim_topk_device": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "grx_sim_stats": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_longlong)] * 9 + [C.POINTER(C.c_double)] * 2),
+    "grx_sim_extract_pairs": (C.c_int, [C.c_void_p, i32p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_double)]),
+    "grx_sim_extract_topk": (C.c_int, [C.c_void_p, i32p, i32p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_double), i32p,
+                                       i32p]),
+    "grx_sim_device_results": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 9),
+    "grx_sim_destroy": (None, [C.c_void_p]),
     "grx_lp_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int]),
     "grx_lp_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p, i32p]),
     "grx_lp_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -2347,6 +2362,167 @@ def gunrock_sample_neighbors(nodes, row_offsets, col_indices, seeds, fanouts, we
         p.reset(seeds)
     return _one_shot(SampleProblem(device=device).init(nodes, row_offsets, col_indices, weights), prepare, SampleProblem.enact,
                      SampleProblem.extract)
+
+
+SIM_AUTO, SIM_LANE, SIM_WAVE, SIM_BLOCK, SIM_GLOBAL = 0, 1, 2, 3, 4  # enum GRX_SIM_* (gunrock_mi355x.h): option "strategy"
+SIM_COMMON, SIM_JACCARD, SIM_OVERLAP, SIM_SORENSEN = 0, 1, 2, 3  # option "metric"
+SIM_MAX_K = 64
+SIM_TOO_LARGE = -4  # grx_sim_pairs / grx_sim_topk: the query is beyond what int32 offsets address
+
+
+class SimTooLarge(ArithmeticError):
+    """SimProblem.pairs / topk: more than INT_MAX pairs, or sources x k beyond INT_MAX (GRX_SIM_TOO_LARGE): nothing ran, the handle
+    takes the next call"""
+
+
+class SimProblem(_Handle):
+    """SimProblem + SimEnactor behind the handle C ABI: vertex similarity of the CSR read as an undirected simple graph -- common
+    neighbours, Jaccard, overlap and Sorensen as exact fractions num / den (int64) with the float64 score num / den, for given pairs
+    and as the k most similar vertices of given sources (score descending by exact comparison, then id ascending)."""
+
+    _destroy = "grx_sim_destroy"
+
+    def __init__(self, instrument=False, device=0):
+        self._create("grx_sim_create", int(instrument), device)
+        self.nodes = 0
+        self.entries = 0
+        self._pairs = 0
+        self._rows = 0
+        self._k = 1
+
+    def init(self, nodes, row_offsets, col_indices):
+        ro, ci = _csr_arrays(row_offsets, col_indices, nodes)
+        self.nodes, self.entries = int(nodes), int(ci.shape[0])
+        _check(lib().grx_sim_init(self._h, self.nodes, self.entries, _p(ro), _p(ci)), "SimProblem::Init")
+        return self
+
+    def init_device(self, nodes, edges, d_row_offsets, d_col_indices):
+        """the CSR stays the caller's; the build reads it, nothing later does"""
+        self.nodes, self.entries = int(nodes), int(edges)
+        _check(lib().grx_sim_init_device(self._h, self.nodes, self.entries, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices)),
+               "SimProblem::Init(device)")
+        return self
+
+    def set_option(self, name, value):
+        """"metric" (SIM_COMMON / SIM_JACCARD / SIM_OVERLAP / SIM_SORENSEN), "skip_neighbors", "strategy" (SIM_AUTO / SIM_LANE / SIM_WAVE /
+        SIM_BLOCK / SIM_GLOBAL), "lane_max", "table_slots", "block_slots", "scratch_mib"; returns the library's code: 0 = set,
+        1 = unknown name (a value out of range raises)"""
+        rc = lib().grx_sim_set_option(self._h, name.encode(), float(value))
+        if rc not in (0, 1):
+            _check(rc, "grx_sim_set_option(%s)" % name)
+        return rc
+
+    def reset(self):
+        _check(lib().grx_sim_reset(self._h), "SimProblem::Reset")
+
+    @staticmethod
+    def _enacted(rc, what):
+        if rc == SIM_TOO_LARGE:
+            raise SimTooLarge("gunrockinst_amd: %s refused: the query is beyond int32 offsets (code %d)" % (what, rc))
+        _check(rc, what)
+
+    def pairs(self, u, v, max_grid_size=0):
+        """scores the pairs (u[i], v[i]) given on the host; the elapsed milliseconds.  An id outside [0, nodes) raises (code -1)"""
+        u, v = _i32(u).ravel(), _i32(v).ravel()
+        if u.shape != v.shape:
+            raise ValueError("gunrockinst_amd: %d and %d pair ends" % (u.shape[0], v.shape[0]))
+        ms = C.c_float()
+        self._pairs = 0
+        self._enacted(lib().grx_sim_pairs(self._h, int(u.shape[0]), _p(u), _p(v), int(max_grid_size), C.byref(ms)), "SimEnactor::EnactPairs")
+        self._pairs = int(u.shape[0])
+        return float(ms.value)
+
+    def pairs_device(self, num_pairs, d_u, d_v, max_grid_size=0):
+        """the same for int32 arrays in device memory, which stay the caller's"""
+        ms = C.c_float()
+        self._pairs = 0
+        self._enacted(lib().grx_sim_pairs_device(self._h, int(num_pairs), C.c_void_p(d_u), C.c_void_p(d_v), int(max_grid_size), C.byref(ms)),
+                      "SimEnactor::EnactPairs(device)")
+        self._pairs = int(num_pairs)
+        return float(ms.value)
+
+    def topk(self, sources, k, max_grid_size=0):
+        """the k most similar vertices of every source given on the host; the elapsed milliseconds"""
+        s = _i32(sources).ravel()
+        ms = C.c_float()
+        self._rows = 0
+        self._enacted(lib().grx_sim_topk(self._h, int(s.shape[0]), _p(s), int(k), int(max_grid_size), C.byref(ms)), "SimEnactor::EnactTopk")
+        self._rows, self._k = int(s.shape[0]), int(k)
+        return float(ms.value)
+
+    def topk_device(self, num_sources, d_sources, k, max_grid_size=0):
+        ms = C.c_float()
+        self._rows = 0
+        self._enacted(lib().grx_sim_topk_device(self._h, int(num_sources), C.c_void_p(d_sources), int(k), int(max_grid_size), C.byref(ms)),
+                      "SimEnactor::EnactTopk(device)")
+        self._rows, self._k = int(num_sources), int(k)
+        return float(ms.value)
+
+    def stats(self):
+        m, w, walked, candidates, probes, n = (C.c_longlong() for _ in range(6))
+        pairs, sources, wedges = (C.c_longlong * 2)(), (C.c_longlong * 3)(), (C.c_longlong * 3)()
+        k, b = C.c_double(), C.c_double()
+        _check(lib().grx_sim_stats(self._h, C.byref(m), C.byref(w), C.byref(walked), pairs, sources, wedges, C.byref(candidates), C.byref(probes),
+                                   C.byref(n), C.byref(k), C.byref(b)), "grx_sim_stats")
+        out = {"simple_edges": m.value, "wedges": w.value, "wedges_walked": walked.value, "candidates": candidates.value,
+               "table_probes": probes.value, "kernel_launches": n.value, "kernel_ms": k.value, "build_ms": b.value,
+               "lane_pairs": int(pairs[0]), "wave_pairs": int(pairs[1])}
+        for i, name in enumerate(("wave", "block", "global")):
+            out[name + "_sources"], out[name + "_wedges"] = int(sources[i]), int(wedges[i])
+        return out
+
+    def extract_pairs(self):
+        """{"common": int32, "num", "den": int64, "score": float64}, one entry per pair of the last pairs()"""
+        count = self._pairs
+        common = np.empty(max(count, 1), dtype=np.int32)
+        num, den = (np.empty(max(count, 1), dtype=np.int64) for _ in range(2))
+        score = np.empty(max(count, 1), dtype=np.float64)
+        _check(lib().grx_sim_extract_pairs(self._h, _p(common), _i64p(num), _i64p(den), score.ctypes.data_as(C.POINTER(C.c_double))),
+               "SimProblem::ExtractPairs")
+        return {"common": common[:count], "num": num[:count], "den": den[:count], "score": score[:count]}
+
+    def extract_topk(self):
+        """{"ids", "common": int32 (S, k); "num", "den": int64 (S, k); "score": float64 (S, k); "count", "candidates": int32 (S)} of the
+        last topk(); ids are -1 and the rest 0 beyond count[s]"""
+        rows, k = self._rows, self._k
+        count = rows * k
+        ids, common = (np.empty(max(count, 1), dtype=np.int32) for _ in range(2))
+        num, den = (np.empty(max(count, 1), dtype=np.int64) for _ in range(2))
+        score = np.empty(max(count, 1), dtype=np.float64)
+        kept, candidates = (np.empty(max(rows, 1), dtype=np.int32) for _ in range(2))
+        _check(lib().grx_sim_extract_topk(self._h, _p(ids), _p(common), _i64p(num), _i64p(den), score.ctypes.data_as(C.POINTER(C.c_double)),
+                                          _p(kept), _p(candidates)), "SimProblem::ExtractTopk")
+        out = {name: a[:count].reshape(rows, k) for name, a in (("ids", ids), ("common", common), ("num", num), ("den", den), ("score", score))}
+        out["count"], out["candidates"] = kept[:rows], candidates[:rows]
+        return out
+
+    def device_results(self):
+        """device pointers of the integer results: {"pair_common", "pair_num", "pair_den", "ids", "common", "num", "den", "count",
+        "candidates"} (None without a result of that mode)"""
+        names = ("pair_common", "pair_num", "pair_den", "ids", "common", "num", "den", "count", "candidates")
+        p = [C.c_void_p() for _ in names]
+        _check(lib().grx_sim_device_results(self._h, *[C.byref(x) for x in p]), "grx_sim_device_results")
+        return {name: x.value for name, x in zip(names, p)}
+
+
+def gunrock_similarity(offsets, cols, u, v, metric=SIM_JACCARD, device=0):
+    """One-shot pair similarity on the CSR (offsets, cols): returns {"common", "num", "den", "score"}, one entry per pair (u[i], v[i])."""
+    offsets = _i32(offsets)
+    return _one_shot(SimProblem(device=device).init(offsets.shape[0] - 1, offsets, cols), lambda p: p.set_option("metric", metric),
+                     lambda p: p.pairs(u, v), SimProblem.extract_pairs)
+
+
+def gunrock_similar_vertices(offsets, cols, sources, k, metric=SIM_JACCARD, skip_neighbors=False, device=0):
+    """One-shot top-k similarity on the CSR (offsets, cols): the k most similar vertices of every source, as {"ids", "common", "num",
+    "den", "score"} of shape (S, k) and {"count", "candidates"} of shape (S); with skip_neighbors the neighbours of a source are no
+    candidates."""
+    offsets = _i32(offsets)
+
+    def prepare(p):
+        p.set_option("metric", metric)
+        p.set_option("skip_neighbors", 1 if skip_neighbors else 0)
+    return _one_shot(SimProblem(device=device).init(offsets.shape[0] - 1, offsets, cols), prepare, lambda p: p.topk(sources, k),
+                     SimProblem.extract_topk)
 
 
 LP_SYNC, LP_CLASSES = 0, 1  # enum GRX_LP_* (gunrock_mi355x.h): option "mode"

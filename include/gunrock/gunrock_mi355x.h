@@ -1209,6 +1209,90 @@ int grx_sample_device_results(grx_sample *p, int **d_vertices, long long **d_off
 void grx_sample_destroy(grx_sample *p);
 
 /* ------------------------------------------------------------------------------------------------
+ * SIM: SimProblem + SimEnactor: vertex similarity by neighbourhoods -- the score of given pairs, and the k most similar vertices of
+ * given sources (no counterpart in the reference snapshot).  The CSR is read exactly as grx_tc_* / grx_c4_* read it, as the simple
+ * undirected graph G: u and v are neighbours when either row holds the other, self-loops are ignored, rows may be unsorted and may hold
+ * duplicates and one-way entries.  d(v) is the degree in G, c(u, v) = |N(u) ^ N(v)| the common neighbours (c(u, u) = d(u)).  Every
+ * metric is an exact fraction num / den:
+ *   GRX_SIM_COMMON    c / 1
+ *   GRX_SIM_JACCARD   c / (d(u) + d(v) - c)
+ *   GRX_SIM_OVERLAP   c / min(d(u), d(v))
+ *   GRX_SIM_SORENSEN  2 c / (d(u) + d(v))
+ * den = 0 happens only with an isolated endpoint and reports num = 0, den = 0, score = 0.0.  num and den are int64 (on the device they
+ * are sums of int32 degrees: the graph has at most INT_MAX / 2 edges); score is float64, the one IEEE division num / den, taken on the
+ * host by the extract calls from the two integer arrays (the device holds no score).  Every output has one value, whatever the
+ * strategy, the thresholds, the grid or the scratch budget.
+ *   Pair mode: P >= 0 pairs (u[i], v[i]) in any order; repeats, u == v, adjacent and non-adjacent pairs allowed.  Per pair: common
+ *   (int32), num, den, score.
+ *   Top-k mode: S >= 0 sources (repeats allowed, every row independent) and k in 1 .. GRX_SIM_MAX_K.  The candidates of u are the
+ *   vertices w != u with c(u, w) >= 1; with "skip_neighbors" those in N(u) are no candidates.  They are ranked by score descending, then
+ *   by id ascending; scores are compared as num den' against num' den in 64-bit integers.  Per source a row of k: ids (int32, -1
+ *   beyond the end), common, num, den, score (0 beyond the end); count[s] = min(k, candidates) and candidates[s], the number before
+ *   the cut.
+ * An id outside [0, nodes) is a bad argument (-1): it is found on the device before a kernel writes a result, and the handle stays
+ * usable.  Init builds the neighbour CSR of G (rows ascending) and Wd(u) = the sum of d(v) over v in N(u), the wedges a top-k of u walks.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct grx_sim grx_sim;
+enum { GRX_SIM_AUTO = 0, GRX_SIM_LANE = 1, GRX_SIM_WAVE = 2, GRX_SIM_BLOCK = 3, GRX_SIM_GLOBAL = 4 };  /* option "strategy" */
+enum { GRX_SIM_COMMON = 0, GRX_SIM_JACCARD = 1, GRX_SIM_OVERLAP = 2, GRX_SIM_SORENSEN = 3 };         /* option "metric" */
+enum { GRX_SIM_MAX_K = 64 };
+enum { GRX_SIM_TOO_LARGE = -4 };  /* next to -1 / -2 / -3; the value of GRX_SAMPLE_TOO_LARGE */
+
+int grx_sim_create(grx_sim **out, int instrument, int device);
+/* SimProblem::Init: validates the CSR and builds the neighbour CSR of G and Wd on the device.  -1: nodes < 1, edges < 0 or a NULL
+ * array; -2: not a CSR of `nodes` vertices, as grx_tc_init; -3: the handle has been given a graph before (accepted or rejected) */
+int grx_sim_init(grx_sim *p, int nodes, int edges, const int *row_offsets, const int *col_indices);
+/* the same for a CSR already in HBM: borrowed, not freed, read by the build only */
+int grx_sim_init_device(grx_sim *p, int nodes, int edges, int *d_row_offsets, int *d_col_indices);
+/* named options, for the next Enact; 0: set, 1: unknown name, -1: a value out of range.  Only "metric" and "skip_neighbors" change a
+ * result.
+ *   "metric"          GRX_SIM_COMMON / _JACCARD (default) / _OVERLAP / _SORENSEN
+ *   "skip_neighbors"  1: top-k mode takes no candidate from N(u), the link-prediction form; 0 (default)
+ *   "strategy"        GRX_SIM_AUTO (default): every pair and every source takes the smallest regime that holds it; GRX_SIM_LANE / _WAVE /
+ *                     _BLOCK / _GLOBAL: nothing takes a smaller regime than this one.  Pair mode has the regimes LANE and WAVE (a
+ *                     forced BLOCK or GLOBAL is WAVE there), top-k mode WAVE, BLOCK and GLOBAL (AUTO and LANE are its WAVE)
+ *   "lane_max"        pair mode: a pair with d(u) + d(v) <= lane_max is one lane's two-pointer merge, a longer one the whole wave's
+ *                     bisection (default 64, 0 .. 2^20)
+ *   "table_slots"     slots of a wave's table, a power of two in 64 .. 1024 (default 1024); the WAVE regime holds Wd <= table_slots / 2
+ *   "block_slots"     slots of a workgroup's table, a power of two in 256 .. 8192 (default 8192, 64 KiB of LDS); the BLOCK regime
+ *                     holds Wd <= block_slots / 2
+ *   "scratch_mib"     the GLOBAL regime runs min(grid, scratch_mib 2^20 / (4 nodes)) workgroups, at least 1, each with a counter row
+ *                     of `nodes` int32 in global scratch (default 1024, 1 .. 65536) */
+int grx_sim_set_option(grx_sim *p, const char *name, double value);
+/* SimProblem::Reset: the handle holds no result and its counters are zero; the graph stays */
+int grx_sim_reset(grx_sim *p);
+/* SimEnactor::EnactPairs, HIP-event timed: h_u, h_v are num_pairs int32 each on the host (NULL allowed with num_pairs = 0).  -1: a
+ * negative count, a NULL array or an id outside [0, nodes); GRX_SIM_TOO_LARGE: num_pairs > INT_MAX.  After either the handle holds no
+ * pair result and takes the next call.  The top-k result of the handle, if any, stays */
+int grx_sim_pairs(grx_sim *p, long long num_pairs, const int *h_u, const int *h_v, int max_grid_size, float *elapsed_ms);
+/* the same for arrays in HBM: borrowed, read by this call only */
+int grx_sim_pairs_device(grx_sim *p, long long num_pairs, const int *d_u, const int *d_v, int max_grid_size, float *elapsed_ms);
+/* SimEnactor::EnactTopk, HIP-event timed: h_sources are num_sources int32 on the host.  -1: a negative count, a NULL array, k outside
+ * 1 .. GRX_SIM_MAX_K or an id outside [0, nodes); GRX_SIM_TOO_LARGE: num_sources k > INT_MAX.  After either the handle holds no top-k
+ * result and takes the next call.  The pair result of the handle, if any, stays */
+int grx_sim_topk(grx_sim *p, long long num_sources, const int *h_sources, int k, int max_grid_size, float *elapsed_ms);
+int grx_sim_topk_device(grx_sim *p, long long num_sources, const int *d_sources, int k, int max_grid_size, float *elapsed_ms);
+/* any pointer may be NULL.  The edges (M) and the wedges (the sum of Wd) of the graph; of the last Enact: the wedges walked (the sum of
+ * Wd over the sources), the pairs of the regimes lane and wave (regime_pairs[2]), the sources and their wedges of the regimes wave,
+ * workgroup and global (regime_sources[3], regime_wedges[3]), the candidates of all sources, the table probes of the wave and workgroup
+ * regimes (not reproducible to the last digit: a probe sequence depends on who claimed a slot first), kernel launches and -- when
+ * instrumented -- the summed kernel time; build_ms: the HIP-event time of Init's build */
+int grx_sim_stats(grx_sim *p, long long *simple_edges, long long *wedges, long long *wedges_walked, long long *regime_pairs, long long *regime_sources,
+                  long long *regime_wedges, long long *candidates, long long *table_probes, long long *kernel_launches, double *kernel_ms,
+                  double *build_ms);
+/* any pointer may be NULL; num_pairs entries each.  Before a finished pair Enact (none yet, a Reset since, or a refused one):
+ * hipErrorNotReady */
+int grx_sim_extract_pairs(grx_sim *p, int *h_common, long long *h_num, long long *h_den, double *h_score);
+/* any pointer may be NULL; h_ids .. h_score: num_sources x k entries, row s at s k; h_count, h_candidates: num_sources.  Before a
+ * finished top-k Enact: hipErrorNotReady */
+int grx_sim_extract_topk(grx_sim *p, int *h_ids, int *h_common, long long *h_num, long long *h_den, double *h_score, int *h_count, int *h_candidates);
+/* device arrays of the handle (integers only), NULL without a finished Enact of their mode or with an empty query.  They stay valid
+ * until the next Enact of their mode */
+int grx_sim_device_results(grx_sim *p, int **d_pair_common, long long **d_pair_num, long long **d_pair_den, int **d_ids, int **d_common,
+                           long long **d_num, long long **d_den, int **d_count, int **d_candidates);
+void grx_sim_destroy(grx_sim *p);
+
+/* ------------------------------------------------------------------------------------------------
  * LP: LpProblem + LpEnactor: label-propagation communities with integer scores and a total tie rule (no counterpart in the
  * reference snapshot).  The CSR is read exactly as grx_matching_* reads it, as the simple undirected graph G with int32 weights
  * (NULL: 1 each; a pair's weight is the largest of its entries in both directions); a pair weight below 1 is refused.  L[v] is an
