@@ -27,7 +27,9 @@
 
 #include <hip/hip_runtime.h>
 
+#include <gunrock/app/table_ladder.hpp>
 #include <gunrock/graphio/pair_graph.hpp>
+#include <gunrock/oprtr/lds_table.hpp>
 #include <gunrock/oprtr/step.hpp>
 #include <gunrock/util/device_intrinsics.hpp>
 
@@ -38,18 +40,22 @@ namespace c4 {
 typedef unsigned long long Count;  // the bits of an int64 count (never beyond 2^62: the enactor refuses first)
 
 enum { C4_AUTO = 0, C4_LANE = 1, C4_WAVE = 2, C4_BLOCK = 3, C4_GLOBAL = 4 };  // "strategy"; 1 .. 4 are the regimes
+static_assert(C4_WAVE == ladder::WAVE && C4_BLOCK == ladder::BLOCK && C4_GLOBAL == ladder::GLOBAL, "the ladder's rungs");
 
 constexpr int kC4Threads = 256;
 constexpr int kC4Waves = kC4Threads / util::kWaveSize;
 constexpr int kLaneArray = 32;        // the private array of the LANE regime: the largest "lane_max_wedges"
 constexpr int kLaneMaxWedges = 16;    // default "lane_max_wedges"  (by reasoning)
-constexpr int kTableSlots = 1024;     // default and largest "table_slots": 8 KiB per wave, 32 KiB per workgroup
-constexpr int kMinTableSlots = 64;
-constexpr int kBlockSlots = 8192;     // default and largest "block_slots": 64 KiB
-constexpr int kMinBlockSlots = 256;
-constexpr int kScratchMib = 1024;     // default "scratch_mib"  (256 ran 64 workgroups at R-MAT 20)
-constexpr int kMaxScratchMib = 65536;
+// the table's options, their defaults and ranges, are the ladder's (app/table_ladder.hpp)
+using ladder::kTableSlots;
+using ladder::kMinTableSlots;
+using ladder::kBlockSlots;
+using ladder::kMinBlockSlots;
+using ladder::kScratchMib;
+using ladder::kMaxScratchMib;
+using ladder::TableSize;
 
+namespace lds = oprtr::lds;
 using util::Fmix32;
 
 // the 64-bit words the kernels and the host share
@@ -81,26 +87,7 @@ __host__ __device__ __forceinline__ int Regime(long long w, int strategy, int la
 {
     int r = strategy == C4_AUTO ? C4_LANE : strategy;
     if (r == C4_LANE && w > lane_max_wedges) r = C4_WAVE;
-    if (r == C4_WAVE && w > table_slots / 2) r = C4_BLOCK;
-    if (r == C4_BLOCK && w > block_slots / 2) r = C4_GLOBAL;
-    return r;
-}
-
-// The slots a table of at most `slots` takes for w wedges: 2 w rounded up to a power of two, at least 64 (w <= slots / 2).
-__host__ __device__ __forceinline__ int TableSize(long long w, int slots)
-{
-    int size = kMinTableSlots;
-    while (size < slots && size < 2 * w) size <<= 1;
-    return size;
-}
-
-// The workgroup slots of the GLOBAL regime: min(grid, scratch_mib 2^20 / (4 n)), at least 1.
-__host__ __device__ __forceinline__ long long GlobalSlots(long long grid, long long scratch_mib, long long nodes)
-{
-    const long long row_bytes = 4 * (nodes > 0 ? nodes : 1);
-    long long slots = (scratch_mib << 20) / row_bytes;
-    if (slots > grid) slots = grid;
-    return slots < 1 ? 1 : slots;
+    return ladder::Widen(r, w, table_slots, block_slots);
 }
 
 __device__ __forceinline__ Count Pairs(int c) { return static_cast<Count>(c) * static_cast<Count>(c - 1) / 2; }
@@ -193,21 +180,6 @@ __device__ __forceinline__ void LaneCount(const Ctx &c, int u, Tally &t)
 
 // ---------------- WAVE and BLOCK ----------------
 
-// the lanes of one wave have finished their LDS operations and see each other's
-__device__ __forceinline__ void WaveLdsSync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-template <bool BLOCK>
-__device__ __forceinline__ void GroupSync()
-{
-    if (BLOCK) __syncthreads();
-    else WaveLdsSync();
-}
-
 // The 4-cycles owned by u, by a wave (BLOCK = false) or by the workgroup (BLOCK = true), uniform over the group.  key[] / count[] are
 // the group's table of `slots` slots.  A wave takes one v at a time and its lanes the w of that v.
 template <bool BLOCK>
@@ -219,45 +191,25 @@ __device__ __forceinline__ void TableCount(const Ctx &c, int u, int *key, int *c
     const int lane = static_cast<int>(util::LaneId());
     const int wave = BLOCK ? static_cast<int>(threadIdx.x) / util::kWaveSize : 0;
     const int size = TableSize(c.wedges[u], slots);
-    const unsigned mask = static_cast<unsigned>(size - 1);
     const int b = c.ro[u], d = c.dlow[u];
-    for (int k = tid; k < size; k += G) {
-        key[k] = -1;
-        count[k] = 0;
-    }
-    GroupSync<BLOCK>();
+    lds::Clear<G>(key, size, tid, [&](int k) { count[k] = 0; });
+    lds::GroupSync<BLOCK>();
     for (int i = b + wave; i < b + d; i += WAVES) {  // pass 1
         const int rv = c.ro[c.ci[i]], p = c.pre[i];
         for (int j = lane; j < p; j += util::kWaveSize) {
             const int w = c.ci[rv + j];
-            unsigned at = Fmix32(static_cast<unsigned>(w)) & mask;
-            for (int probe = 0; probe < size; ++probe) {
-                const int was = atomicCAS(key + at, -1, w);
-                ++t.probes;
-                if (was == -1 || was == w) {
-                    atomicAdd(count + at, 1);
-                    break;
-                }
-                at = (at + 1) & mask;
-            }
+            const int at = lds::Claim(key, size, Fmix32(static_cast<unsigned>(w)), w, t.probes);
+            if (at >= 0) atomicAdd(count + at, 1);  // (always: the table never fills)
         }
     }
-    GroupSync<BLOCK>();
+    lds::GroupSync<BLOCK>();
     for (int i = b + wave; i < b + d; i += WAVES) {  // pass 2 (wave-uniform)
         const int v = c.ci[i], rv = c.ro[v], p = c.pre[i];
         Count through = 0;
         for (int j = lane; j < p; j += util::kWaveSize) {
             const int w = c.ci[rv + j];
-            unsigned at = Fmix32(static_cast<unsigned>(w)) & mask;
-            int same = 0;
-            for (int probe = 0; probe < size; ++probe) {
-                ++t.probes;
-                if (key[at] == w) {
-                    same = count[at];
-                    break;
-                }
-                at = (at + 1) & mask;
-            }
+            const int at = lds::Find(key, size, Fmix32(static_cast<unsigned>(w)), w, t.probes);  // (there: pass 1 claimed it)
+            const int same = at >= 0 ? count[at] : 0;
             if (same < 2) continue;
             through += static_cast<Count>(same - 1);
             if (c.edge_cycles) Credit(c.edge_cycles, c.eid[rv + j], static_cast<Count>(same - 1));
@@ -278,7 +230,7 @@ __device__ __forceinline__ void TableCount(const Ctx &c, int u, int *key, int *c
     t.total += own;
     own = util::WaveSum(own);
     if (lane == 0) Credit(c.cycles, c.inv[u], own);
-    GroupSync<BLOCK>();  // (the next start vertex clears what this one still reads)
+    lds::GroupSync<BLOCK>();  // (the next start vertex clears what this one still reads)
 }
 
 // One wave per 64 start vertices, lane l of wave group g takes the rank l * groups + g: every wave meets the whole range of degrees.
@@ -334,13 +286,6 @@ static __global__ __launch_bounds__(kC4Threads) void BlockKernel(Ctx c)
 
 // ---------------- GLOBAL ----------------
 
-// every wave's global atomics have been performed and every wave knows
-__device__ __forceinline__ void GlobalSync()
-{
-    __threadfence();
-    __syncthreads();
-}
-
 // One workgroup per start vertex of global_list[], workgroup slot blockIdx.x with its counter row rows[blockIdx.x * nodes ..), all 0
 // between two start vertices.  The host launches no more workgroups than there are rows.
 static __global__ __launch_bounds__(kC4Threads) void GlobalKernel(Ctx c, int *rows)
@@ -358,7 +303,7 @@ static __global__ __launch_bounds__(kC4Threads) void GlobalKernel(Ctx c, int *ro
             const int rv = c.ro[c.ci[i]], p = c.pre[i];
             for (int j = lane; j < p; j += util::kWaveSize) atomicAdd(row + c.ci[rv + j], 1);
         }
-        GlobalSync();
+        lds::GlobalSync();
         for (int i = b + wave; i < b + d; i += kC4Waves) {  // pass 2 (wave-uniform)
             const int v = c.ci[i], rv = c.ro[v], p = c.pre[i];
             Count through = 0;
@@ -374,7 +319,7 @@ static __global__ __launch_bounds__(kC4Threads) void GlobalKernel(Ctx c, int *ro
                 if (c.edge_cycles) Credit(c.edge_cycles, c.eid[i], through);
             }
         }
-        GlobalSync();
+        lds::GlobalSync();
         Count own = 0;
         for (int i = b + wave; i < b + d; i += kC4Waves) {  // pass 3: the row back to 0; who clears an end credits it
             const int rv = c.ro[c.ci[i]], p = c.pre[i];
@@ -389,7 +334,7 @@ static __global__ __launch_bounds__(kC4Threads) void GlobalKernel(Ctx c, int *ro
         t.total += own;
         own = util::WaveSum(own);
         if (lane == 0) Credit(c.cycles, c.inv[u], own);
-        GlobalSync();
+        lds::GlobalSync();
     }
     Flush(t, c);
 }

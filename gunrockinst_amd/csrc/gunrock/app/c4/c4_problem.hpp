@@ -42,8 +42,7 @@ struct C4Problem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         int *d_lists = nullptr;          // 2 n: BlockKernel's and GlobalKernel's start vertices
         unsigned long long *d_words = nullptr;    // W_COUNT words of the kernels, then [0] the wedges, [1] the largest W
         double *d_bound = nullptr;
-        int *d_rows = nullptr;           // the GLOBAL regime's counter rows, (re)allocated by Enact, all 0 between launches
-        size_t row_ints = 0;
+        Grown<int> rows;                 // the GLOBAL regime's counter rows, grown by Enact, all 0 between launches
     };
 
     DataSlice **data_slices = nullptr;
@@ -62,9 +61,10 @@ struct C4Problem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
             DataSlice *ds = data_slices[0];
             if (ds) {
                 void *bufs[] = {ds->d_cycles, ds->d_edge_cycles, ds->d_src, ds->d_dst, ds->d_inv, ds->d_ro, ds->d_ci, ds->d_eid, ds->d_pre,
-                                ds->d_dlow, ds->d_wedges, ds->d_lists, ds->d_words, ds->d_bound, ds->d_rows};
+                                ds->d_dlow, ds->d_wedges, ds->d_lists, ds->d_words, ds->d_bound};
                 for (void *b : bufs)
                     if (b) util::GRError(hipFree(b), "C4Problem hipFree failed", __FILE__, __LINE__);
+                ds->rows.Free();
                 delete ds;
             }
             delete[] data_slices;

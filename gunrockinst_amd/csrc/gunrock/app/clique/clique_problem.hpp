@@ -42,8 +42,7 @@ struct CliqueProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         int *d_words = nullptr;        // BinKernel's counters
         Count *d_counters = nullptr;   // [0] cliques, [1] bit-row ANDs, [2] list look-ups; [4] sum of C(d, 2), [5] the largest out-row
         double *d_bound = nullptr;     // [k - 3]: sum over u of C(d+(u), k - 1)
-        int *d_slabs = nullptr;        // the list regime's scratch, (re)allocated by Enact
-        size_t slab_ints = 0;
+        Grown<int> slabs;              // the list regime's scratch, grown by Enact
     };
 
     DataSlice **data_slices = nullptr;
@@ -61,9 +60,10 @@ struct CliqueProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
             DataSlice *ds = data_slices[0];
             if (ds) {
                 void *bufs[] = {ds->d_cliques, ds->d_degrees, ds->d_oro, ds->d_oci, ds->d_osrc, ds->d_bitmap_rows, ds->d_list_edges, ds->d_words,
-                                ds->d_counters, ds->d_bound, ds->d_slabs};
+                                ds->d_counters, ds->d_bound};
                 for (void *b : bufs)
                     if (b) util::GRError(hipFree(b), "CliqueProblem hipFree failed", __FILE__, __LINE__);
+                ds->slabs.Free();
                 delete ds;
             }
             delete[] data_slices;

@@ -30,6 +30,7 @@
 
 #include <climits>
 
+#include <gunrock/oprtr/lds_table.hpp>
 #include <gunrock/oprtr/step.hpp>
 #include <gunrock/util/device_intrinsics.hpp>
 
@@ -46,9 +47,10 @@ constexpr int kLpWaves = kLpThreads / util::kWaveSize;
 constexpr int kLaneMaxRow = 16;     // default "lane_max_row"  (by reasoning)
 constexpr int kWaveMaxRow = 512;    // default "wave_max_row"
 constexpr int kTableSlots = 1024;   // default and largest "table_slots": 12 KiB per wave, 48 KiB per workgroup
-constexpr int kMinTableSlots = 64;
+using oprtr::lds::kMinTableSlots;
 constexpr int kMaxLogSlices = 26;   // 2^26 slices of the 32-bit hash space hold 64 labels each
 
+namespace lds = oprtr::lds;
 using util::Fmix32;
 
 // the 64-bit words the kernels and the host share; the first kRoundWords are cleared in front of every round
@@ -168,21 +170,6 @@ __device__ __forceinline__ int LaneVote(const Ctx &c, int b, int e, int cur)
     return best.label;
 }
 
-// the lanes of one wave have finished their LDS operations and see each other's
-__device__ __forceinline__ void WaveLdsSync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-template <bool BLOCK>
-__device__ __forceinline__ void GroupSync()
-{
-    if (BLOCK) __syncthreads();
-    else WaveLdsSync();
-}
-
 // what a workgroup shares next to its table (HubKernel)
 struct BlockShared {
     unsigned long long score[kLpWaves];
@@ -198,9 +185,7 @@ __device__ __forceinline__ int RowVote(const Ctx &c, int b, int e, int cur, int 
 {
     constexpr int G = BLOCK ? kLpThreads : util::kWaveSize;
     const int tid = BLOCK ? static_cast<int>(threadIdx.x) : static_cast<int>(util::LaneId());
-    int size = kMinTableSlots;
-    while (size < slots && size < 2 * (e - b)) size <<= 1;
-    const unsigned mask = static_cast<unsigned>(size - 1);
+    const int size = lds::TableSize(e - b, slots);
     Cand best;
     int log_slices = 0;
     for (;;) {  // (at most kMaxLogSlices + 1 times)
@@ -208,37 +193,25 @@ __device__ __forceinline__ int RowVote(const Ctx &c, int b, int e, int cur, int 
         bool full = false;
         const unsigned slices = 1u << log_slices;
         for (unsigned s = 0; s < slices; ++s) {
-            for (int k = tid; k < size; k += G) {
-                key[k] = -1;
-                score[k] = 0;
-            }
-            GroupSync<BLOCK>();
+            lds::Clear<G>(key, size, tid, [&](int k) { score[k] = 0; });
+            lds::GroupSync<BLOCK>();
             for (int i = b + tid; i < e; i += G) {
                 const int l = c.labels[c.ci[i]];
                 const unsigned h = Fmix32(static_cast<unsigned>(l));
                 if (log_slices && (h >> (32 - log_slices)) != s) continue;
-                unsigned at = h & mask;
-                bool placed = false;
-                for (int probe = 0; probe < size; ++probe) {
-                    const int was = atomicCAS(key + at, -1, l);
-                    if (was == -1 || was == l) {
-                        atomicAdd(score + at, static_cast<unsigned long long>(c.ew ? c.ew[i] : 1));
-                        placed = true;
-                        break;
-                    }
-                    at = (at + 1) & mask;
-                }
-                full |= !placed;
+                unsigned long long probes = 0;  // (not counted here)
+                const int at = lds::Claim(key, size, h, l, probes);
+                if (at >= 0) atomicAdd(score + at, static_cast<unsigned long long>(c.ew ? c.ew[i] : 1));
+                full |= at < 0;
             }
-            GroupSync<BLOCK>();
+            lds::GroupSync<BLOCK>();
             for (int k = tid; k < size; k += G) {
                 Cand x;
                 x.label = key[k];
                 x.score = score[k];
                 if (x.label >= 0 && Better(x, best, cur)) best = x;
             }
-            if (BLOCK) __syncthreads();  // (the next pass clears what this one still reads)
-            else WaveLdsSync();
+            lds::GroupSync<BLOCK>();  // (the next pass clears what this one still reads)
         }
         // did any pass fill its table?
         bool any;

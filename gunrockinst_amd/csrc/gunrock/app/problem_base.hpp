@@ -190,5 +190,39 @@ struct ProblemBase {
     }
 };
 
+// One device array of a problem's slice that grows with the largest need so far and keeps nothing when it does.  The problem's
+// destructor calls Free().
+template <typename T>
+struct Grown {
+    T *p = nullptr;
+    size_t room = 0;
+    hipError_t Need(size_t count)
+    {
+        hipError_t retval = hipSuccess;
+        if (count <= room) return retval;
+        if (p) GR_CHECK(hipFree(p), "grown array hipFree failed");
+        p = nullptr;
+        room = 0;
+        GR_CHECK(hipMalloc(&p, sizeof(T) * count), "grown array hipMalloc failed");
+        room = count;
+        return retval;
+    }
+    // ... and is all 0 when it has grown: for scratch that every kernel leaves as it found it, cleared once
+    hipError_t NeedZeroed(size_t count, hipStream_t stream)
+    {
+        hipError_t retval = hipSuccess;
+        if (count <= room) return retval;
+        if ((retval = Need(count))) return retval;
+        GR_CHECK(hipMemsetAsync(p, 0, sizeof(T) * count, stream), "grown array memset failed");
+        return retval;
+    }
+    void Free()
+    {
+        if (p) util::GRError(hipFree(p), "grown array hipFree failed", __FILE__, __LINE__);
+        p = nullptr;
+        room = 0;
+    }
+};
+
 }  // namespace app
 }  // namespace gunrock

@@ -11,6 +11,7 @@
 #include <cstring>
 
 #include <gunrock/app/enactor_base.hpp>
+#include <gunrock/app/step_host.hpp>
 #include <gunrock/app/rw/rw_functor.hpp>
 #include <gunrock/app/rw/rw_problem.hpp>
 
@@ -36,7 +37,7 @@ struct RwOptions {
     int Set(const char *name, double value, bool weights)
     {
         if (!(value == value)) return -1;
-        const long long v = static_cast<long long>(value < -1e18 ? -1e18 : value > 1e18 ? 1e18 : value);
+        const long long v = Whole(value);
         const bool whole = static_cast<double>(v) == value;
         if (!std::strcmp(name, "strategy")) {
             if (v < RW_AUTO || v > RW_TILE) return -1;
@@ -75,20 +76,15 @@ template <bool INSTRUMENT>
 class RwEnactor : public EnactorBase {
    public:
     explicit RwEnactor(bool DEBUG = false) : EnactorBase(VERTEX_FRONTIERS, DEBUG) {}
-    ~RwEnactor() override
-    {
-        if (ev[0]) hipEventDestroy(ev[0]);
-        if (ev[1]) hipEventDestroy(ev[1]);
-    }
 
     RwOptions options;
 
-    // of the last Enact
+    // of the last Enact (host: its launches and summed kernel time)
+    StepHost<INSTRUMENT> host{"RwEnactor"};
     int length = 0;
     bool with_visits = false;
     int taken = RW_LANE;  // the strategy that ran
-    long long steps = 0, ended = 0, tries = 0, forced = 0, launches = 0;
-    double kernel_ms = 0;  // INSTRUMENT: summed kernel time
+    long long steps = 0, ended = 0, tries = 0, forced = 0;
 
     template <typename Problem>
     hipError_t Enact(Problem *problem, int max_grid_size = 0)
@@ -97,37 +93,13 @@ class RwEnactor : public EnactorBase {
         typename Problem::DataSlice *ds = problem->data_slices[0];
         hipStream_t stream = problem->graph_slices[0]->stream;
         const long long walks = problem->num_walks;
-        steps = ended = tries = forced = launches = 0;
-        kernel_ms = 0;
+        steps = ended = tries = forced = 0;
+        if ((retval = host.Begin(0))) return retval;
         length = options.length;
         with_visits = options.visits != 0;
         taken = options.Strategy();
         if ((retval = problem->NeedWalks(Pitch(length)))) return retval;
         if (with_visits && (retval = problem->NeedVisits())) return retval;
-        if (INSTRUMENT && !ev[0]) {
-            GR_CHECK(hipEventCreate(&ev[0]), "RwEnactor hipEventCreate failed");
-            GR_CHECK(hipEventCreate(&ev[1]), "RwEnactor hipEventCreate failed");
-        }
-        auto grid = [&](long long blocks, long long cap) {
-            if (blocks > cap) blocks = cap;
-            if (blocks < 1) blocks = 1;
-            return static_cast<int>(max_grid_size > 0 && max_grid_size < blocks ? max_grid_size : blocks);
-        };
-        auto begin = [&]() -> hipError_t {
-            return INSTRUMENT ? util::GRError(hipEventRecord(ev[0], stream), "RwEnactor hipEventRecord failed", __FILE__, __LINE__) : hipSuccess;
-        };
-        auto end = [&]() -> hipError_t {
-            ++launches;
-            if (INSTRUMENT) {
-                float ms = 0;
-                GR_CHECK(hipEventRecord(ev[1], stream), "RwEnactor hipEventRecord failed");
-                GR_CHECK(hipEventSynchronize(ev[1]), "RwEnactor hipEventSynchronize failed");
-                GR_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]), "RwEnactor hipEventElapsedTime failed");
-                kernel_ms += ms;
-            }
-            return hipSuccess;
-        };
-
         Ctx c;
         c.ro = ds->d_ro;
         c.ci = ds->d_ci;
@@ -148,34 +120,30 @@ class RwEnactor : public EnactorBase {
         c.tries = options.tries;
 
         GR_CHECK(hipMemsetAsync(ds->d_words, 0, sizeof(unsigned long long) * W_COUNT, stream), "RwEnactor memset failed");
-        const int blocks = grid((walks + kRwThreads - 1) / kRwThreads, 8192);
-        if ((retval = begin())) return retval;
-        if (taken == RW_TILE) hipLaunchKernelGGL(TileKernel, dim3(blocks), dim3(kRwThreads), 0, stream, c);
-        else hipLaunchKernelGGL(LaneKernel, dim3(blocks), dim3(kRwThreads), 0, stream, c);
-        GR_CHECK(hipGetLastError(), "random walk kernel launch failed");
-        if ((retval = end())) return retval;
+        const int blocks = CappedGrid((walks + kRwThreads - 1) / kRwThreads, 8192, max_grid_size);
+        if ((retval = host.Run(stream, [&]() {
+                 if (taken == RW_TILE) hipLaunchKernelGGL(TileKernel, dim3(blocks), dim3(kRwThreads), 0, stream, c);
+                 else hipLaunchKernelGGL(LaneKernel, dim3(blocks), dim3(kRwThreads), 0, stream, c);
+             })))
+            return retval;
         if (with_visits) {
             GR_CHECK(hipMemsetAsync(ds->d_visits, 0, sizeof(unsigned long long) * static_cast<size_t>(problem->nodes), stream), "RwEnactor memset failed");
-            if ((retval = begin())) return retval;
-            hipLaunchKernelGGL(VisitsKernel, dim3(grid((walks * (length + 1) + 255) / 256, 2048)), dim3(256), 0, stream, ds->d_walks, walks, length + 1,
-                               problem->pitch, ds->d_visits);
-            GR_CHECK(hipGetLastError(), "VisitsKernel launch failed");
-            if ((retval = end())) return retval;
+            if ((retval = host.Run(stream, [&]() {
+                     hipLaunchKernelGGL(VisitsKernel, dim3(CappedGrid((walks * (length + 1) + 255) / 256, 2048, max_grid_size)), dim3(256), 0, stream,
+                                        ds->d_walks, walks, length + 1, problem->pitch, ds->d_visits);
+                 })))
+                return retval;
         }
 
         // the one read-back
         unsigned long long words[W_COUNT];
-        GR_CHECK(hipMemcpyAsync(words, ds->d_words, sizeof(words), hipMemcpyDeviceToHost, stream), "RwEnactor read-back failed");
-        GR_CHECK(hipStreamSynchronize(stream), "RwEnactor read-back sync failed");
+        if ((retval = host.Read(words, ds->d_words, sizeof(words), stream))) return retval;
         steps = static_cast<long long>(words[W_STEPS]);
         ended = static_cast<long long>(words[W_ENDED]);
         tries = static_cast<long long>(words[W_TRIES]);
         forced = static_cast<long long>(words[W_FORCED]);
         return retval;
     }
-
-   private:
-    hipEvent_t ev[2] = {nullptr, nullptr};
 };
 
 }  // namespace rw

@@ -35,6 +35,7 @@
 
 #include <gunrock/app/rw/rw_draw.hpp>
 #include <gunrock/graphio/splitmix.hpp>
+#include <gunrock/oprtr/lds_table.hpp>
 #include <gunrock/util/device_intrinsics.hpp>
 
 namespace gunrock {
@@ -168,13 +169,6 @@ __global__ __launch_bounds__(kRwThreads) void LaneKernel(Ctx c)
 
 // ---------------- TILE ----------------
 
-__device__ __forceinline__ void WaveLdsSync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __global__ __launch_bounds__(kRwThreads) void TileKernel(Ctx c)
 {
     __shared__ int s_tiles[kRwWaves][64 * kTileStride];
@@ -204,7 +198,7 @@ __global__ __launch_bounds__(kRwThreads) void TileKernel(Ctx c)
                 }
                 tile[lane * kTileStride + j] = v;
             }
-            WaveLdsSync();
+            oprtr::lds::WaveLdsSync();
             // four lanes a row, 16 rows an instruction.  Unrolled on purpose: it costs 30 VGPRs (94, occupancy 5), and the kernel
             // at 64 VGPRs and occupancy 8 was 12 to 15 % slower in the weighted and biased modes
             const int part = static_cast<int>(lane & 3u) * 4;
@@ -222,7 +216,7 @@ __global__ __launch_bounds__(kRwThreads) void TileKernel(Ctx c)
                     }
                 }
             }
-            WaveLdsSync();
+            oprtr::lds::WaveLdsSync();
         }
         if (mine) {
             c.lengths[w] = count;

@@ -45,7 +45,7 @@ struct SampleOptions {
     int Set(const char *name, double value, bool weights)
     {
         if (!(value == value)) return -1;
-        const long long v = static_cast<long long>(value < -1e18 ? -1e18 : value > 1e18 ? 1e18 : value);
+        const long long v = Whole(value);
         const bool whole = static_cast<double>(v) == value;
         if (!std::strcmp(name, "strategy")) {
             if (v < SAMPLE_AUTO || v > SAMPLE_GROUP) return -1;

@@ -14,6 +14,8 @@
 #include <cstring>
 
 #include <gunrock/app/enactor_base.hpp>
+#include <gunrock/app/step_host.hpp>
+#include <gunrock/app/table_ladder.hpp>
 #include <gunrock/app/sim/sim_functor.hpp>
 #include <gunrock/app/sim/sim_problem.hpp>
 
@@ -29,17 +31,13 @@ struct SimOptions {
     int strategy = SIM_AUTO;
     int skip_neighbors = 0;
     int lane_max = kLaneMax;
-    int table_slots = kTableSlots;
-    int block_slots = kBlockSlots;
-    int scratch_mib = kScratchMib;
-
-    static bool PowerOfTwo(long long v) { return v > 0 && (v & (v - 1)) == 0; }
+    ladder::TableOptions table;  // "table_slots", "block_slots", "scratch_mib"
 
     // 0: set, 1: unknown name, -1: a value out of range
     int Set(const char *name, double value)
     {
         if (!(value == value)) return -1;
-        const long long v = static_cast<long long>(value < -1e18 ? -1e18 : value > 1e18 ? 1e18 : value);
+        const long long v = Whole(value);
         if (!std::strcmp(name, "metric")) {
             if (v < SIM_COMMON || v > SIM_SORENSEN) return -1;
             metric = static_cast<int>(v);
@@ -52,33 +50,24 @@ struct SimOptions {
         } else if (!std::strcmp(name, "lane_max")) {
             if (v < 0 || v > kMaxLaneMax) return -1;
             lane_max = static_cast<int>(v);
-        } else if (!std::strcmp(name, "table_slots")) {
-            if (v < kMinTableSlots || v > kTableSlots || !PowerOfTwo(v)) return -1;
-            table_slots = static_cast<int>(v);
-        } else if (!std::strcmp(name, "block_slots")) {
-            if (v < kMinBlockSlots || v > kBlockSlots || !PowerOfTwo(v)) return -1;
-            block_slots = static_cast<int>(v);
-        } else if (!std::strcmp(name, "scratch_mib")) {
-            if (v < 1 || v > kMaxScratchMib) return -1;
-            scratch_mib = static_cast<int>(v);
         } else {
-            return 1;
+            return table.Set(name, value);
         }
         return 0;
     }
 
     int PairRegimeOf(long long rows) const { return PairRegime(rows, strategy, lane_max); }
-    int TopkRegimeOf(long long wd) const { return TopkRegime(wd, strategy, table_slots, block_slots); }
+    int TopkRegimeOf(long long wd) const { return TopkRegime(wd, strategy, table.table_slots, table.block_slots); }
     // TopkRegime() never falls as Wd grows: the regimes of no wedge and of the largest Wd tell which kernels a graph can need
     bool AnyBlock(long long max_wedges) const { return TopkRegimeOf(0) <= SIM_BLOCK && TopkRegimeOf(max_wedges) >= SIM_BLOCK; }
     bool AnyGlobal(long long max_wedges) const { return TopkRegimeOf(max_wedges) == SIM_GLOBAL; }
-    long long Slots(long long grid, long long nodes) const { return GlobalSlots(grid, scratch_mib, nodes); }
-    size_t SmallLdsBytes() const { return sizeof(int) * 2 * static_cast<size_t>(kSimWaves) * static_cast<size_t>(table_slots); }
+    long long Slots(long long grid, long long nodes) const { return table.Slots(grid, nodes); }
+    size_t SmallLdsBytes() const { return table.SmallLdsBytes(kSimWaves); }
     // the table, or the lists the waves exchange in its place when that takes more
     size_t BlockLdsBytes() const
     {
-        const size_t ints = 2 * static_cast<size_t>(block_slots);
-        return sizeof(int) * (ints > static_cast<size_t>(kExchangeInts) ? ints : static_cast<size_t>(kExchangeInts));
+        const size_t bytes = table.BlockLdsBytes(), exchange = sizeof(int) * static_cast<size_t>(kExchangeInts);
+        return bytes > exchange ? bytes : exchange;
     }
     // what int32 offsets address
     static bool ValidK(long long k) { return k >= 1 && k <= kMaxK; }
@@ -90,21 +79,16 @@ template <bool INSTRUMENT>
 class SimEnactor : public EnactorBase {
    public:
     explicit SimEnactor(bool DEBUG = false) : EnactorBase(VERTEX_FRONTIERS, DEBUG) {}
-    ~SimEnactor() override
-    {
-        if (ev[0]) hipEventDestroy(ev[0]);
-        if (ev[1]) hipEventDestroy(ev[1]);
-    }
 
     SimOptions options;
 
-    // of the last Enact
+    // of the last Enact (host: its launches and summed kernel time)
+    StepHost<INSTRUMENT> host{"SimEnactor"};
     bool refused = false;  // the query is beyond int32 offsets: nothing ran
     bool bad_id = false;   // an id outside [0, nodes): no result was written
-    long long probes = 0, launches = 0, candidates = 0, walked = 0;
+    long long probes = 0, candidates = 0, walked = 0;
     long long regime_pairs[2] = {0, 0};                                 // LANE, WAVE
     long long regime_sources[3] = {0, 0, 0}, regime_wedges[3] = {0, 0, 0};  // WAVE, BLOCK, GLOBAL
-    double kernel_ms = 0;  // INSTRUMENT: summed kernel time
 
     // d_u, d_v: `pairs` ids each, in device memory
     template <typename Problem>
@@ -114,7 +98,7 @@ class SimEnactor : public EnactorBase {
         typename Problem::DataSlice *ds = problem->data_slices[0];
         stream = problem->graph_slices[0]->stream;
         grid_limit = max_grid_size;
-        Clear();
+        if ((retval = Clear())) return retval;
         problem->pairs = -1;
         refused = !SimOptions::PairsFit(pairs);
         if (refused) return retval;
@@ -131,11 +115,11 @@ class SimEnactor : public EnactorBase {
         if ((retval = ds->pair_den.Need(count))) return retval;
         const Ctx c = Context(problem);
         const long long groups = (pairs + util::kWaveSize - 1) / util::kWaveSize;
-        if ((retval = Begin())) return retval;
-        hipLaunchKernelGGL(PairKernel, dim3(Grid((groups + kSimWaves - 1) / kSimWaves, 8192)), dim3(kSimThreads), 0, stream, c, d_u, d_v, pairs,
-                           ds->pair_common.p, ds->pair_num.p, ds->pair_den.p);
-        GR_CHECK(hipGetLastError(), "PairKernel launch failed");
-        if ((retval = End())) return retval;
+        if ((retval = host.Run(stream, [&]() {
+                 hipLaunchKernelGGL(PairKernel, dim3(CappedGrid((groups + kSimWaves - 1) / kSimWaves, 8192, grid_limit)), dim3(kSimThreads), 0, stream, c,
+                                    d_u, d_v, pairs, ds->pair_common.p, ds->pair_num.p, ds->pair_den.p);
+             })))
+            return retval;
         if ((retval = ReadWords(ds))) return retval;
         problem->pairs = pairs;
         return retval;
@@ -150,7 +134,7 @@ class SimEnactor : public EnactorBase {
         stream = problem->graph_slices[0]->stream;
         grid_limit = max_grid_size;
         const long long n = problem->nodes;
-        Clear();
+        if ((retval = Clear())) return retval;
         problem->sources = -1;
         problem->k = 0;
         refused = !SimOptions::TopkFits(sources, k);
@@ -176,40 +160,27 @@ class SimEnactor : public EnactorBase {
         const int S = static_cast<int>(sources);
         int *block_list = ds->lists.p, *global_list = ds->lists.p + rows;
 
-        if ((retval = Begin())) return retval;
-        hipLaunchKernelGGL(SmallKernel, dim3(Grid((sources + kSimWaves - 1) / kSimWaves, 4096)), dim3(kSimThreads), options.SmallLdsBytes(), stream, c,
-                           o, d_sources, S, k, block_list, global_list);
-        GR_CHECK(hipGetLastError(), "SmallKernel launch failed");
-        if ((retval = End())) return retval;
+        if ((retval = host.Run(stream, [&]() {
+                 hipLaunchKernelGGL(SmallKernel, dim3(CappedGrid((sources + kSimWaves - 1) / kSimWaves, 4096, grid_limit)), dim3(kSimThreads),
+                                    options.SmallLdsBytes(), stream, c, o, d_sources, S, k, block_list, global_list);
+             })))
+            return retval;
 
-        if (options.AnyBlock(problem->max_wedges)) {
-            const size_t lds = options.BlockLdsBytes();
-            if (lds > lds_opted) {  // (64 KiB is all a launch gets unasked; asked for once, for the largest table)
-                GR_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&BlockKernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             static_cast<int>(sizeof(int) * 2 * kBlockSlots)),
-                         "SimEnactor hipFuncSetAttribute failed");
-                lds_opted = sizeof(int) * 2 * kBlockSlots;
-            }
-            if ((retval = Begin())) return retval;
-            hipLaunchKernelGGL(BlockKernel, dim3(Grid(sources, 2048)), dim3(kSimThreads), lds, stream, c, o, d_sources, S, k, block_list);
-            GR_CHECK(hipGetLastError(), "BlockKernel launch failed");
-            if ((retval = End())) return retval;
+        if (options.AnyBlock(problem->max_wedges)) {  // (the LDS: asked for once, for the largest table)
+            if ((retval = AllowLds(reinterpret_cast<const void *>(&BlockKernel), ladder::TableOptions::kMaxBlockLdsBytes, &lds_opted))) return retval;
+            if ((retval = host.Run(stream, [&]() {
+                     hipLaunchKernelGGL(BlockKernel, dim3(CappedGrid(sources, 2048, grid_limit)), dim3(kSimThreads), options.BlockLdsBytes(), stream, c, o,
+                                        d_sources, S, k, block_list);
+                 })))
+                return retval;
         }
         if (options.AnyGlobal(problem->max_wedges)) {
-            const int blocks = static_cast<int>(options.Slots(Grid(sources, 1024), n));
-            const size_t need = static_cast<size_t>(blocks) * static_cast<size_t>(n);
-            if (need > ds->row_ints) {
-                if (ds->d_rows) GR_CHECK(hipFree(ds->d_rows), "SimEnactor hipFree failed");
-                ds->d_rows = nullptr;
-                ds->row_ints = 0;
-                GR_CHECK(hipMalloc(&ds->d_rows, sizeof(int) * need), "SimEnactor hipMalloc d_rows failed");
-                GR_CHECK(hipMemsetAsync(ds->d_rows, 0, sizeof(int) * need, stream), "SimEnactor memset failed");  // (once: the kernel leaves them 0)
-                ds->row_ints = need;
-            }
-            if ((retval = Begin())) return retval;
-            hipLaunchKernelGGL(GlobalKernel, dim3(blocks), dim3(kSimThreads), 0, stream, c, o, d_sources, S, k, global_list, ds->d_rows);
-            GR_CHECK(hipGetLastError(), "GlobalKernel launch failed");
-            if ((retval = End())) return retval;
+            const int blocks = static_cast<int>(options.Slots(CappedGrid(sources, 1024, grid_limit), n));
+            if ((retval = ds->rows.NeedZeroed(static_cast<size_t>(blocks) * static_cast<size_t>(n), stream))) return retval;
+            if ((retval = host.Run(stream, [&]() {
+                     hipLaunchKernelGGL(GlobalKernel, dim3(blocks), dim3(kSimThreads), 0, stream, c, o, d_sources, S, k, global_list, ds->rows.p);
+                 })))
+                return retval;
         }
         if ((retval = ReadWords(ds))) return retval;
         problem->sources = sources;
@@ -218,55 +189,24 @@ class SimEnactor : public EnactorBase {
     }
 
    private:
-    hipEvent_t ev[2] = {nullptr, nullptr};
     size_t lds_opted = 0;
     hipStream_t stream = nullptr;
     int grid_limit = 0;
 
-    void Clear()
+    hipError_t Clear()
     {
         refused = bad_id = false;
-        probes = launches = candidates = walked = 0;
+        probes = candidates = walked = 0;
         regime_pairs[0] = regime_pairs[1] = 0;
         for (int r = 0; r < 3; ++r) regime_sources[r] = regime_wedges[r] = 0;
-        kernel_ms = 0;
-    }
-
-    int Grid(long long blocks, long long cap) const
-    {
-        if (blocks > cap) blocks = cap;
-        if (blocks < 1) blocks = 1;
-        return static_cast<int>(grid_limit > 0 && grid_limit < blocks ? grid_limit : blocks);
+        return host.Begin(0);
     }
 
     template <typename DataSlice>
     hipError_t Prepare(DataSlice *ds)
     {
         hipError_t retval = hipSuccess;
-        if (INSTRUMENT && !ev[0]) {
-            GR_CHECK(hipEventCreate(&ev[0]), "SimEnactor hipEventCreate failed");
-            GR_CHECK(hipEventCreate(&ev[1]), "SimEnactor hipEventCreate failed");
-        }
         GR_CHECK(hipMemsetAsync(ds->d_words, 0, sizeof(unsigned long long) * W_COUNT, stream), "SimEnactor memset failed");
-        return retval;
-    }
-
-    hipError_t Begin()
-    {
-        return INSTRUMENT ? util::GRError(hipEventRecord(ev[0], stream), "SimEnactor hipEventRecord failed", __FILE__, __LINE__) : hipSuccess;
-    }
-
-    hipError_t End()
-    {
-        hipError_t retval = hipSuccess;
-        ++launches;
-        if (INSTRUMENT) {
-            float ms = 0;
-            GR_CHECK(hipEventRecord(ev[1], stream), "SimEnactor hipEventRecord failed");
-            GR_CHECK(hipEventSynchronize(ev[1]), "SimEnactor hipEventSynchronize failed");
-            GR_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]), "SimEnactor hipEventElapsedTime failed");
-            kernel_ms += ms;
-        }
         return retval;
     }
 
@@ -284,8 +224,8 @@ class SimEnactor : public EnactorBase {
         c.strategy = options.strategy;
         c.skip_neighbors = options.skip_neighbors;
         c.lane_max = options.lane_max;
-        c.table_slots = options.table_slots;
-        c.block_slots = options.block_slots;
+        c.table_slots = options.table.table_slots;
+        c.block_slots = options.table.block_slots;
         return c;
     }
 
@@ -296,13 +236,12 @@ class SimEnactor : public EnactorBase {
         hipError_t retval = hipSuccess;
         typename Problem::DataSlice *ds = problem->data_slices[0];
         unsigned long long bad = 0;
-        if ((retval = Begin())) return retval;
-        hipLaunchKernelGGL(ValidateIdsKernel, dim3(Grid((count + 255) / 256, 2048)), dim3(256), 0, stream, d_a, d_b, count,
-                           static_cast<int>(problem->nodes), ds->d_words);
-        GR_CHECK(hipGetLastError(), "ValidateIdsKernel launch failed");
-        if ((retval = End())) return retval;
-        GR_CHECK(hipMemcpyAsync(&bad, ds->d_words + W_BAD, sizeof(bad), hipMemcpyDeviceToHost, stream), "SimEnactor read-back failed");
-        GR_CHECK(hipStreamSynchronize(stream), "SimEnactor read-back sync failed");
+        if ((retval = host.Run(stream, [&]() {
+                 hipLaunchKernelGGL(ValidateIdsKernel, dim3(CappedGrid((count + 255) / 256, 2048, grid_limit)), dim3(256), 0, stream, d_a, d_b, count,
+                                    static_cast<int>(problem->nodes), ds->d_words);
+             })))
+            return retval;
+        if ((retval = host.Read(&bad, ds->d_words + W_BAD, sizeof(bad), stream))) return retval;
         bad_id = bad != 0;
         return retval;
     }
@@ -313,8 +252,7 @@ class SimEnactor : public EnactorBase {
     {
         hipError_t retval = hipSuccess;
         unsigned long long words[W_COUNT];
-        GR_CHECK(hipMemcpyAsync(words, ds->d_words, sizeof(words), hipMemcpyDeviceToHost, stream), "SimEnactor read-back failed");
-        GR_CHECK(hipStreamSynchronize(stream), "SimEnactor read-back sync failed");
+        if ((retval = host.Read(words, ds->d_words, sizeof(words), stream))) return retval;
         probes = static_cast<long long>(words[W_PROBES]);
         candidates = static_cast<long long>(words[W_CANDIDATES]);
         walked = static_cast<long long>(words[W_WALKED]);

@@ -31,6 +31,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <gunrock/app/table_ladder.hpp>
+#include <gunrock/oprtr/lds_table.hpp>
 #include <gunrock/util/device_intrinsics.hpp>
 
 namespace gunrock {
@@ -38,6 +40,7 @@ namespace app {
 namespace sim {
 
 enum { SIM_AUTO = 0, SIM_LANE = 1, SIM_WAVE = 2, SIM_BLOCK = 3, SIM_GLOBAL = 4 };  // "strategy"; 1 .. 4 are the regimes
+static_assert(SIM_WAVE == ladder::WAVE && SIM_BLOCK == ladder::BLOCK && SIM_GLOBAL == ladder::GLOBAL, "the ladder's rungs");
 enum { SIM_COMMON = 0, SIM_JACCARD = 1, SIM_OVERLAP = 2, SIM_SORENSEN = 3 };       // "metric"
 
 constexpr int kSimThreads = 256;
@@ -45,14 +48,18 @@ constexpr int kSimWaves = kSimThreads / util::kWaveSize;
 constexpr int kMaxK = 64;             // one entry of the best list per lane
 constexpr int kLaneMax = 64;          // default "lane_max"  (by reasoning)
 constexpr int kMaxLaneMax = 1 << 20;
-constexpr int kTableSlots = 1024;     // default and largest "table_slots": 8 KiB per wave, 32 KiB per workgroup
-constexpr int kMinTableSlots = 64;
-constexpr int kBlockSlots = 8192;     // default and largest "block_slots": 64 KiB
-constexpr int kMinBlockSlots = 256;
-constexpr int kScratchMib = 1024;     // default "scratch_mib"
-constexpr int kMaxScratchMib = 65536;
 constexpr int kExchangeInts = 3 * kSimThreads + kSimWaves;  // Combine()'s LDS: an Entry per thread, a candidate count per wave
 
+// the table's options, their defaults and ranges, are the ladder's (app/table_ladder.hpp)
+using ladder::kTableSlots;
+using ladder::kMinTableSlots;
+using ladder::kBlockSlots;
+using ladder::kMinBlockSlots;
+using ladder::kScratchMib;
+using ladder::kMaxScratchMib;
+using ladder::TableSize;
+
+namespace lds = oprtr::lds;
 using util::Fmix32;
 
 // the 64-bit words the kernels and the host share
@@ -107,27 +114,7 @@ __host__ __device__ __forceinline__ int PairRegime(long long rows, int strategy,
 // The regime of a source with wd wedges: the smallest that holds it, not below a forced one.
 __host__ __device__ __forceinline__ int TopkRegime(long long wd, int strategy, int table_slots, int block_slots)
 {
-    int r = strategy < SIM_WAVE ? SIM_WAVE : strategy;
-    if (r == SIM_WAVE && wd > table_slots / 2) r = SIM_BLOCK;
-    if (r == SIM_BLOCK && wd > block_slots / 2) r = SIM_GLOBAL;
-    return r;
-}
-
-// The slots a table of at most `slots` takes for wd wedges: 2 wd rounded up to a power of two, at least 64 (wd <= slots / 2).
-__host__ __device__ __forceinline__ int TableSize(long long wd, int slots)
-{
-    int size = kMinTableSlots;
-    while (size < slots && size < 2 * wd) size <<= 1;
-    return size;
-}
-
-// The workgroup slots of the GLOBAL regime: min(grid, scratch_mib 2^20 / (4 n)), at least 1.
-__host__ __device__ __forceinline__ long long GlobalSlots(long long grid, long long scratch_mib, long long nodes)
-{
-    const long long row_bytes = 4 * (nodes > 0 ? nodes : 1);
-    long long slots = (scratch_mib << 20) / row_bytes;
-    if (slots > grid) slots = grid;
-    return slots < 1 ? 1 : slots;
+    return ladder::Widen(strategy < SIM_WAVE ? SIM_WAVE : strategy, wd, table_slots, block_slots);
 }
 
 struct Tally {
@@ -360,21 +347,6 @@ __device__ __forceinline__ void WriteRow(const Ctx &c, const TopkOut &o, int s, 
 
 // ---------------- top-k mode: WAVE and BLOCK ----------------
 
-// the lanes of one wave have finished their LDS operations and see each other's
-__device__ __forceinline__ void WaveLdsSync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-template <bool BLOCK>
-__device__ __forceinline__ void GroupSync()
-{
-    if (BLOCK) __syncthreads();
-    else WaveLdsSync();
-}
-
 // The best of source u, by a wave (BLOCK = false) or by the workgroup (BLOCK = true; then each wave has the best of its part of the
 // table and its number of candidates: Combine() follows).  key[] / count[] are the group's table of `slots` slots.
 template <bool BLOCK>
@@ -386,44 +358,26 @@ __device__ __forceinline__ void TableBest(const Ctx &c, int u, int k, int *key, 
     const int lane = static_cast<int>(util::LaneId());
     const int wave = BLOCK ? static_cast<int>(threadIdx.x) / util::kWaveSize : 0;
     const int size = TableSize(c.wd[u], slots);  // (a multiple of 64)
-    const unsigned mask = static_cast<unsigned>(size - 1);
     const int b = c.ro[u], d = c.ro[u + 1] - b;
-    for (int s = tid; s < size; s += G) {
-        key[s] = -1;
-        count[s] = 0;
-    }
-    GroupSync<BLOCK>();
+    lds::Clear<G>(key, size, tid, [&](int s) { count[s] = 0; });
+    lds::GroupSync<BLOCK>();
     for (int i = b + wave; i < b + d; i += WAVES) {  // the count: a wave takes one v at a time and its lanes the w of that v
         const int v = c.ci[i], rv = c.ro[v], dv = c.ro[v + 1] - rv;
         for (int j = lane; j < dv; j += util::kWaveSize) {
             const int w = c.ci[rv + j];
             if (w == u) continue;
-            unsigned at = Fmix32(static_cast<unsigned>(w)) & mask;
-            for (int probe = 0; probe < size; ++probe) {
-                const int was = atomicCAS(key + at, -1, w);
-                ++t.probes;
-                if (was == -1 || was == w) {
-                    atomicAdd(count + at, 1);
-                    break;
-                }
-                at = (at + 1) & mask;
-            }
+            const int at = lds::Claim(key, size, Fmix32(static_cast<unsigned>(w)), w, t.probes);
+            if (at >= 0) atomicAdd(count + at, 1);  // (always: the table never fills)
         }
     }
-    GroupSync<BLOCK>();
+    lds::GroupSync<BLOCK>();
     if (c.skip_neighbors) {  // (uniform) the ends in row u are no candidates
         for (int i = tid; i < d; i += G) {
             const int v = c.ci[b + i];
-            unsigned at = Fmix32(static_cast<unsigned>(v)) & mask;
-            for (int probe = 0; probe < size; ++probe) {
-                const int was = key[at];
-                ++t.probes;
-                if (was == v) count[at] = 0;
-                if (was == v || was == -1) break;
-                at = (at + 1) & mask;
-            }
+            const int at = lds::Find(key, size, Fmix32(static_cast<unsigned>(v)), v, t.probes);
+            if (at >= 0) count[at] = 0;
         }
-        GroupSync<BLOCK>();
+        lds::GroupSync<BLOCK>();
     }
     best = Empty();
     candidates = 0;
@@ -434,7 +388,7 @@ __device__ __forceinline__ void TableBest(const Ctx &c, int u, int k, int *key, 
         Offer(best, valid ? MakeEntry(c, d, w, same) : Empty(), valid, k, lane);
     }
     candidates = util::WaveSum(candidates);
-    if (!BLOCK) WaveLdsSync();  // (the next source clears what this one still reads; a workgroup's Combine() has the barrier)
+    if (!BLOCK) lds::WaveLdsSync();  // (the next source clears what this one still reads; a workgroup's Combine() has the barrier)
 }
 
 // the source of row s enters a regime's tallies, by one thread
@@ -499,13 +453,6 @@ static __global__ __launch_bounds__(kSimThreads) void BlockKernel(Ctx c, TopkOut
 
 // ---------------- top-k mode: GLOBAL ----------------
 
-// every wave's global atomics have been performed and every wave knows
-__device__ __forceinline__ void GlobalSync()
-{
-    __threadfence();
-    __syncthreads();
-}
-
 // One workgroup per row of global_list[], workgroup slot blockIdx.x with its counter row rows_[blockIdx.x * nodes ..), all 0 between two
 // sources.  The host launches no more workgroups than there are counter rows.
 static __global__ __launch_bounds__(kSimThreads) void GlobalKernel(Ctx c, TopkOut o, const int *sources, int rows, int k, const int *global_list,
@@ -528,10 +475,10 @@ static __global__ __launch_bounds__(kSimThreads) void GlobalKernel(Ctx c, TopkOu
                 if (w != u) atomicAdd(row + w, 1);
             }
         }
-        GlobalSync();
+        lds::GlobalSync();
         if (c.skip_neighbors) {  // (uniform)
             for (int i = static_cast<int>(threadIdx.x); i < d; i += kSimThreads) atomicExch(row + c.ci[b + i], 0);
-            GlobalSync();
+            lds::GlobalSync();
         }
         Entry best = Empty();
         int candidates = 0;
@@ -552,7 +499,7 @@ static __global__ __launch_bounds__(kSimThreads) void GlobalKernel(Ctx c, TopkOu
             if (threadIdx.x == 0) t.candidates += static_cast<unsigned long long>(candidates);
             WriteRow(c, o, s, k, best, candidates);
         }
-        GlobalSync();  // (the next source counts in the row this one cleared)
+        lds::GlobalSync();  // (the next source counts in the row this one cleared)
     }
     Flush(t, c);
 }

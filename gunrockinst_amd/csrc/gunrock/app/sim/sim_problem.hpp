@@ -21,30 +21,6 @@ namespace gunrock {
 namespace app {
 namespace sim {
 
-// one device array that grows and keeps nothing when it does
-template <typename T>
-struct Grown {
-    T *p = nullptr;
-    size_t room = 0;
-    hipError_t Need(size_t count)
-    {
-        hipError_t retval = hipSuccess;
-        if (count <= room) return retval;
-        if (p) GR_CHECK(hipFree(p), "SimProblem hipFree failed");
-        p = nullptr;
-        room = 0;
-        GR_CHECK(hipMalloc(&p, sizeof(T) * count), "SimProblem hipMalloc failed");
-        room = count;
-        return retval;
-    }
-    void Free()
-    {
-        if (p) util::GRError(hipFree(p), "SimProblem hipFree failed", __FILE__, __LINE__);
-        p = nullptr;
-        room = 0;
-    }
-};
-
 template <bool _USE_DOUBLE_BUFFER>
 struct SimProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     typedef ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> Base;
@@ -59,8 +35,7 @@ struct SimProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         Grown<long long> pair_num, pair_den;
         Grown<int> ids, common, count, candidates, lists;  // top-k mode's result: S x k, S x k, S, S; 2 S of row lists
         Grown<long long> num, den;
-        int *d_rows = nullptr;  // the GLOBAL regime's counter rows, (re)allocated by Enact, all 0 between launches
-        size_t row_ints = 0;
+        Grown<int> rows;  // the GLOBAL regime's counter rows, grown by Enact, all 0 between launches
     };
 
     DataSlice **data_slices = nullptr;
@@ -78,7 +53,7 @@ struct SimProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         if (data_slices) {
             DataSlice *ds = data_slices[0];
             if (ds) {
-                void *bufs[] = {ds->d_ro, ds->d_ci, ds->d_wd, ds->d_words, ds->d_rows};
+                void *bufs[] = {ds->d_ro, ds->d_ci, ds->d_wd, ds->d_words};
                 for (void *b : bufs)
                     if (b) util::GRError(hipFree(b), "SimProblem hipFree failed", __FILE__, __LINE__);
                 ds->staged_u.Free();
@@ -93,6 +68,7 @@ struct SimProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
                 ds->lists.Free();
                 ds->num.Free();
                 ds->den.Free();
+                ds->rows.Free();
                 delete ds;
             }
             delete[] data_slices;

@@ -2,7 +2,9 @@
 //
 // LoopOptions are the four options every stepped primitive takes and what they decide: which steps go to the device loop.
 // StepHost owns what an Enact needs around its kernels -- the two events of an instrumented launch, the pinned buffer the
-// read-backs land in, the counts of launches and read-backs -- so that an enactor keeps only its own schedule.
+// read-backs land in, the counts of launches and read-backs -- so that an enactor keeps only its own schedule.  The one-shot
+// enactors (c4, sim, rw, tc, clique: a fixed handful of launches and one read-back, no steps) hold one too, with no pinned buffer:
+// Begin(0), Run per kernel, Read at the end; CappedGrid sizes their launches and AllowLds opts a kernel into a large table.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -10,6 +12,7 @@
 #include <climits>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 
 #include <gunrock/oprtr/step.hpp>
 #include <gunrock/util/error_utils.hpp>
@@ -22,18 +25,19 @@ enum { SCHEDULE_AUTO = 0, SCHEDULE_ROUNDS = 1, SCHEDULE_DEVICE_LOOP = 2 };
 
 constexpr int kStepBlocks = 2048;  // the grid of a wide step at the most: 256 CUs x 8 workgroups
 
+// an option's value as a whole number: out of long long's range the nearest end, NaN the low end (below every option's range)
+inline long long Whole(double value)
+{
+    if (!(value == value)) return LLONG_MIN;
+    return value >= 9.0e18 ? LLONG_MAX : (value <= -9.0e18 ? LLONG_MIN : static_cast<long long>(value));
+}
+
 struct LoopOptions {
     int schedule = SCHEDULE_AUTO;
     int wave_min_row = oprtr::kWaveMinRow;
     long long loop_max_list = oprtr::kLoopMaxList;
     long long loop_max_entries = oprtr::kLoopMaxEntries;
 
-    // an option's value as a whole number: out of long long's range the nearest end, NaN the low end (below every option's range)
-    static long long Whole(double value)
-    {
-        if (!(value == value)) return LLONG_MIN;
-        return value >= 9.0e18 ? LLONG_MAX : (value <= -9.0e18 ? LLONG_MIN : static_cast<long long>(value));
-    }
     // a set_option call: 0 taken, -1 a value out of range, 1 not one of these names (the caller looks at its own)
     int Set(const char *name, double value, int max_schedule = SCHEDULE_DEVICE_LOOP)
     {
@@ -86,6 +90,25 @@ inline dim3 StepGrid(long long count, int tile, int waves_per_block, int max_gri
     if (max_grid_size > 0 && blocks > max_grid_size) blocks = max_grid_size;
     if (blocks < 1) blocks = 1;
     return dim3(static_cast<unsigned>(blocks));
+}
+
+// the grid of a one-shot enactor's launch: `blocks` capped at `cap`, then at max_grid_size, at least 1
+inline int CappedGrid(long long blocks, long long cap, int max_grid_size)
+{
+    if (blocks > cap) blocks = cap;
+    if (max_grid_size > 0 && blocks > max_grid_size) blocks = max_grid_size;
+    if (blocks < 1) blocks = 1;
+    return static_cast<int>(blocks);
+}
+
+// `kernel` may be launched with `bytes` of dynamic LDS (64 KiB is all a launch gets unasked): asked for once, *allowed is what it has
+inline hipError_t AllowLds(const void *kernel, size_t bytes, size_t *allowed)
+{
+    if (bytes <= *allowed) return hipSuccess;
+    const hipError_t retval = util::GRError(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes)),
+                                            "hipFuncSetAttribute failed", __FILE__, __LINE__);
+    if (!retval) *allowed = bytes;
+    return retval;
 }
 
 // INSTRUMENT: every launch is timed with two events (and waited for).  `who` names the enactor in the error messages.
@@ -144,13 +167,15 @@ struct StepHost {
         if (ms) *ms = t;
         return retval;
     }
-    // one kernel launch, counted, and timed when instrumented
+    // one kernel launch, counted, and timed when instrumented.  A launch() that gives a hipError_t ends the Run with it when it
+    // fails: the stop event is not recorded.
     template <typename Launch>
     hipError_t Run(hipStream_t stream, Launch launch)
     {
         hipError_t retval = hipSuccess;
         if ((retval = Start(stream))) return retval;
-        launch();
+        if constexpr (std::is_void<decltype(launch())>::value) launch();
+        else if ((retval = launch())) return retval;
         if ((retval = Check(hipGetLastError(), "kernel launch failed", __LINE__))) return retval;
         ++launches;
         return Stop(stream);

@@ -88,9 +88,9 @@ struct C4RunnerT : C4Runner {
             s.regime_wedges[i] = enactor.regime_wedges[i];
         }
         s.probes = enactor.probes;
-        s.launches = enactor.launches;
+        s.launches = enactor.host.launches;
         s.bound = state.ready ? problem.bound : 0;
-        s.kernel_ms = enactor.kernel_ms;
+        s.kernel_ms = enactor.host.kernel_ms;
         s.build_ms = problem.build_ms;
     }
     hipError_t Extract(long long *cycles, long long *total) override

@@ -104,9 +104,9 @@ struct CliqueRunnerT : CliqueRunner {
         }
         s.bit_ands = enactor.bit_ands;
         s.list_lookups = enactor.list_lookups;
-        s.launches = enactor.launches;
+        s.launches = enactor.host.launches;
         s.bound = enactor.bound;
-        s.kernel_ms = enactor.kernel_ms;
+        s.kernel_ms = enactor.host.kernel_ms;
         s.build_ms = problem.build_ms;
     }
     hipError_t Extract(long long *cliques, long long *total) override

@@ -66,7 +66,7 @@ struct MatchingRunnerT : MatchingRunner {
         if (!(value == value)) return -1;  // (NaN)
         const int shared = enactor.loop.Set(name, value, MATCHING_DEVICE_LOOP);
         if (shared != 1) return shared;
-        const long long v = LoopOptions::Whole(value);
+        const long long v = Whole(value);
         if (!std::strcmp(name, "max_rounds")) {
             if (v < 0 || v > kMaxMaxRounds) return -1;  // (0: back to the derived bound)
             enactor.max_rounds = v;

@@ -65,7 +65,7 @@ struct MaxflowRunnerT : MaxflowRunner {
         if (!(value == value)) return -1;  // (NaN)
         const int shared = enactor.loop.Set(name, value, MAXFLOW_DEVICE_LOOP);
         if (shared != 1) return shared;
-        const long long v = LoopOptions::Whole(value);
+        const long long v = Whole(value);
         if (!std::strcmp(name, "discharge_steps")) {
             if (v < 1 || v > 1024) return -1;
             enactor.discharge_steps = static_cast<int>(v);

@@ -86,8 +86,8 @@ struct RwRunnerT : RwRunner {
         s.ended = enactor.ended;
         s.tries = enactor.tries;
         s.forced = enactor.forced;
-        s.launches = enactor.launches;
-        s.kernel_ms = enactor.kernel_ms;
+        s.launches = enactor.host.launches;
+        s.kernel_ms = enactor.host.kernel_ms;
         s.build_ms = problem.build_ms;
     }
     int Extract(int *walks, int *lengths, long long *visits, long long *steps) override

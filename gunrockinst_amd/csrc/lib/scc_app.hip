@@ -64,7 +64,7 @@ struct SccRunnerT : SccRunner {
     {
         const int shared = enactor.loop.Set(name, value, SCC_DEVICE_LOOP);
         if (shared != 1) return shared;
-        const long long v = LoopOptions::Whole(value);
+        const long long v = Whole(value);
         if (!std::strcmp(name, "pivot_phase")) {
             if (v < 0 || v > 1) return -1;
             enactor.pivot_phase = static_cast<int>(v);

@@ -112,8 +112,8 @@ struct SimRunnerT : SimRunner {
         }
         s.candidates = enactor.candidates;
         s.probes = enactor.probes;
-        s.launches = enactor.launches;
-        s.kernel_ms = enactor.kernel_ms;
+        s.launches = enactor.host.launches;
+        s.kernel_ms = enactor.host.kernel_ms;
         s.build_ms = problem.build_ms;
     }
     hipError_t ExtractPairs(int *common, long long *num, long long *den, double *score) override

@@ -85,10 +85,10 @@ struct TcRunnerT : TcRunner {
         oriented = problem.oriented_edges;
         longest = problem.max_out_row;
         probed = enactor.entries_probed;
-        launches = enactor.launches;
+        launches = enactor.host.launches;
         if (regime_rows)
             for (int i = 0; i < 3; ++i) regime_rows[i] = enactor.regime_rows[i];
-        kernel_ms = enactor.kernel_ms;
+        kernel_ms = enactor.host.kernel_ms;
         build_ms = problem.build_ms;
     }
     hipError_t Extract(long long *triangles, long long *total) override

@@ -1,6 +1,7 @@
 // tests/host/c4_check.hip -- the host side of 4-cycle counting without a GPU: C4Options (app/c4/c4_enactor.hpp) parses the options,
-// chooses the regime of a start vertex from its W and sizes the GLOBAL regime's workgroup slots; TableSize and GlobalSlots
-// (app/c4/c4_functor.hpp) are the formulas the kernels share with it.  Every expectation follows from a formula in those headers.
+// chooses the regime of a start vertex from its W and sizes the GLOBAL regime's workgroup slots.  What it shares with similarity --
+// TableSize, GlobalSlots, the three table options on their own -- is pinned in tests/host/table_check.hip.  Every expectation follows
+// from a formula in those headers.
 // Built with -Xarch_host -fsanitize=address,undefined by tests/test_c4_host.py; makes no HIP call.
 #include <cstdio>
 #include <cstdlib>
@@ -31,8 +32,8 @@ int main()
     CHECK(o.Set("count_limit", 0) == -1 && o.Set("count_limit", 9.3e18) == -1 && o.Set("count_limit", nan) == -1);
     CHECK(o.Set("count_limit", 784) == 0 && o.count_limit == 784.0 && o.Set("count_limit", kCountLimit) == 0);
     // a refused value leaves the option as it was
-    CHECK(o.strategy == C4_AUTO && o.lane_max_wedges == kLaneMaxWedges && o.table_slots == kTableSlots && o.block_slots == kBlockSlots &&
-          o.scratch_mib == kScratchMib && o.edges == 1);
+    CHECK(o.strategy == C4_AUTO && o.lane_max_wedges == kLaneMaxWedges && o.table.table_slots == kTableSlots &&
+          o.table.block_slots == kBlockSlots && o.table.scratch_mib == kScratchMib && o.edges == 1);
 
     // the regimes under the defaults: W <= 16 | <= 1024 / 2 | <= 8192 / 2 | the rest
     CHECK(o.RegimeOf(2) == C4_LANE && o.RegimeOf(16) == C4_LANE && o.RegimeOf(17) == C4_WAVE && o.RegimeOf(512) == C4_WAVE);
@@ -54,13 +55,12 @@ int main()
             CHECK(size >= 2 * w && (size & (size - 1)) == 0 && size >= kMinTableSlots && size <= slots);
         }
     }
-    CHECK(TableSize(512, 1024) == 1024 && TableSize(4096, 8192) == 8192 && TableSize(2, 1024) == 64 && TableSize(33, 1024) == 128);
     C4Options no_lane;
     CHECK(no_lane.Set("lane_max_wedges", 0) == 0 && no_lane.RegimeOf(2) == C4_WAVE);
 
     // the GLOBAL regime's slots: min(grid, scratch_mib 2^20 / (4 n)), at least 1
     C4Options d;
-    CHECK(d.scratch_mib == 1024);
+    CHECK(d.table.scratch_mib == 1024);
     CHECK(d.Slots(1024, 1024) == 1024 && d.Slots(1024, 1 << 20) == 256 && d.Slots(1024, 1 << 22) == 64 && d.Slots(1024, 2147483647LL) == 1);
     CHECK(d.Slots(1, 10) == 1 && d.Slots(0, 10) == 1);
     CHECK(d.Set("scratch_mib", 2) == 0 && d.Slots(1024, 300503) == 1 && d.Slots(1024, 262144) == 2);

@@ -1,7 +1,8 @@
 // tests/host/sim_check.hip -- the host side of vertex similarity without a GPU: SimOptions (app/sim/sim_enactor.hpp) parses the options,
 // chooses the regime of a pair from its rows and of a source from its Wd, sizes the tables, the LDS and the GLOBAL regime's workgroup
-// slots and refuses what int32 offsets do not address; Fraction, TableSize and GlobalSlots (app/sim/sim_functor.hpp) are the formulas
-// the kernels share with it.  Every expectation follows from a formula in those headers.
+// slots and refuses what int32 offsets do not address; Fraction (app/sim/sim_functor.hpp) is the formula the kernels share with it.
+// What it shares with 4-cycle counting -- TableSize, GlobalSlots, the three table options on their own -- is pinned in
+// tests/host/table_check.hip.  Every expectation follows from a formula in those headers.
 // Built with -Xarch_host -fsanitize=address,undefined by tests/test_sim_host.py; makes no HIP call.
 #include <cstdio>
 #include <cstdlib>
@@ -40,8 +41,8 @@ int main()
     CHECK(o.Set("block_slots", 128) == -1 && o.Set("block_slots", 16384) == -1 && o.Set("block_slots", -1e300) == -1);
     CHECK(o.Set("scratch_mib", 0) == -1 && o.Set("scratch_mib", kMaxScratchMib + 1) == -1);
     // a refused value leaves the option as it was
-    CHECK(o.metric == SIM_JACCARD && o.strategy == SIM_AUTO && o.skip_neighbors == 0 && o.lane_max == kLaneMax && o.table_slots == kTableSlots &&
-          o.block_slots == kBlockSlots && o.scratch_mib == kScratchMib);
+    CHECK(o.metric == SIM_JACCARD && o.strategy == SIM_AUTO && o.skip_neighbors == 0 && o.lane_max == kLaneMax &&
+          o.table.table_slots == kTableSlots && o.table.block_slots == kBlockSlots && o.table.scratch_mib == kScratchMib);
 
     // the fractions
     CHECK(Is(SIM_COMMON, 3, 5, 7, 3, 1) && Is(SIM_JACCARD, 3, 5, 7, 3, 9) && Is(SIM_OVERLAP, 3, 5, 7, 3, 5) && Is(SIM_SORENSEN, 3, 5, 7, 6, 12));
@@ -85,11 +86,10 @@ int main()
     SimOptions forced;
     CHECK(forced.Set("strategy", SIM_GLOBAL) == 0 && forced.AnyGlobal(0) && !forced.AnyBlock(0) && !forced.AnyBlock(1 << 20));
     CHECK(forced.Set("strategy", SIM_BLOCK) == 0 && forced.AnyBlock(0) && !forced.AnyGlobal(4096) && forced.AnyGlobal(4097));
-    CHECK(TableSize(512, 1024) == 1024 && TableSize(4096, 8192) == 8192 && TableSize(0, 1024) == 64 && TableSize(33, 1024) == 128);
 
     // the GLOBAL regime's slots: min(grid, scratch_mib 2^20 / (4 n)), at least 1
     SimOptions d;
-    CHECK(d.scratch_mib == 1024);
+    CHECK(d.table.scratch_mib == 1024);
     CHECK(d.Slots(1024, 1024) == 1024 && d.Slots(1024, 1 << 20) == 256 && d.Slots(1024, 1 << 22) == 64 && d.Slots(1024, 2147483647LL) == 1);
     CHECK(d.Slots(1, 10) == 1 && d.Slots(0, 10) == 1);
     CHECK(d.Set("scratch_mib", 2) == 0 && d.Slots(1024, 300503) == 1 && d.Slots(1024, 262144) == 2);

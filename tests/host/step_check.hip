@@ -1,5 +1,5 @@
 // The host-callable pieces of gunrock/oprtr/step.hpp and gunrock/app/step_host.hpp -- the tile rule, Narrow and the Limits a
-// schedule gives, the parsing of the four loop options, the grids of a step -- run on their own, without a GPU call, pinned to
+// schedule gives, the parsing of the four loop options, the grids of a step and of a one-shot launch -- run on their own, without a GPU call, pinned to
 // values that follow from their formulas, in a host build with the address and undefined-behaviour sanitizers
 // (tests/test_step_host.py compiles and runs this file that way).  Exit status 0 = every check held.
 #include <climits>
@@ -83,8 +83,11 @@ void SetGivesTheAbiCodes()
     CHECK(o.Set("loop_max_entries", 65536) == 0 && o.loop_max_entries == 65536);
     // values no long long holds are out of range, not undefined
     const double nan = std::numeric_limits<double>::quiet_NaN();
-    CHECK(LoopOptions::Whole(nan) == LLONG_MIN && LoopOptions::Whole(1e300) == LLONG_MAX && LoopOptions::Whole(-1e300) == LLONG_MIN);
-    CHECK(LoopOptions::Whole(-0.9) == 0 && LoopOptions::Whole(2.9) == 2);
+    CHECK(Whole(nan) == LLONG_MIN && Whole(1e300) == LLONG_MAX && Whole(-1e300) == LLONG_MIN);
+    CHECK(Whole(-0.9) == 0 && Whole(2.9) == 2);
+    // ... the ends of the range: 9.0e18 and beyond is LLONG_MAX, below it the value itself (2^62 is exact)
+    CHECK(Whole(9.0e18) == LLONG_MAX && Whole(-9.0e18) == LLONG_MIN && Whole(4611686018427387904.0) == (1ll << 62) &&
+          Whole(-4611686018427387904.0) == -(1ll << 62) && Whole(0.0) == 0 && Whole(-1.0) == -1);
     CHECK(o.Set("schedule", nan) == -1 && o.Set("wave_min_row", nan) == -1 && o.Set("loop_max_list", nan) == -1);
     CHECK(o.Set("loop_max_entries", 1e300) == 0 && o.loop_max_entries == LLONG_MAX);
     CHECK(o.Set("wave_min_row", 1e300) == 0 && o.wave_min_row == (1 << 30));
@@ -104,6 +107,16 @@ void GridsStayInTheirBounds()
     // 256 items per block
     CHECK(GridFor(0, 0).x == 1 && GridFor(256, 0).x == 1 && GridFor(257, 0).x == 2);
     CHECK(GridFor(1ll << 40, 0).x == 2048 && GridFor(1ll << 40, 3).x == 3);
+    // a one-shot enactor's launch: min(blocks, cap), then min(.., max_grid_size) when that is set, at least 1 -- at the borders of
+    // the caps the enactors use
+    for (long long cap : {1024ll, 2048ll, 4096ll, 8192ll}) {
+        CHECK(CappedGrid(cap - 1, cap, 0) == cap - 1 && CappedGrid(cap, cap, 0) == cap && CappedGrid(cap + 1, cap, 0) == cap);
+        CHECK(CappedGrid(1ll << 40, cap, 0) == cap && CappedGrid(1ll << 40, cap, 7) == 7);
+        CHECK(CappedGrid(cap, cap, static_cast<int>(cap)) == cap && CappedGrid(cap, cap, static_cast<int>(cap) - 1) == cap - 1 &&
+              CappedGrid(cap, cap, static_cast<int>(cap) + 1) == cap);
+    }
+    CHECK(CappedGrid(0, 4096, 0) == 1 && CappedGrid(-5, 4096, 0) == 1 && CappedGrid(0, 4096, 3) == 1 && CappedGrid(1, 4096, 1) == 1);
+    CHECK(CappedGrid(5, 4096, 3) == 3 && CappedGrid(3, 4096, 5) == 3 && CappedGrid(5, 4096, -1) == 5 && CappedGrid(2147483647ll, 1ll << 40, 0) == 2147483647);
 }
 
 // An enactor that never ran: nothing was made, so the destructor has nothing to free (and frees nothing twice).
