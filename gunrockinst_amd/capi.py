@@ -328,6 +328,19 @@ _SIGNATURES = {
                                        i32p]),
     "grx_sim_device_results": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 9),
     "grx_sim_destroy": (None, [C.c_void_p]),
+    "grx_spgemm_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int]),
+    "grx_spgemm_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, i32p, i32p, i32p]),
+    "grx_spgemm_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "grx_spgemm_set_right": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, i32p, i32p, i32p]),
+    "grx_spgemm_set_right_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "grx_spgemm_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
+    "grx_spgemm_reset": (C.c_int, [C.c_void_p]),
+    "grx_spgemm_enact": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
+    "grx_spgemm_stats": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_longlong)] * 7 + [C.POINTER(C.c_double)] * 3),
+    "grx_spgemm_sizes": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
+    "grx_spgemm_extract": (C.c_int, [C.c_void_p, i32p, i32p, C.POINTER(C.c_longlong)]),
+    "grx_spgemm_device_results": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 3),
+    "grx_spgemm_destroy": (None, [C.c_void_p]),
     "grx_lp_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int]),
     "grx_lp_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p, i32p]),
     "grx_lp_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -2523,6 +2536,188 @@ def gunrock_similar_vertices(offsets, cols, sources, k, metric=SIM_JACCARD, skip
         p.set_option("skip_neighbors", 1 if skip_neighbors else 0)
     return _one_shot(SimProblem(device=device).init(offsets.shape[0] - 1, offsets, cols), prepare, lambda p: p.topk(sources, k),
                      SimProblem.extract_topk)
+
+
+SPGEMM_AUTO, SPGEMM_LANE, SPGEMM_WAVE, SPGEMM_BLOCK, SPGEMM_GLOBAL = 0, 1, 2, 3, 4  # enum GRX_SPGEMM_* (gunrock_mi355x.h): option "strategy"
+SPGEMM_SELF, SPGEMM_TRANSPOSE, SPGEMM_GIVEN = 0, 1, 2  # option "right"
+SPGEMM_TOO_LARGE = -4  # grx_spgemm_enact: nnz(C) or the products of one row are beyond what int32 addresses
+SPGEMM_OVERFLOW = -7  # grx_spgemm_enact: the bound on the values reached "count_limit"
+
+
+class SpgemmTooLarge(ArithmeticError):
+    """SpgemmProblem.enact: nnz(C) or the products of one row beyond INT_MAX (GRX_SPGEMM_TOO_LARGE): no result was written, the
+    handle takes the next call"""
+
+
+class SpgemmOverflow(ArithmeticError):
+    """SpgemmProblem.enact: max over i of sum over k in A[i] of |a_ik| sum over j of |b_kj| reached "count_limit"
+    (GRX_SPGEMM_OVERFLOW): no result was written, the handle takes the next call"""
+
+
+def _matrix(m):
+    """((rows, cols), offsets, cols, vals or None) as contiguous int32 from (offsets, cols[, vals]) -- square, of len(offsets) - 1
+    rows -- or (shape, offsets, cols[, vals])"""
+    m = tuple(m)
+    shape = None
+    # three parts whose first has two numbers: a shape when the second is the offsets of that many rows over the third (the one-row
+    # matrix (offsets, cols, vals) is not: its column would have to be 1 of 1)
+    if len(m) == 4 or (len(m) == 3 and m[2] is not None and len(m[0]) == 2 and len(m[1]) == int(m[0][0]) + 1
+                       and int(np.asarray(m[1])[-1]) == len(m[2])):
+        shape, m = (int(m[0][0]), int(m[0][1])), m[1:]
+    if len(m) not in (2, 3):
+        raise ValueError("gunrockinst_amd: a matrix is (offsets, cols[, vals]) or (shape, offsets, cols[, vals])")
+    ro, ci = _i32(m[0]).ravel(), _i32(m[1]).ravel()
+    vals = None if len(m) == 2 or m[2] is None else _i32(m[2]).ravel()
+    if shape is None:
+        shape = (ro.shape[0] - 1,) * 2
+    _check_offsets(ro, shape[0])
+    if vals is not None and vals.shape != ci.shape:
+        raise ValueError("gunrockinst_amd: %d values for %d entries" % (vals.shape[0], ci.shape[0]))
+    return shape, ro, ci, vals
+
+
+class SpgemmProblem(_Handle):
+    """SpgemmProblem + SpgemmEnactor behind the handle C ABI: the sparse product C = A B of CSR matrices with int32 values (absent: 1
+    each) read as given -- duplicates add, rows in any order -- as a CSR with strictly ascending rows and exact int64 values.  C is
+    structural: an entry whose products cancel is stored with the value 0."""
+
+    _destroy = "grx_spgemm_destroy"
+
+    _REGIMES = ("lane", "wave", "block", "global")
+
+    def __init__(self, instrument=False, device=0):
+        self._create("grx_spgemm_create", int(instrument), device)
+        self.rows = 0
+        self.inner = 0
+        self.entries = 0
+
+    def init(self, shape, offsets, cols, vals=None):
+        """A of shape (rows, inner) from the host"""
+        (self.rows, self.inner), ro, ci, v = _matrix((shape, offsets, cols, vals))
+        self.entries = int(ci.shape[0])
+        _check(lib().grx_spgemm_init(self._h, self.rows, self.inner, self.entries, _p(ro), _p(ci), None if v is None else _p(v)),
+               "SpgemmProblem::Init")
+        return self
+
+    def init_device(self, shape, nnz, d_offsets, d_cols, d_vals=None):
+        """the CSR stays the caller's and must outlive the handle's enacts"""
+        self.rows, self.inner, self.entries = int(shape[0]), int(shape[1]), int(nnz)
+        _check(lib().grx_spgemm_init_device(self._h, self.rows, self.inner, self.entries, C.c_void_p(d_offsets), C.c_void_p(d_cols),
+                                            C.c_void_p(d_vals) if d_vals else None), "SpgemmProblem::Init(device)")
+        return self
+
+    def set_right(self, shape, offsets, cols, vals=None):
+        """B of shape (inner, cols) from the host; selects SPGEMM_GIVEN.  Returns the library's code: 0, -1 (B's rows are not A's
+        inner) or -2 (not a CSR); anything else raises"""
+        (rows, ncols), ro, ci, v = _matrix((shape, offsets, cols, vals))
+        rc = lib().grx_spgemm_set_right(self._h, rows, ncols, int(ci.shape[0]), _p(ro), _p(ci), None if v is None else _p(v))
+        if rc not in (0, -1, -2):
+            _check(rc, "SpgemmProblem::SetRight")
+        return rc
+
+    def set_right_device(self, shape, nnz, d_offsets, d_cols, d_vals=None):
+        rc = lib().grx_spgemm_set_right_device(self._h, int(shape[0]), int(shape[1]), int(nnz), C.c_void_p(d_offsets), C.c_void_p(d_cols),
+                                               C.c_void_p(d_vals) if d_vals else None)
+        if rc not in (0, -1, -2):
+            _check(rc, "SpgemmProblem::SetRight(device)")
+        return rc
+
+    def set_option(self, name, value):
+        """"right" (SPGEMM_SELF / SPGEMM_TRANSPOSE / SPGEMM_GIVEN), "pattern_only", "strategy" (SPGEMM_AUTO / SPGEMM_LANE / SPGEMM_WAVE /
+        SPGEMM_BLOCK / SPGEMM_GLOBAL), "lane_max", "table_slots", "block_slots", "scratch_mib", "count_limit"; returns the library's
+        code: 0 = set, 1 = unknown name (a value out of range raises)"""
+        rc = lib().grx_spgemm_set_option(self._h, name.encode(), float(value))
+        if rc not in (0, 1):
+            _check(rc, "grx_spgemm_set_option(%s)" % name)
+        return rc
+
+    def reset(self):
+        _check(lib().grx_spgemm_reset(self._h), "SpgemmProblem::Reset")
+
+    def enact(self, max_grid_size=0):
+        """the elapsed milliseconds; SpgemmTooLarge / SpgemmOverflow when the product was refused.  A shape the right operand does
+        not fit raises (code -1)"""
+        ms = C.c_float()
+        rc = lib().grx_spgemm_enact(self._h, int(max_grid_size), C.byref(ms))
+        if rc == SPGEMM_TOO_LARGE:
+            raise SpgemmTooLarge("gunrockinst_amd: SpgemmEnactor::Enact refused: the product is beyond int32 offsets (code %d)" % rc)
+        if rc == SPGEMM_OVERFLOW:
+            raise SpgemmOverflow("gunrockinst_amd: SpgemmEnactor::Enact refused: the bound %.17g reached count_limit (code %d)"
+                                 % (self.stats()["bound"], rc))
+        _check(rc, "SpgemmEnactor::Enact")
+        return float(ms.value)
+
+    def stats(self):
+        rows, products = (C.c_longlong * 4)(), (C.c_longlong * 4)()
+        total, nnz, probes, n, r = (C.c_longlong() for _ in range(5))
+        bound, k, regime_ms = C.c_double(), C.c_double(), (C.c_double * 4)()
+        _check(lib().grx_spgemm_stats(self._h, rows, products, C.byref(total), C.byref(nnz), C.byref(probes), C.byref(n), C.byref(r),
+                                      C.byref(bound), C.byref(k), regime_ms), "grx_spgemm_stats")
+        out = {"products": total.value, "nnz": nnz.value, "table_probes": probes.value, "kernel_launches": n.value, "readbacks": r.value,
+               "bound": bound.value, "kernel_ms": k.value}
+        for i, name in enumerate(self._REGIMES):
+            out[name + "_rows"], out[name + "_products"], out[name + "_ms"] = int(rows[i]), int(products[i]), float(regime_ms[i])
+        return out
+
+    def sizes(self):
+        """(rows, cols, nnz) of the result"""
+        rows, cols, nnz = C.c_int(), C.c_int(), C.c_longlong()
+        _check(lib().grx_spgemm_sizes(self._h, C.byref(rows), C.byref(cols), C.byref(nnz)), "grx_spgemm_sizes")
+        return rows.value, cols.value, nnz.value
+
+    def extract(self, values=True):
+        """{"offsets": int32[rows + 1], "cols": int32[nnz], "vals": int64[nnz] or None, "shape": (rows, cols)} of the last enact"""
+        rows, cols, nnz = self.sizes()
+        offsets, ci = np.empty(rows + 1, dtype=np.int32), np.empty(max(nnz, 1), dtype=np.int32)
+        vals = np.empty(max(nnz, 1), dtype=np.int64) if values else None
+        _check(lib().grx_spgemm_extract(self._h, _p(offsets), _p(ci), None if vals is None else _i64p(vals)), "SpgemmProblem::Extract")
+        return {"offsets": offsets, "cols": ci[:nnz], "vals": None if vals is None else vals[:nnz], "shape": (rows, cols)}
+
+    def device_results(self):
+        """device pointers {"offsets", "cols": int32; "vals": int64} (None without a result, or without entries or values)"""
+        names = ("offsets", "cols", "vals")
+        p = [C.c_void_p() for _ in names]
+        _check(lib().grx_spgemm_device_results(self._h, *[C.byref(x) for x in p]), "grx_spgemm_device_results")
+        return {name: x.value for name, x in zip(names, p)}
+
+
+def gunrock_spgemm(a, b=None, transpose_right=False, pattern_only=False, device=0):
+    """One-shot sparse product: A A (b None), A A^T (transpose_right) or A B.  A matrix is (offsets, cols[, vals]) -- square -- or
+    (shape, offsets, cols[, vals]), CSR with int32 values (absent: 1 each).  Returns {"offsets", "cols", "vals", "shape"}: rows
+    strictly ascending, vals int64 (None with pattern_only); an entry whose products cancel is stored as 0."""
+    if b is not None and transpose_right:
+        raise ValueError("gunrockinst_amd: a right operand and transpose_right exclude each other")
+    shape, ro, ci, vals = _matrix(a)
+
+    def prepare(p):
+        p.set_option("pattern_only", 1 if pattern_only else 0)
+        if transpose_right:
+            p.set_option("right", SPGEMM_TRANSPOSE)
+        if b is not None:
+            _check(p.set_right(*_matrix(b)), "SpgemmProblem::SetRight")
+    return _one_shot(SpgemmProblem(device=device).init(shape, ro, ci, vals), prepare, SpgemmProblem.enact,
+                     lambda p: p.extract(values=not pattern_only))
+
+
+def gunrock_quotient_graph(offsets, cols, weights, labels, device=0):
+    """The contraction P^T A P of the square CSR (offsets, cols) with int32 weights (None: 1 each) by any label map onto 0 .. c - 1
+    (int32 per vertex; LpProblem's dense community ids fit as they are): entry (x, y) is the sum of the weights of the entries that
+    lead from label x to label y, self-loops included.  Two products: T = A P, then P^T T.  Returns {"offsets", "cols", "vals",
+    "shape"}; SpgemmOverflow when a value of T leaves int32."""
+    labels = _i32(labels).ravel()
+    n = _i32(offsets).shape[0] - 1
+    if labels.shape[0] != n:
+        raise ValueError("gunrockinst_amd: %d labels for %d vertices" % (labels.shape[0], n))
+    if n and int(labels.min()) < 0:
+        raise ValueError("gunrockinst_amd: a negative label")
+    c = int(labels.max()) + 1 if n else 0
+    p = ((n, c), np.arange(n + 1, dtype=np.int32), labels)  # row v holds the one entry (v, labels[v])
+    order = np.argsort(labels, kind="stable").astype(np.int32)
+    pt = ((c, n), np.concatenate(([0], np.cumsum(np.bincount(labels, minlength=c)))).astype(np.int32), order)
+    t = gunrock_spgemm(((n, n), offsets, cols, weights), p, device=device)
+    if t["vals"].shape[0] and (int(t["vals"].max()) > 0x7FFFFFFF or int(t["vals"].min()) < -0x80000000):
+        raise SpgemmOverflow("gunrockinst_amd: gunrock_quotient_graph: a weight sum of A P leaves int32")
+    return gunrock_spgemm(pt, ((n, c), t["offsets"], t["cols"], t["vals"].astype(np.int32)), device=device)
 
 
 LP_SYNC, LP_CLASSES = 0, 1  # enum GRX_LP_* (gunrock_mi355x.h): option "mode"

@@ -1293,6 +1293,76 @@ int grx_sim_device_results(grx_sim *p, int **d_pair_common, long long **d_pair_n
 void grx_sim_destroy(grx_sim *p);
 
 /* ------------------------------------------------------------------------------------------------
+ * SPGEMM: SpgemmProblem + SpgemmEnactor: the sparse matrix product C = A B with exact int64 values (no counterpart in the
+ * reference snapshot).  A is rows x inner, B is inner x cols, both CSR read as given: duplicate entries add, a row may come in any
+ * order, self-loops are ordinary entries.  Values are int32, or absent (NULL), which means 1 each.
+ * C is rows x cols CSR: offsets int32[rows + 1], cols int32[nnz] strictly ascending inside a row, vals int64[nnz].  C is
+ * structural (the GraphBLAS rule): entry (i, j) exists exactly when some k has A(i, k) and B(k, j) stored, also when the products
+ * cancel to 0 -- then the stored value is 0.  With the option "pattern_only" the offsets and cols alone are produced; they equal
+ * those of the numeric run.  Integer sums commute: every output has one value, whatever the schedule or the order of the rows.
+ * The right operand, option "right":
+ *   GRX_SPGEMM_SELF       (default) B = A; rows == inner is required
+ *   GRX_SPGEMM_TRANSPOSE  B = A^T, built on the device at the first Enact that asks for it and kept
+ *   GRX_SPGEMM_GIVEN      B from grx_spgemm_set_right / _set_right_device (calling either selects this mode)
+ * Refusals, before any array of the result is written; after either the handle holds no result and takes the next call:
+ *   GRX_SPGEMM_TOO_LARGE  nnz(C) or the products of one row, sum over k in A[i] of len(B[k]), are beyond INT_MAX
+ *   GRX_SPGEMM_OVERFLOW   the bound max over i of (sum over k in A[i] of |a_ik| times the sum over j of |b_kj|), computed on the
+ *                         device in saturating int64, reached the option "count_limit"
+ * The library returns integers only.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct grx_spgemm grx_spgemm;
+enum { GRX_SPGEMM_AUTO = 0, GRX_SPGEMM_LANE = 1, GRX_SPGEMM_WAVE = 2, GRX_SPGEMM_BLOCK = 3, GRX_SPGEMM_GLOBAL = 4 }; /* option "strategy" */
+enum { GRX_SPGEMM_SELF = 0, GRX_SPGEMM_TRANSPOSE = 1, GRX_SPGEMM_GIVEN = 2 };                                        /* option "right" */
+enum { GRX_SPGEMM_TOO_LARGE = -4 };  /* next to -1 / -2 / -3; the value of GRX_SIM_TOO_LARGE */
+enum { GRX_SPGEMM_OVERFLOW = -7 };   /* the value of GRX_C4_OVERFLOW */
+/* instrument != 0: every kernel is timed with HIP events (and waited for) */
+int grx_spgemm_create(grx_spgemm **out, int instrument, int device);
+/* A: rows >= 0, inner >= 0, nnz >= 0; vals may be NULL.  One per handle (-3 for a second one).  -1: a bad argument; -2: offsets or
+ * cols are not a CSR of that shape (checked on the device) */
+int grx_spgemm_init(grx_spgemm *p, int rows, int inner, int nnz, const int *offsets, const int *cols, const int *vals);
+/* the same for arrays in device memory, which stay the caller's and must outlive the handle's Enacts */
+int grx_spgemm_init_device(grx_spgemm *p, int rows, int inner, int nnz, int *d_offsets, int *d_cols, int *d_vals);
+/* B: rows x cols with nnz entries, vals may be NULL; selects GRX_SPGEMM_GIVEN.  May be called again with another B.  -1: a bad
+ * argument or rows != A's inner; -2: not a CSR of that shape (the handle then has no right operand); before Init: hipErrorNotReady */
+int grx_spgemm_set_right(grx_spgemm *p, int rows, int cols, int nnz, const int *offsets, const int *col_indices, const int *vals);
+int grx_spgemm_set_right_device(grx_spgemm *p, int rows, int cols, int nnz, int *d_offsets, int *d_col_indices, int *d_vals);
+/* 0: set; 1: unknown name; -1: a value out of range (the option keeps its value)
+ *   "right"         GRX_SPGEMM_SELF (default) / _TRANSPOSE / _GIVEN
+ *   "pattern_only"  0 (default) / 1: offsets and cols only
+ *   "strategy"      GRX_SPGEMM_AUTO (default): every row takes the smallest regime that holds its products w: lane (w <= lane_max: a
+ *                   sorted list in one lane's private memory), wave (w <= table_slots / 2: a table in the wave's part of LDS),
+ *                   workgroup (w <= block_slots / 2: the workgroup's LDS as one table), global (a dense int64 row and a bitmap per
+ *                   workgroup slot in global scratch); GRX_SPGEMM_WAVE / _BLOCK / _GLOBAL: no row takes a smaller regime
+ *   "lane_max"      0 .. 64 (default 64)
+ *   "table_slots"   a power of two in 64 .. 1024 (default 1024); a slot is 12 bytes of LDS (4 in a pass without values)
+ *   "block_slots"   a power of two in 256 .. 8192 (default 8192: 96 KiB of the CU's 160)
+ *   "scratch_mib"   1 .. 65536 (default 1024): the global regime runs min(grid, scratch_mib 2^20 / (8 cols + 8 ceil(cols / 64)))
+ *                   workgroups, at least one
+ *   "count_limit"   1 .. 2^62 (default 2^62): the refusal GRX_SPGEMM_OVERFLOW */
+int grx_spgemm_set_option(grx_spgemm *p, const char *name, double value);
+/* the handle holds no result */
+int grx_spgemm_reset(grx_spgemm *p);
+/* C = A B.  -1: GRX_SPGEMM_SELF on a non-square A, or GRX_SPGEMM_GIVEN without a right operand; GRX_SPGEMM_TOO_LARGE,
+ * GRX_SPGEMM_OVERFLOW: see above */
+int grx_spgemm_enact(grx_spgemm *p, int max_grid_size, float *elapsed_ms);
+/* any pointer may be NULL.  Of the last Enact: the rows and their products of the regimes lane, wave, workgroup and global
+ * (regime_rows[4], regime_products[4]), the products of all rows, nnz(C), the table probes of the wave and workgroup regimes in
+ * both passes (not reproducible to the last digit: a probe sequence depends on who claimed a slot first), kernel launches (the scan
+ * counts as one), read-backs, the bound held against "count_limit" and -- when instrumented -- the summed kernel time and the part of
+ * it each regime's kernels took in both passes (regime_ms[4]) */
+int grx_spgemm_stats(grx_spgemm *p, long long *regime_rows, long long *regime_products, long long *products, long long *nnz, long long *table_probes,
+                     long long *kernel_launches, long long *readbacks, double *bound, double *kernel_ms, double *regime_ms);
+/* the shape of the result; before a finished Enact (none yet, a Reset since, or a refused one): hipErrorNotReady */
+int grx_spgemm_sizes(grx_spgemm *p, int *rows, int *cols, long long *nnz);
+/* any pointer may be NULL; rows + 1, nnz and nnz entries.  -1: h_vals of a pattern_only result.  Before a finished Enact:
+ * hipErrorNotReady */
+int grx_spgemm_extract(grx_spgemm *p, int *h_offsets, int *h_cols, long long *h_vals);
+/* device arrays of the handle, NULL without a finished Enact (cols, vals: also with an empty result; vals: also with
+ * pattern_only).  They stay valid until the next Enact */
+int grx_spgemm_device_results(grx_spgemm *p, int **d_offsets, int **d_cols, long long **d_vals);
+void grx_spgemm_destroy(grx_spgemm *p);
+
+/* ------------------------------------------------------------------------------------------------
  * LP: LpProblem + LpEnactor: label-propagation communities with integer scores and a total tie rule (no counterpart in the
  * reference snapshot).  The CSR is read exactly as grx_matching_* reads it, as the simple undirected graph G with int32 weights
  * (NULL: 1 each; a pair's weight is the largest of its entries in both directions); a pair weight below 1 is refused.  L[v] is an
