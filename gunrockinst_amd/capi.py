@@ -354,6 +354,18 @@ _SIGNATURES = {
     "grx_lp_summary": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_longlong)] * 4),
     "grx_lp_device_results": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "grx_lp_destroy": (None, [C.c_void_p]),
+    "grx_wl_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int]),
+    "grx_wl_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p]),
+    "grx_wl_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "grx_wl_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
+    "grx_wl_reset": (C.c_int, [C.c_void_p, i32p]),
+    "grx_wl_enact": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
+    "grx_wl_stats": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_longlong)] * 10 + [C.POINTER(C.c_double)]),
+    "grx_wl_round_trace": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_longlong)]),
+    "grx_wl_extract": (C.c_int, [C.c_void_p, i32p, C.POINTER(C.c_longlong), i32p, C.POINTER(C.c_longlong)]),
+    "grx_wl_history": (C.c_int, [C.c_void_p, C.c_int, i32p, C.POINTER(C.c_longlong)]),
+    "grx_wl_device_results": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 3),
+    "grx_wl_destroy": (None, [C.c_void_p]),
     "grx_sssp_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int]),
     "grx_sssp_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p, C.POINTER(C.c_uint32), C.c_int]),
     "grx_sssp_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float]),
@@ -2860,6 +2872,175 @@ def gunrock_label_propagation(nodes, row_offsets, col_indices, weights=None, mod
         st = p.stats()
         return p.extract() + (st["state"], st["rounds"])
     return _one_shot(LpProblem(device=device).init(nodes, row_offsets, col_indices, weights), prepare, LpProblem.enact, result)
+
+
+WL_AUTO, WL_LANE, WL_WAVE, WL_BLOCK = 0, 1, 2, 3  # enum GRX_WL_* (gunrock_mi355x.h): option "strategy"
+WL_STABLE, WL_CAPPED = 0, 1  # stats()["state"]: how the last enact ended
+WL_TOO_LARGE, WL_NOT_CERTIFIED = -4, -5  # grx_wl_enact's codes next to -1
+
+
+class WlTooLarge(ArithmeticError):
+    """the history of a colour refinement, (max_rounds + 1) * nodes colours, is beyond int32 offsets: nothing ran"""
+
+
+class WlNotCertified(RuntimeError):
+    """more than "max_repairs" certificates of a colour refinement failed: there is no result"""
+
+
+def wl_mix(seed, attempt, colour):
+    """The 128-bit mix of one entry of a row as (lo, hi): app/wl/wl_functor.hpp's Mix().  The signature of a row in signature pass
+    `attempt` (1, 2, ...) is the wrapping 128-bit sum of the mixes of its entries' colours, a colour being the smallest member of a
+    class, cut to its top "sig_bits" bits."""
+    m = (1 << 64) - 1
+
+    def mix(x):
+        x = (x + 0x9E3779B97F4A7C15) & m
+        x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & m
+        x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & m
+        return x ^ (x >> 31)
+    x = ((int(attempt) << 32) | (int(colour) & 0xFFFFFFFF)) & m
+    return mix((int(seed) & m) ^ mix(x)), mix((int(seed) & m) ^ mix(x ^ m))
+
+
+class WlProblem(_Handle):
+    """WlProblem + WlEnactor behind the handle C ABI: colour refinement (1-WL) of the CSR as given -- a row is the multiset of its
+    entries -- from the classes of any int32 start labels down to the coarsest equitable partition, or for a fixed number of rounds.
+    The classes are numbered by ascending smallest member; every result is certified by an exact comparison of rows."""
+
+    _destroy = "grx_wl_destroy"
+
+    _STATS = ("entries", "rounds", "state", "classes", "repairs", "certificate_runs")
+    _STATS_TAIL = ("kernel_launches", "readbacks")
+
+    def __init__(self, instrument=False, device=0):
+        self._create("grx_wl_create", int(instrument), device)
+        self.nodes = 0
+        self.entries = 0
+
+    def init(self, nodes, row_offsets, col_indices):
+        ro, ci = _csr_arrays(row_offsets, col_indices, nodes)
+        self.nodes, self.entries = int(nodes), int(ci.shape[0])
+        _check(lib().grx_wl_init(self._h, self.nodes, self.entries, _p(ro), _p(ci)), "WlProblem::Init")
+        return self
+
+    def init_device(self, nodes, edges, d_row_offsets, d_col_indices):
+        """the CSR stays the caller's and is read by every enact: it has to outlive the handle"""
+        self.nodes, self.entries = int(nodes), int(edges)
+        _check(lib().grx_wl_init_device(self._h, self.nodes, self.entries, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices)),
+               "WlProblem::Init(device)")
+        return self
+
+    def set_option(self, name, value):
+        """"strategy" (WL_AUTO / WL_LANE / WL_WAVE / WL_BLOCK), "lane_max_row", "wave_max_row", "max_rounds", "history", "max_repairs",
+        "sig_bits", "seed", "table_slots", "block_slots", "scratch_mib"; returns the library's code: 0 = set, 1 = unknown name (a value
+        out of range raises)"""
+        rc = lib().grx_wl_set_option(self._h, name.encode(), float(value))
+        if rc not in (0, 1):
+            _check(rc, "grx_wl_set_option(%s)" % name)
+        return rc
+
+    def reset(self, labels=None):
+        """the start labels: int32 of any value per vertex, or None for one class"""
+        lb = None if labels is None else _i32(labels)
+        if lb is not None and lb.shape[0] != self.nodes:
+            raise ValueError("gunrockinst_amd: %d labels for %d nodes" % (lb.shape[0], self.nodes))
+        _check(lib().grx_wl_reset(self._h, None if lb is None else _p(lb)), "WlProblem::Reset")
+
+    def enact(self, max_grid_size=0):
+        """the elapsed milliseconds; stats()["state"] tells how it ended.  WlNotCertified, WlTooLarge: there is no result"""
+        ms = C.c_float()
+        rc = lib().grx_wl_enact(self._h, int(max_grid_size), C.byref(ms))
+        if rc == WL_NOT_CERTIFIED:
+            raise WlNotCertified("gunrockinst_amd: WlEnactor::Enact: more certificates failed than max_repairs allows")
+        if rc == WL_TOO_LARGE:
+            raise WlTooLarge("gunrockinst_amd: WlEnactor::Enact: the history is beyond int32 offsets")
+        _check(rc, "WlEnactor::Enact")
+        return float(ms.value)
+
+    def stats(self):
+        v = [C.c_longlong() for _ in self._STATS]
+        regime, rung = (C.c_longlong * 3)(), (C.c_longlong * 3)()
+        tail = [C.c_longlong() for _ in self._STATS_TAIL]
+        k = C.c_double()
+        _check(lib().grx_wl_stats(self._h, *([C.byref(x) for x in v] + [regime, rung] + [C.byref(x) for x in tail] + [C.byref(k)])),
+               "grx_wl_stats")
+        out = {name: x.value for name, x in zip(self._STATS + self._STATS_TAIL, v + tail)}
+        out["regime_rows"] = [int(x) for x in regime]
+        out["rung_rows"] = [int(x) for x in rung]
+        out["kernel_ms"] = k.value
+        return out
+
+    def round_trace(self):
+        """the classes behind the labels and behind each committed round of the last enact, int64 (rounds + 1 entries)"""
+        count = lib().grx_wl_round_trace(self._h, 0, None)
+        if count < 0:
+            _check(count, "grx_wl_round_trace")
+        classes = np.empty(max(count, 1), dtype=np.int64)
+        lib().grx_wl_round_trace(self._h, count, _i64p(classes))
+        return classes[:count]
+
+    def extract(self):
+        """(colour int32 per vertex, class_size int64 per class, representative int32 per class: its smallest member)"""
+        count = C.c_longlong()
+        _check(lib().grx_wl_extract(self._h, None, None, None, C.byref(count)), "WlProblem::Extract")
+        k = int(count.value)
+        colour, size, rep = np.empty(max(self.nodes, 1), np.int32), np.empty(max(k, 1), np.int64), np.empty(max(k, 1), np.int32)
+        _check(lib().grx_wl_extract(self._h, _p(colour), _i64p(size), _p(rep), None), "WlProblem::Extract")
+        return colour[:self.nodes], size[:k], rep[:k]
+
+    def history(self):
+        """the dense colouring behind every round 0 .. rounds of the last enact with "history": int32, (rounds + 1) x nodes"""
+        rounds = self.stats()["rounds"]
+        out = np.empty((rounds + 1, max(self.nodes, 1)), np.int32)
+        for h in range(rounds + 1):
+            _check(lib().grx_wl_history(self._h, h, _p(out[h]), None), "WlProblem::History")
+        return out[:, :self.nodes]
+
+    def device_results(self):
+        """device pointers {"colour": int32 per vertex, "class_size": int64 per class, "representative": int32 per class}"""
+        a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(lib().grx_wl_device_results(self._h, C.byref(a), C.byref(b), C.byref(c)), "grx_wl_device_results")
+        return {"colour": a.value, "class_size": b.value, "representative": c.value}
+
+
+def gunrock_colour_refinement(nodes, row_offsets, col_indices, labels=None, max_rounds=-1, history=False, seed=0, device=0):
+    """One-shot colour refinement: returns {"colour", "class_size", "representative", "classes", "state", "rounds"} and, with
+    history (max_rounds in 1 .. 64), "history": the colouring behind every round, the WL-h features for h = 0 .. rounds."""
+    def prepare(p):
+        p.set_option("max_rounds", max_rounds)
+        p.set_option("history", 1 if history else 0)
+        p.set_option("seed", seed)
+        p.reset(labels)
+
+    def result(p):
+        st = p.stats()
+        colour, size, rep = p.extract()
+        out = {"colour": colour, "class_size": size, "representative": rep, "classes": st["classes"], "state": st["state"],
+               "rounds": st["rounds"]}
+        if history:
+            out["history"] = p.history()
+        return out
+    return _one_shot(WlProblem(device=device).init(nodes, row_offsets, col_indices), prepare, WlProblem.enact, result)
+
+
+def gunrock_wl_test(graph_a, graph_b, labels_a=None, labels_b=None, device=0):
+    """The 1-WL isomorphism screen of two graphs, each (row_offsets, col_indices): the disjoint union is refined and the class
+    histograms of the two halves compared.  False: the graphs are certainly not isomorphic; True: 1-WL cannot tell them apart.
+    Labels are given for both graphs or for neither."""
+    if (labels_a is None) != (labels_b is None):
+        raise ValueError("gunrockinst_amd: labels for one graph only")
+    (ro_a, ci_a), (ro_b, ci_b) = _csr_arrays(*graph_a), _csr_arrays(*graph_b)
+    na, nb = ro_a.shape[0] - 1, ro_b.shape[0] - 1
+    if na != nb or ci_a.shape[0] != ci_b.shape[0]:
+        return False
+    if na == 0:
+        return True
+    ro = np.concatenate([ro_a, ro_b[1:] + ro_a[-1]]).astype(np.int32)
+    ci = np.concatenate([ci_a, ci_b + na]).astype(np.int32)
+    labels = None if labels_a is None else np.concatenate([_i32(labels_a).ravel(), _i32(labels_b).ravel()])
+    got = gunrock_colour_refinement(na + nb, ro, ci, labels=labels, device=device)
+    k = got["classes"]
+    return bool(np.array_equal(np.bincount(got["colour"][:na], minlength=k), np.bincount(got["colour"][na:], minlength=k)))
 
 
 MSBFS_AUTO, MSBFS_PUSH, MSBFS_PULL, MSBFS_ALTERNATE = 0, 1, 2, 3  # enum GRX_MSBFS_* (gunrock_mi355x.h): option "direction"

@@ -1431,6 +1431,69 @@ int grx_lp_device_results(grx_lp *p, int **d_labels, int **d_community);
 void grx_lp_destroy(grx_lp *p);
 
 /* ------------------------------------------------------------------------------------------------
+ * WL: WlProblem + WlEnactor: colour refinement, the 1-dimensional Weisfeiler-Leman test (no counterpart in the reference
+ * snapshot).  The CSR is read as given, like grx_rw_*: a row is the multiset of its entries, duplicates and self-loops count,
+ * one-way entries are one-way.  The start colours are the classes of labels[] (any int32 values; NULL: one class).  A round maps
+ * the colouring c to c' with c'(u) = c'(v) iff c(u) = c(v) and the multisets {c(w) : w in row(u)} and {c(w) : w in row(v)} are
+ * equal; the partition is stable when a round splits nothing, and it is then the coarsest equitable partition that refines the
+ * labels.  The classes are numbered 0 .. count - 1 by ascending smallest member.  Rows are grouped by a seeded hash of their
+ * multiset; a certificate that compares rows exactly stands behind every result, so every output is an integer with one value.
+ * An Enact ends GRX_WL_STABLE or, behind "max_rounds" rounds, GRX_WL_CAPPED; neither is an error.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct grx_wl grx_wl;
+enum { GRX_WL_AUTO = 0, GRX_WL_LANE = 1, GRX_WL_WAVE = 2, GRX_WL_BLOCK = 3 };  /* option "strategy" */
+enum { GRX_WL_STABLE = 0, GRX_WL_CAPPED = 1 };                                 /* `state` of grx_wl_stats */
+enum { GRX_WL_TOO_LARGE = -4, GRX_WL_NOT_CERTIFIED = -5 };                     /* grx_wl_enact, next to -1 / -2 / -3 */
+
+int grx_wl_create(grx_wl **out, int instrument, int device);
+/* WlProblem::Init: validates the CSR on the device.  -1: nodes < 1, edges < 0 or a NULL array; -2: not a CSR of `nodes` vertices;
+ * -3: the handle has been given a graph before (accepted or rejected) */
+int grx_wl_init(grx_wl *p, int nodes, int edges, const int *row_offsets, const int *col_indices);
+/* the same for a CSR already in HBM: borrowed, not freed, read by every Enact (it has to outlive the handle) */
+int grx_wl_init_device(grx_wl *p, int nodes, int edges, int *d_row_offsets, int *d_col_indices);
+/* named options, for the next Enact; 0: set, 1: unknown name, -1: a value out of range.  Only "max_rounds" and "history" change
+ * a result.
+ *   "strategy"      the signature pass: GRX_WL_AUTO (default): a row of up to "lane_max_row" entries is summed by one lane, one
+ *                   of up to "wave_max_row" by a wave, a longer one by a workgroup; GRX_WL_LANE / _WAVE / _BLOCK force one
+ *   "lane_max_row"  default 16, at least 0
+ *   "wave_max_row"  default 4096, at least 0
+ *   "max_rounds"    -1 (default): refine until stable; h >= 0 (at most 2^30): the colouring after h rounds, every round certified
+ *   "history"       1: keep the colouring behind every round for grx_wl_history; asks for "max_rounds" in 1 .. 64
+ *   "max_repairs"   failed certificates an Enact takes before it gives up (default 64, 0 .. 2^30)
+ *   "sig_bits"      the top bits of the signature that are compared, 1 .. 128 (default 128); fewer make the certificate fail more often
+ *   "seed"          of the signatures, a whole number below 2^64
+ *   "table_slots", "block_slots", "scratch_mib"   the certificate's count table, as for grx_sim_set_option: a vertex whose row and
+ *                   its representative's together hold w entries is compared in a wave's table while w <= table_slots / 2, in the
+ *                   workgroup's while w <= block_slots / 2, else in a dense counter row of global scratch */
+int grx_wl_set_option(grx_wl *p, const char *name, double value);
+/* WlProblem::Reset: the start labels, `nodes` int32 of any value, or NULL for one class.  An Enact without a Reset in front starts
+ * from the labels of the last one */
+int grx_wl_reset(grx_wl *p, const int *labels /* or NULL */);
+/* WlEnactor::Enact(problem, max_grid_size), HIP-event timed.  0 in both end states (grx_wl_stats tells which); -1: "history"
+ * without "max_rounds" in 1 .. 64; GRX_WL_TOO_LARGE: the history, (max_rounds + 1) * nodes colours, is beyond int32 offsets;
+ * GRX_WL_NOT_CERTIFIED: more than "max_repairs" certificates failed.  After any of the three there is no result */
+int grx_wl_enact(grx_wl *p, int max_grid_size, float *elapsed_ms);
+/* any pointer may be NULL.  The entries of the graph; of the last Enact: the committed rounds (each split a class), the end state,
+ * the classes, the failed certificates, the certificates run, the rows of all signature passes per regime (regime_rows[3]: lane,
+ * wave, workgroup), the vertices compared per rung of the certificate (rung_rows[3]: wave, workgroup, global), kernel launches,
+ * host read-backs (one for the labels, one per signature pass) and -- when instrumented -- the summed kernel time */
+int grx_wl_stats(grx_wl *p, long long *entries, long long *rounds, long long *state, long long *classes, long long *repairs,
+                 long long *certificate_runs, long long *regime_rows, long long *rung_rows, long long *kernel_launches, long long *readbacks,
+                 double *kernel_ms);
+/* the classes behind the labels and behind each committed round of the last Enact (rounds + 1 entries); copies at most max_rounds
+ * entries and returns how many there are */
+int grx_wl_round_trace(grx_wl *p, int max_rounds, long long *classes);
+/* colour[]: `nodes` int32, the dense class of every vertex; class_size[]: int64 per class; representative[]: int32 per class, its
+ * smallest member; any may be NULL; *classes: how many there are.  Before a finished Enact: hipErrorNotReady */
+int grx_wl_extract(grx_wl *p, int *h_colour, long long *h_class_size, int *h_representative, long long *classes);
+/* the dense colouring behind round `round` (0: the labels' classes) of the last Enact with "history", and its classes; -1: no
+ * such round; hipErrorNotReady: no finished Enact with "history" */
+int grx_wl_history(grx_wl *p, int round, int *h_colour, long long *classes);
+/* device arrays of the handle, NULL without a finished Enact: colour (`nodes` int32), class_size (int64), representative (int32) */
+int grx_wl_device_results(grx_wl *p, int **d_colour, long long **d_class_size, int **d_representative);
+void grx_wl_destroy(grx_wl *p);
+
+/* ------------------------------------------------------------------------------------------------
  * SSSP: SSSPProblem + SSSPEnactor (reference gunrock/app/sssp/sssp_problem.cuh:35-387, sssp_enactor.cuh:36-563)
  * ---------------------------------------------------------------------------------------------- */
 typedef struct grx_sssp grx_sssp;
