@@ -27,57 +27,29 @@ struct BccProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     typedef ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> Base;
 
     struct DataSlice {
-        int *d_src = nullptr, *d_dst = nullptr;                   // the canonical edges
-        int *d_nro = nullptr, *d_nci = nullptr, *d_neid = nullptr;  // the neighbour CSR, rows ascending, and the edge of every entry
+        DeviceArray<int> d_src, d_dst;  // the canonical edges
+        DeviceArray<int> d_nro, d_nci, d_neid;  // the neighbour CSR, rows ascending, and the edge of every entry
         // per vertex
-        int *d_comp = nullptr, *d_parent = nullptr, *d_level = nullptr, *d_pedge = nullptr, *d_size = nullptr, *d_pre = nullptr, *d_low = nullptr,
-            *d_high = nullptr, *d_queue = nullptr, *d_uf = nullptr, *d_set = nullptr, *d_first = nullptr, *d_tecc = nullptr, *d_tsize = nullptr, *d_min_of = nullptr,
-            *d_cnt_of = nullptr;
-        int *d_bounds = nullptr;       // nodes + 2
-        unsigned *d_ents = nullptr;    // nodes + 2
+        DeviceArray<int> d_comp, d_parent, d_level, d_pedge, d_size, d_pre, d_low, d_high, d_queue, d_uf, d_set, d_first, d_tecc, d_tsize, d_min_of, d_cnt_of;
+        DeviceArray<int> d_bounds;  // nodes + 2
+        DeviceArray<unsigned> d_ents;  // nodes + 2
         // per edge
-        int *d_bcc = nullptr, *d_bsize = nullptr;
-        unsigned char *d_bridge = nullptr, *d_art = nullptr;
-        int *d_cut_vertex = nullptr, *d_cut_block = nullptr;  // the block-cut tree of the last Enact, built at the first request
-        unsigned *d_words = nullptr;
-        unsigned long long *d_counters = nullptr;  // [0] row entries walked, [1] articulation points, [2..4] and [5..7] SummaryKernel's
-        unsigned long long *d_clock = nullptr;     // PHASE_COUNT + 1 stamps
-        Front *d_front = nullptr;
+        DeviceArray<int> d_bcc, d_bsize;
+        DeviceArray<unsigned char> d_bridge, d_art;
+        DeviceArray<int> d_cut_vertex, d_cut_block;  // the block-cut tree of the last Enact, built at the first request
+        DeviceArray<unsigned> d_words;
+        DeviceArray<unsigned long long> d_counters;  // [0] row entries walked, [1] articulation points, [2..4] and [5..7] SummaryKernel's
+        DeviceArray<unsigned long long> d_clock;  // PHASE_COUNT + 1 stamps
+        DeviceArray<Front> d_front;
     };
 
-    DataSlice **data_slices = nullptr;
-    int malformed = 0;
+    SliceHolder<DataSlice> data_slices;
     long long simple_edges = 0;  // M
     bool fresh = false;          // Reset has run and Enact has not
     bool enacted = false;        // the arrays hold a result
     double build_ms = 0;         // HIP-event time of the build of the edges and the neighbour CSR
     Summary summary;             // of the last Enact
     long long cut_pairs = -1;    // the pairs in d_cut_vertex / d_cut_block (-1: not built)
-
-    ~BccProblem() override
-    {
-        if (data_slices) {
-            DataSlice *ds = data_slices[0];
-            if (ds) {
-                void *bufs[] = {ds->d_src, ds->d_dst, ds->d_nro, ds->d_nci, ds->d_neid, ds->d_comp, ds->d_parent, ds->d_level, ds->d_pedge, ds->d_size,
-                                ds->d_pre, ds->d_low, ds->d_high, ds->d_queue, ds->d_uf, ds->d_set, ds->d_first, ds->d_tecc, ds->d_tsize, ds->d_min_of, ds->d_cnt_of,
-                                ds->d_bounds, ds->d_ents, ds->d_bcc, ds->d_bsize, ds->d_bridge, ds->d_art, ds->d_cut_vertex, ds->d_cut_block, ds->d_words, ds->d_counters, ds->d_clock,
-                                ds->d_front};
-                for (void *b : bufs)
-                    if (b) util::GRError(hipFree(b), "BccProblem hipFree failed", __FILE__, __LINE__);
-                delete ds;
-            }
-            delete[] data_slices;
-        }
-    }
-
-    static int Grid(long long work)
-    {
-        long long blocks = (work + 255) / 256;
-        if (blocks < 1) blocks = 1;
-        if (blocks > 2048) blocks = 2048;  // 256 CUs x 8 workgroups, grid-stride the rest
-        return static_cast<int>(blocks);
-    }
 
     Ctx DeviceCtx(int wave_min_row) const
     {
@@ -117,19 +89,13 @@ struct BccProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         hipStream_t stream = gs->stream;
         const long long n = this->nodes, m = this->edges;
         const size_t n1 = static_cast<size_t>(n > 0 ? n : 1);
-        GR_CHECK(hipMalloc(&ds->d_words, sizeof(unsigned) * W_COUNT), "BccProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_counters, sizeof(unsigned long long) * 8), "BccProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_clock, sizeof(unsigned long long) * (PHASE_COUNT + 1)), "BccProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_front, sizeof(Front)), "BccProblem hipMalloc failed");
+        if ((retval = ds->d_words.Alloc(W_COUNT))) return retval;
+        if ((retval = ds->d_counters.Alloc(8))) return retval;
+        if ((retval = ds->d_clock.Alloc(PHASE_COUNT + 1))) return retval;
+        if ((retval = ds->d_front.Alloc(1))) return retval;
 
         // the CSR must be one: the build indexes with what it reads
-        bool bad = false;
-        if ((retval = graphio::DeviceValidateCsr(gs->d_row_offsets, gs->d_column_indices, n, m, reinterpret_cast<int *>(ds->d_words), stream, &bad)))
-            return retval;
-        if (bad) {
-            malformed = 1;
-            return hipErrorInvalidValue;
-        }
+        if ((retval = this->ValidateCsr())) return retval;
 
         long long M = 0;
         {  // (the build's scratch goes with this scope)
@@ -140,11 +106,11 @@ struct BccProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
             if ((retval = pg.Keys(gs->d_row_offsets, gs->d_column_indices, m, stream))) return retval;
             if ((retval = pg.Pairs(stream))) return retval;
             if ((retval = pg.Rows(stream))) return retval;
-            ds->d_src = graphio::Take(pg.d_src);
-            ds->d_dst = graphio::Take(pg.d_dst);
-            ds->d_nro = graphio::Take(pg.d_ro);
-            ds->d_nci = graphio::Take(pg.d_ci);
-            ds->d_neid = graphio::Take(pg.d_eid);
+            ds->d_src.Adopt(graphio::Take(pg.d_src));
+            ds->d_dst.Adopt(graphio::Take(pg.d_dst));
+            ds->d_nro.Adopt(graphio::Take(pg.d_ro));
+            ds->d_nci.Adopt(graphio::Take(pg.d_ci));
+            ds->d_neid.Adopt(graphio::Take(pg.d_eid));
             simple_edges = M = pg.pairs;
             if ((retval = ev.Record(1, stream))) return retval;
             GR_CHECK(hipStreamSynchronize(stream), "BccProblem build sync failed");
@@ -152,15 +118,15 @@ struct BccProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         }
 
         const size_t m1 = static_cast<size_t>(M > 0 ? M : 1);
-        int **vertex_arrays[] = {&ds->d_comp, &ds->d_parent, &ds->d_level, &ds->d_pedge, &ds->d_size, &ds->d_pre, &ds->d_low, &ds->d_high, &ds->d_queue,
+        DeviceArray<int> *vertex_arrays[] = {&ds->d_comp, &ds->d_parent, &ds->d_level, &ds->d_pedge, &ds->d_size, &ds->d_pre, &ds->d_low, &ds->d_high, &ds->d_queue,
                                  &ds->d_uf, &ds->d_set, &ds->d_first, &ds->d_tecc, &ds->d_tsize, &ds->d_min_of, &ds->d_cnt_of};
-        for (int **a : vertex_arrays) GR_CHECK(hipMalloc(a, sizeof(int) * n1), "BccProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_bounds, sizeof(int) * (n1 + 2)), "BccProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_ents, sizeof(unsigned) * (n1 + 2)), "BccProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_bcc, sizeof(int) * m1), "BccProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_bsize, sizeof(int) * m1), "BccProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_bridge, m1), "BccProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_art, n1), "BccProblem hipMalloc failed");
+        for (DeviceArray<int> *a : vertex_arrays) if ((retval = a->Alloc(n1))) return retval;
+        if ((retval = ds->d_bounds.Alloc(n1 + 2))) return retval;
+        if ((retval = ds->d_ents.Alloc(n1 + 2))) return retval;
+        if ((retval = ds->d_bcc.Alloc(m1))) return retval;
+        if ((retval = ds->d_bsize.Alloc(m1))) return retval;
+        if ((retval = ds->d_bridge.Alloc(m1))) return retval;
+        if ((retval = ds->d_art.Alloc(n1))) return retval;
         return retval;
     }
 
@@ -169,8 +135,7 @@ struct BccProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     {
         hipError_t retval = hipSuccess;
         if ((retval = Base::Init(stream_from_host, graph, num_gpus, false))) return retval;
-        data_slices = new DataSlice *[1];
-        data_slices[0] = new DataSlice();
+        data_slices.Make();
         return Build();
     }
 
@@ -178,8 +143,7 @@ struct BccProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     {
         hipError_t retval = hipSuccess;
         if ((retval = Base::InitFromDevice(nodes, edges, d_row_offsets, d_column_indices))) return retval;
-        data_slices = new DataSlice *[1];
-        data_slices[0] = new DataSlice();
+        data_slices.Make();
         return Build();
     }
 
@@ -205,25 +169,13 @@ struct BccProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         return retval;
     }
 
-    template <typename T>
-    hipError_t Read(T *h_out, const T *d_in, size_t count)
-    {
-        hipError_t retval = hipSuccess;
-        hipStream_t stream = this->graph_slices[0]->stream;
-        if (h_out && count) {
-            GR_CHECK(hipMemcpyAsync(h_out, d_in, sizeof(T) * count, hipMemcpyDeviceToHost, stream), "BccProblem read failed");
-            GR_CHECK(hipStreamSynchronize(stream), "BccProblem read sync failed");
-        }
-        return retval;
-    }
-
     hipError_t Edges(int *h_src, int *h_dst)
     {
         hipError_t retval = hipSuccess;
         DataSlice *ds = data_slices[0];
         const size_t M = static_cast<size_t>(simple_edges);
-        if ((retval = Read(h_src, ds->d_src, M))) return retval;
-        return Read(h_dst, ds->d_dst, M);
+        if ((retval = this->Read(h_src, ds->d_src.p, M))) return retval;
+        return this->Read(h_dst, ds->d_dst.p, M);
     }
 
     // every pointer may be NULL
@@ -232,19 +184,18 @@ struct BccProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         hipError_t retval = hipSuccess;
         DataSlice *ds = data_slices[0];
         const size_t n = static_cast<size_t>(this->nodes), M = static_cast<size_t>(simple_edges);
-        if ((retval = Read(h_bcc, ds->d_bcc, M))) return retval;
-        if ((retval = Read(h_bridge, ds->d_bridge, M))) return retval;
-        if ((retval = Read(h_art, ds->d_art, n))) return retval;
-        if ((retval = Read(h_tecc, ds->d_tecc, n))) return retval;
-        return Read(h_block_size, ds->d_bsize, M);
+        if ((retval = this->Read(h_bcc, ds->d_bcc.p, M))) return retval;
+        if ((retval = this->Read(h_bridge, ds->d_bridge.p, M))) return retval;
+        if ((retval = this->Read(h_art, ds->d_art.p, n))) return retval;
+        if ((retval = this->Read(h_tecc, ds->d_tecc.p, n))) return retval;
+        return this->Read(h_block_size, ds->d_bsize.p, M);
     }
 
     void DropBlockCut()
     {
         DataSlice *ds = data_slices[0];
-        if (ds->d_cut_vertex) util::GRError(hipFree(ds->d_cut_vertex), "BccProblem hipFree failed", __FILE__, __LINE__);
-        if (ds->d_cut_block) util::GRError(hipFree(ds->d_cut_block), "BccProblem hipFree failed", __FILE__, __LINE__);
-        ds->d_cut_vertex = ds->d_cut_block = nullptr;
+        ds->d_cut_vertex.Free();
+        ds->d_cut_block.Free();
         cut_pairs = -1;
     }
 
@@ -267,36 +218,31 @@ struct BccProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         const int key_bits = col_bits + edge_bits;  // <= 63
         const unsigned long long sentinel = (1ull << key_bits) - 1ull;
         graphio::DeviceKeySort sort;
-        unsigned *d_keep = nullptr;
-        unsigned long long *d_pos = nullptr, *d_sums = nullptr;
-        auto release = [&]() {
-            void *bufs[] = {d_keep, d_pos, d_sums};
-            for (void *b : bufs)
-                if (b) util::GRError(hipFree(b), "BccProblem hipFree failed", __FILE__, __LINE__);
-        };
+        graphio::DeviceScratch<unsigned> d_keep;
+        graphio::DeviceScratch<unsigned long long> d_pos, d_sums;
         auto run = [&]() -> hipError_t {
             hipError_t retval = hipSuccess;
             GR_CHECK(sort.Reserve(keys), "BccProblem sort scratch failed");
-            GR_CHECK(hipMalloc(&d_keep, sizeof(unsigned) * static_cast<size_t>(keys)), "BccProblem hipMalloc failed");
-            GR_CHECK(hipMalloc(&d_pos, sizeof(unsigned long long) * static_cast<size_t>(keys)), "BccProblem hipMalloc failed");
-            GR_CHECK(hipMalloc(&d_sums, sizeof(unsigned long long) * static_cast<size_t>(graphio::ScanScratchWords(keys))), "BccProblem hipMalloc failed");
-            hipLaunchKernelGGL(BlockCutKeysKernel, dim3(Grid(simple_edges)), dim3(256), 0, stream, ds->d_src, ds->d_dst, ds->d_bcc, ds->d_art, simple_edges,
+            if ((retval = d_keep.Alloc(static_cast<size_t>(keys)))) return retval;
+            if ((retval = d_pos.Alloc(static_cast<size_t>(keys)))) return retval;
+            if ((retval = d_sums.Alloc(static_cast<size_t>(graphio::ScanScratchWords(keys))))) return retval;
+            hipLaunchKernelGGL(BlockCutKeysKernel, dim3(graphio::PairGrid(simple_edges)), dim3(256), 0, stream, ds->d_src, ds->d_dst, ds->d_bcc, ds->d_art, simple_edges,
                                edge_bits, sentinel, sort.Keys());
             GR_CHECK(hipGetLastError(), "BlockCutKeysKernel launch failed");
             unsigned long long *d_sorted = nullptr;
             GR_CHECK(sort.Sort(keys, key_bits, stream, &d_sorted), "BccProblem key sort failed");
-            hipLaunchKernelGGL(graphio::FlagKernel, dim3(Grid(keys)), dim3(256), 0, stream, d_sorted, keys, sentinel, d_keep);
+            hipLaunchKernelGGL(graphio::FlagKernel, dim3(graphio::PairGrid(keys)), dim3(256), 0, stream, d_sorted, keys, sentinel, d_keep);
             GR_CHECK(hipGetLastError(), "FlagKernel launch failed");
-            GR_CHECK(graphio::DeviceExclusiveScan<unsigned long long>(d_keep, d_pos, keys, d_sums, stream), "BccProblem flag scan failed");
+            GR_CHECK(graphio::DeviceExclusiveScan<unsigned long long>(d_keep.p, d_pos.p, keys, d_sums.p, stream), "BccProblem flag scan failed");
             const long long scan_tiles = (keys + graphio::kScanTile - 1) / graphio::kScanTile;  // (the total is behind the tile offsets)
             unsigned long long total = 0;
             GR_CHECK(hipMemcpyAsync(&total, d_sums + scan_tiles, sizeof(total), hipMemcpyDeviceToHost, stream), "BccProblem read total failed");
             GR_CHECK(hipStreamSynchronize(stream), "BccProblem BlockCut sync failed");
             const long long pairs = static_cast<long long>(total);
             if (pairs > 0) {
-                GR_CHECK(hipMalloc(&ds->d_cut_vertex, sizeof(int) * static_cast<size_t>(pairs)), "BccProblem hipMalloc failed");
-                GR_CHECK(hipMalloc(&ds->d_cut_block, sizeof(int) * static_cast<size_t>(pairs)), "BccProblem hipMalloc failed");
-                hipLaunchKernelGGL(scc::CondensationEmitKernel, dim3(Grid(keys)), dim3(256), 0, stream, d_sorted, d_keep, d_pos, keys, edge_bits, pairs,
+                if ((retval = ds->d_cut_vertex.Alloc(static_cast<size_t>(pairs)))) return retval;
+                if ((retval = ds->d_cut_block.Alloc(static_cast<size_t>(pairs)))) return retval;
+                hipLaunchKernelGGL(scc::CondensationEmitKernel, dim3(graphio::PairGrid(keys)), dim3(256), 0, stream, d_sorted, d_keep, d_pos, keys, edge_bits, pairs,
                                    ds->d_cut_vertex, ds->d_cut_block);
                 GR_CHECK(hipGetLastError(), "CondensationEmitKernel launch failed");
                 GR_CHECK(hipStreamSynchronize(stream), "BccProblem BlockCut sync failed");
@@ -305,7 +251,6 @@ struct BccProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
             return retval;
         };
         retval = run();
-        release();
         if (retval) DropBlockCut();
         return retval;
     }
@@ -320,8 +265,8 @@ struct BccProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         *count = cut_pairs;
         const long long take = cut_pairs < max_edges ? cut_pairs : max_edges;
         if (take < 1 || !h_vertex || !h_block) return retval;
-        if ((retval = Read(h_vertex, ds->d_cut_vertex, static_cast<size_t>(take)))) return retval;
-        return Read(h_block, ds->d_cut_block, static_cast<size_t>(take));
+        if ((retval = this->Read(h_vertex, ds->d_cut_vertex.p, static_cast<size_t>(take)))) return retval;
+        return this->Read(h_block, ds->d_cut_block.p, static_cast<size_t>(take));
     }
 };
 

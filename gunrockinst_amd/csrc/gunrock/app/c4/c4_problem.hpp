@@ -28,25 +28,24 @@ struct C4Problem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     typedef ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> Base;
 
     struct DataSlice {
-        Count *d_cycles = nullptr;       // the result, one 64-bit count per vertex
-        Count *d_edge_cycles = nullptr;  // one per canonical pair; allocated by the first Enact that credits edges
-        int *d_src = nullptr;            // the canonical pairs
-        int *d_dst = nullptr;
-        int *d_inv = nullptr;            // rank -> vertex
-        int *d_ro = nullptr;             // the renumbered neighbour CSR
-        int *d_ci = nullptr;
-        int *d_eid = nullptr;
-        int *d_pre = nullptr;
-        int *d_dlow = nullptr;
-        int *d_wedges = nullptr;         // W per start vertex
-        int *d_lists = nullptr;          // 2 n: BlockKernel's and GlobalKernel's start vertices
-        unsigned long long *d_words = nullptr;    // W_COUNT words of the kernels, then [0] the wedges, [1] the largest W
-        double *d_bound = nullptr;
+        DeviceArray<Count> d_cycles;  // the result, one 64-bit count per vertex
+        DeviceArray<Count> d_edge_cycles;  // one per canonical pair; allocated by the first Enact that credits edges
+        DeviceArray<int> d_src;  // the canonical pairs
+        DeviceArray<int> d_dst;
+        DeviceArray<int> d_inv;  // rank -> vertex
+        DeviceArray<int> d_ro;  // the renumbered neighbour CSR
+        DeviceArray<int> d_ci;
+        DeviceArray<int> d_eid;
+        DeviceArray<int> d_pre;
+        DeviceArray<int> d_dlow;
+        DeviceArray<int> d_wedges;  // W per start vertex
+        DeviceArray<int> d_lists;  // 2 n: BlockKernel's and GlobalKernel's start vertices
+        DeviceArray<unsigned long long> d_words;  // W_COUNT words of the kernels, then [0] the wedges, [1] the largest W
+        DeviceArray<double> d_bound;
         Grown<int> rows;                 // the GLOBAL regime's counter rows, grown by Enact, all 0 between launches
     };
 
-    DataSlice **data_slices = nullptr;
-    int malformed = 0;            // Init found offsets or columns that are not a CSR of `nodes` vertices
+    SliceHolder<DataSlice> data_slices;
     long long simple_edges = 0;   // M
     long long wedges = 0;         // the sum of W
     long long max_wedges = 0;     // the largest W
@@ -54,22 +53,6 @@ struct C4Problem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     long long total = 0;          // of the last Extract
     bool dirty = false;           // an Enact has written since the last Reset
     double build_ms = 0;          // HIP-event time of the build
-
-    ~C4Problem() override
-    {
-        if (data_slices) {
-            DataSlice *ds = data_slices[0];
-            if (ds) {
-                void *bufs[] = {ds->d_cycles, ds->d_edge_cycles, ds->d_src, ds->d_dst, ds->d_inv, ds->d_ro, ds->d_ci, ds->d_eid, ds->d_pre,
-                                ds->d_dlow, ds->d_wedges, ds->d_lists, ds->d_words, ds->d_bound};
-                for (void *b : bufs)
-                    if (b) util::GRError(hipFree(b), "C4Problem hipFree failed", __FILE__, __LINE__);
-                ds->rows.Free();
-                delete ds;
-            }
-            delete[] data_slices;
-        }
-    }
 
     hipError_t Build()
     {
@@ -79,29 +62,22 @@ struct C4Problem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         hipStream_t stream = gs->stream;
         const long long n = this->nodes, m = this->edges;
         const size_t n1 = static_cast<size_t>(n > 0 ? n : 1);
-        GR_CHECK(hipMalloc(&ds->d_words, sizeof(unsigned long long) * (W_COUNT + 2)), "C4Problem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_bound, sizeof(double)), "C4Problem hipMalloc failed");
+        if ((retval = ds->d_words.Alloc(W_COUNT + 2))) return retval;
+        if ((retval = ds->d_bound.Alloc(1))) return retval;
 
         // 1. the CSR must be one: the build indexes with what it reads
-        bool bad = false;
-        graphio::DeviceScratch<int> flag;
-        if ((retval = flag.Alloc(1))) return retval;
-        if ((retval = graphio::DeviceValidateCsr(gs->d_row_offsets, gs->d_column_indices, n, m, flag.p, stream, &bad))) return retval;
-        if (bad) {
-            malformed = 1;
-            return hipErrorInvalidValue;
-        }
+        if ((retval = this->ValidateCsr())) return retval;
 
         graphio::BuildEvents ev;
         if ((retval = ev.Create(2))) return retval;
         if ((retval = ev.Record(0, stream))) return retval;
 
-        GR_CHECK(hipMalloc(&ds->d_cycles, sizeof(Count) * n1), "C4Problem hipMalloc d_cycles failed");
-        GR_CHECK(hipMalloc(&ds->d_inv, sizeof(int) * n1), "C4Problem hipMalloc d_inv failed");
-        GR_CHECK(hipMalloc(&ds->d_ro, sizeof(int) * (n1 + 1)), "C4Problem hipMalloc d_ro failed");
-        GR_CHECK(hipMalloc(&ds->d_dlow, sizeof(int) * n1), "C4Problem hipMalloc d_dlow failed");
-        GR_CHECK(hipMalloc(&ds->d_wedges, sizeof(int) * n1), "C4Problem hipMalloc d_wedges failed");
-        GR_CHECK(hipMalloc(&ds->d_lists, sizeof(int) * 2 * n1), "C4Problem hipMalloc d_lists failed");
+        if ((retval = ds->d_cycles.Alloc(n1))) return retval;
+        if ((retval = ds->d_inv.Alloc(n1))) return retval;
+        if ((retval = ds->d_ro.Alloc(n1 + 1))) return retval;
+        if ((retval = ds->d_dlow.Alloc(n1))) return retval;
+        if ((retval = ds->d_wedges.Alloc(n1))) return retval;
+        if ((retval = ds->d_lists.Alloc(2 * n1))) return retval;
         GR_CHECK(hipMemsetAsync(ds->d_cycles, 0, sizeof(Count) * n1, stream), "C4Problem memset failed");
         GR_CHECK(hipMemsetAsync(ds->d_ro, 0, sizeof(int) * (n1 + 1), stream), "C4Problem memset failed");
         GR_CHECK(hipMemsetAsync(ds->d_dlow, 0, sizeof(int) * n1, stream), "C4Problem memset failed");
@@ -139,9 +115,9 @@ struct C4Problem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
             unsigned long long *d_rows = nullptr;
             GR_CHECK(row_sort.Sort(entries, pg.key_bits, stream, &d_rows), "C4Problem row sort failed");
             const size_t es = static_cast<size_t>(entries);
-            GR_CHECK(hipMalloc(&ds->d_ci, sizeof(int) * es), "C4Problem hipMalloc d_ci failed");
-            GR_CHECK(hipMalloc(&ds->d_eid, sizeof(int) * es), "C4Problem hipMalloc d_eid failed");
-            GR_CHECK(hipMalloc(&ds->d_pre, sizeof(int) * es), "C4Problem hipMalloc d_pre failed");
+            if ((retval = ds->d_ci.Alloc(es))) return retval;
+            if ((retval = ds->d_eid.Alloc(es))) return retval;
+            if ((retval = ds->d_pre.Alloc(es))) return retval;
             hipLaunchKernelGGL(OffsetsKernel, dim3(grid_n), dim3(256), 0, stream, d_rows, entries, n, pg.col_bits, ds->d_ro, ds->d_dlow);
             GR_CHECK(hipGetLastError(), "OffsetsKernel launch failed");
             // 4. the entries and W
@@ -152,8 +128,8 @@ struct C4Problem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
             hipLaunchKernelGGL(SummaryKernel, dim3(graphio::PairGrid(n)), dim3(256), 0, stream, ds->d_wedges, ds->d_dlow, n, ds->d_words + W_COUNT,
                                ds->d_bound);
             GR_CHECK(hipGetLastError(), "SummaryKernel launch failed");
-            ds->d_src = graphio::Take(pg.d_src);
-            ds->d_dst = graphio::Take(pg.d_dst);
+            ds->d_src.Adopt(graphio::Take(pg.d_src));
+            ds->d_dst.Adopt(graphio::Take(pg.d_dst));
         }
         unsigned long long summary[2] = {0, 0};
         GR_CHECK(hipMemcpyAsync(summary, ds->d_words + W_COUNT, sizeof(summary), hipMemcpyDeviceToHost, stream), "C4Problem read-back failed");
@@ -166,18 +142,12 @@ struct C4Problem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         return retval;
     }
 
-    void NewSlice()
-    {
-        data_slices = new DataSlice *[1];
-        data_slices[0] = new DataSlice();
-    }
-
     // One Init per object (grx_c4_init refuses a second one)
     hipError_t Init(bool stream_from_host, const Csr<int, int, int> &graph, int num_gpus = 1)
     {
         hipError_t retval = hipSuccess;
         if ((retval = Base::Init(stream_from_host, graph, num_gpus, false))) return retval;
-        NewSlice();
+        data_slices.Make();
         return Build();
     }
 
@@ -185,7 +155,7 @@ struct C4Problem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     {
         hipError_t retval = hipSuccess;
         if ((retval = Base::InitFromDevice(nodes, edges, d_row_offsets, d_column_indices))) return retval;
-        NewSlice();
+        data_slices.Make();
         return Build();
     }
 
@@ -195,9 +165,8 @@ struct C4Problem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         hipError_t retval = hipSuccess;
         DataSlice *ds = data_slices[0];
         if (ds->d_edge_cycles || simple_edges < 1) return retval;
-        const size_t bytes = sizeof(Count) * static_cast<size_t>(simple_edges);
-        GR_CHECK(hipMalloc(&ds->d_edge_cycles, bytes), "C4Problem hipMalloc d_edge_cycles failed");
-        GR_CHECK(hipMemsetAsync(ds->d_edge_cycles, 0, bytes, this->graph_slices[0]->stream), "C4Problem memset failed");
+        if ((retval = ds->d_edge_cycles.Alloc(static_cast<size_t>(simple_edges)))) return retval;
+        GR_CHECK(hipMemsetAsync(ds->d_edge_cycles, 0, sizeof(Count) * static_cast<size_t>(simple_edges), this->graph_slices[0]->stream), "C4Problem memset failed");
         return retval;
     }
 

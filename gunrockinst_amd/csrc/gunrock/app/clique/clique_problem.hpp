@@ -32,43 +32,26 @@ struct CliqueProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     typedef ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> Base;
 
     struct DataSlice {
-        Count *d_cliques = nullptr;    // the result, one 64-bit count per vertex
-        unsigned *d_degrees = nullptr; // d(v) in G
-        int *d_oro = nullptr;          // the oriented CSR
-        int *d_oci = nullptr;
-        int *d_osrc = nullptr;         // the row of every oriented entry
-        int *d_bitmap_rows = nullptr;  // the bitmap regime's row list
-        int *d_list_edges = nullptr;   // the list regime's oriented edges
-        int *d_words = nullptr;        // BinKernel's counters
-        Count *d_counters = nullptr;   // [0] cliques, [1] bit-row ANDs, [2] list look-ups; [4] sum of C(d, 2), [5] the largest out-row
-        double *d_bound = nullptr;     // [k - 3]: sum over u of C(d+(u), k - 1)
+        DeviceArray<Count> d_cliques;  // the result, one 64-bit count per vertex
+        DeviceArray<unsigned> d_degrees; // d(v) in G
+        DeviceArray<int> d_oro;  // the oriented CSR
+        DeviceArray<int> d_oci;
+        DeviceArray<int> d_osrc;  // the row of every oriented entry
+        DeviceArray<int> d_bitmap_rows;  // the bitmap regime's row list
+        DeviceArray<int> d_list_edges;  // the list regime's oriented edges
+        DeviceArray<int> d_words;  // BinKernel's counters
+        DeviceArray<Count> d_counters;  // [0] cliques, [1] bit-row ANDs, [2] list look-ups; [4] sum of C(d, 2), [5] the largest out-row
+        DeviceArray<double> d_bound;  // [k - 3]: sum over u of C(d+(u), k - 1)
         Grown<int> slabs;              // the list regime's scratch, grown by Enact
     };
 
-    DataSlice **data_slices = nullptr;
-    int malformed = 0;             // Init found offsets or columns that are not a CSR of `nodes` vertices
+    SliceHolder<DataSlice> data_slices;
     long long oriented_edges = 0;  // M
     long long max_out_row = 0;
     double bound[4] = {0, 0, 0, 0};  // for k = 3 .. 6
     long long total = 0;           // of the last Extract
     bool dirty = false;            // an Enact has written since the last Reset
     double build_ms = 0;           // HIP-event time of the oriented-graph build
-
-    ~CliqueProblem() override
-    {
-        if (data_slices) {
-            DataSlice *ds = data_slices[0];
-            if (ds) {
-                void *bufs[] = {ds->d_cliques, ds->d_degrees, ds->d_oro, ds->d_oci, ds->d_osrc, ds->d_bitmap_rows, ds->d_list_edges, ds->d_words,
-                                ds->d_counters, ds->d_bound};
-                for (void *b : bufs)
-                    if (b) util::GRError(hipFree(b), "CliqueProblem hipFree failed", __FILE__, __LINE__);
-                ds->slabs.Free();
-                delete ds;
-            }
-            delete[] data_slices;
-        }
-    }
 
     Oriented DeviceGraph() const
     {
@@ -85,26 +68,21 @@ struct CliqueProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         hipStream_t stream = gs->stream;
         const long long n = this->nodes, m = this->edges;
         const size_t n1 = static_cast<size_t>(n > 0 ? n : 1);
-        GR_CHECK(hipMalloc(&ds->d_words, sizeof(int) * 4), "CliqueProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_counters, sizeof(Count) * 6), "CliqueProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_bound, sizeof(double) * 4), "CliqueProblem hipMalloc failed");
+        if ((retval = ds->d_words.Alloc(4))) return retval;
+        if ((retval = ds->d_counters.Alloc(6))) return retval;
+        if ((retval = ds->d_bound.Alloc(4))) return retval;
 
         // 1. the CSR must be one: the build indexes with what it reads
-        bool bad = false;
-        if ((retval = graphio::DeviceValidateCsr(gs->d_row_offsets, gs->d_column_indices, n, m, ds->d_words, stream, &bad))) return retval;
-        if (bad) {
-            malformed = 1;
-            return hipErrorInvalidValue;
-        }
+        if ((retval = this->ValidateCsr())) return retval;
 
         graphio::BuildEvents ev;
         if ((retval = ev.Create(2))) return retval;
         if ((retval = ev.Record(0, stream))) return retval;
 
-        GR_CHECK(hipMalloc(&ds->d_cliques, sizeof(Count) * n1), "CliqueProblem hipMalloc d_cliques failed");
-        GR_CHECK(hipMalloc(&ds->d_degrees, sizeof(unsigned) * n1), "CliqueProblem hipMalloc d_degrees failed");
-        GR_CHECK(hipMalloc(&ds->d_oro, sizeof(int) * (n1 + 1)), "CliqueProblem hipMalloc d_oro failed");
-        GR_CHECK(hipMalloc(&ds->d_bitmap_rows, sizeof(int) * n1), "CliqueProblem hipMalloc d_bitmap_rows failed");
+        if ((retval = ds->d_cliques.Alloc(n1))) return retval;
+        if ((retval = ds->d_degrees.Alloc(n1))) return retval;
+        if ((retval = ds->d_oro.Alloc(n1 + 1))) return retval;
+        if ((retval = ds->d_bitmap_rows.Alloc(n1))) return retval;
         GR_CHECK(hipMemsetAsync(ds->d_cliques, 0, sizeof(Count) * n1, stream), "CliqueProblem memset failed");
         GR_CHECK(hipMemsetAsync(ds->d_degrees, 0, sizeof(unsigned) * n1, stream), "CliqueProblem memset failed");
         GR_CHECK(hipMemsetAsync(ds->d_oro, 0, sizeof(int) * (n1 + 1), stream), "CliqueProblem memset failed");
@@ -148,9 +126,9 @@ struct CliqueProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
             unsigned long long *d_osorted = nullptr;
             GR_CHECK(oriented_sort.Sort(oriented_edges, pg.key_bits, stream, &d_osorted), "CliqueProblem oriented sort failed");
             const size_t ms = static_cast<size_t>(oriented_edges);
-            GR_CHECK(hipMalloc(&ds->d_oci, sizeof(int) * ms), "CliqueProblem hipMalloc d_oci failed");
-            GR_CHECK(hipMalloc(&ds->d_osrc, sizeof(int) * ms), "CliqueProblem hipMalloc d_osrc failed");
-            GR_CHECK(hipMalloc(&ds->d_list_edges, sizeof(int) * ms), "CliqueProblem hipMalloc d_list_edges failed");
+            if ((retval = ds->d_oci.Alloc(ms))) return retval;
+            if ((retval = ds->d_osrc.Alloc(ms))) return retval;
+            if ((retval = ds->d_list_edges.Alloc(ms))) return retval;
             hipLaunchKernelGGL(tc::EmitOrientedKernel, dim3(graphio::PairGrid(oriented_edges)), dim3(256), 0, stream, d_osorted, oriented_edges,
                                pg.col_bits, ds->d_oci, ds->d_osrc);
             GR_CHECK(hipGetLastError(), "EmitOrientedKernel launch failed");
@@ -200,18 +178,12 @@ struct CliqueProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         return retval;
     }
 
-    void NewSlice()
-    {
-        data_slices = new DataSlice *[1];
-        data_slices[0] = new DataSlice();
-    }
-
     // One Init per object (grx_clique_init refuses a second one).  h_rank: `nodes` int32 on the host, or NULL
     hipError_t Init(bool stream_from_host, const Csr<int, int, int> &graph, const int *h_rank, int num_gpus = 1)
     {
         hipError_t retval = hipSuccess;
         if ((retval = Base::Init(stream_from_host, graph, num_gpus, false))) return retval;
-        NewSlice();
+        data_slices.Make();
         graphio::DeviceScratch<int> rank;
         if (h_rank) {
             const size_t bytes = sizeof(int) * static_cast<size_t>(this->nodes);
@@ -225,7 +197,7 @@ struct CliqueProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     {
         hipError_t retval = hipSuccess;
         if ((retval = Base::InitFromDevice(nodes, edges, d_row_offsets, d_column_indices))) return retval;
-        NewSlice();
+        data_slices.Make();
         return Build(d_rank);
     }
 

@@ -29,23 +29,22 @@ struct KcoreProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     typedef ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> Base;
 
     struct DataSlice {
-        int *d_core = nullptr;       // the working degrees, then the result
-        int *d_degrees = nullptr;    // d(v) in G (nodes + 1 words, the last 0: scanned into the offsets)
-        int *d_nro = nullptr;        // the neighbour CSR
-        int *d_nci = nullptr;
-        int *d_queue = nullptr;      // every vertex once, in peeling order
-        int *d_list[2] = {nullptr, nullptr};  // the live list, rebuilt from one into the other
-        unsigned *d_words = nullptr;          // W_* of kcore_functor.hpp
-        unsigned long long *d_counters = nullptr;  // [0] row entries walked; [1], [2] Members' counts; [3] the end of the trace's clock
-        int *d_trace_k = nullptr;    // one entry per level scan (max degree + 1: levels are distinct values)
-        int *d_trace_tail = nullptr;
-        unsigned long long *d_trace_clock = nullptr;
-        unsigned long long *d_shell = nullptr;  // allocated at the first request
-        unsigned char *d_mask = nullptr;        // allocated at the first request
+        DeviceArray<int> d_core;  // the working degrees, then the result
+        DeviceArray<int> d_degrees;  // d(v) in G (nodes + 1 words, the last 0: scanned into the offsets)
+        DeviceArray<int> d_nro;  // the neighbour CSR
+        DeviceArray<int> d_nci;
+        DeviceArray<int> d_queue;  // every vertex once, in peeling order
+        DeviceArray<int> d_list[2];  // the live list, rebuilt from one into the other
+        DeviceArray<unsigned> d_words;  // W_* of kcore_functor.hpp
+        DeviceArray<unsigned long long> d_counters;  // [0] row entries walked; [1], [2] Members' counts; [3] the end of the trace's clock
+        DeviceArray<int> d_trace_k;  // one entry per level scan (max degree + 1: levels are distinct values)
+        DeviceArray<int> d_trace_tail;
+        DeviceArray<unsigned long long> d_trace_clock;
+        DeviceArray<unsigned long long> d_shell;  // allocated at the first request
+        DeviceArray<unsigned char> d_mask;  // allocated at the first request
     };
 
-    DataSlice **data_slices = nullptr;
-    int malformed = 0;           // Init found offsets or columns that are not a CSR of `nodes` vertices
+    SliceHolder<DataSlice> data_slices;
     long long simple_edges = 0;  // M
     long long max_degree = 0;
     long long min_degree = 0;    // the smallest positive d(v)
@@ -55,29 +54,6 @@ struct KcoreProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     int degeneracy = 0;          // of the last Extract
     bool fresh = false;          // Reset has run and Enact has not: core[] holds d(v) and the words are clear
     double build_ms = 0;         // HIP-event time of the neighbour-CSR build
-
-    ~KcoreProblem() override
-    {
-        if (data_slices) {
-            DataSlice *ds = data_slices[0];
-            if (ds) {
-                void *bufs[] = {ds->d_core, ds->d_degrees, ds->d_nro, ds->d_nci, ds->d_queue, ds->d_list[0], ds->d_list[1], ds->d_words,
-                                ds->d_counters, ds->d_trace_k, ds->d_trace_tail, ds->d_trace_clock, ds->d_shell, ds->d_mask};
-                for (void *b : bufs)
-                    if (b) util::GRError(hipFree(b), "KcoreProblem hipFree failed", __FILE__, __LINE__);
-                delete ds;
-            }
-            delete[] data_slices;
-        }
-    }
-
-    static int Grid(long long work)
-    {
-        long long blocks = (work + 255) / 256;
-        if (blocks < 1) blocks = 1;
-        if (blocks > 2048) blocks = 2048;  // 256 CUs x 8 workgroups, grid-stride the rest
-        return static_cast<int>(blocks);
-    }
 
     Graph DeviceGraph() const
     {
@@ -94,7 +70,7 @@ struct KcoreProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         const unsigned init[3] = {0u, kNoLevel, 0u};
         unsigned *d_out = ds->d_words + W_COUNT;  // (three words behind the shared ones)
         GR_CHECK(hipMemcpyAsync(d_out, init, sizeof(init), hipMemcpyHostToDevice, stream), "KcoreProblem summary init failed");
-        hipLaunchKernelGGL(SummaryKernel, dim3(Grid(this->nodes)), dim3(256), 0, stream, d_values, static_cast<long long>(this->nodes), d_out);
+        hipLaunchKernelGGL(SummaryKernel, dim3(graphio::PairGrid(this->nodes)), dim3(256), 0, stream, d_values, static_cast<long long>(this->nodes), d_out);
         GR_CHECK(hipGetLastError(), "SummaryKernel launch failed");
         GR_CHECK(hipMemcpyAsync(out, d_out, sizeof(init), hipMemcpyDeviceToHost, stream), "KcoreProblem read-back failed");
         GR_CHECK(hipStreamSynchronize(stream), "KcoreProblem read-back sync failed");
@@ -109,29 +85,23 @@ struct KcoreProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         hipStream_t stream = gs->stream;
         const long long n = this->nodes, m = this->edges;
         const size_t n1 = static_cast<size_t>(n > 0 ? n : 1);
-        GR_CHECK(hipMalloc(&ds->d_words, sizeof(unsigned) * (W_COUNT + 4)), "KcoreProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_counters, sizeof(unsigned long long) * 4), "KcoreProblem hipMalloc failed");
+        if ((retval = ds->d_words.Alloc(W_COUNT + 4))) return retval;
+        if ((retval = ds->d_counters.Alloc(4))) return retval;
 
         // 1. the CSR must be one: the build indexes with what it reads
-        bool bad = false;
         GR_CHECK(hipMemsetAsync(ds->d_words, 0, sizeof(unsigned) * (W_COUNT + 4), stream), "KcoreProblem memset failed");
-        if ((retval = graphio::DeviceValidateCsr(gs->d_row_offsets, gs->d_column_indices, n, m, reinterpret_cast<int *>(ds->d_words), stream, &bad)))
-            return retval;
-        if (bad) {
-            malformed = 1;
-            return hipErrorInvalidValue;
-        }
+        if ((retval = this->ValidateCsr())) return retval;
 
         graphio::BuildEvents ev;
         if ((retval = ev.Create(2))) return retval;
         if ((retval = ev.Record(0, stream))) return retval;
 
-        GR_CHECK(hipMalloc(&ds->d_core, sizeof(int) * n1), "KcoreProblem hipMalloc d_core failed");
-        GR_CHECK(hipMalloc(&ds->d_degrees, sizeof(int) * (n1 + 1)), "KcoreProblem hipMalloc d_degrees failed");
-        GR_CHECK(hipMalloc(&ds->d_nro, sizeof(int) * (n1 + 1)), "KcoreProblem hipMalloc d_nro failed");
-        GR_CHECK(hipMalloc(&ds->d_queue, sizeof(int) * n1), "KcoreProblem hipMalloc d_queue failed");
-        GR_CHECK(hipMalloc(&ds->d_list[0], sizeof(int) * n1), "KcoreProblem hipMalloc d_list failed");
-        GR_CHECK(hipMalloc(&ds->d_list[1], sizeof(int) * n1), "KcoreProblem hipMalloc d_list failed");
+        if ((retval = ds->d_core.Alloc(n1))) return retval;
+        if ((retval = ds->d_degrees.Alloc(n1 + 1))) return retval;
+        if ((retval = ds->d_nro.Alloc(n1 + 1))) return retval;
+        if ((retval = ds->d_queue.Alloc(n1))) return retval;
+        if ((retval = ds->d_list[0].Alloc(n1))) return retval;
+        if ((retval = ds->d_list[1].Alloc(n1))) return retval;
         GR_CHECK(hipMemsetAsync(ds->d_degrees, 0, sizeof(int) * (n1 + 1), stream), "KcoreProblem memset failed");
         GR_CHECK(hipMemsetAsync(ds->d_nro, 0, sizeof(int) * (n1 + 1), stream), "KcoreProblem memset failed");
 
@@ -144,10 +114,10 @@ struct KcoreProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
             if ((retval = sums.Alloc(static_cast<size_t>(graphio::ScanScratchWords(n + 1))))) return retval;
             GR_CHECK(hipMemsetAsync(cursor.p, 0, sizeof(unsigned) * n1, stream), "KcoreProblem memset failed");
             if ((retval = pg.Keys(gs->d_row_offsets, gs->d_column_indices, m, stream))) return retval;
-            hipLaunchKernelGGL(tc::DegreeKernel, dim3(Grid(m)), dim3(256), 0, stream, pg.d_sorted, pg.d_keep, m, pg.col_bits,
-                               reinterpret_cast<unsigned *>(ds->d_degrees));
+            hipLaunchKernelGGL(tc::DegreeKernel, dim3(graphio::PairGrid(m)), dim3(256), 0, stream, pg.d_sorted, pg.d_keep, m, pg.col_bits,
+                               reinterpret_cast<unsigned *>(ds->d_degrees.p));
             GR_CHECK(hipGetLastError(), "DegreeKernel launch failed");
-            GR_CHECK(graphio::DeviceExclusiveScan<int>(reinterpret_cast<unsigned *>(ds->d_degrees), ds->d_nro, n + 1, sums.p, stream),
+            GR_CHECK(graphio::DeviceExclusiveScan<int>(reinterpret_cast<unsigned *>(ds->d_degrees.p), ds->d_nro, n + 1, sums.p, stream),
                      "KcoreProblem offset scan failed");
             int entries = 0;  // 2M <= 2 * edges; edges is an int, and so is every offset: refuse what does not fit
             GR_CHECK(hipMemcpyAsync(&entries, ds->d_nro + n, sizeof(int), hipMemcpyDeviceToHost, stream), "KcoreProblem read-back failed");
@@ -155,8 +125,8 @@ struct KcoreProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
             if (entries < 0) return hipErrorInvalidValue;
             simple_edges = entries / 2;
             if (entries > 0) {
-                GR_CHECK(hipMalloc(&ds->d_nci, sizeof(int) * static_cast<size_t>(entries)), "KcoreProblem hipMalloc d_nci failed");
-                hipLaunchKernelGGL(NeighbourScatterKernel, dim3(Grid(m)), dim3(256), 0, stream, pg.d_sorted, pg.d_keep, m, pg.col_bits, ds->d_nro,
+                if ((retval = ds->d_nci.Alloc(static_cast<size_t>(entries)))) return retval;
+                hipLaunchKernelGGL(NeighbourScatterKernel, dim3(graphio::PairGrid(m)), dim3(256), 0, stream, pg.d_sorted, pg.d_keep, m, pg.col_bits, ds->d_nro,
                                    cursor.p, ds->d_nci);
                 GR_CHECK(hipGetLastError(), "NeighbourScatterKernel launch failed");
             }
@@ -170,9 +140,9 @@ struct KcoreProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         min_degree = summary[1] == kNoLevel ? 0 : summary[1];
         zeros = summary[2];
         trace_capacity = max_degree + 1;
-        GR_CHECK(hipMalloc(&ds->d_trace_k, sizeof(int) * static_cast<size_t>(trace_capacity)), "KcoreProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_trace_tail, sizeof(int) * static_cast<size_t>(trace_capacity)), "KcoreProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_trace_clock, sizeof(unsigned long long) * static_cast<size_t>(trace_capacity)), "KcoreProblem hipMalloc failed");
+        if ((retval = ds->d_trace_k.Alloc(static_cast<size_t>(trace_capacity)))) return retval;
+        if ((retval = ds->d_trace_tail.Alloc(static_cast<size_t>(trace_capacity)))) return retval;
+        if ((retval = ds->d_trace_clock.Alloc(static_cast<size_t>(trace_capacity)))) return retval;
         return retval;
     }
 
@@ -181,8 +151,7 @@ struct KcoreProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     {
         hipError_t retval = hipSuccess;
         if ((retval = Base::Init(stream_from_host, graph, num_gpus, false))) return retval;
-        data_slices = new DataSlice *[1];
-        data_slices[0] = new DataSlice();
+        data_slices.Make();
         return Build();
     }
 
@@ -190,8 +159,7 @@ struct KcoreProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     {
         hipError_t retval = hipSuccess;
         if ((retval = Base::InitFromDevice(nodes, edges, d_row_offsets, d_column_indices))) return retval;
-        data_slices = new DataSlice *[1];
-        data_slices[0] = new DataSlice();
+        data_slices.Make();
         return Build();
     }
 
@@ -239,13 +207,11 @@ struct KcoreProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         if (count) *count = static_cast<int>(shells);
         if (!h_sizes || max_entries < 1) return retval;
         if (shells > shell_capacity) {
-            if (ds->d_shell) GR_CHECK(hipFree(ds->d_shell), "KcoreProblem hipFree failed");
-            ds->d_shell = nullptr;
-            GR_CHECK(hipMalloc(&ds->d_shell, sizeof(unsigned long long) * static_cast<size_t>(shells)), "KcoreProblem hipMalloc d_shell failed");
+            if ((retval = ds->d_shell.Alloc(static_cast<size_t>(shells)))) return retval;
             shell_capacity = shells;
         }
         GR_CHECK(hipMemsetAsync(ds->d_shell, 0, sizeof(unsigned long long) * static_cast<size_t>(shells), stream), "KcoreProblem memset failed");
-        hipLaunchKernelGGL(ShellKernel, dim3(Grid(this->nodes)), dim3(256), 0, stream, ds->d_core, static_cast<long long>(this->nodes), ds->d_shell);
+        hipLaunchKernelGGL(ShellKernel, dim3(graphio::PairGrid(this->nodes)), dim3(256), 0, stream, ds->d_core, static_cast<long long>(this->nodes), ds->d_shell);
         GR_CHECK(hipGetLastError(), "ShellKernel launch failed");
         const long long take = shells < max_entries ? shells : max_entries;
         GR_CHECK(hipMemcpyAsync(h_sizes, ds->d_shell, sizeof(long long) * static_cast<size_t>(take), hipMemcpyDeviceToHost, stream),
@@ -261,9 +227,9 @@ struct KcoreProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         DataSlice *ds = data_slices[0];
         hipStream_t stream = this->graph_slices[0]->stream;
         const size_t n = static_cast<size_t>(this->nodes);
-        if (!ds->d_mask) GR_CHECK(hipMalloc(&ds->d_mask, n), "KcoreProblem hipMalloc d_mask failed");
+        if (!ds->d_mask && (retval = ds->d_mask.Alloc(n))) return retval;
         GR_CHECK(hipMemsetAsync(ds->d_counters + 1, 0, sizeof(unsigned long long) * 2, stream), "KcoreProblem memset failed");
-        hipLaunchKernelGGL(MembersKernel, dim3(Grid(this->nodes)), dim3(kKcoreThreads), 0, stream, DeviceGraph(), ds->d_core,
+        hipLaunchKernelGGL(MembersKernel, dim3(graphio::PairGrid(this->nodes)), dim3(kKcoreThreads), 0, stream, DeviceGraph(), ds->d_core,
                            static_cast<long long>(this->nodes), k, wave_min_row, ds->d_mask, ds->d_counters + 1);
         GR_CHECK(hipGetLastError(), "MembersKernel launch failed");
         unsigned long long out[2] = {0, 0};

@@ -31,16 +31,15 @@ struct LpProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     typedef ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> Base;
 
     struct DataSlice {
-        int *d_src = nullptr, *d_dst = nullptr, *d_pw = nullptr;  // the canonical pairs and their weights
-        int *d_nro = nullptr, *d_nci = nullptr, *d_ew = nullptr;   // the neighbour CSR and the weight of every entry (NULL: 1 each)
-        int *d_labels = nullptr, *d_fresh = nullptr, *d_prev = nullptr, *d_chround = nullptr, *d_dirty = nullptr, *d_hubs = nullptr;  // per vertex
-        int *d_list[2] = {nullptr, nullptr}, *d_start = nullptr, *d_community = nullptr;
-        int *d_class = nullptr, *d_class_list = nullptr;
-        unsigned long long *d_words = nullptr;
+        DeviceArray<int> d_src, d_dst, d_pw;  // the canonical pairs and their weights
+        DeviceArray<int> d_nro, d_nci, d_ew;  // the neighbour CSR and the weight of every entry (NULL: 1 each)
+        DeviceArray<int> d_labels, d_fresh, d_prev, d_chround, d_dirty, d_hubs;  // per vertex
+        DeviceArray<int> d_list[2], d_start, d_community;
+        DeviceArray<int> d_class, d_class_list;
+        DeviceArray<unsigned long long> d_words;
     };
 
-    DataSlice **data_slices = nullptr;
-    int malformed = 0;       // no CSR, or a pair weight below 1
+    SliceHolder<DataSlice> data_slices;
     long long pairs = 0;     // M
     int longest_row = 0;
     bool fresh = false;      // Reset has run and Enact has not
@@ -50,24 +49,6 @@ struct LpProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     // the classes (SetClasses): vertices [class_off[k], class_off[k + 1]) of d_class_list are class k
     int classes = 0;
     std::vector<int> class_off, class_longest;
-
-    ~LpProblem() override
-    {
-        if (data_slices) {
-            DataSlice *ds = data_slices[0];
-            if (ds) {
-                void *bufs[] = {ds->d_src, ds->d_dst, ds->d_pw, ds->d_nro, ds->d_nci, ds->d_ew, ds->d_labels, ds->d_fresh, ds->d_prev, ds->d_chround,
-                                ds->d_dirty, ds->d_hubs, ds->d_list[0], ds->d_list[1], ds->d_start, ds->d_community, ds->d_class, ds->d_class_list,
-                                ds->d_words};
-                for (void *b : bufs)
-                    if (b) util::GRError(hipFree(b), "LpProblem hipFree failed", __FILE__, __LINE__);
-                delete ds;
-            }
-            delete[] data_slices;
-        }
-    }
-
-    static int Grid(long long work) { return graphio::PairGrid(work); }
 
     Ctx DeviceCtx(int strategy, int lane_max_row, int wave_max_row, int table_slots) const
     {
@@ -109,18 +90,11 @@ struct LpProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         const long long n = this->nodes, m = this->edges;
         const size_t n1 = static_cast<size_t>(n > 0 ? n : 1);
         const bool weighted = gs->d_edge_values != nullptr;
-        GR_CHECK(hipMalloc(&ds->d_words, sizeof(unsigned long long) * W_COUNT), "LpProblem hipMalloc failed");
+        if ((retval = ds->d_words.Alloc(W_COUNT))) return retval;
         GR_CHECK(hipMemsetAsync(ds->d_words, 0, sizeof(unsigned long long) * W_COUNT, stream), "LpProblem memset failed");
 
         // the CSR must be one: the build indexes with what it reads
-        bool bad = false;
-        if ((retval = graphio::DeviceValidateCsr(gs->d_row_offsets, gs->d_column_indices, n, m, reinterpret_cast<int *>(ds->d_words + W_FLAG), stream,
-                                                 &bad)))
-            return retval;
-        if (bad) {
-            malformed = 1;
-            return hipErrorInvalidValue;
-        }
+        if ((retval = this->ValidateCsr())) return retval;
 
         long long M = 0;
         {  // (the build's scratch goes with this scope)
@@ -131,29 +105,29 @@ struct LpProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
             if ((retval = pg.Keys(gs->d_row_offsets, gs->d_column_indices, m, stream))) return retval;
             if ((retval = pg.Pairs(stream))) return retval;
             if ((retval = pg.Rows(stream))) return retval;
-            ds->d_src = graphio::Take(pg.d_src);
-            ds->d_dst = graphio::Take(pg.d_dst);
-            ds->d_nro = graphio::Take(pg.d_ro);
-            ds->d_nci = graphio::Take(pg.d_ci);
+            ds->d_src.Adopt(graphio::Take(pg.d_src));
+            ds->d_dst.Adopt(graphio::Take(pg.d_dst));
+            ds->d_nro.Adopt(graphio::Take(pg.d_ro));
+            ds->d_nci.Adopt(graphio::Take(pg.d_ci));
             pairs = M = pg.pairs;
             if (M > 0) {
                 // the weights as matching builds them: every input entry raises its pair's weight to its own
                 const size_t ms = static_cast<size_t>(M);
-                GR_CHECK(hipMalloc(&ds->d_pw, sizeof(int) * ms), "LpProblem hipMalloc d_pw failed");
-                hipLaunchKernelGGL(oprtr::FillKernel<int>, dim3(Grid(M)), dim3(256), 0, stream, ds->d_pw, M, weighted ? INT_MIN : 1);
+                if ((retval = ds->d_pw.Alloc(ms))) return retval;
+                hipLaunchKernelGGL(oprtr::FillKernel<int>, dim3(graphio::PairGrid(M)), dim3(256), 0, stream, ds->d_pw, M, weighted ? INT_MIN : 1);
                 GR_CHECK(hipGetLastError(), "FillKernel launch failed");
                 if (weighted) {
-                    GR_CHECK(hipMalloc(&ds->d_ew, sizeof(int) * 2 * ms), "LpProblem hipMalloc d_ew failed");
-                    hipLaunchKernelGGL(matching::PairWeightKernel, dim3(Grid(m)), dim3(256), 0, stream, gs->d_row_offsets, gs->d_column_indices,
+                    if ((retval = ds->d_ew.Alloc(2 * ms))) return retval;
+                    hipLaunchKernelGGL(matching::PairWeightKernel, dim3(graphio::PairGrid(m)), dim3(256), 0, stream, gs->d_row_offsets, gs->d_column_indices,
                                        gs->d_edge_values, static_cast<int>(n), m, ds->d_nro, ds->d_nci, pg.d_eid, ds->d_pw);
                     GR_CHECK(hipGetLastError(), "PairWeightKernel launch failed");
-                    hipLaunchKernelGGL(matching::EntryWeightKernel, dim3(Grid(2 * M)), dim3(256), 0, stream, pg.d_eid, ds->d_pw, 2 * M, ds->d_ew);
+                    hipLaunchKernelGGL(matching::EntryWeightKernel, dim3(graphio::PairGrid(2 * M)), dim3(256), 0, stream, pg.d_eid, ds->d_pw, 2 * M, ds->d_ew);
                     GR_CHECK(hipGetLastError(), "EntryWeightKernel launch failed");
-                    hipLaunchKernelGGL(MinWeightKernel, dim3(Grid(M)), dim3(256), 0, stream, ds->d_pw, M, ds->d_words + W_FLAG);
+                    hipLaunchKernelGGL(MinWeightKernel, dim3(graphio::PairGrid(M)), dim3(256), 0, stream, ds->d_pw, M, ds->d_words + W_FLAG);
                     GR_CHECK(hipGetLastError(), "MinWeightKernel launch failed");
                 }
             }
-            hipLaunchKernelGGL(LongestRowKernel, dim3(Grid(n)), dim3(256), 0, stream, ds->d_nro, n, ds->d_words + W_HUBS);
+            hipLaunchKernelGGL(LongestRowKernel, dim3(graphio::PairGrid(n)), dim3(256), 0, stream, ds->d_nro, n, ds->d_words + W_HUBS);
             GR_CHECK(hipGetLastError(), "LongestRowKernel launch failed");
             if ((retval = ev.Record(1, stream))) return retval;
             GR_CHECK(hipStreamSynchronize(stream), "LpProblem build sync failed");
@@ -163,14 +137,11 @@ struct LpProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         if ((retval = ReadWord(W_HUBS, &longest))) return retval;  // (the word is the enactor's from the first Reset on)
         longest_row = static_cast<int>(longest);
         if ((retval = ReadWord(W_FLAG, &flag))) return retval;
-        if (flag) {  // a pair weight below 1
-            malformed = 1;
-            return hipErrorInvalidValue;
-        }
+        if (flag) return this->Malformed();  // a pair weight below 1
 
-        int **vertex_arrays[] = {&ds->d_labels, &ds->d_fresh, &ds->d_prev, &ds->d_chround, &ds->d_dirty, &ds->d_hubs, &ds->d_list[0],
+        DeviceArray<int> *vertex_arrays[] = {&ds->d_labels, &ds->d_fresh, &ds->d_prev, &ds->d_chround, &ds->d_dirty, &ds->d_hubs, &ds->d_list[0],
                                  &ds->d_list[1], &ds->d_start, &ds->d_community, &ds->d_class, &ds->d_class_list};
-        for (int **a : vertex_arrays) GR_CHECK(hipMalloc(a, sizeof(int) * n1), "LpProblem hipMalloc failed");
+        for (DeviceArray<int> *a : vertex_arrays) if ((retval = a->Alloc(n1))) return retval;
         return retval;
     }
 
@@ -179,8 +150,7 @@ struct LpProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     {
         hipError_t retval = hipSuccess;
         if ((retval = Base::Init(stream_from_host, graph, num_gpus, true))) return retval;
-        data_slices = new DataSlice *[1];
-        data_slices[0] = new DataSlice();
+        data_slices.Make();
         return Build();
     }
 
@@ -189,8 +159,7 @@ struct LpProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     {
         hipError_t retval = hipSuccess;
         if ((retval = Base::InitFromDevice(nodes, edges, d_row_offsets, d_column_indices, d_weights))) return retval;
-        data_slices = new DataSlice *[1];
-        data_slices[0] = new DataSlice();
+        data_slices.Make();
         return Build();
     }
 
@@ -207,7 +176,7 @@ struct LpProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         GR_CHECK(hipMemcpyAsync(ds->d_class, h_classes, sizeof(int) * static_cast<size_t>(n), hipMemcpyHostToDevice, stream), "LpProblem upload failed");
         GR_CHECK(hipMemsetAsync(ds->d_words + W_FLAG, 0, sizeof(unsigned long long), stream), "LpProblem memset failed");
         if (pairs > 0) {
-            hipLaunchKernelGGL(ClassCheckKernel, dim3(Grid(pairs)), dim3(256), 0, stream, ds->d_src, ds->d_dst, ds->d_class, pairs, ds->d_words + W_FLAG);
+            hipLaunchKernelGGL(ClassCheckKernel, dim3(graphio::PairGrid(pairs)), dim3(256), 0, stream, ds->d_src, ds->d_dst, ds->d_class, pairs, ds->d_words + W_FLAG);
             GR_CHECK(hipGetLastError(), "ClassCheckKernel launch failed");
         }
         unsigned long long flag = 0;
@@ -226,11 +195,11 @@ struct LpProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         if ((retval = off.Alloc(static_cast<size_t>(count) + 1))) return retval;
         if ((retval = longest.Alloc(static_cast<size_t>(count)))) return retval;
         GR_CHECK(hipMemsetAsync(longest.p, 0, sizeof(int) * static_cast<size_t>(count), stream), "LpProblem memset failed");
-        hipLaunchKernelGGL(ClassKeysKernel, dim3(Grid(n)), dim3(256), 0, stream, ds->d_class, ds->d_nro, n, col_bits, sort.Keys(), longest.p);
+        hipLaunchKernelGGL(ClassKeysKernel, dim3(graphio::PairGrid(n)), dim3(256), 0, stream, ds->d_class, ds->d_nro, n, col_bits, sort.Keys(), longest.p);
         GR_CHECK(hipGetLastError(), "ClassKeysKernel launch failed");
         unsigned long long *d_sorted = nullptr;
         GR_CHECK(sort.Sort(n, class_bits + col_bits, stream, &d_sorted), "LpProblem class sort failed");
-        hipLaunchKernelGGL(ClassListKernel, dim3(Grid(n > count ? n : count + 1)), dim3(256), 0, stream, d_sorted, n, count, col_bits,
+        hipLaunchKernelGGL(ClassListKernel, dim3(graphio::PairGrid(n > count ? n : count + 1)), dim3(256), 0, stream, d_sorted, n, count, col_bits,
                            ds->d_class_list, off.p);
         GR_CHECK(hipGetLastError(), "ClassListKernel launch failed");
         class_off.assign(static_cast<size_t>(count) + 1, 0);
@@ -254,7 +223,7 @@ struct LpProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         if (h_start)
             GR_CHECK(hipMemcpyAsync(ds->d_start, h_start, sizeof(int) * static_cast<size_t>(n), hipMemcpyHostToDevice, stream), "LpProblem upload failed");
         GR_CHECK(hipMemsetAsync(ds->d_words, 0, sizeof(unsigned long long) * W_COUNT, stream), "LpProblem memset failed");
-        hipLaunchKernelGGL(ResetKernel, dim3(Grid(n)), dim3(256), 0, stream, DeviceCtx(LP_AUTO, kLaneMaxRow, kWaveMaxRow, kTableSlots),
+        hipLaunchKernelGGL(ResetKernel, dim3(graphio::PairGrid(n)), dim3(256), 0, stream, DeviceCtx(LP_AUTO, kLaneMaxRow, kWaveMaxRow, kTableSlots),
                            h_start ? ds->d_start : nullptr, ds->d_list[0]);
         GR_CHECK(hipGetLastError(), "ResetKernel launch failed");
         GR_CHECK(hipStreamSynchronize(stream), "LpProblem Reset sync failed");  // (h_start is the caller's again)
@@ -279,26 +248,14 @@ struct LpProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         if ((retval = rank.Alloc(static_cast<size_t>(n)))) return retval;
         if ((retval = sums.Alloc(static_cast<size_t>(graphio::ScanScratchWords(n))))) return retval;
         GR_CHECK(hipMemsetAsync(used.p, 0, sizeof(unsigned) * static_cast<size_t>(n), stream), "LpProblem memset failed");
-        hipLaunchKernelGGL(UsedKernel, dim3(Grid(n)), dim3(256), 0, stream, ds->d_labels, n, used.p);
+        hipLaunchKernelGGL(UsedKernel, dim3(graphio::PairGrid(n)), dim3(256), 0, stream, ds->d_labels, n, used.p);
         GR_CHECK(hipGetLastError(), "UsedKernel launch failed");
         GR_CHECK(graphio::DeviceExclusiveScan<int>(used.p, rank.p, n, sums.p, stream), "LpProblem rank scan failed");
-        hipLaunchKernelGGL(CommunityKernel, dim3(Grid(n)), dim3(256), 0, stream, ds->d_labels, rank.p, n, ds->d_community);
+        hipLaunchKernelGGL(CommunityKernel, dim3(graphio::PairGrid(n)), dim3(256), 0, stream, ds->d_labels, rank.p, n, ds->d_community);
         GR_CHECK(hipGetLastError(), "CommunityKernel launch failed");
         GR_CHECK(hipMemcpyAsync(ds->d_words + W_COMMUNITIES, sums.p + tiles, sizeof(unsigned long long), hipMemcpyDeviceToDevice, stream),
                  "LpProblem copy failed");
         GR_CHECK(hipStreamSynchronize(stream), "LpProblem Finish sync failed");  // (the scratch goes with this scope)
-        return retval;
-    }
-
-    template <typename T>
-    hipError_t Read(T *h_out, const T *d_in, size_t count)
-    {
-        hipError_t retval = hipSuccess;
-        hipStream_t stream = this->graph_slices[0]->stream;
-        if (h_out && count) {
-            GR_CHECK(hipMemcpyAsync(h_out, d_in, sizeof(T) * count, hipMemcpyDeviceToHost, stream), "LpProblem read failed");
-            GR_CHECK(hipStreamSynchronize(stream), "LpProblem read sync failed");
-        }
         return retval;
     }
 
@@ -308,8 +265,8 @@ struct LpProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         hipError_t retval = hipSuccess;
         DataSlice *ds = data_slices[0];
         const size_t n = static_cast<size_t>(this->nodes);
-        if ((retval = Read(h_labels, ds->d_labels, n))) return retval;
-        return Read(h_community, ds->d_community, n);
+        if ((retval = this->Read(h_labels, ds->d_labels.p, n))) return retval;
+        return this->Read(h_community, ds->d_community.p, n);
     }
 
     // int64 per community: size, internal weight, volume; *total = W.  Every pointer may be NULL.
@@ -323,18 +280,18 @@ struct LpProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         graphio::DeviceScratch<unsigned long long> sums;  // size, internal, volume, W
         if ((retval = sums.Alloc(3 * k + 1))) return retval;
         GR_CHECK(hipMemsetAsync(sums.p, 0, sizeof(unsigned long long) * (3 * k + 1), stream), "LpProblem memset failed");
-        hipLaunchKernelGGL(SizeVolumeKernel, dim3(Grid(n)), dim3(256), 0, stream, ds->d_community, ds->d_nro, ds->d_ew, n, sums.p, sums.p + 2 * k);
+        hipLaunchKernelGGL(SizeVolumeKernel, dim3(graphio::PairGrid(n)), dim3(256), 0, stream, ds->d_community, ds->d_nro, ds->d_ew, n, sums.p, sums.p + 2 * k);
         GR_CHECK(hipGetLastError(), "SizeVolumeKernel launch failed");
         if (pairs > 0) {
-            hipLaunchKernelGGL(InternalKernel, dim3(Grid(pairs)), dim3(256), 0, stream, ds->d_src, ds->d_dst, ds->d_pw, ds->d_community, pairs,
+            hipLaunchKernelGGL(InternalKernel, dim3(graphio::PairGrid(pairs)), dim3(256), 0, stream, ds->d_src, ds->d_dst, ds->d_pw, ds->d_community, pairs,
                                sums.p + k, sums.p + 3 * k);
             GR_CHECK(hipGetLastError(), "InternalKernel launch failed");
         }
         const unsigned long long *d = sums.p;
-        if ((retval = Read(reinterpret_cast<unsigned long long *>(h_size), d, k))) return retval;
-        if ((retval = Read(reinterpret_cast<unsigned long long *>(h_internal), d + k, k))) return retval;
-        if ((retval = Read(reinterpret_cast<unsigned long long *>(h_volume), d + 2 * k, k))) return retval;
-        if ((retval = Read(reinterpret_cast<unsigned long long *>(total), d + 3 * k, 1))) return retval;
+        if ((retval = this->Read(reinterpret_cast<unsigned long long *>(h_size), d, k))) return retval;
+        if ((retval = this->Read(reinterpret_cast<unsigned long long *>(h_internal), d + k, k))) return retval;
+        if ((retval = this->Read(reinterpret_cast<unsigned long long *>(h_volume), d + 2 * k, k))) return retval;
+        if ((retval = this->Read(reinterpret_cast<unsigned long long *>(total), d + 3 * k, 1))) return retval;
         GR_CHECK(hipStreamSynchronize(stream), "LpProblem Summary sync failed");
         return retval;
     }

@@ -28,19 +28,18 @@ struct MatchingProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     typedef ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> Base;
 
     struct DataSlice {
-        int *d_src = nullptr, *d_dst = nullptr, *d_pw = nullptr;                     // the canonical pairs and their weights
-        int *d_nro = nullptr, *d_nci = nullptr, *d_neid = nullptr, *d_ew = nullptr;  // the neighbour CSR; the pair and the weight of every entry
-        int *d_mate = nullptr, *d_tgt = nullptr, *d_pp = nullptr, *d_cur = nullptr, *d_list[2] = {nullptr, nullptr};  // per vertex
-        unsigned char *d_in = nullptr;                                               // per pair
-        unsigned *d_words = nullptr;
-        unsigned long long *d_counters = nullptr;
-        Active *d_active = nullptr;
+        DeviceArray<int> d_src, d_dst, d_pw;  // the canonical pairs and their weights
+        DeviceArray<int> d_nro, d_nci, d_neid, d_ew;  // the neighbour CSR; the pair and the weight of every entry
+        DeviceArray<int> d_mate, d_tgt, d_pp, d_cur, d_list[2];  // per vertex
+        DeviceArray<unsigned char> d_in;  // per pair
+        DeviceArray<unsigned> d_words;
+        DeviceArray<unsigned long long> d_counters;
+        DeviceArray<Active> d_active;
         // the coarse graph of the last Contract
-        int *d_map = nullptr, *d_vweight = nullptr, *d_cro = nullptr, *d_cci = nullptr, *d_cw = nullptr;
+        DeviceArray<int> d_map, d_vweight, d_cro, d_cci, d_cw;
     };
 
-    DataSlice **data_slices = nullptr;
-    int malformed = 0;
+    SliceHolder<DataSlice> data_slices;
     long long pairs = 0;     // M
     long long with_neighbours = 0;  // vertices of degree > 0 (the first live list of the last Reset)
     unsigned seed = 0;
@@ -50,30 +49,6 @@ struct MatchingProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     double build_ms = 0;     // HIP-event time of the build of the pairs and the neighbour CSR
     Summary summary;         // of the last Enact
     long long coarse_nodes = -1, coarse_entries = 0;  // of the last Contract (-1: none)
-
-    ~MatchingProblem() override
-    {
-        if (data_slices) {
-            DataSlice *ds = data_slices[0];
-            if (ds) {
-                DropCoarse();
-                void *bufs[] = {ds->d_src, ds->d_dst, ds->d_pw, ds->d_nro, ds->d_nci, ds->d_neid, ds->d_ew, ds->d_mate, ds->d_tgt, ds->d_pp, ds->d_cur,
-                                ds->d_list[0], ds->d_list[1], ds->d_in, ds->d_words, ds->d_counters, ds->d_active};
-                for (void *b : bufs)
-                    if (b) util::GRError(hipFree(b), "MatchingProblem hipFree failed", __FILE__, __LINE__);
-                delete ds;
-            }
-            delete[] data_slices;
-        }
-    }
-
-    static int Grid(long long work)
-    {
-        long long blocks = (work + 255) / 256;
-        if (blocks < 1) blocks = 1;
-        if (blocks > 2048) blocks = 2048;  // 256 CUs x 8 workgroups, grid-stride the rest
-        return static_cast<int>(blocks);
-    }
 
     Ctx DeviceCtx(int wave_min_row) const
     {
@@ -106,18 +81,12 @@ struct MatchingProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         const long long n = this->nodes, m = this->edges;
         const size_t n1 = static_cast<size_t>(n > 0 ? n : 1);
         weighted = gs->d_edge_values != nullptr;
-        GR_CHECK(hipMalloc(&ds->d_words, sizeof(unsigned) * W_COUNT), "MatchingProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_counters, sizeof(unsigned long long) * C_COUNT), "MatchingProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_active, sizeof(Active)), "MatchingProblem hipMalloc failed");
+        if ((retval = ds->d_words.Alloc(W_COUNT))) return retval;
+        if ((retval = ds->d_counters.Alloc(C_COUNT))) return retval;
+        if ((retval = ds->d_active.Alloc(1))) return retval;
 
         // the CSR must be one: the build indexes with what it reads
-        bool bad = false;
-        if ((retval = graphio::DeviceValidateCsr(gs->d_row_offsets, gs->d_column_indices, n, m, reinterpret_cast<int *>(ds->d_words), stream, &bad)))
-            return retval;
-        if (bad) {
-            malformed = 1;
-            return hipErrorInvalidValue;
-        }
+        if ((retval = this->ValidateCsr())) return retval;
 
         long long M = 0;
         {  // (the build's scratch goes with this scope)
@@ -128,25 +97,25 @@ struct MatchingProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
             if ((retval = pg.Keys(gs->d_row_offsets, gs->d_column_indices, m, stream))) return retval;
             if ((retval = pg.Pairs(stream))) return retval;
             if ((retval = pg.Rows(stream))) return retval;
-            ds->d_src = graphio::Take(pg.d_src);
-            ds->d_dst = graphio::Take(pg.d_dst);
-            ds->d_nro = graphio::Take(pg.d_ro);
-            ds->d_nci = graphio::Take(pg.d_ci);
-            ds->d_neid = graphio::Take(pg.d_eid);
+            ds->d_src.Adopt(graphio::Take(pg.d_src));
+            ds->d_dst.Adopt(graphio::Take(pg.d_dst));
+            ds->d_nro.Adopt(graphio::Take(pg.d_ro));
+            ds->d_nci.Adopt(graphio::Take(pg.d_ci));
+            ds->d_neid.Adopt(graphio::Take(pg.d_eid));
             pairs = M = pg.pairs;
             if (M > 0) {
                 // the weights: every input entry finds its pair by bisecting the sorted row (the key sort carries no payload) and
                 // raises the pair's weight to its own, as max-flow's build adds its capacities up
                 const size_t ms = static_cast<size_t>(M);
-                GR_CHECK(hipMalloc(&ds->d_pw, sizeof(int) * ms), "MatchingProblem hipMalloc d_pw failed");
-                hipLaunchKernelGGL(oprtr::FillKernel<int>, dim3(Grid(M)), dim3(256), 0, stream, ds->d_pw, M, weighted ? INT_MIN : 1);
+                if ((retval = ds->d_pw.Alloc(ms))) return retval;
+                hipLaunchKernelGGL(oprtr::FillKernel<int>, dim3(graphio::PairGrid(M)), dim3(256), 0, stream, ds->d_pw, M, weighted ? INT_MIN : 1);
                 GR_CHECK(hipGetLastError(), "FillKernel launch failed");
                 if (weighted) {
-                    GR_CHECK(hipMalloc(&ds->d_ew, sizeof(int) * 2 * ms), "MatchingProblem hipMalloc d_ew failed");
-                    hipLaunchKernelGGL(PairWeightKernel, dim3(Grid(m)), dim3(256), 0, stream, gs->d_row_offsets, gs->d_column_indices,
+                    if ((retval = ds->d_ew.Alloc(2 * ms))) return retval;
+                    hipLaunchKernelGGL(PairWeightKernel, dim3(graphio::PairGrid(m)), dim3(256), 0, stream, gs->d_row_offsets, gs->d_column_indices,
                                        gs->d_edge_values, static_cast<int>(n), m, ds->d_nro, ds->d_nci, ds->d_neid, ds->d_pw);
                     GR_CHECK(hipGetLastError(), "PairWeightKernel launch failed");
-                    hipLaunchKernelGGL(EntryWeightKernel, dim3(Grid(2 * M)), dim3(256), 0, stream, ds->d_neid, ds->d_pw, 2 * M, ds->d_ew);
+                    hipLaunchKernelGGL(EntryWeightKernel, dim3(graphio::PairGrid(2 * M)), dim3(256), 0, stream, ds->d_neid, ds->d_pw, 2 * M, ds->d_ew);
                     GR_CHECK(hipGetLastError(), "EntryWeightKernel launch failed");
                 }
             }
@@ -156,9 +125,9 @@ struct MatchingProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         }
 
         const size_t m1 = static_cast<size_t>(M > 0 ? M : 1);
-        int **vertex_arrays[] = {&ds->d_mate, &ds->d_tgt, &ds->d_pp, &ds->d_cur, &ds->d_list[0], &ds->d_list[1]};
-        for (int **a : vertex_arrays) GR_CHECK(hipMalloc(a, sizeof(int) * n1), "MatchingProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_in, m1), "MatchingProblem hipMalloc failed");
+        DeviceArray<int> *vertex_arrays[] = {&ds->d_mate, &ds->d_tgt, &ds->d_pp, &ds->d_cur, &ds->d_list[0], &ds->d_list[1]};
+        for (DeviceArray<int> *a : vertex_arrays) if ((retval = a->Alloc(n1))) return retval;
+        if ((retval = ds->d_in.Alloc(m1))) return retval;
         return retval;
     }
 
@@ -168,8 +137,7 @@ struct MatchingProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         hipError_t retval = hipSuccess;
         seed = new_seed;
         if ((retval = Base::Init(stream_from_host, graph, num_gpus, true))) return retval;
-        data_slices = new DataSlice *[1];
-        data_slices[0] = new DataSlice();
+        data_slices.Make();
         return Build();
     }
 
@@ -179,8 +147,7 @@ struct MatchingProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         hipError_t retval = hipSuccess;
         seed = new_seed;
         if ((retval = Base::InitFromDevice(nodes, edges, d_row_offsets, d_column_indices, d_weights))) return retval;
-        data_slices = new DataSlice *[1];
-        data_slices[0] = new DataSlice();
+        data_slices.Make();
         return Build();
     }
 
@@ -194,7 +161,7 @@ struct MatchingProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         GR_CHECK(hipMemsetAsync(ds->d_words, 0, sizeof(unsigned) * W_COUNT, stream), "MatchingProblem memset failed");
         GR_CHECK(hipMemsetAsync(ds->d_counters, 0, sizeof(unsigned long long) * C_COUNT, stream), "MatchingProblem memset failed");
         if (pairs) GR_CHECK(hipMemsetAsync(ds->d_in, 0, static_cast<size_t>(pairs), stream), "MatchingProblem memset failed");
-        hipLaunchKernelGGL(SeedKernel, dim3(Grid(n)), dim3(256), 0, stream, DeviceCtx(kWaveMinRow), ds->d_list[0]);
+        hipLaunchKernelGGL(SeedKernel, dim3(graphio::PairGrid(n)), dim3(256), 0, stream, DeviceCtx(kWaveMinRow), ds->d_list[0]);
         GR_CHECK(hipGetLastError(), "SeedKernel launch failed");
         unsigned first = 0;
         GR_CHECK(hipMemcpyAsync(&first, ds->d_words + W_NEXT, sizeof(first), hipMemcpyDeviceToHost, stream), "MatchingProblem read-back failed");
@@ -207,27 +174,15 @@ struct MatchingProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         return retval;
     }
 
-    template <typename T>
-    hipError_t Read(T *h_out, const T *d_in, size_t count)
-    {
-        hipError_t retval = hipSuccess;
-        hipStream_t stream = this->graph_slices[0]->stream;
-        if (h_out && count) {
-            GR_CHECK(hipMemcpyAsync(h_out, d_in, sizeof(T) * count, hipMemcpyDeviceToHost, stream), "MatchingProblem read failed");
-            GR_CHECK(hipStreamSynchronize(stream), "MatchingProblem read sync failed");
-        }
-        return retval;
-    }
-
     // every pointer may be NULL
     hipError_t Pairs(int *h_src, int *h_dst, int *h_weight)
     {
         hipError_t retval = hipSuccess;
         DataSlice *ds = data_slices[0];
         const size_t M = static_cast<size_t>(pairs);
-        if ((retval = Read(h_src, ds->d_src, M))) return retval;
-        if ((retval = Read(h_dst, ds->d_dst, M))) return retval;
-        return Read(h_weight, ds->d_pw, M);
+        if ((retval = this->Read(h_src, ds->d_src.p, M))) return retval;
+        if ((retval = this->Read(h_dst, ds->d_dst.p, M))) return retval;
+        return this->Read(h_weight, ds->d_pw.p, M);
     }
 
     hipError_t Extract(unsigned char *h_in, int *h_mate, int *h_medge)
@@ -235,19 +190,15 @@ struct MatchingProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         hipError_t retval = hipSuccess;
         DataSlice *ds = data_slices[0];
         const size_t n = static_cast<size_t>(this->nodes), M = static_cast<size_t>(pairs);
-        if ((retval = Read(h_in, ds->d_in, M))) return retval;
-        if ((retval = Read(h_mate, ds->d_mate, n))) return retval;
-        return Read(h_medge, ds->d_pp, n);
+        if ((retval = this->Read(h_in, ds->d_in.p, M))) return retval;
+        if ((retval = this->Read(h_mate, ds->d_mate.p, n))) return retval;
+        return this->Read(h_medge, ds->d_pp.p, n);
     }
 
     void DropCoarse()
     {
         DataSlice *ds = data_slices[0];
-        int **bufs[] = {&ds->d_map, &ds->d_vweight, &ds->d_cro, &ds->d_cci, &ds->d_cw};
-        for (int **b : bufs) {
-            if (*b) util::GRError(hipFree(*b), "MatchingProblem hipFree failed", __FILE__, __LINE__);
-            *b = nullptr;
-        }
+        for (DeviceArray<int> *a : {&ds->d_map, &ds->d_vweight, &ds->d_cro, &ds->d_cci, &ds->d_cw}) a->Free();
         coarse_nodes = -1;
         coarse_entries = 0;
     }
@@ -278,19 +229,19 @@ struct MatchingProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         if ((retval = rep.Alloc(static_cast<size_t>(n)))) return retval;
         if ((retval = sums.Alloc(static_cast<size_t>(graphio::ScanScratchWords(n))))) return retval;
         if ((retval = rank.Alloc(static_cast<size_t>(n)))) return retval;
-        GR_CHECK(hipMalloc(&ds->d_map, sizeof(int) * static_cast<size_t>(n)), "MatchingProblem hipMalloc failed");
+        if ((retval = ds->d_map.Alloc(static_cast<size_t>(n)))) return retval;
         GR_CHECK(hipMemsetAsync(ds->d_words + W_FLAG, 0, sizeof(unsigned), stream), "MatchingProblem memset failed");
 
         // the representatives and their ranks (the total is behind the scan's tile offsets)
-        hipLaunchKernelGGL(RepFlagKernel, dim3(Grid(n)), dim3(256), 0, stream, ds->d_mate, n, rep.p);
+        hipLaunchKernelGGL(RepFlagKernel, dim3(graphio::PairGrid(n)), dim3(256), 0, stream, ds->d_mate, n, rep.p);
         GR_CHECK(hipGetLastError(), "RepFlagKernel launch failed");
         GR_CHECK(graphio::DeviceExclusiveScan<int>(rep.p, rank.p, n, sums.p, stream), "MatchingProblem rank scan failed");
         unsigned long long total = 0;
         GR_CHECK(hipMemcpyAsync(&total, sums.p + scan_tiles_n, sizeof(total), hipMemcpyDeviceToHost, stream), "MatchingProblem read total failed");
         GR_CHECK(hipStreamSynchronize(stream), "MatchingProblem Contract sync failed");
         const long long nc = static_cast<long long>(total);
-        GR_CHECK(hipMalloc(&ds->d_vweight, sizeof(int) * static_cast<size_t>(nc)), "MatchingProblem hipMalloc failed");
-        hipLaunchKernelGGL(MapKernel, dim3(Grid(n)), dim3(256), 0, stream, ds->d_mate, rank.p, d_vertex_weights, n, ds->d_map, ds->d_vweight,
+        if ((retval = ds->d_vweight.Alloc(static_cast<size_t>(nc)))) return retval;
+        hipLaunchKernelGGL(MapKernel, dim3(graphio::PairGrid(n)), dim3(256), 0, stream, ds->d_mate, rank.p, d_vertex_weights, n, ds->d_map, ds->d_vweight,
                            ds->d_words + W_FLAG);
         GR_CHECK(hipGetLastError(), "MapKernel launch failed");
 
@@ -298,7 +249,7 @@ struct MatchingProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         graphio::PairGraph pg(nc);
         if (M > 0) {
             if ((retval = pg.Reserve(M))) return retval;
-            hipLaunchKernelGGL(CoarseKeysKernel, dim3(Grid(M)), dim3(256), 0, stream, ds->d_src, ds->d_dst, ds->d_map, M, pg.col_bits, pg.sentinel,
+            hipLaunchKernelGGL(CoarseKeysKernel, dim3(graphio::PairGrid(M)), dim3(256), 0, stream, ds->d_src, ds->d_dst, ds->d_map, M, pg.col_bits, pg.sentinel,
                                pg.sort.Keys());
             GR_CHECK(hipGetLastError(), "CoarseKeysKernel launch failed");
             if ((retval = pg.SortKeys(stream))) return retval;
@@ -308,16 +259,16 @@ struct MatchingProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         if (Mc > 0) {
             if ((retval = w64.Alloc(static_cast<size_t>(Mc)))) return retval;
             GR_CHECK(hipMemsetAsync(w64.p, 0, sizeof(unsigned long long) * static_cast<size_t>(Mc), stream), "MatchingProblem memset failed");
-            hipLaunchKernelGGL(CoarseWeightKernel, dim3(Grid(M)), dim3(256), 0, stream, ds->d_src, ds->d_dst, ds->d_pw, ds->d_map, M, pg.col_bits,
+            hipLaunchKernelGGL(CoarseWeightKernel, dim3(graphio::PairGrid(M)), dim3(256), 0, stream, ds->d_src, ds->d_dst, ds->d_pw, ds->d_map, M, pg.col_bits,
                                pg.sentinel, pg.d_ckeys, Mc, w64.p);
             GR_CHECK(hipGetLastError(), "CoarseWeightKernel launch failed");
         }
         if ((retval = pg.Rows(stream))) return retval;
-        ds->d_cro = graphio::Take(pg.d_ro);
-        ds->d_cci = graphio::Take(pg.d_ci);
+        ds->d_cro.Adopt(graphio::Take(pg.d_ro));
+        ds->d_cci.Adopt(graphio::Take(pg.d_ci));
         if (Mc > 0) {
-            GR_CHECK(hipMalloc(&ds->d_cw, sizeof(int) * 2 * static_cast<size_t>(Mc)), "MatchingProblem hipMalloc failed");
-            hipLaunchKernelGGL(CoarseEntriesKernel, dim3(Grid(2 * Mc)), dim3(256), 0, stream, pg.d_eid, w64.p, 2 * Mc, ds->d_cw, ds->d_words + W_FLAG);
+            if ((retval = ds->d_cw.Alloc(2 * static_cast<size_t>(Mc)))) return retval;
+            hipLaunchKernelGGL(CoarseEntriesKernel, dim3(graphio::PairGrid(2 * Mc)), dim3(256), 0, stream, pg.d_eid, w64.p, 2 * Mc, ds->d_cw, ds->d_words + W_FLAG);
             GR_CHECK(hipGetLastError(), "CoarseEntriesKernel launch failed");
         }
         unsigned flag = 0;
@@ -335,11 +286,11 @@ struct MatchingProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         hipError_t retval = hipSuccess;
         DataSlice *ds = data_slices[0];
         const size_t nc = static_cast<size_t>(coarse_nodes), entries = static_cast<size_t>(coarse_entries);
-        if ((retval = Read(h_map, ds->d_map, static_cast<size_t>(this->nodes)))) return retval;
-        if ((retval = Read(h_ro, ds->d_cro, nc + 1))) return retval;
-        if ((retval = Read(h_ci, ds->d_cci, entries))) return retval;
-        if ((retval = Read(h_w, ds->d_cw, entries))) return retval;
-        return Read(h_vweight, ds->d_vweight, nc);
+        if ((retval = this->Read(h_map, ds->d_map.p, static_cast<size_t>(this->nodes)))) return retval;
+        if ((retval = this->Read(h_ro, ds->d_cro.p, nc + 1))) return retval;
+        if ((retval = this->Read(h_ci, ds->d_cci.p, entries))) return retval;
+        if ((retval = this->Read(h_w, ds->d_cw.p, entries))) return retval;
+        return this->Read(h_vweight, ds->d_vweight.p, nc);
     }
 };
 

@@ -27,26 +27,25 @@ struct MaxflowProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     typedef ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> Base;
 
     struct DataSlice {
-        int *d_a = nullptr, *d_b = nullptr, *d_cap_ab = nullptr, *d_cap_ba = nullptr, *d_pent = nullptr;  // per pair (pent: the entry a -> b)
-        int *d_nro = nullptr, *d_nci = nullptr, *d_neid = nullptr;                                      // the residual CSR and the pair of every entry
-        int *d_mate = nullptr, *d_cap = nullptr, *d_res = nullptr;                                      // per entry
+        DeviceArray<int> d_a, d_b, d_cap_ab, d_cap_ba, d_pent;  // per pair (pent: the entry a -> b)
+        DeviceArray<int> d_nro, d_nci, d_neid;  // the residual CSR and the pair of every entry
+        DeviceArray<int> d_mate, d_cap, d_res;  // per entry
         // per vertex
-        long long *d_excess = nullptr;
-        int *d_height = nullptr, *d_queue = nullptr, *d_mark = nullptr, *d_list[2] = {nullptr, nullptr}, *d_fwd = nullptr, *d_bwd = nullptr;
-        unsigned char *d_side = nullptr;
+        DeviceArray<long long> d_excess;
+        DeviceArray<int> d_height, d_queue, d_mark, d_list[2], d_fwd, d_bwd;
+        DeviceArray<unsigned char> d_side;
         // per pair
-        int *d_flow = nullptr;
-        unsigned char *d_cut = nullptr;
-        int *d_arc_flow = nullptr;  // per input entry, built at the first request behind an Enact
-        unsigned *d_words = nullptr;
-        unsigned long long *d_counters = nullptr;
-        unsigned long long *d_clock = nullptr;  // PHASE_COUNT + 1 stamps
-        Front *d_front = nullptr;
-        Active *d_active = nullptr;
+        DeviceArray<int> d_flow;
+        DeviceArray<unsigned char> d_cut;
+        DeviceArray<int> d_arc_flow;  // per input entry, built at the first request behind an Enact
+        DeviceArray<unsigned> d_words;
+        DeviceArray<unsigned long long> d_counters;
+        DeviceArray<unsigned long long> d_clock;  // PHASE_COUNT + 1 stamps
+        DeviceArray<Front> d_front;
+        DeviceArray<Active> d_active;
     };
 
-    DataSlice **data_slices = nullptr;
-    int malformed = 0;
+    SliceHolder<DataSlice> data_slices;
     long long pairs = 0;   // M
     int src = -1, sink = -1;
     bool fresh = false;    // Reset has run and Enact has not
@@ -54,30 +53,6 @@ struct MaxflowProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     bool have_arc_flow = false;
     double build_ms = 0;   // HIP-event time of the build of the pairs and the residual CSR
     Summary summary;       // of the last Enact
-
-    ~MaxflowProblem() override
-    {
-        if (data_slices) {
-            DataSlice *ds = data_slices[0];
-            if (ds) {
-                void *bufs[] = {ds->d_a, ds->d_b, ds->d_cap_ab, ds->d_cap_ba, ds->d_pent, ds->d_nro, ds->d_nci, ds->d_neid, ds->d_mate, ds->d_cap, ds->d_res,
-                                ds->d_excess, ds->d_height, ds->d_queue, ds->d_mark, ds->d_list[0], ds->d_list[1], ds->d_fwd, ds->d_bwd, ds->d_side, ds->d_flow,
-                                ds->d_cut, ds->d_arc_flow, ds->d_words, ds->d_counters, ds->d_clock, ds->d_front, ds->d_active};
-                for (void *b : bufs)
-                    if (b) util::GRError(hipFree(b), "MaxflowProblem hipFree failed", __FILE__, __LINE__);
-                delete ds;
-            }
-            delete[] data_slices;
-        }
-    }
-
-    static int Grid(long long work)
-    {
-        long long blocks = (work + 255) / 256;
-        if (blocks < 1) blocks = 1;
-        if (blocks > 2048) blocks = 2048;  // 256 CUs x 8 workgroups, grid-stride the rest
-        return static_cast<int>(blocks);
-    }
 
     Ctx DeviceCtx(int wave_min_row, int discharge_steps) const
     {
@@ -109,21 +84,15 @@ struct MaxflowProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         hipStream_t stream = gs->stream;
         const long long n = this->nodes, m = this->edges;
         const size_t n1 = static_cast<size_t>(n > 0 ? n : 1);
-        GR_CHECK(hipMalloc(&ds->d_words, sizeof(unsigned) * W_COUNT), "MaxflowProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_counters, sizeof(unsigned long long) * C_COUNT), "MaxflowProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_clock, sizeof(unsigned long long) * (PHASE_COUNT + 1)), "MaxflowProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_front, sizeof(Front)), "MaxflowProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_active, sizeof(Active)), "MaxflowProblem hipMalloc failed");
+        if ((retval = ds->d_words.Alloc(W_COUNT))) return retval;
+        if ((retval = ds->d_counters.Alloc(C_COUNT))) return retval;
+        if ((retval = ds->d_clock.Alloc(PHASE_COUNT + 1))) return retval;
+        if ((retval = ds->d_front.Alloc(1))) return retval;
+        if ((retval = ds->d_active.Alloc(1))) return retval;
 
         // the CSR must be one: the build indexes with what it reads
-        bool bad = false;
         GR_CHECK(hipMemsetAsync(ds->d_words, 0, sizeof(unsigned) * W_COUNT, stream), "MaxflowProblem memset failed");  // (W_BAD, for the build)
-        if ((retval = graphio::DeviceValidateCsr(gs->d_row_offsets, gs->d_column_indices, n, m, reinterpret_cast<int *>(ds->d_words), stream, &bad)))
-            return retval;
-        if (bad) {
-            malformed = 1;
-            return hipErrorInvalidValue;
-        }
+        if ((retval = this->ValidateCsr())) return retval;
 
         long long M = 0;
         {  // (the build's scratch goes with this scope)
@@ -135,11 +104,11 @@ struct MaxflowProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
             if ((retval = pg.Keys(gs->d_row_offsets, gs->d_column_indices, m, stream))) return retval;
             if ((retval = pg.Pairs(stream))) return retval;
             if ((retval = pg.Rows(stream))) return retval;
-            ds->d_a = graphio::Take(pg.d_src);
-            ds->d_b = graphio::Take(pg.d_dst);
-            ds->d_nro = graphio::Take(pg.d_ro);
-            ds->d_nci = graphio::Take(pg.d_ci);
-            ds->d_neid = graphio::Take(pg.d_eid);
+            ds->d_a.Adopt(graphio::Take(pg.d_src));
+            ds->d_b.Adopt(graphio::Take(pg.d_dst));
+            ds->d_nro.Adopt(graphio::Take(pg.d_ro));
+            ds->d_nci.Adopt(graphio::Take(pg.d_ci));
+            ds->d_neid.Adopt(graphio::Take(pg.d_eid));
             M = pg.pairs;
             if (m > 0) {
                 if (M > 0) {
@@ -148,29 +117,26 @@ struct MaxflowProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
                     const size_t ms = static_cast<size_t>(M);
                     if ((retval = cap64.Alloc(2 * ms))) return retval;
                     GR_CHECK(hipMemsetAsync(cap64.p, 0, sizeof(unsigned long long) * 2 * ms, stream), "MaxflowProblem memset failed");
-                    GR_CHECK(hipMalloc(&ds->d_mate, sizeof(int) * 2 * ms), "MaxflowProblem hipMalloc d_mate failed");
-                    GR_CHECK(hipMalloc(&ds->d_cap, sizeof(int) * 2 * ms), "MaxflowProblem hipMalloc d_cap failed");
-                    GR_CHECK(hipMalloc(&ds->d_res, sizeof(int) * 2 * ms), "MaxflowProblem hipMalloc d_res failed");
-                    GR_CHECK(hipMalloc(&ds->d_cap_ab, sizeof(int) * ms), "MaxflowProblem hipMalloc failed");
-                    GR_CHECK(hipMalloc(&ds->d_cap_ba, sizeof(int) * ms), "MaxflowProblem hipMalloc failed");
-                    GR_CHECK(hipMalloc(&ds->d_pent, sizeof(int) * ms), "MaxflowProblem hipMalloc failed");
+                    if ((retval = ds->d_mate.Alloc(2 * ms))) return retval;
+                    if ((retval = ds->d_cap.Alloc(2 * ms))) return retval;
+                    if ((retval = ds->d_res.Alloc(2 * ms))) return retval;
+                    if ((retval = ds->d_cap_ab.Alloc(ms))) return retval;
+                    if ((retval = ds->d_cap_ba.Alloc(ms))) return retval;
+                    if ((retval = ds->d_pent.Alloc(ms))) return retval;
                 }
                 // (self-loops only, M = 0: their capacities are still looked at)
-                hipLaunchKernelGGL(AccumulateKernel, dim3(Grid(m)), dim3(256), 0, stream, gs->d_row_offsets, gs->d_column_indices, gs->d_edge_values,
+                hipLaunchKernelGGL(AccumulateKernel, dim3(graphio::PairGrid(m)), dim3(256), 0, stream, gs->d_row_offsets, gs->d_column_indices, gs->d_edge_values,
                                    static_cast<int>(n), m, ds->d_nro, ds->d_nci, cap64.p, ds->d_words + W_BAD);
                 GR_CHECK(hipGetLastError(), "AccumulateKernel launch failed");
                 if (M > 0) {
-                    hipLaunchKernelGGL(PairEntriesKernel, dim3(Grid(M)), dim3(256), 0, stream, ds->d_a, ds->d_b, M, ds->d_nro, ds->d_nci, cap64.p, ds->d_pent,
+                    hipLaunchKernelGGL(PairEntriesKernel, dim3(graphio::PairGrid(M)), dim3(256), 0, stream, ds->d_a, ds->d_b, M, ds->d_nro, ds->d_nci, cap64.p, ds->d_pent,
                                        ds->d_mate, ds->d_cap, ds->d_cap_ab, ds->d_cap_ba, ds->d_words + W_BAD);
                     GR_CHECK(hipGetLastError(), "PairEntriesKernel launch failed");
                 }
                 unsigned bad_cap = 0;
                 GR_CHECK(hipMemcpyAsync(&bad_cap, ds->d_words + W_BAD, sizeof(bad_cap), hipMemcpyDeviceToHost, stream), "MaxflowProblem read-back failed");
                 GR_CHECK(hipStreamSynchronize(stream), "MaxflowProblem read-back sync failed");
-                if (bad_cap) {
-                    malformed = 1;
-                    return hipErrorInvalidValue;
-                }
+                if (bad_cap) return this->Malformed();
             }
             pairs = M;
             if ((retval = ev.Record(1, stream))) return retval;
@@ -179,13 +145,13 @@ struct MaxflowProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         }
 
         const size_t m1 = static_cast<size_t>(M > 0 ? M : 1);
-        int **vertex_arrays[] = {&ds->d_height, &ds->d_queue, &ds->d_mark, &ds->d_list[0], &ds->d_list[1], &ds->d_fwd, &ds->d_bwd};
-        for (int **a : vertex_arrays) GR_CHECK(hipMalloc(a, sizeof(int) * n1), "MaxflowProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_excess, sizeof(long long) * n1), "MaxflowProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_side, n1), "MaxflowProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_flow, sizeof(int) * m1), "MaxflowProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_cut, m1), "MaxflowProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_arc_flow, sizeof(int) * static_cast<size_t>(m > 0 ? m : 1)), "MaxflowProblem hipMalloc failed");
+        DeviceArray<int> *vertex_arrays[] = {&ds->d_height, &ds->d_queue, &ds->d_mark, &ds->d_list[0], &ds->d_list[1], &ds->d_fwd, &ds->d_bwd};
+        for (DeviceArray<int> *a : vertex_arrays) if ((retval = a->Alloc(n1))) return retval;
+        if ((retval = ds->d_excess.Alloc(n1))) return retval;
+        if ((retval = ds->d_side.Alloc(n1))) return retval;
+        if ((retval = ds->d_flow.Alloc(m1))) return retval;
+        if ((retval = ds->d_cut.Alloc(m1))) return retval;
+        if ((retval = ds->d_arc_flow.Alloc(static_cast<size_t>(m > 0 ? m : 1)))) return retval;
         return retval;
     }
 
@@ -194,8 +160,7 @@ struct MaxflowProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     {
         hipError_t retval = hipSuccess;
         if ((retval = Base::Init(stream_from_host, graph, num_gpus, true))) return retval;
-        data_slices = new DataSlice *[1];
-        data_slices[0] = new DataSlice();
+        data_slices.Make();
         return Build();
     }
 
@@ -203,8 +168,7 @@ struct MaxflowProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     {
         hipError_t retval = hipSuccess;
         if ((retval = Base::InitFromDevice(nodes, edges, d_row_offsets, d_column_indices, d_capacities))) return retval;
-        data_slices = new DataSlice *[1];
-        data_slices[0] = new DataSlice();
+        data_slices.Make();
         return Build();
     }
 
@@ -232,28 +196,16 @@ struct MaxflowProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         return retval;
     }
 
-    template <typename T>
-    hipError_t Read(T *h_out, const T *d_in, size_t count)
-    {
-        hipError_t retval = hipSuccess;
-        hipStream_t stream = this->graph_slices[0]->stream;
-        if (h_out && count) {
-            GR_CHECK(hipMemcpyAsync(h_out, d_in, sizeof(T) * count, hipMemcpyDeviceToHost, stream), "MaxflowProblem read failed");
-            GR_CHECK(hipStreamSynchronize(stream), "MaxflowProblem read sync failed");
-        }
-        return retval;
-    }
-
     // every pointer may be NULL
     hipError_t Pairs(int *h_a, int *h_b, int *h_cap_ab, int *h_cap_ba)
     {
         hipError_t retval = hipSuccess;
         DataSlice *ds = data_slices[0];
         const size_t M = static_cast<size_t>(pairs);
-        if ((retval = Read(h_a, ds->d_a, M))) return retval;
-        if ((retval = Read(h_b, ds->d_b, M))) return retval;
-        if ((retval = Read(h_cap_ab, ds->d_cap_ab, M))) return retval;
-        return Read(h_cap_ba, ds->d_cap_ba, M);
+        if ((retval = this->Read(h_a, ds->d_a.p, M))) return retval;
+        if ((retval = this->Read(h_b, ds->d_b.p, M))) return retval;
+        if ((retval = this->Read(h_cap_ab, ds->d_cap_ab.p, M))) return retval;
+        return this->Read(h_cap_ba, ds->d_cap_ba.p, M);
     }
 
     hipError_t Extract(int *h_flow, unsigned char *h_side, unsigned char *h_cut)
@@ -261,9 +213,9 @@ struct MaxflowProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         hipError_t retval = hipSuccess;
         DataSlice *ds = data_slices[0];
         const size_t n = static_cast<size_t>(this->nodes), M = static_cast<size_t>(pairs);
-        if ((retval = Read(h_flow, ds->d_flow, M))) return retval;
-        if ((retval = Read(h_side, ds->d_side, n))) return retval;
-        return Read(h_cut, ds->d_cut, M);
+        if ((retval = this->Read(h_flow, ds->d_flow.p, M))) return retval;
+        if ((retval = this->Read(h_side, ds->d_side.p, n))) return retval;
+        return this->Read(h_cut, ds->d_cut.p, M);
     }
 
     // arc_flow[] per input entry: a function of the residuals and the input, computed once per Enact
@@ -276,7 +228,7 @@ struct MaxflowProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         if (m < 1) return retval;
         if (!have_arc_flow) {
             if (pairs > 0) {
-                hipLaunchKernelGGL(ArcFlowKernel, dim3(Grid(m)), dim3(256), 0, gs->stream, gs->d_row_offsets, gs->d_column_indices, gs->d_edge_values,
+                hipLaunchKernelGGL(ArcFlowKernel, dim3(graphio::PairGrid(m)), dim3(256), 0, gs->stream, gs->d_row_offsets, gs->d_column_indices, gs->d_edge_values,
                                    static_cast<int>(this->nodes), m, ds->d_nro, ds->d_nci, ds->d_cap, ds->d_res, ds->d_arc_flow);
                 GR_CHECK(hipGetLastError(), "ArcFlowKernel launch failed");
             } else {
@@ -284,7 +236,7 @@ struct MaxflowProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
             }
             have_arc_flow = true;
         }
-        return Read(h_arc_flow, ds->d_arc_flow, static_cast<size_t>(m));
+        return this->Read(h_arc_flow, ds->d_arc_flow.p, static_cast<size_t>(m));
     }
 };
 

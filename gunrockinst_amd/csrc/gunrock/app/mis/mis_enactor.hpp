@@ -99,7 +99,7 @@ class MISEnactor : public EnactorBase {
         const Keys k = problem->DeviceKeys();
         const State st = problem->DeviceState();
         auto grid = [&](long long work, int cap) {
-            int blocks = Problem::Grid(work);
+            int blocks = graphio::PairGrid(work);
             if (blocks > cap) blocks = cap;
             return max_grid_size > 0 && max_grid_size < blocks ? max_grid_size : blocks;
         };

@@ -30,24 +30,23 @@ struct MISProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     typedef int Value;
 
     struct DataSlice {
-        int *d_mis_ids = nullptr;              // the result (reference d_mis_ids); the colourings' state table
-        unsigned char *d_state = nullptr;      // the set's state table: 0 undecided, 1 in, 2 out
-        int *d_priorities = nullptr;           // caller priorities (owned copy, or borrowed with the device CSR), or NULL: hashed
-        bool owns_priorities = false;
-        int *d_pos = nullptr;                  // cursors (mis_functor.hpp State)
-        int *d_acc = nullptr;
-        unsigned long long *d_mask = nullptr;
-        int *d_list[2] = {nullptr, nullptr};   // the worklist of undecided vertices, double-buffered
-        int *d_words = nullptr;                // [0], [1] worklist lengths
-        int *d_tail_words = nullptr;           // [0] undecided after a tail pass; per window [1 + 2w] its undecided, [2 + 2w] its sweeps
-        unsigned long long *d_reads = nullptr; // [0] row entries walked; [1], [2] Extract's sum and maximum of ids; [3] polls
-        int *d_inv_row_offsets = nullptr;      // in-neighbour CSR of an asymmetric input (owned)
-        int *d_inv_column_indices = nullptr;
+        DeviceArray<int> d_mis_ids;  // the result (reference d_mis_ids); the colourings' state table
+        DeviceArray<unsigned char> d_state;  // the set's state table: 0 undecided, 1 in, 2 out
+        DeviceArray<int> d_own_priorities;  // the copy of the priorities a host Init gave
+        int *d_priorities = nullptr;             // caller priorities (that copy, or borrowed with the device CSR), or NULL: hashed
+        DeviceArray<int> d_pos;  // cursors (mis_functor.hpp State)
+        DeviceArray<int> d_acc;
+        DeviceArray<unsigned long long> d_mask;
+        DeviceArray<int> d_list[2];  // the worklist of undecided vertices, double-buffered
+        DeviceArray<int> d_words;  // [0], [1] worklist lengths
+        DeviceArray<int> d_tail_words;  // [0] undecided after a tail pass; per window [1 + 2w] its undecided, [2 + 2w] its sweeps
+        DeviceArray<unsigned long long> d_reads; // [0] row entries walked; [1], [2] Extract's sum and maximum of ids; [3] polls
+        DeviceArray<int> d_inv_row_offsets;  // in-neighbour CSR of an asymmetric input (owned)
+        DeviceArray<int> d_inv_column_indices;
     };
 
-    DataSlice **data_slices = nullptr;
+    SliceHolder<DataSlice> data_slices;
     int symmetric = 0;      // every edge has its mirror (sorted duplicate-free rows): a row is the whole neighbourhood
-    int malformed = 0;      // Init found offsets or columns that are not a CSR of `nodes` vertices
     unsigned seed = 0;
     int mode = MIS_SET;     // of the last Enact: Extract's summary is the set size or the number of colours
     long long summary = 0;
@@ -56,29 +55,11 @@ struct MISProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     long long tail_windows = 0;            // windows d_tail_words has room for
     graphio::DeviceKeySort order_sort;     // orders the tail's worklist by key (scratch allocated at the first use)
 
+    // (the slice frees its own arrays; the pinned words are the problem's)
     ~MISProblem() override
     {
-        if (data_slices) {
-            DataSlice *ds = data_slices[0];
-            if (ds) {
-                void *bufs[] = {ds->d_mis_ids, ds->d_state, ds->owns_priorities ? ds->d_priorities : nullptr, ds->d_pos, ds->d_acc, ds->d_mask,
-                                ds->d_list[0], ds->d_list[1], ds->d_words, ds->d_tail_words, ds->d_reads, ds->d_inv_row_offsets, ds->d_inv_column_indices};
-                for (void *b : bufs)
-                    if (b) util::GRError(hipFree(b), "MISProblem hipFree failed", __FILE__, __LINE__);
-                delete ds;
-            }
-            delete[] data_slices;
-        }
         if (h_words) util::GRError(hipHostFree(h_words), "MISProblem hipHostFree failed", __FILE__, __LINE__);
         if (h_tail_words) util::GRError(hipHostFree(h_tail_words), "MISProblem hipHostFree failed", __FILE__, __LINE__);
-    }
-
-    static int Grid(long long work)
-    {
-        long long blocks = (work + kSweepThreads - 1) / kSweepThreads;
-        if (blocks < 1) blocks = 1;
-        if (blocks > 2048) blocks = 2048;  // 256 CUs x 8 workgroups, grid-stride the rest
-        return static_cast<int>(blocks);
     }
 
     // `count` device words read back (pinned), count <= 4
@@ -96,14 +77,12 @@ struct MISProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         hipError_t retval = hipSuccess;
         if (windows <= tail_windows) return retval;
         DataSlice *ds = data_slices[0];
-        if (ds->d_tail_words) GR_CHECK(hipFree(ds->d_tail_words), "MISProblem hipFree failed");
         if (h_tail_words) GR_CHECK(hipHostFree(h_tail_words), "MISProblem hipHostFree failed");
-        ds->d_tail_words = nullptr;
         h_tail_words = nullptr;
         tail_windows = 0;
-        const size_t bytes = sizeof(int) * static_cast<size_t>(2 * windows + 1);
-        GR_CHECK(hipMalloc(&ds->d_tail_words, bytes), "MISProblem hipMalloc failed");
-        GR_CHECK(hipHostMalloc(&h_tail_words, bytes, hipHostMallocDefault), "MISProblem hipHostMalloc failed");
+        const size_t words = static_cast<size_t>(2 * windows + 1);
+        if ((retval = ds->d_tail_words.Alloc(words))) return retval;
+        GR_CHECK(hipHostMalloc(&h_tail_words, sizeof(int) * words, hipHostMallocDefault), "MISProblem hipHostMalloc failed");
         tail_windows = windows;
         return retval;
     }
@@ -130,16 +109,11 @@ struct MISProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         const long long n = this->nodes, m = this->edges;
         const size_t n1 = static_cast<size_t>(n > 0 ? n : 1);
         GR_CHECK(hipHostMalloc(&h_words, sizeof(int) * 4, hipHostMallocDefault), "MISProblem hipHostMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_words, sizeof(int) * 4), "MISProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_reads, sizeof(unsigned long long) * 4), "MISProblem hipMalloc failed");
+        if ((retval = ds->d_words.Alloc(4))) return retval;
+        if ((retval = ds->d_reads.Alloc(4))) return retval;
 
         // 1. the CSR must be one: nothing in the sweeps indexes with an unchecked value
-        bool bad = false;
-        if ((retval = graphio::DeviceValidateCsr(gs->d_row_offsets, gs->d_column_indices, n, m, ds->d_words, stream, &bad))) return retval;
-        if (bad) {
-            malformed = 1;
-            return hipErrorInvalidValue;
-        }
+        if ((retval = this->ValidateCsr())) return retval;
 
         // 2. is a row the whole neighbourhood?  (exact test, graphio/symmetry.hpp; "no" for unsorted rows and duplicates too)
         symmetric = 0;
@@ -149,21 +123,21 @@ struct MISProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
                      "MISProblem symmetry test failed");
             symmetric = yes ? 1 : 0;
             if (!yes) {
-                GR_CHECK(hipMalloc(&ds->d_inv_row_offsets, sizeof(int) * (n1 + 1)), "MISProblem hipMalloc inverse offsets failed");
-                GR_CHECK(hipMalloc(&ds->d_inv_column_indices, sizeof(int) * static_cast<size_t>(m)), "MISProblem hipMalloc inverse columns failed");
+                if ((retval = ds->d_inv_row_offsets.Alloc(n1 + 1))) return retval;
+                if ((retval = ds->d_inv_column_indices.Alloc(static_cast<size_t>(m)))) return retval;
                 GR_CHECK(graphio::DeviceTransposeCsr(static_cast<int>(n), m, gs->d_row_offsets, gs->d_column_indices, ds->d_inv_row_offsets,
                                                      ds->d_inv_column_indices, stream),
                          "MISProblem transpose failed");
             }
         }
 
-        GR_CHECK(hipMalloc(&ds->d_mis_ids, sizeof(int) * n1), "MISProblem hipMalloc d_mis_ids failed");
-        GR_CHECK(hipMalloc(&ds->d_state, n1), "MISProblem hipMalloc d_state failed");
-        GR_CHECK(hipMalloc(&ds->d_pos, sizeof(int) * n1), "MISProblem hipMalloc d_pos failed");
-        GR_CHECK(hipMalloc(&ds->d_acc, sizeof(int) * n1), "MISProblem hipMalloc d_acc failed");
-        GR_CHECK(hipMalloc(&ds->d_mask, sizeof(unsigned long long) * n1), "MISProblem hipMalloc d_mask failed");
-        GR_CHECK(hipMalloc(&ds->d_list[0], sizeof(int) * n1), "MISProblem hipMalloc d_list failed");
-        GR_CHECK(hipMalloc(&ds->d_list[1], sizeof(int) * n1), "MISProblem hipMalloc d_list failed");
+        if ((retval = ds->d_mis_ids.Alloc(n1))) return retval;
+        if ((retval = ds->d_state.Alloc(n1))) return retval;
+        if ((retval = ds->d_pos.Alloc(n1))) return retval;
+        if ((retval = ds->d_acc.Alloc(n1))) return retval;
+        if ((retval = ds->d_mask.Alloc(n1))) return retval;
+        if ((retval = ds->d_list[0].Alloc(n1))) return retval;
+        if ((retval = ds->d_list[1].Alloc(n1))) return retval;
         GR_CHECK(hipStreamSynchronize(stream), "MISProblem AllocData failed");
         return retval;
     }
@@ -175,13 +149,11 @@ struct MISProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         hipError_t retval = hipSuccess;
         if ((retval = Base::Init(stream_from_host, graph, num_gpus, false))) return retval;
         seed = seed_;
-        data_slices = new DataSlice *[1];
-        data_slices[0] = new DataSlice();
+        data_slices.Make();
         if (h_priorities) {
             DataSlice *ds = data_slices[0];
-            const size_t bytes = sizeof(int) * static_cast<size_t>(graph.nodes > 0 ? graph.nodes : 1);
-            GR_CHECK(hipMalloc(&ds->d_priorities, bytes), "MISProblem hipMalloc d_priorities failed");
-            ds->owns_priorities = true;
+            if ((retval = ds->d_own_priorities.Alloc(static_cast<size_t>(graph.nodes)))) return retval;
+            ds->d_priorities = ds->d_own_priorities;
             GR_CHECK(hipMemcpy(ds->d_priorities, h_priorities, sizeof(int) * static_cast<size_t>(graph.nodes), hipMemcpyHostToDevice),
                      "MISProblem hipMemcpy d_priorities failed");
         }
@@ -193,8 +165,7 @@ struct MISProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         hipError_t retval = hipSuccess;
         if ((retval = Base::InitFromDevice(nodes, edges, d_row_offsets, d_column_indices))) return retval;
         seed = seed_;
-        data_slices = new DataSlice *[1];
-        data_slices[0] = new DataSlice();
+        data_slices.Make();
         data_slices[0]->d_priorities = d_priorities;
         return AllocData();
     }
@@ -223,7 +194,7 @@ struct MISProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         hipStream_t stream = this->graph_slices[0]->stream;
         unsigned long long out[2] = {0, 0};
         GR_CHECK(hipMemsetAsync(ds->d_reads + 1, 0, sizeof(unsigned long long) * 2, stream), "MISProblem memset failed");
-        hipLaunchKernelGGL(SummaryKernel, dim3(Grid(this->nodes)), dim3(256), 0, stream, ds->d_mis_ids, static_cast<long long>(this->nodes),
+        hipLaunchKernelGGL(SummaryKernel, dim3(graphio::PairGrid(this->nodes)), dim3(256), 0, stream, ds->d_mis_ids, static_cast<long long>(this->nodes),
                            ds->d_reads + 1);
         GR_CHECK(hipGetLastError(), "SummaryKernel launch failed");
         GR_CHECK(hipMemcpyAsync(out, ds->d_reads + 1, sizeof(out), hipMemcpyDeviceToHost, stream), "MISProblem read summary failed");

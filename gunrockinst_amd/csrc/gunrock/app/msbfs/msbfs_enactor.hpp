@@ -109,7 +109,7 @@ class MsbfsEnactor : public EnactorBase {
                 if ((retval = step.Start(stream))) return retval;  // (a level is timed as a whole)
                 if (pull) {
                     if ((retval = clear_words())) return retval;
-                    hipLaunchKernelGGL(PullKernel, cap(Problem::Grid(n)), block, 0, stream, c);
+                    hipLaunchKernelGGL(PullKernel, cap(graphio::PairGrid(n)), block, 0, stream, c);
                     GR_CHECK(hipGetLastError(), "PullKernel launch failed");
                     ++step.launches;
                     ++pull_levels;
@@ -125,7 +125,7 @@ class MsbfsEnactor : public EnactorBase {
                     }
                     if (!queued) {
                         if ((retval = clear_words())) return retval;
-                        hipLaunchKernelGGL(CompactKernel, cap(Problem::Grid(n)), block, 0, stream, c);
+                        hipLaunchKernelGGL(CompactKernel, cap(graphio::PairGrid(n)), block, 0, stream, c);
                         GR_CHECK(hipGetLastError(), "CompactKernel launch failed");
                         ++step.launches;
                         queued = true;
@@ -135,7 +135,7 @@ class MsbfsEnactor : public EnactorBase {
                     hipLaunchKernelGGL(PushKernel, StepGrid(count, tile, kPushWavesPerBlock, max_grid_size), block, 0, stream, c, count, tile);
                     GR_CHECK(hipGetLastError(), "PushKernel launch failed");
                     // a push reaches at most one vertex per entry it walks
-                    hipLaunchKernelGGL(UpdateKernel, cap(Problem::Grid(frontier_edges < n ? frontier_edges : n)), block, 0, stream, c);
+                    hipLaunchKernelGGL(UpdateKernel, cap(graphio::PairGrid(frontier_edges < n ? frontier_edges : n)), block, 0, stream, c);
                     GR_CHECK(hipGetLastError(), "UpdateKernel launch failed");
                     step.launches += 2;
                     ++push_levels;

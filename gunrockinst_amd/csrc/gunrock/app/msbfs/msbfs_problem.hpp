@@ -30,22 +30,21 @@ struct MsbfsProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
 
     struct DataSlice {
         int *d_lent_iro = nullptr, *d_lent_ici = nullptr;    // the caller's in-neighbour lists
-        int *d_built_iro = nullptr, *d_built_ici = nullptr;  // the transpose built here
+        DeviceArray<int> d_built_iro, d_built_ici;  // the transpose built here
         const int *d_iro = nullptr, *d_ici = nullptr;        // what the pull levels read (nullptr: none)
-        Word *d_seen = nullptr, *d_frontier = nullptr, *d_next = nullptr;
-        int *d_queue[2] = {nullptr, nullptr};
-        Word *d_words = nullptr;
-        int *d_sources = nullptr;
-        unsigned long long *d_reached = nullptr, *d_dist_sum = nullptr;
-        int *d_ecc = nullptr;
-        int *d_sources_reaching = nullptr;
-        unsigned long long *d_in_dist_sum = nullptr;
-        int *d_depth = nullptr;
+        DeviceArray<Word> d_seen, d_frontier, d_next;
+        DeviceArray<int> d_queue[2];
+        DeviceArray<Word> d_words;
+        DeviceArray<int> d_sources;
+        DeviceArray<unsigned long long> d_reached, d_dist_sum;
+        DeviceArray<int> d_ecc;
+        DeviceArray<int> d_sources_reaching;
+        DeviceArray<unsigned long long> d_in_dist_sum;
+        DeviceArray<int> d_depth;
         size_t source_capacity = 0, depth_capacity = 0;
     };
 
-    DataSlice **data_slices = nullptr;
-    int malformed = 0;    // Init found offsets or columns that are not a CSR of `nodes` vertices
+    SliceHolder<DataSlice> data_slices;
     bool fresh = false;   // Reset has run and Enact has not
     double build_ms = 0;  // HIP-event time of the transpose (0 when none was built)
     int inverse = INVERSE_AUTO;  // option "inverse", settled by the next Reset
@@ -53,29 +52,6 @@ struct MsbfsProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     int symmetric = -1;          // the symmetry check's answer once asked
     std::vector<int> sources;    // of the last Reset
     bool store_depths = false;
-
-    ~MsbfsProblem() override
-    {
-        if (data_slices) {
-            DataSlice *ds = data_slices[0];
-            if (ds) {
-                void *bufs[] = {ds->d_built_iro, ds->d_built_ici, ds->d_seen, ds->d_frontier, ds->d_next, ds->d_queue[0], ds->d_queue[1], ds->d_words,
-                                ds->d_sources, ds->d_reached, ds->d_dist_sum, ds->d_ecc, ds->d_sources_reaching, ds->d_in_dist_sum, ds->d_depth};
-                for (void *b : bufs)
-                    if (b) util::GRError(hipFree(b), "MsbfsProblem hipFree failed", __FILE__, __LINE__);
-                delete ds;
-            }
-            delete[] data_slices;
-        }
-    }
-
-    static int Grid(long long work)
-    {
-        long long blocks = (work + kThreads - 1) / kThreads;
-        if (blocks < 1) blocks = 1;
-        if (blocks > 2048) blocks = 2048;  // 256 CUs x 8 workgroups, grid-stride the rest
-        return static_cast<int>(blocks);
-    }
 
     long long Batches() const { return (static_cast<long long>(sources.size()) + kBatch - 1) / kBatch; }
 
@@ -110,35 +86,23 @@ struct MsbfsProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         return c;
     }
 
-    // a CSR of `nodes` vertices?  (the kernels index with what they read)
-    hipError_t Validate(const int *d_ro, const int *d_ci, bool *bad)
-    {
-        return graphio::DeviceValidateCsr(d_ro, d_ci, this->nodes, this->edges, reinterpret_cast<int *>(data_slices[0]->d_words),
-                                          this->graph_slices[0]->stream, bad);
-    }
-
     hipError_t Build(int *d_inv_row_offsets, int *d_inv_col_indices)
     {
         hipError_t retval = hipSuccess;
         DataSlice *ds = data_slices[0];
-        GraphSlice<int, int, int> *gs = this->graph_slices[0];
         const size_t n1 = static_cast<size_t>(this->nodes > 0 ? this->nodes : 1);
-        GR_CHECK(hipMalloc(&ds->d_words, sizeof(Word) * W_COUNT), "MsbfsProblem hipMalloc failed");
-        bool bad = false;
-        if ((retval = Validate(gs->d_row_offsets, gs->d_column_indices, &bad))) return retval;
-        if (!bad && d_inv_row_offsets && (retval = Validate(d_inv_row_offsets, d_inv_col_indices, &bad))) return retval;
-        if (bad) {
-            malformed = 1;
-            return hipErrorInvalidValue;
-        }
+        if ((retval = ds->d_words.Alloc(W_COUNT))) return retval;
+        // CSRs of `nodes` vertices?  (the kernels index with what they read)
+        if ((retval = this->ValidateCsr())) return retval;
+        if (d_inv_row_offsets && (retval = this->ValidateCsr(d_inv_row_offsets, d_inv_col_indices))) return retval;
         ds->d_lent_iro = d_inv_row_offsets;
         ds->d_lent_ici = d_inv_col_indices;
-        Word **words[] = {&ds->d_seen, &ds->d_frontier, &ds->d_next};
-        for (Word **a : words) GR_CHECK(hipMalloc(a, sizeof(Word) * n1), "MsbfsProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_queue[0], sizeof(int) * n1), "MsbfsProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_queue[1], sizeof(int) * n1), "MsbfsProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_sources_reaching, sizeof(int) * n1), "MsbfsProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_in_dist_sum, sizeof(unsigned long long) * n1), "MsbfsProblem hipMalloc failed");
+        DeviceArray<Word> *words[] = {&ds->d_seen, &ds->d_frontier, &ds->d_next};
+        for (DeviceArray<Word> *a : words) if ((retval = a->Alloc(n1))) return retval;
+        if ((retval = ds->d_queue[0].Alloc(n1))) return retval;
+        if ((retval = ds->d_queue[1].Alloc(n1))) return retval;
+        if ((retval = ds->d_sources_reaching.Alloc(n1))) return retval;
+        if ((retval = ds->d_in_dist_sum.Alloc(n1))) return retval;
         return retval;
     }
 
@@ -147,8 +111,7 @@ struct MsbfsProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     {
         hipError_t retval = hipSuccess;
         if ((retval = Base::Init(stream_from_host, graph, num_gpus, false))) return retval;
-        data_slices = new DataSlice *[1];
-        data_slices[0] = new DataSlice();
+        data_slices.Make();
         return Build(nullptr, nullptr);
     }
 
@@ -158,8 +121,7 @@ struct MsbfsProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     {
         hipError_t retval = hipSuccess;
         if ((retval = Base::InitFromDevice(nodes, edges, d_row_offsets, d_column_indices))) return retval;
-        data_slices = new DataSlice *[1];
-        data_slices[0] = new DataSlice();
+        data_slices.Make();
         return Build(d_inv_row_offsets, d_inv_col_indices);
     }
 
@@ -220,8 +182,8 @@ struct MsbfsProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
                 GR_CHECK(hipEventCreate(&ev[0]), "MsbfsProblem hipEventCreate failed");
                 GR_CHECK(hipEventCreate(&ev[1]), "MsbfsProblem hipEventCreate failed");
                 GR_CHECK(hipEventRecord(ev[0], stream), "MsbfsProblem hipEventRecord failed");
-                GR_CHECK(hipMalloc(&ds->d_built_iro, sizeof(int) * (static_cast<size_t>(n) + 1)), "MsbfsProblem hipMalloc d_iro failed");
-                GR_CHECK(hipMalloc(&ds->d_built_ici, sizeof(int) * static_cast<size_t>(m > 0 ? m : 1)), "MsbfsProblem hipMalloc d_ici failed");
+                if ((retval = ds->d_built_iro.Alloc(static_cast<size_t>(n) + 1))) return retval;
+                if ((retval = ds->d_built_ici.Alloc(static_cast<size_t>(m > 0 ? m : 1)))) return retval;
                 GR_CHECK(graphio::DeviceTransposeCsr(static_cast<int>(n), m, gs->d_row_offsets, gs->d_column_indices, ds->d_built_iro, ds->d_built_ici, stream),
                          "MsbfsProblem transpose failed");
                 GR_CHECK(hipEventRecord(ev[1], stream), "MsbfsProblem hipEventRecord failed");
@@ -255,25 +217,17 @@ struct MsbfsProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         store_depths = with_depths;
         fresh = false;
         if (rounded > ds->source_capacity) {
-            void *old[] = {ds->d_sources, ds->d_reached, ds->d_dist_sum, ds->d_ecc};
-            for (void *b : old)
-                if (b) GR_CHECK(hipFree(b), "MsbfsProblem hipFree failed");
-            ds->d_sources = nullptr;
-            ds->d_reached = ds->d_dist_sum = nullptr;
-            ds->d_ecc = nullptr;
             ds->source_capacity = 0;
-            GR_CHECK(hipMalloc(&ds->d_sources, sizeof(int) * rounded), "MsbfsProblem hipMalloc failed");
-            GR_CHECK(hipMalloc(&ds->d_reached, sizeof(unsigned long long) * rounded), "MsbfsProblem hipMalloc failed");
-            GR_CHECK(hipMalloc(&ds->d_dist_sum, sizeof(unsigned long long) * rounded), "MsbfsProblem hipMalloc failed");
-            GR_CHECK(hipMalloc(&ds->d_ecc, sizeof(int) * rounded), "MsbfsProblem hipMalloc failed");
+            if ((retval = ds->d_sources.Alloc(rounded))) return retval;
+            if ((retval = ds->d_reached.Alloc(rounded))) return retval;
+            if ((retval = ds->d_dist_sum.Alloc(rounded))) return retval;
+            if ((retval = ds->d_ecc.Alloc(rounded))) return retval;
             ds->source_capacity = rounded;
         }
         const size_t cells = static_cast<size_t>(count) * n;
         if (with_depths && cells > ds->depth_capacity) {
-            if (ds->d_depth) GR_CHECK(hipFree(ds->d_depth), "MsbfsProblem hipFree failed");
-            ds->d_depth = nullptr;
             ds->depth_capacity = 0;
-            GR_CHECK(hipMalloc(&ds->d_depth, sizeof(int) * cells), "MsbfsProblem hipMalloc d_depth failed");
+            if ((retval = ds->d_depth.Alloc(cells))) return retval;
             ds->depth_capacity = cells;
         }
         GR_CHECK(hipMemcpyAsync(ds->d_sources, sources.data(), sizeof(int) * static_cast<size_t>(count), hipMemcpyHostToDevice, stream),
@@ -284,8 +238,8 @@ struct MsbfsProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         GR_CHECK(hipMemsetAsync(ds->d_sources_reaching, 0, sizeof(int) * n, stream), "MsbfsProblem memset failed");
         GR_CHECK(hipMemsetAsync(ds->d_in_dist_sum, 0, sizeof(unsigned long long) * n, stream), "MsbfsProblem memset failed");
         if (with_depths) GR_CHECK(hipMemsetAsync(ds->d_depth, 0xFF, sizeof(int) * cells, stream), "MsbfsProblem memset failed");
-        hipLaunchKernelGGL(ResetKernel, dim3(Grid(count)), dim3(kThreads), 0, stream, ds->d_sources, count, static_cast<int>(this->nodes), ds->d_reached,
-                           ds->d_dist_sum, ds->d_ecc, ds->d_sources_reaching, with_depths ? ds->d_depth : nullptr);
+        hipLaunchKernelGGL(ResetKernel, dim3(graphio::PairGrid(count)), dim3(kThreads), 0, stream, ds->d_sources, count, static_cast<int>(this->nodes), ds->d_reached,
+                           ds->d_dist_sum, ds->d_ecc, ds->d_sources_reaching, with_depths ? ds->d_depth.p : nullptr);
         GR_CHECK(hipGetLastError(), "ResetKernel launch failed");
         GR_CHECK(hipStreamSynchronize(stream), "MsbfsProblem Reset sync failed");
         fresh = true;
@@ -295,22 +249,11 @@ struct MsbfsProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     // the last Reset's again (an Enact that does not follow one)
     hipError_t ResetAgain(bool *refused) { return Reset(sources.data(), static_cast<long long>(sources.size()), store_depths, refused); }
 
-    template <typename T>
-    hipError_t Read(T *h_out, const void *d_in, size_t count)
-    {
-        hipError_t retval = hipSuccess;
-        hipStream_t stream = this->graph_slices[0]->stream;
-        if (!h_out || count == 0) return retval;
-        GR_CHECK(hipMemcpyAsync(h_out, d_in, sizeof(T) * count, hipMemcpyDeviceToHost, stream), "MsbfsProblem read failed");
-        GR_CHECK(hipStreamSynchronize(stream), "MsbfsProblem read sync failed");
-        return retval;
-    }
-
     // rows [first, first + count) of depth[source][vertex]; the caller has checked the range and that the depths are stored
     hipError_t ExtractDepths(long long first, long long count, int *h_depth)
     {
         const size_t n = static_cast<size_t>(this->nodes);
-        return Read(h_depth, data_slices[0]->d_depth + static_cast<size_t>(first) * n, static_cast<size_t>(count) * n);
+        return this->template Read<int>(h_depth, data_slices[0]->d_depth + static_cast<size_t>(first) * n, static_cast<size_t>(count) * n);
     }
 
     hipError_t SourceSummary(long long *h_reached, long long *h_dist_sum, int *h_ecc)
@@ -318,9 +261,9 @@ struct MsbfsProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         hipError_t retval = hipSuccess;
         DataSlice *ds = data_slices[0];
         const size_t k = sources.size();
-        if ((retval = Read(h_reached, ds->d_reached, k))) return retval;
-        if ((retval = Read(h_dist_sum, ds->d_dist_sum, k))) return retval;
-        return Read(h_ecc, ds->d_ecc, k);
+        if ((retval = this->Read(reinterpret_cast<unsigned long long *>(h_reached), ds->d_reached.p, k))) return retval;
+        if ((retval = this->Read(reinterpret_cast<unsigned long long *>(h_dist_sum), ds->d_dist_sum.p, k))) return retval;
+        return this->Read(h_ecc, ds->d_ecc.p, k);
     }
 
     hipError_t VertexSummary(int *h_sources_reaching, long long *h_in_dist_sum)
@@ -328,8 +271,8 @@ struct MsbfsProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         hipError_t retval = hipSuccess;
         DataSlice *ds = data_slices[0];
         const size_t n = static_cast<size_t>(this->nodes);
-        if ((retval = Read(h_sources_reaching, ds->d_sources_reaching, n))) return retval;
-        return Read(h_in_dist_sum, ds->d_in_dist_sum, n);
+        if ((retval = this->Read(h_sources_reaching, ds->d_sources_reaching.p, n))) return retval;
+        return this->Read(reinterpret_cast<unsigned long long *>(h_in_dist_sum), ds->d_in_dist_sum.p, n);
     }
 };
 

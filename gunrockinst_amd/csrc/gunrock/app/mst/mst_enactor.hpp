@@ -70,7 +70,7 @@ class MSTEnactor : public EnactorBase {
             GR_CHECK(hipEventCreate(&ev_round[1]), "MSTEnactor hipEventCreate failed");
         }
         auto grid = [&](long long work) {
-            const int g = Problem::Grid(work);
+            const int g = graphio::PairGrid(work);
             return max_grid_size > 0 && max_grid_size < g ? max_grid_size : g;
         };
         auto launched = [&](const char *what) -> hipError_t {
@@ -122,7 +122,7 @@ class MSTEnactor : public EnactorBase {
         // ---- round 1 by rows (mirrored input with equal mirror weights) ----
         if (problem->mirrored) {
             if ((retval = begin())) return retval;
-            util::Memset(ds->d_best, kNoEdge, n, stream);
+            util::Memset(ds->d_best.p, kNoEdge, n, stream);
             if ((retval = launched("MemsetKernel launch failed"))) return retval;
             hipLaunchKernelGGL(RowMinKernel, dim3(grid(m)), dim3(256), 0, stream, ds->d_froms, gs->d_column_indices, gs->d_edge_values, m,
                                ds->d_best);
@@ -150,7 +150,7 @@ class MSTEnactor : public EnactorBase {
         // ---- Borůvka rounds over the shrinking list ----
         while (len > 0) {
             if ((retval = begin())) return retval;
-            util::Memset(ds->d_best, kNoEdge, n, stream);
+            util::Memset(ds->d_best.p, kNoEdge, n, stream);
             if ((retval = launched("MemsetKernel launch failed"))) return retval;
             hipLaunchKernelGGL(ListMinKernel, dim3(grid(len)), dim3(256), 0, stream, ds->d_cu[b], ds->d_cv[b], ds->d_key[b], len, ds->d_best);
             if ((retval = launched("ListMinKernel launch failed"))) return retval;

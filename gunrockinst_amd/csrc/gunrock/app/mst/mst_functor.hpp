@@ -44,24 +44,6 @@ __device__ __forceinline__ int RowFind(const int *d_row_offsets, const int *d_co
     return lo < end && d_cols[lo] == wanted ? lo : -1;
 }
 
-// d_bad = 1 unless row_offsets[0] = 0, row_offsets[nodes] = edges, the offsets never decrease and every column is a vertex.
-// (Runs at Init: a malformed CSR must not reach the kernels below, which index with what they read.)
-static __global__ void ValidateCsrKernel(const int *d_row_offsets, const int *d_cols, long long nodes, long long edges, int *d_bad)
-{
-    const long long stride = static_cast<long long>(gridDim.x) * blockDim.x;
-    const long long count = nodes > edges ? nodes : edges;
-    bool bad = false;
-    for (long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; i <= count; i += stride) {
-        if (i < nodes) bad |= d_row_offsets[i] > d_row_offsets[i + 1];
-        if (i == 0) bad |= d_row_offsets[0] != 0 || d_row_offsets[nodes] != edges;
-        if (i < edges) {
-            const int t = d_cols[i];
-            bad |= t < 0 || t >= nodes;
-        }
-    }
-    if (__ballot(bad) && util::LaneId() == 0) *d_bad = 1;
-}
-
 // d_bad = 1 when an entry (f, t), f < t, has a mirror of a different weight (exact symmetry already holds: the mirror exists)
 static __global__ void MirrorWeightKernel(const int *d_row_offsets, const int *d_cols, const int *d_weights, const int *d_froms,
                                           long long edges, int *d_bad)

@@ -35,52 +35,32 @@ struct MSTProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     typedef int Value;
 
     struct DataSlice {
-        int *d_selected = nullptr;               // per CSR entry: 1 = in the forest (reference d_mst_output)
-        int *d_parent[2] = {nullptr, nullptr};   // component of every vertex; the hook writes the other buffer
+        DeviceArray<int> d_selected;  // per CSR entry: 1 = in the forest (reference d_mst_output)
+        DeviceArray<int> d_parent[2];  // component of every vertex; the hook writes the other buffer
         int cur = 0;                             // which d_parent is current
-        unsigned long long *d_best = nullptr;    // per component: smallest key of an entry leaving it
-        int *d_froms = nullptr;                  // per CSR entry: its row
-        int *d_cu[2] = {nullptr, nullptr};       // the list of inter-component entries, double-buffered
-        int *d_cv[2] = {nullptr, nullptr};
-        unsigned long long *d_key[2] = {nullptr, nullptr};
-        unsigned *d_flags = nullptr;             // filter: keep flags (list length + 1) ...
-        unsigned *d_pos = nullptr;               // ... and their exclusive scan
-        unsigned long long *d_scan_sums = nullptr;
-        unsigned long long *d_totals = nullptr;  // [0] forest weight (two's complement), [1] forest edges
-        int *d_flag = nullptr;                   // convergence / validation word
+        DeviceArray<unsigned long long> d_best;  // per component: smallest key of an entry leaving it
+        DeviceArray<int> d_froms;  // per CSR entry: its row
+        DeviceArray<int> d_cu[2];  // the list of inter-component entries, double-buffered
+        DeviceArray<int> d_cv[2];
+        DeviceArray<unsigned long long> d_key[2];
+        DeviceArray<unsigned> d_flags;  // filter: keep flags (list length + 1) ...
+        DeviceArray<unsigned> d_pos;  // ... and their exclusive scan
+        DeviceArray<unsigned long long> d_scan_sums;
+        DeviceArray<unsigned long long> d_totals;  // [0] forest weight (two's complement), [1] forest edges
+        DeviceArray<int> d_flag;  // convergence / mirror-weight word
     };
 
-    DataSlice **data_slices = nullptr;
+    SliceHolder<DataSlice> data_slices;
     int mirrored = 0;       // exact symmetry with equal mirror weights: round 1 by rows, only the f < t copies are listed
-    int malformed = 0;      // Init found offsets or columns that are not a CSR of `nodes` vertices
     long long list_capacity = 0;
     long long forest_edges = 0;
     long long total_weight = 0;
     int *h_word = nullptr;  // pinned read-back words
 
+    // (the slice frees its own arrays; the pinned words are the problem's)
     ~MSTProblem() override
     {
-        if (data_slices) {
-            DataSlice *ds = data_slices[0];
-            if (ds) {
-                void *bufs[] = {ds->d_selected, ds->d_parent[0], ds->d_parent[1], ds->d_best, ds->d_froms, ds->d_cu[0], ds->d_cu[1],
-                                ds->d_cv[0], ds->d_cv[1], ds->d_key[0], ds->d_key[1], ds->d_flags, ds->d_pos, ds->d_scan_sums,
-                                ds->d_totals, ds->d_flag};
-                for (void *b : bufs)
-                    if (b) util::GRError(hipFree(b), "MSTProblem hipFree failed", __FILE__, __LINE__);
-                delete ds;
-            }
-            delete[] data_slices;
-        }
         if (h_word) util::GRError(hipHostFree(h_word), "MSTProblem hipHostFree failed", __FILE__, __LINE__);
-    }
-
-    static int Grid(long long work)
-    {
-        long long blocks = (work + 255) / 256;
-        if (blocks < 1) blocks = 1;
-        if (blocks > 2048) blocks = 2048;  // 256 CUs x 8 workgroups, grid-stride the rest
-        return static_cast<int>(blocks);
     }
 
     // one device word read back (pinned)
@@ -96,34 +76,24 @@ struct MSTProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     hipError_t AllocData()
     {
         hipError_t retval = hipSuccess;
-        data_slices = new DataSlice *[1];
-        data_slices[0] = new DataSlice();
+        data_slices.Make();
         DataSlice *ds = data_slices[0];
         GraphSlice<int, int, int> *gs = this->graph_slices[0];
         hipStream_t stream = gs->stream;
         const long long n = this->nodes, m = this->edges;
         const size_t n1 = static_cast<size_t>(n > 0 ? n : 1), m1 = static_cast<size_t>(m > 0 ? m : 1);
         GR_CHECK(hipHostMalloc(&h_word, sizeof(int) * 2, hipHostMallocDefault), "MSTProblem hipHostMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_flag, sizeof(int)), "MSTProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_totals, sizeof(unsigned long long) * 2), "MSTProblem hipMalloc failed");
+        if ((retval = ds->d_flag.Alloc(1))) return retval;
+        if ((retval = ds->d_totals.Alloc(2))) return retval;
 
         // 1. the CSR must be one: nothing below indexes with an unchecked value
-        GR_CHECK(hipMemsetAsync(ds->d_flag, 0, sizeof(int), stream), "MSTProblem memset failed");
-        hipLaunchKernelGGL(ValidateCsrKernel, dim3(Grid((n > m ? n : m) + 1)), dim3(256), 0, stream, gs->d_row_offsets, gs->d_column_indices, n,
-                           m, ds->d_flag);
-        GR_CHECK(hipGetLastError(), "ValidateCsrKernel launch failed");
-        int bad = 0;
-        if ((retval = ReadWord(ds->d_flag, bad, stream))) return retval;
-        if (bad) {
-            malformed = 1;
-            return hipErrorInvalidValue;
-        }
+        if ((retval = this->ValidateCsr())) return retval;
 
-        GR_CHECK(hipMalloc(&ds->d_selected, sizeof(int) * m1), "MSTProblem hipMalloc d_selected failed");
-        GR_CHECK(hipMalloc(&ds->d_parent[0], sizeof(int) * n1), "MSTProblem hipMalloc d_parent failed");
-        GR_CHECK(hipMalloc(&ds->d_parent[1], sizeof(int) * n1), "MSTProblem hipMalloc d_parent failed");
-        GR_CHECK(hipMalloc(&ds->d_best, sizeof(unsigned long long) * n1), "MSTProblem hipMalloc d_best failed");
-        GR_CHECK(hipMalloc(&ds->d_froms, sizeof(int) * m1), "MSTProblem hipMalloc d_froms failed");
+        if ((retval = ds->d_selected.Alloc(m1))) return retval;
+        if ((retval = ds->d_parent[0].Alloc(n1))) return retval;
+        if ((retval = ds->d_parent[1].Alloc(n1))) return retval;
+        if ((retval = ds->d_best.Alloc(n1))) return retval;
+        if ((retval = ds->d_froms.Alloc(m1))) return retval;
         if (n > 0) {
             hipLaunchKernelGGL((cc::ExpandRowsKernel<int, int>), dim3(2048), dim3(256), 0, stream, gs->d_row_offsets, static_cast<int>(n),
                                ds->d_froms);
@@ -139,9 +109,10 @@ struct MSTProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
                      "MSTProblem symmetry test failed");
             if (symmetric) {
                 GR_CHECK(hipMemsetAsync(ds->d_flag, 0, sizeof(int), stream), "MSTProblem memset failed");
-                hipLaunchKernelGGL(MirrorWeightKernel, dim3(Grid(m)), dim3(256), 0, stream, gs->d_row_offsets, gs->d_column_indices,
+                hipLaunchKernelGGL(MirrorWeightKernel, dim3(graphio::PairGrid(m)), dim3(256), 0, stream, gs->d_row_offsets, gs->d_column_indices,
                                    gs->d_edge_values, ds->d_froms, m, ds->d_flag);
                 GR_CHECK(hipGetLastError(), "MirrorWeightKernel launch failed");
+                int bad = 0;
                 if ((retval = ReadWord(ds->d_flag, bad, stream))) return retval;
                 mirrored = bad ? 0 : 1;
             }
@@ -151,14 +122,13 @@ struct MSTProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         list_capacity = mirrored ? m / 2 + 1 : m;  // (every f < t entry of a mirrored input has its f > t twin)
         const size_t lc = static_cast<size_t>(list_capacity > 0 ? list_capacity : 1);
         for (int b = 0; b < 2; ++b) {
-            GR_CHECK(hipMalloc(&ds->d_cu[b], sizeof(int) * lc), "MSTProblem hipMalloc list failed");
-            GR_CHECK(hipMalloc(&ds->d_cv[b], sizeof(int) * lc), "MSTProblem hipMalloc list failed");
-            GR_CHECK(hipMalloc(&ds->d_key[b], sizeof(unsigned long long) * lc), "MSTProblem hipMalloc list failed");
+            if ((retval = ds->d_cu[b].Alloc(lc))) return retval;
+            if ((retval = ds->d_cv[b].Alloc(lc))) return retval;
+            if ((retval = ds->d_key[b].Alloc(lc))) return retval;
         }
-        GR_CHECK(hipMalloc(&ds->d_flags, sizeof(unsigned) * (m1 + 1)), "MSTProblem hipMalloc d_flags failed");
-        GR_CHECK(hipMalloc(&ds->d_pos, sizeof(unsigned) * (m1 + 1)), "MSTProblem hipMalloc d_pos failed");
-        GR_CHECK(hipMalloc(&ds->d_scan_sums, sizeof(unsigned long long) * static_cast<size_t>(graphio::ScanScratchWords(static_cast<long long>(m1) + 1))),
-                 "MSTProblem hipMalloc scan scratch failed");
+        if ((retval = ds->d_flags.Alloc(m1 + 1))) return retval;
+        if ((retval = ds->d_pos.Alloc(m1 + 1))) return retval;
+        if ((retval = ds->d_scan_sums.Alloc(static_cast<size_t>(graphio::ScanScratchWords(static_cast<long long>(m1) + 1))))) return retval;
         GR_CHECK(hipStreamSynchronize(stream), "MSTProblem AllocData failed");
         return retval;
     }
@@ -183,8 +153,8 @@ struct MSTProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         DataSlice *ds = data_slices[0];
         hipStream_t stream = this->graph_slices[0]->stream;
         ds->cur = 0;
-        util::MemsetIdx(ds->d_parent[0], this->nodes, stream);
-        util::Memset(ds->d_selected, 0, this->edges, stream);
+        util::MemsetIdx(ds->d_parent[0].p, this->nodes, stream);
+        util::Memset(ds->d_selected.p, 0, this->edges, stream);
         GR_CHECK(hipMemsetAsync(ds->d_totals, 0, sizeof(unsigned long long) * 2, stream), "MSTProblem memset failed");
         GR_CHECK(hipStreamSynchronize(stream), "MSTProblem Reset sync failed");
         forest_edges = total_weight = 0;

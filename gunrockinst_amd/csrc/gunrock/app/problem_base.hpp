@@ -15,11 +15,15 @@
 #include <hip/hip_runtime.h>
 
 #include <gunrock/csr.hpp>
+#include <gunrock/graphio/pair_graph.hpp>
+#include <gunrock/util/device_array.hpp>
 #include <gunrock/util/error_utils.hpp>
 #include <gunrock/util/frontier.hpp>
 
 namespace gunrock {
 namespace app {
+
+using util::DeviceArray;
 
 enum FrontierType {
     VERTEX_FRONTIERS,  // O(n) ping-pong frontier queues
@@ -72,6 +76,25 @@ struct GraphSlice {
     }
 };
 
+// The owner of a problem's DataSlice, spelled as the reference's array of one per GPU: data_slices[0] is the slice, null until Make().
+// The slice's DeviceArray members free themselves when it goes, however far its build came.
+template <typename DataSlice>
+struct SliceHolder {
+    DataSlice *slice = nullptr;
+    SliceHolder() = default;
+    SliceHolder(const SliceHolder &) = delete;
+    SliceHolder &operator=(const SliceHolder &) = delete;
+    ~SliceHolder() { delete slice; }
+    DataSlice *operator[](int) const { return slice; }
+    explicit operator bool() const { return slice != nullptr; }
+    DataSlice *Make()
+    {
+        delete slice;
+        slice = new DataSlice();
+        return slice;
+    }
+};
+
 template <typename _VertexId, typename _SizeT, typename _Value, bool _USE_DOUBLE_BUFFER = false>
 struct ProblemBase {
     typedef _VertexId VertexId;
@@ -83,6 +106,7 @@ struct ProblemBase {
     SizeT nodes = 0;
     SizeT edges = 0;
     GraphSlice<VertexId, SizeT, Value> **graph_slices = nullptr;
+    int malformed = 0;  // ValidateCsr found offsets or columns that are not a CSR of `nodes` vertices
 
     virtual ~ProblemBase()
     {
@@ -155,6 +179,39 @@ struct ProblemBase {
         return retval;
     }
 
+    // The CSR must be one before a build indexes with what it reads: hipErrorInvalidValue, and `malformed` set, when it is not.
+    // Without arguments the problem's own graph; with them another CSR of as many vertices and entries (a caller's transpose).
+    hipError_t ValidateCsr(const SizeT *d_row_offsets, const VertexId *d_column_indices)
+    {
+        hipError_t retval = hipSuccess;
+        DeviceArray<int> flag;
+        bool bad = false;
+        if ((retval = flag.Alloc(1))) return retval;
+        if ((retval = graphio::DeviceValidateCsr(d_row_offsets, d_column_indices, nodes, edges, flag.p, graph_slices[0]->stream, &bad))) return retval;
+        return bad ? Malformed() : retval;
+    }
+    hipError_t ValidateCsr() { return ValidateCsr(graph_slices[0]->d_row_offsets, graph_slices[0]->d_column_indices); }
+
+    // what an Init returns when the input is not what the primitive takes
+    hipError_t Malformed()
+    {
+        malformed = 1;
+        return hipErrorInvalidValue;
+    }
+
+    // count elements of d_in to the host, and the stream drained; h_out may be NULL and count 0: then nothing happens
+    template <typename T>
+    hipError_t Read(T *h_out, const T *d_in, size_t count)
+    {
+        hipError_t retval = hipSuccess;
+        hipStream_t stream = graph_slices[0]->stream;
+        if (h_out && count) {
+            GR_CHECK(hipMemcpyAsync(h_out, d_in, sizeof(T) * count, hipMemcpyDeviceToHost, stream), "ProblemBase read failed");
+            GR_CHECK(hipStreamSynchronize(stream), "ProblemBase read sync failed");
+        }
+        return retval;
+    }
+
     // (Re)size the ping-pong queues; memory is reused when large enough (problem_base.cuh:352-431).
     hipError_t Reset(FrontierType frontier_type, double queue_sizing)
     {
@@ -190,20 +247,16 @@ struct ProblemBase {
     }
 };
 
-// One device array of a problem's slice that grows with the largest need so far and keeps nothing when it does.  The problem's
-// destructor calls Free().
+// One device array of a problem's slice that grows with the largest need so far and keeps nothing when it does.
 template <typename T>
-struct Grown {
-    T *p = nullptr;
+struct Grown : util::DeviceArray<T> {
     size_t room = 0;
     hipError_t Need(size_t count)
     {
         hipError_t retval = hipSuccess;
         if (count <= room) return retval;
-        if (p) GR_CHECK(hipFree(p), "grown array hipFree failed");
-        p = nullptr;
         room = 0;
-        GR_CHECK(hipMalloc(&p, sizeof(T) * count), "grown array hipMalloc failed");
+        if ((retval = this->Alloc(count))) return retval;
         room = count;
         return retval;
     }
@@ -213,13 +266,12 @@ struct Grown {
         hipError_t retval = hipSuccess;
         if (count <= room) return retval;
         if ((retval = Need(count))) return retval;
-        GR_CHECK(hipMemsetAsync(p, 0, sizeof(T) * count, stream), "grown array memset failed");
+        GR_CHECK(hipMemsetAsync(this->p, 0, sizeof(T) * count, stream), "grown array memset failed");
         return retval;
     }
     void Free()
     {
-        if (p) util::GRError(hipFree(p), "grown array hipFree failed", __FILE__, __LINE__);
-        p = nullptr;
+        util::DeviceArray<T>::Free();
         room = 0;
     }
 };

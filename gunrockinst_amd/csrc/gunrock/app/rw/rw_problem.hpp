@@ -45,38 +45,23 @@ struct RwProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     typedef ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> Base;
 
     struct DataSlice {
-        int *d_ro = nullptr;  // the sorted copy
-        int *d_ci = nullptr;
-        int *d_w = nullptr;
-        long long *d_prefix = nullptr;
-        int *d_starts = nullptr;
-        int *d_lengths = nullptr;
-        int *d_walks = nullptr;  // num_walks x pitch, (re)allocated by Enact
+        DeviceArray<int> d_ro;  // the sorted copy
+        DeviceArray<int> d_ci;
+        DeviceArray<int> d_w;
+        DeviceArray<long long> d_prefix;
+        DeviceArray<int> d_starts;
+        DeviceArray<int> d_lengths;
+        DeviceArray<int> d_walks;  // num_walks x pitch, (re)allocated by Enact
         size_t walk_ints = 0;
-        unsigned long long *d_visits = nullptr;  // allocated by the first Enact that counts them
-        unsigned long long *d_words = nullptr;
+        DeviceArray<unsigned long long> d_visits;  // allocated by the first Enact that counts them
+        DeviceArray<unsigned long long> d_words;
     };
 
-    DataSlice **data_slices = nullptr;
-    int malformed = 0;
+    SliceHolder<DataSlice> data_slices;
     bool weights = false;      // Init had weights
     long long num_walks = 0;   // of the last Reset
     long long pitch = 0;       // of the last Enact
     double build_ms = 0;
-
-    ~RwProblem() override
-    {
-        if (data_slices) {
-            DataSlice *ds = data_slices[0];
-            if (ds) {
-                void *bufs[] = {ds->d_ro, ds->d_ci, ds->d_w, ds->d_prefix, ds->d_starts, ds->d_lengths, ds->d_walks, ds->d_visits, ds->d_words};
-                for (void *b : bufs)
-                    if (b) util::GRError(hipFree(b), "RwProblem hipFree failed", __FILE__, __LINE__);
-                delete ds;
-            }
-            delete[] data_slices;
-        }
-    }
 
     hipError_t Build()
     {
@@ -88,35 +73,31 @@ struct RwProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         const size_t n1 = static_cast<size_t>(n > 0 ? n : 1), m1 = static_cast<size_t>(m > 0 ? m : 1);
         weights = gs->d_edge_values != nullptr;
 
-        bool bad = false;
-        graphio::DeviceScratch<int> flag;
-        if ((retval = flag.Alloc(1))) return retval;
-        if ((retval = graphio::DeviceValidateCsr(gs->d_row_offsets, gs->d_column_indices, n, m, flag.p, stream, &bad))) return retval;
-        if (!bad && weights && m > 0) {
+        if ((retval = this->ValidateCsr())) return retval;
+        if (weights && m > 0) {
             int negative = 0;
+            graphio::DeviceScratch<int> flag;
+            if ((retval = flag.Alloc(1))) return retval;
+            GR_CHECK(hipMemsetAsync(flag.p, 0, sizeof(int), stream), "RwProblem memset failed");
             hipLaunchKernelGGL(NegativeWeightKernel, dim3(graphio::PairGrid(m)), dim3(256), 0, stream, gs->d_edge_values, m, flag.p);
             GR_CHECK(hipGetLastError(), "NegativeWeightKernel launch failed");
             GR_CHECK(hipMemcpyAsync(&negative, flag.p, sizeof(int), hipMemcpyDeviceToHost, stream), "RwProblem read-back failed");
             GR_CHECK(hipStreamSynchronize(stream), "RwProblem read-back sync failed");
-            bad = negative != 0;
-        }
-        if (bad) {
-            malformed = 1;
-            return hipErrorInvalidValue;
+            if (negative) return this->Malformed();
         }
 
         graphio::BuildEvents ev;
         if ((retval = ev.Create(2))) return retval;
         if ((retval = ev.Record(0, stream))) return retval;
 
-        GR_CHECK(hipMalloc(&ds->d_words, sizeof(unsigned long long) * W_COUNT), "RwProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_ro, sizeof(int) * (n1 + 1)), "RwProblem hipMalloc d_ro failed");
-        GR_CHECK(hipMalloc(&ds->d_ci, sizeof(int) * m1), "RwProblem hipMalloc d_ci failed");
+        if ((retval = ds->d_words.Alloc(W_COUNT))) return retval;
+        if ((retval = ds->d_ro.Alloc(n1 + 1))) return retval;
+        if ((retval = ds->d_ci.Alloc(m1))) return retval;
         GR_CHECK(hipMemsetAsync(ds->d_words, 0, sizeof(unsigned long long) * W_COUNT, stream), "RwProblem memset failed");
         GR_CHECK(hipMemcpyAsync(ds->d_ro, gs->d_row_offsets, sizeof(int) * (n1 + 1), hipMemcpyDeviceToDevice, stream), "RwProblem copy failed");
         if (weights) {
-            GR_CHECK(hipMalloc(&ds->d_w, sizeof(int) * m1), "RwProblem hipMalloc d_w failed");
-            GR_CHECK(hipMalloc(&ds->d_prefix, sizeof(long long) * m1), "RwProblem hipMalloc d_prefix failed");
+            if ((retval = ds->d_w.Alloc(m1))) return retval;
+            if ((retval = ds->d_prefix.Alloc(m1))) return retval;
         }
         graphio::DeviceKeySort sort_a, sort_b, sort_c;  // (their buffers go behind the sync below)
         if (m > 0) {
@@ -156,18 +137,12 @@ struct RwProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         return retval;
     }
 
-    void NewSlice()
-    {
-        data_slices = new DataSlice *[1];
-        data_slices[0] = new DataSlice();
-    }
-
     // One Init per object (grx_rw_init refuses a second one)
     hipError_t Init(bool stream_from_host, const Csr<int, int, int> &graph, int num_gpus = 1)
     {
         hipError_t retval = hipSuccess;
         if ((retval = Base::Init(stream_from_host, graph, num_gpus, true))) return retval;
-        NewSlice();
+        data_slices.Make();
         return Build();
     }
 
@@ -175,7 +150,7 @@ struct RwProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     {
         hipError_t retval = hipSuccess;
         if ((retval = Base::InitFromDevice(nodes, edges, d_row_offsets, d_column_indices, d_weights))) return retval;
-        NewSlice();
+        data_slices.Make();
         return Build();
     }
 
@@ -186,12 +161,9 @@ struct RwProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         DataSlice *ds = data_slices[0];
         hipStream_t stream = this->graph_slices[0]->stream;
         if (walks != num_walks) {
-            if (ds->d_starts) GR_CHECK(hipFree(ds->d_starts), "RwProblem hipFree failed");
-            if (ds->d_lengths) GR_CHECK(hipFree(ds->d_lengths), "RwProblem hipFree failed");
-            ds->d_starts = ds->d_lengths = nullptr;
             num_walks = 0;
-            GR_CHECK(hipMalloc(&ds->d_starts, sizeof(int) * static_cast<size_t>(walks)), "RwProblem hipMalloc d_starts failed");
-            GR_CHECK(hipMalloc(&ds->d_lengths, sizeof(int) * static_cast<size_t>(walks)), "RwProblem hipMalloc d_lengths failed");
+            if ((retval = ds->d_starts.Alloc(static_cast<size_t>(walks)))) return retval;
+            if ((retval = ds->d_lengths.Alloc(static_cast<size_t>(walks)))) return retval;
             num_walks = walks;
         }
         GR_CHECK(hipMemcpyAsync(ds->d_starts, h_starts, sizeof(int) * static_cast<size_t>(walks), hipMemcpyHostToDevice, stream),
@@ -207,10 +179,8 @@ struct RwProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         DataSlice *ds = data_slices[0];
         const size_t need = static_cast<size_t>(num_walks) * static_cast<size_t>(row_pitch);
         if (need > ds->walk_ints) {
-            if (ds->d_walks) GR_CHECK(hipFree(ds->d_walks), "RwProblem hipFree failed");
-            ds->d_walks = nullptr;
             ds->walk_ints = 0;
-            GR_CHECK(hipMalloc(&ds->d_walks, sizeof(int) * need), "RwProblem hipMalloc d_walks failed");
+            if ((retval = ds->d_walks.Alloc(need))) return retval;
             ds->walk_ints = need;
         }
         pitch = row_pitch;
@@ -221,7 +191,7 @@ struct RwProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     {
         hipError_t retval = hipSuccess;
         DataSlice *ds = data_slices[0];
-        if (!ds->d_visits) GR_CHECK(hipMalloc(&ds->d_visits, sizeof(unsigned long long) * static_cast<size_t>(this->nodes)), "RwProblem hipMalloc d_visits failed");
+        if (!ds->d_visits && (retval = ds->d_visits.Alloc(static_cast<size_t>(this->nodes)))) return retval;
         return retval;
     }
 

@@ -13,6 +13,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <utility>
 #include <vector>
 
 #include <gunrock/app/problem_base.hpp>
@@ -69,55 +70,38 @@ struct SampleProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     typedef ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> Base;
 
     struct DataSlice {
-        int *d_ro = nullptr;  // the sorted copy
-        int *d_ci = nullptr;
-        int *d_ent = nullptr;
-        int *d_w = nullptr;
-        long long *d_prefix = nullptr;
-        int *d_local = nullptr;
-        unsigned *d_bitmap = nullptr;  // words32 words
-        unsigned *d_bit_counts = nullptr;
-        unsigned long long *d_bit_base = nullptr;
-        unsigned long long *d_bit_sums = nullptr;  // the new vertices of a hop behind its tile offsets
-        unsigned long long *d_words = nullptr;
+        DeviceArray<int> d_ro;  // the sorted copy
+        DeviceArray<int> d_ci;
+        DeviceArray<int> d_ent;
+        DeviceArray<int> d_w;
+        DeviceArray<long long> d_prefix;
+        DeviceArray<int> d_local;
+        DeviceArray<unsigned> d_bitmap;  // words32 words
+        DeviceArray<unsigned> d_bit_counts;
+        DeviceArray<unsigned long long> d_bit_base;
+        DeviceArray<unsigned long long> d_bit_sums;  // the new vertices of a hop behind its tile offsets
+        DeviceArray<unsigned long long> d_words;
         // per frontier row (NeedFrontier)
-        unsigned *d_counts = nullptr;
-        unsigned long long *d_row_base = nullptr;
-        unsigned long long *d_count_sums = nullptr;  // the edges of a hop behind its tile offsets
-        int *d_long_rows = nullptr;
+        DeviceArray<unsigned> d_counts;
+        DeviceArray<unsigned long long> d_row_base;
+        DeviceArray<unsigned long long> d_count_sums;  // the edges of a hop behind its tile offsets
+        DeviceArray<int> d_long_rows;
         size_t frontier_cap = 0;
         // the sample (NeedVertices / NeedEdges)
-        int *d_vertices = nullptr;
-        long long *d_offsets = nullptr;
-        int *d_cols = nullptr;
-        int *d_eids = nullptr;
+        DeviceArray<int> d_vertices;
+        DeviceArray<long long> d_offsets;
+        DeviceArray<int> d_cols;
+        DeviceArray<int> d_eids;
         size_t vertex_cap = 0, offset_cap = 0, col_cap = 0, eid_cap = 0;
     };
 
-    DataSlice **data_slices = nullptr;
-    int malformed = 0;
+    SliceHolder<DataSlice> data_slices;
     bool weights = false;  // Init had weights
     long long words32 = 0;
     long long num_seeds = 0;  // of the last Reset
     // of the last Enact (the seeds alone behind a Reset)
     long long num_vertices = 0, num_edges = 0;
     double build_ms = 0;
-
-    ~SampleProblem() override
-    {
-        if (data_slices) {
-            DataSlice *ds = data_slices[0];
-            if (ds) {
-                void *bufs[] = {ds->d_ro, ds->d_ci, ds->d_ent, ds->d_w, ds->d_prefix, ds->d_local, ds->d_bitmap, ds->d_bit_counts, ds->d_bit_base,
-                                ds->d_bit_sums, ds->d_words, ds->d_counts, ds->d_row_base, ds->d_count_sums, ds->d_long_rows, ds->d_vertices,
-                                ds->d_offsets, ds->d_cols, ds->d_eids};
-                for (void *b : bufs)
-                    if (b) util::GRError(hipFree(b), "SampleProblem hipFree failed", __FILE__, __LINE__);
-                delete ds;
-            }
-            delete[] data_slices;
-        }
-    }
 
     hipError_t Build()
     {
@@ -129,21 +113,17 @@ struct SampleProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         const size_t n1 = static_cast<size_t>(n > 0 ? n : 1), m1 = static_cast<size_t>(m > 0 ? m : 1);
         weights = gs->d_edge_values != nullptr;
 
-        bool bad = false;
-        graphio::DeviceScratch<int> flag;
-        if ((retval = flag.Alloc(1))) return retval;
-        if ((retval = graphio::DeviceValidateCsr(gs->d_row_offsets, gs->d_column_indices, n, m, flag.p, stream, &bad))) return retval;
-        if (!bad && weights && m > 0) {
+        if ((retval = this->ValidateCsr())) return retval;
+        if (weights && m > 0) {
             int negative = 0;
+            graphio::DeviceScratch<int> flag;
+            if ((retval = flag.Alloc(1))) return retval;
+            GR_CHECK(hipMemsetAsync(flag.p, 0, sizeof(int), stream), "SampleProblem memset failed");
             hipLaunchKernelGGL(rw::NegativeWeightKernel, dim3(graphio::PairGrid(m)), dim3(256), 0, stream, gs->d_edge_values, m, flag.p);
             GR_CHECK(hipGetLastError(), "NegativeWeightKernel launch failed");
             GR_CHECK(hipMemcpyAsync(&negative, flag.p, sizeof(int), hipMemcpyDeviceToHost, stream), "SampleProblem read-back failed");
             GR_CHECK(hipStreamSynchronize(stream), "SampleProblem read-back sync failed");
-            bad = negative != 0;
-        }
-        if (bad) {
-            malformed = 1;
-            return hipErrorInvalidValue;
+            if (negative) return this->Malformed();
         }
 
         graphio::BuildEvents ev;
@@ -152,23 +132,22 @@ struct SampleProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
 
         words32 = (n + 31) / 32;
         const size_t w1 = static_cast<size_t>(words32 > 0 ? words32 : 1);
-        GR_CHECK(hipMalloc(&ds->d_words, sizeof(unsigned long long) * W_COUNT), "SampleProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_ro, sizeof(int) * (n1 + 1)), "SampleProblem hipMalloc d_ro failed");
-        GR_CHECK(hipMalloc(&ds->d_ci, sizeof(int) * m1), "SampleProblem hipMalloc d_ci failed");
-        GR_CHECK(hipMalloc(&ds->d_ent, sizeof(int) * m1), "SampleProblem hipMalloc d_ent failed");
-        GR_CHECK(hipMalloc(&ds->d_local, sizeof(int) * n1), "SampleProblem hipMalloc d_local failed");
-        GR_CHECK(hipMalloc(&ds->d_bitmap, sizeof(unsigned) * w1), "SampleProblem hipMalloc d_bitmap failed");
-        GR_CHECK(hipMalloc(&ds->d_bit_counts, sizeof(unsigned) * w1), "SampleProblem hipMalloc d_bit_counts failed");
-        GR_CHECK(hipMalloc(&ds->d_bit_base, sizeof(unsigned long long) * w1), "SampleProblem hipMalloc d_bit_base failed");
-        GR_CHECK(hipMalloc(&ds->d_bit_sums, sizeof(unsigned long long) * static_cast<size_t>(graphio::ScanScratchWords(words32))),
-                 "SampleProblem hipMalloc d_bit_sums failed");
+        if ((retval = ds->d_words.Alloc(W_COUNT))) return retval;
+        if ((retval = ds->d_ro.Alloc(n1 + 1))) return retval;
+        if ((retval = ds->d_ci.Alloc(m1))) return retval;
+        if ((retval = ds->d_ent.Alloc(m1))) return retval;
+        if ((retval = ds->d_local.Alloc(n1))) return retval;
+        if ((retval = ds->d_bitmap.Alloc(w1))) return retval;
+        if ((retval = ds->d_bit_counts.Alloc(w1))) return retval;
+        if ((retval = ds->d_bit_base.Alloc(w1))) return retval;
+        if ((retval = ds->d_bit_sums.Alloc(static_cast<size_t>(graphio::ScanScratchWords(words32))))) return retval;
         GR_CHECK(hipMemsetAsync(ds->d_words, 0, sizeof(unsigned long long) * W_COUNT, stream), "SampleProblem memset failed");
         GR_CHECK(hipMemsetAsync(ds->d_local, 0xff, sizeof(int) * n1, stream), "SampleProblem memset failed");  // the one whole-array clear
         GR_CHECK(hipMemsetAsync(ds->d_bitmap, 0, sizeof(unsigned) * w1, stream), "SampleProblem memset failed");
         GR_CHECK(hipMemcpyAsync(ds->d_ro, gs->d_row_offsets, sizeof(int) * (n1 + 1), hipMemcpyDeviceToDevice, stream), "SampleProblem copy failed");
         if (weights) {
-            GR_CHECK(hipMalloc(&ds->d_w, sizeof(int) * m1), "SampleProblem hipMalloc d_w failed");
-            GR_CHECK(hipMalloc(&ds->d_prefix, sizeof(long long) * m1), "SampleProblem hipMalloc d_prefix failed");
+            if ((retval = ds->d_w.Alloc(m1))) return retval;
+            if ((retval = ds->d_prefix.Alloc(m1))) return retval;
         }
         graphio::DeviceKeySort sort_a, sort_b, sort_c;  // (their buffers go behind the sync below)
         if (m > 0) {
@@ -211,18 +190,12 @@ struct SampleProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         return retval;
     }
 
-    void NewSlice()
-    {
-        data_slices = new DataSlice *[1];
-        data_slices[0] = new DataSlice();
-    }
-
     // One Init per object (grx_sample_init refuses a second one)
     hipError_t Init(bool stream_from_host, const Csr<int, int, int> &graph, int num_gpus = 1)
     {
         hipError_t retval = hipSuccess;
         if ((retval = Base::Init(stream_from_host, graph, num_gpus, true))) return retval;
-        NewSlice();
+        data_slices.Make();
         return Build();
     }
 
@@ -230,32 +203,27 @@ struct SampleProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     {
         hipError_t retval = hipSuccess;
         if ((retval = Base::InitFromDevice(nodes, edges, d_row_offsets, d_column_indices, d_weights))) return retval;
-        NewSlice();
+        data_slices.Make();
         return Build();
     }
 
     // room for `need` entries behind the `keep` that stay
     template <typename T>
-    hipError_t Grow(T *&p, size_t &cap, size_t need, size_t keep)
+    hipError_t Grow(DeviceArray<T> &p, size_t &cap, size_t need, size_t keep)
     {
         hipError_t retval = hipSuccess;
         if (need <= cap) return retval;
         hipStream_t stream = this->graph_slices[0]->stream;
         size_t room = cap * 2 > need ? cap * 2 : need;
         if (room < 1024) room = 1024;
-        T *q = nullptr;
-        GR_CHECK(hipMalloc(&q, sizeof(T) * room), "SampleProblem hipMalloc failed");
+        DeviceArray<T> q;
+        if ((retval = q.Alloc(room))) return retval;
         if (p) {
             // the copy, and whatever queued kernel still reads the old array, are done before it goes
-            if (keep) retval = hipMemcpyAsync(q, p, sizeof(T) * keep, hipMemcpyDeviceToDevice, stream);
-            if (retval == hipSuccess) retval = hipStreamSynchronize(stream);
-            if (retval) {
-                hipFree(q);
-                return util::GRError(retval, "SampleProblem copy failed", __FILE__, __LINE__);
-            }
-            GR_CHECK(hipFree(p), "SampleProblem hipFree failed");
+            if (keep) GR_CHECK(hipMemcpyAsync(q.p, p.p, sizeof(T) * keep, hipMemcpyDeviceToDevice, stream), "SampleProblem copy failed");
+            GR_CHECK(hipStreamSynchronize(stream), "SampleProblem copy failed");
         }
-        p = q;
+        p = std::move(q);
         cap = room;
         return retval;
     }
@@ -288,20 +256,12 @@ struct SampleProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         if (need <= ds->frontier_cap) return retval;
         // (the sampler of the hop before may still be reading the row bases)
         GR_CHECK(hipStreamSynchronize(this->graph_slices[0]->stream), "SampleProblem NeedFrontier sync failed");
-        void *old[] = {ds->d_counts, ds->d_row_base, ds->d_count_sums, ds->d_long_rows};
-        for (void *b : old)
-            if (b) GR_CHECK(hipFree(b), "SampleProblem hipFree failed");
-        ds->d_counts = nullptr;
-        ds->d_row_base = nullptr;
-        ds->d_count_sums = nullptr;
-        ds->d_long_rows = nullptr;
         ds->frontier_cap = 0;
         const size_t room = need < 1024 ? 1024 : need + need / 2;
-        GR_CHECK(hipMalloc(&ds->d_counts, sizeof(unsigned) * room), "SampleProblem hipMalloc d_counts failed");
-        GR_CHECK(hipMalloc(&ds->d_row_base, sizeof(unsigned long long) * room), "SampleProblem hipMalloc d_row_base failed");
-        GR_CHECK(hipMalloc(&ds->d_count_sums, sizeof(unsigned long long) * static_cast<size_t>(graphio::ScanScratchWords(static_cast<long long>(room)))),
-                 "SampleProblem hipMalloc d_count_sums failed");
-        GR_CHECK(hipMalloc(&ds->d_long_rows, sizeof(int) * room), "SampleProblem hipMalloc d_long_rows failed");
+        if ((retval = ds->d_counts.Alloc(room))) return retval;
+        if ((retval = ds->d_row_base.Alloc(room))) return retval;
+        if ((retval = ds->d_count_sums.Alloc(static_cast<size_t>(graphio::ScanScratchWords(static_cast<long long>(room)))))) return retval;
+        if ((retval = ds->d_long_rows.Alloc(room))) return retval;
         ds->frontier_cap = room;
         return retval;
     }

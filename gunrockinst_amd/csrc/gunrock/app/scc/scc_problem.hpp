@@ -22,50 +22,24 @@ struct SccProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     typedef ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> Base;
 
     struct DataSlice {
-        int *d_iro = nullptr;  // the transpose (built here, or the caller's)
-        int *d_ici = nullptr;
-        bool owns_inverse = false;
-        int *d_region = nullptr, *d_outdeg = nullptr, *d_indeg = nullptr, *d_colour = nullptr, *d_mark = nullptr, *d_comp = nullptr;
-        int *d_list[2] = {nullptr, nullptr};
-        int *d_queue[2] = {nullptr, nullptr};
-        int *d_size = nullptr;  // allocated at the first request
-        unsigned *d_words = nullptr;
-        unsigned long long *d_counters = nullptr;  // [0] row entries walked, [1] the end of the trace's clock, [2..4] SummaryKernel's
-        State *d_state = nullptr;                  // LoopKernel's state on return
-        int *d_trace_kind = nullptr;
-        unsigned *d_trace_finished = nullptr;
-        unsigned long long *d_trace_clock = nullptr;
+        DeviceArray<int> d_built_iro, d_built_ici;  // the transpose built here
+        int *d_iro = nullptr, *d_ici = nullptr;     // the transpose the kernels read (that one, or the caller's)
+        DeviceArray<int> d_region, d_outdeg, d_indeg, d_colour, d_mark, d_comp;
+        DeviceArray<int> d_list[2];
+        DeviceArray<int> d_queue[2];
+        DeviceArray<int> d_size;  // allocated at the first request
+        DeviceArray<unsigned> d_words;
+        DeviceArray<unsigned long long> d_counters;  // [0] row entries walked, [1] the end of the trace's clock, [2..4] SummaryKernel's
+        DeviceArray<State> d_state;  // LoopKernel's state on return
+        DeviceArray<int> d_trace_kind;
+        DeviceArray<unsigned> d_trace_finished;
+        DeviceArray<unsigned long long> d_trace_clock;
     };
 
-    DataSlice **data_slices = nullptr;
-    int malformed = 0;     // Init found offsets or columns that are not a CSR of `nodes` vertices
+    SliceHolder<DataSlice> data_slices;
     bool fresh = false;    // Reset has run and Enact has not
     bool sizes_valid = false;
     double build_ms = 0;   // HIP-event time of the transpose (0 for a borrowed one)
-
-    ~SccProblem() override
-    {
-        if (data_slices) {
-            DataSlice *ds = data_slices[0];
-            if (ds) {
-                void *bufs[] = {ds->owns_inverse ? ds->d_iro : nullptr, ds->owns_inverse ? ds->d_ici : nullptr, ds->d_region, ds->d_outdeg, ds->d_indeg,
-                                ds->d_colour, ds->d_mark, ds->d_comp, ds->d_list[0], ds->d_list[1], ds->d_queue[0], ds->d_queue[1], ds->d_size,
-                                ds->d_words, ds->d_counters, ds->d_state, ds->d_trace_kind, ds->d_trace_finished, ds->d_trace_clock};
-                for (void *b : bufs)
-                    if (b) util::GRError(hipFree(b), "SccProblem hipFree failed", __FILE__, __LINE__);
-                delete ds;
-            }
-            delete[] data_slices;
-        }
-    }
-
-    static int Grid(long long work)
-    {
-        long long blocks = (work + 255) / 256;
-        if (blocks < 1) blocks = 1;
-        if (blocks > 2048) blocks = 2048;  // 256 CUs x 8 workgroups, grid-stride the rest
-        return static_cast<int>(blocks);
-    }
 
     Ctx DeviceCtx(int wave_min_row) const
     {
@@ -96,13 +70,6 @@ struct SccProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         return c;
     }
 
-    // a CSR of `nodes` vertices?  (the kernels index with what they read)
-    hipError_t Validate(const int *d_ro, const int *d_ci, bool *bad)
-    {
-        return graphio::DeviceValidateCsr(d_ro, d_ci, this->nodes, this->edges, reinterpret_cast<int *>(data_slices[0]->d_words),
-                                          this->graph_slices[0]->stream, bad);
-    }
-
     hipError_t Build(int *d_inv_row_offsets, int *d_inv_col_indices)
     {
         hipError_t retval = hipSuccess;
@@ -111,17 +78,13 @@ struct SccProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         hipStream_t stream = gs->stream;
         const long long n = this->nodes, m = this->edges;
         const size_t n1 = static_cast<size_t>(n > 0 ? n : 1), m1 = static_cast<size_t>(m > 0 ? m : 1);
-        GR_CHECK(hipMalloc(&ds->d_words, sizeof(unsigned) * W_COUNT), "SccProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_counters, sizeof(unsigned long long) * 5), "SccProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_state, sizeof(State)), "SccProblem hipMalloc failed");
+        if ((retval = ds->d_words.Alloc(W_COUNT))) return retval;
+        if ((retval = ds->d_counters.Alloc(5))) return retval;
+        if ((retval = ds->d_state.Alloc(1))) return retval;
 
-        bool bad = false;
-        if ((retval = Validate(gs->d_row_offsets, gs->d_column_indices, &bad))) return retval;
-        if (!bad && d_inv_row_offsets && (retval = Validate(d_inv_row_offsets, d_inv_col_indices, &bad))) return retval;
-        if (bad) {
-            malformed = 1;
-            return hipErrorInvalidValue;
-        }
+        // CSRs of `nodes` vertices?  (the kernels index with what they read)
+        if ((retval = this->ValidateCsr())) return retval;
+        if (d_inv_row_offsets && (retval = this->ValidateCsr(d_inv_row_offsets, d_inv_col_indices))) return retval;
 
         if (d_inv_row_offsets) {
             ds->d_iro = d_inv_row_offsets;
@@ -132,9 +95,10 @@ struct SccProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
             GR_CHECK(hipEventCreate(&ev[0]), "SccProblem hipEventCreate failed");
             GR_CHECK(hipEventCreate(&ev[1]), "SccProblem hipEventCreate failed");
             GR_CHECK(hipEventRecord(ev[0], stream), "SccProblem hipEventRecord failed");
-            ds->owns_inverse = true;
-            GR_CHECK(hipMalloc(&ds->d_iro, sizeof(int) * (n1 + 1)), "SccProblem hipMalloc d_iro failed");
-            GR_CHECK(hipMalloc(&ds->d_ici, sizeof(int) * m1), "SccProblem hipMalloc d_ici failed");
+            if ((retval = ds->d_built_iro.Alloc(n1 + 1))) return retval;
+            if ((retval = ds->d_built_ici.Alloc(m1))) return retval;
+            ds->d_iro = ds->d_built_iro;
+            ds->d_ici = ds->d_built_ici;
             GR_CHECK(graphio::DeviceTransposeCsr(static_cast<int>(n), m, gs->d_row_offsets, gs->d_column_indices, ds->d_iro, ds->d_ici, stream),
                      "SccProblem transpose failed");
             GR_CHECK(hipEventRecord(ev[1], stream), "SccProblem hipEventRecord failed");
@@ -146,16 +110,16 @@ struct SccProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
             hipEventDestroy(ev[1]);
         }
 
-        int **arrays[] = {&ds->d_region, &ds->d_outdeg, &ds->d_indeg, &ds->d_colour, &ds->d_mark, &ds->d_comp, &ds->d_list[0], &ds->d_list[1],
+        DeviceArray<int> *arrays[] = {&ds->d_region, &ds->d_outdeg, &ds->d_indeg, &ds->d_colour, &ds->d_mark, &ds->d_comp, &ds->d_list[0], &ds->d_list[1],
                           &ds->d_queue[0], &ds->d_queue[1]};
-        for (int **a : arrays) GR_CHECK(hipMalloc(a, sizeof(int) * n1), "SccProblem hipMalloc failed");
+        for (DeviceArray<int> *a : arrays) if ((retval = a->Alloc(n1))) return retval;
         // no representative yet: a result asked for before the first Enact finds every entry negative, which the result kernels
         // skip, and never an index taken from fresh memory
         GR_CHECK(hipMemsetAsync(ds->d_comp, 0xFF, sizeof(int) * n1, stream), "SccProblem memset failed");
         GR_CHECK(hipStreamSynchronize(stream), "SccProblem build sync failed");
-        GR_CHECK(hipMalloc(&ds->d_trace_kind, sizeof(int) * kTraceRows), "SccProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_trace_finished, sizeof(unsigned) * kTraceRows), "SccProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_trace_clock, sizeof(unsigned long long) * kTraceRows), "SccProblem hipMalloc failed");
+        if ((retval = ds->d_trace_kind.Alloc(kTraceRows))) return retval;
+        if ((retval = ds->d_trace_finished.Alloc(kTraceRows))) return retval;
+        if ((retval = ds->d_trace_clock.Alloc(kTraceRows))) return retval;
         return retval;
     }
 
@@ -164,8 +128,7 @@ struct SccProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     {
         hipError_t retval = hipSuccess;
         if ((retval = Base::Init(stream_from_host, graph, num_gpus, false))) return retval;
-        data_slices = new DataSlice *[1];
-        data_slices[0] = new DataSlice();
+        data_slices.Make();
         return Build(nullptr, nullptr);
     }
 
@@ -175,8 +138,7 @@ struct SccProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     {
         hipError_t retval = hipSuccess;
         if ((retval = Base::InitFromDevice(nodes, edges, d_row_offsets, d_column_indices))) return retval;
-        data_slices = new DataSlice *[1];
-        data_slices[0] = new DataSlice();
+        data_slices.Make();
         return Build(d_inv_row_offsets, d_inv_col_indices);
     }
 
@@ -208,11 +170,11 @@ struct SccProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         DataSlice *ds = data_slices[0];
         hipStream_t stream = this->graph_slices[0]->stream;
         const long long n = this->nodes;
-        hipLaunchKernelGGL(IotaKernel, dim3(Grid(n)), dim3(256), 0, stream, ds->d_colour, n);
+        hipLaunchKernelGGL(IotaKernel, dim3(graphio::PairGrid(n)), dim3(256), 0, stream, ds->d_colour, n);
         GR_CHECK(hipGetLastError(), "IotaKernel launch failed");
-        hipLaunchKernelGGL(MergeKernel<false>, dim3(Grid(n)), dim3(256), 0, stream, ds->d_comp, n, ds->d_colour);
+        hipLaunchKernelGGL(MergeKernel<false>, dim3(graphio::PairGrid(n)), dim3(256), 0, stream, ds->d_comp, n, ds->d_colour);
         GR_CHECK(hipGetLastError(), "MergeKernel launch failed");
-        hipLaunchKernelGGL(GatherKernel, dim3(Grid(n)), dim3(256), 0, stream, ds->d_comp, n, ds->d_colour, ds->d_comp);
+        hipLaunchKernelGGL(GatherKernel, dim3(graphio::PairGrid(n)), dim3(256), 0, stream, ds->d_comp, n, ds->d_colour, ds->d_comp);
         GR_CHECK(hipGetLastError(), "GatherKernel launch failed");
         return retval;
     }
@@ -225,11 +187,11 @@ struct SccProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         DataSlice *ds = data_slices[0];
         hipStream_t stream = this->graph_slices[0]->stream;
         const long long n = this->nodes;
-        if (!ds->d_size) GR_CHECK(hipMalloc(&ds->d_size, sizeof(int) * static_cast<size_t>(n)), "SccProblem hipMalloc d_size failed");
+        if (!ds->d_size && (retval = ds->d_size.Alloc(static_cast<size_t>(n)))) return retval;
         GR_CHECK(hipMemsetAsync(ds->d_colour, 0, sizeof(int) * static_cast<size_t>(n), stream), "SccProblem memset failed");
-        hipLaunchKernelGGL(MergeKernel<true>, dim3(Grid(n)), dim3(256), 0, stream, ds->d_comp, n, ds->d_colour);
+        hipLaunchKernelGGL(MergeKernel<true>, dim3(graphio::PairGrid(n)), dim3(256), 0, stream, ds->d_comp, n, ds->d_colour);
         GR_CHECK(hipGetLastError(), "MergeKernel launch failed");
-        hipLaunchKernelGGL(GatherKernel, dim3(Grid(n)), dim3(256), 0, stream, ds->d_comp, n, ds->d_colour, ds->d_size);
+        hipLaunchKernelGGL(GatherKernel, dim3(graphio::PairGrid(n)), dim3(256), 0, stream, ds->d_comp, n, ds->d_colour, ds->d_size);
         GR_CHECK(hipGetLastError(), "GatherKernel launch failed");
         sizes_valid = true;
         return retval;
@@ -256,7 +218,7 @@ struct SccProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         if ((retval = DeviceSizes())) return retval;
         unsigned long long out[3] = {0, 0, 0};
         GR_CHECK(hipMemsetAsync(ds->d_counters + 2, 0, sizeof(out), stream), "SccProblem memset failed");
-        hipLaunchKernelGGL(SummaryKernel, dim3(Grid(this->nodes)), dim3(256), 0, stream, ds->d_comp, ds->d_size, static_cast<long long>(this->nodes),
+        hipLaunchKernelGGL(SummaryKernel, dim3(graphio::PairGrid(this->nodes)), dim3(256), 0, stream, ds->d_comp, ds->d_size, static_cast<long long>(this->nodes),
                            ds->d_counters + 2);
         GR_CHECK(hipGetLastError(), "SummaryKernel launch failed");
         GR_CHECK(hipMemcpyAsync(out, ds->d_counters + 2, sizeof(out), hipMemcpyDeviceToHost, stream), "SccProblem read-back failed");
@@ -299,47 +261,36 @@ struct SccProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         const int key_bits = 2 * col_bits;  // <= 62
         const unsigned long long sentinel = (1ull << key_bits) - 1ull;  // from = to = 2^cb - 1: never a pair
         graphio::DeviceKeySort sort;
-        unsigned *d_keep = nullptr;
-        unsigned long long *d_pos = nullptr, *d_sums = nullptr;
-        int *d_from = nullptr, *d_to = nullptr;
-        auto release = [&]() {
-            void *bufs[] = {d_keep, d_pos, d_sums, d_from, d_to};
-            for (void *b : bufs)
-                if (b) util::GRError(hipFree(b), "SccProblem hipFree failed", __FILE__, __LINE__);
-        };
-        auto run = [&]() -> hipError_t {
-            hipError_t retval = hipSuccess;
-            GR_CHECK(sort.Reserve(m), "SccProblem sort scratch failed");
-            GR_CHECK(hipMalloc(&d_keep, sizeof(unsigned) * static_cast<size_t>(m)), "SccProblem hipMalloc failed");
-            GR_CHECK(hipMalloc(&d_pos, sizeof(unsigned long long) * static_cast<size_t>(m)), "SccProblem hipMalloc failed");
-            GR_CHECK(hipMalloc(&d_sums, sizeof(unsigned long long) * static_cast<size_t>(graphio::ScanScratchWords(m))), "SccProblem hipMalloc failed");
-            hipLaunchKernelGGL(CondensationKeysKernel, dim3(Grid(m)), dim3(256), 0, stream, gs->d_row_offsets, gs->d_column_indices, ds->d_comp,
-                               static_cast<int>(n), m, col_bits, sentinel, sort.Keys());
-            GR_CHECK(hipGetLastError(), "CondensationKeysKernel launch failed");
-            unsigned long long *d_sorted = nullptr;
-            GR_CHECK(sort.Sort(m, key_bits, stream, &d_sorted), "SccProblem key sort failed");
-            hipLaunchKernelGGL(graphio::FlagKernel, dim3(Grid(m)), dim3(256), 0, stream, d_sorted, m, sentinel, d_keep);
-            GR_CHECK(hipGetLastError(), "FlagKernel launch failed");
-            GR_CHECK(graphio::DeviceExclusiveScan<unsigned long long>(d_keep, d_pos, m, d_sums, stream), "SccProblem flag scan failed");
-            // the total is behind the tile offsets (DeviceCooToCsr reads it from there too)
-            const long long scan_tiles = (m + graphio::kScanTile - 1) / graphio::kScanTile;
-            unsigned long long total = 0;
-            GR_CHECK(hipMemcpyAsync(&total, d_sums + scan_tiles, sizeof(total), hipMemcpyDeviceToHost, stream), "SccProblem read total failed");
-            GR_CHECK(hipStreamSynchronize(stream), "SccProblem Condensation sync failed");
-            *count = static_cast<long long>(total);
-            const long long take = *count < max_edges ? *count : max_edges;
-            if (take < 1 || !h_from || !h_to) return retval;
-            GR_CHECK(hipMalloc(&d_from, sizeof(int) * static_cast<size_t>(take)), "SccProblem hipMalloc failed");
-            GR_CHECK(hipMalloc(&d_to, sizeof(int) * static_cast<size_t>(take)), "SccProblem hipMalloc failed");
-            hipLaunchKernelGGL(CondensationEmitKernel, dim3(Grid(m)), dim3(256), 0, stream, d_sorted, d_keep, d_pos, m, col_bits, take, d_from, d_to);
-            GR_CHECK(hipGetLastError(), "CondensationEmitKernel launch failed");
-            GR_CHECK(hipMemcpyAsync(h_from, d_from, sizeof(int) * static_cast<size_t>(take), hipMemcpyDeviceToHost, stream), "SccProblem read failed");
-            GR_CHECK(hipMemcpyAsync(h_to, d_to, sizeof(int) * static_cast<size_t>(take), hipMemcpyDeviceToHost, stream), "SccProblem read failed");
-            GR_CHECK(hipStreamSynchronize(stream), "SccProblem Condensation sync failed");
-            return retval;
-        };
-        retval = run();
-        release();
+        graphio::DeviceScratch<unsigned> d_keep;
+        graphio::DeviceScratch<unsigned long long> d_pos, d_sums;
+        graphio::DeviceScratch<int> d_from, d_to;
+        GR_CHECK(sort.Reserve(m), "SccProblem sort scratch failed");
+        if ((retval = d_keep.Alloc(static_cast<size_t>(m)))) return retval;
+        if ((retval = d_pos.Alloc(static_cast<size_t>(m)))) return retval;
+        if ((retval = d_sums.Alloc(static_cast<size_t>(graphio::ScanScratchWords(m))))) return retval;
+        hipLaunchKernelGGL(CondensationKeysKernel, dim3(graphio::PairGrid(m)), dim3(256), 0, stream, gs->d_row_offsets, gs->d_column_indices, ds->d_comp,
+                           static_cast<int>(n), m, col_bits, sentinel, sort.Keys());
+        GR_CHECK(hipGetLastError(), "CondensationKeysKernel launch failed");
+        unsigned long long *d_sorted = nullptr;
+        GR_CHECK(sort.Sort(m, key_bits, stream, &d_sorted), "SccProblem key sort failed");
+        hipLaunchKernelGGL(graphio::FlagKernel, dim3(graphio::PairGrid(m)), dim3(256), 0, stream, d_sorted, m, sentinel, d_keep);
+        GR_CHECK(hipGetLastError(), "FlagKernel launch failed");
+        GR_CHECK(graphio::DeviceExclusiveScan<unsigned long long>(d_keep.p, d_pos.p, m, d_sums.p, stream), "SccProblem flag scan failed");
+        // the total is behind the tile offsets (DeviceCooToCsr reads it from there too)
+        const long long scan_tiles = (m + graphio::kScanTile - 1) / graphio::kScanTile;
+        unsigned long long total = 0;
+        GR_CHECK(hipMemcpyAsync(&total, d_sums + scan_tiles, sizeof(total), hipMemcpyDeviceToHost, stream), "SccProblem read total failed");
+        GR_CHECK(hipStreamSynchronize(stream), "SccProblem Condensation sync failed");
+        *count = static_cast<long long>(total);
+        const long long take = *count < max_edges ? *count : max_edges;
+        if (take < 1 || !h_from || !h_to) return retval;
+        if ((retval = d_from.Alloc(static_cast<size_t>(take)))) return retval;
+        if ((retval = d_to.Alloc(static_cast<size_t>(take)))) return retval;
+        hipLaunchKernelGGL(CondensationEmitKernel, dim3(graphio::PairGrid(m)), dim3(256), 0, stream, d_sorted, d_keep, d_pos, m, col_bits, take, d_from, d_to);
+        GR_CHECK(hipGetLastError(), "CondensationEmitKernel launch failed");
+        GR_CHECK(hipMemcpyAsync(h_from, d_from, sizeof(int) * static_cast<size_t>(take), hipMemcpyDeviceToHost, stream), "SccProblem read failed");
+        GR_CHECK(hipMemcpyAsync(h_to, d_to, sizeof(int) * static_cast<size_t>(take), hipMemcpyDeviceToHost, stream), "SccProblem read failed");
+        GR_CHECK(hipStreamSynchronize(stream), "SccProblem Condensation sync failed");
         return retval;
     }
 };

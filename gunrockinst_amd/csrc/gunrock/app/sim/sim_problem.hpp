@@ -26,10 +26,10 @@ struct SimProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     typedef ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> Base;
 
     struct DataSlice {
-        int *d_ro = nullptr;  // the neighbour CSR of G
-        int *d_ci = nullptr;
-        int *d_wd = nullptr;  // Wd per vertex
-        unsigned long long *d_words = nullptr;  // W_COUNT words of the kernels, then [0] the sum of Wd, [1] the largest
+        DeviceArray<int> d_ro;  // the neighbour CSR of G
+        DeviceArray<int> d_ci;
+        DeviceArray<int> d_wd;  // Wd per vertex
+        DeviceArray<unsigned long long> d_words;  // W_COUNT words of the kernels, then [0] the sum of Wd, [1] the largest
         Grown<int> staged_u, staged_v;          // queries given on the host
         Grown<int> pair_common;                 // pair mode's result
         Grown<long long> pair_num, pair_den;
@@ -38,8 +38,7 @@ struct SimProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         Grown<int> rows;  // the GLOBAL regime's counter rows, grown by Enact, all 0 between launches
     };
 
-    DataSlice **data_slices = nullptr;
-    int malformed = 0;           // Init found offsets or columns that are not a CSR of `nodes` vertices
+    SliceHolder<DataSlice> data_slices;
     long long simple_edges = 0;  // M
     long long wedges = 0;        // the sum of Wd
     long long max_wedges = 0;    // the largest Wd
@@ -47,33 +46,6 @@ struct SimProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     long long sources = -1;      // of the last finished top-k Enact, or -1
     int k = 0;                   // ... and its k
     double build_ms = 0;         // HIP-event time of the build
-
-    ~SimProblem() override
-    {
-        if (data_slices) {
-            DataSlice *ds = data_slices[0];
-            if (ds) {
-                void *bufs[] = {ds->d_ro, ds->d_ci, ds->d_wd, ds->d_words};
-                for (void *b : bufs)
-                    if (b) util::GRError(hipFree(b), "SimProblem hipFree failed", __FILE__, __LINE__);
-                ds->staged_u.Free();
-                ds->staged_v.Free();
-                ds->pair_common.Free();
-                ds->pair_num.Free();
-                ds->pair_den.Free();
-                ds->ids.Free();
-                ds->common.Free();
-                ds->count.Free();
-                ds->candidates.Free();
-                ds->lists.Free();
-                ds->num.Free();
-                ds->den.Free();
-                ds->rows.Free();
-                delete ds;
-            }
-            delete[] data_slices;
-        }
-    }
 
     hipError_t Build()
     {
@@ -83,23 +55,16 @@ struct SimProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         hipStream_t stream = gs->stream;
         const long long n = this->nodes, m = this->edges;
         const size_t n1 = static_cast<size_t>(n > 0 ? n : 1);
-        GR_CHECK(hipMalloc(&ds->d_words, sizeof(unsigned long long) * (W_COUNT + 2)), "SimProblem hipMalloc failed");
+        if ((retval = ds->d_words.Alloc(W_COUNT + 2))) return retval;
 
         // 1. the CSR must be one: the build indexes with what it reads
-        bool bad = false;
-        graphio::DeviceScratch<int> flag;
-        if ((retval = flag.Alloc(1))) return retval;
-        if ((retval = graphio::DeviceValidateCsr(gs->d_row_offsets, gs->d_column_indices, n, m, flag.p, stream, &bad))) return retval;
-        if (bad) {
-            malformed = 1;
-            return hipErrorInvalidValue;
-        }
+        if ((retval = this->ValidateCsr())) return retval;
 
         graphio::BuildEvents ev;
         if ((retval = ev.Create(2))) return retval;
         if ((retval = ev.Record(0, stream))) return retval;
 
-        GR_CHECK(hipMalloc(&ds->d_wd, sizeof(int) * n1), "SimProblem hipMalloc d_wd failed");
+        if ((retval = ds->d_wd.Alloc(n1))) return retval;
         GR_CHECK(hipMemsetAsync(ds->d_wd, 0, sizeof(int) * n1, stream), "SimProblem memset failed");
         GR_CHECK(hipMemsetAsync(ds->d_words, 0, sizeof(unsigned long long) * (W_COUNT + 2), stream), "SimProblem memset failed");
 
@@ -121,17 +86,11 @@ struct SimProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         if ((retval = ev.Record(1, stream))) return retval;
         GR_CHECK(hipStreamSynchronize(stream), "SimProblem build sync failed");  // (the sorts' buffers go behind this)
         if ((retval = ev.Elapsed(0, 1, &build_ms))) return retval;
-        ds->d_ro = graphio::Take(pg.d_ro);
-        ds->d_ci = graphio::Take(pg.d_ci);
+        ds->d_ro.Adopt(graphio::Take(pg.d_ro));
+        ds->d_ci.Adopt(graphio::Take(pg.d_ci));
         wedges = static_cast<long long>(summary[0]);
         max_wedges = static_cast<long long>(summary[1]);
         return retval;
-    }
-
-    void NewSlice()
-    {
-        data_slices = new DataSlice *[1];
-        data_slices[0] = new DataSlice();
     }
 
     // One Init per object (grx_sim_init refuses a second one)
@@ -139,7 +98,7 @@ struct SimProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     {
         hipError_t retval = hipSuccess;
         if ((retval = Base::Init(stream_from_host, graph, num_gpus, false))) return retval;
-        NewSlice();
+        data_slices.Make();
         return Build();
     }
 
@@ -147,7 +106,7 @@ struct SimProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     {
         hipError_t retval = hipSuccess;
         if ((retval = Base::InitFromDevice(nodes, edges, d_row_offsets, d_column_indices))) return retval;
-        NewSlice();
+        data_slices.Make();
         return Build();
     }
 
@@ -187,13 +146,6 @@ struct SimProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         for (size_t i = 0; i < count; ++i) score[i] = den[i] ? static_cast<double>(num[i]) / static_cast<double>(den[i]) : 0.0;
     }
 
-    template <typename T>
-    hipError_t Read(T *host, const T *device, size_t count)
-    {
-        if (!host || !count) return hipSuccess;
-        return util::GRError(hipMemcpy(host, device, sizeof(T) * count, hipMemcpyDeviceToHost), "SimProblem read failed", __FILE__, __LINE__);
-    }
-
     hipError_t ExtractPairs(int *h_common, long long *h_num, long long *h_den, double *h_score)
     {
         hipError_t retval = hipSuccess;
@@ -202,9 +154,9 @@ struct SimProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         std::vector<long long> num, den;
         if (h_score && !h_num) num.resize(count), h_num = num.data();
         if (h_score && !h_den) den.resize(count), h_den = den.data();
-        if ((retval = Read(h_common, ds->pair_common.p, count))) return retval;
-        if ((retval = Read(h_num, ds->pair_num.p, count))) return retval;
-        if ((retval = Read(h_den, ds->pair_den.p, count))) return retval;
+        if ((retval = this->Read(h_common, ds->pair_common.p, count))) return retval;
+        if ((retval = this->Read(h_num, ds->pair_num.p, count))) return retval;
+        if ((retval = this->Read(h_den, ds->pair_den.p, count))) return retval;
         if (h_score) Scores(count, h_num, h_den, h_score);
         return retval;
     }
@@ -217,12 +169,12 @@ struct SimProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         std::vector<long long> num, den;
         if (h_score && !h_num) num.resize(count), h_num = num.data();
         if (h_score && !h_den) den.resize(count), h_den = den.data();
-        if ((retval = Read(h_ids, ds->ids.p, count))) return retval;
-        if ((retval = Read(h_common, ds->common.p, count))) return retval;
-        if ((retval = Read(h_num, ds->num.p, count))) return retval;
-        if ((retval = Read(h_den, ds->den.p, count))) return retval;
-        if ((retval = Read(h_count, ds->count.p, rows))) return retval;
-        if ((retval = Read(h_candidates, ds->candidates.p, rows))) return retval;
+        if ((retval = this->Read(h_ids, ds->ids.p, count))) return retval;
+        if ((retval = this->Read(h_common, ds->common.p, count))) return retval;
+        if ((retval = this->Read(h_num, ds->num.p, count))) return retval;
+        if ((retval = this->Read(h_den, ds->den.p, count))) return retval;
+        if ((retval = this->Read(h_count, ds->count.p, rows))) return retval;
+        if ((retval = this->Read(h_candidates, ds->candidates.p, rows))) return retval;
         if (h_score) Scores(count, h_num, h_den, h_score);
         return retval;
     }

@@ -25,34 +25,32 @@ namespace spgemm {
 
 // a CSR in device memory: the problem's own (freed with it) or the caller's
 struct DeviceMat {
-    int *ro = nullptr, *ci = nullptr, *val = nullptr;
+    DeviceArray<int> own_ro, own_ci, own_val;          // the problem's own arrays, when it made them
+    int *ro = nullptr, *ci = nullptr, *val = nullptr;  // what the kernels read: those, or the caller's
     int rows = 0, cols = 0, nnz = 0;
-    bool owned = false, set = false;
+    bool set = false;
 
-    void Free()
+    void Free() { *this = DeviceMat(); }
+    // arrays of its own: `offsets` row offsets, nnz_ columns and, with_val, as many values
+    hipError_t Own(int rows_, int cols_, int nnz_, size_t offsets, bool with_val)
     {
-        if (owned) {
-            int *bufs[] = {ro, ci, val};
-            for (int *b : bufs)
-                if (b) util::GRError(hipFree(b), "SpgemmProblem hipFree failed", __FILE__, __LINE__);
-        }
-        *this = DeviceMat();
+        hipError_t retval = hipSuccess;
+        Free();
+        rows = rows_, cols = cols_, nnz = nnz_;
+        if ((retval = own_ro.Alloc(offsets))) return retval;
+        if ((retval = own_ci.Alloc(static_cast<size_t>(nnz)))) return retval;
+        if (with_val && (retval = own_val.Alloc(static_cast<size_t>(nnz)))) return retval;
+        ro = own_ro, ci = own_ci, val = own_val;
+        return retval;
     }
     hipError_t Upload(int rows_, int cols_, int nnz_, const int *h_ro, const int *h_ci, const int *h_val)
     {
         hipError_t retval = hipSuccess;
-        Free();
-        owned = true;
-        rows = rows_, cols = cols_, nnz = nnz_;
-        const size_t n1 = static_cast<size_t>(rows) + 1, m = static_cast<size_t>(nnz), m1 = m ? m : 1;
-        GR_CHECK(hipMalloc(&ro, sizeof(int) * n1), "SpgemmProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ci, sizeof(int) * m1), "SpgemmProblem hipMalloc failed");
+        const size_t n1 = static_cast<size_t>(rows_) + 1, m = static_cast<size_t>(nnz_);
+        if ((retval = Own(rows_, cols_, nnz_, n1, h_val != nullptr))) return retval;
         GR_CHECK(hipMemcpy(ro, h_ro, sizeof(int) * n1, hipMemcpyHostToDevice), "SpgemmProblem hipMemcpy failed");
         if (m) GR_CHECK(hipMemcpy(ci, h_ci, sizeof(int) * m, hipMemcpyHostToDevice), "SpgemmProblem hipMemcpy failed");
-        if (h_val) {
-            GR_CHECK(hipMalloc(&val, sizeof(int) * m1), "SpgemmProblem hipMalloc failed");
-            if (m) GR_CHECK(hipMemcpy(val, h_val, sizeof(int) * m, hipMemcpyHostToDevice), "SpgemmProblem hipMemcpy failed");
-        }
+        if (h_val && m) GR_CHECK(hipMemcpy(val, h_val, sizeof(int) * m, hipMemcpyHostToDevice), "SpgemmProblem hipMemcpy failed");
         return retval;
     }
     void Borrow(int rows_, int cols_, int nnz_, int *d_ro, int *d_ci, int *d_val)
@@ -67,7 +65,7 @@ struct DeviceMat {
 struct SpgemmProblem {
     DeviceMat a, given, transposed;
     hipStream_t stream = nullptr;
-    unsigned long long *d_words = nullptr;  // W_COUNT words of the kernels
+    DeviceArray<unsigned long long> d_words;  // W_COUNT words of the kernels
     Grown<long long> work, babs;            // w_i per row of A; the sum of |b| per row of B
     Grown<int> lists;                       // 4 x rows
     Grown<unsigned> counts;                 // rows + 1: the distinct columns per row, then 0
@@ -82,21 +80,8 @@ struct SpgemmProblem {
     SpgemmProblem() = default;
     SpgemmProblem(const SpgemmProblem &) = delete;
     SpgemmProblem &operator=(const SpgemmProblem &) = delete;
-    ~SpgemmProblem()
+    ~SpgemmProblem()  // (the arrays free themselves)
     {
-        a.Free();
-        given.Free();
-        transposed.Free();
-        if (d_words) util::GRError(hipFree(d_words), "SpgemmProblem hipFree failed", __FILE__, __LINE__);
-        work.Free();
-        babs.Free();
-        lists.Free();
-        counts.Free();
-        sums.Free();
-        scratch.Free();
-        offsets.Free();
-        cols.Free();
-        vals.Free();
         if (stream) util::GRError(hipStreamDestroy(stream), "SpgemmProblem hipStreamDestroy failed", __FILE__, __LINE__);
     }
 
@@ -122,8 +107,8 @@ struct SpgemmProblem {
         bool bad = false;
         malformed = 0;
         if ((retval = Validate(m, &bad))) return retval;
+        malformed = bad;
         if (bad) {
-            malformed = 1;
             m.Free();
             return hipErrorInvalidValue;
         }
@@ -136,8 +121,7 @@ struct SpgemmProblem {
     {
         hipError_t retval = hipSuccess;
         GR_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking), "SpgemmProblem hipStreamCreate failed");
-        GR_CHECK(hipMalloc(&d_words, sizeof(unsigned long long) * W_COUNT), "SpgemmProblem hipMalloc failed");
-        return retval;
+        return d_words.Alloc(W_COUNT);
     }
 
     // One Init per object (grx_spgemm_init refuses a second one).  vals may be NULL.
@@ -171,13 +155,8 @@ struct SpgemmProblem {
         hipError_t retval = hipSuccess;
         if (transposed.set) return retval;
         const int n = a.rows > a.cols ? a.rows : a.cols;
-        const size_t n1 = static_cast<size_t>(n) + 1, m1 = a.nnz ? static_cast<size_t>(a.nnz) : 1;
-        transposed.Free();
-        transposed.owned = true;
-        transposed.rows = a.cols, transposed.cols = a.rows, transposed.nnz = a.nnz;
-        GR_CHECK(hipMalloc(&transposed.ro, sizeof(int) * n1), "SpgemmProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&transposed.ci, sizeof(int) * m1), "SpgemmProblem hipMalloc failed");
-        if (a.val) GR_CHECK(hipMalloc(&transposed.val, sizeof(int) * m1), "SpgemmProblem hipMalloc failed");
+        const size_t n1 = static_cast<size_t>(n) + 1;
+        if ((retval = transposed.Own(a.cols, a.rows, a.nnz, n1, a.val != nullptr))) return retval;
         graphio::DeviceScratch<int> padded;
         const int *ro = a.ro;
         if (n > a.rows) {

@@ -27,47 +27,23 @@ struct TCProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     typedef ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> Base;
 
     struct DataSlice {
-        Count *d_triangles = nullptr;   // the result, one 64-bit count per vertex
-        unsigned *d_degrees = nullptr;  // d(v) in G
-        int *d_oro = nullptr;           // the oriented CSR
-        int *d_oci = nullptr;
-        int *d_osrc = nullptr;          // the row of every oriented entry
-        int *d_rows[2] = {nullptr, nullptr};  // the LDS and the global regime's row lists
-        int *d_words = nullptr;         // BinKernel's counters
-        Count *d_counters = nullptr;    // [0] triangles, [1] entries probed; [2] sum of C(d, 2), [3] the largest out-row
-        double *d_coeff = nullptr;      // clustering coefficients (allocated at the first request)
+        DeviceArray<Count> d_triangles;  // the result, one 64-bit count per vertex
+        DeviceArray<unsigned> d_degrees;  // d(v) in G
+        DeviceArray<int> d_oro;  // the oriented CSR
+        DeviceArray<int> d_oci;
+        DeviceArray<int> d_osrc;  // the row of every oriented entry
+        DeviceArray<int> d_rows[2];  // the LDS and the global regime's row lists
+        DeviceArray<int> d_words;  // BinKernel's counters
+        DeviceArray<Count> d_counters;  // [0] triangles, [1] entries probed; [2] sum of C(d, 2), [3] the largest out-row
+        DeviceArray<double> d_coeff;  // clustering coefficients (allocated at the first request)
     };
 
-    DataSlice **data_slices = nullptr;
-    int malformed = 0;            // Init found offsets or columns that are not a CSR of `nodes` vertices
+    SliceHolder<DataSlice> data_slices;
     long long oriented_edges = 0; // M
     long long max_out_row = 0;
     long long wedges = 0;         // sum over v of C(d(v), 2)
     long long total = 0;          // of the last Extract
     double build_ms = 0;          // HIP-event time of the oriented-graph build
-
-    ~TCProblem() override
-    {
-        if (data_slices) {
-            DataSlice *ds = data_slices[0];
-            if (ds) {
-                void *bufs[] = {ds->d_triangles, ds->d_degrees, ds->d_oro, ds->d_oci, ds->d_osrc, ds->d_rows[0], ds->d_rows[1], ds->d_words,
-                                ds->d_counters, ds->d_coeff};
-                for (void *b : bufs)
-                    if (b) util::GRError(hipFree(b), "TCProblem hipFree failed", __FILE__, __LINE__);
-                delete ds;
-            }
-            delete[] data_slices;
-        }
-    }
-
-    static int Grid(long long work)
-    {
-        long long blocks = (work + 255) / 256;
-        if (blocks < 1) blocks = 1;
-        if (blocks > 2048) blocks = 2048;  // 256 CUs x 8 workgroups, grid-stride the rest
-        return static_cast<int>(blocks);
-    }
 
     Oriented DeviceGraph() const
     {
@@ -83,26 +59,21 @@ struct TCProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         hipStream_t stream = gs->stream;
         const long long n = this->nodes, m = this->edges;
         const size_t n1 = static_cast<size_t>(n > 0 ? n : 1);
-        GR_CHECK(hipMalloc(&ds->d_words, sizeof(int) * 4), "TCProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_counters, sizeof(Count) * 4), "TCProblem hipMalloc failed");
+        if ((retval = ds->d_words.Alloc(4))) return retval;
+        if ((retval = ds->d_counters.Alloc(4))) return retval;
 
         // 1. the CSR must be one: the build indexes with what it reads
-        bool bad = false;
-        if ((retval = graphio::DeviceValidateCsr(gs->d_row_offsets, gs->d_column_indices, n, m, ds->d_words, stream, &bad))) return retval;
-        if (bad) {
-            malformed = 1;
-            return hipErrorInvalidValue;
-        }
+        if ((retval = this->ValidateCsr())) return retval;
 
         graphio::BuildEvents ev;
         if ((retval = ev.Create(2))) return retval;
         if ((retval = ev.Record(0, stream))) return retval;
 
-        GR_CHECK(hipMalloc(&ds->d_triangles, sizeof(Count) * n1), "TCProblem hipMalloc d_triangles failed");
-        GR_CHECK(hipMalloc(&ds->d_degrees, sizeof(unsigned) * n1), "TCProblem hipMalloc d_degrees failed");
-        GR_CHECK(hipMalloc(&ds->d_oro, sizeof(int) * (n1 + 1)), "TCProblem hipMalloc d_oro failed");
-        GR_CHECK(hipMalloc(&ds->d_rows[0], sizeof(int) * n1), "TCProblem hipMalloc d_rows failed");
-        GR_CHECK(hipMalloc(&ds->d_rows[1], sizeof(int) * n1), "TCProblem hipMalloc d_rows failed");
+        if ((retval = ds->d_triangles.Alloc(n1))) return retval;
+        if ((retval = ds->d_degrees.Alloc(n1))) return retval;
+        if ((retval = ds->d_oro.Alloc(n1 + 1))) return retval;
+        if ((retval = ds->d_rows[0].Alloc(n1))) return retval;
+        if ((retval = ds->d_rows[1].Alloc(n1))) return retval;
         GR_CHECK(hipMemsetAsync(ds->d_degrees, 0, sizeof(unsigned) * n1, stream), "TCProblem memset failed");
         GR_CHECK(hipMemsetAsync(ds->d_oro, 0, sizeof(int) * (n1 + 1), stream), "TCProblem memset failed");
         GR_CHECK(hipMemsetAsync(ds->d_counters, 0, sizeof(Count) * 4, stream), "TCProblem memset failed");
@@ -112,26 +83,26 @@ struct TCProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         if ((retval = pg.Keys(gs->d_row_offsets, gs->d_column_indices, m, stream))) return retval;
         if ((retval = pg.CountKept(stream, &oriented_edges))) return retval;
         if (oriented_edges > 0) {
-            hipLaunchKernelGGL(DegreeKernel, dim3(Grid(m)), dim3(256), 0, stream, pg.d_sorted, pg.d_keep, m, pg.col_bits, ds->d_degrees);
+            hipLaunchKernelGGL(DegreeKernel, dim3(graphio::PairGrid(m)), dim3(256), 0, stream, pg.d_sorted, pg.d_keep, m, pg.col_bits, ds->d_degrees);
             GR_CHECK(hipGetLastError(), "DegreeKernel launch failed");
             GR_CHECK(oriented_sort.Reserve(oriented_edges), "TCProblem sort scratch failed");
             graphio::DeviceScratch<unsigned> outdeg;  // n + 1 words, the last one 0: its scan is the offsets
             if ((retval = outdeg.Alloc(n1 + 1))) return retval;
             GR_CHECK(hipMemsetAsync(outdeg.p, 0, sizeof(unsigned) * (n1 + 1), stream), "TCProblem memset failed");
-            hipLaunchKernelGGL(OrientKernel, dim3(Grid(m)), dim3(256), 0, stream, pg.d_sorted, pg.d_keep, pg.d_pos, m, pg.col_bits, ds->d_degrees,
+            hipLaunchKernelGGL(OrientKernel, dim3(graphio::PairGrid(m)), dim3(256), 0, stream, pg.d_sorted, pg.d_keep, pg.d_pos, m, pg.col_bits, ds->d_degrees,
                                oriented_sort.Keys(), outdeg.p);
             GR_CHECK(hipGetLastError(), "OrientKernel launch failed");
             GR_CHECK(graphio::DeviceExclusiveScan<int>(outdeg.p, ds->d_oro, n + 1, pg.d_sums, stream), "TCProblem offset scan failed");
             unsigned long long *d_osorted = nullptr;
             GR_CHECK(oriented_sort.Sort(oriented_edges, pg.key_bits, stream, &d_osorted), "TCProblem oriented sort failed");
-            GR_CHECK(hipMalloc(&ds->d_oci, sizeof(int) * static_cast<size_t>(oriented_edges)), "TCProblem hipMalloc d_oci failed");
-            GR_CHECK(hipMalloc(&ds->d_osrc, sizeof(int) * static_cast<size_t>(oriented_edges)), "TCProblem hipMalloc d_osrc failed");
-            hipLaunchKernelGGL(EmitOrientedKernel, dim3(Grid(oriented_edges)), dim3(256), 0, stream, d_osorted, oriented_edges, pg.col_bits, ds->d_oci,
+            if ((retval = ds->d_oci.Alloc(static_cast<size_t>(oriented_edges)))) return retval;
+            if ((retval = ds->d_osrc.Alloc(static_cast<size_t>(oriented_edges)))) return retval;
+            hipLaunchKernelGGL(EmitOrientedKernel, dim3(graphio::PairGrid(oriented_edges)), dim3(256), 0, stream, d_osorted, oriented_edges, pg.col_bits, ds->d_oci,
                                ds->d_osrc);
             GR_CHECK(hipGetLastError(), "EmitOrientedKernel launch failed");
             GR_CHECK(hipStreamSynchronize(stream), "TCProblem build sync failed");  // (outdeg goes here)
         }
-        hipLaunchKernelGGL(RowSummaryKernel, dim3(Grid(n)), dim3(256), 0, stream, ds->d_degrees, ds->d_oro, n, ds->d_counters + 2);
+        hipLaunchKernelGGL(RowSummaryKernel, dim3(graphio::PairGrid(n)), dim3(256), 0, stream, ds->d_degrees, ds->d_oro, n, ds->d_counters + 2);
         GR_CHECK(hipGetLastError(), "RowSummaryKernel launch failed");
         Count summary[2] = {0, 0};
         GR_CHECK(hipMemcpyAsync(summary, ds->d_counters + 2, sizeof(summary), hipMemcpyDeviceToHost, stream), "TCProblem read-back failed");
@@ -148,8 +119,7 @@ struct TCProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     {
         hipError_t retval = hipSuccess;
         if ((retval = Base::Init(stream_from_host, graph, num_gpus, false))) return retval;
-        data_slices = new DataSlice *[1];
-        data_slices[0] = new DataSlice();
+        data_slices.Make();
         return Build();
     }
 
@@ -157,8 +127,7 @@ struct TCProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     {
         hipError_t retval = hipSuccess;
         if ((retval = Base::InitFromDevice(nodes, edges, d_row_offsets, d_column_indices))) return retval;
-        data_slices = new DataSlice *[1];
-        data_slices[0] = new DataSlice();
+        data_slices.Make();
         return Build();
     }
 
@@ -202,8 +171,8 @@ struct TCProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         if (transitivity) *transitivity = wedges > 0 ? static_cast<double>(3 * total) / static_cast<double>(wedges) : 0.0;
         if (!h_coeff) return retval;
         const size_t n = static_cast<size_t>(this->nodes);
-        if (!ds->d_coeff) GR_CHECK(hipMalloc(&ds->d_coeff, sizeof(double) * n), "TCProblem hipMalloc d_coeff failed");
-        hipLaunchKernelGGL(ClusteringKernel, dim3(Grid(this->nodes)), dim3(256), 0, stream, ds->d_triangles, ds->d_degrees,
+        if (!ds->d_coeff && (retval = ds->d_coeff.Alloc(n))) return retval;
+        hipLaunchKernelGGL(ClusteringKernel, dim3(graphio::PairGrid(this->nodes)), dim3(256), 0, stream, ds->d_triangles, ds->d_degrees,
                            static_cast<long long>(this->nodes), ds->d_coeff);
         GR_CHECK(hipGetLastError(), "ClusteringKernel launch failed");
         GR_CHECK(hipMemcpyAsync(h_coeff, ds->d_coeff, sizeof(double) * n, hipMemcpyDeviceToHost, stream), "TCProblem read d_coeff failed");

@@ -22,29 +22,28 @@ struct TrussProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     typedef ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> Base;
 
     struct DataSlice {
-        int *d_src = nullptr;      // the canonical edges
-        int *d_dst = nullptr;
-        int *d_nro = nullptr;      // the neighbour CSR, rows ascending,
-        int *d_nci = nullptr;
-        int *d_neid = nullptr;     // and the edge of every entry
-        int *d_support = nullptr;  // triangles per edge
-        int *d_val = nullptr;      // the working array: support, then truss - 2
-        int *d_stamp = nullptr;    // 0: live; else the sub-round in which the edge is in the frontier
-        int *d_truss = nullptr;    // the result of the last Enact
-        int *d_queue = nullptr;    // every edge once, in peeling order
-        int *d_vertex = nullptr;   // `nodes` words: Members' flags, VertexTruss's result
-        unsigned *d_words = nullptr;               // W_* of truss_functor.hpp, and three words behind them for the summaries
-        unsigned long long *d_counters = nullptr;  // [0] entries walked by the peel; [1], [2] Members' counts; [3] the trace's end; [4] the
+        DeviceArray<int> d_src;  // the canonical edges
+        DeviceArray<int> d_dst;
+        DeviceArray<int> d_nro;  // the neighbour CSR, rows ascending,
+        DeviceArray<int> d_nci;
+        DeviceArray<int> d_neid;  // and the edge of every entry
+        DeviceArray<int> d_support;  // triangles per edge
+        DeviceArray<int> d_val;  // the working array: support, then truss - 2
+        DeviceArray<int> d_stamp;  // 0: live; else the sub-round in which the edge is in the frontier
+        DeviceArray<int> d_truss;  // the result of the last Enact
+        DeviceArray<int> d_queue;  // every edge once, in peeling order
+        DeviceArray<int> d_vertex;  // `nodes` words: Members' flags, VertexTruss's result
+        DeviceArray<unsigned> d_words;  // W_* of truss_functor.hpp, and three words behind them for the summaries
+        DeviceArray<unsigned long long> d_counters;  // [0] entries walked by the peel; [1], [2] Members' counts; [3] the trace's end; [4] the
                                                    // support pass's entries; [5] sum(support)
-        int *d_trace_k = nullptr;
-        int *d_trace_tail = nullptr;
-        unsigned long long *d_trace_clock = nullptr;
-        unsigned long long *d_classes = nullptr;  // allocated at the first request
-        unsigned char *d_mask = nullptr;          // allocated at the first request
+        DeviceArray<int> d_trace_k;
+        DeviceArray<int> d_trace_tail;
+        DeviceArray<unsigned long long> d_trace_clock;
+        DeviceArray<unsigned long long> d_classes;  // allocated at the first request
+        DeviceArray<unsigned char> d_mask;  // allocated at the first request
     };
 
-    DataSlice **data_slices = nullptr;
-    int malformed = 0;
+    SliceHolder<DataSlice> data_slices;
     long long simple_edges = 0;  // M
     long long triangles = 0;
     long long max_support = 0;
@@ -58,30 +57,6 @@ struct TrussProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     bool enacted = false;    // truss[] holds a result
     double build_ms = 0;     // HIP-event time of the build of the edges and the neighbour CSR
     double support_ms = 0;   // and of the support pass
-
-    ~TrussProblem() override
-    {
-        if (data_slices) {
-            DataSlice *ds = data_slices[0];
-            if (ds) {
-                void *bufs[] = {ds->d_src, ds->d_dst, ds->d_nro, ds->d_nci, ds->d_neid, ds->d_support, ds->d_val, ds->d_stamp, ds->d_truss,
-                                ds->d_queue, ds->d_vertex, ds->d_words, ds->d_counters, ds->d_trace_k, ds->d_trace_tail, ds->d_trace_clock,
-                                ds->d_classes, ds->d_mask};
-                for (void *b : bufs)
-                    if (b) util::GRError(hipFree(b), "TrussProblem hipFree failed", __FILE__, __LINE__);
-                delete ds;
-            }
-            delete[] data_slices;
-        }
-    }
-
-    static int Grid(long long work)
-    {
-        long long blocks = (work + 255) / 256;
-        if (blocks < 1) blocks = 1;
-        if (blocks > 2048) blocks = 2048;  // 256 CUs x 8 workgroups, grid-stride the rest
-        return static_cast<int>(blocks);
-    }
 
     Graph DeviceGraph() const
     {
@@ -97,42 +72,36 @@ struct TrussProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         hipStream_t stream = gs->stream;
         const long long n = this->nodes, m = this->edges;
         const size_t n1 = static_cast<size_t>(n > 0 ? n : 1);
-        GR_CHECK(hipMalloc(&ds->d_words, sizeof(unsigned) * (W_COUNT + 4)), "TrussProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_counters, sizeof(unsigned long long) * 8), "TrussProblem hipMalloc failed");
+        if ((retval = ds->d_words.Alloc(W_COUNT + 4))) return retval;
+        if ((retval = ds->d_counters.Alloc(8))) return retval;
 
         // the CSR must be one: the build indexes with what it reads
-        bool bad = false;
         GR_CHECK(hipMemsetAsync(ds->d_counters, 0, sizeof(unsigned long long) * 8, stream), "TrussProblem memset failed");
-        if ((retval = graphio::DeviceValidateCsr(gs->d_row_offsets, gs->d_column_indices, n, m, reinterpret_cast<int *>(ds->d_words), stream, &bad)))
-            return retval;
-        if (bad) {
-            malformed = 1;
-            return hipErrorInvalidValue;
-        }
+        if ((retval = this->ValidateCsr())) return retval;
         GR_CHECK(hipMemsetAsync(ds->d_words, 0, sizeof(unsigned) * (W_COUNT + 4), stream), "TrussProblem memset failed");
 
         graphio::BuildEvents ev;
         if ((retval = ev.Create(3))) return retval;
         if ((retval = ev.Record(0, stream))) return retval;
 
-        GR_CHECK(hipMalloc(&ds->d_vertex, sizeof(int) * n1), "TrussProblem hipMalloc d_vertex failed");
+        if ((retval = ds->d_vertex.Alloc(n1))) return retval;
         graphio::PairGraph pg(n);  // steps 1 to 3
         if ((retval = pg.Keys(gs->d_row_offsets, gs->d_column_indices, m, stream))) return retval;
         if ((retval = pg.Pairs(stream))) return retval;
         if ((retval = pg.Rows(stream))) return retval;
-        ds->d_src = graphio::Take(pg.d_src);
-        ds->d_dst = graphio::Take(pg.d_dst);
-        ds->d_nro = graphio::Take(pg.d_ro);
-        ds->d_nci = graphio::Take(pg.d_ci);
-        ds->d_neid = graphio::Take(pg.d_eid);
+        ds->d_src.Adopt(graphio::Take(pg.d_src));
+        ds->d_dst.Adopt(graphio::Take(pg.d_dst));
+        ds->d_nro.Adopt(graphio::Take(pg.d_ro));
+        ds->d_nci.Adopt(graphio::Take(pg.d_ci));
+        ds->d_neid.Adopt(graphio::Take(pg.d_eid));
         const long long M = pg.pairs;
         simple_edges = M;
         const size_t m1 = static_cast<size_t>(M > 0 ? M : 1);
-        GR_CHECK(hipMalloc(&ds->d_support, sizeof(int) * m1), "TrussProblem hipMalloc d_support failed");
-        GR_CHECK(hipMalloc(&ds->d_val, sizeof(int) * m1), "TrussProblem hipMalloc d_val failed");
-        GR_CHECK(hipMalloc(&ds->d_stamp, sizeof(int) * m1), "TrussProblem hipMalloc d_stamp failed");
-        GR_CHECK(hipMalloc(&ds->d_truss, sizeof(int) * m1), "TrussProblem hipMalloc d_truss failed");
-        GR_CHECK(hipMalloc(&ds->d_queue, sizeof(int) * m1), "TrussProblem hipMalloc d_queue failed");
+        if ((retval = ds->d_support.Alloc(m1))) return retval;
+        if ((retval = ds->d_val.Alloc(m1))) return retval;
+        if ((retval = ds->d_stamp.Alloc(m1))) return retval;
+        if ((retval = ds->d_truss.Alloc(m1))) return retval;
+        if ((retval = ds->d_queue.Alloc(m1))) return retval;
         GR_CHECK(hipMemsetAsync(ds->d_support, 0, sizeof(int) * m1, stream), "TrussProblem memset failed");
         GR_CHECK(hipMemsetAsync(ds->d_truss, 0, sizeof(int) * m1, stream), "TrussProblem memset failed");
         if ((retval = ev.Record(1, stream))) return retval;
@@ -141,10 +110,10 @@ struct TrussProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         unsigned *d_out = ds->d_words + W_COUNT;
         GR_CHECK(hipMemcpyAsync(d_out, summary, sizeof(summary), hipMemcpyHostToDevice, stream), "TrussProblem summary init failed");
         if (M > 0) {
-            hipLaunchKernelGGL(SupportKernel, dim3(Grid(M)), dim3(kTrussThreads), 0, stream, DeviceGraph(), M, wave_min_row, ds->d_support,
+            hipLaunchKernelGGL(SupportKernel, dim3(graphio::PairGrid(M)), dim3(kTrussThreads), 0, stream, DeviceGraph(), M, wave_min_row, ds->d_support,
                                ds->d_counters + 4);
             GR_CHECK(hipGetLastError(), "SupportKernel launch failed");
-            hipLaunchKernelGGL(SupportSummaryKernel, dim3(Grid(M)), dim3(256), 0, stream, ds->d_support, M, d_out, ds->d_counters + 5);
+            hipLaunchKernelGGL(SupportSummaryKernel, dim3(graphio::PairGrid(M)), dim3(256), 0, stream, ds->d_support, M, d_out, ds->d_counters + 5);
             GR_CHECK(hipGetLastError(), "SupportSummaryKernel launch failed");
         }
         if ((retval = ev.Record(2, stream))) return retval;
@@ -159,9 +128,9 @@ struct TrussProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         support_entries = static_cast<long long>(sums[0]);
         triangles = static_cast<long long>(sums[1] / 3);
         trace_capacity = max_support + 2;
-        GR_CHECK(hipMalloc(&ds->d_trace_k, sizeof(int) * static_cast<size_t>(trace_capacity)), "TrussProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_trace_tail, sizeof(int) * static_cast<size_t>(trace_capacity)), "TrussProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_trace_clock, sizeof(unsigned long long) * static_cast<size_t>(trace_capacity)), "TrussProblem hipMalloc failed");
+        if ((retval = ds->d_trace_k.Alloc(static_cast<size_t>(trace_capacity)))) return retval;
+        if ((retval = ds->d_trace_tail.Alloc(static_cast<size_t>(trace_capacity)))) return retval;
+        if ((retval = ds->d_trace_clock.Alloc(static_cast<size_t>(trace_capacity)))) return retval;
         return retval;
     }
 
@@ -170,8 +139,7 @@ struct TrussProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     {
         hipError_t retval = hipSuccess;
         if ((retval = Base::Init(stream_from_host, graph, num_gpus, false))) return retval;
-        data_slices = new DataSlice *[1];
-        data_slices[0] = new DataSlice();
+        data_slices.Make();
         return Build();
     }
 
@@ -179,8 +147,7 @@ struct TrussProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     {
         hipError_t retval = hipSuccess;
         if ((retval = Base::InitFromDevice(nodes, edges, d_row_offsets, d_column_indices))) return retval;
-        data_slices = new DataSlice *[1];
-        data_slices[0] = new DataSlice();
+        data_slices.Make();
         return Build();
     }
 
@@ -237,7 +204,7 @@ struct TrussProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         unsigned *d_out = ds->d_words + W_COUNT;
         GR_CHECK(hipMemcpyAsync(d_out, summary, sizeof(summary), hipMemcpyHostToDevice, stream), "TrussProblem summary init failed");
         if (simple_edges > 0) {
-            hipLaunchKernelGGL(SupportSummaryKernel, dim3(Grid(simple_edges)), dim3(256), 0, stream, ds->d_truss, simple_edges, d_out,
+            hipLaunchKernelGGL(SupportSummaryKernel, dim3(graphio::PairGrid(simple_edges)), dim3(256), 0, stream, ds->d_truss, simple_edges, d_out,
                                ds->d_counters + 6);
             GR_CHECK(hipGetLastError(), "SupportSummaryKernel launch failed");
         }
@@ -260,14 +227,12 @@ struct TrussProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         if (count) *count = static_cast<int>(classes);
         if (!h_sizes || max_entries < 1) return retval;
         if (classes > class_capacity) {
-            if (ds->d_classes) GR_CHECK(hipFree(ds->d_classes), "TrussProblem hipFree failed");
-            ds->d_classes = nullptr;
-            GR_CHECK(hipMalloc(&ds->d_classes, sizeof(unsigned long long) * static_cast<size_t>(classes)), "TrussProblem hipMalloc d_classes failed");
+            if ((retval = ds->d_classes.Alloc(static_cast<size_t>(classes)))) return retval;
             class_capacity = classes;
         }
         GR_CHECK(hipMemsetAsync(ds->d_classes, 0, sizeof(unsigned long long) * static_cast<size_t>(classes), stream), "TrussProblem memset failed");
         if (simple_edges > 0) {  // (k-core's kernel: the lanes of a wave that hold the same value add once)
-            hipLaunchKernelGGL(kcore::ShellKernel, dim3(Grid(simple_edges)), dim3(256), 0, stream, ds->d_truss, simple_edges, ds->d_classes);
+            hipLaunchKernelGGL(kcore::ShellKernel, dim3(graphio::PairGrid(simple_edges)), dim3(256), 0, stream, ds->d_truss, simple_edges, ds->d_classes);
             GR_CHECK(hipGetLastError(), "ShellKernel launch failed");
         }
         const long long take = classes < max_entries ? classes : max_entries;
@@ -284,14 +249,14 @@ struct TrussProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         DataSlice *ds = data_slices[0];
         hipStream_t stream = this->graph_slices[0]->stream;
         const size_t M = static_cast<size_t>(simple_edges);
-        if (!ds->d_mask) GR_CHECK(hipMalloc(&ds->d_mask, M > 0 ? M : 1), "TrussProblem hipMalloc d_mask failed");
+        if (!ds->d_mask && (retval = ds->d_mask.Alloc(M > 0 ? M : 1))) return retval;
         GR_CHECK(hipMemsetAsync(ds->d_counters + 1, 0, sizeof(unsigned long long) * 2, stream), "TrussProblem memset failed");
         GR_CHECK(hipMemsetAsync(ds->d_vertex, 0, sizeof(int) * static_cast<size_t>(this->nodes), stream), "TrussProblem memset failed");
         if (M > 0) {
-            hipLaunchKernelGGL(MemberEdgesKernel, dim3(Grid(simple_edges)), dim3(256), 0, stream, DeviceGraph(), ds->d_truss, simple_edges, k,
+            hipLaunchKernelGGL(MemberEdgesKernel, dim3(graphio::PairGrid(simple_edges)), dim3(256), 0, stream, DeviceGraph(), ds->d_truss, simple_edges, k,
                                ds->d_mask, ds->d_vertex, ds->d_counters + 1);
             GR_CHECK(hipGetLastError(), "MemberEdgesKernel launch failed");
-            hipLaunchKernelGGL(CountFlagsKernel, dim3(Grid(this->nodes)), dim3(256), 0, stream, ds->d_vertex, static_cast<long long>(this->nodes),
+            hipLaunchKernelGGL(CountFlagsKernel, dim3(graphio::PairGrid(this->nodes)), dim3(256), 0, stream, ds->d_vertex, static_cast<long long>(this->nodes),
                                ds->d_counters + 2);
             GR_CHECK(hipGetLastError(), "CountFlagsKernel launch failed");
         }
@@ -312,7 +277,7 @@ struct TrussProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         const size_t bytes = sizeof(int) * static_cast<size_t>(this->nodes);
         GR_CHECK(hipMemsetAsync(ds->d_vertex, 0, bytes, stream), "TrussProblem memset failed");
         if (simple_edges > 0) {
-            hipLaunchKernelGGL(VertexTrussKernel, dim3(Grid(simple_edges)), dim3(256), 0, stream, DeviceGraph(), ds->d_truss, simple_edges,
+            hipLaunchKernelGGL(VertexTrussKernel, dim3(graphio::PairGrid(simple_edges)), dim3(256), 0, stream, DeviceGraph(), ds->d_truss, simple_edges,
                                ds->d_vertex);
             GR_CHECK(hipGetLastError(), "VertexTrussKernel launch failed");
         }

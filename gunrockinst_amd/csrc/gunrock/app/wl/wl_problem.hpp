@@ -23,22 +23,21 @@ struct WlProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     typedef ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> Base;
 
     struct DataSlice {
-        int *d_start = nullptr;                  // the labels of the last Reset
-        int *d_colour[3] = {nullptr, nullptr, nullptr};  // c, c' and a refused attempt at c' (the enactor rotates them)
-        Sig *d_sig = nullptr;
-        unsigned long long *d_slot = nullptr;
-        int *d_owner = nullptr;
-        unsigned *d_smallest = nullptr;
-        int *d_waves = nullptr, *d_hubs = nullptr, *d_block_list = nullptr, *d_global_list = nullptr;
-        int *d_dense = nullptr, *d_representative = nullptr;
-        unsigned long long *d_size = nullptr;
-        unsigned long long *d_words = nullptr;
+        DeviceArray<int> d_start;  // the labels of the last Reset
+        DeviceArray<int> d_colour[3];  // c, c' and a refused attempt at c' (the enactor rotates them)
+        DeviceArray<Sig> d_sig;
+        DeviceArray<unsigned long long> d_slot;
+        DeviceArray<int> d_owner;
+        DeviceArray<unsigned> d_smallest;
+        DeviceArray<int> d_waves, d_hubs, d_block_list, d_global_list;
+        DeviceArray<int> d_dense, d_representative;
+        DeviceArray<unsigned long long> d_size;
+        DeviceArray<unsigned long long> d_words;
         Grown<int> history;  // (rounds + 1) x n working colours, when asked for
         Grown<int> rows;     // the GLOBAL rung's counter rows, all 0 between launches
     };
 
-    DataSlice **data_slices = nullptr;
-    int malformed = 0;
+    SliceHolder<DataSlice> data_slices;
     int longest_row = 0;
     unsigned long long table_slots = 0;  // a power of two, at least 2 n
     bool labelled = false;               // the last Reset gave labels
@@ -46,25 +45,6 @@ struct WlProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     int current = 0;                     // d_colour[current] is c
     long long classes = 0;               // of the last Enact
     int history_rounds = -1;             // history[0 .. history_rounds] is kept, or -1
-
-    ~WlProblem() override
-    {
-        if (data_slices) {
-            DataSlice *ds = data_slices[0];
-            if (ds) {
-                void *bufs[] = {ds->d_start, ds->d_colour[0], ds->d_colour[1], ds->d_colour[2], ds->d_sig, ds->d_slot, ds->d_owner, ds->d_smallest, ds->d_waves, ds->d_hubs,
-                                ds->d_block_list, ds->d_global_list, ds->d_dense, ds->d_representative, ds->d_size, ds->d_words};
-                for (void *b : bufs)
-                    if (b) util::GRError(hipFree(b), "WlProblem hipFree failed", __FILE__, __LINE__);
-                ds->history.Free();
-                ds->rows.Free();
-                delete ds;
-            }
-            delete[] data_slices;
-        }
-    }
-
-    static int Grid(long long work) { return graphio::PairGrid(work); }
 
     // the slots of the grouping table of n vertices: the smallest power of two that is at least 2 n (at least 64)
     static unsigned long long TableSlots(long long n)
@@ -80,42 +60,30 @@ struct WlProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         DataSlice *ds = data_slices[0];
         GraphSlice<int, int, int> *gs = this->graph_slices[0];
         hipStream_t stream = gs->stream;
-        const long long n = this->nodes, m = this->edges;
+        const long long n = this->nodes;
         const size_t n1 = static_cast<size_t>(n > 0 ? n : 1);
-        GR_CHECK(hipMalloc(&ds->d_words, sizeof(unsigned long long) * W_COUNT), "WlProblem hipMalloc failed");
+        if ((retval = ds->d_words.Alloc(W_COUNT))) return retval;
         GR_CHECK(hipMemsetAsync(ds->d_words, 0, sizeof(unsigned long long) * W_COUNT, stream), "WlProblem memset failed");
 
-        bool bad = false;
-        if ((retval = graphio::DeviceValidateCsr(gs->d_row_offsets, gs->d_column_indices, n, m, reinterpret_cast<int *>(ds->d_words), stream, &bad)))
-            return retval;
-        if (bad) {
-            malformed = 1;
-            return hipErrorInvalidValue;
-        }
+        if ((retval = this->ValidateCsr())) return retval;
         unsigned long long longest = 0;
         GR_CHECK(hipMemsetAsync(ds->d_words, 0, sizeof(unsigned long long), stream), "WlProblem memset failed");
-        hipLaunchKernelGGL(LongestKernel, dim3(Grid(n)), dim3(256), 0, stream, gs->d_row_offsets, n, ds->d_words);
+        hipLaunchKernelGGL(LongestKernel, dim3(graphio::PairGrid(n)), dim3(256), 0, stream, gs->d_row_offsets, n, ds->d_words);
         GR_CHECK(hipGetLastError(), "LongestKernel launch failed");
         GR_CHECK(hipMemcpyAsync(&longest, ds->d_words, sizeof(longest), hipMemcpyDeviceToHost, stream), "WlProblem read-back failed");
         GR_CHECK(hipStreamSynchronize(stream), "WlProblem build sync failed");
         longest_row = static_cast<int>(longest);
 
         table_slots = TableSlots(n);
-        int **vertex_arrays[] = {&ds->d_start, &ds->d_colour[0], &ds->d_colour[1], &ds->d_colour[2], &ds->d_waves, &ds->d_hubs, &ds->d_block_list, &ds->d_global_list,
+        DeviceArray<int> *vertex_arrays[] = {&ds->d_start, &ds->d_colour[0], &ds->d_colour[1], &ds->d_colour[2], &ds->d_waves, &ds->d_hubs, &ds->d_block_list, &ds->d_global_list,
                                  &ds->d_dense, &ds->d_representative};
-        for (int **a : vertex_arrays) GR_CHECK(hipMalloc(a, sizeof(int) * n1), "WlProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_sig, sizeof(Sig) * n1), "WlProblem hipMalloc d_sig failed");
-        GR_CHECK(hipMalloc(&ds->d_slot, sizeof(unsigned long long) * n1), "WlProblem hipMalloc d_slot failed");
-        GR_CHECK(hipMalloc(&ds->d_size, sizeof(unsigned long long) * n1), "WlProblem hipMalloc d_size failed");
-        GR_CHECK(hipMalloc(&ds->d_owner, sizeof(int) * static_cast<size_t>(table_slots)), "WlProblem hipMalloc d_owner failed");
-        GR_CHECK(hipMalloc(&ds->d_smallest, sizeof(unsigned) * static_cast<size_t>(table_slots)), "WlProblem hipMalloc d_smallest failed");
+        for (DeviceArray<int> *a : vertex_arrays) if ((retval = a->Alloc(n1))) return retval;
+        if ((retval = ds->d_sig.Alloc(n1))) return retval;
+        if ((retval = ds->d_slot.Alloc(n1))) return retval;
+        if ((retval = ds->d_size.Alloc(n1))) return retval;
+        if ((retval = ds->d_owner.Alloc(static_cast<size_t>(table_slots)))) return retval;
+        if ((retval = ds->d_smallest.Alloc(static_cast<size_t>(table_slots)))) return retval;
         return retval;
-    }
-
-    void NewSlice()
-    {
-        data_slices = new DataSlice *[1];
-        data_slices[0] = new DataSlice();
     }
 
     // One Init per object (grx_wl_init refuses a second one)
@@ -123,7 +91,7 @@ struct WlProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     {
         hipError_t retval = hipSuccess;
         if ((retval = Base::Init(stream_from_host, graph, num_gpus, false))) return retval;
-        NewSlice();
+        data_slices.Make();
         return Build();
     }
 
@@ -131,7 +99,7 @@ struct WlProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     {
         hipError_t retval = hipSuccess;
         if ((retval = Base::InitFromDevice(nodes, edges, d_row_offsets, d_column_indices))) return retval;
-        NewSlice();
+        data_slices.Make();
         return Build();
     }
 
@@ -177,11 +145,11 @@ struct WlProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         if ((retval = flag.Alloc(static_cast<size_t>(n)))) return retval;
         if ((retval = rank.Alloc(static_cast<size_t>(n)))) return retval;
         if ((retval = sums.Alloc(static_cast<size_t>(graphio::ScanScratchWords(n))))) return retval;
-        hipLaunchKernelGGL(LeaderFlagKernel, dim3(Grid(n)), dim3(256), 0, stream, colour, n, flag.p);
+        hipLaunchKernelGGL(LeaderFlagKernel, dim3(graphio::PairGrid(n)), dim3(256), 0, stream, colour, n, flag.p);
         GR_CHECK(hipGetLastError(), "LeaderFlagKernel launch failed");
         GR_CHECK(graphio::DeviceExclusiveScan<int>(flag.p, rank.p, n, sums.p, stream), "WlProblem rank scan failed");
         if (full) GR_CHECK(hipMemsetAsync(ds->d_size, 0, sizeof(unsigned long long) * static_cast<size_t>(n), stream), "WlProblem memset failed");
-        hipLaunchKernelGGL(DenseKernel, dim3(Grid(n)), dim3(256), 0, stream, colour, rank.p, n, dense, full ? ds->d_size : nullptr,
+        hipLaunchKernelGGL(DenseKernel, dim3(graphio::PairGrid(n)), dim3(256), 0, stream, colour, rank.p, n, dense, full ? ds->d_size : nullptr,
                            full ? ds->d_representative : nullptr);
         GR_CHECK(hipGetLastError(), "DenseKernel launch failed");
         unsigned long long total = 0;
@@ -193,26 +161,14 @@ struct WlProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
 
     hipError_t Finish() { return Densify(data_slices[0]->d_colour[current], data_slices[0]->d_dense, true, &classes); }
 
-    template <typename T>
-    hipError_t Read(T *h_out, const T *d_in, size_t count)
-    {
-        hipError_t retval = hipSuccess;
-        hipStream_t stream = this->graph_slices[0]->stream;
-        if (h_out && count) {
-            GR_CHECK(hipMemcpyAsync(h_out, d_in, sizeof(T) * count, hipMemcpyDeviceToHost, stream), "WlProblem read failed");
-            GR_CHECK(hipStreamSynchronize(stream), "WlProblem read sync failed");
-        }
-        return retval;
-    }
-
     // every pointer may be NULL
     hipError_t Extract(int *h_colour, long long *h_size, int *h_representative)
     {
         hipError_t retval = hipSuccess;
         DataSlice *ds = data_slices[0];
-        if ((retval = Read(h_colour, ds->d_dense, static_cast<size_t>(this->nodes)))) return retval;
-        if ((retval = Read(reinterpret_cast<unsigned long long *>(h_size), ds->d_size, static_cast<size_t>(classes)))) return retval;
-        return Read(h_representative, ds->d_representative, static_cast<size_t>(classes));
+        if ((retval = this->Read(h_colour, ds->d_dense.p, static_cast<size_t>(this->nodes)))) return retval;
+        if ((retval = this->Read(reinterpret_cast<unsigned long long *>(h_size), ds->d_size.p, static_cast<size_t>(classes)))) return retval;
+        return this->Read(h_representative, ds->d_representative.p, static_cast<size_t>(classes));
     }
 
     // the dense colouring behind round h of the last Enact, h in 0 .. history_rounds (checked by the caller)
@@ -225,7 +181,7 @@ struct WlProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         if ((retval = dense.Alloc(static_cast<size_t>(this->nodes)))) return retval;
         if ((retval = Densify(ds->history.p + static_cast<size_t>(h) * static_cast<size_t>(this->nodes), dense.p, false, &c))) return retval;
         if (count) *count = c;
-        return Read(h_colour, dense.p, static_cast<size_t>(this->nodes));
+        return this->Read(h_colour, dense.p, static_cast<size_t>(this->nodes));
     }
 };
 

@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include <gunrock/graphio/device_sort.hpp>
+#include <gunrock/util/device_array.hpp>
 
 namespace gunrock {
 namespace graphio {
@@ -174,17 +175,7 @@ inline T *Take(T *&p)
 
 // one device array that goes with its scope
 template <typename T>
-struct DeviceScratch {
-    T *p = nullptr;
-    DeviceScratch() = default;
-    DeviceScratch(const DeviceScratch &) = delete;
-    DeviceScratch &operator=(const DeviceScratch &) = delete;
-    ~DeviceScratch()
-    {
-        if (p) util::GRError(hipFree(p), "DeviceScratch hipFree failed", __FILE__, __LINE__);
-    }
-    hipError_t Alloc(size_t count) { return util::GRError(hipMalloc(&p, sizeof(T) * count), "DeviceScratch hipMalloc failed", __FILE__, __LINE__); }
-};
+using DeviceScratch = util::DeviceArray<T>;
 
 // the HIP events of a build that times itself: destroyed on every path out
 struct BuildEvents {

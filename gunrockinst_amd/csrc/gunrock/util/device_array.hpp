@@ -1,0 +1,72 @@
+// util/device_array.hpp -- one device array and its owner.
+//
+// A DeviceArray<T> member says "this object allocated the array and frees it": a scope's scratch (graphio::DeviceScratch is this
+// type), an array that grows (app::Grown holds one) and the long-lived arrays of a problem's DataSlice are all this.  A raw T * beside
+// it is borrowed or points into another array.  It converts to T *, so kernel launches, null tests, pointer arithmetic and copies
+// read as they do with a raw pointer; where a template deduces from it or a cast reinterprets it, take .p.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <gunrock/util/error_utils.hpp>
+
+namespace gunrock {
+namespace util {
+
+struct HipMem {
+    static hipError_t Malloc(void **p, size_t bytes) { return hipMalloc(p, bytes); }
+    static hipError_t Free(void *p) { return hipFree(p); }
+};
+
+// Mem: where the array lives.  Only the host check of this header (tests/host/device_array_check.hip) passes another one.
+template <typename T, typename Mem = HipMem>
+struct DeviceArray {
+    T *p = nullptr;
+
+    DeviceArray() = default;
+    DeviceArray(const DeviceArray &) = delete;
+    DeviceArray &operator=(const DeviceArray &) = delete;
+    DeviceArray(DeviceArray &&other) noexcept : p(other.Release()) {}
+    DeviceArray &operator=(DeviceArray &&other) noexcept
+    {
+        if (this != &other) Adopt(other.Release());
+        return *this;
+    }
+    ~DeviceArray() { Free(); }
+
+    operator T *() const { return p; }
+
+    // what it held goes first; a count of 0 is one element, so that an empty graph's arrays are still arrays
+    hipError_t Alloc(size_t count)
+    {
+        Free();
+        void *raw = nullptr;
+        const hipError_t error = GRError(Mem::Malloc(&raw, sizeof(T) * (count > 0 ? count : 1)), "DeviceArray malloc failed", __FILE__, __LINE__);
+        if (!error) p = static_cast<T *>(raw);
+        return error;
+    }
+
+    // owns an array that another owner gave up (graphio::Take)
+    void Adopt(T *raw)
+    {
+        Free();
+        p = raw;
+    }
+
+    // ... and gives its own up
+    T *Release()
+    {
+        T *raw = p;
+        p = nullptr;
+        return raw;
+    }
+
+    void Free()
+    {
+        if (p) GRError(Mem::Free(p), "DeviceArray free failed", __FILE__, __LINE__);
+        p = nullptr;
+    }
+};
+
+}  // namespace util
+}  // namespace gunrock

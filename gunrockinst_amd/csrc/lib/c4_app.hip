@@ -115,8 +115,8 @@ struct C4RunnerT : C4Runner {
     void DeviceResults(long long **d_cycles, long long **d_edge_cycles, int **d_src, int **d_dst) override
     {
         typename Problem::DataSlice *ds = state.ready ? problem.data_slices[0] : nullptr;
-        if (d_cycles) *d_cycles = ds ? reinterpret_cast<long long *>(ds->d_cycles) : nullptr;
-        if (d_edge_cycles) *d_edge_cycles = ds && finished && enactor.with_edges ? reinterpret_cast<long long *>(ds->d_edge_cycles) : nullptr;
+        if (d_cycles) *d_cycles = ds ? reinterpret_cast<long long *>(ds->d_cycles.p) : nullptr;
+        if (d_edge_cycles) *d_edge_cycles = ds && finished && enactor.with_edges ? reinterpret_cast<long long *>(ds->d_edge_cycles.p) : nullptr;
         if (d_src) *d_src = ds ? ds->d_src : nullptr;
         if (d_dst) *d_dst = ds ? ds->d_dst : nullptr;
     }

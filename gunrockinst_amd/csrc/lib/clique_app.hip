@@ -118,8 +118,8 @@ struct CliqueRunnerT : CliqueRunner {
     }
     void DeviceResults(long long **d_cliques, int **d_degrees) override
     {
-        if (d_cliques) *d_cliques = state.ready ? reinterpret_cast<long long *>(problem.data_slices[0]->d_cliques) : nullptr;
-        if (d_degrees) *d_degrees = state.ready ? reinterpret_cast<int *>(problem.data_slices[0]->d_degrees) : nullptr;
+        if (d_cliques) *d_cliques = state.ready ? reinterpret_cast<long long *>(problem.data_slices[0]->d_cliques.p) : nullptr;
+        if (d_degrees) *d_degrees = state.ready ? reinterpret_cast<int *>(problem.data_slices[0]->d_degrees.p) : nullptr;
     }
 };
 

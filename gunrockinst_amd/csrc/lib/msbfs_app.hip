@@ -142,11 +142,11 @@ struct MsbfsRunnerT : MsbfsRunner {
         const bool have = HasSources();
         typename Problem::DataSlice *ds = have ? problem.data_slices[0] : nullptr;
         if (d_depth) *d_depth = have && problem.store_depths ? ds->d_depth : nullptr;
-        if (d_reached) *d_reached = have ? reinterpret_cast<long long *>(ds->d_reached) : nullptr;
-        if (d_dist_sum) *d_dist_sum = have ? reinterpret_cast<long long *>(ds->d_dist_sum) : nullptr;
+        if (d_reached) *d_reached = have ? reinterpret_cast<long long *>(ds->d_reached.p) : nullptr;
+        if (d_dist_sum) *d_dist_sum = have ? reinterpret_cast<long long *>(ds->d_dist_sum.p) : nullptr;
         if (d_ecc) *d_ecc = have ? ds->d_ecc : nullptr;
         if (d_sources_reaching) *d_sources_reaching = have ? ds->d_sources_reaching : nullptr;
-        if (d_in_dist_sum) *d_in_dist_sum = have ? reinterpret_cast<long long *>(ds->d_in_dist_sum) : nullptr;
+        if (d_in_dist_sum) *d_in_dist_sum = have ? reinterpret_cast<long long *>(ds->d_in_dist_sum.p) : nullptr;
     }
 };
 

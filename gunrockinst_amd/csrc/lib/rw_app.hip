@@ -102,7 +102,7 @@ struct RwRunnerT : RwRunner {
         typename Problem::DataSlice *ds = state.ready && finished ? problem.data_slices[0] : nullptr;
         if (d_walks) *d_walks = ds ? ds->d_walks : nullptr;
         if (d_lengths) *d_lengths = ds ? ds->d_lengths : nullptr;
-        if (d_visits) *d_visits = ds && enactor.with_visits ? reinterpret_cast<long long *>(ds->d_visits) : nullptr;
+        if (d_visits) *d_visits = ds && enactor.with_visits ? reinterpret_cast<long long *>(ds->d_visits.p) : nullptr;
         if (pitch) *pitch = ds ? problem.pitch : 0;
     }
 };

@@ -105,8 +105,8 @@ struct TcRunnerT : TcRunner {
     }
     void DeviceResults(long long **d_triangles, int **d_degrees) override
     {
-        if (d_triangles) *d_triangles = state.ready ? reinterpret_cast<long long *>(problem.data_slices[0]->d_triangles) : nullptr;
-        if (d_degrees) *d_degrees = state.ready ? reinterpret_cast<int *>(problem.data_slices[0]->d_degrees) : nullptr;
+        if (d_triangles) *d_triangles = state.ready ? reinterpret_cast<long long *>(problem.data_slices[0]->d_triangles.p) : nullptr;
+        if (d_degrees) *d_degrees = state.ready ? reinterpret_cast<int *>(problem.data_slices[0]->d_degrees.p) : nullptr;
     }
 };
 

@@ -1,0 +1,26 @@
+"""csrc/gunrock/util/device_array.hpp and the slice holder of csrc/gunrock/app/problem_base.hpp on the host:
+tests/host/device_array_check.hip runs every way an owning array takes, gives up and frees a block -- scope exit, a second Alloc,
+Alloc(0), a move, Adopt of a taken array, Release, Free twice, a slice built only in part, a holder made or never made -- over a
+counting malloc / free, as a stand-alone program built with the address and undefined-behaviour sanitizers on the host side, so a
+leak, a double free or a use after one ends the program with a report.  No GPU."""
+import os
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+SANITIZE = "-fsanitize=address,undefined"
+
+
+def test_owning_arrays_under_sanitizers(tmp_path):
+    exe = str(tmp_path / "device_array_check")
+    build = subprocess.run([HIPCC, "-O1", "-g", "-std=c++17", "--offload-arch=gfx950", "-Wall", "-Xarch_host", SANITIZE,
+                            "-Xarch_host", "-fno-sanitize-recover=undefined", "-Xarch_host", "-fno-omit-frame-pointer",
+                            "-I", os.path.join(ROOT, "gunrockinst_amd", "csrc"), "-I", os.path.join(ROOT, "include"),
+                            os.path.join(ROOT, "tests", "host", "device_array_check.hip"), SANITIZE, "-o", exe],
+                           capture_output=True, text=True, timeout=600)
+    assert build.returncode == 0, build.stderr
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert "device_array host checks passed" in run.stdout
+    assert "ERROR: AddressSanitizer" not in run.stderr and "ERROR: LeakSanitizer" not in run.stderr and "runtime error" not in run.stderr, run.stderr
