@@ -58,47 +58,39 @@ struct BCProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
         VertexId src_node = -1;
         VertexId iteration = 0;         // level of the frontier being expanded
     };
+    static_assert(std::is_trivially_copyable<DataSlice>::value,
+                  "the DataSlice is copied into kernel arguments and functors: views only, the owners sit in the problem");
 
-    DataSlice **data_slices = nullptr;
+    SliceHolder<DataSlice> data_slices;
+    // what the slice views, under the slice's names
+    DeviceArray<VertexId> d_labels;
+    DeviceArray<Value> d_sigmas, d_deltas, d_bc_values, d_ebc_values;
+    DeviceArray<int2> d_packed;
     SizeT src_row[2] = {0, 0};
     // path-count overflow: one word of pinned + mapped host memory that BCEnactor clears before a search and its PackTermsKernel
     // sets when a labelled vertex has a sigma above 2^126 (inf, NaN, or a count whose reciprocal is subnormal).  Only an overflowing
     // search stores to it; the synchronisation that ends Enact makes the store readable.
-    int *h_overflow = nullptr;
-
-    ~BCProblem() override
-    {
-        if (data_slices) {
-            DataSlice *ds = data_slices[0];
-            if (ds) {
-                if (ds->d_labels) hipFree(ds->d_labels);
-                if (ds->d_sigmas) hipFree(ds->d_sigmas);
-                if (ds->d_deltas) hipFree(ds->d_deltas);
-                if (ds->d_packed) hipFree(ds->d_packed);
-                if (ds->d_bc_values) hipFree(ds->d_bc_values);
-                if (ds->d_ebc_values) hipFree(ds->d_ebc_values);
-                delete ds;
-            }
-            delete[] data_slices;
-        }
-        if (h_overflow) hipHostFree(h_overflow);
-    }
+    util::PinnedArray<int, hipHostMallocMapped> h_overflow;
 
     hipError_t AllocData()
     {
         hipError_t retval = hipSuccess;
-        data_slices = new DataSlice *[1];
-        data_slices[0] = new DataSlice();
-        DataSlice *ds = data_slices[0];
+        DataSlice *ds = data_slices.Make();
         const size_t n = static_cast<size_t>(this->nodes > 0 ? this->nodes : 1);
         const size_t m = static_cast<size_t>(this->edges > 0 ? this->edges : 1);
-        GR_CHECK(hipMalloc(&ds->d_labels, sizeof(VertexId) * n), "BCProblem hipMalloc d_labels failed");
-        GR_CHECK(hipMalloc(&ds->d_sigmas, sizeof(Value) * n), "BCProblem hipMalloc d_sigmas failed");
-        GR_CHECK(hipMalloc(&ds->d_deltas, sizeof(Value) * n), "BCProblem hipMalloc d_deltas failed");
-        GR_CHECK(hipMalloc(&ds->d_packed, sizeof(int2) * n), "BCProblem hipMalloc d_packed failed");
-        GR_CHECK(hipMalloc(&ds->d_bc_values, sizeof(Value) * n), "BCProblem hipMalloc d_bc_values failed");
-        GR_CHECK(hipMalloc(&ds->d_ebc_values, sizeof(Value) * m), "BCProblem hipMalloc d_ebc_values failed");
-        GR_CHECK(hipHostMalloc(reinterpret_cast<void **>(&h_overflow), sizeof(int), hipHostMallocMapped), "BCProblem hipHostMalloc failed");
+        GR_CHECK(d_labels.Alloc(n), "BCProblem d_labels failed");
+        GR_CHECK(d_sigmas.Alloc(n), "BCProblem d_sigmas failed");
+        GR_CHECK(d_deltas.Alloc(n), "BCProblem d_deltas failed");
+        GR_CHECK(d_packed.Alloc(n), "BCProblem d_packed failed");
+        GR_CHECK(d_bc_values.Alloc(n), "BCProblem d_bc_values failed");
+        GR_CHECK(d_ebc_values.Alloc(m), "BCProblem d_ebc_values failed");
+        ds->d_labels = d_labels;
+        ds->d_sigmas = d_sigmas;
+        ds->d_deltas = d_deltas;
+        ds->d_packed = d_packed;
+        ds->d_bc_values = d_bc_values;
+        ds->d_ebc_values = d_ebc_values;
+        GR_CHECK(h_overflow.Alloc(1), "BCProblem overflow word failed");
         *h_overflow = 0;
         GR_CHECK(hipMemset(ds->d_bc_values, 0, sizeof(Value) * n), "BCProblem hipMemset failed");
         GR_CHECK(hipMemset(ds->d_ebc_values, 0, sizeof(Value) * m), "BCProblem hipMemset failed");

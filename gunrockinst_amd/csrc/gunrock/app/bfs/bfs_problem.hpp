@@ -19,6 +19,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include <gunrock/app/problem_base.hpp>
 #include <gunrock/graphio/device_csr.hpp>
 #include <gunrock/graphio/relabel.hpp>
@@ -556,19 +558,16 @@ struct SearchGraph {
     VertexId *d_column_indices = nullptr;
     const SizeT *d_inv_row_offsets = nullptr;  // in-neighbour CSR (borrowed)
     const VertexId *d_inv_column_indices = nullptr;
-    unsigned *d_never_mask = nullptr;  // bit v = v has no in-edge
-    unsigned *d_head_base = nullptr;   // vertices with in-edges before each 64-vertex word
-    int2 *d_inv_heads = nullptr;       // first two in-neighbours of every vertex with in-edges
+    DeviceArray<unsigned> d_never_mask;  // bit v = v has no in-edge
+    DeviceArray<unsigned> d_head_base;   // vertices with in-edges before each 64-vertex word
+    DeviceArray<int2> d_inv_heads;       // first two in-neighbours of every vertex with in-edges
     long long with_in_edges = 0;
 
     void Release()
     {
-        if (d_never_mask) util::GRError(hipFree(d_never_mask), "SearchGraph hipFree d_never_mask failed", __FILE__, __LINE__);
-        if (d_head_base) util::GRError(hipFree(d_head_base), "SearchGraph hipFree d_head_base failed", __FILE__, __LINE__);
-        if (d_inv_heads) util::GRError(hipFree(d_inv_heads), "SearchGraph hipFree d_inv_heads failed", __FILE__, __LINE__);
-        d_never_mask = nullptr;
-        d_head_base = nullptr;
-        d_inv_heads = nullptr;
+        d_never_mask.Free();
+        d_head_base.Free();
+        d_inv_heads.Free();
     }
 
     // fill the static state from the in-neighbour CSR (synchronous); mask_words: 32-bit words of a vertex bitmap
@@ -577,25 +576,22 @@ struct SearchGraph {
         hipError_t retval = hipSuccess;
         // Bit v set when v has no in-edge.  Reset preloads the visited bitmap with it, so the bottom-up sweep skips those
         // vertices (half of an R-MAT graph) without touching their row offsets, 64 at a time.
-        if (!d_never_mask)
-            GR_CHECK(hipMalloc(&d_never_mask, sizeof(unsigned) * static_cast<size_t>(mask_words + 2)), "SearchGraph hipMalloc d_never_mask failed");
-        if (!d_inv_heads)
-            GR_CHECK(hipMalloc(&d_inv_heads, sizeof(int2) * static_cast<size_t>(nodes > 0 ? nodes : 1)), "SearchGraph hipMalloc d_inv_heads failed");
+        if (!d_never_mask) GR_CHECK(d_never_mask.Alloc(static_cast<size_t>(mask_words + 2)), "SearchGraph d_never_mask failed");
+        if (!d_inv_heads) GR_CHECK(d_inv_heads.Alloc(static_cast<size_t>(nodes)), "SearchGraph d_inv_heads failed");
         const long long words64 = mask_words / 2 + 1;
         long long grid = (words64 + 3) / 4;
         if (grid > 2048) grid = 2048;
         hipLaunchKernelGGL((NoInEdgeMaskKernel<SizeT>), dim3(static_cast<unsigned>(grid)), dim3(256), 0, stream, d_inv_row_offsets, nodes, words64,
-                           reinterpret_cast<unsigned long long *>(d_never_mask));
+                           reinterpret_cast<unsigned long long *>(d_never_mask.p));
         GR_CHECK(hipGetLastError(), "NoInEdgeMaskKernel launch failed");
         // heads are stored only for vertices that have in-edges: d_head_base[w] = such vertices before word w
-        if (!d_head_base)
-            GR_CHECK(hipMalloc(&d_head_base, sizeof(unsigned) * static_cast<size_t>(words64 + 1)), "SearchGraph hipMalloc d_head_base failed");
-        unsigned *d_counts = nullptr;
-        unsigned long long *d_scan_sums = nullptr;
-        GR_CHECK(hipMalloc(&d_counts, sizeof(unsigned) * static_cast<size_t>(words64 + 1)), "SearchGraph hipMalloc failed");
-        GR_CHECK(hipMalloc(&d_scan_sums, sizeof(unsigned long long) * static_cast<size_t>(graphio::ScanScratchWords(words64))), "SearchGraph hipMalloc failed");
+        if (!d_head_base) GR_CHECK(d_head_base.Alloc(static_cast<size_t>(words64 + 1)), "SearchGraph d_head_base failed");
+        DeviceArray<unsigned> d_counts;
+        DeviceArray<unsigned long long> d_scan_sums;
+        GR_CHECK(d_counts.Alloc(static_cast<size_t>(words64 + 1)), "SearchGraph scratch failed");
+        GR_CHECK(d_scan_sums.Alloc(static_cast<size_t>(graphio::ScanScratchWords(words64))), "SearchGraph scratch failed");
         hipLaunchKernelGGL(WithInEdgesCountKernel, dim3(static_cast<unsigned>((words64 + 255) / 256)), dim3(256), 0, stream,
-                           reinterpret_cast<const unsigned long long *>(d_never_mask), nodes, words64, d_counts);
+                           reinterpret_cast<const unsigned long long *>(d_never_mask.p), nodes, words64, d_counts);
         GR_CHECK(hipGetLastError(), "WithInEdgesCountKernel launch failed");
         GR_CHECK(graphio::DeviceExclusiveScan<unsigned>(d_counts, d_head_base, words64, d_scan_sums, stream), "SearchGraph head-base scan failed");
         GR_CHECK(hipStreamSynchronize(stream), "NoInEdgeMaskKernel failed");
@@ -605,14 +601,14 @@ struct SearchGraph {
             GR_CHECK(hipMemcpy(&last_count, d_counts + (words64 - 1), sizeof(unsigned), hipMemcpyDeviceToHost), "SearchGraph read failed");
             with_in_edges = static_cast<long long>(last_base) + last_count;
         }
-        GR_CHECK(hipFree(d_counts), "SearchGraph hipFree failed");
-        GR_CHECK(hipFree(d_scan_sums), "SearchGraph hipFree failed");
+        d_counts.Free();
+        d_scan_sums.Free();
         if (nodes > 0) {
             long long hgrid = (nodes + 3) / 4;  // one wave per vertex
             if (hgrid > 8192) hgrid = 8192;
             hipLaunchKernelGGL((oprtr::advance::BuildHeadsKernel<VertexId, SizeT>), dim3(static_cast<unsigned>(hgrid)), dim3(256), 0, stream,
                                d_inv_row_offsets, d_inv_column_indices, nodes, d_inv_heads, d_inv_row_offsets,
-                               reinterpret_cast<const unsigned long long *>(d_never_mask), d_head_base);
+                               reinterpret_cast<const unsigned long long *>(d_never_mask.p), d_head_base);
             GR_CHECK(hipGetLastError(), "BuildHeadsKernel launch failed");
             GR_CHECK(hipStreamSynchronize(stream), "BuildHeadsKernel failed");
         }
@@ -647,6 +643,8 @@ struct BFSProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
         const SizeT *d_inv_row_offsets = nullptr;           // in-neighbour CSR (CSC of the graph)
         const VertexId *d_inv_column_indices = nullptr;
     };
+    static_assert(std::is_trivially_copyable<DataSlice>::value,
+                  "the DataSlice is a kernel argument and is repointed between numberings: views only, the owners sit in the problem");
 
     // direction-optimizing switches, names from the reference's DOBFS driver (tests/dobfs/test_dobfs.cu:530-534)
     bool direction_optimizing = false;
@@ -696,35 +694,11 @@ struct BFSProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
     int persistent_edge_limit = 1 << 20;  // ... and up to this many inside the persistent multi-workgroup kernel (0 = off)
     int tail_edge_limit = 8192;  // levels with at most this many edge slots run inside the single-workgroup tail kernel
 
-    DataSlice **data_slices = nullptr;  // host copies (by-value kernel arguments), one per GPU
+    SliceHolder<DataSlice> data_slices;   // host copy (a by-value kernel argument)
     DataSlice **d_data_slices = nullptr;  // kept for source compatibility; unused (no device-side struct)
-
-    BFSProblem() {}
-
-    ~BFSProblem() override
-    {
-        if (data_slices && active != 0) UseNumbering(0);  // (the graph slice frees the caller's CSR when it owns it)
-        if (data_slices) {
-            DataSlice *ds = data_slices[0];
-            if (ds) {
-                if (d_out_labels) util::GRError(hipFree(d_out_labels), "BFSProblem hipFree d_labels failed", __FILE__, __LINE__);
-                if (d_out_preds) util::GRError(hipFree(d_out_preds), "BFSProblem hipFree d_preds failed", __FILE__, __LINE__);
-                if (d_work_labels) util::GRError(hipFree(d_work_labels), "BFSProblem hipFree work labels failed", __FILE__, __LINE__);
-                if (d_work_preds) util::GRError(hipFree(d_work_preds), "BFSProblem hipFree work preds failed", __FILE__, __LINE__);
-                if (ds->d_visited_mask) util::GRError(hipFree(ds->d_visited_mask), "BFSProblem hipFree d_visited_mask failed", __FILE__, __LINE__);
-                for (int i = 0; i < kLevelMasks; ++i)
-                    if (ds->d_frontier_mask[i]) util::GRError(hipFree(ds->d_frontier_mask[i]), "BFSProblem hipFree d_frontier_mask failed", __FILE__, __LINE__);
-                if (ds->d_snapshot) util::GRError(hipFree(ds->d_snapshot), "BFSProblem hipFree d_snapshot failed", __FILE__, __LINE__);
-                if (ds->d_fresh) util::GRError(hipFree(ds->d_fresh), "BFSProblem hipFree d_fresh failed", __FILE__, __LINE__);
-                delete ds;
-            }
-            delete[] data_slices;
-        }
-        for (int k = 0; k < 2; ++k) numbering[k].Release();
-        relabelled.Release();
-        if (h_src_box) util::GRError(hipHostFree(h_src_box), "BFSProblem hipHostFree failed", __FILE__, __LINE__);
-        bin_pool.Release();
-    }
+    // what the slice views, under the slice's names (d_labels and d_preds view d_out_* or d_work_* below)
+    DeviceArray<unsigned> d_visited_mask, d_frontier_mask[kLevelMasks], d_snapshot;
+    DeviceArray<unsigned char> d_fresh;
 
     // bitmaps are sized in whole 64-bit words: one wave owns one word in the bottom-up sweep
     SizeT MaskWords() const { return ((this->nodes + 63) / 64) * 2; }
@@ -758,8 +732,8 @@ struct BFSProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
     int active = 0;                   // state: numbering of the running search
     bool translate_pending = false;   // state: a non-deferred search on the copy still owes its caller-order pass
     VertexId caller_source = -1;      // the source in the caller's numbering (`source` is in the active one)
-    VertexId *d_out_labels = nullptr, *d_out_preds = nullptr;    // results, caller order
-    VertexId *d_work_labels = nullptr, *d_work_preds = nullptr;  // the copy's numbering (allocated with the copy)
+    DeviceArray<VertexId> d_out_labels, d_out_preds;    // results, caller order
+    DeviceArray<VertexId> d_work_labels, d_work_preds;  // the copy's numbering (allocated with the copy)
 
     // (re)build the relabelled copy of a symmetric problem with at most `hubs` vertices in the hub tier
     hipError_t BuildRelabelled(long long hubs)
@@ -779,9 +753,9 @@ struct BFSProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
         numbering[1].d_inv_row_offsets = relabelled.d_row_offsets;
         numbering[1].d_inv_column_indices = relabelled.d_cols;
         GR_CHECK(numbering[1].Build(this->nodes, MaskWords(), stream), "BFSProblem relabelled static state failed");
-        const size_t n = static_cast<size_t>(this->nodes > 0 ? this->nodes : 1);
-        if (!d_work_labels) GR_CHECK(hipMalloc(&d_work_labels, sizeof(VertexId) * n), "BFSProblem hipMalloc work labels failed");
-        if (MARK_PREDECESSORS && !d_work_preds) GR_CHECK(hipMalloc(&d_work_preds, sizeof(VertexId) * n), "BFSProblem hipMalloc work preds failed");
+        const size_t n = static_cast<size_t>(this->nodes);
+        if (!d_work_labels) GR_CHECK(d_work_labels.Alloc(n), "BFSProblem work labels failed");
+        if (MARK_PREDECESSORS && !d_work_preds) GR_CHECK(d_work_preds.Alloc(n), "BFSProblem work preds failed");
         relabel_hubs = hubs;
         return retval;
     }
@@ -826,18 +800,12 @@ struct BFSProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
         numbering[0].d_column_indices = this->graph_slices[0]->d_column_indices;
         numbering[0].d_inv_row_offsets = d_inv_row_offsets;
         numbering[0].d_inv_column_indices = d_inv_column_indices;
-        for (int i = 0; i < kLevelMasks; ++i)
-            if (!ds->d_frontier_mask[i])
-                GR_CHECK(hipMalloc(&ds->d_frontier_mask[i], sizeof(unsigned) * static_cast<size_t>(MaskWords() + 2)),
-                         "BFSProblem hipMalloc d_frontier_mask failed");
-        if (!ds->d_snapshot)
-            GR_CHECK(hipMalloc(&ds->d_snapshot, sizeof(unsigned) * static_cast<size_t>(MaskWords() + 2)), "BFSProblem hipMalloc d_snapshot failed");
-        if (!ds->d_fresh) {
-            const size_t bytes = (static_cast<size_t>(this->nodes) + 1023) / 1024 * 1024 + 1024;  // FreshToBitmapKernel reads 1 KiB steps
-            GR_CHECK(hipMalloc(&ds->d_fresh, bytes), "BFSProblem hipMalloc d_fresh failed");
-            GR_CHECK(hipMemset(ds->d_fresh, 0, bytes), "BFSProblem hipMemset d_fresh failed");  // levels leave it zero again
-            GR_CHECK(hipDeviceSynchronize(), "BFSProblem sync failed");  // (null-stream memset: the problem's stream is not ordered behind it)
+        for (int i = 0; i < kLevelMasks; ++i) GR_CHECK(EnsureMask(i), "BFSProblem d_frontier_mask failed");
+        if (!ds->d_snapshot) {
+            GR_CHECK(d_snapshot.Alloc(static_cast<size_t>(MaskWords() + 2)), "BFSProblem d_snapshot failed");
+            ds->d_snapshot = d_snapshot;
         }
+        GR_CHECK(EnsureFresh(), "BFSProblem d_fresh failed");
         GR_CHECK(numbering[0].Build(static_cast<long long>(this->nodes), MaskWords(), this->graph_slices[0]->stream),
                  "BFSProblem static search state failed");
         UseNumbering(0);
@@ -847,24 +815,39 @@ struct BFSProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
         direction_optimizing = true;
         return retval;
     }
+    // bitmap i of the pool, allocated at the first request
+    hipError_t EnsureMask(int i)
+    {
+        hipError_t retval = hipSuccess;
+        DataSlice *ds = data_slices[0];
+        if (ds->d_frontier_mask[i]) return retval;
+        if ((retval = d_frontier_mask[i].Alloc(static_cast<size_t>(MaskWords() + 2)))) return retval;
+        ds->d_frontier_mask[i] = d_frontier_mask[i];
+        return retval;
+    }
+    // ... and the flag bytes of the count-only and binned levels, all zero from here on
+    hipError_t EnsureFresh()
+    {
+        hipError_t retval = hipSuccess;
+        DataSlice *ds = data_slices[0];
+        if (ds->d_fresh) return retval;
+        const size_t bytes = (static_cast<size_t>(this->nodes) + 1023) / 1024 * 1024 + 1024;  // FreshToBitmapKernel reads 1 KiB steps
+        if ((retval = d_fresh.Alloc(bytes))) return retval;
+        GR_CHECK(hipMemset(d_fresh, 0, bytes), "BFSProblem hipMemset d_fresh failed");  // levels leave it zero again
+        GR_CHECK(hipDeviceSynchronize(), "BFSProblem sync failed");  // (null-stream memset: the problem's stream is not ordered behind it)
+        ds->d_fresh = d_fresh;
+        return retval;
+    }
     // Scratch of the binned advance: the chunk pool (sized for a level that hands over every edge of the graph from
     // `workgroups` workgroups), the flag bytes and the bitmap its closing sweep writes.  Allocated on first use.
     hipError_t EnsureBinned(int workgroups, int *d_overflow)
     {
         hipError_t retval = hipSuccess;
-        DataSlice *ds = data_slices[0];
         if (!bin_pool.Ready() || bin_pool.workgroups < workgroups)
             GR_CHECK(bin_pool.Allocate(static_cast<long long>(this->edges), workgroups, MARK_PREDECESSORS, d_overflow),
                      "BFSProblem bin pool allocation failed");
-        if (!ds->d_fresh) {
-            const size_t bytes = (static_cast<size_t>(this->nodes) + 1023) / 1024 * 1024 + 1024;  // FreshToBitmapKernel reads 1 KiB steps
-            GR_CHECK(hipMalloc(&ds->d_fresh, bytes), "BFSProblem hipMalloc d_fresh failed");
-            GR_CHECK(hipMemset(ds->d_fresh, 0, bytes), "BFSProblem hipMemset d_fresh failed");  // levels leave it zero again
-            GR_CHECK(hipDeviceSynchronize(), "BFSProblem sync failed");  // (null-stream memset: the problem's stream is not ordered behind it)
-        }
-        if (!ds->d_frontier_mask[0])
-            GR_CHECK(hipMalloc(&ds->d_frontier_mask[0], sizeof(unsigned) * static_cast<size_t>(MaskWords() + 2)),
-                     "BFSProblem hipMalloc d_frontier_mask failed");
+        GR_CHECK(EnsureFresh(), "BFSProblem d_fresh failed");
+        GR_CHECK(EnsureMask(0), "BFSProblem d_frontier_mask failed");
         return retval;
     }
 
@@ -889,17 +872,18 @@ struct BFSProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
     hipError_t AllocData()
     {
         hipError_t retval = hipSuccess;
-        data_slices = new DataSlice *[1];
-        data_slices[0] = new DataSlice();
-        DataSlice *ds = data_slices[0];
-        const size_t n = static_cast<size_t>(this->nodes > 0 ? this->nodes : 1);
-        GR_CHECK(hipMalloc(&ds->d_labels, sizeof(VertexId) * n), "BFSProblem hipMalloc d_labels failed");
-        if (MARK_PREDECESSORS)
-            GR_CHECK(hipMalloc(&ds->d_preds, sizeof(VertexId) * n), "BFSProblem hipMalloc d_preds failed");
-        d_out_labels = ds->d_labels;
-        d_out_preds = ds->d_preds;
-        GR_CHECK(hipMalloc(&ds->d_visited_mask, sizeof(unsigned) * static_cast<size_t>(MaskWords() + 2)),
-                 "BFSProblem hipMalloc d_visited_mask failed");
+        DataSlice *ds = data_slices.Make();
+        // (a second Init: the new slice views nothing yet, so what the first one viewed goes)
+        for (int i = 0; i < kLevelMasks; ++i) d_frontier_mask[i].Free();
+        d_snapshot.Free();
+        d_fresh.Free();
+        const size_t n = static_cast<size_t>(this->nodes);
+        GR_CHECK(d_out_labels.Alloc(n), "BFSProblem d_labels failed");
+        if (MARK_PREDECESSORS) GR_CHECK(d_out_preds.Alloc(n), "BFSProblem d_preds failed");
+        ds->d_labels = d_out_labels;
+        ds->d_preds = d_out_preds;
+        GR_CHECK(d_visited_mask.Alloc(static_cast<size_t>(MaskWords() + 2)), "BFSProblem d_visited_mask failed");
+        ds->d_visited_mask = d_visited_mask;
         return retval;
     }
 
@@ -927,7 +911,7 @@ struct BFSProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
         DataSlice *ds = data_slices[0];
         hipStream_t stream = gs->stream;
         if (!h_src_box) {
-            GR_CHECK(hipHostMalloc(reinterpret_cast<void **>(&h_src_box), sizeof(SourceBox), hipHostMallocMapped), "BFSProblem hipHostMalloc failed");
+            GR_CHECK(h_src_box.Alloc(1), "BFSProblem source box failed");
             h_src_box->seq = 0;
         }
         // the numbering of this search: the relabelled copy while `relabel` is on and the copy exists
@@ -1209,7 +1193,7 @@ struct BFSProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
         unsigned long long seq;
         SizeT row[2];
     };
-    SourceBox *h_src_box = nullptr;  // pinned + mapped: written by BfsResetKernel
+    util::PinnedArray<SourceBox, hipHostMallocMapped> h_src_box;  // pinned + mapped: written by BfsResetKernel
     unsigned long long reset_seq = 0;
     bool src_row_pending = false;
 };

@@ -88,7 +88,7 @@ class CCEnactor : public EnactorBase {
         // something clears its flag; poll() is the read-back kernel, which mirrors the word to pinned memory and sets it back
         // to all ones for the next sweep -- no copy up, no copy down, no stream synchronisation per sweep.
         typename CCProblem::DataSlice slice = *ds;
-        slice.d_vertex_flag = reinterpret_cast<int *>(work_progress.d_tail);
+        slice.d_vertex_flag = reinterpret_cast<int *>(work_progress.d_tail.p);
         slice.d_edge_flag = slice.d_vertex_flag + 1;
         if ((retval = work_progress.Reset(stream))) return retval;
         GR_CHECK(hipMemsetAsync(work_progress.d_tail, 0xFF, sizeof(unsigned long long), stream), "CCEnactor arm flags failed");

@@ -16,6 +16,7 @@
 
 #include <cstdlib>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include <gunrock/app/problem_base.hpp>
@@ -203,58 +204,49 @@ struct CCProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
         int *d_vertex_flag = nullptr;         // cleared by a pointer-jump sweep that changed something
         int *d_edge_flag = nullptr;           // cleared by a hook sweep that hooked something
     };
+    static_assert(std::is_trivially_copyable<DataSlice>::value,
+                  "the DataSlice is copied into kernel arguments and functors: views only, the owners sit in the problem");
 
-    DataSlice **data_slices = nullptr;
+    SliceHolder<DataSlice> data_slices;
+    // what the slice views, under the slice's names (d_tos and d_low_offsets: the compact layout only; d_tos otherwise aliases the
+    // CSR's columns)
+    DeviceArray<_VertexId> d_component_ids, d_froms, d_tos, d_first_lower;
+    DeviceArray<int> d_masks, d_vertex_flag;
+    DeviceArray<unsigned char> d_marks;
+    DeviceArray<_SizeT> d_low_offsets;
     unsigned int num_components = 0;
-    int *h_flags = nullptr;  // pinned: [0] vertex flag, [1] edge flag
+    util::PinnedArray<int> h_flags;  // pinned: [0] vertex flag, [1] edge flag
     // edges the hooking sweeps run over: all of them, or -- mirrored input -- the from > to orientation only (AllocData)
     _SizeT sweep_edges = 0;
     bool compact_mirrored = true;      // policy (tests switch it off to run the parking path)
     bool row_form = true;              // policy: hooking sweeps in row form when a sampled component dominates (cc_functor.hpp)
-    _VertexId *d_owned_first = nullptr;
-    _SizeT *d_owned_low_offsets = nullptr;
     int neighbour_rounds = 1;          // policy: neighbour rounds in front of the row-form sweeps (0: first hooking sweep in edge form).
                                        // Scale-24 R-MAT, whole CC: 0 -> 1.51 ms, 1 -> 0.84, 2 -> 1.11, 3 -> 1.38 (a round costs ~0.3 ms:
                                        // 16 M random parent gathers and the jumps; the second one no longer shortens what follows)
-    _VertexId *d_owned_tos = nullptr;  // the compact `to` array when the problem owns one (d_tos otherwise aliases the CSR's columns)
-
-    ~CCProblem() override
-    {
-        if (data_slices) {
-            DataSlice *ds = data_slices[0];
-            if (ds) {
-                if (ds->d_component_ids) util::GRError(hipFree(ds->d_component_ids), "CCProblem hipFree failed", __FILE__, __LINE__);
-                if (ds->d_masks) util::GRError(hipFree(ds->d_masks), "CCProblem hipFree failed", __FILE__, __LINE__);
-                if (ds->d_marks) util::GRError(hipFree(ds->d_marks), "CCProblem hipFree failed", __FILE__, __LINE__);
-                if (ds->d_froms) util::GRError(hipFree(ds->d_froms), "CCProblem hipFree failed", __FILE__, __LINE__);
-                if (ds->d_vertex_flag) util::GRError(hipFree(ds->d_vertex_flag), "CCProblem hipFree failed", __FILE__, __LINE__);
-                delete ds;
-            }
-            delete[] data_slices;
-        }
-        if (h_flags) util::GRError(hipHostFree(h_flags), "CCProblem hipHostFree failed", __FILE__, __LINE__);
-        if (d_owned_tos) util::GRError(hipFree(d_owned_tos), "CCProblem hipFree failed", __FILE__, __LINE__);
-        if (d_owned_first) util::GRError(hipFree(d_owned_first), "CCProblem hipFree failed", __FILE__, __LINE__);
-        if (d_owned_low_offsets) util::GRError(hipFree(d_owned_low_offsets), "CCProblem hipFree failed", __FILE__, __LINE__);
-    }
 
     hipError_t AllocData()
     {
         hipError_t retval = hipSuccess;
-        data_slices = new DataSlice *[1];
-        data_slices[0] = new DataSlice();
-        DataSlice *ds = data_slices[0];
+        DataSlice *ds = data_slices.Make();
+        d_tos.Free();  // (a second Init: the compact layout of the first goes, this graph may not take one)
+        d_first_lower.Free();
+        d_low_offsets.Free();
         GraphSlice<VertexId, SizeT, Value> *gs = this->graph_slices[0];
-        const size_t n = static_cast<size_t>(this->nodes > 0 ? this->nodes : 1);
+        const size_t n = static_cast<size_t>(this->nodes);
         const size_t m = static_cast<size_t>(this->edges > 0 ? this->edges : 1);
-        GR_CHECK(hipMalloc(&ds->d_component_ids, sizeof(VertexId) * n), "CCProblem hipMalloc d_component_ids failed");
-        GR_CHECK(hipMalloc(&ds->d_masks, sizeof(int) * n), "CCProblem hipMalloc d_masks failed");
-        GR_CHECK(hipMalloc(&ds->d_marks, m + 16), "CCProblem hipMalloc d_marks failed");  // (+16: the skipping sweep reads 16 flags at a time)
-        GR_CHECK(hipMalloc(&ds->d_froms, sizeof(VertexId) * m), "CCProblem hipMalloc d_froms failed");
-        GR_CHECK(hipMalloc(&ds->d_vertex_flag, sizeof(int) * 2), "CCProblem hipMalloc flags failed");
+        GR_CHECK(d_component_ids.Alloc(n), "CCProblem d_component_ids failed");
+        GR_CHECK(d_masks.Alloc(n), "CCProblem d_masks failed");
+        GR_CHECK(d_marks.Alloc(m + 16), "CCProblem d_marks failed");  // (+16: the skipping sweep reads 16 flags at a time)
+        GR_CHECK(d_froms.Alloc(m), "CCProblem d_froms failed");
+        GR_CHECK(d_vertex_flag.Alloc(2), "CCProblem flags failed");
+        ds->d_component_ids = d_component_ids;
+        ds->d_masks = d_masks;
+        ds->d_marks = d_marks;
+        ds->d_froms = d_froms;
+        ds->d_vertex_flag = d_vertex_flag;
         ds->d_edge_flag = ds->d_vertex_flag + 1;
         ds->d_tos = gs->d_column_indices;
-        GR_CHECK(hipHostMalloc(&h_flags, sizeof(int) * 2, hipHostMallocDefault), "CCProblem hipHostMalloc failed");
+        GR_CHECK(h_flags.Alloc(2), "CCProblem pinned flags failed");
         if (this->nodes > 0) {
             hipLaunchKernelGGL((ExpandRowsKernel<VertexId, SizeT>), dim3(2048), dim3(256), 0, gs->stream, gs->d_row_offsets,
                                this->nodes, ds->d_froms);
@@ -283,12 +275,11 @@ struct CCProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
             // same hook).  Materialise only the from > to pairs -- half the edge stream for HookInit and for every HookMax sweep
             // (the reference sweeps both orientations of its COO, cc_enactor.cuh:407-424, 560-600).
             const long long n1 = static_cast<long long>(this->nodes) + 1;
-            unsigned *d_count = nullptr;
-            unsigned long long *d_sums = nullptr;
-            SizeT *d_low_offsets = nullptr;
-            GR_CHECK(hipMalloc(&d_count, sizeof(unsigned) * static_cast<size_t>(n1)), "CCProblem hipMalloc failed");
-            GR_CHECK(hipMalloc(&d_low_offsets, sizeof(SizeT) * static_cast<size_t>(n1)), "CCProblem hipMalloc failed");
-            GR_CHECK(hipMalloc(&d_sums, sizeof(unsigned long long) * static_cast<size_t>(graphio::ScanScratchWords(n1))), "CCProblem hipMalloc failed");
+            DeviceArray<unsigned> d_count;
+            DeviceArray<unsigned long long> d_sums;
+            GR_CHECK(d_count.Alloc(static_cast<size_t>(n1)), "CCProblem scratch failed");
+            GR_CHECK(d_low_offsets.Alloc(static_cast<size_t>(n1)), "CCProblem d_low_offsets failed");
+            GR_CHECK(d_sums.Alloc(static_cast<size_t>(graphio::ScanScratchWords(n1))), "CCProblem scratch failed");
             hipLaunchKernelGGL((LowerCountKernel<VertexId, SizeT>), dim3(2048), dim3(256), 0, gs->stream, gs->d_row_offsets, ds->d_tos,
                                static_cast<long long>(this->nodes), d_count);
             GR_CHECK(hipGetLastError(), "LowerCountKernel launch failed");
@@ -297,22 +288,22 @@ struct CCProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
             GR_CHECK(hipMemcpyAsync(&low_edges, d_low_offsets + this->nodes, sizeof(SizeT), hipMemcpyDeviceToHost, gs->stream), "CCProblem read failed");
             GR_CHECK(hipStreamSynchronize(gs->stream), "CCProblem lower-offset scan failed");
             const size_t lm = static_cast<size_t>(low_edges > 0 ? low_edges : 1);
-            VertexId *d_low_froms = nullptr, *d_low_tos = nullptr;
-            GR_CHECK(hipMalloc(&d_low_froms, sizeof(VertexId) * lm), "CCProblem hipMalloc failed");
-            GR_CHECK(hipMalloc(&d_low_tos, sizeof(VertexId) * lm), "CCProblem hipMalloc failed");
+            DeviceArray<VertexId> d_low_froms, d_low_tos;
+            GR_CHECK(d_low_froms.Alloc(lm), "CCProblem compact froms failed");
+            GR_CHECK(d_low_tos.Alloc(lm), "CCProblem compact tos failed");
             hipLaunchKernelGGL((LowerFillKernel<VertexId, SizeT>), dim3(2048), dim3(256), 0, gs->stream, gs->d_row_offsets, ds->d_tos, d_low_offsets,
                                static_cast<long long>(this->nodes), d_low_froms, d_low_tos);
             GR_CHECK(hipGetLastError(), "LowerFillKernel launch failed");
             GR_CHECK(hipStreamSynchronize(gs->stream), "LowerFillKernel failed");
             // ... and per vertex its smallest neighbour below it (the first entry of its compact row), which is all HookInit needs
-            VertexId *d_first = nullptr;
-            GR_CHECK(hipMalloc(&d_first, sizeof(VertexId) * static_cast<size_t>(this->nodes > 0 ? this->nodes : 1)), "CCProblem hipMalloc failed");
+            DeviceArray<VertexId> d_first;
+            GR_CHECK(d_first.Alloc(n), "CCProblem d_first_lower failed");
             hipLaunchKernelGGL((FirstLowerKernel<VertexId, SizeT>), dim3(2048), dim3(256), 0, gs->stream, d_low_offsets, d_low_tos,
                                static_cast<long long>(this->nodes), d_first);
             GR_CHECK(hipGetLastError(), "FirstLowerKernel launch failed");
             GR_CHECK(hipStreamSynchronize(gs->stream), "FirstLowerKernel failed");
-            ds->d_first_lower = d_first;
-            d_owned_first = d_first;
+            d_first_lower = std::move(d_first);
+            ds->d_first_lower = d_first_lower;
             // The row form lets a vertex of the giant component skip its row and relies on the OTHER end of each of its edges walking
             // its own: that needs every edge mirrored, both orientations.  `symmetric` above is weaker (only from < to edges were
             // checked -- enough to drop that orientation): a graph whose unmirrored edges all point from a higher to a lower id
@@ -328,15 +319,12 @@ struct CCProblem : ProblemBase<_VertexId, _SizeT, _Value, _USE_DOUBLE_BUFFER> {
                 ds->d_row_offsets = gs->d_row_offsets;
                 ds->d_columns = gs->d_column_indices;
             }
-            GR_CHECK(hipFree(ds->d_froms), "CCProblem hipFree failed");  // the full expansion is not needed any more
-            ds->d_froms = d_low_froms;
-            ds->d_tos = d_low_tos;
-            d_owned_tos = d_low_tos;
+            d_froms = std::move(d_low_froms);  // the full expansion is not needed any more
+            d_tos = std::move(d_low_tos);
+            ds->d_froms = d_froms;
+            ds->d_tos = d_tos;
             sweep_edges = low_edges;
-            GR_CHECK(hipFree(d_count), "CCProblem hipFree failed");
             ds->d_low_offsets = d_low_offsets;  // (kept: the neighbour rounds of the row form index the compact rows)
-            d_owned_low_offsets = d_low_offsets;
-            GR_CHECK(hipFree(d_sums), "CCProblem hipFree failed");
         }
         return retval;
     }

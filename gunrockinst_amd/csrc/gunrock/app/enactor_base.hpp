@@ -53,15 +53,13 @@ class EnactorBase {
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;  // INSTRUMENT: brackets one operator launch
     // INSTRUMENT: runtime-stamp words of the operator launches of one Enact (KernelRuntimeStats role)
     static constexpr int kDutyLaunches = 512;
-    unsigned long long *d_duty = nullptr;
+    util::DeviceArray<unsigned long long> d_duty;
     int duty_used = 0;
 
     EnactorBase(FrontierType ft, bool debug) : frontier_type(ft), DEBUG(debug) {}
 
     virtual ~EnactorBase()
     {
-        work_progress.Release();
-        if (d_duty) util::GRError(hipFree(d_duty), "EnactorBase hipFree failed", __FILE__, __LINE__);
         if (ev_begin) util::GRError(hipEventDestroy(ev_begin), "EnactorBase hipEventDestroy failed", __FILE__, __LINE__);
         if (ev_end) util::GRError(hipEventDestroy(ev_end), "EnactorBase hipEventDestroy failed", __FILE__, __LINE__);
     }
@@ -86,7 +84,7 @@ class EnactorBase {
     hipError_t DutyBegin(hipStream_t stream)
     {
         hipError_t retval = hipSuccess;
-        if (!d_duty) GR_CHECK(hipMalloc(&d_duty, sizeof(unsigned long long) * util::kDutyWords * kDutyLaunches), "EnactorBase hipMalloc failed");
+        if (!d_duty) GR_CHECK(d_duty.Alloc(static_cast<size_t>(util::kDutyWords) * kDutyLaunches), "EnactorBase duty words failed");
         duty_used = 0;
         enactor_stats.total_runtimes = 0;
         enactor_stats.total_lifetimes = 0;

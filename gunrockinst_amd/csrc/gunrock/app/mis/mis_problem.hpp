@@ -50,17 +50,10 @@ struct MISProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     unsigned seed = 0;
     int mode = MIS_SET;     // of the last Enact: Extract's summary is the set size or the number of colours
     long long summary = 0;
-    int *h_words = nullptr; // pinned read-back words
-    int *h_tail_words = nullptr;           // pinned copy of d_tail_words
+    util::PinnedArray<int> h_words;        // pinned read-back words
+    util::PinnedArray<int> h_tail_words;   // pinned copy of d_tail_words
     long long tail_windows = 0;            // windows d_tail_words has room for
     graphio::DeviceKeySort order_sort;     // orders the tail's worklist by key (scratch allocated at the first use)
-
-    // (the slice frees its own arrays; the pinned words are the problem's)
-    ~MISProblem() override
-    {
-        if (h_words) util::GRError(hipHostFree(h_words), "MISProblem hipHostFree failed", __FILE__, __LINE__);
-        if (h_tail_words) util::GRError(hipHostFree(h_tail_words), "MISProblem hipHostFree failed", __FILE__, __LINE__);
-    }
 
     // `count` device words read back (pinned), count <= 4
     hipError_t ReadWords(const int *d_from, int count, hipStream_t stream)
@@ -77,12 +70,11 @@ struct MISProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         hipError_t retval = hipSuccess;
         if (windows <= tail_windows) return retval;
         DataSlice *ds = data_slices[0];
-        if (h_tail_words) GR_CHECK(hipHostFree(h_tail_words), "MISProblem hipHostFree failed");
-        h_tail_words = nullptr;
+        h_tail_words.Free();
         tail_windows = 0;
         const size_t words = static_cast<size_t>(2 * windows + 1);
         if ((retval = ds->d_tail_words.Alloc(words))) return retval;
-        GR_CHECK(hipHostMalloc(&h_tail_words, sizeof(int) * words, hipHostMallocDefault), "MISProblem hipHostMalloc failed");
+        if ((retval = h_tail_words.Alloc(words))) return retval;
         tail_windows = windows;
         return retval;
     }
@@ -108,7 +100,7 @@ struct MISProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         hipStream_t stream = gs->stream;
         const long long n = this->nodes, m = this->edges;
         const size_t n1 = static_cast<size_t>(n > 0 ? n : 1);
-        GR_CHECK(hipHostMalloc(&h_words, sizeof(int) * 4, hipHostMallocDefault), "MISProblem hipHostMalloc failed");
+        if ((retval = h_words.Alloc(4))) return retval;
         if ((retval = ds->d_words.Alloc(4))) return retval;
         if ((retval = ds->d_reads.Alloc(4))) return retval;
 

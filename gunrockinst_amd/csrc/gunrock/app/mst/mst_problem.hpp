@@ -55,13 +55,7 @@ struct MSTProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
     long long list_capacity = 0;
     long long forest_edges = 0;
     long long total_weight = 0;
-    int *h_word = nullptr;  // pinned read-back words
-
-    // (the slice frees its own arrays; the pinned words are the problem's)
-    ~MSTProblem() override
-    {
-        if (h_word) util::GRError(hipHostFree(h_word), "MSTProblem hipHostFree failed", __FILE__, __LINE__);
-    }
+    util::PinnedArray<int> h_word;  // pinned read-back words
 
     // one device word read back (pinned)
     hipError_t ReadWord(const int *d_word, int &value, hipStream_t stream)
@@ -82,7 +76,7 @@ struct MSTProblem : ProblemBase<int, int, int, _USE_DOUBLE_BUFFER> {
         hipStream_t stream = gs->stream;
         const long long n = this->nodes, m = this->edges;
         const size_t n1 = static_cast<size_t>(n > 0 ? n : 1), m1 = static_cast<size_t>(m > 0 ? m : 1);
-        GR_CHECK(hipHostMalloc(&h_word, sizeof(int) * 2, hipHostMallocDefault), "MSTProblem hipHostMalloc failed");
+        if ((retval = h_word.Alloc(2))) return retval;
         if ((retval = ds->d_flag.Alloc(1))) return retval;
         if ((retval = ds->d_totals.Alloc(2))) return retval;
 

@@ -56,56 +56,50 @@ struct PRProblem : ProblemBase<_VertexId, _SizeT, _Value, false> {
         Value threshold = 0;
         VertexId src_node = -1;
     };
+    static_assert(std::is_trivially_copyable<DataSlice>::value,
+                  "the DataSlice is copied into kernel arguments and functors: views only, the owners sit in the problem");
 
-    DataSlice **data_slices = nullptr;
+    SliceHolder<DataSlice> data_slices;
     DataSlice **d_data_slices = nullptr;  // kept for source compatibility; unused
+    // what the slice views, under the slice's names
+    DeviceArray<Value> d_rank_curr, d_rank_next, d_contrib, d_rank_sorted;
+    DeviceArray<SizeT> d_degrees, d_degrees_pong;
+    DeviceArray<int> d_zero_flag, d_zero_count;
+    DeviceArray<VertexId> d_node_ids;
     const SizeT *d_inv_row_offsets = nullptr;  // in-neighbour lists
     const VertexId *d_inv_column_indices = nullptr;
-    SizeT *d_own_inv_row_offsets = nullptr;    // set when the transpose was built here
-    VertexId *d_own_inv_column_indices = nullptr;
+    DeviceArray<SizeT> d_own_inv_row_offsets;  // the transpose when BuildInverse made it
+    DeviceArray<VertexId> d_own_inv_column_indices;
     util::Frontier<VertexId, SizeT> inv_frontier;  // surviving vertices with the degree prefix of their in-lists
+    FrontierStorage<VertexId, SizeT> inv_storage;  // (inv_frontier is its view)
     graphio::DeviceKeySort sorter;
-
-    ~PRProblem() override
-    {
-        if (data_slices) {
-            DataSlice *ds = data_slices[0];
-            if (ds) {
-                void *ptrs[] = {ds->d_rank_curr, ds->d_rank_next, ds->d_contrib, ds->d_degrees, ds->d_degrees_pong, ds->d_zero_flag,
-                                ds->d_zero_count, ds->d_node_ids, ds->d_rank_sorted};
-                for (void *p : ptrs)
-                    if (p) util::GRError(hipFree(p), "PRProblem hipFree failed", __FILE__, __LINE__);
-                delete ds;
-            }
-            delete[] data_slices;
-        }
-        if (d_own_inv_row_offsets) util::GRError(hipFree(d_own_inv_row_offsets), "PRProblem hipFree failed", __FILE__, __LINE__);
-        if (d_own_inv_column_indices) util::GRError(hipFree(d_own_inv_column_indices), "PRProblem hipFree failed", __FILE__, __LINE__);
-        void *q[] = {inv_frontier.v, inv_frontier.row_start, inv_frontier.scan};
-        for (void *p : q)
-            if (p) util::GRError(hipFree(p), "PRProblem hipFree failed", __FILE__, __LINE__);
-    }
 
     hipError_t AllocData()
     {
         hipError_t retval = hipSuccess;
-        data_slices = new DataSlice *[1];
-        data_slices[0] = new DataSlice();
-        DataSlice *ds = data_slices[0];
+        DataSlice *ds = data_slices.Make();
         const size_t n = static_cast<size_t>(this->nodes > 0 ? this->nodes : 1);
-        GR_CHECK(hipMalloc(&ds->d_rank_curr, sizeof(Value) * n), "PRProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_rank_next, sizeof(Value) * n), "PRProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_contrib, sizeof(Value) * n), "PRProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_rank_sorted, sizeof(Value) * n), "PRProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_degrees, sizeof(SizeT) * n), "PRProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_degrees_pong, sizeof(SizeT) * n), "PRProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_zero_flag, sizeof(int) * n), "PRProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_zero_count, sizeof(int) * n), "PRProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&ds->d_node_ids, sizeof(VertexId) * n), "PRProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&inv_frontier.v, sizeof(VertexId) * (n + 1)), "PRProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&inv_frontier.row_start, sizeof(SizeT) * (n + 1)), "PRProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&inv_frontier.scan, sizeof(SizeT) * (n + 1)), "PRProblem hipMalloc failed");
-        inv_frontier.capacity = static_cast<SizeT>(n + 1);
+        GR_CHECK(d_rank_curr.Alloc(n), "PRProblem d_rank_curr failed");
+        GR_CHECK(d_rank_next.Alloc(n), "PRProblem d_rank_next failed");
+        GR_CHECK(d_contrib.Alloc(n), "PRProblem d_contrib failed");
+        GR_CHECK(d_rank_sorted.Alloc(n), "PRProblem d_rank_sorted failed");
+        GR_CHECK(d_degrees.Alloc(n), "PRProblem d_degrees failed");
+        GR_CHECK(d_degrees_pong.Alloc(n), "PRProblem d_degrees_pong failed");
+        GR_CHECK(d_zero_flag.Alloc(n), "PRProblem d_zero_flag failed");
+        GR_CHECK(d_zero_count.Alloc(n), "PRProblem d_zero_count failed");
+        GR_CHECK(d_node_ids.Alloc(n), "PRProblem d_node_ids failed");
+        ds->d_rank_curr = d_rank_curr;
+        ds->d_rank_next = d_rank_next;
+        ds->d_contrib = d_contrib;
+        ds->d_rank_sorted = d_rank_sorted;
+        ds->d_degrees = d_degrees;
+        ds->d_degrees_pong = d_degrees_pong;
+        ds->d_zero_flag = d_zero_flag;
+        ds->d_zero_count = d_zero_count;
+        ds->d_node_ids = d_node_ids;
+        retval = inv_storage.Grow(static_cast<SizeT>(n + 1));
+        inv_frontier = inv_storage.view;
+        if (retval) return util::GRError(retval, "PRProblem inverse frontier failed", __FILE__, __LINE__);
         return retval;
     }
 
@@ -135,11 +129,9 @@ struct PRProblem : ProblemBase<_VertexId, _SizeT, _Value, false> {
     {
         hipError_t retval = hipSuccess;
         GraphSlice<VertexId, SizeT, Value> *gs = this->graph_slices[0];
-        if (!d_own_inv_row_offsets) {
-            GR_CHECK(hipMalloc(&d_own_inv_row_offsets, sizeof(SizeT) * (static_cast<size_t>(this->nodes) + 2)), "PRProblem hipMalloc failed");
-            GR_CHECK(hipMalloc(&d_own_inv_column_indices, sizeof(VertexId) * static_cast<size_t>(this->edges > 0 ? this->edges : 1)),
-                     "PRProblem hipMalloc failed");
-        }
+        // (every build: what an earlier one made goes, so the arrays always have this graph's size)
+        GR_CHECK(d_own_inv_row_offsets.Alloc(static_cast<size_t>(this->nodes) + 2), "PRProblem inverse offsets failed");
+        GR_CHECK(d_own_inv_column_indices.Alloc(static_cast<size_t>(this->edges)), "PRProblem inverse columns failed");
         GR_CHECK(graphio::DeviceTransposeCsr(this->nodes, this->edges, gs->d_row_offsets, gs->d_column_indices, d_own_inv_row_offsets,
                                              d_own_inv_column_indices, gs->stream),
                  "PRProblem transpose failed");

@@ -14,6 +14,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <utility>
+
 #include <gunrock/csr.hpp>
 #include <gunrock/graphio/pair_graph.hpp>
 #include <gunrock/util/device_array.hpp>
@@ -31,53 +33,74 @@ enum FrontierType {
     MIXED_FRONTIERS    // O(n) + O(m)
 };
 
+// A frontier queue and its owner, shaped like oprtr::advance::BinPoolStorage: `view` is what kernels take by value, the three
+// arrays beside it are what is freed.  Mem as in DeviceArray.
+template <typename VertexId, typename SizeT, typename Mem = util::HipMem>
+struct FrontierStorage {
+    util::Frontier<VertexId, SizeT> view;
+    DeviceArray<VertexId, Mem> v;
+    DeviceArray<SizeT, Mem> row_start, scan;
+
+    // Room for `elements` entries; a queue that has it stays.  The new arrays come first and the view and its capacity are
+    // published only when all three exist: a grow that fails leaves an empty queue, which the next call grows again.
+    hipError_t Grow(SizeT elements)
+    {
+        hipError_t retval = hipSuccess;
+        if (view.capacity >= elements) return retval;
+        DeviceArray<VertexId, Mem> new_v;
+        DeviceArray<SizeT, Mem> new_row_start, new_scan;
+        const size_t count = static_cast<size_t>(elements);
+        if ((retval = new_v.Alloc(count)) || (retval = new_row_start.Alloc(count)) || (retval = new_scan.Alloc(count))) {
+            Free();
+            return retval;
+        }
+        v = std::move(new_v);
+        row_start = std::move(new_row_start);
+        scan = std::move(new_scan);
+        view.v = v;
+        view.row_start = row_start;
+        view.scan = scan;
+        view.capacity = elements;
+        return retval;
+    }
+
+    void Free()
+    {
+        view = util::Frontier<VertexId, SizeT>();
+        v.Free();
+        row_start.Free();
+        scan.Free();
+    }
+};
+
 template <typename VertexId, typename SizeT, typename Value>
 struct GraphSlice {
     int index = 0;
     SizeT nodes = 0;
     SizeT edges = 0;
+    // the CSR the kernels read: views of the arrays below (Init uploaded them) or of the caller's (InitFromDevice: borrowed)
     SizeT *d_row_offsets = nullptr;
     VertexId *d_column_indices = nullptr;
     Value *d_edge_values = nullptr;  // only when a primitive asks for weights
-    bool owns_graph = false;
+    DeviceArray<SizeT> own_row_offsets;
+    DeviceArray<VertexId> own_column_indices;
+    DeviceArray<Value> own_edge_values;
 
-    util::Frontier<VertexId, SizeT> frontier_queues[2];
-    SizeT frontier_elements[2] = {0, 0};
+    util::Frontier<VertexId, SizeT> frontier_queues[2];  // = queue_storage[i].view as of the last Reset: the kernel argument
+    FrontierStorage<VertexId, SizeT> queue_storage[2];
     hipStream_t stream = 0;
 
-    ~GraphSlice() { Release(); }
-
-    void ReleaseQueues()
+    GraphSlice() = default;
+    GraphSlice(const GraphSlice &) = delete;
+    GraphSlice &operator=(const GraphSlice &) = delete;
+    ~GraphSlice()
     {
-        for (int i = 0; i < 2; ++i) {
-            if (frontier_queues[i].v) util::GRError(hipFree(frontier_queues[i].v), "GraphSlice hipFree queue failed", __FILE__, __LINE__);
-            if (frontier_queues[i].row_start) util::GRError(hipFree(frontier_queues[i].row_start), "GraphSlice hipFree queue failed", __FILE__, __LINE__);
-            if (frontier_queues[i].scan) util::GRError(hipFree(frontier_queues[i].scan), "GraphSlice hipFree queue failed", __FILE__, __LINE__);
-            frontier_queues[i] = util::Frontier<VertexId, SizeT>();
-            frontier_elements[i] = 0;
-        }
-    }
-
-    void Release()
-    {
-        ReleaseQueues();
-        if (owns_graph) {
-            if (d_row_offsets) util::GRError(hipFree(d_row_offsets), "GraphSlice hipFree d_row_offsets failed", __FILE__, __LINE__);
-            if (d_column_indices) util::GRError(hipFree(d_column_indices), "GraphSlice hipFree d_column_indices failed", __FILE__, __LINE__);
-            if (d_edge_values) util::GRError(hipFree(d_edge_values), "GraphSlice hipFree d_edge_values failed", __FILE__, __LINE__);
-        }
-        d_row_offsets = nullptr;
-        d_column_indices = nullptr;
-        d_edge_values = nullptr;
-        if (stream) {
-            util::GRError(hipStreamDestroy(stream), "GraphSlice hipStreamDestroy failed", __FILE__, __LINE__);
-            stream = 0;
-        }
+        if (stream) util::GRError(hipStreamDestroy(stream), "GraphSlice hipStreamDestroy failed", __FILE__, __LINE__);
     }
 };
 
-// The owner of a problem's DataSlice, spelled as the reference's array of one per GPU: data_slices[0] is the slice, null until Make().
-// The slice's DeviceArray members free themselves when it goes, however far its build came.
+// The owner of a problem's slice, spelled as the reference's array of one per GPU: data_slices[0] (graph_slices[0]) is the slice,
+// null until Make().  The slice's DeviceArray members free themselves when it goes, however far its build came.
 template <typename DataSlice>
 struct SliceHolder {
     DataSlice *slice = nullptr;
@@ -105,31 +128,19 @@ struct ProblemBase {
     int num_gpus = 1;
     SizeT nodes = 0;
     SizeT edges = 0;
-    GraphSlice<VertexId, SizeT, Value> **graph_slices = nullptr;
+    SliceHolder<GraphSlice<VertexId, SizeT, Value>> graph_slices;
     int malformed = 0;  // ValidateCsr found offsets or columns that are not a CSR of `nodes` vertices
 
-    virtual ~ProblemBase()
-    {
-        if (graph_slices) {
-            for (int i = 0; i < num_gpus; ++i) delete graph_slices[i];
-            delete[] graph_slices;
-        }
-    }
+    virtual ~ProblemBase() {}
 
     hipError_t MakeSlice()
     {
         hipError_t retval = hipSuccess;
-        if (graph_slices) {
-            for (int i = 0; i < num_gpus; ++i) delete graph_slices[i];
-            delete[] graph_slices;
-        }
         num_gpus = 1;  // one process per GPU; N-GPU runs partition above this class
-        graph_slices = new GraphSlice<VertexId, SizeT, Value> *[1];
-        graph_slices[0] = new GraphSlice<VertexId, SizeT, Value>();
-        graph_slices[0]->nodes = nodes;
-        graph_slices[0]->edges = edges;
-        GR_CHECK(hipStreamCreateWithFlags(&graph_slices[0]->stream, hipStreamNonBlocking),
-                 "ProblemBase hipStreamCreate failed");
+        GraphSlice<VertexId, SizeT, Value> *gs = graph_slices.Make();  // (a second Init: the first slice goes with all it held)
+        gs->nodes = nodes;
+        gs->edges = edges;
+        GR_CHECK(hipStreamCreateWithFlags(&gs->stream, hipStreamNonBlocking), "ProblemBase hipStreamCreate failed");
         return retval;
     }
 
@@ -142,11 +153,11 @@ struct ProblemBase {
         edges = graph.edges;
         if ((retval = MakeSlice())) return retval;
         GraphSlice<VertexId, SizeT, Value> *gs = graph_slices[0];
-        gs->owns_graph = true;
         const size_t ro_bytes = sizeof(SizeT) * (static_cast<size_t>(nodes) + 1);
-        const size_t ci_bytes = sizeof(VertexId) * static_cast<size_t>(edges > 0 ? edges : 1);
-        GR_CHECK(hipMalloc(&gs->d_row_offsets, ro_bytes), "ProblemBase hipMalloc d_row_offsets failed");
-        GR_CHECK(hipMalloc(&gs->d_column_indices, ci_bytes), "ProblemBase hipMalloc d_column_indices failed");
+        GR_CHECK(gs->own_row_offsets.Alloc(static_cast<size_t>(nodes) + 1), "ProblemBase d_row_offsets failed");
+        GR_CHECK(gs->own_column_indices.Alloc(static_cast<size_t>(edges)), "ProblemBase d_column_indices failed");
+        gs->d_row_offsets = gs->own_row_offsets;
+        gs->d_column_indices = gs->own_column_indices;
         GR_CHECK(hipMemcpy(gs->d_row_offsets, graph.row_offsets, ro_bytes, hipMemcpyHostToDevice),
                  "ProblemBase hipMemcpy d_row_offsets failed");
         if (edges > 0)
@@ -154,8 +165,8 @@ struct ProblemBase {
                                hipMemcpyHostToDevice),
                      "ProblemBase hipMemcpy d_column_indices failed");
         if (load_edge_values && graph.edge_values) {
-            GR_CHECK(hipMalloc(&gs->d_edge_values, sizeof(Value) * static_cast<size_t>(edges > 0 ? edges : 1)),
-                     "ProblemBase hipMalloc d_edge_values failed");
+            GR_CHECK(gs->own_edge_values.Alloc(static_cast<size_t>(edges)), "ProblemBase d_edge_values failed");
+            gs->d_edge_values = gs->own_edge_values;
             if (edges > 0)
                 GR_CHECK(hipMemcpy(gs->d_edge_values, graph.edge_values, sizeof(Value) * static_cast<size_t>(edges),
                                    hipMemcpyHostToDevice),
@@ -172,7 +183,6 @@ struct ProblemBase {
         nodes = nodes_;
         edges = edges_;
         if ((retval = MakeSlice())) return retval;
-        graph_slices[0]->owns_graph = false;
         graph_slices[0]->d_row_offsets = d_row_offsets;
         graph_slices[0]->d_column_indices = d_column_indices;
         graph_slices[0]->d_edge_values = d_edge_values;
@@ -228,20 +238,9 @@ struct ProblemBase {
         if (want > 2147483000.0) want = 2147483000.0;
         const SizeT elements = static_cast<SizeT>(want);
         for (int i = 0; i < 2; ++i) {
-            if (gs->frontier_elements[i] >= elements) continue;
-            if (gs->frontier_queues[i].v) {
-                util::GRError(hipFree(gs->frontier_queues[i].v), "GraphSlice hipFree queue failed", __FILE__, __LINE__);
-                util::GRError(hipFree(gs->frontier_queues[i].row_start), "GraphSlice hipFree queue failed", __FILE__, __LINE__);
-                util::GRError(hipFree(gs->frontier_queues[i].scan), "GraphSlice hipFree queue failed", __FILE__, __LINE__);
-            }
-            GR_CHECK(hipMalloc(&gs->frontier_queues[i].v, sizeof(VertexId) * static_cast<size_t>(elements)),
-                     "ProblemBase hipMalloc frontier queue failed");
-            GR_CHECK(hipMalloc(&gs->frontier_queues[i].row_start, sizeof(SizeT) * static_cast<size_t>(elements)),
-                     "ProblemBase hipMalloc frontier queue failed");
-            GR_CHECK(hipMalloc(&gs->frontier_queues[i].scan, sizeof(SizeT) * static_cast<size_t>(elements)),
-                     "ProblemBase hipMalloc frontier queue failed");
-            gs->frontier_queues[i].capacity = elements;
-            gs->frontier_elements[i] = elements;
+            retval = gs->queue_storage[i].Grow(elements);
+            gs->frontier_queues[i] = gs->queue_storage[i].view;  // (empty after a grow that failed)
+            if (retval) return util::GRError(retval, "ProblemBase frontier queue failed", __FILE__, __LINE__);
         }
         return retval;
     }

@@ -18,6 +18,7 @@
 
 #include <hip/hip_runtime.h>
 #include <climits>
+#include <type_traits>
 
 #include <gunrock/app/problem_base.hpp>
 #include <gunrock/graphio/device_sort.hpp>
@@ -97,26 +98,33 @@ struct SSSPProblem : ProblemBase<_VertexId, _SizeT, _Value, false> {
             return d_labels[v];
         }
     };
+    static_assert(std::is_trivially_copyable<DataSlice>::value,
+                  "the DataSlice is copied into kernel arguments and functors: views only, the owners sit in the problem");
 
-    DataSlice **data_slices = nullptr;
+    SliceHolder<DataSlice> data_slices;
+    // what the slice views, under the slice's names (d_weights and d_inv_weights are the graph slice's or the caller's)
+    DeviceArray<unsigned> d_labels;
+    DeviceArray<unsigned long long> d_dist_pred;
+    DeviceArray<VertexId> d_preds;
+    DeviceArray<int> d_visit_lookup;
+    DeviceArray<unsigned char> d_pull;  // (bytes: a distance or a packed word per vertex)
     int delta_factor = 16;
-    bool owns_weights = false;
-    unsigned *d_weights_owned = nullptr;
 
     // far pile: vertices whose bucket lies beyond the current level, with the distance they had when parked
-    VertexId *d_far_v[2] = {nullptr, nullptr};
-    unsigned *d_far_d[2] = {nullptr, nullptr};
-    VertexId *d_candidates = nullptr;  // advance output (ids, duplicates allowed)
-    SizeT far_capacity = 0;
+    Grown<VertexId> d_far_v[2];
+    Grown<unsigned> d_far_d[2];
+    Grown<VertexId> d_candidates;  // advance output (ids, duplicates allowed)
+    SizeT far_capacity = 0;        // room of every pile and of the candidates: they grow together
     SizeT candidate_capacity = 0;
     SizeT src_row[2] = {0, 0};
     // in-neighbour lists with their weights (SetInverseGraph / BuildInverse): enable pull iterations
     const SizeT *d_inv_row_offsets = nullptr;
     const VertexId *d_inv_column_indices = nullptr;
-    SizeT *d_own_inv_row_offsets = nullptr;
-    VertexId *d_own_inv_column_indices = nullptr;
-    unsigned *d_own_inv_weights = nullptr;
+    DeviceArray<SizeT> d_own_inv_row_offsets;  // the transpose when BuildInverse made it
+    DeviceArray<VertexId> d_own_inv_column_indices;
+    DeviceArray<unsigned> d_own_inv_weights;
     util::Frontier<VertexId, SizeT> inv_frontier;  // every vertex that has in-edges, with the degree prefix of the in-lists
+    FrontierStorage<VertexId, SizeT> inv_storage;  // (inv_frontier is its view)
     SizeT inv_frontier_len = 0;
     SizeT inv_frontier_edges = 0;
     // a level relaxes by PULL when its frontier has more than this many out-edges (-1: 3/4 of the edges; 0: never).  A pull
@@ -128,48 +136,22 @@ struct SSSPProblem : ProblemBase<_VertexId, _SizeT, _Value, false> {
     bool HasInverse() const { return d_inv_row_offsets != nullptr && inv_frontier.v != nullptr; }
     long long PullMinEdges() const { return pull_min_edges >= 0 ? pull_min_edges : static_cast<long long>(this->edges) / 4 * 3 + 1; }
 
-    ~SSSPProblem() override
-    {
-        if (data_slices) {
-            DataSlice *ds = data_slices[0];
-            if (ds) {
-                if (ds->d_labels) hipFree(ds->d_labels);
-                if (ds->d_dist_pred) hipFree(ds->d_dist_pred);
-                if (ds->d_preds) hipFree(ds->d_preds);
-                if (ds->d_visit_lookup) hipFree(ds->d_visit_lookup);
-                if (ds->d_pull) hipFree(ds->d_pull);
-                delete ds;
-                data_slices[0] = nullptr;
-            }
-            delete[] data_slices;
-        }
-        for (int i = 0; i < 2; ++i) {
-            if (d_far_v[i]) hipFree(d_far_v[i]);
-            if (d_far_d[i]) hipFree(d_far_d[i]);
-        }
-        if (d_candidates) hipFree(d_candidates);
-        if (d_weights_owned) hipFree(d_weights_owned);
-        if (d_own_inv_row_offsets) hipFree(d_own_inv_row_offsets);
-        if (d_own_inv_column_indices) hipFree(d_own_inv_column_indices);
-        if (d_own_inv_weights) hipFree(d_own_inv_weights);
-        if (inv_frontier.v) hipFree(inv_frontier.v);
-        if (inv_frontier.row_start) hipFree(inv_frontier.row_start);
-        if (inv_frontier.scan) hipFree(inv_frontier.scan);
-    }
-
     hipError_t AllocData()
     {
         hipError_t retval = hipSuccess;
-        data_slices = new DataSlice *[1];
-        data_slices[0] = new DataSlice();
-        DataSlice *ds = data_slices[0];
-        const size_t n = static_cast<size_t>(this->nodes > 0 ? this->nodes : 1);
-        GR_CHECK(hipMalloc(&ds->d_labels, sizeof(unsigned) * n), "SSSPProblem hipMalloc d_labels failed");
+        DataSlice *ds = data_slices.Make();
+        d_pull.Free();  // (a second Init: the new slice views none yet)
+        const size_t n = static_cast<size_t>(this->nodes);
+        GR_CHECK(d_labels.Alloc(n), "SSSPProblem d_labels failed");
         if (MARK_PATHS) {
-            GR_CHECK(hipMalloc(&ds->d_dist_pred, sizeof(unsigned long long) * n), "SSSPProblem hipMalloc d_dist_pred failed");
-            GR_CHECK(hipMalloc(&ds->d_preds, sizeof(VertexId) * n), "SSSPProblem hipMalloc d_preds failed");
+            GR_CHECK(d_dist_pred.Alloc(n), "SSSPProblem d_dist_pred failed");
+            GR_CHECK(d_preds.Alloc(n), "SSSPProblem d_preds failed");
         }
-        GR_CHECK(hipMalloc(&ds->d_visit_lookup, sizeof(int) * n), "SSSPProblem hipMalloc d_visit_lookup failed");
+        GR_CHECK(d_visit_lookup.Alloc(n), "SSSPProblem d_visit_lookup failed");
+        ds->d_labels = d_labels;
+        ds->d_dist_pred = d_dist_pred;
+        ds->d_preds = d_preds;
+        ds->d_visit_lookup = d_visit_lookup;
         return retval;
     }
 
@@ -223,15 +205,13 @@ struct SSSPProblem : ProblemBase<_VertexId, _SizeT, _Value, false> {
                       (queue_sizing > 0 ? queue_sizing : 1.0);
         if (want > 2147483000.0) want = 2147483000.0;
         const SizeT cap = static_cast<SizeT>(want);
-        if (cap > far_capacity) {
+        if (cap > far_capacity) {  // (all five to the same room, as before: a Need that fails leaves the capacities 0 for the next Reset)
+            far_capacity = candidate_capacity = 0;
             for (int i = 0; i < 2; ++i) {
-                if (d_far_v[i]) hipFree(d_far_v[i]);
-                if (d_far_d[i]) hipFree(d_far_d[i]);
-                GR_CHECK(hipMalloc(&d_far_v[i], sizeof(VertexId) * static_cast<size_t>(cap)), "SSSPProblem hipMalloc far pile failed");
-                GR_CHECK(hipMalloc(&d_far_d[i], sizeof(unsigned) * static_cast<size_t>(cap)), "SSSPProblem hipMalloc far pile failed");
+                GR_CHECK(d_far_v[i].Need(static_cast<size_t>(cap)), "SSSPProblem far pile failed");
+                GR_CHECK(d_far_d[i].Need(static_cast<size_t>(cap)), "SSSPProblem far pile failed");
             }
-            if (d_candidates) hipFree(d_candidates);
-            GR_CHECK(hipMalloc(&d_candidates, sizeof(VertexId) * static_cast<size_t>(cap)), "SSSPProblem hipMalloc candidates failed");
+            GR_CHECK(d_candidates.Need(static_cast<size_t>(cap)), "SSSPProblem candidates failed");
             far_capacity = cap;
             candidate_capacity = cap;
         }
@@ -280,22 +260,22 @@ struct SSSPProblem : ProblemBase<_VertexId, _SizeT, _Value, false> {
         d_inv_row_offsets = d_iro;
         d_inv_column_indices = d_ici;
         ds->d_inv_weights = d_iw;
-        if (!inv_frontier.v) {
-            const size_t cap = static_cast<size_t>(n > 0 ? n : 1) + 1;
-            GR_CHECK(hipMalloc(&inv_frontier.v, sizeof(VertexId) * cap), "SSSPProblem hipMalloc failed");
-            GR_CHECK(hipMalloc(&inv_frontier.row_start, sizeof(SizeT) * cap), "SSSPProblem hipMalloc failed");
-            GR_CHECK(hipMalloc(&inv_frontier.scan, sizeof(SizeT) * cap), "SSSPProblem hipMalloc failed");
-            inv_frontier.capacity = static_cast<SizeT>(cap);
-            GR_CHECK(hipMalloc(&ds->d_pull, (MARK_PATHS ? sizeof(unsigned long long) : sizeof(unsigned)) * cap), "SSSPProblem hipMalloc failed");
+        const size_t cap = static_cast<size_t>(n > 0 ? n : 1) + 1;
+        retval = inv_storage.Grow(static_cast<SizeT>(cap));
+        inv_frontier = inv_storage.view;
+        if (retval) return util::GRError(retval, "SSSPProblem inverse frontier failed", __FILE__, __LINE__);
+        if (!ds->d_pull) {
+            GR_CHECK(d_pull.Alloc((MARK_PATHS ? sizeof(unsigned long long) : sizeof(unsigned)) * cap), "SSSPProblem d_pull failed");
+            ds->d_pull = d_pull.p;
         }
         inv_frontier_len = 0;
         inv_frontier_edges = 0;
         if (n <= 0) return retval;
-        unsigned *d_flags = nullptr, *d_pos = nullptr;
-        unsigned long long *d_sums = nullptr;
-        GR_CHECK(hipMalloc(&d_flags, sizeof(unsigned) * static_cast<size_t>(n + 1)), "SSSPProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&d_pos, sizeof(unsigned) * static_cast<size_t>(n + 1)), "SSSPProblem hipMalloc failed");
-        GR_CHECK(hipMalloc(&d_sums, sizeof(unsigned long long) * static_cast<size_t>(graphio::ScanScratchWords(n + 1))), "SSSPProblem hipMalloc failed");
+        DeviceArray<unsigned> d_flags, d_pos;
+        DeviceArray<unsigned long long> d_sums;
+        GR_CHECK(d_flags.Alloc(static_cast<size_t>(n + 1)), "SSSPProblem scratch failed");
+        GR_CHECK(d_pos.Alloc(static_cast<size_t>(n + 1)), "SSSPProblem scratch failed");
+        GR_CHECK(d_sums.Alloc(static_cast<size_t>(graphio::ScanScratchWords(n + 1))), "SSSPProblem scratch failed");
         hipLaunchKernelGGL((HasInEdgesKernel<SizeT>), dim3(1024), dim3(256), 0, stream, d_iro, n, d_flags);
         GR_CHECK(hipGetLastError(), "HasInEdgesKernel launch failed");
         GR_CHECK(graphio::DeviceExclusiveScan<unsigned>(d_flags, d_pos, n + 1, d_sums, stream), "SSSPProblem scan failed");
@@ -309,9 +289,6 @@ struct SSSPProblem : ProblemBase<_VertexId, _SizeT, _Value, false> {
         GR_CHECK(hipStreamSynchronize(stream), "SSSPProblem sync failed");
         inv_frontier_len = static_cast<SizeT>(total);
         inv_frontier_edges = m_inv;
-        GR_CHECK(hipFree(d_flags), "SSSPProblem hipFree failed");
-        GR_CHECK(hipFree(d_pos), "SSSPProblem hipFree failed");
-        GR_CHECK(hipFree(d_sums), "SSSPProblem hipFree failed");
         return retval;
     }
     // ... or built here: the transpose of the CSR, the weights travelling with their edges
@@ -319,12 +296,10 @@ struct SSSPProblem : ProblemBase<_VertexId, _SizeT, _Value, false> {
     {
         hipError_t retval = hipSuccess;
         GraphSlice<VertexId, SizeT, Value> *gs = this->graph_slices[0];
-        if (!d_own_inv_row_offsets) {
-            const size_t m = static_cast<size_t>(this->edges > 0 ? this->edges : 1);
-            GR_CHECK(hipMalloc(&d_own_inv_row_offsets, sizeof(SizeT) * (static_cast<size_t>(this->nodes) + 2)), "SSSPProblem hipMalloc failed");
-            GR_CHECK(hipMalloc(&d_own_inv_column_indices, sizeof(VertexId) * m), "SSSPProblem hipMalloc failed");
-            GR_CHECK(hipMalloc(&d_own_inv_weights, sizeof(unsigned) * m), "SSSPProblem hipMalloc failed");
-        }
+        // (every build: what an earlier one made goes, so the arrays always have this graph's size)
+        GR_CHECK(d_own_inv_row_offsets.Alloc(static_cast<size_t>(this->nodes) + 2), "SSSPProblem inverse offsets failed");
+        GR_CHECK(d_own_inv_column_indices.Alloc(static_cast<size_t>(this->edges)), "SSSPProblem inverse columns failed");
+        GR_CHECK(d_own_inv_weights.Alloc(static_cast<size_t>(this->edges)), "SSSPProblem inverse weights failed");
         GR_CHECK(graphio::DeviceTransposeCsr(this->nodes, this->edges, gs->d_row_offsets, gs->d_column_indices, d_own_inv_row_offsets,
                                              d_own_inv_column_indices, gs->stream, data_slices[0]->d_weights, d_own_inv_weights),
                  "SSSPProblem transpose failed");

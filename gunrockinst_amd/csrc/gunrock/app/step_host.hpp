@@ -15,6 +15,7 @@
 #include <type_traits>
 
 #include <gunrock/oprtr/step.hpp>
+#include <gunrock/util/device_array.hpp>
 #include <gunrock/util/error_utils.hpp>
 
 namespace gunrock {
@@ -116,6 +117,7 @@ template <bool INSTRUMENT>
 struct StepHost {
     const char *who;
     unsigned char *pinned = nullptr;  // the read-backs land here without a staging copy; the enactor lays it out
+    util::PinnedArray<unsigned char> pinned_block;  // (its owner)
     // of the last Enact
     long long launches = 0, readbacks = 0;
     double kernel_ms = 0;  // INSTRUMENT: summed kernel time
@@ -127,7 +129,6 @@ struct StepHost {
     {
         if (ev[0]) hipEventDestroy(ev[0]);
         if (ev[1]) hipEventDestroy(ev[1]);
-        if (pinned) hipHostFree(pinned);
     }
 
     // the start of an Enact: the counts at zero, `pinned_bytes` of pinned memory (zeroed when first made), the events
@@ -137,10 +138,10 @@ struct StepHost {
         launches = readbacks = 0;
         kernel_ms = 0;
         if (pinned_bytes > bytes) {
-            if (pinned) hipHostFree(pinned);
             pinned = nullptr;
             bytes = 0;
-            if ((retval = Check(hipHostMalloc(&pinned, pinned_bytes), "hipHostMalloc failed", __LINE__))) return retval;
+            if ((retval = Check(pinned_block.Alloc(pinned_bytes), "hipHostMalloc failed", __LINE__))) return retval;
+            pinned = pinned_block;
             bytes = pinned_bytes;
             std::memset(pinned, 0, bytes);
         }

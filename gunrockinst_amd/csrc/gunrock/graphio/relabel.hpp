@@ -20,6 +20,7 @@
 
 #include <gunrock/graphio/device_csr.hpp>
 #include <gunrock/graphio/device_sort.hpp>
+#include <gunrock/util/device_array.hpp>
 
 namespace gunrock {
 namespace graphio {
@@ -153,11 +154,10 @@ static __global__ void RelabelColsKernel(const unsigned long long *d_sorted, lon
 // a search) without a device round trip.
 struct RelabelledCsr {
     long long nodes = 0, edges = 0, words64 = 0;
-    int *d_row_offsets = nullptr;
-    int *d_cols = nullptr;
-    int *d_old_of_new = nullptr;  // only when built with predecessors
-    unsigned long long *d_hub = nullptr, *d_edge = nullptr;
-    unsigned *d_base0 = nullptr, *d_base1 = nullptr;
+    util::DeviceArray<int> d_row_offsets, d_cols;
+    util::DeviceArray<int> d_old_of_new;  // only when built with predecessors
+    util::DeviceArray<unsigned long long> d_hub, d_edge;
+    util::DeviceArray<unsigned> d_base0, d_base1;
     long long hubs = 0, with_edges = 0;
     int threshold = 0;
     float build_ms = 0.f;
@@ -189,21 +189,15 @@ struct RelabelledCsr {
 
     void Release()
     {
-        int *ints[3] = {d_row_offsets, d_cols, d_old_of_new};
-        for (int *p : ints)
-            if (p) util::GRError(hipFree(p), "RelabelledCsr hipFree failed", __FILE__, __LINE__);
-        unsigned long long *masks[2] = {d_hub, d_edge};
-        for (unsigned long long *p : masks)
-            if (p) util::GRError(hipFree(p), "RelabelledCsr hipFree failed", __FILE__, __LINE__);
-        unsigned *bases[2] = {d_base0, d_base1};
-        for (unsigned *p : bases)
-            if (p) util::GRError(hipFree(p), "RelabelledCsr hipFree failed", __FILE__, __LINE__);
-        d_row_offsets = d_cols = d_old_of_new = nullptr;
-        d_hub = d_edge = nullptr;
-        d_base0 = d_base1 = nullptr;
+        d_row_offsets.Free();
+        d_cols.Free();
+        d_old_of_new.Free();
+        d_hub.Free();
+        d_edge.Free();
+        d_base0.Free();
+        d_base1.Free();
         bytes = 0;
     }
-    ~RelabelledCsr() { Release(); }
 
     // Build the copy of the CSR (d_row_offsets[nodes + 1], d_cols[edges]) with at most max_hubs hubs.  Synchronous.
     hipError_t Build(long long nodes_, long long edges_, const int *d_ro, const int *d_ci, long long max_hubs, bool old_of_new,
@@ -220,8 +214,8 @@ struct RelabelledCsr {
         GR_CHECK(hipEventRecord(t0, stream), "hipEventRecord failed");
 
         // 1. threshold: the smallest T >= 1 with at most max_hubs vertices of degree >= T (degree histogram)
-        int *d_max = nullptr;
-        GR_CHECK(hipMalloc(&d_max, sizeof(int)), "RelabelledCsr hipMalloc failed");
+        util::DeviceArray<int> d_max;
+        GR_CHECK(d_max.Alloc(1), "RelabelledCsr scratch failed");
         GR_CHECK(hipMemsetAsync(d_max, 0, sizeof(int), stream), "RelabelledCsr memset failed");
         const unsigned grid = 2048;
         if (nodes > 0) {
@@ -231,11 +225,11 @@ struct RelabelledCsr {
         int max_degree = 0;
         GR_CHECK(hipMemcpyAsync(&max_degree, d_max, sizeof(int), hipMemcpyDeviceToHost, stream), "RelabelledCsr read failed");
         GR_CHECK(hipStreamSynchronize(stream), "RelabelledCsr sync failed");
-        GR_CHECK(hipFree(d_max), "RelabelledCsr hipFree failed");
+        d_max.Free();
         std::vector<unsigned> hist(static_cast<size_t>(max_degree) + 1, 0u);
         {
-            unsigned *d_hist = nullptr;
-            GR_CHECK(hipMalloc(&d_hist, sizeof(unsigned) * hist.size()), "RelabelledCsr hipMalloc failed");
+            util::DeviceArray<unsigned> d_hist;
+            GR_CHECK(d_hist.Alloc(hist.size()), "RelabelledCsr scratch failed");
             GR_CHECK(hipMemsetAsync(d_hist, 0, sizeof(unsigned) * hist.size(), stream), "RelabelledCsr memset failed");
             if (nodes > 0) {
                 hipLaunchKernelGGL(DegreeHistogramKernel, dim3(grid), dim3(256), 0, stream, d_ro, nodes, max_degree, d_hist);
@@ -243,7 +237,6 @@ struct RelabelledCsr {
             }
             GR_CHECK(hipMemcpyAsync(hist.data(), d_hist, sizeof(unsigned) * hist.size(), hipMemcpyDeviceToHost, stream), "RelabelledCsr read failed");
             GR_CHECK(hipStreamSynchronize(stream), "RelabelledCsr sync failed");
-            GR_CHECK(hipFree(d_hist), "RelabelledCsr hipFree failed");
         }
         threshold = max_degree + 1;  // no hubs
         for (long long above = 0, d = max_degree; d >= 1; --d) {
@@ -253,15 +246,15 @@ struct RelabelledCsr {
         }
 
         // 2. tier masks, per-word counts, prefix counts
-        GR_CHECK(hipMalloc(&d_hub, sizeof(unsigned long long) * words64), "RelabelledCsr hipMalloc failed");
-        GR_CHECK(hipMalloc(&d_edge, sizeof(unsigned long long) * words64), "RelabelledCsr hipMalloc failed");
-        GR_CHECK(hipMalloc(&d_base0, sizeof(unsigned) * words64), "RelabelledCsr hipMalloc failed");
-        GR_CHECK(hipMalloc(&d_base1, sizeof(unsigned) * words64), "RelabelledCsr hipMalloc failed");
-        unsigned *d_counts = nullptr;
-        unsigned long long *d_sums = nullptr;
+        GR_CHECK(d_hub.Alloc(static_cast<size_t>(words64)), "RelabelledCsr d_hub failed");
+        GR_CHECK(d_edge.Alloc(static_cast<size_t>(words64)), "RelabelledCsr d_edge failed");
+        GR_CHECK(d_base0.Alloc(static_cast<size_t>(words64)), "RelabelledCsr d_base0 failed");
+        GR_CHECK(d_base1.Alloc(static_cast<size_t>(words64)), "RelabelledCsr d_base1 failed");
+        util::DeviceArray<unsigned> d_counts;
+        util::DeviceArray<unsigned long long> d_sums;
         const long long scan_n = (nodes + 1 > 2 * words64) ? nodes + 1 : 2 * words64;
-        GR_CHECK(hipMalloc(&d_counts, sizeof(unsigned) * static_cast<size_t>(scan_n)), "RelabelledCsr hipMalloc failed");
-        GR_CHECK(hipMalloc(&d_sums, sizeof(unsigned long long) * static_cast<size_t>(ScanScratchWords(scan_n))), "RelabelledCsr hipMalloc failed");
+        GR_CHECK(d_counts.Alloc(static_cast<size_t>(scan_n)), "RelabelledCsr scratch failed");
+        GR_CHECK(d_sums.Alloc(static_cast<size_t>(ScanScratchWords(scan_n))), "RelabelledCsr scratch failed");
         {
             long long g = (words64 + 3) / 4;
             if (g > 4096) g = 4096;
@@ -285,10 +278,10 @@ struct RelabelledCsr {
         const RelabelView map = View();
 
         // 3. new row offsets (every entry kept: the degrees do not change) and new -> old
-        GR_CHECK(hipMalloc(&d_row_offsets, sizeof(int) * static_cast<size_t>(nodes + 1)), "RelabelledCsr hipMalloc failed");
+        GR_CHECK(d_row_offsets.Alloc(static_cast<size_t>(nodes + 1)), "RelabelledCsr d_row_offsets failed");
         GR_CHECK(hipMemsetAsync(d_counts, 0, sizeof(unsigned) * static_cast<size_t>(nodes + 1), stream), "RelabelledCsr memset failed");
         if (old_of_new)
-            GR_CHECK(hipMalloc(&d_old_of_new, sizeof(int) * static_cast<size_t>(nodes > 0 ? nodes : 1)), "RelabelledCsr hipMalloc failed");
+            GR_CHECK(d_old_of_new.Alloc(static_cast<size_t>(nodes)), "RelabelledCsr d_old_of_new failed");
         if (nodes > 0) {
             hipLaunchKernelGGL(RelabelDegreesKernel, dim3(grid), dim3(256), 0, stream, map, d_ro, nodes, d_counts, d_old_of_new);
             GR_CHECK(hipGetLastError(), "RelabelDegreesKernel launch failed");
@@ -296,7 +289,7 @@ struct RelabelledCsr {
         GR_CHECK(DeviceExclusiveScan<int>(d_counts, d_row_offsets, nodes + 1, d_sums, stream), "RelabelledCsr offsets scan failed");
 
         // 4. columns: sort the (new row, new column) keys of all entries
-        GR_CHECK(hipMalloc(&d_cols, sizeof(int) * static_cast<size_t>(edges > 0 ? edges : 1)), "RelabelledCsr hipMalloc failed");
+        GR_CHECK(d_cols.Alloc(static_cast<size_t>(edges)), "RelabelledCsr d_cols failed");
         if (edges > 0) {
             int col_bits = 1;
             while ((1ll << col_bits) < nodes) ++col_bits;
@@ -315,8 +308,6 @@ struct RelabelledCsr {
         GR_CHECK(hipEventElapsedTime(&build_ms, t0, t1), "hipEventElapsedTime failed");
         GR_CHECK(hipEventDestroy(t0), "hipEventDestroy failed");
         GR_CHECK(hipEventDestroy(t1), "hipEventDestroy failed");
-        GR_CHECK(hipFree(d_counts), "RelabelledCsr hipFree failed");
-        GR_CHECK(hipFree(d_sums), "RelabelledCsr hipFree failed");
         bytes = sizeof(int) * static_cast<size_t>(nodes + 1 + edges + (old_of_new ? nodes : 0)) + (2 * sizeof(unsigned long long) + 2 * sizeof(unsigned)) * words64;
         return retval;
     }

@@ -29,7 +29,10 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include <gunrock/oprtr/advance/functor_hooks.hpp>
+#include <gunrock/util/device_array.hpp>
 #include <gunrock/util/device_intrinsics.hpp>
 #include <gunrock/util/error_utils.hpp>
 
@@ -73,6 +76,8 @@ struct BinPool {
     __device__ __forceinline__ int *BinCursor(int b) const { return d_ctrl + (1 + kBins + b) * kBinCtrlStride; }
     static constexpr size_t CtrlInts() { return static_cast<size_t>(1 + 2 * kBins) * kBinCtrlStride; }
 };
+static_assert(std::is_trivially_copyable<BinPool<int>>::value,
+              "a BinPool is a kernel argument: a view of raw pointers; its owner is BinPoolStorage");
 
 // Chunks that can be needed by a phase 1 that hands over at most `entries` pairs from `workgroups` workgroups: full chunks
 // plus, per workgroup and bin, the open chunk and the pre-allocated next one.
@@ -257,10 +262,13 @@ __global__ __launch_bounds__(THREADS) void BinnedApplyKernel(BinPool<typename Pr
     }
 }
 
-// Host side of the pool: owned by the problem that uses a binned advance.
+// Host side of the pool: owned by the problem that uses a binned advance.  `view` is the kernel argument; the arrays beside it
+// are what is freed.
 template <typename VertexId>
 struct BinPoolStorage {
     BinPool<VertexId> view;
+    util::DeviceArray<VertexId> d_dst, d_src;
+    util::DeviceArray<int> d_chunk_count, d_bin_list, d_ctrl;
     long long capacity_entries = 0;
     int workgroups = 0;
 
@@ -274,11 +282,16 @@ struct BinPoolStorage {
         if (chunks > 0x7FFFFFFFll / 2) return util::GRError(hipErrorInvalidValue, "BinPool: too many chunks", __FILE__, __LINE__);
         view.max_chunks = static_cast<int>(chunks);
         const size_t entries = static_cast<size_t>(chunks) * kBinChunk;
-        GR_CHECK(hipMalloc(&view.d_dst, sizeof(VertexId) * entries), "BinPool hipMalloc d_dst failed");
-        if (with_src) GR_CHECK(hipMalloc(&view.d_src, sizeof(VertexId) * entries), "BinPool hipMalloc d_src failed");
-        GR_CHECK(hipMalloc(&view.d_chunk_count, sizeof(int) * static_cast<size_t>(chunks)), "BinPool hipMalloc failed");
-        GR_CHECK(hipMalloc(&view.d_bin_list, sizeof(int) * static_cast<size_t>(chunks) * kBins), "BinPool hipMalloc failed");
-        GR_CHECK(hipMalloc(&view.d_ctrl, sizeof(int) * BinPool<VertexId>::CtrlInts()), "BinPool hipMalloc failed");
+        GR_CHECK(d_dst.Alloc(entries), "BinPool d_dst failed");
+        if (with_src) GR_CHECK(d_src.Alloc(entries), "BinPool d_src failed");
+        GR_CHECK(d_chunk_count.Alloc(static_cast<size_t>(chunks)), "BinPool d_chunk_count failed");
+        GR_CHECK(d_bin_list.Alloc(static_cast<size_t>(chunks) * kBins), "BinPool d_bin_list failed");
+        GR_CHECK(d_ctrl.Alloc(BinPool<VertexId>::CtrlInts()), "BinPool d_ctrl failed");
+        view.d_dst = d_dst;
+        view.d_src = d_src;
+        view.d_chunk_count = d_chunk_count;
+        view.d_bin_list = d_bin_list;
+        view.d_ctrl = d_ctrl;
         view.d_overflow = d_overflow;
         capacity_entries = max_entries;
         workgroups = max_workgroups;
@@ -293,11 +306,11 @@ struct BinPoolStorage {
 
     void Release()
     {
-        if (view.d_dst) util::GRError(hipFree(view.d_dst), "BinPool hipFree failed", __FILE__, __LINE__);
-        if (view.d_src) util::GRError(hipFree(view.d_src), "BinPool hipFree failed", __FILE__, __LINE__);
-        if (view.d_chunk_count) util::GRError(hipFree(view.d_chunk_count), "BinPool hipFree failed", __FILE__, __LINE__);
-        if (view.d_bin_list) util::GRError(hipFree(view.d_bin_list), "BinPool hipFree failed", __FILE__, __LINE__);
-        if (view.d_ctrl) util::GRError(hipFree(view.d_ctrl), "BinPool hipFree failed", __FILE__, __LINE__);
+        d_dst.Free();
+        d_src.Free();
+        d_chunk_count.Free();
+        d_bin_list.Free();
+        d_ctrl.Free();
         view = BinPool<VertexId>();
         capacity_entries = 0;
         workgroups = 0;

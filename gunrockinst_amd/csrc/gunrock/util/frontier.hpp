@@ -20,7 +20,9 @@
 #include <set>
 #include <cstdint>
 #include <cstring>
+#include <type_traits>
 
+#include <gunrock/util/device_array.hpp>
 #include <gunrock/util/error_utils.hpp>
 
 namespace gunrock {
@@ -33,6 +35,8 @@ struct Frontier {
     SizeT *scan = nullptr;   // exclusive prefix sum of degrees, in queue order
     SizeT capacity = 0;
 };
+static_assert(std::is_trivially_copyable<Frontier<int, int>>::value,
+              "a Frontier is a kernel argument: a view of raw pointers; its owner is app::FrontierStorage (app/problem_base.hpp)");
 
 __host__ __device__ __forceinline__ unsigned long long PackTail(unsigned count, unsigned edges)
 {
@@ -142,14 +146,15 @@ static __global__ void ArmKernel(unsigned long long *d_tail, int *d_overflow, un
     if (lane == 0) *d_overflow = 0;
 }
 
-// Device words shared by all kernels of one enactor.
+// Device words shared by all kernels of one enactor.  The struct stays on the host (kernels take its words one by one, or a
+// PublishArgs), so it owns them.
 struct WorkProgress {
     static constexpr int kSlots = 8;       // 0..3: BSP ring, 4: auxiliary tail, 5: SSSP far-min, 6: tail-kernel level count,
                                            // 7: grid barrier (counter | timeout); tail-kernel sums live in d_sums[2]
     static constexpr int kAux = 4;
-    unsigned long long *d_tail = nullptr;  // [kSlots] packed (edges<<32 | vertices)
-    int *d_overflow = nullptr;             // set when a writer ran out of queue capacity
-    unsigned long long *d_sums = nullptr;  // [2] tail kernel: summed frontier lengths / edges
+    DeviceArray<unsigned long long> d_tail;  // [kSlots] packed (edges<<32 | vertices)
+    DeviceArray<int> d_overflow;             // set when a writer ran out of queue capacity
+    DeviceArray<unsigned long long> d_sums;  // [2] tail kernel: summed frontier lengths / edges
     // "Wide" tail: kWideLines packed counters, 128 bytes apart.  Atomics on ONE address retire at ~80 per microsecond on
     // MI355X (measured: 8192 wave-level adds = 103 us, tools/xcd_store_bench.hip), so kernels whose every workgroup reports
     // a count (bottom-up sweep, fresh-flag pass) spread their adds over these lines; PublishKernel folds and clears them.
@@ -158,14 +163,14 @@ struct WorkProgress {
     // kWideSets such sets back to back: set 0 is "the" wide tail; sets 1.. take the finds of the sweeps of a chain (bottom_up.hpp)
     static constexpr int kWideSets = 8;
     static constexpr int kWideSetWords = kWideLines * kWideStride;
-    unsigned long long *d_wide = nullptr;
-    int *d_chain_log = nullptr;            // [8] action each sweep of a chain took; [8], [9]: gate words of the kernels queued behind
+    DeviceArray<unsigned long long> d_wide;
+    DeviceArray<int> d_chain_log;          // [8] action each sweep of a chain took; [8], [9]: gate words of the kernels queued behind
                                            // a chain (did the closing levels run; how many sweeps ran)
     int publish_sets = 1;                  // wide sets PublishKernel folds (enactors that chain sweeps raise it)
     // Host view.  Every blocking read-back of a BSP step is ONE tiny kernel that writes the mailbox in pinned host memory and
     // a host spin on its sequence word: the previous form (one or two hipMemcpyAsync = blit kernels of 4-5 us each, then a
     // stream query loop) cost ~20 us per level.
-    HostMailbox *box = nullptr;            // pinned + mapped
+    PinnedArray<HostMailbox, hipHostMallocMapped> box;  // pinned + mapped
     unsigned long long *h_sums = nullptr;  // = box->sums
     unsigned long long *h_tail = nullptr;  // = box->tail
     unsigned long long seq = 0;
@@ -185,17 +190,16 @@ struct WorkProgress {
         hipError_t retval = hipSuccess;
         if (d_tail) return retval;
         Live().insert(this);
-        GR_CHECK(hipMalloc(&d_tail, sizeof(unsigned long long) * kSlots), "WorkProgress hipMalloc d_tail failed");
-        GR_CHECK(hipMalloc(&d_overflow, sizeof(int)), "WorkProgress hipMalloc d_overflow failed");
-        GR_CHECK(hipHostMalloc(reinterpret_cast<void **>(&box), sizeof(HostMailbox), hipHostMallocMapped),
-                 "WorkProgress hipHostMalloc failed");
-        std::memset(box, 0, sizeof(HostMailbox));
+        GR_CHECK(d_tail.Alloc(kSlots), "WorkProgress d_tail failed");
+        GR_CHECK(d_overflow.Alloc(1), "WorkProgress d_overflow failed");
+        GR_CHECK(box.Alloc(1), "WorkProgress mailbox failed");
+        std::memset(box.p, 0, sizeof(HostMailbox));
         h_tail = box->tail;
         h_sums = box->sums;
-        GR_CHECK(hipMalloc(&d_sums, sizeof(unsigned long long) * 2), "WorkProgress hipMalloc d_sums failed");
+        GR_CHECK(d_sums.Alloc(2), "WorkProgress d_sums failed");
         GR_CHECK(hipMemset(d_sums, 0, sizeof(unsigned long long) * 2), "WorkProgress memset failed");
-        GR_CHECK(hipMalloc(&d_wide, sizeof(unsigned long long) * kWideSets * kWideSetWords), "WorkProgress hipMalloc d_wide failed");
-        GR_CHECK(hipMalloc(&d_chain_log, sizeof(int) * 16), "WorkProgress hipMalloc d_chain_log failed");
+        GR_CHECK(d_wide.Alloc(kWideSets * kWideSetWords), "WorkProgress d_wide failed");
+        GR_CHECK(d_chain_log.Alloc(16), "WorkProgress d_chain_log failed");
         GR_CHECK(hipMemset(d_chain_log, 0, sizeof(int) * 16), "WorkProgress memset failed");
         // Blocking clears: the enactors work on non-blocking streams, which are NOT ordered behind the null stream -- an
         // asynchronous clear issued here could land after the first search's seed (seen: a search that found nothing).
@@ -342,18 +346,7 @@ struct WorkProgress {
         return retval;
     }
 
-    void Release()
-    {
-        Live().erase(this);
-        if (d_tail) GRError(hipFree(d_tail), "WorkProgress hipFree failed", __FILE__, __LINE__);
-        if (d_overflow) GRError(hipFree(d_overflow), "WorkProgress hipFree failed", __FILE__, __LINE__);
-        if (box) GRError(hipHostFree(box), "WorkProgress hipHostFree failed", __FILE__, __LINE__);
-        if (d_sums) GRError(hipFree(d_sums), "WorkProgress hipFree failed", __FILE__, __LINE__);
-        if (d_wide) GRError(hipFree(d_wide), "WorkProgress hipFree failed", __FILE__, __LINE__);
-        if (d_chain_log) GRError(hipFree(d_chain_log), "WorkProgress hipFree failed", __FILE__, __LINE__);
-        d_chain_log = nullptr;
-        d_tail = nullptr; d_overflow = nullptr; box = nullptr; h_tail = nullptr; h_sums = nullptr; d_sums = nullptr; d_wide = nullptr;
-    }
+    ~WorkProgress() { Live().erase(this); }  // (the words free themselves)
 };
 
 }  // namespace util

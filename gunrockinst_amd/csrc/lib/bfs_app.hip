@@ -65,7 +65,6 @@ struct BfsRunnerT : BfsRunner {
     EventPair timer;
 
     explicit BfsRunnerT(int device) : context(device), enactor(false) { timer.Create(); }
-    ~BfsRunnerT() override { FreeInverse(); }
     hipError_t Init(const Csr<int, int, int> &g) override { return problem.Init(false, g, 1); }
     hipError_t InitDevice(int nodes, int edges, int *d_ro, int *d_ci) override
     {
@@ -108,24 +107,15 @@ struct BfsRunnerT : BfsRunner {
     hipError_t BuildInverse(GraphSlice<int, int, int> *gs)
     {
         hipError_t retval = hipSuccess;
-        FreeInverse();
-        GR_CHECK(hipMalloc(&d_inv_row_offsets, sizeof(int) * (static_cast<size_t>(problem.nodes) + 1)), "BFS hipMalloc inverse offsets failed");
-        GR_CHECK(hipMalloc(&d_inv_column_indices, sizeof(int) * static_cast<size_t>(problem.edges)), "BFS hipMalloc inverse columns failed");
+        GR_CHECK(d_inv_row_offsets.Alloc(static_cast<size_t>(problem.nodes) + 1), "BFS inverse offsets failed");  // (what an earlier build made goes)
+        GR_CHECK(d_inv_column_indices.Alloc(static_cast<size_t>(problem.edges)), "BFS inverse columns failed");
         GR_CHECK(graphio::DeviceTransposeCsr(problem.nodes, problem.edges, gs->d_row_offsets, gs->d_column_indices, d_inv_row_offsets,
                                              d_inv_column_indices, gs->stream),
                  "BFS transpose failed");
         GR_CHECK(problem.SetInverseGraph(d_inv_row_offsets, d_inv_column_indices), "BFS SetInverseGraph failed");
         return retval;
     }
-    void FreeInverse()
-    {
-        if (d_inv_row_offsets) util::GRError(hipFree(d_inv_row_offsets), "BFS hipFree inverse offsets failed", __FILE__, __LINE__);
-        if (d_inv_column_indices) util::GRError(hipFree(d_inv_column_indices), "BFS hipFree inverse columns failed", __FILE__, __LINE__);
-        d_inv_row_offsets = nullptr;
-        d_inv_column_indices = nullptr;
-    }
-    int *d_inv_row_offsets = nullptr;     // in-neighbour CSR built by AutoInverse for a directed input (owned)
-    int *d_inv_column_indices = nullptr;
+    util::DeviceArray<int> d_inv_row_offsets, d_inv_column_indices;  // in-neighbour CSR built by AutoInverse for a directed input
     void SetPersistentLimit(int limit) override { problem.persistent_edge_limit = limit; }
     void SetTwcLimit(int limit) override { problem.twc_edge_limit = limit; }
     void SetCooperativeLaunch(bool on) override { problem.cooperative_launch = on; }
@@ -220,8 +210,8 @@ struct BfsRunnerT : BfsRunner {
     void DeviceResults(int **labels, int **preds) override
     {
         // (the caller-order arrays: the same pointers whichever numbering the searches run in)
-        if (labels) *labels = problem.data_slices ? problem.d_out_labels : nullptr;
-        if (preds) *preds = problem.data_slices ? problem.d_out_preds : nullptr;
+        if (labels) *labels = problem.d_out_labels;
+        if (preds) *preds = problem.d_out_preds;
     }
 };
 
@@ -465,10 +455,10 @@ int grx_filter_queue(int n, const int *d_in, const int *d_row_offsets, int capac
     typedef oprtr::filter::KernelPolicy<256, 4, 8> Policy;
     if (n < 0 || !d_out_v || !out_len || (d_row_offsets && (!d_out_row_start || !d_out_scan))) return -1;
     hipError_t retval = hipSuccess;
-    unsigned long long *d_tail = nullptr;
-    int *d_overflow = nullptr;
-    GR_CHECK(hipMalloc(&d_tail, sizeof(unsigned long long)), "grx_filter_queue hipMalloc failed");
-    GR_CHECK(hipMalloc(&d_overflow, sizeof(int)), "grx_filter_queue hipMalloc failed");
+    util::DeviceArray<unsigned long long> d_tail;
+    util::DeviceArray<int> d_overflow;
+    GR_CHECK(d_tail.Alloc(1), "grx_filter_queue tail word failed");
+    GR_CHECK(d_overflow.Alloc(1), "grx_filter_queue overflow word failed");
     GR_CHECK(hipMemset(d_tail, 0, sizeof(unsigned long long)), "grx_filter_queue memset failed");
     GR_CHECK(hipMemset(d_overflow, 0, sizeof(int)), "grx_filter_queue memset failed");
     GR_CHECK(hipDeviceSynchronize(), "grx_filter_queue sync failed");
@@ -493,8 +483,6 @@ int grx_filter_queue(int n, const int *d_in, const int *d_row_offsets, int capac
     int overflow = 0;
     if (!retval) retval = util::GRError(hipMemcpy(&tail, d_tail, sizeof(tail), hipMemcpyDeviceToHost), "grx_filter_queue read failed", __FILE__, __LINE__);
     if (!retval) retval = util::GRError(hipMemcpy(&overflow, d_overflow, sizeof(int), hipMemcpyDeviceToHost), "grx_filter_queue read failed", __FILE__, __LINE__);
-    hipFree(d_tail);
-    hipFree(d_overflow);
     if (retval) return static_cast<int>(retval);
     if (overflow) return static_cast<int>(util::GRError(hipErrorInvalidConfiguration, "Frontier queue overflow. Please increase queue-sizing factor.", __FILE__, __LINE__));
     *out_len = static_cast<int>(util::TailCount(tail));

@@ -131,7 +131,7 @@ struct MatchingRunnerT : MatchingRunner {
     {
         if (!Done()) return -1;
         // the vertex weights may be the caller's host array or a device array (the vweight of a level before)
-        int *d_upload = nullptr;
+        util::DeviceArray<int> d_upload;
         const int *d_vw = vertex_weights;
         if (vertex_weights) {
             hipPointerAttribute_t attr;
@@ -139,18 +139,14 @@ struct MatchingRunnerT : MatchingRunner {
             if (known != hipSuccess) (void)hipGetLastError();  // (a plain host pointer is no error here)
             if (known != hipSuccess || attr.type != hipMemoryTypeDevice) {
                 const size_t bytes = sizeof(int) * static_cast<size_t>(problem.nodes);
-                hipError_t rc = hipMalloc(&d_upload, bytes);
+                hipError_t rc = d_upload.Alloc(static_cast<size_t>(problem.nodes));
                 if (rc == hipSuccess) rc = hipMemcpy(d_upload, vertex_weights, bytes, hipMemcpyHostToDevice);
-                if (rc != hipSuccess) {
-                    if (d_upload) hipFree(d_upload);
-                    return static_cast<int>(rc);
-                }
+                if (rc != hipSuccess) return static_cast<int>(rc);
                 d_vw = d_upload;
             }
         }
         bool overflow = false;
         const hipError_t rc = problem.Contract(d_vw, &overflow);
-        if (d_upload) hipFree(d_upload);
         if (rc) return static_cast<int>(rc);
         if (overflow) return kOverflow;
         if (nodes) *nodes = problem.coarse_nodes;

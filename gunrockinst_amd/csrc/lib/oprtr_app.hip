@@ -181,10 +181,10 @@ int grx_advance_queue(const int *d_row_offsets, const int *d_col_indices, const 
     if (mode != GRX_ADVANCE_COUNT_ONLY && (capacity < 0 || !d_out_v)) return kBadArgument;
     if (mode == GRX_ADVANCE_FRONTIER && (!d_out_row_start || !d_out_scan)) return kBadArgument;
     hipError_t retval = hipSuccess;
-    unsigned long long *d_tail = nullptr;
-    int *d_overflow = nullptr;
-    GR_CHECK(hipMalloc(&d_tail, sizeof(unsigned long long)), "grx_advance_queue hipMalloc failed");
-    GR_CHECK(hipMalloc(&d_overflow, sizeof(int)), "grx_advance_queue hipMalloc failed");
+    util::DeviceArray<unsigned long long> d_tail;
+    util::DeviceArray<int> d_overflow;
+    GR_CHECK(d_tail.Alloc(1), "grx_advance_queue tail word failed");
+    GR_CHECK(d_overflow.Alloc(1), "grx_advance_queue overflow word failed");
     GR_CHECK(hipMemset(d_tail, 0, sizeof(unsigned long long)), "grx_advance_queue memset failed");
     GR_CHECK(hipMemset(d_overflow, 0, sizeof(int)), "grx_advance_queue memset failed");
     GR_CHECK(hipDeviceSynchronize(), "grx_advance_queue sync failed");
@@ -221,8 +221,6 @@ int grx_advance_queue(const int *d_row_offsets, const int *d_col_indices, const 
     int overflow = 0;
     if (!retval) retval = util::GRError(hipMemcpy(&tail, d_tail, sizeof(tail), hipMemcpyDeviceToHost), "grx_advance_queue read failed", __FILE__, __LINE__);
     if (!retval) retval = util::GRError(hipMemcpy(&overflow, d_overflow, sizeof(int), hipMemcpyDeviceToHost), "grx_advance_queue read failed", __FILE__, __LINE__);
-    hipFree(d_tail);
-    hipFree(d_overflow);
     if (retval) return static_cast<int>(retval);
     if (overflow) return static_cast<int>(util::GRError(hipErrorInvalidConfiguration, "Frontier queue overflow. Please increase queue-sizing factor.", __FILE__, __LINE__));
     *out_len = static_cast<int>(util::TailCount(tail));

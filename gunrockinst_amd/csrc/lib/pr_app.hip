@@ -215,16 +215,16 @@ void gunrock_topk_func(struct GunrockGraph *graph_out, void *node_ids, void *in_
     int count = topk_config.top_nodes;
     if (count > n) count = n;  // (topk_app.cu clamps the same way before Extract)
     if (n <= 0 || count <= 0) return;
-    int *d_ro = nullptr, *d_co = nullptr, *d_out3 = nullptr;
+    util::DeviceArray<int> d_ro, d_co, d_out3;
     hipStream_t stream = 0;
     graphio::DeviceKeySort sorter;
-    hipError_t rc = hipMalloc(&d_ro, sizeof(int) * (static_cast<size_t>(n) + 1));
+    hipError_t rc = d_ro.Alloc(static_cast<size_t>(n) + 1);
     if (!rc) rc = hipMemcpy(d_ro, graph_in->row_offsets, sizeof(int) * (static_cast<size_t>(n) + 1), hipMemcpyHostToDevice);
     if (!rc && graph_in->col_offsets) {
-        rc = hipMalloc(&d_co, sizeof(int) * (static_cast<size_t>(n) + 1));
+        rc = d_co.Alloc(static_cast<size_t>(n) + 1);
         if (!rc) rc = hipMemcpy(d_co, graph_in->col_offsets, sizeof(int) * (static_cast<size_t>(n) + 1), hipMemcpyHostToDevice);
     }
-    if (!rc) rc = hipMalloc(&d_out3, sizeof(int) * 3 * static_cast<size_t>(count));
+    if (!rc) rc = d_out3.Alloc(3 * static_cast<size_t>(count));
     if (!rc) rc = sorter.Reserve(n);
     unsigned long long *sorted = nullptr;
     if (!rc) {
@@ -241,9 +241,6 @@ void gunrock_topk_func(struct GunrockGraph *graph_out, void *node_ids, void *in_
     if (!rc) rc = hipMemcpy(in_degrees, d_out3 + count, sizeof(int) * count, hipMemcpyDeviceToHost);
     if (!rc) rc = hipMemcpy(out_degrees, d_out3 + 2 * count, sizeof(int) * count, hipMemcpyDeviceToHost);
     util::GRError(rc, "TOPK failed", __FILE__, __LINE__);
-    if (d_ro) hipFree(d_ro);
-    if (d_co) hipFree(d_co);
-    if (d_out3) hipFree(d_out3);
     std::printf("==> GPU Top K Degree Centrality Complete.\n");
 }
 

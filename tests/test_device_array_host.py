@@ -1,7 +1,9 @@
-"""csrc/gunrock/util/device_array.hpp and the slice holder of csrc/gunrock/app/problem_base.hpp on the host:
+"""csrc/gunrock/util/device_array.hpp and the slice holder and frontier storage of csrc/gunrock/app/problem_base.hpp on the host:
 tests/host/device_array_check.hip runs every way an owning array takes, gives up and frees a block -- scope exit, a second Alloc,
-Alloc(0), a move, Adopt of a taken array, Release, Free twice, a slice built only in part, a holder made or never made -- over a
-counting malloc / free, as a stand-alone program built with the address and undefined-behaviour sanitizers on the host side, so a
+Alloc(0), a move, Adopt of a taken array, Release, Free twice, a slice built only in part, a holder made or never made, a frontier
+queue that grows or fails to at each of its three allocations, a graph slice over its own arrays and over borrowed ones, a slice of
+raw views over owners beside it, a build with scoped scratch left at each check -- over a counting malloc / free (and one that
+fails on request), as a stand-alone program built with the address and undefined-behaviour sanitizers on the host side, so a
 leak, a double free or a use after one ends the program with a report.  No GPU."""
 import os
 import subprocess

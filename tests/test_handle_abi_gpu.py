@@ -13,7 +13,12 @@ guard their phases: the same calls there would read a slice that does not exist,
 
 The eighteen again, for the ways a problem goes: a handle closed before any init (no slice to free), a handle whose init refused
 a malformed CSR (a slice built as far as the check, freed by its members), and a fresh handle afterwards that computes what a
-clean one does."""
+clean one does.
+
+The five, whose slices are views of owners held beside them in the problem: a handle closed before any init; a CSR on the device
+that the test owns (gunrockinst_amd/devgraph.py), borrowed by one handle after the other, and intact after each close; the builds
+a handle may repeat (the relabelled copy and the inverse of BFS, the transposes SSSP and PageRank build themselves), which must
+compute what a handle that built once does; and a second init on one handle."""
 import gc
 import math
 import os
@@ -22,6 +27,7 @@ import numpy as np
 import pytest
 
 import gunrockinst_amd as ga
+from gunrockinst_amd import devgraph
 
 pytestmark = pytest.mark.gpu
 
@@ -201,3 +207,176 @@ def test_a_problem_goes_cleanly_however_far_it_was_built(graph, family):
     fresh.close()
     assert math.isfinite(ms) and ms > 0
     assert same(got, want)
+
+
+# ---- the five families the benchmark times: the slice is a view, its owners sit beside it in the problem ----
+FIVE = ("bc", "bfs", "cc", "pr", "sssp")
+FIVE_CLASSES = {"bc": ga.BcProblem, "bfs": ga.BfsProblem, "cc": ga.CcProblem, "pr": ga.PrProblem, "sssp": ga.SsspProblem}
+# the same init on a handle made earlier
+FIVE_INIT = {
+    "bc": lambda p, n, ro, ci: p.init(n, ro, ci),
+    "bfs": lambda p, n, ro, ci: p.init(n, ro, ci),
+    "cc": lambda p, n, ro, ci: p.init(n, ro, ci),
+    "pr": lambda p, n, ro, ci: p.init(n, ro, ci).set_inverse_graph(),
+    "sssp": lambda p, n, ro, ci: p.init(n, ro, ci, _weights(ci, np.uint32)),
+}
+SSSP_DELTA = 16.0  # (any bucket width: distances do not depend on it)
+
+
+@pytest.fixture(scope="module")
+def wanted(graph):
+    """what a clean handle of each of the five computes, once"""
+    out = {}
+    for family in FIVE:
+        make, run, _ = FAMILIES[family]
+        p = make(*graph)
+        out[family] = run(p)[1]
+        p.close()
+    return out
+
+
+@pytest.mark.parametrize("family", FIVE)
+def test_the_five_closed_before_any_init(graph, wanted, family):
+    make, run, same = FAMILIES[family]
+    FIVE_CLASSES[family]().close()  # no slice, no graph slice, no stream: nothing to free
+    fresh = make(*graph)
+    ms, got = run(fresh)
+    fresh.close()
+    assert math.isfinite(ms) and ms > 0
+    assert same(got, wanted[family])
+
+
+@pytest.fixture(scope="module")
+def device_graph(graph):
+    """chesapeake's CSR in device arrays the test owns, built from its (row, column) pairs by the library's device sort"""
+    import torch
+    nodes, ro, ci = graph
+    rows = torch.from_numpy(np.repeat(np.arange(nodes, dtype=np.int32), np.diff(ro))).cuda()
+    cols = torch.from_numpy(np.array(ci, dtype=np.int32)).cuda()
+    d_ro, d_ci = devgraph.csr_from_tuples_device(nodes, rows, cols, undirected=False)
+    d_w = torch.ones(ci.shape[0], dtype=torch.int32, device="cuda")  # (the bits of uint32 ones)
+    torch.cuda.synchronize()
+    return d_ro, d_ci, d_w
+
+
+def _intact(device_graph, graph):
+    d_ro, d_ci, d_w = device_graph
+    h_ro, h_ci = devgraph.to_host_csr(d_ro, d_ci)
+    return np.array_equal(h_ro, graph[1]) and np.array_equal(h_ci, graph[2]) and bool((d_w == 1).all())
+
+
+@pytest.mark.parametrize("family", FIVE)
+def test_a_borrowed_csr_outlives_the_handles_that_used_it(graph, device_graph, wanted, family):
+    nodes, _, ci = graph
+    d_ro, d_ci, d_w = device_graph
+    run, same = FAMILIES[family][1:]
+    assert _intact(device_graph, graph)
+    results = []
+    for _ in range(2):  # the second handle reads what the first one's close must not have freed
+        p = FIVE_CLASSES[family]()
+        if family == "sssp":
+            p.init_device(nodes, ci.shape[0], d_ro.data_ptr(), d_ci.data_ptr(), d_w.data_ptr(), SSSP_DELTA)
+        else:
+            p.init_device(nodes, ci.shape[0], d_ro.data_ptr(), d_ci.data_ptr())
+        if family == "pr":
+            p.set_inverse_graph()
+        ms, got = run(p)
+        p.close()
+        assert math.isfinite(ms) and ms > 0
+        assert _intact(device_graph, graph)
+        results.append(got)
+    assert same(results[0], results[1])
+    assert same(results[0], wanted[family])
+
+
+def _valid_parents(graph, labels, preds, src):
+    """every reached vertex but the source has a parent one level up that lists it; the source -1, the unreached -2"""
+    _, ro, ci = graph
+    for v, (l, p) in enumerate(zip(labels.tolist(), preds.tolist())):
+        if v == src:
+            ok = (l, p) == (0, -1)
+        elif l < 0:
+            ok = p == -2
+        else:
+            ok = p >= 0 and labels[p] == l - 1 and v in ci[ro[p]:ro[p + 1]]
+        if not ok:
+            return False
+    return True
+
+
+@pytest.mark.parametrize("mark_pred", (False, True))
+def test_bfs_rebuilds_its_copy_and_its_inverse(graph, mark_pred):
+    """The relabelled copy is built by auto_inverse(), again by another relabel_hubs, and again by a second auto_inverse(); every
+    search on the copy gives the depths of a handle that built once.  Which of several parents one level up a vertex gets is decided
+    by the order two wavefronts arrive in, on a single build as well, so parents are checked for being parents."""
+    def search(p):
+        p.reset(SRC)
+        ms = p.enact(SRC, traversal_mode=2)
+        labels, preds = p.extract()
+        assert math.isfinite(ms) and ms > 0
+        assert preds is None or _valid_parents(graph, labels, preds, SRC)
+        return labels.copy()
+
+    once = ga.BfsProblem(mark_pred=mark_pred).init(*graph)
+    assert once.auto_inverse()[0]
+    once.set_option("relabel", 1)
+    want = search(once)
+    once.close()
+    assert want[SRC] == 0 and want.max() > 0
+
+    p = ga.BfsProblem(mark_pred=mark_pred).init(*graph)
+    assert p.auto_inverse()[0]
+    p.set_option("relabel", 1)
+    hubs = p.relabel_info()["hubs"]
+    assert hubs >= 0
+    first = search(p)
+    p.set_option("relabel_hubs", 2 if hubs != 2 else 3)  # another hub tier: the copy is built again
+    assert p.relabel_info()["hubs"] != hubs
+    second = search(p)
+    assert p.auto_inverse()[0]  # the inverse and the copy once more
+    third = search(p)
+    p.close()
+    assert np.array_equal(first, want) and np.array_equal(second, want) and np.array_equal(third, want)
+
+
+def test_sssp_builds_its_inverse_twice(graph, wanted):
+    nodes, ro, ci = graph
+    results = []
+    for builds in (1, 2):
+        p = ga.SsspProblem().init(nodes, ro, ci, _weights(ci, np.uint32))
+        for _ in range(builds):
+            p.set_inverse_graph(pull_min_edges=1)  # the weighted transpose, built by the problem; every level may pull
+        _, got = FAMILIES["sssp"][1](p)
+        p.close()
+        results.append(got)
+    assert _same(results[0], results[1])
+    assert _same(results[1], wanted["sssp"])
+
+
+def test_pr_builds_its_inverse_twice(graph, wanted):
+    nodes, ro, ci = graph
+    results = []
+    for builds in (1, 2):
+        p = ga.PrProblem().init(nodes, ro, ci)
+        for _ in range(builds):
+            p.set_inverse_graph(build=True)  # the transpose, built by the problem
+        _, got = FAMILIES["pr"][1](p)
+        p.close()
+        results.append(got)
+    assert _pr_same(results[0], results[1])
+    assert _pr_same(results[1], wanted["pr"])
+
+
+@pytest.mark.parametrize("family", FIVE)
+def test_a_second_init_on_one_handle(graph, wanted, family):
+    """init, run, init again with the same graph, run: the first slice and its arrays go, the second run computes the same"""
+    run, same = FAMILIES[family][1:]
+    p = FIVE_CLASSES[family]()
+    FIVE_INIT[family](p, *graph)
+    _, first = run(p)
+    FIVE_INIT[family](p, *graph)
+    ms, second = run(p)
+    p.close()
+    assert math.isfinite(ms) and ms > 0
+    assert same(first, second)
+    assert same(second, wanted[family])
