@@ -453,8 +453,89 @@ def _p(a):
     return a.ctypes.data_as(i32p)
 
 
+def _i64p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_longlong))
+
+
+def _u8p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_ubyte))
+
+
+def _f64p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _f32p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def _u32p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint32))
+
+
+_POINTER_OF = {"int32": _p, "int64": _i64p, "uint8": _u8p, "float64": _f64p, "float32": _f32p}
+
+
+def _opt(a):
+    """None, or the pointer of a's element type"""
+    return None if a is None else _POINTER_OF[a.dtype.name](a)
+
+
+def _out(n, dtype=np.int32, wanted=True):
+    """An output array for n entries (never of size 0: the library gets a valid pointer), or None when it is not wanted"""
+    return np.empty(max(n, 1), dtype=dtype) if wanted else None
+
+
+def _cut(a, n):
+    """An output array cut back to its n entries; None stays None"""
+    return None if a is None else a[:n]
+
+
 def _i32(a):
     return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _i32_of(values, count, what, of):
+    """None, or `values` as contiguous int32 once there are `count` of them: one per entry, per node, ..."""
+    if values is None:
+        return None
+    a = _i32(values)
+    if a.shape[0] != count:
+        raise ValueError("gunrockinst_amd: %d %s for %d %s" % (a.shape[0], what, count, of))
+    return a
+
+
+def _count_then_fill(fn, h, what, dtypes, negated=False):
+    """The columns of a trace or a list behind `fn(h, capacity, *columns)`: asks for the count with no columns, allocates one
+    column per dtype, has them filled and returns them cut to the count.  A negative count raises.  The library has two
+    conventions and `negated` picks the family's: the traces return a code, reported as it is, and their fill cannot fail; the
+    lists (negated) return minus the code -- the message shows the positive number -- and their fill is checked the same way."""
+    count = fn(h, 0, *[None] * len(dtypes))
+    if count < 0:
+        _check(-count if negated else count, what)
+    columns = [_out(count, dtype) for dtype in dtypes]
+    rc = fn(h, count, *[_opt(c) for c in columns])
+    if negated and rc < 0:
+        _check(-rc, what)
+    return tuple(c[:count] for c in columns)
+
+
+_TRACE = (np.int32, np.int64, np.float64)  # the columns of a level or phase trace: (k or kind, items, milliseconds)
+
+
+def _pair_list(fn, h, what, max_edges):
+    """(first, second, count) of a sorted int32 pair list behind `fn(h, capacity, first, second)`; max_edges caps what is copied
+    (None: all, 0: the count only).  Codes come negated, as in the lists of _count_then_fill."""
+    count = fn(h, 0, None, None)
+    if count < 0:
+        _check(-count, what)
+    take = count if max_edges is None else min(count, int(max_edges))
+    a, b = _out(take), _out(take)
+    if take > 0:
+        rc = fn(h, take, _p(a), _p(b))
+        if rc < 0:
+            _check(-rc, what)
+    return a[:take], b[:take], count
 
 
 def _check_offsets(row_offsets, nodes):
@@ -495,6 +576,130 @@ class _Handle:
             self.close()
         except Exception:
             pass
+
+
+class _Problem(_Handle):
+    """One family of the handle C ABI, grx_<family>_*: the Python counterpart of handle_runner.hpp.  A subclass declares
+
+      _family              "tc" for grx_tc_*
+      _problem, _enactor   the names in messages: "TCProblem", "TCEnactor"
+      _count               the attribute that holds the number of CSR entries: "edges" or "entries" (None: not kept)
+      _stats               (int64 fields, double fields) in the order of grx_<family>_stats.  An int64 field is a name, a
+                           (name, n) pair for an array of n kept as a list, or a tuple of names for an array spread over keys
+      _results             the names of grx_<family>_device_results' pointers (device_results returns a dict), or their
+                           number (a tuple)
+
+    and writes: init / init_device where Init has trailing arguments, as one call of _init_host / _init_device; _ready() for
+    what has to be read back behind either; its extract methods; and any phase whose signature or return codes are its own.
+    reset, enact and run of the five benchmarked classes sit in the benchmark's timing loops and name their symbols directly,
+    lib().grx_bfs_enact: nothing is looked up by name there."""
+
+    _family = _problem = _enactor = None
+    _count = "edges"
+    _check_rows = True  # False: the classes that mirror the reference's Init, which takes the offsets as they come
+    _stats = ((), ())
+    _results = 0
+
+    def __init__(self, instrument=False, device=0):
+        self._create("grx_%s_create" % self._family, int(instrument), device)
+        self._sized(0, 0)
+
+    def _fn(self, phase):
+        return getattr(lib(), "grx_%s_%s" % (self._family, phase))
+
+    def close(self):
+        if self._h:
+            self._fn("destroy")(self._h)
+            self._h = None
+
+    def _sized(self, nodes, entries):
+        self.nodes = int(nodes)
+        if self._count:
+            setattr(self, self._count, int(entries))
+        return self.nodes, int(entries)
+
+    def _ready(self):
+        """called behind a successful Init: what a family reads back once (the number of its canonical edges, ...)"""
+
+    def _init_host(self, nodes, row_offsets, col_indices, *extra, per_entry=None, per_node=None):
+        """Init from host arrays.  per_entry = (values or None, "weights", "entries"): the family's optional int32 array with
+        one value per CSR entry and the words of its length check; it follows the column indices.  per_node = (values or None,
+        "ranks", "nodes"): the same with one value per vertex; it comes next.  `extra` are the trailing arguments.  The checks
+        run in this order: row offsets, per_entry, per_node."""
+        ro, ci = _csr_arrays(row_offsets, col_indices, nodes if self._check_rows else None)
+        args = [_p(ro), _p(ci)]
+        if per_entry is not None:
+            args.append(_opt(_i32_of(per_entry[0], ci.shape[0], *per_entry[1:])))
+        if per_node is not None:
+            args.append(_opt(_i32_of(per_node[0], int(nodes), *per_node[1:])))
+        _check(self._fn("init")(self._h, *self._sized(nodes, ci.shape[0]), *args, *extra), self._problem + "::Init")
+        self._ready()
+        return self
+
+    def _init_device(self, nodes, edges, d_row_offsets, d_col_indices, *extra):
+        """Init from a CSR in device memory: integer addresses (torch.Tensor.data_ptr()), borrowed.  An address among `extra`
+        goes through C.c_void_p, for which None and 0 are the null pointer."""
+        _check(self._fn("init_device")(self._h, *self._sized(nodes, edges), C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices), *extra),
+               self._problem + "::Init(device)")
+        self._ready()
+        return self
+
+    def init(self, nodes, row_offsets, col_indices):
+        return self._init_host(nodes, row_offsets, col_indices)
+
+    def init_device(self, nodes, edges, d_row_offsets, d_col_indices):
+        """d_* are integer device addresses (e.g. torch.Tensor.data_ptr()); borrowed: see the class for how long they are read"""
+        return self._init_device(nodes, edges, d_row_offsets, d_col_indices)
+
+    def reset(self):
+        _check(self._fn("reset")(self._h), self._problem + "::Reset")
+
+    def _reset_labels(self, labels):
+        """Reset of the families that start from optional int32 labels, one per vertex"""
+        _check(self._fn("reset")(self._h, _opt(_i32_of(labels, self.nodes, "labels", "nodes"))), self._problem + "::Reset")
+
+    def enact(self, max_grid_size=0):
+        """the elapsed milliseconds"""
+        return self._timed(self._fn("enact"), self._enactor + "::Enact", int(max_grid_size))
+
+    def stats(self):
+        ints, doubles = self._stats
+        slots = [C.c_longlong() if isinstance(f, str) else (C.c_longlong * (f[1] if isinstance(f[1], int) else len(f)))() for f in ints]
+        ms = [C.c_double() for _ in doubles]
+        _check(self._fn("stats")(self._h, *[C.byref(s) if isinstance(f, str) else s for f, s in zip(ints, slots)], *map(C.byref, ms)),
+               "grx_%s_stats" % self._family)
+        out = {}
+        for f, s in zip(ints, slots):
+            if isinstance(f, str):
+                out[f] = s.value
+            elif isinstance(f[1], int):
+                out[f[0]] = [int(x) for x in s]
+            else:
+                out.update(zip(f, (int(x) for x in s)))
+        out.update((name, x.value) for name, x in zip(doubles, ms))
+        return out
+
+    def _device_pointers(self, count, phase="device_results"):
+        p = [C.c_void_p() for _ in range(count)]
+        _check(self._fn(phase)(self._h, *map(C.byref, p)), "grx_%s_%s" % (self._family, phase))
+        return [x.value for x in p]
+
+    def device_results(self):
+        """the device pointers of the results, which live as long as the handle: see the class for their names or order"""
+        if isinstance(self._results, int):
+            return tuple(self._device_pointers(self._results))
+        return dict(zip(self._results, self._device_pointers(len(self._results))))
+
+
+class _TunedProblem(_Problem):
+    """A family with grx_<family>_set_option; its class docstring lists the names."""
+
+    def set_option(self, name, value):
+        """returns the library's code: 0 = set, 1 = unknown name (a value out of range raises)"""
+        rc = self._fn("set_option")(self._h, name.encode(), float(value))
+        if rc not in (0, 1):
+            _check(rc, "grx_%s_set_option(%s)" % (self._family, name))
+        return rc
 
 
 def _one_shot(problem, *steps):
@@ -592,28 +797,19 @@ class HostGraph(_Handle):
         return int(lib().grx_graph_average_degree(self._h))
 
 
-class BfsProblem(_Handle):
-    """BFSProblem + BFSEnactor behind the handle C ABI (Init once, Reset + Enact per run, Extract)."""
+class BfsProblem(_Problem):
+    """BFSProblem + BFSEnactor behind the handle C ABI (Init once, Reset + Enact per run, Extract).  reset and enact are timed
+    by the benchmark and name their symbols directly; device_results: (labels, predecessors).  The arrays given to init_device
+    are borrowed for every search and must outlive the problem."""
 
-    _destroy = "grx_bfs_destroy"
+    _family, _problem, _enactor = "bfs", "BFSProblem", "BFSEnactor"
+    _count, _check_rows = None, False
+    _results = 2
 
     def __init__(self, mark_pred=False, idempotence=False, instrument=False, device=0):
         self.mark_pred = bool(mark_pred)
         self._create("grx_bfs_create", int(mark_pred), int(idempotence), int(instrument), device)
         self.nodes = 0
-
-    def init(self, nodes, row_offsets, col_indices):
-        ro, ci = _csr_arrays(row_offsets, col_indices)
-        self.nodes = int(nodes)
-        _check(lib().grx_bfs_init(self._h, nodes, ci.shape[0], _p(ro), _p(ci)), "BFSProblem::Init")
-        return self
-
-    def init_device(self, nodes, edges, d_row_offsets, d_col_indices):
-        """d_* are integer device addresses (e.g. torch.Tensor.data_ptr()); borrowed, must outlive the problem."""
-        self.nodes = int(nodes)
-        _check(lib().grx_bfs_init_device(self._h, nodes, edges, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices)),
-               "BFSProblem::Init(device)")
-        return self
 
     def set_inverse_graph(self, d_inv_row_offsets=None, d_inv_col_indices=None, alpha=0.0, beta=0.0):
         """Enable traversal_mode=2 (direction-optimizing).  No arguments = the graph is symmetric."""
@@ -687,15 +883,9 @@ class BfsProblem(_Handle):
         return [{"frontier": fr[i], "edges": ed[i], "ms": ms[i], "kind": kd[i]} for i in range(n)]
 
     def extract(self):
-        labels = np.empty(max(self.nodes, 1), dtype=np.int32)
-        preds = np.empty(max(self.nodes, 1), dtype=np.int32) if self.mark_pred else None
-        _check(lib().grx_bfs_extract(self._h, _p(labels), None if preds is None else _p(preds)), "BFSProblem::Extract")
-        return labels[:self.nodes], (None if preds is None else preds[:self.nodes])
-
-    def device_results(self):
-        dl, dp = C.c_void_p(), C.c_void_p()
-        _check(lib().grx_bfs_device_results(self._h, C.byref(dl), C.byref(dp)), "grx_bfs_device_results")
-        return dl.value, dp.value
+        labels, preds = _out(self.nodes), _out(self.nodes, wanted=self.mark_pred)
+        _check(lib().grx_bfs_extract(self._h, _p(labels), _opt(preds)), "BFSProblem::Extract")
+        return labels[:self.nodes], _cut(preds, self.nodes)
 
     def mask_flushes(self):
         """kept level bitmaps flushed into the labels in the middle of a search, over the handle's life"""
@@ -758,26 +948,13 @@ def gunrock_bfs(nodes, row_offsets, col_indices, src=0, mark_pred=False, idempot
     return _take_node_values(gout, nodes, np.int32)
 
 
-class CcProblem(_Handle):
-    """CCProblem + CCEnactor behind the handle C ABI."""
+class CcProblem(_Problem):
+    """CCProblem + CCEnactor behind the handle C ABI.  reset and enact are timed by the benchmark and name their symbols
+    directly."""
 
-    _destroy = "grx_cc_destroy"
-
-    def __init__(self, instrument=False, device=0):
-        self._create("grx_cc_create", int(instrument), device)
-        self.nodes = 0
-
-    def init(self, nodes, row_offsets, col_indices):
-        ro, ci = _csr_arrays(row_offsets, col_indices)
-        self.nodes = int(nodes)
-        _check(lib().grx_cc_init(self._h, nodes, ci.shape[0], _p(ro), _p(ci)), "CCProblem::Init")
-        return self
-
-    def init_device(self, nodes, edges, d_row_offsets, d_col_indices):
-        self.nodes = int(nodes)
-        _check(lib().grx_cc_init_device(self._h, nodes, edges, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices)),
-               "CCProblem::Init(device)")
-        return self
+    _family, _problem, _enactor = "cc", "CCProblem", "CCEnactor"
+    _count, _check_rows = None, False
+    _stats = (("edge_sweeps", "vertex_sweeps", "kernel_launches"), ("kernel_ms",))
 
     def reset(self):
         _check(lib().grx_cc_reset(self._h), "CCProblem::Reset")
@@ -786,26 +963,21 @@ class CcProblem(_Handle):
         return self._timed(lib().grx_cc_enact, "CCEnactor::Enact", max_grid_size)
 
     def stats(self):
-        es, vs, l = C.c_longlong(), C.c_longlong(), C.c_longlong()
-        k = C.c_double()
-        _check(lib().grx_cc_stats(self._h, C.byref(es), C.byref(vs), C.byref(l), C.byref(k)), "grx_cc_stats")
-        mir = C.c_int()
+        out = super().stats()
+        mir, se = C.c_int(), C.c_longlong()
         _check(lib().grx_cc_mirrored(self._h, C.byref(mir)), "grx_cc_mirrored")
-        se = C.c_longlong()
         _check(lib().grx_cc_sweep_edges(self._h, C.byref(se)), "grx_cc_sweep_edges")
-        return {"edge_sweeps": es.value, "vertex_sweeps": vs.value, "kernel_launches": l.value, "kernel_ms": k.value,
-                "mirrored": bool(mir.value), "sweep_edges": se.value}
+        out["mirrored"], out["sweep_edges"] = bool(mir.value), se.value
+        return out
 
     def extract(self):
-        ids = np.empty(max(self.nodes, 1), dtype=np.int32)
-        nc = C.c_uint()
+        ids, nc = _out(self.nodes), C.c_uint()
         _check(lib().grx_cc_extract(self._h, _p(ids), C.byref(nc)), "CCProblem::Extract")
         return ids[:self.nodes], int(nc.value)
 
     def device_results(self):
-        d = C.c_void_p()
-        _check(lib().grx_cc_device_results(self._h, C.byref(d)), "grx_cc_device_results")
-        return d.value
+        """the device pointer of the component ids"""
+        return self._device_pointers(1)[0]
 
 
 def gunrock_cc(nodes, row_offsets, col_indices, device=0):
@@ -820,44 +992,18 @@ def gunrock_cc(nodes, row_offsets, col_indices, device=0):
     return _take_node_values(gout, nodes, np.int32)
 
 
-class MstProblem(_Handle):
+class MstProblem(_Problem):
     """MSTProblem + MSTEnactor behind the handle C ABI: the minimum spanning forest of the CSR read as an undirected multigraph,
     unique under the order (weight as int32, then CSR index)."""
 
-    _destroy = "grx_mst_destroy"
-
-    def __init__(self, instrument=False, device=0):
-        self._create("grx_mst_create", int(instrument), device)
-        self.nodes = 0
-        self.edges = 0
+    _family, _problem, _enactor = "mst", "MSTProblem", "MSTEnactor"
+    _stats = (("rounds", "edges_scanned", "kernel_launches"), ("kernel_ms",))
 
     def init(self, nodes, row_offsets, col_indices, edge_values):
-        ro, ci = _csr_arrays(row_offsets, col_indices)
-        w = _i32(edge_values)
-        if w.shape[0] != ci.shape[0]:
-            raise ValueError("gunrockinst_amd: %d edge values for %d edges" % (w.shape[0], ci.shape[0]))
-        _check_offsets(ro, nodes)
-        self.nodes, self.edges = int(nodes), int(ci.shape[0])
-        _check(lib().grx_mst_init(self._h, self.nodes, self.edges, _p(ro), _p(ci), _p(w)), "MSTProblem::Init")
-        return self
+        return self._init_host(nodes, row_offsets, col_indices, per_entry=(_i32(edge_values), "edge values", "edges"))
 
     def init_device(self, nodes, edges, d_row_offsets, d_col_indices, d_edge_values):
-        self.nodes, self.edges = int(nodes), int(edges)
-        _check(lib().grx_mst_init_device(self._h, self.nodes, self.edges, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices),
-                                         C.c_void_p(d_edge_values)), "MSTProblem::Init(device)")
-        return self
-
-    def reset(self):
-        _check(lib().grx_mst_reset(self._h), "MSTProblem::Reset")
-
-    def enact(self, max_grid_size=0):
-        return self._timed(lib().grx_mst_enact, "MSTEnactor::Enact", max_grid_size)
-
-    def stats(self):
-        r, s, l = C.c_longlong(), C.c_longlong(), C.c_longlong()
-        k = C.c_double()
-        _check(lib().grx_mst_stats(self._h, C.byref(r), C.byref(s), C.byref(l), C.byref(k)), "grx_mst_stats")
-        return {"rounds": r.value, "edges_scanned": s.value, "kernel_launches": l.value, "kernel_ms": k.value}
+        return self._init_device(nodes, edges, d_row_offsets, d_col_indices, C.c_void_p(d_edge_values))
 
     def round_trace(self, max_rounds=1024):
         entries = (C.c_longlong * max_rounds)()
@@ -868,15 +1014,14 @@ class MstProblem(_Handle):
 
     def extract(self, selected=True):
         """(selected 0/1 per CSR entry as int32, or None; total_weight; forest_edges)"""
-        sel = np.empty(max(self.edges, 1), dtype=np.int32) if selected else None
+        sel = _out(self.edges, wanted=selected)
         tw, fe = C.c_longlong(), C.c_int()
-        _check(lib().grx_mst_extract(self._h, None if sel is None else _p(sel), C.byref(tw), C.byref(fe)), "MSTProblem::Extract")
-        return (None if sel is None else sel[:self.edges]), int(tw.value), int(fe.value)
+        _check(lib().grx_mst_extract(self._h, _opt(sel), C.byref(tw), C.byref(fe)), "MSTProblem::Extract")
+        return _cut(sel, self.edges), int(tw.value), int(fe.value)
 
     def device_results(self):
-        d = C.c_void_p()
-        _check(lib().grx_mst_device_results(self._h, C.byref(d)), "grx_mst_device_results")
-        return d.value
+        """the device pointer of the selected flags"""
+        return self._device_pointers(1)[0]
 
 
 def gunrock_mst(nodes, row_offsets, col_indices, edge_values, device=0):
@@ -900,51 +1045,26 @@ def mis_priorities(nodes, seed=0):
     return h.astype(np.uint32)
 
 
-class MisProblem(_Handle):
+class MisProblem(_Problem):
     """MISProblem + MISEnactor behind the handle C ABI: the lexicographically first maximal independent set and the two greedy
     colourings of the CSR read as an undirected simple graph, unique under the order key(v) = (prio(v), v)."""
 
-    _destroy = "grx_mis_destroy"
-
-    def __init__(self, instrument=False, device=0):
-        self._create("grx_mis_create", int(instrument), device)
-        self.nodes = 0
-        self.edges = 0
+    _family, _problem, _enactor = "mis", "MISProblem", "MISEnactor"
+    _stats = (("rounds", "tail_sweeps", "entries_read", "polls", "kernel_launches"), ("kernel_ms",))
 
     def init(self, nodes, row_offsets, col_indices, priorities=None, seed=0):
-        ro, ci = _csr_arrays(row_offsets, col_indices)
-        pr = None if priorities is None else _i32(priorities)
-        if pr is not None and pr.shape[0] != int(nodes):
-            raise ValueError("gunrockinst_amd: %d priorities for %d nodes" % (pr.shape[0], int(nodes)))
-        _check_offsets(ro, nodes)
-        self.nodes, self.edges = int(nodes), int(ci.shape[0])
-        _check(lib().grx_mis_init(self._h, self.nodes, self.edges, _p(ro), _p(ci), None if pr is None else _p(pr),
-                                  int(seed) & 0xFFFFFFFF), "MISProblem::Init")
-        return self
+        return self._init_host(nodes, row_offsets, col_indices, int(seed) & 0xFFFFFFFF, per_node=(priorities, "priorities", "nodes"))
 
     def init_device(self, nodes, edges, d_row_offsets, d_col_indices, d_priorities=None, seed=0):
-        self.nodes, self.edges = int(nodes), int(edges)
-        _check(lib().grx_mis_init_device(self._h, self.nodes, self.edges, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices),
-                                         C.c_void_p(d_priorities), int(seed) & 0xFFFFFFFF), "MISProblem::Init(device)")
-        return self
+        return self._init_device(nodes, edges, d_row_offsets, d_col_indices, C.c_void_p(d_priorities), int(seed) & 0xFFFFFFFF)
 
     def set_tail(self, enable=True):
         """False: one launch and one read-back per round to the end instead of the device-side tail loop (same result)"""
         _check(lib().grx_mis_set_tail(self._h, int(bool(enable))), "grx_mis_set_tail")
         return self
 
-    def reset(self):
-        _check(lib().grx_mis_reset(self._h), "MISProblem::Reset")
-
     def enact(self, mode=MIS_SET, max_grid_size=0):
-        return self._timed(lib().grx_mis_enact, "MISEnactor::Enact", int(mode), max_grid_size)
-
-    def stats(self):
-        r, t, e, q, l = C.c_longlong(), C.c_longlong(), C.c_longlong(), C.c_longlong(), C.c_longlong()
-        k = C.c_double()
-        _check(lib().grx_mis_stats(self._h, C.byref(r), C.byref(t), C.byref(e), C.byref(q), C.byref(l), C.byref(k)), "grx_mis_stats")
-        return {"rounds": r.value, "tail_sweeps": t.value, "entries_read": e.value, "polls": q.value, "kernel_launches": l.value,
-                "kernel_ms": k.value}
+        return self._timed(lib().grx_mis_enact, "MISEnactor::Enact", int(mode), int(max_grid_size))
 
     def round_trace(self, max_rounds=4096):
         vertices = (C.c_longlong * max_rounds)()
@@ -955,15 +1075,13 @@ class MisProblem(_Handle):
 
     def extract(self, ids=True):
         """(ids as int32 per vertex, or None; summary = the size of the set or the number of colours)"""
-        out = np.empty(max(self.nodes, 1), dtype=np.int32) if ids else None
-        summary = C.c_longlong()
-        _check(lib().grx_mis_extract(self._h, None if out is None else _p(out), C.byref(summary)), "MISProblem::Extract")
-        return (None if out is None else out[:self.nodes]), int(summary.value)
+        out, summary = _out(self.nodes, wanted=ids), C.c_longlong()
+        _check(lib().grx_mis_extract(self._h, _opt(out), C.byref(summary)), "MISProblem::Extract")
+        return _cut(out, self.nodes), int(summary.value)
 
     def device_results(self):
-        d = C.c_void_p()
-        _check(lib().grx_mis_device_results(self._h, C.byref(d)), "grx_mis_device_results")
-        return d.value
+        """the device pointer of the ids"""
+        return self._device_pointers(1)[0]
 
 
 def _mis_one_shot(mode, nodes, row_offsets, col_indices, priorities, seed, device):
@@ -986,72 +1104,29 @@ def gunrock_color(nodes, row_offsets, col_indices, priorities=None, seed=0, firs
 TC_AUTO, TC_LANE, TC_LDS, TC_GLOBAL = 0, 1, 2, 3  # enum GRX_TC_* (gunrock_mi355x.h)
 
 
-class TcProblem(_Handle):
+class TcProblem(_TunedProblem):
     """TCProblem + TCEnactor behind the handle C ABI: per-vertex triangle counts (int64), their total, clustering coefficients and
-    the transitivity of the CSR read as an undirected simple graph."""
+    the transitivity of the CSR read as an undirected simple graph.
 
-    _destroy = "grx_tc_destroy"
+    Options: "strategy" (TC_AUTO / TC_LANE / TC_LDS / TC_GLOBAL), "lds_entries", "lane_max_row".
+    device_results: (device pointer of the int64 counts, device pointer of the int32 degrees)."""
 
-    def __init__(self, instrument=False, device=0):
-        self._create("grx_tc_create", int(instrument), device)
-        self.nodes = 0
-        self.edges = 0
-
-    def init(self, nodes, row_offsets, col_indices):
-        ro, ci = _csr_arrays(row_offsets, col_indices, nodes)
-        self.nodes, self.edges = int(nodes), int(ci.shape[0])
-        _check(lib().grx_tc_init(self._h, self.nodes, self.edges, _p(ro), _p(ci)), "TCProblem::Init")
-        return self
-
-    def init_device(self, nodes, edges, d_row_offsets, d_col_indices):
-        self.nodes, self.edges = int(nodes), int(edges)
-        _check(lib().grx_tc_init_device(self._h, self.nodes, self.edges, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices)),
-               "TCProblem::Init(device)")
-        return self
-
-    def set_option(self, name, value):
-        """"strategy" (TC_AUTO / TC_LANE / TC_LDS / TC_GLOBAL), "lds_entries", "lane_max_row"; returns the library's code:
-        0 = set, 1 = unknown name (a value out of range raises)"""
-        rc = lib().grx_tc_set_option(self._h, name.encode(), float(value))
-        if rc not in (0, 1):
-            _check(rc, "grx_tc_set_option(%s)" % name)
-        return rc
-
-    def reset(self):
-        _check(lib().grx_tc_reset(self._h), "TCProblem::Reset")
-
-    def enact(self, max_grid_size=0):
-        return self._timed(lib().grx_tc_enact, "TCEnactor::Enact", max_grid_size)
-
-    def stats(self):
-        o, r, e, l = C.c_longlong(), C.c_longlong(), C.c_longlong(), C.c_longlong()
-        rows = (C.c_longlong * 3)()
-        k, b = C.c_double(), C.c_double()
-        _check(lib().grx_tc_stats(self._h, C.byref(o), C.byref(r), C.byref(e), C.byref(l), rows, C.byref(k), C.byref(b)), "grx_tc_stats")
-        return {"oriented_edges": o.value, "max_out_row": r.value, "entries_probed": e.value, "kernel_launches": l.value,
-                "lane_rows": rows[0], "lds_rows": rows[1], "global_rows": rows[2], "kernel_ms": k.value, "build_ms": b.value}
+    _family, _problem, _enactor = "tc", "TCProblem", "TCEnactor"
+    _stats = (("oriented_edges", "max_out_row", "entries_probed", "kernel_launches", ("lane_rows", "lds_rows", "global_rows")),
+              ("kernel_ms", "build_ms"))
+    _results = 2
 
     def extract(self, triangles=True):
         """(triangles as int64 per vertex, or None; the number of triangles of the graph)"""
-        out = np.empty(max(self.nodes, 1), dtype=np.int64) if triangles else None
-        total = C.c_longlong()
-        _check(lib().grx_tc_extract(self._h, None if out is None else out.ctypes.data_as(C.POINTER(C.c_longlong)), C.byref(total)),
-               "TCProblem::Extract")
-        return (None if out is None else out[:self.nodes]), int(total.value)
+        out, total = _out(self.nodes, np.int64, triangles), C.c_longlong()
+        _check(lib().grx_tc_extract(self._h, _opt(out), C.byref(total)), "TCProblem::Extract")
+        return _cut(out, self.nodes), int(total.value)
 
     def clustering(self, coefficients=True):
         """(clustering coefficient as float64 per vertex, or None; the transitivity of the graph)"""
-        out = np.empty(max(self.nodes, 1), dtype=np.float64) if coefficients else None
-        t = C.c_double()
-        _check(lib().grx_tc_clustering(self._h, None if out is None else out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(t)),
-               "TCProblem::Clustering")
-        return (None if out is None else out[:self.nodes]), float(t.value)
-
-    def device_results(self):
-        """(device pointer of the int64 counts, device pointer of the int32 degrees)"""
-        t, d = C.c_void_p(), C.c_void_p()
-        _check(lib().grx_tc_device_results(self._h, C.byref(t), C.byref(d)), "grx_tc_device_results")
-        return t.value, d.value
+        out, t = _out(self.nodes, np.float64, coefficients), C.c_double()
+        _check(lib().grx_tc_clustering(self._h, _opt(out), C.byref(t)), "TCProblem::Clustering")
+        return _cut(out, self.nodes), float(t.value)
 
 
 def gunrock_tc(nodes, row_offsets, col_indices, device=0):
@@ -1067,96 +1142,41 @@ def gunrock_clustering(nodes, row_offsets, col_indices, device=0):
 KCORE_AUTO, KCORE_ROUNDS, KCORE_DEVICE_LOOP = 0, 1, 2  # enum GRX_KCORE_* (gunrock_mi355x.h)
 
 
-class KcoreProblem(_Handle):
+class KcoreProblem(_TunedProblem):
     """KcoreProblem + KcoreEnactor behind the handle C ABI: the core number of every vertex (int32), the degeneracy, the shell
-    sizes and the k-cores of the CSR read as an undirected simple graph."""
+    sizes and the k-cores of the CSR read as an undirected simple graph.
 
-    _destroy = "grx_kcore_destroy"
+    Options: "schedule" (KCORE_AUTO / KCORE_ROUNDS / KCORE_DEVICE_LOOP), "compact_below", "wave_min_row", "loop_max_list",
+    "loop_max_entries".
+    device_results: (device pointer of the int32 core numbers, device pointer of the int32 degrees)."""
 
-    _STATS = ("simple_edges", "max_degree", "levels", "rounds", "vertices_peeled", "entries_read", "compactions", "kernel_launches")
-
-    def __init__(self, instrument=False, device=0):
-        self._create("grx_kcore_create", int(instrument), device)
-        self.nodes = 0
-        self.edges = 0
-
-    def init(self, nodes, row_offsets, col_indices):
-        ro, ci = _csr_arrays(row_offsets, col_indices, nodes)
-        self.nodes, self.edges = int(nodes), int(ci.shape[0])
-        _check(lib().grx_kcore_init(self._h, self.nodes, self.edges, _p(ro), _p(ci)), "KcoreProblem::Init")
-        return self
-
-    def init_device(self, nodes, edges, d_row_offsets, d_col_indices):
-        self.nodes, self.edges = int(nodes), int(edges)
-        _check(lib().grx_kcore_init_device(self._h, self.nodes, self.edges, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices)),
-               "KcoreProblem::Init(device)")
-        return self
-
-    def set_option(self, name, value):
-        """"schedule" (KCORE_AUTO / KCORE_ROUNDS / KCORE_DEVICE_LOOP), "compact_below", "wave_min_row", "loop_max_list",
-        "loop_max_entries"; returns the library's code: 0 = set, 1 = unknown name (a value out of range raises)"""
-        rc = lib().grx_kcore_set_option(self._h, name.encode(), float(value))
-        if rc not in (0, 1):
-            _check(rc, "grx_kcore_set_option(%s)" % name)
-        return rc
-
-    def reset(self):
-        _check(lib().grx_kcore_reset(self._h), "KcoreProblem::Reset")
+    _family, _problem, _enactor = "kcore", "KcoreProblem", "KcoreEnactor"
+    _stats = (("simple_edges", "max_degree", "levels", "rounds", "vertices_peeled", "entries_read", "compactions", "kernel_launches"),
+              ("kernel_ms", "build_ms"))
+    _results = 2
 
     def enact(self, k_limit=-1, max_grid_size=0):
-        return self._timed(lib().grx_kcore_enact, "KcoreEnactor::Enact", int(k_limit), max_grid_size)
-
-    def stats(self):
-        v = [C.c_longlong() for _ in self._STATS]
-        k, b = C.c_double(), C.c_double()
-        _check(lib().grx_kcore_stats(self._h, *([C.byref(x) for x in v] + [C.byref(k), C.byref(b)])), "grx_kcore_stats")
-        out = {name: x.value for name, x in zip(self._STATS, v)}
-        out["kernel_ms"], out["build_ms"] = k.value, b.value
-        return out
+        return self._timed(lib().grx_kcore_enact, "KcoreEnactor::Enact", int(k_limit), int(max_grid_size))
 
     def level_trace(self):
         """the non-empty levels of the last enact: (k as int32, vertices peeled at it as int64, milliseconds as float64)"""
-        count = lib().grx_kcore_level_trace(self._h, 0, None, None, None)
-        if count < 0:
-            _check(count, "grx_kcore_level_trace")
-        k = np.empty(max(count, 1), dtype=np.int32)
-        vertices = np.empty(max(count, 1), dtype=np.int64)
-        ms = np.empty(max(count, 1), dtype=np.float64)
-        lib().grx_kcore_level_trace(self._h, count, _p(k), vertices.ctypes.data_as(C.POINTER(C.c_longlong)),
-                                    ms.ctypes.data_as(C.POINTER(C.c_double)))
-        return k[:count], vertices[:count], ms[:count]
+        return _count_then_fill(lib().grx_kcore_level_trace, self._h, "grx_kcore_level_trace", _TRACE)
 
     def extract(self, core=True):
         """(core numbers as int32 per vertex, or None; the degeneracy)"""
-        out = np.empty(max(self.nodes, 1), dtype=np.int32) if core else None
-        d = C.c_int()
-        _check(lib().grx_kcore_extract(self._h, None if out is None else _p(out), C.byref(d)), "KcoreProblem::Extract")
-        return (None if out is None else out[:self.nodes]), int(d.value)
+        out, d = _out(self.nodes, wanted=core), C.c_int()
+        _check(lib().grx_kcore_extract(self._h, _opt(out), C.byref(d)), "KcoreProblem::Extract")
+        return _cut(out, self.nodes), int(d.value)
 
     def shells(self):
         """shell sizes as int64: entry k is the number of vertices with core number k, k = 0 .. degeneracy"""
-        count = lib().grx_kcore_shells(self._h, 0, None)
-        if count < 0:
-            _check(-count, "KcoreProblem::Shells")
-        out = np.empty(max(count, 1), dtype=np.int64)
-        rc = lib().grx_kcore_shells(self._h, count, out.ctypes.data_as(C.POINTER(C.c_longlong)))
-        if rc < 0:
-            _check(-rc, "KcoreProblem::Shells")
-        return out[:count]
+        return _count_then_fill(lib().grx_kcore_shells, self._h, "KcoreProblem::Shells", (np.int64,), negated=True)[0]
 
     def members(self, k, mask=True):
         """the k-core: (mask core >= k as uint8 per vertex, or None; its vertices; the edges of the graph inside it)"""
-        out = np.empty(max(self.nodes, 1), dtype=np.uint8) if mask else None
-        v, e = C.c_longlong(), C.c_longlong()
-        _check(lib().grx_kcore_members(self._h, int(k), None if out is None else out.ctypes.data_as(C.POINTER(C.c_ubyte)), C.byref(v),
-                                       C.byref(e)), "KcoreProblem::Members")
-        return (None if out is None else out[:self.nodes]), int(v.value), int(e.value)
-
-    def device_results(self):
-        """(device pointer of the int32 core numbers, device pointer of the int32 degrees)"""
-        c, d = C.c_void_p(), C.c_void_p()
-        _check(lib().grx_kcore_device_results(self._h, C.byref(c), C.byref(d)), "grx_kcore_device_results")
-        return c.value, d.value
+        out, v, e = _out(self.nodes, np.uint8, mask), C.c_longlong(), C.c_longlong()
+        _check(lib().grx_kcore_members(self._h, int(k), _opt(out), C.byref(v), C.byref(e)), "KcoreProblem::Members")
+        return _cut(out, self.nodes), int(v.value), int(e.value)
 
 
 def gunrock_kcore(nodes, row_offsets, col_indices, device=0):
@@ -1174,131 +1194,79 @@ def gunrock_kcore_members(nodes, row_offsets, col_indices, k, device=0):
 TRUSS_AUTO, TRUSS_ROUNDS = 0, 1  # enum GRX_TRUSS_* (gunrock_mi355x.h)
 
 
-class TrussProblem(_Handle):
-    """TrussProblem + TrussEnactor behind the handle C ABI: the triangle support and the truss number of every edge (int32, in
-    the canonical edge order: (a, b) with a < b, sorted), the truss classes, the k-trusses and the per-vertex maximum, of the CSR
-    read as an undirected simple graph."""
+class _EdgeListProblem(_TunedProblem):
+    """A family over the canonical edges of the simple graph, (a, b) with a < b, sorted: their number, simple_edges, is read back
+    behind Init and edges() returns them."""
 
-    _destroy = "grx_truss_destroy"
-
-    _STATS = ("simple_edges", "triangles", "max_support", "levels", "rounds", "edges_peeled", "support_entries", "peel_entries",
-              "kernel_launches", "readbacks")
+    _count = "entries"
 
     def __init__(self, instrument=False, device=0):
-        self._create("grx_truss_create", int(instrument), device)
-        self.nodes = 0
-        self.entries = 0
+        super().__init__(instrument, device)
         self.simple_edges = 0
 
-    def _ready(self):
-        m = lib().grx_truss_edges(self._h, None, None)
+    def _edge_list(self, src, dst):
+        m = self._fn("edges")(self._h, _opt(src), _opt(dst))
         if m < 0:
-            _check(-m, "TrussProblem::Edges")
-        self.simple_edges = int(m)
+            _check(-m, self._problem + "::Edges")
+        return int(m)
 
-    def init(self, nodes, row_offsets, col_indices):
-        ro, ci = _csr_arrays(row_offsets, col_indices, nodes)
-        self.nodes, self.entries = int(nodes), int(ci.shape[0])
-        _check(lib().grx_truss_init(self._h, self.nodes, self.entries, _p(ro), _p(ci)), "TrussProblem::Init")
-        self._ready()
-        return self
-
-    def init_device(self, nodes, edges, d_row_offsets, d_col_indices):
-        self.nodes, self.entries = int(nodes), int(edges)
-        _check(lib().grx_truss_init_device(self._h, self.nodes, self.entries, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices)),
-               "TrussProblem::Init(device)")
-        self._ready()
-        return self
-
-    def set_option(self, name, value):
-        """"schedule" (TRUSS_AUTO / TRUSS_ROUNDS), "wave_min_row", "loop_max_list", "loop_max_entries"; returns the library's
-        code: 0 = set, 1 = unknown name (a value out of range raises)"""
-        rc = lib().grx_truss_set_option(self._h, name.encode(), float(value))
-        if rc not in (0, 1):
-            _check(rc, "grx_truss_set_option(%s)" % name)
-        return rc
-
-    def reset(self):
-        _check(lib().grx_truss_reset(self._h), "TrussProblem::Reset")
-
-    def enact(self, k_limit=-1, max_grid_size=0):
-        return self._timed(lib().grx_truss_enact, "TrussEnactor::Enact", int(k_limit), max_grid_size)
-
-    def stats(self):
-        v = [C.c_longlong() for _ in self._STATS]
-        d = [C.c_double() for _ in range(3)]
-        _check(lib().grx_truss_stats(self._h, *[C.byref(x) for x in v + d]), "grx_truss_stats")
-        out = {name: x.value for name, x in zip(self._STATS, v)}
-        out["kernel_ms"], out["build_ms"], out["support_ms"] = (x.value for x in d)
-        return out
-
-    def level_trace(self):
-        """the non-empty levels of the last enact: (k as int32, edges peeled at it as int64, milliseconds as float64)"""
-        count = lib().grx_truss_level_trace(self._h, 0, None, None, None)
-        if count < 0:
-            _check(count, "grx_truss_level_trace")
-        k = np.empty(max(count, 1), dtype=np.int32)
-        edges = np.empty(max(count, 1), dtype=np.int64)
-        ms = np.empty(max(count, 1), dtype=np.float64)
-        lib().grx_truss_level_trace(self._h, count, _p(k), edges.ctypes.data_as(C.POINTER(C.c_longlong)),
-                                    ms.ctypes.data_as(C.POINTER(C.c_double)))
-        return k[:count], edges[:count], ms[:count]
-
-    def _edge_array(self, dtype=np.int32):
-        return np.empty(max(self.simple_edges, 1), dtype=dtype)
+    def _ready(self):
+        self.simple_edges = self._edge_list(None, None)
 
     def edges(self):
         """the canonical edges (src, dst) as int32, src < dst, sorted by (src, dst)"""
-        src, dst = self._edge_array(), self._edge_array()
-        m = lib().grx_truss_edges(self._h, _p(src), _p(dst))
-        if m < 0:
-            _check(-m, "TrussProblem::Edges")
+        src, dst = _out(self.simple_edges), _out(self.simple_edges)
+        m = self._edge_list(src, dst)
         return src[:m], dst[:m]
+
+
+class TrussProblem(_EdgeListProblem):
+    """TrussProblem + TrussEnactor behind the handle C ABI: the triangle support and the truss number of every edge (int32, in
+    the canonical edge order: (a, b) with a < b, sorted), the truss classes, the k-trusses and the per-vertex maximum, of the CSR
+    read as an undirected simple graph.
+
+    Options: "schedule" (TRUSS_AUTO / TRUSS_ROUNDS), "wave_min_row", "loop_max_list", "loop_max_entries".
+    device_results: device pointers of the int32 arrays (truss, support, src, dst), simple_edges entries each."""
+
+    _family, _problem, _enactor = "truss", "TrussProblem", "TrussEnactor"
+    _stats = (("simple_edges", "triangles", "max_support", "levels", "rounds", "edges_peeled", "support_entries", "peel_entries",
+               "kernel_launches", "readbacks"), ("kernel_ms", "build_ms", "support_ms"))
+    _results = 4
+
+    def enact(self, k_limit=-1, max_grid_size=0):
+        return self._timed(lib().grx_truss_enact, "TrussEnactor::Enact", int(k_limit), int(max_grid_size))
+
+    def level_trace(self):
+        """the non-empty levels of the last enact: (k as int32, edges peeled at it as int64, milliseconds as float64)"""
+        return _count_then_fill(lib().grx_truss_level_trace, self._h, "grx_truss_level_trace", _TRACE)
 
     def support(self):
         """(triangles per edge as int32, the triangles of the graph); valid after init"""
-        out = self._edge_array()
-        total = C.c_longlong()
+        out, total = _out(self.simple_edges), C.c_longlong()
         _check(lib().grx_truss_support(self._h, _p(out), C.byref(total)), "TrussProblem::Support")
         return out[:self.simple_edges], int(total.value)
 
     def extract(self, truss=True):
         """(truss numbers as int32 per edge, or None; the largest)"""
-        out = self._edge_array() if truss else None
-        top = C.c_int()
-        _check(lib().grx_truss_extract(self._h, None if out is None else _p(out), C.byref(top)), "TrussProblem::Extract")
-        return (None if out is None else out[:self.simple_edges]), int(top.value)
+        out, top = _out(self.simple_edges, wanted=truss), C.c_int()
+        _check(lib().grx_truss_extract(self._h, _opt(out), C.byref(top)), "TrussProblem::Extract")
+        return _cut(out, self.simple_edges), int(top.value)
 
     def classes(self):
         """class sizes as int64: entry k is the number of edges with truss number k, k = 0 .. max_truss"""
-        count = lib().grx_truss_classes(self._h, 0, None)
-        if count < 0:
-            _check(-count, "TrussProblem::Classes")
-        out = np.empty(max(count, 1), dtype=np.int64)
-        rc = lib().grx_truss_classes(self._h, count, out.ctypes.data_as(C.POINTER(C.c_longlong)))
-        if rc < 0:
-            _check(-rc, "TrussProblem::Classes")
-        return out[:count]
+        return _count_then_fill(lib().grx_truss_classes, self._h, "TrussProblem::Classes", (np.int64,), negated=True)[0]
 
     def members(self, k, mask=True):
         """the k-truss: (mask truss >= k as uint8 per edge, or None; its edges; the vertices at one of them)"""
-        out = self._edge_array(np.uint8) if mask else None
-        e, v = C.c_longlong(), C.c_longlong()
-        _check(lib().grx_truss_members(self._h, int(k), None if out is None else out.ctypes.data_as(C.POINTER(C.c_ubyte)), C.byref(e),
-                                       C.byref(v)), "TrussProblem::Members")
-        return (None if out is None else out[:self.simple_edges]), int(e.value), int(v.value)
+        out, e, v = _out(self.simple_edges, np.uint8, mask), C.c_longlong(), C.c_longlong()
+        _check(lib().grx_truss_members(self._h, int(k), _opt(out), C.byref(e), C.byref(v)), "TrussProblem::Members")
+        return _cut(out, self.simple_edges), int(e.value), int(v.value)
 
     def vertex_truss(self):
         """the largest truss number over the edges at every vertex, int32; 0 without a neighbour"""
-        out = np.empty(max(self.nodes, 1), dtype=np.int32)
+        out = _out(self.nodes)
         _check(lib().grx_truss_vertex_truss(self._h, _p(out)), "TrussProblem::VertexTruss")
         return out[:self.nodes]
-
-    def device_results(self):
-        """device pointers of the int32 arrays (truss, support, src, dst), simple_edges entries each"""
-        p = [C.c_void_p() for _ in range(4)]
-        _check(lib().grx_truss_device_results(self._h, *[C.byref(x) for x in p]), "grx_truss_device_results")
-        return tuple(x.value for x in p)
 
 
 def gunrock_truss(nodes, row_offsets, col_indices, device=0):
@@ -1322,107 +1290,50 @@ SCC_AUTO, SCC_ROUNDS, SCC_DEVICE_LOOP = 0, 1, 2  # enum GRX_SCC_* (gunrock_mi355
 SCC_TRIM, SCC_PIVOT, SCC_COLOUR = 0, 1, 2  # enum GRX_SCC_PHASE_* (gunrock_mi355x.h): the kinds of phase_trace()
 
 
-class SccProblem(_Handle):
+class SccProblem(_TunedProblem):
     """SccProblem + SccEnactor behind the handle C ABI: the strongly connected components of the CSR read as a directed
-    multigraph: comp[v] = the smallest vertex id of v's component (int32), the component sizes and the condensation."""
+    multigraph: comp[v] = the smallest vertex id of v's component (int32), the component sizes and the condensation.
 
-    _destroy = "grx_scc_destroy"
+    Options: "schedule" (SCC_AUTO / SCC_ROUNDS / SCC_DEVICE_LOOP), "pivot_phase", "trim", "pair_trim", "wave_min_row",
+    "loop_max_list", "loop_max_entries".
+    device_results: (device pointers of comp (int32 per vertex), of the transpose's row offsets and of its column indices)."""
 
-    _STATS = ("trimmed", "trim_rounds", "pivot_component", "colour_rounds", "sweeps", "bfs_levels", "entries_read", "kernel_launches")
-
-    def __init__(self, instrument=False, device=0):
-        self._create("grx_scc_create", int(instrument), device)
-        self.nodes = 0
-        self.edges = 0
-
-    def init(self, nodes, row_offsets, col_indices):
-        ro, ci = _csr_arrays(row_offsets, col_indices, nodes)
-        self.nodes, self.edges = int(nodes), int(ci.shape[0])
-        _check(lib().grx_scc_init(self._h, self.nodes, self.edges, _p(ro), _p(ci)), "SccProblem::Init")
-        return self
+    _family, _problem, _enactor = "scc", "SccProblem", "SccEnactor"
+    _stats = (("trimmed", "trim_rounds", "pivot_component", "colour_rounds", "sweeps", "bfs_levels", "entries_read", "kernel_launches"),
+              ("kernel_ms", "build_ms"))
+    _results = 3
 
     def init_device(self, nodes, edges, d_row_offsets, d_col_indices, d_inv_row_offsets=None, d_inv_col_indices=None):
         """a CSR in HBM (borrowed); the transpose too when both inverse pointers are given, else it is built"""
-        self.nodes, self.edges = int(nodes), int(edges)
-        _check(lib().grx_scc_init_device(self._h, self.nodes, self.edges, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices),
-                                         C.c_void_p(d_inv_row_offsets), C.c_void_p(d_inv_col_indices)), "SccProblem::Init(device)")
-        return self
-
-    def set_option(self, name, value):
-        """"schedule" (SCC_AUTO / SCC_ROUNDS / SCC_DEVICE_LOOP), "pivot_phase", "trim", "pair_trim", "wave_min_row", "loop_max_list",
-        "loop_max_entries"; returns the library's code: 0 = set, 1 = unknown name (a value out of range raises)"""
-        rc = lib().grx_scc_set_option(self._h, name.encode(), float(value))
-        if rc not in (0, 1):
-            _check(rc, "grx_scc_set_option(%s)" % name)
-        return rc
-
-    def reset(self):
-        _check(lib().grx_scc_reset(self._h), "SccProblem::Reset")
-
-    def enact(self, max_grid_size=0):
-        return self._timed(lib().grx_scc_enact, "SccEnactor::Enact", max_grid_size)
-
-    def stats(self):
-        v = [C.c_longlong() for _ in self._STATS]
-        k, b = C.c_double(), C.c_double()
-        _check(lib().grx_scc_stats(self._h, *([C.byref(x) for x in v] + [C.byref(k), C.byref(b)])), "grx_scc_stats")
-        out = {name: x.value for name, x in zip(self._STATS, v)}
-        out["kernel_ms"], out["build_ms"] = k.value, b.value
-        return out
+        return self._init_device(nodes, edges, d_row_offsets, d_col_indices, C.c_void_p(d_inv_row_offsets), C.c_void_p(d_inv_col_indices))
 
     def phase_trace(self):
         """the phases of the last enact in order: (kind as int32: SCC_TRIM / SCC_PIVOT / SCC_COLOUR, vertices finished in it as
         int64, milliseconds as float64)"""
-        count = lib().grx_scc_phase_trace(self._h, 0, None, None, None)
-        if count < 0:
-            _check(count, "grx_scc_phase_trace")
-        kind = np.empty(max(count, 1), dtype=np.int32)
-        vertices = np.empty(max(count, 1), dtype=np.int64)
-        ms = np.empty(max(count, 1), dtype=np.float64)
-        lib().grx_scc_phase_trace(self._h, count, _p(kind), vertices.ctypes.data_as(C.POINTER(C.c_longlong)),
-                                  ms.ctypes.data_as(C.POINTER(C.c_double)))
-        return kind[:count], vertices[:count], ms[:count]
+        return _count_then_fill(lib().grx_scc_phase_trace, self._h, "grx_scc_phase_trace", _TRACE)
 
     def extract(self, comp=True):
         """(comp as int32 per vertex, or None; the number of components)"""
-        out = np.empty(max(self.nodes, 1), dtype=np.int32) if comp else None
-        n = C.c_longlong()
-        _check(lib().grx_scc_extract(self._h, None if out is None else _p(out), C.byref(n)), "SccProblem::Extract")
-        return (None if out is None else out[:self.nodes]), int(n.value)
+        out, n = _out(self.nodes, wanted=comp), C.c_longlong()
+        _check(lib().grx_scc_extract(self._h, _opt(out), C.byref(n)), "SccProblem::Extract")
+        return _cut(out, self.nodes), int(n.value)
 
     def summary(self):
         """{"components", "trivial", "largest", "largest_root"}"""
-        c, t, l = C.c_longlong(), C.c_longlong(), C.c_longlong()
-        r = C.c_int()
+        c, t, l, r = C.c_longlong(), C.c_longlong(), C.c_longlong(), C.c_int()
         _check(lib().grx_scc_summary(self._h, C.byref(c), C.byref(t), C.byref(l), C.byref(r)), "SccProblem::Summary")
         return {"components": int(c.value), "trivial": int(t.value), "largest": int(l.value), "largest_root": int(r.value)}
 
     def sizes(self):
         """size[v] as int32: the vertex count of v's component"""
-        out = np.empty(max(self.nodes, 1), dtype=np.int32)
+        out = _out(self.nodes)
         _check(lib().grx_scc_sizes(self._h, _p(out)), "SccProblem::Sizes")
         return out[:self.nodes]
 
     def condensation(self, max_edges=None):
         """the condensation sorted by (from, to): (from as int32, to as int32, the number of pairs); max_edges caps what is
         copied (0: the count only)"""
-        count = lib().grx_scc_condensation(self._h, 0, None, None)
-        if count < 0:
-            _check(-count, "SccProblem::Condensation")
-        take = count if max_edges is None else min(count, int(max_edges))
-        f = np.empty(max(take, 1), dtype=np.int32)
-        t = np.empty(max(take, 1), dtype=np.int32)
-        if take > 0:
-            rc = lib().grx_scc_condensation(self._h, take, _p(f), _p(t))
-            if rc < 0:
-                _check(-rc, "SccProblem::Condensation")
-        return f[:take], t[:take], count
-
-    def device_results(self):
-        """(device pointers of comp (int32 per vertex), of the transpose's row offsets and of its column indices)"""
-        c, r, i = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        _check(lib().grx_scc_device_results(self._h, C.byref(c), C.byref(r), C.byref(i)), "grx_scc_device_results")
-        return c.value, r.value, i.value
+        return _pair_list(lib().grx_scc_condensation, self._h, "SccProblem::Condensation", max_edges)
 
 
 def gunrock_scc(nodes, row_offsets, col_indices, device=0):
@@ -1440,99 +1351,33 @@ BCC_AUTO, BCC_ROUNDS, BCC_DEVICE_LOOP = 0, 1, 2  # enum GRX_BCC_* (gunrock_mi355
 BCC_FOREST, BCC_SIZES, BCC_NUMBER, BCC_LOWHIGH, BCC_LINK, BCC_LABEL = range(6)  # enum GRX_BCC_PHASE_*: the kinds of phase_trace()
 
 
-def _u8p(a):
-    return a.ctypes.data_as(C.POINTER(C.c_ubyte))
-
-
-class BccProblem(_Handle):
+class BccProblem(_EdgeListProblem):
     """BccProblem + BccEnactor behind the handle C ABI: the biconnected components (bcc[e] = the smallest canonical edge index of
     e's block, int32), the bridges and the articulation points (uint8 masks), the 2-edge-connected components (tecc[v] = the
     smallest id, int32) and the block-cut tree, of the CSR read as an undirected simple graph; per-edge arrays in the canonical
-    edge order ((a, b) with a < b, sorted)."""
+    edge order ((a, b) with a < b, sorted).
 
-    _destroy = "grx_bcc_destroy"
+    Options: "schedule" (BCC_AUTO / BCC_ROUNDS / BCC_DEVICE_LOOP), "wave_min_row", "loop_max_list", "loop_max_entries".
+    device_results: int32 arrays but for the two uint8 masks; per edge: bcc, bridge, src, dst; per vertex: the rest.  parent /
+    level are the spanning forest (not unique)."""
 
-    _STATS = ("simple_edges", "trees", "levels", "entries_read", "kernel_launches", "readbacks")
+    _family, _problem, _enactor = "bcc", "BccProblem", "BccEnactor"
+    _stats = (("simple_edges", "trees", "levels", "entries_read", "kernel_launches", "readbacks"), ("kernel_ms", "build_ms"))
+    _results = ("bcc", "tecc", "bridge", "articulation", "src", "dst", "parent", "level")
     _SUMMARY = ("blocks", "bridges", "articulation_points", "largest_block", "largest_block_id", "tecc_components", "largest_tecc",
                 "largest_tecc_root")
-
-    def __init__(self, instrument=False, device=0):
-        self._create("grx_bcc_create", int(instrument), device)
-        self.nodes = 0
-        self.entries = 0
-        self.simple_edges = 0
-
-    def _ready(self):
-        m = lib().grx_bcc_edges(self._h, None, None)
-        if m < 0:
-            _check(-m, "BccProblem::Edges")
-        self.simple_edges = int(m)
-
-    def init(self, nodes, row_offsets, col_indices):
-        ro, ci = _csr_arrays(row_offsets, col_indices, nodes)
-        self.nodes, self.entries = int(nodes), int(ci.shape[0])
-        _check(lib().grx_bcc_init(self._h, self.nodes, self.entries, _p(ro), _p(ci)), "BccProblem::Init")
-        self._ready()
-        return self
-
-    def init_device(self, nodes, edges, d_row_offsets, d_col_indices):
-        self.nodes, self.entries = int(nodes), int(edges)
-        _check(lib().grx_bcc_init_device(self._h, self.nodes, self.entries, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices)),
-               "BccProblem::Init(device)")
-        self._ready()
-        return self
-
-    def set_option(self, name, value):
-        """"schedule" (BCC_AUTO / BCC_ROUNDS / BCC_DEVICE_LOOP), "wave_min_row", "loop_max_list", "loop_max_entries"; returns the
-        library's code: 0 = set, 1 = unknown name (a value out of range raises)"""
-        rc = lib().grx_bcc_set_option(self._h, name.encode(), float(value))
-        if rc not in (0, 1):
-            _check(rc, "grx_bcc_set_option(%s)" % name)
-        return rc
-
-    def reset(self):
-        _check(lib().grx_bcc_reset(self._h), "BccProblem::Reset")
-
-    def enact(self, max_grid_size=0):
-        return self._timed(lib().grx_bcc_enact, "BccEnactor::Enact", max_grid_size)
-
-    def stats(self):
-        v = [C.c_longlong() for _ in self._STATS]
-        k, b = C.c_double(), C.c_double()
-        _check(lib().grx_bcc_stats(self._h, *([C.byref(x) for x in v] + [C.byref(k), C.byref(b)])), "grx_bcc_stats")
-        out = {name: x.value for name, x in zip(self._STATS, v)}
-        out["kernel_ms"], out["build_ms"] = k.value, b.value
-        return out
 
     def phase_trace(self):
         """the six phases of the last enact: (kind as int32: BCC_FOREST .. BCC_LABEL, vertices or edges touched as int64,
         milliseconds as float64)"""
-        count = lib().grx_bcc_phase_trace(self._h, 0, None, None, None)
-        if count < 0:
-            _check(count, "grx_bcc_phase_trace")
-        kind = np.empty(max(count, 1), dtype=np.int32)
-        items = np.empty(max(count, 1), dtype=np.int64)
-        ms = np.empty(max(count, 1), dtype=np.float64)
-        lib().grx_bcc_phase_trace(self._h, count, _p(kind), items.ctypes.data_as(C.POINTER(C.c_longlong)),
-                                  ms.ctypes.data_as(C.POINTER(C.c_double)))
-        return kind[:count], items[:count], ms[:count]
-
-    def edges(self):
-        """the canonical edges (src, dst) as int32, src < dst, sorted by (src, dst)"""
-        src, dst = (np.empty(max(self.simple_edges, 1), dtype=np.int32) for _ in range(2))
-        m = lib().grx_bcc_edges(self._h, _p(src), _p(dst))
-        if m < 0:
-            _check(-m, "BccProblem::Edges")
-        return src[:m], dst[:m]
+        return _count_then_fill(lib().grx_bcc_phase_trace, self._h, "grx_bcc_phase_trace", _TRACE)
 
     def extract(self):
         """{"bcc": int32 per edge, "bridge": uint8 per edge, "articulation": uint8 per vertex, "tecc": int32 per vertex,
         "block_size": int32 per edge}"""
-        m, n = max(self.simple_edges, 1), max(self.nodes, 1)
-        bcc, size, tecc = np.empty(m, np.int32), np.empty(m, np.int32), np.empty(n, np.int32)
-        bridge, art = np.empty(m, np.uint8), np.empty(n, np.uint8)
-        _check(lib().grx_bcc_extract(self._h, _p(bcc), _u8p(bridge), _u8p(art), _p(tecc), _p(size)), "BccProblem::Extract")
         M, N = self.simple_edges, self.nodes
+        bcc, size, tecc, bridge, art = _out(M), _out(M), _out(N), _out(M, np.uint8), _out(N, np.uint8)
+        _check(lib().grx_bcc_extract(self._h, _p(bcc), _u8p(bridge), _u8p(art), _p(tecc), _p(size)), "BccProblem::Extract")
         return {"bcc": bcc[:M], "bridge": bridge[:M], "articulation": art[:N], "tecc": tecc[:N], "block_size": size[:M]}
 
     def summary(self):
@@ -1545,25 +1390,7 @@ class BccProblem(_Handle):
     def block_cut(self, max_edges=None):
         """the block-cut tree sorted by (vertex, block): (articulation point as int32, bcc id as int32, the number of pairs);
         max_edges caps what is copied (0: the count only).  The library builds the pairs once per enact: the second call copies"""
-        count = lib().grx_bcc_block_cut(self._h, 0, None, None)
-        if count < 0:
-            _check(-count, "BccProblem::BlockCut")
-        take = count if max_edges is None else min(count, int(max_edges))
-        v = np.empty(max(take, 1), dtype=np.int32)
-        b = np.empty(max(take, 1), dtype=np.int32)
-        if take > 0:
-            rc = lib().grx_bcc_block_cut(self._h, take, _p(v), _p(b))
-            if rc < 0:
-                _check(-rc, "BccProblem::BlockCut")
-        return v[:take], b[:take], count
-
-    def device_results(self):
-        """device pointers {"bcc", "tecc", "bridge", "articulation", "src", "dst", "parent", "level"}: int32 arrays but for the two
-        uint8 masks; per edge: bcc, bridge, src, dst; per vertex: the rest.  parent / level are the spanning forest (not unique)"""
-        names = ("bcc", "tecc", "bridge", "articulation", "src", "dst", "parent", "level")
-        p = [C.c_void_p() for _ in names]
-        _check(lib().grx_bcc_device_results(self._h, *[C.byref(x) for x in p]), "grx_bcc_device_results")
-        return {name: x.value for name, x in zip(names, p)}
+        return _pair_list(lib().grx_bcc_block_cut, self._h, "BccProblem::BlockCut", max_edges)
 
 
 def gunrock_bcc(nodes, row_offsets, col_indices, device=0):
@@ -1594,56 +1421,57 @@ class MaxflowGaveUp(RuntimeError):
     """MaxflowProblem.enact passed "max_rounds" (GRX_MAXFLOW_GAVE_UP): the handle holds no result and takes the next reset"""
 
 
-class MaxflowProblem(_Handle):
+class _PairListProblem(_TunedProblem):
+    """A family over the canonical pairs of the graph, (a, b) with a < b, sorted: their number, num_pairs, is read back behind
+    Init and pairs() returns them with the family's values, _pair_columns int32 columns in all."""
+
+    _count = "entries"
+    _pair_columns = 0
+
+    def __init__(self, instrument=False, device=0):
+        super().__init__(instrument, device)
+        self.num_pairs = 0
+
+    def _pair_list(self, columns):
+        m = self._fn("pairs")(self._h, *map(_opt, columns))
+        if m < 0:
+            _check(-m, self._problem + "::Pairs")
+        return int(m)
+
+    def _ready(self):
+        self.num_pairs = self._pair_list([None] * self._pair_columns)
+
+    def pairs(self):
+        """the canonical pairs and their values as int32 columns, sorted by (a, b): see the class"""
+        columns = [_out(self.num_pairs) for _ in range(self._pair_columns)]
+        m = self._pair_list(columns)
+        return tuple(c[:m] for c in columns)
+
+
+class MaxflowProblem(_PairListProblem):
     """MaxflowProblem + MaxflowEnactor behind the handle C ABI: the maximum flow from src to sink and the minimum cuts of the CSR read
     as a directed multigraph with int32 capacities (None: 1 each; parallel arcs add up, self-loops are ignored).  Per-pair arrays in
     the canonical pair order ((a, b) with a < b and an arc either way, sorted).  value, side and cut have one value each; flow and
-    arc_flow are a valid maximum flow that depends on the run."""
+    arc_flow are a valid maximum flow that depends on the run.  pairs(): (a, b, cap_ab, cap_ba).
 
-    _destroy = "grx_maxflow_destroy"
+    Options: "schedule" (MAXFLOW_AUTO / MAXFLOW_ROUNDS / MAXFLOW_DEVICE_LOOP), "wave_min_row", "discharge_steps",
+    "relabel_interval", "max_rounds", "loop_max_list", "loop_max_entries".
+    device_results: per pair flow (int32), cut (uint8), a, b (int32); per vertex side (uint8), excess (int64) and height (int32,
+    not unique)."""
 
-    _STATS = ("pairs", "rounds", "global_relabels", "pushes", "relabels", "entries_read", "kernel_launches", "readbacks")
+    _family, _problem, _enactor = "maxflow", "MaxflowProblem", "MaxflowEnactor"
+    _pair_columns = 4  # (a, b, cap_ab, cap_ba)
+    _stats = (("pairs", "rounds", "global_relabels", "pushes", "relabels", "entries_read", "kernel_launches", "readbacks"),
+              ("kernel_ms", "build_ms"))
+    _results = ("flow", "side", "cut", "a", "b", "excess", "height")
     _SUMMARY = ("value", "side0", "side1", "side2", "cut0", "cut1")
 
-    def __init__(self, instrument=False, device=0):
-        self._create("grx_maxflow_create", int(instrument), device)
-        self.nodes = 0
-        self.entries = 0
-        self.num_pairs = 0
-
-    def _ready(self):
-        m = lib().grx_maxflow_pairs(self._h, None, None, None, None)
-        if m < 0:
-            _check(-m, "MaxflowProblem::Pairs")
-        self.num_pairs = int(m)
-
     def init(self, nodes, row_offsets, col_indices, capacities=None):
-        ro, ci = _csr_arrays(row_offsets, col_indices, nodes)
-        cap = None if capacities is None else _i32(capacities)
-        if cap is not None and cap.shape[0] != ci.shape[0]:
-            raise ValueError("gunrockinst_amd: %d capacities for %d arcs" % (cap.shape[0], ci.shape[0]))
-        self.nodes, self.entries = int(nodes), int(ci.shape[0])
-        _check(lib().grx_maxflow_init(self._h, self.nodes, self.entries, _p(ro), _p(ci), None if cap is None else _p(cap)),
-               "MaxflowProblem::Init")
-        self._ready()
-        return self
+        return self._init_host(nodes, row_offsets, col_indices, per_entry=(capacities, "capacities", "arcs"))
 
     def init_device(self, nodes, edges, d_row_offsets, d_col_indices, d_capacities=None):
         """the CSR (and the capacities) stay the caller's and must outlive the handle"""
-        self.nodes, self.entries = int(nodes), int(edges)
-        _check(lib().grx_maxflow_init_device(self._h, self.nodes, self.entries, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices),
-                                             C.c_void_p(d_capacities) if d_capacities else None), "MaxflowProblem::Init(device)")
-        self._ready()
-        return self
-
-    def set_option(self, name, value):
-        """"schedule" (MAXFLOW_AUTO / MAXFLOW_ROUNDS / MAXFLOW_DEVICE_LOOP), "wave_min_row", "discharge_steps", "relabel_interval",
-        "max_rounds", "loop_max_list", "loop_max_entries"; returns the library's code: 0 = set, 1 = unknown name (a value out of
-        range raises)"""
-        rc = lib().grx_maxflow_set_option(self._h, name.encode(), float(value))
-        if rc not in (0, 1):
-            _check(rc, "grx_maxflow_set_option(%s)" % name)
-        return rc
+        return self._init_device(nodes, edges, d_row_offsets, d_col_indices, C.c_void_p(d_capacities))
 
     def reset(self, src, sink):
         _check(lib().grx_maxflow_reset(self._h, int(src), int(sink)), "MaxflowProblem::Reset")
@@ -1657,46 +1485,21 @@ class MaxflowProblem(_Handle):
         _check(rc, "MaxflowEnactor::Enact")
         return ms.value
 
-    def stats(self):
-        v = [C.c_longlong() for _ in self._STATS]
-        k, b = C.c_double(), C.c_double()
-        _check(lib().grx_maxflow_stats(self._h, *([C.byref(x) for x in v] + [C.byref(k), C.byref(b)])), "grx_maxflow_stats")
-        out = {name: x.value for name, x in zip(self._STATS, v)}
-        out["kernel_ms"], out["build_ms"] = k.value, b.value
-        return out
-
     def phase_trace(self):
         """the three phases of the last enact: (kind as int32: MAXFLOW_PREFLOW / MAXFLOW_RETURN / MAXFLOW_CUT, rounds as int64,
         milliseconds as float64)"""
-        count = lib().grx_maxflow_phase_trace(self._h, 0, None, None, None)
-        if count < 0:
-            _check(count, "grx_maxflow_phase_trace")
-        kind = np.empty(max(count, 1), dtype=np.int32)
-        rounds = np.empty(max(count, 1), dtype=np.int64)
-        ms = np.empty(max(count, 1), dtype=np.float64)
-        lib().grx_maxflow_phase_trace(self._h, count, _p(kind), rounds.ctypes.data_as(C.POINTER(C.c_longlong)),
-                                      ms.ctypes.data_as(C.POINTER(C.c_double)))
-        return kind[:count], rounds[:count], ms[:count]
-
-    def pairs(self):
-        """the canonical pairs (a, b, cap_ab, cap_ba) as int32, a < b, sorted by (a, b)"""
-        a, b, cab, cba = (np.empty(max(self.num_pairs, 1), dtype=np.int32) for _ in range(4))
-        m = lib().grx_maxflow_pairs(self._h, _p(a), _p(b), _p(cab), _p(cba))
-        if m < 0:
-            _check(-m, "MaxflowProblem::Pairs")
-        return a[:m], b[:m], cab[:m], cba[:m]
+        return _count_then_fill(lib().grx_maxflow_phase_trace, self._h, "grx_maxflow_phase_trace", _TRACE)
 
     def extract(self):
         """{"value": int, "flow": int32 per pair, "side": uint8 per vertex, "cut": uint8 per pair}"""
-        m, n = max(self.num_pairs, 1), max(self.nodes, 1)
-        value = C.c_longlong()
-        flow, side, cut = np.empty(m, np.int32), np.empty(n, np.uint8), np.empty(m, np.uint8)
+        M, N, value = self.num_pairs, self.nodes, C.c_longlong()
+        flow, side, cut = _out(M), _out(N, np.uint8), _out(M, np.uint8)
         _check(lib().grx_maxflow_extract(self._h, C.byref(value), _p(flow), _u8p(side), _u8p(cut)), "MaxflowProblem::Extract")
-        return {"value": int(value.value), "flow": flow[:self.num_pairs], "side": side[:self.nodes], "cut": cut[:self.num_pairs]}
+        return {"value": int(value.value), "flow": flow[:M], "side": side[:N], "cut": cut[:M]}
 
     def arc_flow(self):
         """int32 per CSR entry of the input"""
-        out = np.empty(max(self.entries, 1), dtype=np.int32)
+        out = _out(self.entries)
         _check(lib().grx_maxflow_arc_flow(self._h, _p(out)), "MaxflowProblem::ArcFlow")
         return out[:self.entries]
 
@@ -1705,14 +1508,6 @@ class MaxflowProblem(_Handle):
         v = (C.c_longlong * 6)()
         _check(lib().grx_maxflow_summary(self._h, v), "MaxflowProblem::Summary")
         return {name: int(x) for name, x in zip(self._SUMMARY, v)}
-
-    def device_results(self):
-        """device pointers {"flow", "side", "cut", "a", "b", "excess", "height"}: per pair flow (int32), cut (uint8), a, b (int32);
-        per vertex side (uint8), excess (int64) and height (int32, not unique)"""
-        names = ("flow", "side", "cut", "a", "b", "excess", "height")
-        p = [C.c_void_p() for _ in names]
-        _check(lib().grx_maxflow_device_results(self._h, *[C.byref(x) for x in p]), "grx_maxflow_device_results")
-        return {name: x.value for name, x in zip(names, p)}
 
 
 def gunrock_maxflow(nodes, row_offsets, col_indices, capacities, src, sink, device=0):
@@ -1752,60 +1547,32 @@ def matching_keys(pair_weights, seed=0):
     return (high << np.uint64(32)) | mis_priorities(w.shape[0], seed).astype(np.uint64)
 
 
-class MatchingProblem(_Handle):
+class MatchingProblem(_PairListProblem):
     """MatchingProblem + MatchingEnactor behind the handle C ABI: the locally dominant (heavy-edge) matching of the CSR read as an
     undirected simple graph with int32 weights (None: 1 each; a pair's weight is the largest of its entries), unique under the order
     matching_keys(); and its contraction into the coarse graph.  Per-pair arrays in the canonical pair order ((a, b) with a < b,
-    sorted)."""
+    sorted); pairs(): (src, dst, weight).
 
-    _destroy = "grx_matching_destroy"
+    Options: "schedule" (MATCHING_AUTO / MATCHING_ROUNDS / MATCHING_DEVICE_LOOP), "wave_min_row", "max_rounds", "loop_max_list",
+    "loop_max_entries".
+    device_results: per pair in_matching (uint8), src, dst, weight (int32); per vertex mate and medge (int32)."""
 
-    _STATS = ("pairs", "rounds", "loop_rounds", "entries_read", "polls", "kernel_launches")
+    _family, _problem, _enactor = "matching", "MatchingProblem", "MatchingEnactor"
+    _pair_columns = 3
+    _stats = (("pairs", "rounds", "loop_rounds", "entries_read", "polls", "kernel_launches"), ("kernel_ms", "build_ms"))
+    _results = ("in_matching", "mate", "medge", "src", "dst", "weight")
     _SUMMARY = ("pairs", "matched", "weight", "unmatched", "unmatched_with_neighbours")
 
     def __init__(self, instrument=False, device=0):
-        self._create("grx_matching_create", int(instrument), device)
-        self.nodes = 0
-        self.entries = 0
-        self.num_pairs = 0
+        super().__init__(instrument, device)
         self.coarse_nodes = self.coarse_entries = 0
 
-    def _ready(self):
-        m = lib().grx_matching_pairs(self._h, None, None, None)
-        if m < 0:
-            _check(-m, "MatchingProblem::Pairs")
-        self.num_pairs = int(m)
-
     def init(self, nodes, row_offsets, col_indices, weights=None, seed=0):
-        ro, ci = _csr_arrays(row_offsets, col_indices, nodes)
-        w = None if weights is None else _i32(weights)
-        if w is not None and w.shape[0] != ci.shape[0]:
-            raise ValueError("gunrockinst_amd: %d weights for %d entries" % (w.shape[0], ci.shape[0]))
-        self.nodes, self.entries = int(nodes), int(ci.shape[0])
-        _check(lib().grx_matching_init(self._h, self.nodes, self.entries, _p(ro), _p(ci), None if w is None else _p(w), int(seed) & 0xFFFFFFFF),
-               "MatchingProblem::Init")
-        self._ready()
-        return self
+        return self._init_host(nodes, row_offsets, col_indices, int(seed) & 0xFFFFFFFF, per_entry=(weights, "weights", "entries"))
 
     def init_device(self, nodes, edges, d_row_offsets, d_col_indices, d_weights=None, seed=0):
         """the CSR (and the weights) stay the caller's; the build reads them, nothing later does"""
-        self.nodes, self.entries = int(nodes), int(edges)
-        _check(lib().grx_matching_init_device(self._h, self.nodes, self.entries, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices),
-                                              C.c_void_p(d_weights) if d_weights else None, int(seed) & 0xFFFFFFFF),
-               "MatchingProblem::Init(device)")
-        self._ready()
-        return self
-
-    def set_option(self, name, value):
-        """"schedule" (MATCHING_AUTO / MATCHING_ROUNDS / MATCHING_DEVICE_LOOP), "wave_min_row", "max_rounds", "loop_max_list",
-        "loop_max_entries"; returns the library's code: 0 = set, 1 = unknown name (a value out of range raises)"""
-        rc = lib().grx_matching_set_option(self._h, name.encode(), float(value))
-        if rc not in (0, 1):
-            _check(rc, "grx_matching_set_option(%s)" % name)
-        return rc
-
-    def reset(self):
-        _check(lib().grx_matching_reset(self._h), "MatchingProblem::Reset")
+        return self._init_device(nodes, edges, d_row_offsets, d_col_indices, C.c_void_p(d_weights), int(seed) & 0xFFFFFFFF)
 
     def enact(self, max_grid_size=0):
         """the elapsed milliseconds; MatchingGaveUp when the rounds passed the option max_rounds"""
@@ -1816,53 +1583,23 @@ class MatchingProblem(_Handle):
         _check(rc, "MatchingEnactor::Enact")
         return ms.value
 
-    def stats(self):
-        v = [C.c_longlong() for _ in self._STATS]
-        k, b = C.c_double(), C.c_double()
-        _check(lib().grx_matching_stats(self._h, *([C.byref(x) for x in v] + [C.byref(k), C.byref(b)])), "grx_matching_stats")
-        out = {name: x.value for name, x in zip(self._STATS, v)}
-        out["kernel_ms"], out["build_ms"] = k.value, b.value
-        return out
-
     def round_trace(self):
         """the host's steps of the last enact: (kind as int32: MATCHING_STEP_WIDE / MATCHING_STEP_LOOP, rounds, live list, matched
         pairs as int64)"""
-        count = lib().grx_matching_round_trace(self._h, 0, None, None, None, None)
-        if count < 0:
-            _check(count, "grx_matching_round_trace")
-        kind = np.empty(max(count, 1), dtype=np.int32)
-        rounds, live, matched = (np.empty(max(count, 1), dtype=np.int64) for _ in range(3))
-        lib().grx_matching_round_trace(self._h, count, _p(kind), _i64p(rounds), _i64p(live), _i64p(matched))
-        return kind[:count], rounds[:count], live[:count], matched[:count]
-
-    def pairs(self):
-        """the canonical pairs (src, dst, weight) as int32, src < dst, sorted by (src, dst)"""
-        a, b, w = (np.empty(max(self.num_pairs, 1), dtype=np.int32) for _ in range(3))
-        m = lib().grx_matching_pairs(self._h, _p(a), _p(b), _p(w))
-        if m < 0:
-            _check(-m, "MatchingProblem::Pairs")
-        return a[:m], b[:m], w[:m]
+        return _count_then_fill(lib().grx_matching_round_trace, self._h, "grx_matching_round_trace", (np.int32,) + (np.int64,) * 3)
 
     def extract(self):
         """{"in_matching": uint8 per pair, "mate": int32 per vertex (-1: unmatched), "medge": int32 per vertex (-1: unmatched)}"""
-        m, n = max(self.num_pairs, 1), max(self.nodes, 1)
-        in_matching, mate, medge = np.empty(m, np.uint8), np.empty(n, np.int32), np.empty(n, np.int32)
+        M, N = self.num_pairs, self.nodes
+        in_matching, mate, medge = _out(M, np.uint8), _out(N), _out(N)
         _check(lib().grx_matching_extract(self._h, _u8p(in_matching), _p(mate), _p(medge)), "MatchingProblem::Extract")
-        return {"in_matching": in_matching[:self.num_pairs], "mate": mate[:self.nodes], "medge": medge[:self.nodes]}
+        return {"in_matching": in_matching[:M], "mate": mate[:N], "medge": medge[:N]}
 
     def summary(self):
         """{"pairs", "matched", "weight", "unmatched", "unmatched_with_neighbours"}"""
         v = (C.c_longlong * 5)()
         _check(lib().grx_matching_summary(self._h, v), "MatchingProblem::Summary")
         return {name: int(x) for name, x in zip(self._SUMMARY, v)}
-
-    def device_results(self):
-        """device pointers {"in_matching", "mate", "medge", "src", "dst", "weight"}: per pair in_matching (uint8), src, dst, weight
-        (int32); per vertex mate and medge (int32)"""
-        names = ("in_matching", "mate", "medge", "src", "dst", "weight")
-        p = [C.c_void_p() for _ in names]
-        _check(lib().grx_matching_device_results(self._h, *[C.byref(x) for x in p]), "grx_matching_device_results")
-        return {name: x.value for name, x in zip(names, p)}
 
     def contract(self, vertex_weights=None):
         """builds the coarse graph of the last enact on the device; returns (coarse_nodes, coarse_entries).  vertex_weights: None (1
@@ -1872,9 +1609,7 @@ class MatchingProblem(_Handle):
         if vertex_weights is None or isinstance(vertex_weights, int):
             vw, ptr = None, C.c_void_p(vertex_weights) if vertex_weights else None
         else:
-            vw = _i32(vertex_weights)
-            if vw.shape[0] != self.nodes:
-                raise ValueError("gunrockinst_amd: %d vertex weights for %d nodes" % (vw.shape[0], self.nodes))
+            vw = _i32_of(vertex_weights, self.nodes, "vertex weights", "nodes")
             ptr = C.c_void_p(vw.ctypes.data)
         rc = lib().grx_matching_contract(self._h, ptr, C.byref(nc), C.byref(ne))
         if rc == MATCHING_OVERFLOW:
@@ -1885,18 +1620,16 @@ class MatchingProblem(_Handle):
 
     def coarse_extract(self):
         """(map, coarse_nodes, row_offsets, col_indices, weights, vweight) of the last contract, int32 arrays"""
-        n, nc, ne = max(self.nodes, 1), self.coarse_nodes, max(self.coarse_entries, 1)
-        cmap, ro, ci, w, vw = np.empty(n, np.int32), np.empty(nc + 1, np.int32), np.empty(ne, np.int32), np.empty(ne, np.int32), np.empty(max(nc, 1), np.int32)
+        nc, ne = self.coarse_nodes, self.coarse_entries
+        cmap, ro, ci, w, vw = _out(self.nodes), _out(nc + 1), _out(ne), _out(ne), _out(nc)
         _check(lib().grx_matching_coarse_extract(self._h, _p(cmap), _p(ro), _p(ci), _p(w), _p(vw)), "MatchingProblem::CoarseExtract")
-        return cmap[:self.nodes], nc, ro, ci[:self.coarse_entries], w[:self.coarse_entries], vw[:nc]
+        return cmap[:self.nodes], nc, ro, ci[:ne], w[:ne], vw[:nc]
 
     def coarse_device(self):
         """device pointers {"map", "row_offsets", "col_indices", "weights", "vweight"} of the last contract: they live until this
         handle's next reset, contract or close"""
         names = ("map", "row_offsets", "col_indices", "weights", "vweight")
-        p = [C.c_void_p() for _ in names]
-        _check(lib().grx_matching_coarse_device(self._h, *[C.byref(x) for x in p]), "grx_matching_coarse_device")
-        return {name: x.value for name, x in zip(names, p)}
+        return dict(zip(names, self._device_pointers(len(names), "coarse_device")))
 
 
 def gunrock_matching(nodes, row_offsets, col_indices, weights=None, seed=0, device=0):
@@ -1947,43 +1680,22 @@ class CliqueOverflow(ArithmeticError):
     no result and takes the next enact"""
 
 
-class CliqueProblem(_Handle):
+class CliqueProblem(_TunedProblem):
     """CliqueProblem + CliqueEnactor behind the handle C ABI: for k = 3 .. 6 the number of k-cliques through every vertex (int64)
     and their total, of the CSR read as an undirected simple graph.  `rank` (int32 per vertex, or None) orients the build; no rank
-    changes a result."""
+    changes a result.
 
-    _destroy = "grx_clique_destroy"
+    Options: "strategy" (CLIQUE_AUTO / CLIQUE_BITMAP / CLIQUE_LIST), "bitmap_rows", "count_limit".
+    device_results: (device pointer of the int64 counts, device pointer of the int32 degrees)."""
 
-    def __init__(self, instrument=False, device=0):
-        self._create("grx_clique_create", int(instrument), device)
-        self.nodes = 0
-        self.edges = 0
+    _family, _problem, _enactor = "clique", "CliqueProblem", "CliqueEnactor"
+    _results = 2
 
     def init(self, nodes, row_offsets, col_indices, rank=None):
-        ro, ci = _csr_arrays(row_offsets, col_indices, nodes)
-        rk = None if rank is None else _i32(rank)
-        if rk is not None and rk.shape[0] != int(nodes):
-            raise ValueError("gunrockinst_amd: %d ranks for %d nodes" % (rk.shape[0], int(nodes)))
-        self.nodes, self.edges = int(nodes), int(ci.shape[0])
-        _check(lib().grx_clique_init(self._h, self.nodes, self.edges, _p(ro), _p(ci), None if rk is None else _p(rk)), "CliqueProblem::Init")
-        return self
+        return self._init_host(nodes, row_offsets, col_indices, per_node=(rank, "ranks", "nodes"))
 
     def init_device(self, nodes, edges, d_row_offsets, d_col_indices, d_rank=None):
-        self.nodes, self.edges = int(nodes), int(edges)
-        _check(lib().grx_clique_init_device(self._h, self.nodes, self.edges, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices),
-                                            C.c_void_p(d_rank)), "CliqueProblem::Init(device)")
-        return self
-
-    def set_option(self, name, value):
-        """"strategy" (CLIQUE_AUTO / CLIQUE_BITMAP / CLIQUE_LIST), "bitmap_rows", "count_limit"; returns the library's code:
-        0 = set, 1 = unknown name (a value out of range raises)"""
-        rc = lib().grx_clique_set_option(self._h, name.encode(), float(value))
-        if rc not in (0, 1):
-            _check(rc, "grx_clique_set_option(%s)" % name)
-        return rc
-
-    def reset(self):
-        _check(lib().grx_clique_reset(self._h), "CliqueProblem::Reset")
+        return self._init_device(nodes, edges, d_row_offsets, d_col_indices, C.c_void_p(d_rank))
 
     def enact(self, k, max_grid_size=0):
         """the elapsed milliseconds; CliqueOverflow when the bound on the counts reached the option count_limit"""
@@ -2007,16 +1719,9 @@ class CliqueProblem(_Handle):
 
     def extract(self, cliques=True):
         """(cliques as int64 per vertex, or None; the number of k-cliques of the graph)"""
-        out = np.empty(max(self.nodes, 1), dtype=np.int64) if cliques else None
-        total = C.c_longlong()
-        _check(lib().grx_clique_extract(self._h, None if out is None else _i64p(out), C.byref(total)), "CliqueProblem::Extract")
-        return (None if out is None else out[:self.nodes]), int(total.value)
-
-    def device_results(self):
-        """(device pointer of the int64 counts, device pointer of the int32 degrees)"""
-        t, d = C.c_void_p(), C.c_void_p()
-        _check(lib().grx_clique_device_results(self._h, C.byref(t), C.byref(d)), "grx_clique_device_results")
-        return t.value, d.value
+        out, total = _out(self.nodes, np.int64, cliques), C.c_longlong()
+        _check(lib().grx_clique_extract(self._h, _opt(out), C.byref(total)), "CliqueProblem::Extract")
+        return _cut(out, self.nodes), int(total.value)
 
 
 def gunrock_cliques(nodes, row_offsets, col_indices, k, rank=None, device=0):
@@ -2034,51 +1739,18 @@ class C4Overflow(ArithmeticError):
     result and takes the next enact"""
 
 
-class C4Problem(_Handle):
+class C4Problem(_EdgeListProblem):
     """C4Problem + C4Enactor behind the handle C ABI: the 4-cycles (butterflies) through every vertex and every edge (int64, the edges
-    in the canonical order: (a, b) with a < b, sorted) and their total, of the CSR read as an undirected simple graph."""
+    in the canonical order: (a, b) with a < b, sorted) and their total, of the CSR read as an undirected simple graph.  The build
+    reads a device CSR and nothing later does.
 
-    _destroy = "grx_c4_destroy"
+    Options: "strategy" (C4_AUTO / C4_LANE / C4_WAVE / C4_BLOCK / C4_GLOBAL), "lane_max_wedges", "table_slots", "block_slots",
+    "scratch_mib", "edges", "count_limit".
+    device_results: "cycles", "edge_cycles": int64 per vertex and per canonical edge; "src", "dst": int32 per edge."""
 
+    _family, _problem, _enactor = "c4", "C4Problem", "C4Enactor"
+    _results = ("cycles", "edge_cycles", "src", "dst")
     _REGIMES = ("lane", "wave", "block", "global")
-
-    def __init__(self, instrument=False, device=0):
-        self._create("grx_c4_create", int(instrument), device)
-        self.nodes = 0
-        self.entries = 0
-        self.simple_edges = 0
-
-    def _ready(self):
-        m = lib().grx_c4_edges(self._h, None, None)
-        if m < 0:
-            _check(-m, "C4Problem::Edges")
-        self.simple_edges = int(m)
-
-    def init(self, nodes, row_offsets, col_indices):
-        ro, ci = _csr_arrays(row_offsets, col_indices, nodes)
-        self.nodes, self.entries = int(nodes), int(ci.shape[0])
-        _check(lib().grx_c4_init(self._h, self.nodes, self.entries, _p(ro), _p(ci)), "C4Problem::Init")
-        self._ready()
-        return self
-
-    def init_device(self, nodes, edges, d_row_offsets, d_col_indices):
-        """the CSR stays the caller's; the build reads it, nothing later does"""
-        self.nodes, self.entries = int(nodes), int(edges)
-        _check(lib().grx_c4_init_device(self._h, self.nodes, self.entries, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices)),
-               "C4Problem::Init(device)")
-        self._ready()
-        return self
-
-    def set_option(self, name, value):
-        """"strategy" (C4_AUTO / C4_LANE / C4_WAVE / C4_BLOCK / C4_GLOBAL), "lane_max_wedges", "table_slots", "block_slots",
-        "scratch_mib", "edges", "count_limit"; returns the library's code: 0 = set, 1 = unknown name (a value out of range raises)"""
-        rc = lib().grx_c4_set_option(self._h, name.encode(), float(value))
-        if rc not in (0, 1):
-            _check(rc, "grx_c4_set_option(%s)" % name)
-        return rc
-
-    def reset(self):
-        _check(lib().grx_c4_reset(self._h), "C4Problem::Reset")
 
     def enact(self, max_grid_size=0):
         """the elapsed milliseconds; C4Overflow when the bound on the counts reached the option count_limit"""
@@ -2104,31 +1776,15 @@ class C4Problem(_Handle):
 
     def extract(self, cycles=True):
         """(4-cycles as int64 per vertex, or None; the 4-cycles of the graph)"""
-        out = np.empty(max(self.nodes, 1), dtype=np.int64) if cycles else None
-        total = C.c_longlong()
-        _check(lib().grx_c4_extract(self._h, None if out is None else _i64p(out), C.byref(total)), "C4Problem::Extract")
-        return (None if out is None else out[:self.nodes]), int(total.value)
-
-    def edges(self):
-        """the canonical edges (src, dst) as int32, src < dst, sorted by (src, dst)"""
-        src, dst = (np.empty(max(self.simple_edges, 1), dtype=np.int32) for _ in range(2))
-        m = lib().grx_c4_edges(self._h, _p(src), _p(dst))
-        if m < 0:
-            _check(-m, "C4Problem::Edges")
-        return src[:m], dst[:m]
+        out, total = _out(self.nodes, np.int64, cycles), C.c_longlong()
+        _check(lib().grx_c4_extract(self._h, _opt(out), C.byref(total)), "C4Problem::Extract")
+        return _cut(out, self.nodes), int(total.value)
 
     def extract_edges(self):
         """4-cycles as int64 per canonical edge; refused (code -1) when the last enact ran with the option edges = 0"""
-        out = np.empty(max(self.simple_edges, 1), dtype=np.int64)
+        out = _out(self.simple_edges, np.int64)
         _check(lib().grx_c4_extract_edges(self._h, _i64p(out)), "C4Problem::ExtractEdges")
         return out[:self.simple_edges]
-
-    def device_results(self):
-        """device pointers {"cycles", "edge_cycles": int64 per vertex and per canonical edge; "src", "dst": int32 per edge}"""
-        names = ("cycles", "edge_cycles", "src", "dst")
-        p = [C.c_void_p() for _ in names]
-        _check(lib().grx_c4_device_results(self._h, *[C.byref(x) for x in p]), "grx_c4_device_results")
-        return {name: x.value for name, x in zip(names, p)}
 
 
 def gunrock_four_cycles(nodes, row_offsets, col_indices, device=0):
@@ -2163,44 +1819,34 @@ def rw_draw(seed, walk, step, t):
     return out if out.ndim else np.uint64(out)
 
 
-class RwProblem(_Handle):
+class RwProblem(_TunedProblem):
     """RwProblem + RwEnactor behind the handle C ABI: uniform, weighted and node2vec-biased random walks on the CSR as given (directed,
     self-loops and duplicates kept).  Every draw is rw_draw(seed, walk, step, try) and every choice exact integer arithmetic on it
     (gunrock_mi355x.h has the definition), so the walks are integers with one value: no option but "length", "seed", "weighted",
-    the biases and "tries" changes them."""
+    the biases and "tries" changes them.  The build reads a device CSR (and the weights) and nothing later does.
 
-    _destroy = "grx_rw_destroy"
+    Options: "strategy" (RW_AUTO / RW_LANE / RW_TILE), "length", "seed", "weighted", "bias_return", "bias_in", "bias_out", "tries",
+    "visits"."""
+
+    _family, _problem, _enactor = "rw", "RwProblem", "RwEnactor"
+    _count = "entries"
+    _stats = (("walks", "steps", "ended_early", "biased_tries", "forced_fallbacks", "kernel_launches"), ("kernel_ms", "build_ms"))
+    _results = ("walks", "lengths", "visits")
 
     def __init__(self, instrument=False, device=0):
-        self._create("grx_rw_create", int(instrument), device)
-        self.nodes = 0
-        self.entries = 0
+        super().__init__(instrument, device)
         self.num_walks = 0
         self.length = 0  # of the last enact
         self._length = 0  # the option
 
     def init(self, nodes, row_offsets, col_indices, weights=None):
-        ro, ci = _csr_arrays(row_offsets, col_indices, nodes)
-        w = None if weights is None else _i32(weights)
-        if w is not None and w.shape[0] != ci.shape[0]:
-            raise ValueError("gunrockinst_amd: %d weights for %d entries" % (w.shape[0], ci.shape[0]))
-        self.nodes, self.entries = int(nodes), int(ci.shape[0])
-        _check(lib().grx_rw_init(self._h, self.nodes, self.entries, _p(ro), _p(ci), None if w is None else _p(w)), "RwProblem::Init")
-        return self
+        return self._init_host(nodes, row_offsets, col_indices, per_entry=(weights, "weights", "entries"))
 
     def init_device(self, nodes, edges, d_row_offsets, d_col_indices, d_weights=None):
-        """the CSR (and the weights) stay the caller's; the build reads them, nothing later does"""
-        self.nodes, self.entries = int(nodes), int(edges)
-        _check(lib().grx_rw_init_device(self._h, self.nodes, self.entries, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices),
-                                        C.c_void_p(d_weights)), "RwProblem::Init(device)")
-        return self
+        return self._init_device(nodes, edges, d_row_offsets, d_col_indices, C.c_void_p(d_weights))
 
     def set_option(self, name, value):
-        """"strategy" (RW_AUTO / RW_LANE / RW_TILE), "length", "seed", "weighted", "bias_return", "bias_in", "bias_out", "tries",
-        "visits"; returns the library's code: 0 = set, 1 = unknown name (a value out of range raises)"""
-        rc = lib().grx_rw_set_option(self._h, name.encode(), float(value))
-        if rc not in (0, 1):
-            _check(rc, "grx_rw_set_option(%s)" % name)
+        rc = super().set_option(name, value)
         if rc == 0 and name == "length":
             self._length = int(value)
         return rc
@@ -2212,39 +1858,23 @@ class RwProblem(_Handle):
         self.num_walks = int(s.shape[0])
 
     def enact(self, max_grid_size=0):
-        """the elapsed milliseconds"""
-        ms = self._timed(lib().grx_rw_enact, "RwEnactor::Enact", int(max_grid_size))
+        ms = super().enact(max_grid_size)
         self.length = self._length
         return ms
-
-    def stats(self):
-        w, s, e, t, f, n = (C.c_longlong() for _ in range(6))
-        k, b = C.c_double(), C.c_double()
-        _check(lib().grx_rw_stats(self._h, *[C.byref(x) for x in (w, s, e, t, f, n, k, b)]), "grx_rw_stats")
-        return {"walks": w.value, "steps": s.value, "ended_early": e.value, "biased_tries": t.value, "forced_fallbacks": f.value,
-                "kernel_launches": n.value, "kernel_ms": k.value, "build_ms": b.value}
 
     def extract(self, walks=True, lengths=True, visits=False):
         """(walks int32 num_walks x (length + 1), lengths int32, visits int64 per vertex, steps); None for what was not asked for"""
         out_w = np.empty((max(self.num_walks, 1), self.length + 1), dtype=np.int32) if walks else None
-        out_l = np.empty(max(self.num_walks, 1), dtype=np.int32) if lengths else None
-        out_v = np.empty(max(self.nodes, 1), dtype=np.int64) if visits else None
-        steps = C.c_longlong()
-        _check(lib().grx_rw_extract(self._h, None if out_w is None else _p(out_w), None if out_l is None else _p(out_l),
-                                    None if out_v is None else _i64p(out_v), C.byref(steps)), "RwProblem::Extract")
-        return (None if out_w is None else out_w[:self.num_walks], None if out_l is None else out_l[:self.num_walks],
-                None if out_v is None else out_v[:self.nodes], int(steps.value))
+        out_l, out_v, steps = _out(self.num_walks, wanted=lengths), _out(self.nodes, np.int64, visits), C.c_longlong()
+        _check(lib().grx_rw_extract(self._h, _opt(out_w), _opt(out_l), _opt(out_v), C.byref(steps)), "RwProblem::Extract")
+        return _cut(out_w, self.num_walks), _cut(out_l, self.num_walks), _cut(out_v, self.nodes), int(steps.value)
 
     def device_results(self):
         """device pointers {"walks": int32, rows "pitch" entries apart; "lengths": int32 per walk; "visits": int64 per vertex or None}
         and "pitch" """
-        names = ("walks", "lengths", "visits")
-        p = [C.c_void_p() for _ in names]
-        pitch = C.c_longlong()
-        _check(lib().grx_rw_device_results(self._h, *([C.byref(x) for x in p] + [C.byref(pitch)])), "grx_rw_device_results")
-        out = {name: x.value for name, x in zip(names, p)}
-        out["pitch"] = int(pitch.value)
-        return out
+        p, pitch = [C.c_void_p() for _ in self._results], C.c_longlong()
+        _check(lib().grx_rw_device_results(self._h, *map(C.byref, p), C.byref(pitch)), "grx_rw_device_results")
+        return dict(zip(self._results, (x.value for x in p)), pitch=int(pitch.value))
 
 
 def gunrock_random_walks(nodes, row_offsets, col_indices, starts, length, weights=None, seed=0, bias=None, tries=32, visits=False, device=0):
@@ -2276,43 +1906,29 @@ class SampleTooLarge(ArithmeticError):
     did not run, the handle holds no result and takes the next reset / enact."""
 
 
-class SampleProblem(_Handle):
+class SampleProblem(_TunedProblem):
     """SampleProblem + SampleEnactor behind the handle C ABI: multi-hop fanout neighbourhood samples of the CSR as given (directed,
     self-loops and duplicates kept), renumbered to dense local ids.  Every draw is rw_draw(seed, vertex, hop, slot); without
     replacement the picks of a row are Robert Floyd's subset over those draws (gunrock_mi355x.h has the definition), so the sample is
-    integers with one value: no option but "seed", "replace" and "weighted", the fanouts and the seeds changes it."""
+    integers with one value: no option but "seed", "replace" and "weighted", the fanouts and the seeds changes it.  The build reads
+    a device CSR (and the weights) and nothing later does.
 
-    _destroy = "grx_sample_destroy"
+    Options: "strategy" (SAMPLE_AUTO / SAMPLE_LANE / SAMPLE_GROUP), "seed", "replace", "weighted", "edge_limit", "long_row", "eids".
+    device_results: "vertices": int32[V], "offsets": int64[V + 1], "cols": int32[E], "eids": int32[E] or None."""
+
+    _family, _problem, _enactor = "sample", "SampleProblem", "SampleEnactor"
+    _count = "entries"
+    _results = ("vertices", "offsets", "cols", "eids")
 
     def __init__(self, instrument=False, device=0):
-        self._create("grx_sample_create", int(instrument), device)
-        self.nodes = 0
-        self.entries = 0
+        super().__init__(instrument, device)
         self.hops = 0
 
     def init(self, nodes, row_offsets, col_indices, weights=None):
-        ro, ci = _csr_arrays(row_offsets, col_indices, nodes)
-        w = None if weights is None else _i32(weights)
-        if w is not None and w.shape[0] != ci.shape[0]:
-            raise ValueError("gunrockinst_amd: %d weights for %d entries" % (w.shape[0], ci.shape[0]))
-        self.nodes, self.entries = int(nodes), int(ci.shape[0])
-        _check(lib().grx_sample_init(self._h, self.nodes, self.entries, _p(ro), _p(ci), None if w is None else _p(w)), "SampleProblem::Init")
-        return self
+        return self._init_host(nodes, row_offsets, col_indices, per_entry=(weights, "weights", "entries"))
 
     def init_device(self, nodes, edges, d_row_offsets, d_col_indices, d_weights=None):
-        """the CSR (and the weights) stay the caller's; the build reads them, nothing later does"""
-        self.nodes, self.entries = int(nodes), int(edges)
-        _check(lib().grx_sample_init_device(self._h, self.nodes, self.entries, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices),
-                                            C.c_void_p(d_weights)), "SampleProblem::Init(device)")
-        return self
-
-    def set_option(self, name, value):
-        """"strategy" (SAMPLE_AUTO / SAMPLE_LANE / SAMPLE_GROUP), "seed", "replace", "weighted", "edge_limit", "long_row", "eids";
-        returns the library's code: 0 = set, 1 = unknown name (a value out of range raises)"""
-        rc = lib().grx_sample_set_option(self._h, name.encode(), float(value))
-        if rc not in (0, 1):
-            _check(rc, "grx_sample_set_option(%s)" % name)
-        return rc
+        return self._init_device(nodes, edges, d_row_offsets, d_col_indices, C.c_void_p(d_weights))
 
     def set_fanouts(self, fanouts):
         """the fanout of every hop: -1 (the whole row) or 1 .. 64, for 1 .. 16 hops"""
@@ -2360,19 +1976,9 @@ class SampleProblem(_Handle):
     def extract(self, eids=True):
         """{"vertices", "vertex_ptr", "offsets", "cols", "eids" (None when not asked for), "edge_ptr"}"""
         v, e, vp, ep = self.sizes()
-        vertices, offsets = np.empty(max(v, 1), dtype=np.int32), np.empty(v + 1, dtype=np.int64)
-        cols = np.empty(max(e, 1), dtype=np.int32)
-        ids = np.empty(max(e, 1), dtype=np.int32) if eids else None
-        _check(lib().grx_sample_extract(self._h, _p(vertices), _i64p(offsets), _p(cols), None if ids is None else _p(ids)), "SampleProblem::Extract")
-        return {"vertices": vertices[:v], "vertex_ptr": vp, "offsets": offsets, "cols": cols[:e], "eids": None if ids is None else ids[:e],
-                "edge_ptr": ep}
-
-    def device_results(self):
-        """device pointers {"vertices": int32[V], "offsets": int64[V + 1], "cols": int32[E], "eids": int32[E] or None}"""
-        names = ("vertices", "offsets", "cols", "eids")
-        p = [C.c_void_p() for _ in names]
-        _check(lib().grx_sample_device_results(self._h, *[C.byref(x) for x in p]), "grx_sample_device_results")
-        return {name: x.value for name, x in zip(names, p)}
+        vertices, offsets, cols, ids = _out(v), _out(v + 1, np.int64), _out(e), _out(e, wanted=eids)
+        _check(lib().grx_sample_extract(self._h, _p(vertices), _i64p(offsets), _p(cols), _opt(ids)), "SampleProblem::Extract")
+        return {"vertices": vertices[:v], "vertex_ptr": vp, "offsets": offsets, "cols": cols[:e], "eids": _cut(ids, e), "edge_ptr": ep}
 
 
 def gunrock_sample_neighbors(nodes, row_offsets, col_indices, seeds, fanouts, weights=None, replace=False, seed=0, device=0):
@@ -2400,45 +2006,31 @@ class SimTooLarge(ArithmeticError):
     takes the next call"""
 
 
-class SimProblem(_Handle):
+class SimProblem(_TunedProblem):
     """SimProblem + SimEnactor behind the handle C ABI: vertex similarity of the CSR read as an undirected simple graph -- common
     neighbours, Jaccard, overlap and Sorensen as exact fractions num / den (int64) with the float64 score num / den, for given pairs
-    and as the k most similar vertices of given sources (score descending by exact comparison, then id ascending)."""
+    and as the k most similar vertices of given sources (score descending by exact comparison, then id ascending).  pairs / topk and
+    their _device forms take the place of enact.  The build reads a device CSR and nothing later does.
 
-    _destroy = "grx_sim_destroy"
+    Options: "metric" (SIM_COMMON / SIM_JACCARD / SIM_OVERLAP / SIM_SORENSEN), "skip_neighbors", "strategy" (SIM_AUTO / SIM_LANE /
+    SIM_WAVE / SIM_BLOCK / SIM_GLOBAL), "lane_max", "table_slots", "block_slots", "scratch_mib".
+    device_results: the integer results (None without a result of that mode)."""
+
+    _family, _problem, _enactor = "sim", "SimProblem", "SimEnactor"
+    _count = "entries"
+    _stats = (("simple_edges", "wedges", "wedges_walked", ("lane_pairs", "wave_pairs"), ("wave_sources", "block_sources", "global_sources"),
+               ("wave_wedges", "block_wedges", "global_wedges"), "candidates", "table_probes", "kernel_launches"), ("kernel_ms", "build_ms"))
+    _results = ("pair_common", "pair_num", "pair_den", "ids", "common", "num", "den", "count", "candidates")
+
+    @property
+    def enact(self):
+        raise AttributeError("SimProblem has no enact: pairs() and topk() take its place")
 
     def __init__(self, instrument=False, device=0):
-        self._create("grx_sim_create", int(instrument), device)
-        self.nodes = 0
-        self.entries = 0
+        super().__init__(instrument, device)
         self._pairs = 0
         self._rows = 0
         self._k = 1
-
-    def init(self, nodes, row_offsets, col_indices):
-        ro, ci = _csr_arrays(row_offsets, col_indices, nodes)
-        self.nodes, self.entries = int(nodes), int(ci.shape[0])
-        _check(lib().grx_sim_init(self._h, self.nodes, self.entries, _p(ro), _p(ci)), "SimProblem::Init")
-        return self
-
-    def init_device(self, nodes, edges, d_row_offsets, d_col_indices):
-        """the CSR stays the caller's; the build reads it, nothing later does"""
-        self.nodes, self.entries = int(nodes), int(edges)
-        _check(lib().grx_sim_init_device(self._h, self.nodes, self.entries, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices)),
-               "SimProblem::Init(device)")
-        return self
-
-    def set_option(self, name, value):
-        """"metric" (SIM_COMMON / SIM_JACCARD / SIM_OVERLAP / SIM_SORENSEN), "skip_neighbors", "strategy" (SIM_AUTO / SIM_LANE / SIM_WAVE /
-        SIM_BLOCK / SIM_GLOBAL), "lane_max", "table_slots", "block_slots", "scratch_mib"; returns the library's code: 0 = set,
-        1 = unknown name (a value out of range raises)"""
-        rc = lib().grx_sim_set_option(self._h, name.encode(), float(value))
-        if rc not in (0, 1):
-            _check(rc, "grx_sim_set_option(%s)" % name)
-        return rc
-
-    def reset(self):
-        _check(lib().grx_sim_reset(self._h), "SimProblem::Reset")
 
     @staticmethod
     def _enacted(rc, what):
@@ -2483,27 +2075,11 @@ class SimProblem(_Handle):
         self._rows, self._k = int(num_sources), int(k)
         return float(ms.value)
 
-    def stats(self):
-        m, w, walked, candidates, probes, n = (C.c_longlong() for _ in range(6))
-        pairs, sources, wedges = (C.c_longlong * 2)(), (C.c_longlong * 3)(), (C.c_longlong * 3)()
-        k, b = C.c_double(), C.c_double()
-        _check(lib().grx_sim_stats(self._h, C.byref(m), C.byref(w), C.byref(walked), pairs, sources, wedges, C.byref(candidates), C.byref(probes),
-                                   C.byref(n), C.byref(k), C.byref(b)), "grx_sim_stats")
-        out = {"simple_edges": m.value, "wedges": w.value, "wedges_walked": walked.value, "candidates": candidates.value,
-               "table_probes": probes.value, "kernel_launches": n.value, "kernel_ms": k.value, "build_ms": b.value,
-               "lane_pairs": int(pairs[0]), "wave_pairs": int(pairs[1])}
-        for i, name in enumerate(("wave", "block", "global")):
-            out[name + "_sources"], out[name + "_wedges"] = int(sources[i]), int(wedges[i])
-        return out
-
     def extract_pairs(self):
         """{"common": int32, "num", "den": int64, "score": float64}, one entry per pair of the last pairs()"""
         count = self._pairs
-        common = np.empty(max(count, 1), dtype=np.int32)
-        num, den = (np.empty(max(count, 1), dtype=np.int64) for _ in range(2))
-        score = np.empty(max(count, 1), dtype=np.float64)
-        _check(lib().grx_sim_extract_pairs(self._h, _p(common), _i64p(num), _i64p(den), score.ctypes.data_as(C.POINTER(C.c_double))),
-               "SimProblem::ExtractPairs")
+        common, num, den, score = _out(count), _out(count, np.int64), _out(count, np.int64), _out(count, np.float64)
+        _check(lib().grx_sim_extract_pairs(self._h, _p(common), _i64p(num), _i64p(den), _f64p(score)), "SimProblem::ExtractPairs")
         return {"common": common[:count], "num": num[:count], "den": den[:count], "score": score[:count]}
 
     def extract_topk(self):
@@ -2511,23 +2087,13 @@ class SimProblem(_Handle):
         last topk(); ids are -1 and the rest 0 beyond count[s]"""
         rows, k = self._rows, self._k
         count = rows * k
-        ids, common = (np.empty(max(count, 1), dtype=np.int32) for _ in range(2))
-        num, den = (np.empty(max(count, 1), dtype=np.int64) for _ in range(2))
-        score = np.empty(max(count, 1), dtype=np.float64)
-        kept, candidates = (np.empty(max(rows, 1), dtype=np.int32) for _ in range(2))
-        _check(lib().grx_sim_extract_topk(self._h, _p(ids), _p(common), _i64p(num), _i64p(den), score.ctypes.data_as(C.POINTER(C.c_double)),
-                                          _p(kept), _p(candidates)), "SimProblem::ExtractTopk")
+        ids, common, num, den, score = _out(count), _out(count), _out(count, np.int64), _out(count, np.int64), _out(count, np.float64)
+        kept, candidates = _out(rows), _out(rows)
+        _check(lib().grx_sim_extract_topk(self._h, _p(ids), _p(common), _i64p(num), _i64p(den), _f64p(score), _p(kept), _p(candidates)),
+               "SimProblem::ExtractTopk")
         out = {name: a[:count].reshape(rows, k) for name, a in (("ids", ids), ("common", common), ("num", num), ("den", den), ("score", score))}
         out["count"], out["candidates"] = kept[:rows], candidates[:rows]
         return out
-
-    def device_results(self):
-        """device pointers of the integer results: {"pair_common", "pair_num", "pair_den", "ids", "common", "num", "den", "count",
-        "candidates"} (None without a result of that mode)"""
-        names = ("pair_common", "pair_num", "pair_den", "ids", "common", "num", "den", "count", "candidates")
-        p = [C.c_void_p() for _ in names]
-        _check(lib().grx_sim_device_results(self._h, *[C.byref(x) for x in p]), "grx_sim_device_results")
-        return {name: x.value for name, x in zip(names, p)}
 
 
 def gunrock_similarity(offsets, cols, u, v, metric=SIM_JACCARD, device=0):
@@ -2588,13 +2154,18 @@ def _matrix(m):
     return shape, ro, ci, vals
 
 
-class SpgemmProblem(_Handle):
+class SpgemmProblem(_TunedProblem):
     """SpgemmProblem + SpgemmEnactor behind the handle C ABI: the sparse product C = A B of CSR matrices with int32 values (absent: 1
     each) read as given -- duplicates add, rows in any order -- as a CSR with strictly ascending rows and exact int64 values.  C is
-    structural: an entry whose products cancel is stored with the value 0."""
+    structural: an entry whose products cancel is stored with the value 0.  Its operands are matrices with a shape, so init,
+    init_device and the constructor's attributes (rows, inner, entries) are its own.
 
-    _destroy = "grx_spgemm_destroy"
+    Options: "right" (SPGEMM_SELF / SPGEMM_TRANSPOSE / SPGEMM_GIVEN), "pattern_only", "strategy" (SPGEMM_AUTO / SPGEMM_LANE /
+    SPGEMM_WAVE / SPGEMM_BLOCK / SPGEMM_GLOBAL), "lane_max", "table_slots", "block_slots", "scratch_mib", "count_limit".
+    device_results: "offsets", "cols": int32; "vals": int64 (None without a result, or without entries or values)."""
 
+    _family, _problem, _enactor = "spgemm", "SpgemmProblem", "SpgemmEnactor"
+    _results = ("offsets", "cols", "vals")
     _REGIMES = ("lane", "wave", "block", "global")
 
     def __init__(self, instrument=False, device=0):
@@ -2607,44 +2178,31 @@ class SpgemmProblem(_Handle):
         """A of shape (rows, inner) from the host"""
         (self.rows, self.inner), ro, ci, v = _matrix((shape, offsets, cols, vals))
         self.entries = int(ci.shape[0])
-        _check(lib().grx_spgemm_init(self._h, self.rows, self.inner, self.entries, _p(ro), _p(ci), None if v is None else _p(v)),
-               "SpgemmProblem::Init")
+        _check(lib().grx_spgemm_init(self._h, self.rows, self.inner, self.entries, _p(ro), _p(ci), _opt(v)), "SpgemmProblem::Init")
         return self
 
     def init_device(self, shape, nnz, d_offsets, d_cols, d_vals=None):
         """the CSR stays the caller's and must outlive the handle's enacts"""
         self.rows, self.inner, self.entries = int(shape[0]), int(shape[1]), int(nnz)
         _check(lib().grx_spgemm_init_device(self._h, self.rows, self.inner, self.entries, C.c_void_p(d_offsets), C.c_void_p(d_cols),
-                                            C.c_void_p(d_vals) if d_vals else None), "SpgemmProblem::Init(device)")
+                                            C.c_void_p(d_vals)), "SpgemmProblem::Init(device)")
         return self
 
     def set_right(self, shape, offsets, cols, vals=None):
         """B of shape (inner, cols) from the host; selects SPGEMM_GIVEN.  Returns the library's code: 0, -1 (B's rows are not A's
         inner) or -2 (not a CSR); anything else raises"""
         (rows, ncols), ro, ci, v = _matrix((shape, offsets, cols, vals))
-        rc = lib().grx_spgemm_set_right(self._h, rows, ncols, int(ci.shape[0]), _p(ro), _p(ci), None if v is None else _p(v))
+        rc = lib().grx_spgemm_set_right(self._h, rows, ncols, int(ci.shape[0]), _p(ro), _p(ci), _opt(v))
         if rc not in (0, -1, -2):
             _check(rc, "SpgemmProblem::SetRight")
         return rc
 
     def set_right_device(self, shape, nnz, d_offsets, d_cols, d_vals=None):
         rc = lib().grx_spgemm_set_right_device(self._h, int(shape[0]), int(shape[1]), int(nnz), C.c_void_p(d_offsets), C.c_void_p(d_cols),
-                                               C.c_void_p(d_vals) if d_vals else None)
+                                               C.c_void_p(d_vals))
         if rc not in (0, -1, -2):
             _check(rc, "SpgemmProblem::SetRight(device)")
         return rc
-
-    def set_option(self, name, value):
-        """"right" (SPGEMM_SELF / SPGEMM_TRANSPOSE / SPGEMM_GIVEN), "pattern_only", "strategy" (SPGEMM_AUTO / SPGEMM_LANE / SPGEMM_WAVE /
-        SPGEMM_BLOCK / SPGEMM_GLOBAL), "lane_max", "table_slots", "block_slots", "scratch_mib", "count_limit"; returns the library's
-        code: 0 = set, 1 = unknown name (a value out of range raises)"""
-        rc = lib().grx_spgemm_set_option(self._h, name.encode(), float(value))
-        if rc not in (0, 1):
-            _check(rc, "grx_spgemm_set_option(%s)" % name)
-        return rc
-
-    def reset(self):
-        _check(lib().grx_spgemm_reset(self._h), "SpgemmProblem::Reset")
 
     def enact(self, max_grid_size=0):
         """the elapsed milliseconds; SpgemmTooLarge / SpgemmOverflow when the product was refused.  A shape the right operand does
@@ -2680,17 +2238,9 @@ class SpgemmProblem(_Handle):
     def extract(self, values=True):
         """{"offsets": int32[rows + 1], "cols": int32[nnz], "vals": int64[nnz] or None, "shape": (rows, cols)} of the last enact"""
         rows, cols, nnz = self.sizes()
-        offsets, ci = np.empty(rows + 1, dtype=np.int32), np.empty(max(nnz, 1), dtype=np.int32)
-        vals = np.empty(max(nnz, 1), dtype=np.int64) if values else None
-        _check(lib().grx_spgemm_extract(self._h, _p(offsets), _p(ci), None if vals is None else _i64p(vals)), "SpgemmProblem::Extract")
-        return {"offsets": offsets, "cols": ci[:nnz], "vals": None if vals is None else vals[:nnz], "shape": (rows, cols)}
-
-    def device_results(self):
-        """device pointers {"offsets", "cols": int32; "vals": int64} (None without a result, or without entries or values)"""
-        names = ("offsets", "cols", "vals")
-        p = [C.c_void_p() for _ in names]
-        _check(lib().grx_spgemm_device_results(self._h, *[C.byref(x) for x in p]), "grx_spgemm_device_results")
-        return {name: x.value for name, x in zip(names, p)}
+        offsets, ci, vals = _out(rows + 1), _out(nnz), _out(nnz, np.int64, values)
+        _check(lib().grx_spgemm_extract(self._h, _p(offsets), _p(ci), _opt(vals)), "SpgemmProblem::Extract")
+        return {"offsets": offsets, "cols": ci[:nnz], "vals": _cut(vals, nnz), "shape": (rows, cols)}
 
 
 def gunrock_spgemm(a, b=None, transpose_right=False, pattern_only=False, device=0):
@@ -2738,112 +2288,60 @@ LP_CONVERGED, LP_PERIOD2, LP_CAPPED = 0, 1, 2  # stats()["state"]: how the last 
 LP_BAD_CLASSES = -8  # grx_lp_set_classes: a pair has both ends in one class
 
 
-class LpProblem(_Handle):
+class LpProblem(_TunedProblem):
     """LpProblem + LpEnactor behind the handle C ABI: label-propagation communities of the CSR read as an undirected simple graph
     with int32 weights of at least 1 (None: 1 each; a pair's weight is the largest of its entries).  Integer scores and a total tie
-    rule (keep the current label, else the smallest): every label has one value after any number of rounds."""
+    rule (keep the current label, else the smallest): every label has one value after any number of rounds.  The build reads a
+    device CSR (and the weights) and nothing later does; stats()["state"] tells how the last enact ended.
 
-    _destroy = "grx_lp_destroy"
+    Options: "mode" (LP_CLASSES / LP_SYNC), "strategy" (LP_AUTO / LP_LANE / LP_WAVE / LP_BLOCK), "lane_max_row", "wave_max_row",
+    "table_slots", "max_rounds".
+    device_results: "labels", "community": int32 per vertex."""
 
-    _STATS = ("pairs", "rounds", "state", "visits", "entries_read")
-    _STATS_TAIL = ("fallback_rows", "kernel_launches", "readbacks")
-
-    def __init__(self, instrument=False, device=0):
-        self._create("grx_lp_create", int(instrument), device)
-        self.nodes = 0
-        self.entries = 0
+    _family, _problem, _enactor = "lp", "LpProblem", "LpEnactor"
+    _count = "entries"
+    _stats = (("pairs", "rounds", "state", "visits", "entries_read", ("regime_rows", 3), "fallback_rows", "kernel_launches", "readbacks"),
+              ("kernel_ms", "build_ms"))
+    _results = ("labels", "community")
 
     def init(self, nodes, row_offsets, col_indices, weights=None):
-        ro, ci = _csr_arrays(row_offsets, col_indices, nodes)
-        w = None if weights is None else _i32(weights)
-        if w is not None and w.shape[0] != ci.shape[0]:
-            raise ValueError("gunrockinst_amd: %d weights for %d entries" % (w.shape[0], ci.shape[0]))
-        self.nodes, self.entries = int(nodes), int(ci.shape[0])
-        _check(lib().grx_lp_init(self._h, self.nodes, self.entries, _p(ro), _p(ci), None if w is None else _p(w)), "LpProblem::Init")
-        return self
+        return self._init_host(nodes, row_offsets, col_indices, per_entry=(weights, "weights", "entries"))
 
     def init_device(self, nodes, edges, d_row_offsets, d_col_indices, d_weights=None):
-        """the CSR (and the weights) stay the caller's; the build reads them, nothing later does"""
-        self.nodes, self.entries = int(nodes), int(edges)
-        _check(lib().grx_lp_init_device(self._h, self.nodes, self.entries, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices),
-                                        C.c_void_p(d_weights) if d_weights else None), "LpProblem::Init(device)")
-        return self
+        return self._init_device(nodes, edges, d_row_offsets, d_col_indices, C.c_void_p(d_weights))
 
     def set_classes(self, classes, num_classes=None):
         """a proper colouring for LP_CLASSES: int32 per vertex in [0, num_classes) (None: max + 1); returns the library's code:
         0 = installed, LP_BAD_CLASSES = a pair has both ends in one class and nothing is installed (anything else raises)"""
-        cl = _i32(classes)
-        if cl.shape[0] != self.nodes:
-            raise ValueError("gunrockinst_amd: %d classes for %d nodes" % (cl.shape[0], self.nodes))
+        cl = _i32_of(classes, self.nodes, "classes", "nodes")
         count = int(cl.max()) + 1 if num_classes is None else int(num_classes)
         rc = lib().grx_lp_set_classes(self._h, _p(cl), count)
         if rc not in (0, LP_BAD_CLASSES):
             _check(rc, "LpProblem::SetClasses")
         return rc
 
-    def set_option(self, name, value):
-        """"mode" (LP_CLASSES / LP_SYNC), "strategy" (LP_AUTO / LP_LANE / LP_WAVE / LP_BLOCK), "lane_max_row", "wave_max_row",
-        "table_slots", "max_rounds"; returns the library's code: 0 = set, 1 = unknown name (a value out of range raises)"""
-        rc = lib().grx_lp_set_option(self._h, name.encode(), float(value))
-        if rc not in (0, 1):
-            _check(rc, "grx_lp_set_option(%s)" % name)
-        return rc
-
     def reset(self, labels=None):
         """L[v] = labels[v] (int32 in [0, nodes)), or v for None"""
-        lb = None if labels is None else _i32(labels)
-        if lb is not None and lb.shape[0] != self.nodes:
-            raise ValueError("gunrockinst_amd: %d labels for %d nodes" % (lb.shape[0], self.nodes))
-        _check(lib().grx_lp_reset(self._h, None if lb is None else _p(lb)), "LpProblem::Reset")
-
-    def enact(self, max_grid_size=0):
-        """the elapsed milliseconds; stats()["state"] tells how it ended"""
-        return self._timed(lib().grx_lp_enact, "LpEnactor::Enact", int(max_grid_size))
-
-    def stats(self):
-        v = [C.c_longlong() for _ in self._STATS]
-        regime = (C.c_longlong * 3)()
-        tail = [C.c_longlong() for _ in self._STATS_TAIL]
-        k, b = C.c_double(), C.c_double()
-        _check(lib().grx_lp_stats(self._h, *([C.byref(x) for x in v] + [regime] + [C.byref(x) for x in tail] + [C.byref(k), C.byref(b)])),
-               "grx_lp_stats")
-        out = {name: x.value for name, x in zip(self._STATS + self._STATS_TAIL, v + tail)}
-        out["regime_rows"] = [int(x) for x in regime]
-        out["kernel_ms"], out["build_ms"] = k.value, b.value
-        return out
+        self._reset_labels(labels)
 
     def round_trace(self):
         """per round of the last enact, the closing one included: (vertices visited, labels changed) as int64"""
-        count = lib().grx_lp_round_trace(self._h, 0, None, None)
-        if count < 0:
-            _check(count, "grx_lp_round_trace")
-        visited, changed = (np.empty(max(count, 1), dtype=np.int64) for _ in range(2))
-        lib().grx_lp_round_trace(self._h, count, _i64p(visited), _i64p(changed))
-        return visited[:count], changed[:count]
+        return _count_then_fill(lib().grx_lp_round_trace, self._h, "grx_lp_round_trace", (np.int64, np.int64))
 
     def extract(self):
         """(labels int32 per vertex, community int32 per vertex: the rank of its label among the labels in use, communities)"""
-        n = max(self.nodes, 1)
-        labels, community = np.empty(n, np.int32), np.empty(n, np.int32)
-        count = C.c_longlong()
+        labels, community, count = _out(self.nodes), _out(self.nodes), C.c_longlong()
         _check(lib().grx_lp_extract(self._h, _p(labels), _p(community), C.byref(count)), "LpProblem::Extract")
         return labels[:self.nodes], community[:self.nodes], int(count.value)
 
     def summary(self):
         """{"size", "internal", "volume": int64 per community, "W": the sum of all pair weights}"""
-        count = C.c_longlong()
+        count, total = C.c_longlong(), C.c_longlong()
         _check(lib().grx_lp_extract(self._h, None, None, C.byref(count)), "LpProblem::Extract")
         k = int(count.value)
-        size, internal, volume = (np.empty(max(k, 1), np.int64) for _ in range(3))
-        total = C.c_longlong()
+        size, internal, volume = (_out(k, np.int64) for _ in range(3))
         _check(lib().grx_lp_summary(self._h, _i64p(size), _i64p(internal), _i64p(volume), C.byref(total)), "LpProblem::Summary")
         return {"size": size[:k], "internal": internal[:k], "volume": volume[:k], "W": int(total.value)}
-
-    def device_results(self):
-        """device pointers {"labels", "community"}: int32 per vertex"""
-        a, b = C.c_void_p(), C.c_void_p()
-        _check(lib().grx_lp_device_results(self._h, C.byref(a), C.byref(b)), "grx_lp_device_results")
-        return {"labels": a.value, "community": b.value}
 
 
 def modularity_from_sums(internal, volume, W):
@@ -2902,49 +2400,25 @@ def wl_mix(seed, attempt, colour):
     return mix((int(seed) & m) ^ mix(x)), mix((int(seed) & m) ^ mix(x ^ m))
 
 
-class WlProblem(_Handle):
+class WlProblem(_TunedProblem):
     """WlProblem + WlEnactor behind the handle C ABI: colour refinement (1-WL) of the CSR as given -- a row is the multiset of its
     entries -- from the classes of any int32 start labels down to the coarsest equitable partition, or for a fixed number of rounds.
-    The classes are numbered by ascending smallest member; every result is certified by an exact comparison of rows."""
+    The classes are numbered by ascending smallest member; every result is certified by an exact comparison of rows.  A device CSR
+    stays the caller's and is read by every enact: it has to outlive the handle.
 
-    _destroy = "grx_wl_destroy"
+    Options: "strategy" (WL_AUTO / WL_LANE / WL_WAVE / WL_BLOCK), "lane_max_row", "wave_max_row", "max_rounds", "history",
+    "max_repairs", "sig_bits", "seed", "table_slots", "block_slots", "scratch_mib".
+    device_results: "colour": int32 per vertex, "class_size": int64 per class, "representative": int32 per class."""
 
-    _STATS = ("entries", "rounds", "state", "classes", "repairs", "certificate_runs")
-    _STATS_TAIL = ("kernel_launches", "readbacks")
-
-    def __init__(self, instrument=False, device=0):
-        self._create("grx_wl_create", int(instrument), device)
-        self.nodes = 0
-        self.entries = 0
-
-    def init(self, nodes, row_offsets, col_indices):
-        ro, ci = _csr_arrays(row_offsets, col_indices, nodes)
-        self.nodes, self.entries = int(nodes), int(ci.shape[0])
-        _check(lib().grx_wl_init(self._h, self.nodes, self.entries, _p(ro), _p(ci)), "WlProblem::Init")
-        return self
-
-    def init_device(self, nodes, edges, d_row_offsets, d_col_indices):
-        """the CSR stays the caller's and is read by every enact: it has to outlive the handle"""
-        self.nodes, self.entries = int(nodes), int(edges)
-        _check(lib().grx_wl_init_device(self._h, self.nodes, self.entries, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices)),
-               "WlProblem::Init(device)")
-        return self
-
-    def set_option(self, name, value):
-        """"strategy" (WL_AUTO / WL_LANE / WL_WAVE / WL_BLOCK), "lane_max_row", "wave_max_row", "max_rounds", "history", "max_repairs",
-        "sig_bits", "seed", "table_slots", "block_slots", "scratch_mib"; returns the library's code: 0 = set, 1 = unknown name (a value
-        out of range raises)"""
-        rc = lib().grx_wl_set_option(self._h, name.encode(), float(value))
-        if rc not in (0, 1):
-            _check(rc, "grx_wl_set_option(%s)" % name)
-        return rc
+    _family, _problem, _enactor = "wl", "WlProblem", "WlEnactor"
+    _count = "entries"
+    _stats = (("entries", "rounds", "state", "classes", "repairs", "certificate_runs", ("regime_rows", 3), ("rung_rows", 3), "kernel_launches",
+               "readbacks"), ("kernel_ms",))
+    _results = ("colour", "class_size", "representative")
 
     def reset(self, labels=None):
         """the start labels: int32 of any value per vertex, or None for one class"""
-        lb = None if labels is None else _i32(labels)
-        if lb is not None and lb.shape[0] != self.nodes:
-            raise ValueError("gunrockinst_amd: %d labels for %d nodes" % (lb.shape[0], self.nodes))
-        _check(lib().grx_wl_reset(self._h, None if lb is None else _p(lb)), "WlProblem::Reset")
+        self._reset_labels(labels)
 
     def enact(self, max_grid_size=0):
         """the elapsed milliseconds; stats()["state"] tells how it ended.  WlNotCertified, WlTooLarge: there is no result"""
@@ -2957,34 +2431,16 @@ class WlProblem(_Handle):
         _check(rc, "WlEnactor::Enact")
         return float(ms.value)
 
-    def stats(self):
-        v = [C.c_longlong() for _ in self._STATS]
-        regime, rung = (C.c_longlong * 3)(), (C.c_longlong * 3)()
-        tail = [C.c_longlong() for _ in self._STATS_TAIL]
-        k = C.c_double()
-        _check(lib().grx_wl_stats(self._h, *([C.byref(x) for x in v] + [regime, rung] + [C.byref(x) for x in tail] + [C.byref(k)])),
-               "grx_wl_stats")
-        out = {name: x.value for name, x in zip(self._STATS + self._STATS_TAIL, v + tail)}
-        out["regime_rows"] = [int(x) for x in regime]
-        out["rung_rows"] = [int(x) for x in rung]
-        out["kernel_ms"] = k.value
-        return out
-
     def round_trace(self):
         """the classes behind the labels and behind each committed round of the last enact, int64 (rounds + 1 entries)"""
-        count = lib().grx_wl_round_trace(self._h, 0, None)
-        if count < 0:
-            _check(count, "grx_wl_round_trace")
-        classes = np.empty(max(count, 1), dtype=np.int64)
-        lib().grx_wl_round_trace(self._h, count, _i64p(classes))
-        return classes[:count]
+        return _count_then_fill(lib().grx_wl_round_trace, self._h, "grx_wl_round_trace", (np.int64,))[0]
 
     def extract(self):
         """(colour int32 per vertex, class_size int64 per class, representative int32 per class: its smallest member)"""
         count = C.c_longlong()
         _check(lib().grx_wl_extract(self._h, None, None, None, C.byref(count)), "WlProblem::Extract")
         k = int(count.value)
-        colour, size, rep = np.empty(max(self.nodes, 1), np.int32), np.empty(max(k, 1), np.int64), np.empty(max(k, 1), np.int32)
+        colour, size, rep = _out(self.nodes), _out(k, np.int64), _out(k)
         _check(lib().grx_wl_extract(self._h, _p(colour), _i64p(size), _p(rep), None), "WlProblem::Extract")
         return colour[:self.nodes], size[:k], rep[:k]
 
@@ -2995,12 +2451,6 @@ class WlProblem(_Handle):
         for h in range(rounds + 1):
             _check(lib().grx_wl_history(self._h, h, _p(out[h]), None), "WlProblem::History")
         return out[:, :self.nodes]
-
-    def device_results(self):
-        """device pointers {"colour": int32 per vertex, "class_size": int64 per class, "representative": int32 per class}"""
-        a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        _check(lib().grx_wl_device_results(self._h, C.byref(a), C.byref(b), C.byref(c)), "grx_wl_device_results")
-        return {"colour": a.value, "class_size": b.value, "representative": c.value}
 
 
 def gunrock_colour_refinement(nodes, row_offsets, col_indices, labels=None, max_rounds=-1, history=False, seed=0, device=0):
@@ -3049,44 +2499,25 @@ MSBFS_LEVEL_PUSH, MSBFS_LEVEL_PULL = 0, 1  # enum GRX_MSBFS_LEVEL_*: the kinds o
 MSBFS_DEPTHS_NOT_STORED, MSBFS_INVERSE_NOT_SYMMETRIC = -4, -5  # the family's codes next to -1 / -2 / -3
 
 
-def _i64p(a):
-    return a.ctypes.data_as(C.POINTER(C.c_longlong))
-
-
-class MsbfsProblem(_Handle):
+class MsbfsProblem(_TunedProblem):
     """MsbfsProblem + MsbfsEnactor behind the handle C ABI: breadth-first searches from k sources on the CSR read as a directed
-    multigraph, 64 sources per pass over the edges.  All results are integers: depths(), source_summary(), vertex_summary()."""
+    multigraph, 64 sources per pass over the edges.  All results are integers: depths(), source_summary(), vertex_summary().
 
-    _destroy = "grx_msbfs_destroy"
+    Options: "direction" (MSBFS_AUTO / MSBFS_PUSH / MSBFS_PULL / MSBFS_ALTERNATE), "inverse" (MSBFS_INVERSE_*, settled by the next
+    reset), "alpha", "beta", "wave_min_row".
+    device_results: device pointers of (depth or None, reached, dist_sum, ecc, sources_reaching, in_dist_sum)."""
 
-    _STATS = ("batches", "levels", "push_levels", "pull_levels", "entries_read", "kernel_launches")
+    _family, _problem, _enactor = "msbfs", "MsbfsProblem", "MsbfsEnactor"
+    _stats = (("batches", "levels", "push_levels", "pull_levels", "entries_read", "kernel_launches"), ("kernel_ms", "build_ms"))
+    _results = 6
 
     def __init__(self, instrument=False, device=0):
-        self._create("grx_msbfs_create", int(instrument), device)
-        self.nodes = 0
-        self.edges = 0
+        super().__init__(instrument, device)
         self.sources = 0
-
-    def init(self, nodes, row_offsets, col_indices):
-        ro, ci = _csr_arrays(row_offsets, col_indices, nodes)
-        self.nodes, self.edges = int(nodes), int(ci.shape[0])
-        _check(lib().grx_msbfs_init(self._h, self.nodes, self.edges, _p(ro), _p(ci)), "MsbfsProblem::Init")
-        return self
 
     def init_device(self, nodes, edges, d_row_offsets, d_col_indices, d_inv_row_offsets=None, d_inv_col_indices=None):
         """a CSR in HBM (borrowed); the in-neighbour lists too when both inverse pointers are given"""
-        self.nodes, self.edges = int(nodes), int(edges)
-        _check(lib().grx_msbfs_init_device(self._h, self.nodes, self.edges, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices),
-                                           C.c_void_p(d_inv_row_offsets), C.c_void_p(d_inv_col_indices)), "MsbfsProblem::Init(device)")
-        return self
-
-    def set_option(self, name, value):
-        """"direction" (MSBFS_AUTO / MSBFS_PUSH / MSBFS_PULL / MSBFS_ALTERNATE), "inverse" (MSBFS_INVERSE_*, settled by the next
-        reset), "alpha", "beta", "wave_min_row"; returns the library's code: 0 = set, 1 = unknown name (a value out of range raises)"""
-        rc = lib().grx_msbfs_set_option(self._h, name.encode(), float(value))
-        if rc not in (0, 1):
-            _check(rc, "grx_msbfs_set_option(%s)" % name)
-        return rc
+        return self._init_device(nodes, edges, d_row_offsets, d_col_indices, C.c_void_p(d_inv_row_offsets), C.c_void_p(d_inv_col_indices))
 
     def reset(self, sources, store_depths=True):
         """the sources (vertex ids, repeats allowed, at least one) of the next enact.  Raises with code -1 for a source outside
@@ -3095,28 +2526,11 @@ class MsbfsProblem(_Handle):
         _check(lib().grx_msbfs_reset(self._h, _p(src), int(src.shape[0]), int(bool(store_depths))), "MsbfsProblem::Reset")
         self.sources = int(src.shape[0])
 
-    def enact(self, max_grid_size=0):
-        return self._timed(lib().grx_msbfs_enact, "MsbfsEnactor::Enact", max_grid_size)
-
-    def stats(self):
-        v = [C.c_longlong() for _ in self._STATS]
-        k, b = C.c_double(), C.c_double()
-        _check(lib().grx_msbfs_stats(self._h, *([C.byref(x) for x in v] + [C.byref(k), C.byref(b)])), "grx_msbfs_stats")
-        out = {name: x.value for name, x in zip(self._STATS, v)}
-        out["kernel_ms"], out["build_ms"] = k.value, b.value
-        return out
-
     def level_trace(self):
         """the levels of the last enact in order: (batch, level, kind: MSBFS_LEVEL_PUSH / MSBFS_LEVEL_PULL) as int32, (frontier
         vertices, frontier out-row entries) as int64, milliseconds as float64 (0 unless instrumented)"""
-        count = lib().grx_msbfs_level_trace(self._h, 0, None, None, None, None, None, None)
-        if count < 0:
-            _check(count, "grx_msbfs_level_trace")
-        batch, level, kind = (np.empty(max(count, 1), dtype=np.int32) for _ in range(3))
-        frontier, edges = (np.empty(max(count, 1), dtype=np.int64) for _ in range(2))
-        ms = np.empty(max(count, 1), dtype=np.float64)
-        lib().grx_msbfs_level_trace(self._h, count, _p(batch), _p(level), _p(kind), _i64p(frontier), _i64p(edges), ms.ctypes.data_as(C.POINTER(C.c_double)))
-        return batch[:count], level[:count], kind[:count], frontier[:count], edges[:count], ms[:count]
+        return _count_then_fill(lib().grx_msbfs_level_trace, self._h, "grx_msbfs_level_trace",
+                                (np.int32,) * 3 + (np.int64,) * 2 + (np.float64,))
 
     def depths(self, first=0, count=None):
         """depth[first : first + count] as int32 [count, nodes]; raises with code -4 after a reset with store_depths off"""
@@ -3127,23 +2541,16 @@ class MsbfsProblem(_Handle):
 
     def source_summary(self):
         """(reached int64, dist_sum int64, ecc int32), one entry per source"""
-        reached, dist_sum = (np.empty(max(self.sources, 1), dtype=np.int64) for _ in range(2))
-        ecc = np.empty(max(self.sources, 1), dtype=np.int32)
+        k = self.sources
+        reached, dist_sum, ecc = _out(k, np.int64), _out(k, np.int64), _out(k)
         _check(lib().grx_msbfs_source_summary(self._h, _i64p(reached), _i64p(dist_sum), _p(ecc)), "MsbfsProblem::SourceSummary")
-        return reached[:self.sources], dist_sum[:self.sources], ecc[:self.sources]
+        return reached[:k], dist_sum[:k], ecc[:k]
 
     def vertex_summary(self):
         """(sources_reaching int32, in_dist_sum int64), one entry per vertex"""
-        reaching = np.empty(max(self.nodes, 1), dtype=np.int32)
-        in_dist_sum = np.empty(max(self.nodes, 1), dtype=np.int64)
+        reaching, in_dist_sum = _out(self.nodes), _out(self.nodes, np.int64)
         _check(lib().grx_msbfs_vertex_summary(self._h, _p(reaching), _i64p(in_dist_sum)), "MsbfsProblem::VertexSummary")
         return reaching[:self.nodes], in_dist_sum[:self.nodes]
-
-    def device_results(self):
-        """device pointers of (depth or None, reached, dist_sum, ecc, sources_reaching, in_dist_sum)"""
-        v = [C.c_void_p() for _ in range(6)]
-        _check(lib().grx_msbfs_device_results(self._h, *[C.byref(x) for x in v]), "grx_msbfs_device_results")
-        return tuple(x.value for x in v)
 
 
 def closeness_from_sums(nodes, sources, sources_reaching, in_dist_sum, wf_improved=True):
@@ -3218,8 +2625,7 @@ def gunrock_pr(nodes, row_offsets, col_indices, src=-1, delta=0.85, error=0.01, 
     cfg.src_node, cfg.device, cfg.src_mode = src, device, src_mode
     cfg.delta, cfg.error, cfg.max_iter, cfg.top_nodes = delta, error, max_iter, top_nodes
     count = nodes if top_nodes <= 0 else min(nodes, top_nodes)
-    ids = np.empty(max(count, 1), dtype=np.int32)
-    ranks = np.empty(max(count, 1), dtype=np.float32)
+    ids, ranks = _out(count), _out(count, np.float32)
     dt = GunrockDataType(VTXID_INT, SIZET_INT, VALUE_FLOAT)
     lib().gunrock_pr_func(C.byref(gout), ids.ctypes.data_as(C.c_void_p), ranks.ctypes.data_as(C.c_void_p), C.byref(gin), cfg, dt)
     return ids[:count], ranks[:count]
@@ -3244,26 +2650,18 @@ def gunrock_topk(nodes, row_offsets, col_indices, col_offsets, row_indices, top_
     return ids[:k], ind[:k], outd[:k]
 
 
-class PrProblem(_Handle):
-    """PRProblem + PREnactor behind the handle ABI (grx_pr_*)."""
+class PrProblem(_Problem):
+    """PRProblem + PREnactor behind the handle ABI (grx_pr_*).  reset and enact are timed by the benchmark and name their symbols
+    directly; device_results: (ranks, node ids)."""
 
-    _destroy = "grx_pr_destroy"
+    _family, _problem, _enactor = "pr", "PRProblem", "PREnactor"
+    _check_rows = False
+    _stats = (("iterations", "peeling_rounds", "surviving_nodes"), ())
+    _results = 2
 
     def __init__(self, device=0):
         self._create("grx_pr_create", device)
         self.nodes = self.edges = 0
-
-    def init(self, nodes, row_offsets, col_indices):
-        ro, ci = _csr_arrays(row_offsets, col_indices)
-        self.nodes, self.edges = int(nodes), int(ci.shape[0])
-        _check(lib().grx_pr_init(self._h, self.nodes, self.edges, _p(ro), _p(ci)), "PRProblem::Init")
-        return self
-
-    def init_device(self, nodes, edges, d_row_offsets, d_col_indices):
-        self.nodes, self.edges = int(nodes), int(edges)
-        _check(lib().grx_pr_init_device(self._h, self.nodes, self.edges, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices)),
-               "PRProblem::Init (device)")
-        return self
 
     def set_inverse_graph(self, d_inv_row_offsets=None, d_inv_col_indices=None, build=False):
         """No arguments: the graph is symmetric (its CSR is its own inverse); build=True: transpose on the device."""
@@ -3278,22 +2676,11 @@ class PrProblem(_Handle):
     def enact(self, max_iter=20, max_grid_size=0):
         return self._timed(lib().grx_pr_enact, "PREnactor::Enact", int(max_iter), int(max_grid_size))
 
-    def stats(self):
-        it, pr, sv = C.c_longlong(), C.c_longlong(), C.c_longlong()
-        _check(lib().grx_pr_stats(self._h, C.byref(it), C.byref(pr), C.byref(sv)), "grx_pr_stats")
-        return {"iterations": int(it.value), "peeling_rounds": int(pr.value), "surviving_nodes": int(sv.value)}
-
     def extract(self, count=-1):
         k = self.nodes if count < 0 else min(count, self.nodes)
-        ranks = np.empty(max(k, 1), dtype=np.float32)
-        ids = np.empty(max(k, 1), dtype=np.int32)
-        _check(lib().grx_pr_extract(self._h, ranks.ctypes.data_as(C.POINTER(C.c_float)), _p(ids), k), "PRProblem::Extract")
+        ranks, ids = _out(k, np.float32), _out(k)
+        _check(lib().grx_pr_extract(self._h, _f32p(ranks), _p(ids), k), "PRProblem::Extract")
         return ids[:k], ranks[:k]
-
-    def device_results(self):
-        r, i = C.c_void_p(), C.c_void_p()
-        _check(lib().grx_pr_device_results(self._h, C.byref(r), C.byref(i)), "grx_pr_device_results")
-        return r.value, i.value
 
 
 BC_OVERFLOW = -6  # enum GRX_BC_OVERFLOW (gunrock_mi355x.h)
@@ -3305,7 +2692,8 @@ class BcOverflow(ArithmeticError):
 
 
 class BcProblem(_Handle):
-    """BCProblem + BCEnactor behind the handle ABI (grx_bc_*)."""
+    """BCProblem + BCEnactor behind the handle ABI (grx_bc_*): Init, one run() in place of Reset + Enact, Extract, with untyped
+    array arguments -- none of the phases _Problem carries, so the class is written out."""
 
     _destroy = "grx_bc_destroy"
 
@@ -3324,7 +2712,7 @@ class BcProblem(_Handle):
     def init_device(self, nodes, edges, d_row_offsets, d_col_indices):
         self.nodes, self.edges = int(nodes), int(edges)
         _check(lib().grx_bc_init_device(self._h, self.nodes, self.edges, C.c_void_p(d_row_offsets), C.c_void_p(d_col_indices)),
-               "BCProblem::Init (device)")
+               "BCProblem::Init(device)")
         return self
 
     def run(self, src=-1, max_grid_size=0, queue_sizing=1.0):
@@ -3338,8 +2726,7 @@ class BcProblem(_Handle):
         return float(ms.value)
 
     def extract(self):
-        sig = np.empty(max(self.nodes, 1), dtype=np.float32)
-        bc = np.empty(max(self.nodes, 1), dtype=np.float32)
+        sig, bc = _out(self.nodes, np.float32), _out(self.nodes, np.float32)
         _check(lib().grx_bc_extract(self._h, sig.ctypes.data_as(C.c_void_p), bc.ctypes.data_as(C.c_void_p), None), "BCProblem::Extract")
         return sig[:self.nodes], bc[:self.nodes]
 
@@ -3485,7 +2872,8 @@ def advance_reduce(row_offsets, col_indices, vertices, values, r_type="vertex", 
 
 
 class SsspProblem(_Handle):
-    """SSSPProblem + SSSPEnactor behind the handle C ABI."""
+    """SSSPProblem + SSSPEnactor behind the handle C ABI.  Every phase has arguments of its own (uint32 weights, delta, the source)
+    and the family has no device_results, so the class is written out on _Handle."""
 
     _destroy = "grx_sssp_destroy"
 
@@ -3498,7 +2886,7 @@ class SsspProblem(_Handle):
         ro, ci = _csr_arrays(row_offsets, col_indices)
         w = np.ascontiguousarray(weights, dtype=np.uint32)
         self.nodes = int(nodes)
-        _check(lib().grx_sssp_init(self._h, nodes, ci.shape[0], _p(ro), _p(ci), w.ctypes.data_as(C.POINTER(C.c_uint32)),
+        _check(lib().grx_sssp_init(self._h, nodes, ci.shape[0], _p(ro), _p(ci), _u32p(w),
                                    delta_factor), "SSSPProblem::Init")
         return self
 
@@ -3534,11 +2922,9 @@ class SsspProblem(_Handle):
                 "kernel_launches": l.value, "kernel_ms": k.value, "delta": d.value}
 
     def extract(self):
-        dist = np.empty(max(self.nodes, 1), dtype=np.uint32)
-        preds = np.empty(max(self.nodes, 1), dtype=np.int32) if self.mark_pred else None
-        _check(lib().grx_sssp_extract(self._h, dist.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                      None if preds is None else _p(preds)), "SSSPProblem::Extract")
-        return dist[:self.nodes], (None if preds is None else preds[:self.nodes])
+        dist, preds = _out(self.nodes, np.uint32), _out(self.nodes, wanted=self.mark_pred)
+        _check(lib().grx_sssp_extract(self._h, _u32p(dist), _opt(preds)), "SSSPProblem::Extract")
+        return dist[:self.nodes], _cut(preds, self.nodes)
 
 
 def gunrock_sssp(nodes, row_offsets, col_indices, weights, src=0, mark_pred=True, delta_factor=16, queue_size=1.0,
@@ -3551,7 +2937,7 @@ def gunrock_sssp(nodes, row_offsets, col_indices, weights, src=0, mark_pred=True
     cfg = GunrockConfig()
     cfg.mark_pred, cfg.src_node, cfg.device = mark_pred, src, device
     cfg.delta_factor, cfg.queue_size, cfg.src_mode = delta_factor, queue_size, src_mode
-    preds = np.empty(max(nodes, 1), dtype=np.int32)
+    preds = _out(nodes)
     dt = GunrockDataType(VTXID_INT, SIZET_INT, VALUE_UINT)
     lib().gunrock_sssp_func(C.byref(gout), preds.ctypes.data_as(C.c_void_p), C.byref(gin), cfg, dt)
     return _take_node_values(gout, nodes, np.uint32), preds[:nodes]
