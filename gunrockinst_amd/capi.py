@@ -341,6 +341,20 @@ _SIGNATURES = {
     "grx_spgemm_extract": (C.c_int, [C.c_void_p, i32p, i32p, C.POINTER(C.c_longlong)]),
     "grx_spgemm_device_results": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 3),
     "grx_spgemm_destroy": (None, [C.c_void_p]),
+    "grx_bipartite_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int]),
+    "grx_bipartite_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, i32p, i32p]),
+    "grx_bipartite_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "grx_bipartite_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
+    "grx_bipartite_reset": (C.c_int, [C.c_void_p, i32p]),
+    "grx_bipartite_enact": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
+    "grx_bipartite_stats": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_longlong)] * 12 + [C.POINTER(C.c_double)] * 2),
+    "grx_bipartite_phase_trace": (C.c_int, [C.c_void_p, C.c_int, i32p, C.POINTER(C.c_longlong), C.POINTER(C.c_double)]),
+    "grx_bipartite_extract_matching": (C.c_int, [C.c_void_p, i32p, i32p, C.POINTER(C.c_longlong)]),
+    "grx_bipartite_extract_parts": (C.c_int, [C.c_void_p, i32p, i32p, C.POINTER(C.c_longlong)]),
+    "grx_bipartite_extract_cover": (C.c_int, [C.c_void_p, C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte)]),
+    "grx_bipartite_square_graph": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)] + [C.POINTER(C.c_void_p)] * 3),
+    "grx_bipartite_device_results": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 6),
+    "grx_bipartite_destroy": (None, [C.c_void_p]),
     "grx_lp_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int]),
     "grx_lp_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p, i32p]),
     "grx_lp_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),

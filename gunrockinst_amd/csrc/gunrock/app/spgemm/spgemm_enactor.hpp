@@ -130,8 +130,8 @@ class SpgemmEnactor : public EnactorBase {
         GR_CHECK(hipMemsetAsync(problem->counts.p, 0, sizeof(unsigned) * (n + 1), stream), "SpgemmEnactor memset failed");
 
         Ctx c;
-        c.a = problem->a.View();
-        c.b = right->View();
+        c.a = View(problem->a);
+        c.b = View(*right);
         c.babs = nullptr;
         c.words = problem->d_words;
         c.work = problem->work.p;

@@ -27,6 +27,7 @@
 #include <climits>
 
 #include <gunrock/app/table_ladder.hpp>
+#include <gunrock/graphio/rect_csr.hpp>
 #include <gunrock/oprtr/lds_table.hpp>
 #include <gunrock/util/device_intrinsics.hpp>
 
@@ -61,7 +62,7 @@ enum {
     W_SUM,          // the sum of w_i
     W_MAX,          // the largest w_i
     W_BOUND,        // the largest bound of a row, saturating
-    W_BAD,          // ValidateKernel: not a CSR
+    W_BAD,          // graphio::ValidateRectKernel: not a CSR
     W_LISTS,        // four words: the rows listed for LANE, WAVE, BLOCK, GLOBAL
     W_PRODUCTS = W_LISTS + 4,  // four words: their products
     W_COUNT = 16
@@ -134,33 +135,6 @@ __host__ __device__ __forceinline__ bool Fits(long long nnz, long long max_row_p
 }
 
 // ---------------- validation and the build ----------------
-
-// words[W_BAD] = 1 unless ro / ci are a CSR of `rows` rows, `nnz` entries and columns in [0, cols)
-static __global__ void ValidateKernel(const int *ro, const int *ci, long long rows, long long nnz, int cols, unsigned long long *words)
-{
-    const long long stride = static_cast<long long>(gridDim.x) * blockDim.x;
-    const long long count = rows + 1 > nnz ? rows + 1 : nnz;
-    bool bad = false;
-    for (long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; i < count; i += stride) {
-        if (i <= rows) {
-            const long long at = ro[i];
-            bad |= at < 0 || at > nnz || (i == 0 && at != 0) || (i == rows && at != nnz);
-            if (i < rows) bad |= at > ro[i + 1];
-        }
-        if (i < nnz) {
-            const int j = ci[i];
-            bad |= j < 0 || j >= cols;
-        }
-    }
-    if (__ballot(bad) && util::LaneId() == 0) words[W_BAD] = 1ull;
-}
-
-// offsets of `rows` rows as offsets of `padded` >= rows rows, the added ones empty
-static __global__ void PadOffsetsKernel(const int *ro, long long rows, long long padded, int nnz, int *out)
-{
-    const long long stride = static_cast<long long>(gridDim.x) * blockDim.x;
-    for (long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; i <= padded; i += stride) out[i] = i <= rows ? ro[i] : nnz;
-}
 
 // babs[k] = the sum of |b| over row k (below 2^62: at most 2^31 entries of at most 2^31)
 static __global__ void RowAbsKernel(Mat b, long long *babs)

@@ -24,43 +24,8 @@ namespace app {
 namespace spgemm {
 
 // a CSR in device memory: the problem's own (freed with it) or the caller's
-struct DeviceMat {
-    DeviceArray<int> own_ro, own_ci, own_val;          // the problem's own arrays, when it made them
-    int *ro = nullptr, *ci = nullptr, *val = nullptr;  // what the kernels read: those, or the caller's
-    int rows = 0, cols = 0, nnz = 0;
-    bool set = false;
-
-    void Free() { *this = DeviceMat(); }
-    // arrays of its own: `offsets` row offsets, nnz_ columns and, with_val, as many values
-    hipError_t Own(int rows_, int cols_, int nnz_, size_t offsets, bool with_val)
-    {
-        hipError_t retval = hipSuccess;
-        Free();
-        rows = rows_, cols = cols_, nnz = nnz_;
-        if ((retval = own_ro.Alloc(offsets))) return retval;
-        if ((retval = own_ci.Alloc(static_cast<size_t>(nnz)))) return retval;
-        if (with_val && (retval = own_val.Alloc(static_cast<size_t>(nnz)))) return retval;
-        ro = own_ro, ci = own_ci, val = own_val;
-        return retval;
-    }
-    hipError_t Upload(int rows_, int cols_, int nnz_, const int *h_ro, const int *h_ci, const int *h_val)
-    {
-        hipError_t retval = hipSuccess;
-        const size_t n1 = static_cast<size_t>(rows_) + 1, m = static_cast<size_t>(nnz_);
-        if ((retval = Own(rows_, cols_, nnz_, n1, h_val != nullptr))) return retval;
-        GR_CHECK(hipMemcpy(ro, h_ro, sizeof(int) * n1, hipMemcpyHostToDevice), "SpgemmProblem hipMemcpy failed");
-        if (m) GR_CHECK(hipMemcpy(ci, h_ci, sizeof(int) * m, hipMemcpyHostToDevice), "SpgemmProblem hipMemcpy failed");
-        if (h_val && m) GR_CHECK(hipMemcpy(val, h_val, sizeof(int) * m, hipMemcpyHostToDevice), "SpgemmProblem hipMemcpy failed");
-        return retval;
-    }
-    void Borrow(int rows_, int cols_, int nnz_, int *d_ro, int *d_ci, int *d_val)
-    {
-        Free();
-        rows = rows_, cols = cols_, nnz = nnz_;
-        ro = d_ro, ci = d_ci, val = d_val;
-    }
-    Mat View() const { return Mat{ro, ci, val, rows, cols}; }
-};
+using DeviceMat = graphio::RectCsr;
+inline Mat View(const DeviceMat &m) { return Mat{m.ro, m.ci, m.val, m.rows, m.cols}; }
 
 struct SpgemmProblem {
     DeviceMat a, given, transposed;
@@ -92,8 +57,8 @@ struct SpgemmProblem {
         unsigned long long word = 0;
         GR_CHECK(hipMemsetAsync(d_words + W_BAD, 0, sizeof(unsigned long long), stream), "SpgemmProblem memset failed");
         const long long count = m.rows + 1ll > m.nnz ? m.rows + 1ll : m.nnz;
-        hipLaunchKernelGGL(ValidateKernel, dim3(CappedGrid((count + 255) / 256, 2048, 0)), dim3(256), 0, stream, m.ro, m.ci,
-                           static_cast<long long>(m.rows), static_cast<long long>(m.nnz), m.cols, d_words);
+        hipLaunchKernelGGL(graphio::ValidateRectKernel, dim3(CappedGrid((count + 255) / 256, 2048, 0)), dim3(256), 0, stream, m.ro, m.ci,
+                           static_cast<long long>(m.rows), static_cast<long long>(m.nnz), m.cols, d_words + W_BAD);
         GR_CHECK(hipGetLastError(), "ValidateKernel launch failed");
         GR_CHECK(hipMemcpyAsync(&word, d_words + W_BAD, sizeof(word), hipMemcpyDeviceToHost, stream), "SpgemmProblem read-back failed");
         GR_CHECK(hipStreamSynchronize(stream), "SpgemmProblem sync failed");
@@ -161,7 +126,7 @@ struct SpgemmProblem {
         const int *ro = a.ro;
         if (n > a.rows) {
             if ((retval = padded.Alloc(n1))) return retval;
-            hipLaunchKernelGGL(PadOffsetsKernel, dim3(CappedGrid((n + 256) / 256, 2048, 0)), dim3(256), 0, stream, a.ro, static_cast<long long>(a.rows),
+            hipLaunchKernelGGL(graphio::PadOffsetsKernel, dim3(CappedGrid((n + 256) / 256, 2048, 0)), dim3(256), 0, stream, a.ro, static_cast<long long>(a.rows),
                                static_cast<long long>(n), a.nnz, padded.p);
             GR_CHECK(hipGetLastError(), "PadOffsetsKernel launch failed");
             ro = padded.p;

@@ -1494,6 +1494,80 @@ int grx_wl_device_results(grx_wl *p, int **d_colour, long long **d_class_size, i
 void grx_wl_destroy(grx_wl *p);
 
 /* ------------------------------------------------------------------------------------------------
+ * BIPARTITE: BipartiteProblem + BipartiteEnactor: a maximum matching of the bipartite graph rows -- columns of a CSR pattern of
+ * shape (rows, cols), and its Dulmage-Mendelsohn decomposition (no counterpart in the reference snapshot).  The pattern is read as
+ * given: values there are none, duplicates and unsorted rows mean nothing, empty rows and columns and a dimension of 0 are
+ * allowed.  The size of the matching (the structural rank), the horizontal / square / vertical part of every row and column and
+ * König's minimum vertex cover have one value whatever the schedule; the matching itself has not, and is validated: a device pass
+ * over the entries certifies it and the parts before anything is reported as maximum.  An Enact ends GRX_BIPARTITE_MAXIMUM or,
+ * behind "max_phases" phases that all augmented, GRX_BIPARTITE_CAPPED (a valid matching not known to be maximum); neither is an
+ * error.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct grx_bipartite grx_bipartite;
+enum { GRX_BIPARTITE_AUTO = 0, GRX_BIPARTITE_LANE = 1, GRX_BIPARTITE_WAVE = 2, GRX_BIPARTITE_BLOCK = 3 };  /* option "strategy" */
+enum { GRX_BIPARTITE_HORIZONTAL = 0, GRX_BIPARTITE_SQUARE = 1, GRX_BIPARTITE_VERTICAL = 2 };               /* row_part / col_part */
+enum { GRX_BIPARTITE_MAXIMUM = 0, GRX_BIPARTITE_CAPPED = 1 };                                              /* `state` of the stats */
+/* next to -1 / -2 / -3: the certificate failed (no result); reset was given no matching; the call needs a maximum matching and
+ * the last Enact ended GRX_BIPARTITE_CAPPED */
+enum { GRX_BIPARTITE_NOT_CERTIFIED = -4, GRX_BIPARTITE_BAD_MATCHING = -5, GRX_BIPARTITE_NOT_MAXIMUM = -6 };
+
+int grx_bipartite_create(grx_bipartite **out, int instrument, int device);
+/* BipartiteProblem::Init: validates the CSR on the device and builds its transpose, once.  -1: a negative size or a NULL array
+ * (col_indices may be NULL without entries); -2: not a CSR of that shape; -3: the handle has been given a matrix before */
+int grx_bipartite_init(grx_bipartite *p, int rows, int cols, int entries, const int *row_offsets, const int *col_indices);
+/* the same for a CSR already in HBM: borrowed, not freed, read by every Enact (it has to outlive the handle) */
+int grx_bipartite_init_device(grx_bipartite *p, int rows, int cols, int entries, int *d_row_offsets, int *d_col_indices);
+/* named options, for the next Enact; 0: set, 1: unknown name, -1: a value out of range.  None changes a pinned result.
+ *   "greedy"        1 (default): every unmatched row first claims its first free column; 0: the phases start from the matching
+ *                   of the last reset exactly
+ *   "max_phases"    0 (default): none; h > 0: at most h phases
+ *   "strategy"      how a frontier column's entries are walked: GRX_BIPARTITE_AUTO (default): fewer than "wave_min_row" (16)
+ *                   entries by one lane, fewer than "block_min_row" (2048) by a wave, the others by a workgroup;
+ *                   GRX_BIPARTITE_LANE / _WAVE / _BLOCK force one
+ *   "schedule"      0 (default): a level runs in the one-workgroup device loop when its frontier has at most "loop_max_list"
+ *                   (32768) vertices with at most "loop_max_entries" (8192) entries, else as one launch; 1: every level is a
+ *                   launch; 2: every level runs in the device loop */
+int grx_bipartite_set_option(grx_bipartite *p, const char *name, double value);
+/* BipartiteProblem::Reset: the matching the next Enact starts from: mate_row[r] = a column or -1, `rows` int32 on the host, or
+ * NULL for the empty one.  Checked on the device: GRX_BIPARTITE_BAD_MATCHING when a mate is out of range, a pair is no entry or a
+ * column is used twice (the start is then the empty matching) */
+int grx_bipartite_reset(grx_bipartite *p, const int *mate_row /* or NULL */);
+/* BipartiteEnactor::Enact(problem, max_grid_size), HIP-event timed.  0 in both end states; GRX_BIPARTITE_NOT_CERTIFIED: there is
+ * no result */
+int grx_bipartite_enact(grx_bipartite *p, int max_grid_size, float *elapsed_ms);
+/* Of the last Enact; any pointer may be NULL.  *size: the pairs; *phases: the searches from the unmatched columns, the last one
+ * (which found no end) included; *levels: their levels; *vertical_levels: the levels of the search from the unmatched rows;
+ * certificate[3]: mates that are not mutual or no entry (0), entries the cover misses plus vertices in two parts (0), the size
+ * of the cover (*size, when the state is GRX_BIPARTITE_MAXIMUM); regime_columns[3]: frontier vertices walked by a lane, a wave,
+ * a workgroup; *loop_levels: levels that ran in the device loop; kernel_ms[6]: when instrumented, the summed kernel time, then
+ * that of the root, level, device-loop and augmenting kernels and of the rest; *build_ms: the transpose */
+int grx_bipartite_stats(grx_bipartite *p, long long *size, long long *phases, long long *levels, long long *vertical_levels,
+                        long long *augmentations, long long *greedy_pairs, long long *state, long long *certificate,
+                        long long *regime_columns, long long *loop_levels, long long *kernel_launches, long long *readbacks,
+                        double *kernel_ms, double *build_ms);
+/* One row per phase of the last Enact and a last one for the search from the unmatched rows: its levels, the paths it flipped,
+ * host milliseconds.  Copies the first min(count, max_phases) rows into the arrays that are not NULL and returns the count */
+int grx_bipartite_phase_trace(grx_bipartite *p, int max_phases, int *levels, long long *augmentations, double *ms);
+/* The matching of the last Enact (either end state): `rows` and `cols` int32, -1 for unmatched; any may be NULL.  Before a
+ * finished Enact: hipErrorNotReady */
+int grx_bipartite_extract_matching(grx_bipartite *p, int *h_mate_row, int *h_mate_col, long long *size);
+/* The coarse decomposition: GRX_BIPARTITE_HORIZONTAL / _SQUARE / _VERTICAL per row and per column; part_sizes[6]: rows then
+ * columns in the three parts.  GRX_BIPARTITE_NOT_MAXIMUM behind a capped Enact */
+int grx_bipartite_extract_parts(grx_bipartite *p, int *h_row_part, int *h_col_part, long long *part_sizes);
+/* König's minimum vertex cover, 1 = in the cover: the rows outside the vertical part and the columns inside it */
+int grx_bipartite_extract_cover(grx_bipartite *p, unsigned char *h_row_cover, unsigned char *h_col_cover);
+/* The square part with every matched pair contracted, built on the device once per result and kept with the handle: *k vertices
+ * (the square rows in ascending order), one arc local(r) -> local(mate_col[c]) per entry (r, c) with both ends in the square part;
+ * d_row_offsets: k + 1 int32, d_col_indices: *arcs int32, d_rows: the row of every vertex (NULL when there is none).  Its
+ * strongly connected components are the blocks of the fine decomposition.  GRX_BIPARTITE_NOT_MAXIMUM behind a capped Enact */
+int grx_bipartite_square_graph(grx_bipartite *p, int *k, int *arcs, int **d_row_offsets, int **d_col_indices, int **d_rows);
+/* device arrays of the handle, NULL without a finished Enact (the last four also behind a capped one): mate_row, mate_col,
+ * row_part, col_part (int32), row_cover, col_cover (uint8) */
+int grx_bipartite_device_results(grx_bipartite *p, int **d_mate_row, int **d_mate_col, int **d_row_part, int **d_col_part,
+                                 unsigned char **d_row_cover, unsigned char **d_col_cover);
+void grx_bipartite_destroy(grx_bipartite *p);
+
+/* ------------------------------------------------------------------------------------------------
  * SSSP: SSSPProblem + SSSPEnactor (reference gunrock/app/sssp/sssp_problem.cuh:35-387, sssp_enactor.cuh:36-563)
  * ---------------------------------------------------------------------------------------------- */
 typedef struct grx_sssp grx_sssp;
