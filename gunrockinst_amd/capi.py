@@ -355,6 +355,18 @@ _SIGNATURES = {
     "grx_bipartite_square_graph": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)] + [C.POINTER(C.c_void_p)] * 3),
     "grx_bipartite_device_results": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 6),
     "grx_bipartite_destroy": (None, [C.c_void_p]),
+    "grx_sm_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int]),
+    "grx_sm_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p, i32p]),
+    "grx_sm_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "grx_sm_set_pattern": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p, i32p, C.c_int]),
+    "grx_sm_pattern_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), i32p, C.POINTER(C.c_int), i32p, i32p]),
+    "grx_sm_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
+    "grx_sm_reset": (C.c_int, [C.c_void_p]),
+    "grx_sm_enact": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
+    "grx_sm_stats": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_longlong)] * 9 + [C.POINTER(C.c_double)] * 7),
+    "grx_sm_extract": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "grx_sm_device_results": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "grx_sm_destroy": (None, [C.c_void_p]),
     "grx_lp_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int]),
     "grx_lp_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, i32p, i32p, i32p]),
     "grx_lp_init_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),

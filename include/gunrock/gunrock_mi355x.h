@@ -1568,6 +1568,66 @@ int grx_bipartite_device_results(grx_bipartite *p, int **d_mate_row, int **d_mat
 void grx_bipartite_destroy(grx_bipartite *p);
 
 /* ------------------------------------------------------------------------------------------------
+ * SM: SmProblem + SmEnactor: the occurrences of a small labelled pattern H in a graph G (subgraph matching; the reference
+ * snapshot's app/sm is a stub).  G is the CSR read as the simple undirected graph, as TC and the clique family read it, with an
+ * optional int32 label per vertex (NULL: all 0).  H has q vertices, 2 <= q <= GRX_SM_MAX_Q, is simple and connected, and has an
+ * optional int32 label per vertex, -1 a wildcard that matches any label.  An embedding is an injective map f: V(H) -> V(G) that
+ * respects the labels and maps every pattern edge onto an edge and, when `induced`, every pattern non-edge onto a non-edge.
+ * Aut(H) are the label-preserving automorphisms of H (the wildcard a label of its own), aut their number (<= 720).  The results:
+ * occurrences = embeddings / aut; count[v] = the occurrences whose image contains v (sum = q * occurrences).  All are integers
+ * with one value whatever the options; for H = K_k they are the clique family's cliques[] and total.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct grx_sm grx_sm;
+enum { GRX_SM_AUTO = 0, GRX_SM_GROUP8 = 1, GRX_SM_WAVE = 2 };  /* option "strategy" */
+enum { GRX_SM_MAX_Q = 6, GRX_SM_MAX_CONSTRAINTS = 15 };
+/* grx_sm_enact, next to -1 / -2 / -3: the work bound exceeds "work_limit" (nothing ran); a count was no multiple of aut under
+ * "symmetry" 0.  After either there is no result */
+enum { GRX_SM_TOO_LARGE = -4, GRX_SM_NOT_CERTIFIED = -5 };
+
+int grx_sm_create(grx_sm **out, int instrument, int device);
+/* SmProblem::Init: validates the CSR on the device, builds the neighbour CSR and copies the labels, once.  nodes and edges may be
+ * 0.  -1: a negative size or a NULL array (col_indices may be NULL without entries); -2: not a CSR of `nodes` vertices; -3: the
+ * handle has been given a graph before */
+int grx_sm_init(grx_sm *p, int nodes, int edges, const int *row_offsets, const int *col_indices, const int *labels /* or NULL */);
+/* the same for a CSR and labels already in HBM: borrowed, not freed; the labels are read by every Enact */
+int grx_sm_init_device(grx_sm *p, int nodes, int edges, int *d_row_offsets, int *d_col_indices, const int *d_labels /* or NULL */);
+/* The pattern of the next Enact: num_pairs pairs (a[i], b[i]); duplicates and both orientations of a pair are one edge.  -1, and
+ * the pattern in force stays: q outside 2 .. GRX_SM_MAX_Q, an endpoint outside [0, q), a self-loop, a disconnected pattern, a
+ * pattern label below -1.  May be called before init */
+int grx_sm_set_pattern(grx_sm *p, int q, int num_pairs, const int *a, const int *b, const int *pattern_labels /* or NULL */, int induced);
+/* Of the pattern in force, under the options in force (hipErrorNotReady without one); any pointer may be NULL.  order[]:
+ * GRX_SM_MAX_Q entries, the matching order, -1 behind the q-th; the symmetry-breaking constraints f(lower[i]) < f(higher[i]),
+ * GRX_SM_MAX_CONSTRAINTS entries each, -1 behind the *num_constraints-th */
+int grx_sm_pattern_info(grx_sm *p, int *q, int *aut, int *order, int *num_constraints, int *lower, int *higher);
+/* named options, for the next Enact; 0: set, 1: unknown name, -1: a value out of range.  None changes a result.
+ *   "symmetry"      1 (default): the constraints of Grochow and Kellis let every occurrence be found once; 0: none, every
+ *                   occurrence is found aut times and the counts are divided on the device (a remainder: GRX_SM_NOT_CERTIFIED)
+ *   "per_vertex"    1 (default); 0: count[] is not written (it stays 0), only the totals
+ *   "strategy"      GRX_SM_AUTO (default): an item whose two end rows have at most "group_max_row" (16) entries is searched by
+ *                   8 lanes, the others by a wave; GRX_SM_GROUP8 / GRX_SM_WAVE force one
+ *   "work_limit"    default 2^38, at most 2^62: Enact refuses when (q - 1) * hom(T, G) exceeds it
+ *   "order"         the matching order: 0 (default) the rule; 1 the reverse-key rule; 2 ascending id where that is a connected
+ *                   order, else 0.  For tests */
+int grx_sm_set_option(grx_sm *p, const char *name, double value);
+/* SmProblem::Reset: count[] and the totals to zero (an Enact on written counts does it itself) */
+int grx_sm_reset(grx_sm *p);
+/* SmEnactor::Enact(problem, max_grid_size), HIP-event timed.  hipErrorNotReady without a graph or a pattern;
+ * GRX_SM_TOO_LARGE; GRX_SM_NOT_CERTIFIED */
+int grx_sm_enact(grx_sm *p, int max_grid_size, float *elapsed_ms);
+/* Of the last Enact; any pointer may be NULL.  *items: the CSR entries that passed levels 0 and 1; regime_items[2]: those searched
+ * by 8 lanes, by a wave; *candidates: row entries streamed below them; *bisections: adjacency tests; *pairs: the edges of G;
+ * *bound: hom(T, G) of the anchor tree in float64; when instrumented, *kernel_ms and its split over the bin, the two enumeration
+ * launches and the division; *build_ms: the neighbour CSR */
+int grx_sm_stats(grx_sm *p, long long *items, long long *regime_items, long long *candidates, long long *bisections, long long *occurrences,
+                 long long *embeddings, long long *pairs, long long *longest_row, long long *kernel_launches, double *bound, double *kernel_ms,
+                 double *bin_ms, double *group8_ms, double *wave_ms, double *finish_ms, double *build_ms);
+/* h_count: `nodes` int64, or NULL.  Before a finished Enact, or behind a refused one: hipErrorNotReady */
+int grx_sm_extract(grx_sm *p, long long *h_count /* or NULL */, long long *occurrences, long long *embeddings);
+/* device arrays of the handle: count (`nodes` int64) and the degrees of G (`nodes` int32) */
+int grx_sm_device_results(grx_sm *p, long long **d_count, int **d_degrees);
+void grx_sm_destroy(grx_sm *p);
+
+/* ------------------------------------------------------------------------------------------------
  * SSSP: SSSPProblem + SSSPEnactor (reference gunrock/app/sssp/sssp_problem.cuh:35-387, sssp_enactor.cuh:36-563)
  * ---------------------------------------------------------------------------------------------- */
 typedef struct grx_sssp grx_sssp;
