@@ -403,6 +403,13 @@ _SIGNATURES = {
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.c_int]),
     "grx_advance_reduce": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 7 + [C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_int]),
+    "grx_device_scan": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.POINTER(C.c_ulonglong)]),
+    "grx_device_key_sort": (C.c_int, [C.c_int, C.POINTER(C.c_longlong), i32p, C.c_void_p, C.c_void_p]),
+    "grx_device_transpose": (C.c_int, [C.c_int, C.c_longlong] + [C.c_void_p] * 6),
+    "grx_wave_ops": (C.c_int, [C.c_int] * 4 + [C.c_longlong] + [C.c_void_p] * 4),
+    "grx_bisect_queue": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                   C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                   C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.c_int]),
     "grx_sssp_reset": (C.c_int, [C.c_void_p, C.c_int, C.c_double]),
     "grx_sssp_enact": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]),
     "grx_sssp_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
@@ -2895,6 +2902,148 @@ def advance_reduce(row_offsets, col_indices, vertices, values, r_type="vertex", 
         res["edge_hits"] = d_hits[:ci.size].cpu().numpy()
         res["edge_src"] = d_src[:ci.size].cpu().numpy()
     return res
+
+
+SCAN_OUT_TYPES = {"int32": 0, "uint32": 1, "uint64": 2}
+WAVE_OPS = {"inclusive_sum": 0, "inclusive_sum_dpp": 1, "inclusive_max_dpp": 2, "segmented_scan_dpp": 3, "wave_sum": 4,
+            "rank_in_mask": 5, "block_scan": 6, "dpp_move": 7}
+DPP_MOVE_IDENTITY = 0xA5A5A5A55A5A5A5A
+_CARRIER = {1: "uint8", 4: "int32", 8: "int64"}
+
+
+def _dev(torch, a, dtype=None):
+    """a device copy of a numpy array of any 1-, 4- or 8-byte type (bit patterns travel as signed words); never of size 0"""
+    a = np.array(a, dtype=dtype, order="C").reshape(-1)
+    carrier = np.dtype(_CARRIER[a.dtype.itemsize])
+    return torch.from_numpy(a.view(carrier)).cuda() if a.size else torch.zeros(1, dtype=getattr(torch, carrier.name), device="cuda")
+
+
+def _host(t, dtype, n):
+    return t.cpu().numpy().view(dtype)[:n]
+
+
+def device_scan(values, out_type="uint64"):
+    """graphio::DeviceExclusiveScan<out_type> of uint32 `values` (grx_device_scan), on the GPU: (prefix as out_type, 64-bit total)"""
+    import torch
+    values = np.ascontiguousarray(values, dtype=np.uint32)
+    n = int(values.size)
+    out_dtype = np.dtype(out_type)
+    d_in = _dev(torch, values)
+    d_out = torch.zeros(max(n, 1), dtype=torch.int64 if out_dtype.itemsize == 8 else torch.int32, device="cuda")
+    total = C.c_ulonglong()
+    torch.cuda.synchronize()
+    _check(lib().grx_device_scan(_ptr(d_in), n, SCAN_OUT_TYPES[out_dtype.name], _ptr(d_out), C.byref(total)), "DeviceExclusiveScan")
+    return _host(d_out, out_dtype, n), int(total.value)
+
+
+def device_key_sort(key_arrays, key_bits):
+    """ONE graphio::DeviceKeySort sorts the uint64 arrays of `key_arrays` one after the other, array a on its low key_bits[a]
+    bits (grx_device_key_sort), on the GPU.  Returns the list of sorted arrays."""
+    import torch
+    arrays = [np.ascontiguousarray(k, dtype=np.uint64).reshape(-1) for k in key_arrays]
+    bits = np.ascontiguousarray(key_bits, dtype=np.int32).reshape(-1)
+    if bits.size != len(arrays):
+        raise ValueError("device_key_sort: one key_bits per array")
+    counts = np.array([a.size for a in arrays], dtype=np.int64)
+    total = int(counts.sum())
+    d_in = _dev(torch, np.concatenate(arrays) if arrays else np.zeros(0, dtype=np.uint64))
+    d_out = torch.zeros(max(total, 1), dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    _check(lib().grx_device_key_sort(len(arrays), _i64p(counts), _p(bits), _ptr(d_in), _ptr(d_out)), "DeviceKeySort")
+    out = _host(d_out, np.uint64, total)
+    ends = np.cumsum(counts)
+    return [out[int(e - c):int(e)] for c, e in zip(counts, ends)]
+
+
+def device_transpose(row_offsets, col_indices, values=None):
+    """graphio::DeviceTransposeCsr (grx_device_transpose), on the GPU: (inv_row_offsets, inv_col_indices[, inv_values]);
+    `values` = one uint32 per edge that travels with it."""
+    import torch
+    ro, ci = _csr_arrays(row_offsets, col_indices)
+    nodes, edges = int(ro.size - 1), int(ci.size)
+    d_ro, d_ci = _dev_i32(torch, ro), _dev_i32(torch, ci)
+    d_vals = d_ivals = None
+    if values is not None:
+        values = np.ascontiguousarray(values, dtype=np.uint32)
+        if values.size != edges:
+            raise ValueError("device_transpose: one value per edge")
+        d_vals = _dev(torch, values)
+        d_ivals = torch.full((max(edges, 1),), -7, dtype=torch.int32, device="cuda")
+    d_iro = torch.full((nodes + 1,), -7, dtype=torch.int32, device="cuda")
+    d_ici = torch.full((max(edges, 1),), -7, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    _check(lib().grx_device_transpose(nodes, edges, _ptr(d_ro), _ptr(d_ci), _ptr(d_vals), _ptr(d_iro), _ptr(d_ici), _ptr(d_ivals)),
+           "DeviceTransposeCsr")
+    res = (d_iro.cpu().numpy(), d_ici.cpu().numpy()[:edges])
+    return res if values is None else res + (_host(d_ivals, np.uint32, edges),)
+
+
+def wave_ops(op, values, threads=256, r_op=None, heads=None, step=0):
+    """One building block of util/device_intrinsics.hpp per element of `values` (grx_wave_ops), on the GPU: element i is lane
+    i % 64 of a workgroup of `threads` threads.  `values`' dtype picks the value type; r_op (a REDUCE_OPS name) and `heads`
+    belong to "segmented_scan_dpp", `step` (0..5) to "dpp_move".  Returns the result array; for "block_scan" the tuple
+    (first result, first total, second result, second total), the second scan over the workgroup's elements in mirrored order.
+    A combination the library does not instantiate raises RuntimeError."""
+    import torch
+    values = np.ascontiguousarray(values).reshape(-1)
+    n = int(values.size)
+    vt = REDUCE_VALUE_TYPES[values.dtype.name]
+    out_dtype = np.dtype(np.uint32) if op == "rank_in_mask" else values.dtype
+    d_in = _dev(torch, values)
+    d_out = _dev(torch, np.zeros(max(n, 1), dtype=out_dtype))
+    d_heads = _dev(torch, np.asarray(heads) != 0, dtype=np.uint8) if heads is not None else None
+    if heads is not None and np.asarray(heads).size != n:
+        raise ValueError("wave_ops: one head flag per value")
+    d_aux = _dev(torch, np.zeros(max(3 * n, 1), dtype=values.dtype)) if op == "block_scan" else None
+    second = REDUCE_OPS[r_op] if op == "segmented_scan_dpp" else int(step)
+    torch.cuda.synchronize()
+    _check(lib().grx_wave_ops(WAVE_OPS[op], second, vt, int(threads), n, _ptr(d_in), _ptr(d_heads), _ptr(d_out), _ptr(d_aux)),
+           "wave block %s" % op)
+    out = _host(d_out, out_dtype, n)
+    if op != "block_scan":
+        return out
+    aux = _host(d_aux, values.dtype, 3 * n)
+    return out, aux[:n], aux[n:2 * n], aux[2 * n:]
+
+
+def bisect_queue(row_offsets, dist, visit_lookup, delta, queue, level, tag, parked=None, count_on_device=None, near_capacity=None,
+                 far_capacity=None, mark_paths=False, guard=64, max_grid_size=0):
+    """priority_queue::Bisect with the SSSP enactor's template arguments over `queue` (grx_bisect_queue), on the GPU.
+    dist: uint32 distance per vertex; visit_lookup: int32 tag per vertex (returned updated); parked: the distance every queue
+    entry was parked with, or None; count_on_device: the element count that goes through the packed device tail (the queue's
+    length is then the loose upper bound), or None to pass the length by value.  Every output array is allocated `guard`
+    entries longer than its capacity and pre-filled with -7.  Returns a dict: `near_len`, `near_edges`, `far_len` (the tails),
+    `far_min`, `overflow`, the whole `near_v` / `near_row_start` / `near_scan` / `far_v` / `far_d` allocations, `visit_lookup`."""
+    import torch
+    ro = np.ascontiguousarray(row_offsets, dtype=np.int32)
+    queue = np.ascontiguousarray(queue, dtype=np.int32).reshape(-1)
+    n = int(queue.size)
+    near_cap = int(near_capacity if near_capacity is not None else max(n, 1))
+    far_cap = int(far_capacity if far_capacity is not None else max(n, 1))
+    dist = np.ascontiguousarray(dist, dtype=np.uint32)
+    d_ro, d_in = _dev_i32(torch, ro), _dev_i32(torch, queue)
+    d_dist = _dev(torch, (dist.astype(np.uint64) << np.uint64(32)) | np.arange(dist.size, dtype=np.uint64)) if mark_paths else _dev(torch, dist)
+    d_lookup = _dev_i32(torch, visit_lookup)
+    d_parked = _dev(torch, parked, dtype=np.uint32) if parked is not None else None
+    if parked is not None and np.asarray(parked).size != n:
+        raise ValueError("bisect_queue: one parked distance per queue entry")
+    d_count = None
+    if count_on_device is not None:
+        if not 0 <= int(count_on_device) <= n:
+            raise ValueError("bisect_queue: the device count exceeds the queue")
+        d_count = _dev(torch, np.array([int(count_on_device) | (12345 << 32)], dtype=np.uint64))   # (the edge half is not the count)
+    near = [torch.full((near_cap + guard,), -7, dtype=torch.int32, device="cuda") for _ in range(3)]
+    far = [torch.full((far_cap + guard,), -7, dtype=torch.int32, device="cuda") for _ in range(2)]
+    near_tail, far_tail, far_min, overflow = C.c_ulonglong(), C.c_ulonglong(), C.c_uint32(), C.c_int()
+    torch.cuda.synchronize()
+    _check(lib().grx_bisect_queue(_ptr(d_ro), _ptr(d_dist), int(bool(mark_paths)), _ptr(d_lookup), float(delta), _ptr(d_in), _ptr(d_parked),
+                                  n, _ptr(d_count), int(level), int(tag), near_cap, _ptr(near[0]), _ptr(near[1]), _ptr(near[2]), far_cap,
+                                  _ptr(far[0]), _ptr(far[1]), C.byref(near_tail), C.byref(far_tail), C.byref(far_min), C.byref(overflow),
+                                  int(max_grid_size)), "priority_queue::Bisect")
+    return {"near_len": int(near_tail.value & 0xFFFFFFFF), "near_edges": int(near_tail.value >> 32), "far_len": int(far_tail.value),
+            "far_min": int(far_min.value), "overflow": int(overflow.value), "near_v": near[0].cpu().numpy(),
+            "near_row_start": near[1].cpu().numpy(), "near_scan": near[2].cpu().numpy(), "far_v": far[0].cpu().numpy(),
+            "far_d": far[1].cpu().numpy().view(np.uint32), "visit_lookup": d_lookup.cpu().numpy()[:np.asarray(visit_lookup).size]}
 
 
 class SsspProblem(_Handle):

@@ -113,9 +113,11 @@ static __global__ __launch_bounds__(kScanThreads) void ScanApplyKernel(const uns
     }
 }
 
-// Exclusive scan of n unsigned values; *d_total (device, 8 bytes) receives the grand total.  d_sums: scratch of
-// (tiles + 1) 64-bit words.  Handles up to 1024 * 2^20 tiles in the single-workgroup middle phase comfortably
-// (2^31 elements = 524288 tiles = 512 rounds of 1024).
+// Exclusive scan of n unsigned values: d_out[i] = d_in[0] + ... + d_in[i - 1], summed in 64 bits and stored as OutT (int,
+// unsigned: exact wherever the prefix fits; unsigned long long: always).  d_sums: scratch of ScanScratchWords(n) 64-bit
+// words (device).  Afterwards d_sums[0 .. tiles) hold the tile offsets and d_sums[tiles], tiles = ceil(n / kScanTile), the
+// 64-bit grand total (n = 0: d_sums[0] = 0); there is no separate total argument.  The single-workgroup middle phase
+// handles 2^31 elements = 524288 tiles in 512 rounds of 1024 comfortably.
 template <typename OutT>
 inline hipError_t DeviceExclusiveScan(const unsigned *d_in, OutT *d_out, long long n, unsigned long long *d_sums,
                                       hipStream_t stream)

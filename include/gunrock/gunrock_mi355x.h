@@ -234,6 +234,55 @@ int grx_advance_reduce(const int *d_row_offsets, const int *d_col_indices, const
                        long long out_len, const void *d_values, void *d_reduced, int functor, const int *d_mask, int *d_edge_hits,
                        int *d_edge_src, int max_grid_size);
 
+/* The device building blocks under the operators, each by itself (lib/blocks_app.hip).  All d_ pointers are device pointers;
+ * every function returns 0, a HIP error code, -1 for an argument that makes no sense or -2 for a combination that is not
+ * instantiated. */
+enum grx_scan_out { GRX_SCAN_INT = 0, GRX_SCAN_UINT = 1, GRX_SCAN_ULONGLONG = 2 };
+/* graphio::DeviceExclusiveScan<out_type>: d_out[i] = d_in[0] + ... + d_in[i - 1], computed in 64 bits and stored as out_type;
+ * *total (host) = the 64-bit grand total, read from the scratch word behind the tile offsets. */
+int grx_device_scan(const unsigned *d_in, long long n, int out_type, void *d_out, unsigned long long *total);
+/* ONE graphio::DeviceKeySort sorts `arrays` key arrays one after the other: array a has counts[a] keys (host array), stored
+ * back to back in d_in, and is sorted on its low key_bits[a] (1..64) bits; the results land back to back in d_out. */
+int grx_device_key_sort(int arrays, const long long *counts, const int *key_bits, const unsigned long long *d_in,
+                        unsigned long long *d_out);
+/* graphio::DeviceTransposeCsr: d_inv_row_offsets[nodes + 1], d_inv_col_indices[edges]; d_vals / d_inv_vals (both or neither):
+ * one 32-bit value per edge that travels with it. */
+int grx_device_transpose(int nodes, long long edges, const int *d_row_offsets, const int *d_col_indices, const unsigned *d_vals,
+                         int *d_inv_row_offsets, int *d_inv_col_indices, unsigned *d_inv_vals);
+enum grx_wave_op {
+    GRX_WAVE_INCLUSIVE_SUM = 0,      /* util::WaveInclusiveSum: int, unsigned, unsigned long long */
+    GRX_WAVE_INCLUSIVE_SUM_DPP = 1,  /* util::WaveInclusiveSumDpp: unsigned */
+    GRX_WAVE_INCLUSIVE_MAX_DPP = 2,  /* util::WaveInclusiveMaxDpp: unsigned */
+    GRX_WAVE_SEGMENTED_SCAN_DPP = 3, /* util::WaveSegmentedScanDpp<ReduceOps<r_op, type>>: the pairs of grx_advance_reduce but float MULTIPLIES */
+    GRX_WAVE_SUM = 4,                /* util::WaveSum: int, unsigned, unsigned long long */
+    GRX_WAVE_RANK_IN_MASK = 5,       /* util::RankInMask: unsigned long long masks in, unsigned ranks out */
+    GRX_WAVE_BLOCK_SCAN = 6,         /* util::BlockScan<threads, type>::ExclusiveSum, twice: int, unsigned long long */
+    GRX_WAVE_DPP_MOVE = 7            /* util::DppMove: unsigned, unsigned long long; r_op = step 0..5 of the scan network */
+};
+/* what a lane without a source shows after GRX_WAVE_DPP_MOVE (its low word for 32-bit values) */
+#define GRX_DPP_MOVE_IDENTITY 0xA5A5A5A55A5A5A5Aull
+/* A grid of workgroups of `threads` (64, 256 or 1024) threads; thread i of the launch, lane i % 64 of its wave, loads d_in[i],
+ * calls the block and stores d_out[i]; threads past n take part with a zero.  r_op: the grx_reduce_op of a segmented scan
+ * (d_heads[i] != 0 opens a segment at element i; NULL: no heads), or the step of a DPP move: 0..3 = row_shr 1, 2, 4, 8,
+ * 4 = row_bcast:15 under row mask 0xA, 5 = row_bcast:31 under row mask 0xC.  BLOCK_SCAN scans the elements of a workgroup, then,
+ * on the same storage, the same elements in mirrored order (thread t takes element threads - 1 - t of its workgroup):
+ * d_out[i] = first result, d_aux[i], d_aux[n + i], d_aux[2n + i] = first total, second result and second total as thread i
+ * received them.  d_aux is unused otherwise. */
+int grx_wave_ops(int op, int r_op, int value_type, int threads, long long n, const void *d_in, const unsigned char *d_heads, void *d_out,
+                 void *d_aux);
+/* priority_queue::Bisect<256, 4, SSSPProblem<int, int, int, mark_paths>, PQFunctor> over the queue d_in (-1 = no entry) with a data
+ * slice filled from the arguments: d_dist = one unsigned distance per vertex, or with mark_paths one packed
+ * (distance << 32 | predecessor) word; d_visit_lookup; delta.  d_in_dist (or NULL): the distance each entry was parked with.
+ * d_num_elements (or NULL): packed device tail whose low word is the element count; num_elements is then the upper bound that
+ * sizes the grid.  Outputs: the near frontier (near_capacity entries of v, row_start, scan), the far pile (far_capacity
+ * entries of vertex and distance), and on the host the packed near tail (count | edges << 32), the far tail, the smallest
+ * far bucket (UINT_MAX when nothing was parked) and the overflow flag.  max_grid_size: 0 = one resident grid. */
+int grx_bisect_queue(const int *d_row_offsets, const void *d_dist, int mark_paths, int *d_visit_lookup, float delta, const int *d_in,
+                     const unsigned *d_in_dist, int num_elements, const unsigned long long *d_num_elements, unsigned level, int tag,
+                     int near_capacity, int *d_near_v, int *d_near_row_start, int *d_near_scan, int far_capacity, int *d_far_v,
+                     unsigned *d_far_d, unsigned long long *near_tail, unsigned long long *far_tail, unsigned *far_min, int *overflow,
+                     int max_grid_size);
+
 /* DisplayStats' counters (reference tests/bfs/test_bfs.cu:184-196): visited vertices and the sum of their
  * out-degrees -- the numerator of MTEPS = edges_visited / (elapsed_ms * 1000) */
 void grx_bfs_count_visited(int nodes, const int *row_offsets, const int *labels,
