@@ -1222,6 +1222,8 @@ int grx_pbfs_frontier_bitmap(grx_pbfs *p, unsigned **d_bitmap, int *words)
     return 0;
 }
 
+// *found_edges is not part of the contract (the sweeps leave the edge half of their tail 0, bottom_up.hpp): callers use
+// *found alone and take the edge count from grx_pbfs_bitmap_to_queue when they return to top-down.
 int grx_pbfs_bottom_up(grx_pbfs *p, const unsigned *d_gathered, int words_per_rank, unsigned *found, unsigned *found_edges)
 {
     if (!p || !d_gathered || !found || !found_edges) return -1;

@@ -280,6 +280,10 @@ class HipEngine:
         return self._dg.as_tensor(ptr.value, words.value, device=self.device)
 
     def bottom_up(self, gathered, words_per_rank):
+        """One bottom-up level against the gathered frontier bitmaps.  Returns (found, edges): `found` is the number of
+        vertices discovered (the next local frontier's size).  The second value is NOT part of the contract -- the dense
+        sweep reports 0 -- and the level loops do not use it while a search stays bottom-up; bitmap_to_queue() recomputes the
+        edge count when the search returns to top-down."""
         gathered = gathered.contiguous()
         self._keep = gathered
         return self._pair(self.lib.grx_pbfs_bottom_up, C.c_void_p(gathered.data_ptr()), int(words_per_rank))
@@ -294,6 +298,12 @@ class HipEngine:
 
     def labels(self):
         return self.labels_tensor().cpu().numpy()
+
+    def preds(self):
+        """Local parents as GLOBAL ids (-1 source, -2 none recorded)."""
+        ptr = C.c_void_p()
+        self._check(self.lib.grx_pbfs_preds(self._h, C.byref(ptr)), "grx_pbfs_preds")
+        return self._dg.as_tensor(ptr.value, self.n_local, device=self.device).cpu().numpy()
 
     def close(self):
         if self._h:
@@ -388,7 +398,7 @@ class LibraryBfs:
         return int(levels.value), float(ms.value)
 
     def set_option(self, name, value):
-        """Named tuning knob of the level loop (grx_pbfs_set_option): "lite_factor", "alpha", "sparse_sweep_div"."""
+        """Named tuning knob of the level loop (grx_pbfs_set_option): "lite_factor", "alpha", "sparse_sweep_div", "walk_queue"."""
         HipEngine._check(self.lib.grx_pbfs_set_option(self._h, name.encode(), float(value)), "grx_pbfs_set_option(%s)" % name)
         return self
 
@@ -396,9 +406,7 @@ class LibraryBfs:
         return int(self.lib.grx_pbfs_stat(self._h, name.encode()))
 
     def preds(self):
-        ptr = C.c_void_p()
-        HipEngine._check(self.lib.grx_pbfs_preds(self._h, C.byref(ptr)), "grx_pbfs_preds")
-        return self.engine._dg.as_tensor(ptr.value, self.engine.n_local, device=self.engine.device).cpu().numpy()
+        return self.engine.preds()
 
 
 # ------------------------------------------------------------------------------------------------------------------

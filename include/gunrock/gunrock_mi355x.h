@@ -1738,7 +1738,10 @@ int grx_pbfs_filter_received(grx_pbfs *p, const int *d_recv, int n_recv, unsigne
 int grx_pbfs_queue_to_bitmap(grx_pbfs *p);
 /* the local frontier bitmap to all-gather: `words` 32-bit words, identical on every rank */
 int grx_pbfs_frontier_bitmap(grx_pbfs *p, unsigned **d_bitmap, int *words);
-/* bottom-up level over the owned unvisited vertices against the all-gathered bitmaps (parts x words_per_rank words) */
+/* bottom-up level over the owned unvisited vertices against the all-gathered bitmaps (parts x words_per_rank words; words
+ * of a rank's stretch behind its bitmap are never read as vertex bits).  *found = vertices discovered, the next local
+ * frontier's size.  *found_edges is NOT part of the contract: the dense sweep reports 0, a level loop needs no edge count
+ * while it stays bottom-up, and grx_pbfs_bitmap_to_queue recomputes it exactly on the way back to top-down. */
 int grx_pbfs_bottom_up(grx_pbfs *p, const unsigned *d_gathered, int words_per_rank, unsigned *found, unsigned *found_edges);
 /* local frontier bitmap -> local queue (leaving bottom-up) */
 int grx_pbfs_bitmap_to_queue(grx_pbfs *p, unsigned *len, unsigned *edges);

@@ -63,12 +63,10 @@ class NumpyEngine:
 
     def bottom_up(self, gathered, words_per_rank):
         bits = np.unpackbits(gathered.numpy().view(np.uint8), bitorder="little").astype(bool).reshape(self.parts, -1)
-        found = []
-        for v in np.nonzero(self.labels_ == -1)[0]:
-            nb = self.ci[self.ro[v]:self.ro[v + 1]]
-            if nb.size and bits[nb % self.parts, nb // self.parts].any():
-                found.append(v)
-        found = np.asarray(found, dtype=np.int64)
+        # every unvisited vertex with a neighbour in the gathered frontier (one pass over the entries, not one per vertex)
+        rows = np.repeat(np.arange(self.n_local, dtype=np.int64), np.diff(self.ro))
+        hit = bits[self.ci % self.parts, self.ci // self.parts] & (self.labels_[rows] == -1)
+        found = np.unique(rows[hit])
         self.labels_[found] = self.level + 1
         self.level += 1
         self.bitmap[:] = False
